@@ -2,8 +2,15 @@
 """bench.py — headline benchmark of the render-loop hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload sponza|s10m] [--scaling auto|weak|strong] [--mode parity|global|wide]
+                    [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): Msamples/s, whole job.
+
+A plain run does only what the headline needs: scene set-up, W warm-up steps, K timed steps, the outputs of the last timed step
+(--dump-outputs DIR: the image a caller of the timed path receives, DIR/rgb8_image.npy or DIR/linear_framebuffer.npy, float32),
+then ONE compact JSON line (metric, value, unit, ms_per_step, ...; the records below are null there). Everything else this file
+measures — the roofline record and its live PMC passes, config4, the production modes, cpu_baseline, extra_workloads — runs
+only with --full, after the headline, as described below.
 
 Workloads (the reference ships no Sponza asset, so both are the deterministic synthetic sets it names):
   sponza (default, BASELINE config 3/4): "S-sponza" = 262 144 random triangles in a closed 40x16x20 room + 12 wall
@@ -12,7 +19,7 @@ Workloads (the reference ships no Sponza asset, so both are the de
   s10m   (BASELINE config 5): "S-10M" = the same recipe with 10^7 triangles (vertex offsets +-0.03), 2048x2048,
          32 SPP per GPU (256 SPP on 8 GPUs). Working set (nodes 0.64 GB + triangles 0.48 GB + attributes 1.28 GB) is far
          beyond the 256 MiB Infinity Cache: the configuration where HBM traffic / time / 8 TB/s is a real fraction.
-With no --workload the line describes S-sponza (config 3) and, on one GPU, carries config 5 as well: `extra_workloads.s10m`
+With no --workload the line describes S-sponza (config 3) and, with --full on one GPU, carries config 5 as well: `extra_workloads.s10m`
 is the same measurement on S-10M taken in the same invocation (its CPU leg is skipped: the oracle's 10^7-triangle BVH build
 alone takes longer than the whole bench should).
 
@@ -22,7 +29,7 @@ HBM (RT_FLAG_DEVICE_FB) + for N > 1 the RCCL gather of the rgb8 image to rank 0.
 before the timed region, like the reference's RaytracerStaticContext (raytracer.h:633) precedes its pixel loop.
 
 Traversal modes (--mode; the headline is ALWAYS parity unless --mode says otherwise, the others are reported beside it under
-"production" on one GPU):
+"production" on one GPU with --full):
   parity  the reference's tree and traversal order (bvh.h:195-235, near-local pruning): hits, event counters and image are the
           oracle's bit for bit. The headline.
   global  same tree, every box culled against the global best hit (RT_FLAG_GLOBAL_BEST).
@@ -34,10 +41,10 @@ N > 1, two ways to launch, same sharding (interleaved 8-row tiles, block b -> GP
     multi-GPU scene (rt_create_on: a replica per GPU + ncclCommInitAll, csrc/rt_group.cpp) renders and gathers.
 Either way the line says n_gpus = N only if N GPUs really took part; fewer visible devices or a rank-count mismatch exit non-zero.
 --scaling weak (default, = auto): SPP = 64 x N (per-GPU work fixed), at every N: the driver's 1 -> 8 curve is one regime. --scaling strong:
-BASELINE config 4 exactly, 1000x1000 at 1000 SPP in all, as the headline. Whatever the headline, a sponza run also carries `config4`: one
+BASELINE config 4 exactly, 1000x1000 at 1000 SPP in all, as the headline. Whatever the headline, a sponza run with --full also carries `config4`: one
 timed step of config 4 (1000 SPP in all over the N GPUs taking part) measured after the headline, so a strong-scaling curve exists beside it.
 
-The "roofline" object (dominant kernel: the closest-hit kernel, wf_extend / wf_extend_packet / wf_extend_wide):
+The "roofline" object (--full; dominant kernel: the closest-hit kernel, wf_extend / wf_extend_packet / wf_extend_wide):
   achieved / frac / traffic   HBM-SIDE bytes per launch (rocprofv3 PMC passes kept under profiles/, FETCH_SIZE doubled + WRITE_SIZE
                        as MI355X_MICROARCH.md prescribes for gfx950, stamped with the hash of the device sources they were measured
                        on and used only while that hash matches this run's sources) / the live HIP-event launch duration,
@@ -51,7 +58,7 @@ The "roofline" object (dominant kernel: the closest-hit kernel, wf_extend / wf_e
   binding_roof         the roof that actually binds the kernel in the committed counter profile (vector-L1 access rate, or the
                        HBM request rate for random gathers), its fraction and source.
   request_frac, l1_frac, limiter, pmc   as measured in the same committed profile.
-"cpu_baseline": the CPU oracle (port of the reference algorithm, byte-identical to the reference binary on the
+"cpu_baseline" (--full): the CPU oracle (port of the reference algorithm, byte-identical to the reference binary on the
 fixtures; profiles/r03_cpu_baseline_crosscheck.json times both) on this box's host cores on a bounded sample; rank 0, N = 1 only.
 """
 import argparse
@@ -71,6 +78,7 @@ SEED = 0x5EED5EED
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 PROFILE_ROUND = "r04"
 CONFIG4_SPP = 1000
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files of one run together stay below this
 
 WORKLOADS = {
     "sponza": dict(label="S-sponza", width=1000, height=1000, spp_per_gpu=64, triangles=262144, offset=0.15, tex_size=1024, cpu_share=4,
@@ -272,6 +280,24 @@ def resolve_spp(scaling: str, gpus: int, wl: dict, explicit_spp: int):
     return wl["spp_per_gpu"] * gpus, "weak"
 
 
+def dump_image(out_dir: str, name: str, flat, W: int, H: int):
+    """--dump-outputs: the image of the last timed step as out_dir/<name>.npy, float32 of shape (H, W, 3). An image larger than
+    DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its pixels: <name>.npy of shape (k, 3) and their row-major pixel indices
+    in <name>_pixels.npy (float64, exact). Returns the names of the files written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.asarray(flat, dtype=np.float32).reshape(H * W, 3)
+    if img.nbytes + 4096 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, name + ".npy"), img.reshape(H, W, 3))
+        return [name + ".npy"]
+    k = (DUMP_LIMIT_BYTES - 8192) // (img.itemsize * 3 + 8)
+    idx = np.sort(np.random.default_rng(SEED).choice(H * W, size=k, replace=False))
+    np.save(os.path.join(out_dir, name + ".npy"), img[idx])
+    np.save(os.path.join(out_dir, name + "_pixels.npy"), idx.astype(np.float64))
+    return [name + ".npy", name + "_pixels.npy"]
+
+
 def make_scene(rt, wl, n_tri, tex_size, aspect):
     return rt.scenegen.room_scene(n_tri, seed=SEED, tex_size=tex_size, n_tex_sets=16, n_materials=64, n_lights=16,
                                   light_strength=20.0, alpha_fraction=0.02, offset=wl["offset"],
@@ -317,8 +343,9 @@ class Runner:
             _, st = self.dev.run_raytracer_rgb8(self.W, self.H, self.spp, seed=SEED, device_rgb8=self.img.data_ptr(), global_best=self.m["gbest"], **self.shard_kw())
         else:
             _, st = self.dev.run_raytracer(self.W, self.H, self.spp, seed=SEED, device_fb=self.fb.data_ptr(), global_best=self.m["gbest"], **self.shard_kw())
-        # torchrun, N > 1: RCCL gather of this rank's interleaved blocks to rank 0 over xGMI (no-op at N = 1; inside the library for "group")
-        self.gather.gather(self.img if self.backend == "nccl" else self.img.cpu())
+        # torchrun, N > 1: RCCL gather of this rank's interleaved blocks to rank 0 over xGMI (no-op at N = 1; inside the library for "group").
+        # `output`: the whole image on rank 0 (None on the other ranks), what a caller of this path receives
+        self.output = self.gather.gather(self.img if self.backend == "nccl" else self.img.cpu())
         return st
 
     def sync(self):
@@ -524,13 +551,16 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS), help="default: sponza, with S-10M as extra_workloads.s10m on one GPU")
+    ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS), help="default: sponza, with S-10M as extra_workloads.s10m on one GPU with --full")
     ap.add_argument("--scaling", default="auto", choices=["auto", "weak", "strong"], help="weak (= auto): 64 SPP per GPU at every N; strong = BASELINE config 4 (1000 SPP in all) as the headline")
-    ap.add_argument("--live-pmc", default="auto", choices=["auto", "off"], help="auto: on one GPU, at a workload's full size, measure the headline kernel's HBM traffic and SQ "
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else this file reports: roofline (with the live PMC passes), config4, "
+                    "production modes, cpu_baseline, extra_workloads; a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the image of the last timed step (what a caller of the timed path receives) as DIR/<name>.npy, float32")
+    ap.add_argument("--live-pmc", default="auto", choices=["auto", "off"], help="--full only. auto: on one GPU, at a workload's full size, measure the headline kernel's HBM traffic and SQ "
                     "figures with child rocprofv3 passes of this command after the timed steps (about a minute); off: quote the committed, hash-checked profiles only")
-    ap.add_argument("--no-config4", action="store_true", help="skip the extra config-4 record (one 1000-SPP step after the headline)")
+    ap.add_argument("--no-config4", action="store_true", help="--full only: skip the extra config-4 record (one 1000-SPP step after the headline)")
     ap.add_argument("--gather", default="gather", choices=["gather", "allgather"], help="torchrun flow: dist.gather to rank 0, or all_gather_into_tensor")
-    ap.add_argument("--mode", default="parity", choices=sorted(MODES), help="traversal mode of the HEADLINE value (default parity; the others are reported under 'production')")
+    ap.add_argument("--mode", default="parity", choices=sorted(MODES), help="traversal mode of the HEADLINE value (default parity; with --full the others are reported under 'production')")
     ap.add_argument("--bvh", default="reference", choices=["reference", "device"],
                     help="binary builder: reference = host build in the reference's exact topology (the parity tree); device = built on the GPU (rt_bvh_device.hip: PLOC, or the radix-tree LBVH with RT_DEVICE_BUILDER=lbvh). "
                          "--mode wide collapses whichever is chosen")
@@ -539,12 +569,14 @@ def main() -> None:
     ap.add_argument("--spp", type=int, default=0, help="samples per pixel of the whole job (default: by --scaling)")
     ap.add_argument("--triangles", type=int, default=0)
     ap.add_argument("--tex-size", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline: no production-mode records, no extra workload")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full only: skip the cpu_baseline record")
+    ap.add_argument("--no-extras", action="store_true", help="--full only: no production-mode records, no extra workload")
     ap.add_argument("--film", default="device", choices=["device", "none"], help="device: rt_render_rgb8 (film on the GPU, rgb8 gathered); none: rt_render (float3 gathered)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal of the torchrun flow on fewer GPUs (all ranks on GPU 0, gather staged through host)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     wl_name = args.workload or "sponza"
     wl = WORKLOADS[wl_name]
 
@@ -587,18 +619,23 @@ def main() -> None:
     if launcher == "group" and run.ranks_formed != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but the library formed {run.ranks_formed} rank(s)")
     value = run.timed(args.steps, args.warmup)
-    live = None
-    if args.live_pmc == "auto" and args.gpus == 1 and rank == 0 and full_size is True and not os.environ.get("RT_AMD_LIB"):
-        child = ["--workload", wl_name, "--mode", args.mode, "--bvh", args.bvh, "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-config4", "--live-pmc", "off", "--film", args.film]
-        live = live_pmc(child, args.mode)
-    roofline = run.roofline(live)
-    roofline["packet"] = run.packet_record()
     elapsed = run.elapsed
+    if args.dump_outputs and rank == 0:
+        dump_image(args.dump_outputs, "rgb8_image" if film else "linear_framebuffer", run.output.cpu().numpy(), W, H)
+    live = None
+    if args.full and args.live_pmc == "auto" and args.gpus == 1 and rank == 0 and full_size is True and not os.environ.get("RT_AMD_LIB"):
+        # the children time the headline only: a plain run of the same workload and mode
+        child = ["--workload", wl_name, "--mode", args.mode, "--bvh", args.bvh, "--steps", "1", "--warmup", "1", "--film", args.film]
+        live = live_pmc(child, args.mode)
+    roofline = None
+    if args.full:
+        roofline = run.roofline(live)
+        roofline["packet"] = run.packet_record()
     single = args.gpus == 1 and rank == 0
-    extras = single and not args.no_extras
+    extras = args.full and single and not args.no_extras
     parity_fb = run.float_image() if (extras and args.mode == "parity") else None
     config4 = None
-    if wl_name == "sponza" and full_geometry and scaling != "strong" and not args.no_config4 and args.mode == "parity":
+    if args.full and wl_name == "sponza" and full_geometry and scaling != "strong" and not args.no_config4 and args.mode == "parity":
         # BASELINE config 4 beside the weak-scaling headline: 1000 SPP in all over the GPUs taking part, one timed step (10^9 samples)
         keep = (run.spp, run.elapsed, run.steps, run.kernel_ms, run.dom_ms, run.dom_launches, run.last_stats)
         run.spp = max(1, min(CONFIG4_SPP, (128 << 20) // max(1, run.my_pixels)))  # untimed: one sample pass of config 4's size grows the path workspace to it
@@ -641,7 +678,7 @@ def main() -> None:
         del parity_fb
 
     cpu_baseline = None
-    if single and not args.no_cpu_baseline:
+    if args.full and single and not args.no_cpu_baseline:
         cpu_baseline = cpu_baseline_leg(rt, scene, wl, W, H, args.cpu_seconds)
 
     extra_workloads = None
@@ -703,6 +740,7 @@ def main() -> None:
                 "traversal": MODES[args.mode]["text"],
                 "bvh": "reference topology, host build" if args.bvh == "reference" else "built on the device (PLOC; identical closest hits, different topology and counters)",
             },
+            "full": args.full,  # false: the records below were not measured (bench.py --full measures them)
             "roofline": roofline,
             "config4": config4,
             "cpu_baseline": cpu_baseline,

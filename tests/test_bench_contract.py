@@ -1,18 +1,19 @@
-"""bench.py keeps the driver's contract: ONE JSON line with the agreed keys, the roofline and cpu_baseline objects."""
+"""bench.py keeps the driver's contract: ONE JSON line with the agreed keys; with --full also the roofline and cpu_baseline objects."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TINY = ["--width", "96", "--height", "64", "--spp", "4", "--triangles", "3000", "--tex-size", "16"]
 
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--width", "96", "--height", "64", "--spp", "4",
-           "--triangles", "3000", "--tex-size", "16", "--cpu-seconds", "0.5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "1", "--warmup", "1", *TINY, "--cpu-seconds", "0.5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -58,6 +59,58 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb, k
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0
+    assert j["full"] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_image_of_its_last_step(gpu, tmp_path):
+    """Without --full the line carries the headline only (the other records are null), --steps sets the timed steps, and
+    --dump-outputs writes the rgb8 image of the last timed step: the same bytes as the same render through the library directly."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", *TINY, "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "data", "config", "setup_s"):
+        assert k in j, k
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["full"] is False and j["unit"] == "Msamples/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert j["value"] > 0 and abs(j["value"] - 96 * 64 * 4 / (j["ms_per_step"] * 1e3)) / j["value"] < 0.02
+    for k in ("roofline", "config4", "cpu_baseline", "production", "extra_workloads"):
+        assert j[k] is None, k
+    assert sorted(os.listdir(out)) == ["rgb8_image.npy"]
+    img = np.load(out / "rgb8_image.npy")
+    assert img.dtype == np.float32 and img.shape == (64, 96, 3)
+    sc = bench.make_scene(gpu, bench.WORKLOADS["sponza"], 3000, 16, 96 / 64)
+    dev = gpu.DeviceScene(sc, device=0)
+    ref, _ = dev.run_raytracer_rgb8(96, 64, 4, seed=bench.SEED)
+    dev.close()
+    assert np.array_equal(img, ref.astype(np.float32))
+
+
+def test_dump_image_writes_float32_and_samples_what_is_too_large(tmp_path):
+    """bench.dump_image (--dump-outputs): float32 (H, W, 3) when it fits the size limit; otherwise a fixed, seeded sample of pixels with
+    their indices, the files together within the limit. CPU-only."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = np.arange(4 * 5 * 3, dtype=np.uint8)
+    assert bench.dump_image(str(tmp_path / "a"), "img", small, 5, 4) == ["img.npy"]
+    a = np.load(tmp_path / "a" / "img.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 5, 3) and np.array_equal(a.reshape(-1), small.astype(np.float32))
+    W, H = 2400, 2400  # 69 MB as float32
+    big = np.random.default_rng(1).integers(0, 256, size=W * H * 3, dtype=np.uint8)
+    for d in ("b", "c"):
+        assert bench.dump_image(str(tmp_path / d), "img", big, W, H) == ["img.npy", "img_pixels.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in ("img.npy", "img_pixels.npy")) <= bench.DUMP_LIMIT_BYTES
+    px, idx = np.load(tmp_path / "b" / "img.npy"), np.load(tmp_path / "b" / "img_pixels.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and px.shape == (idx.size, 3) and idx.size > W * H // 2
+    assert np.array_equal(px, big.reshape(-1, 3)[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(px, np.load(tmp_path / "c" / "img.npy")) and np.array_equal(idx, np.load(tmp_path / "c" / "img_pixels.npy"))
 
 
 def test_committed_profiles_are_stamped_and_stale_ones_are_never_quoted():

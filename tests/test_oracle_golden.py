@@ -4,6 +4,7 @@ UNMODIFIED reference (tests/golden/make_golden.py). CPU only.
 Parity chain, hop 1: oracle in reference-RNG mode + libm sin/cos == the reference binary, byte for
 byte in the PPM, bit for bit in BVH nodes, closest hits (prim, b, c, t) and light pdf values.
 """
+import hashlib
 import os
 
 import numpy as np
@@ -12,6 +13,7 @@ import pytest
 from conftest import golden_scene_specs, make_scene
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+LIVE = os.path.join(GOLD, "live")  # the reference's answers for the "live" tests below (make_live_golden.py)
 GENERATED = list(golden_scene_specs().keys())
 # "features": hand-built glTF committed under tests/golden/features/ (scene selection, matrix + TRS nodes, strips,
 # u8/u16/u32 indices, missing attributes, lower-case `tangent`, emissive texture + strength, ...; make_features_gltf.py)
@@ -157,32 +159,38 @@ def test_parallel_subtree_build_is_bit_identical(rt, sg, oracle, monkeypatch):
     assert (leaves[:, 9] - leaves[:, 8]).sum() == sc.n_triangles
 
 
+def reference_ppm(oracle, gltf, w, h, spp, tmp_path, name):
+    """The reference binary's PPM of a scene, stored as tests/golden/live/<name> (make_live_golden.py); where oracle/_ref exists the
+    binary runs live as well and must reproduce the stored bytes."""
+    stored = oracle.read_ppm(os.path.join(LIVE, name))
+    if oracle.have_reference_build():
+        assert np.array_equal(oracle.run_reference(gltf, w, h, spp, str(tmp_path / "ref.ppm")), stored), name
+    return stored
+
+
 def test_live_reference_bvh_dump_at_100k_if_present(oracle, rt, sg, tmp_path):
     """The reference's own BVH::build (through oracle/_ref/ref_probe) on 100 000 triangles against the oracle's parallel
-    build and the product's host builder: nodes and object order bit for bit. Container only (needs oracle/_ref)."""
-    if not oracle.have_reference_build():
-        pytest.skip("oracle/_ref not built (GPU box): covered by the committed fixtures")
+    build and the product's host builder: nodes and object order bit for bit. The reference's dump is stored as its sha256
+    (tests/golden/live/bvh_room100k.sha256); where oracle/_ref exists the dump is also made live and checked against it."""
     sc = sg.room_scene(100000, seed=99, n_lights=20, n_materials=4, tex_size=0, offset=0.05)
     path = sg.write_gltf(sc, str(tmp_path / "big.gltf"))
-    oracle.ref_probe("bvh", path, 64, 48, str(tmp_path / "bvh.bin"))
-    words = np.fromfile(str(tmp_path / "bvh.bin"), dtype=np.uint32)
+    stored = open(os.path.join(LIVE, "bvh_room100k.sha256")).read().split()[0]
+    if oracle.have_reference_build():
+        oracle.ref_probe("bvh", path, 64, 48, str(tmp_path / "bvh.bin"))
+        assert hashlib.sha256(np.fromfile(str(tmp_path / "bvh.bin"), dtype=np.uint32).tobytes()).hexdigest() == stored
     ls = rt.parse_gltf_scene(path, 64 / 48)
     orc = oracle.OracleScene(ls)
     a = ls.arrays()
     lights = np.array([i for i, m in enumerate(a["material_ids"]) if np.any(a["materials"][int(m)]["emission"] != 0)], dtype=np.uint32)
-    p = 0
+    words = []  # the oracle's trees in the layout of the reference's dump: node count, object count, root, nodes, object order
     for which, sub in ((0, None), (1, lights)):
-        nn, no, root = (int(x) for x in words[p : p + 3])
-        p += 3
-        nodes = words[p : p + 10 * nn].reshape(nn, 10)
-        p += 10 * nn
-        order = words[p : p + no]
-        p += no
         ob = orc.bvh_info(which)
         pb = rt.bvh_build_host(a["positions"], sub)
-        assert ob["root"] == root == pb["root"]
-        assert np.array_equal(ob["nodes"], nodes) and np.array_equal(ob["order"], order), which
-        assert np.array_equal(pb["nodes"], nodes) and np.array_equal(pb["order"], order), which
+        nn, no = len(ob["nodes"]), len(ob["order"])
+        assert ob["root"] == pb["root"]
+        assert np.array_equal(pb["nodes"], ob["nodes"]) and np.array_equal(pb["order"], ob["order"]), which
+        words += [np.array([nn, no, ob["root"]], dtype=np.uint32), np.asarray(ob["nodes"], dtype=np.uint32).reshape(-1), np.asarray(ob["order"], dtype=np.uint32)]
+    assert hashlib.sha256(np.concatenate(words).tobytes()).hexdigest() == stored
     assert nn > 1  # 20 lights: a light BVH with inner nodes
 
 
@@ -201,12 +209,11 @@ def test_oracle_sharding_union(oracles, rt):
 
 
 def test_live_reference_binary_if_present(oracle, rt, sg, tmp_path):
-    """Where oracle/_ref exists (this container), run the reference binary on a fresh scene that is NOT a fixture."""
-    if not oracle.have_reference_build():
-        pytest.skip("oracle/_ref not built (GPU box): covered by the committed fixtures")
+    """The reference binary on a scene outside the golden_scene_specs set, at another image shape: its PPM is stored
+    (tests/golden/live/), and where oracle/_ref exists the binary runs live too."""
     sc = sg.room_scene(900, seed=777, n_lights=5, n_materials=7, tex_size=8, n_tex_sets=3, alpha_fraction=0.3, smooth_normals=True)
     path = sg.write_gltf(sc, str(tmp_path / "live.gltf"))
-    ref = oracle.run_reference(path, 40, 56, 3, str(tmp_path / "ref.ppm"))
+    ref = reference_ppm(oracle, path, 40, 56, 3, tmp_path, "room900_40x56x3.ppm")
     ls = rt.parse_gltf_scene(path, 40 / 56)
     orc = oracle.OracleScene(ls)
     fb, _ = orc.run_raytracer(40, 56, 3, rng_mode=rt.RT_RNG_REFERENCE)
@@ -215,12 +222,10 @@ def test_live_reference_binary_if_present(oracle, rt, sg, tmp_path):
 
 def test_live_reference_binary_on_a_deep_tree_if_present(oracle, rt, sg, tmp_path):
     """Same as above at 30 000 triangles (a BVH ~20 levels deep, textured, dense overlaps): the oracle's PPM must still be
-    byte-identical to the reference binary's. Container only (needs oracle/_ref)."""
-    if not oracle.have_reference_build():
-        pytest.skip("oracle/_ref not built (GPU box): covered by the committed fixtures")
+    byte-identical to the reference binary's (stored under tests/golden/live/; live as well where oracle/_ref exists)."""
     sc = sg.room_scene(30000, seed=4711, n_lights=6, n_materials=12, tex_size=16, n_tex_sets=4, alpha_fraction=0.1, offset=0.4)
     path = sg.write_gltf(sc, str(tmp_path / "deep.gltf"))
-    ref = oracle.run_reference(path, 96, 64, 2, str(tmp_path / "ref.ppm"))
+    ref = reference_ppm(oracle, path, 96, 64, 2, tmp_path, "room30000_96x64x2.ppm")
     ls = rt.parse_gltf_scene(path, 96 / 64)
     fb, _ = oracle.OracleScene(ls).run_raytracer(96, 64, 2, rng_mode=rt.RT_RNG_REFERENCE)
     assert np.array_equal(oracle.tonemap(fb), ref)

@@ -15,6 +15,7 @@ import pytest
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TXT = os.path.join(GOLD, "txt")
+SAMPLE_DATA = os.path.join(GOLD, "sample_data")  # the reference's sample_data/ scene files (data fixtures)
 W, H, SPP = 64, 48, 4
 
 
@@ -214,11 +215,9 @@ def test_config2_fixture_is_the_reference_file_and_renders(rt, oracle):
 
 
 def test_reference_sample_data_parses_if_present(rt, oracle):
-    """Every scene file the reference ships under sample_data/ (BASELINE config 1 names scene-000.txt) goes through the
-    loader and renders on the CPU oracle. Container only: /root/reference does not exist on the GPU box."""
-    files = sorted(glob.glob("/root/reference/sample_data/*.txt") + glob.glob("/root/reference/sample_data/homebrew_primitives/*.txt"))
-    if not files:
-        pytest.skip("/root/reference/sample_data absent")
+    """Every scene file the reference ships under sample_data/ (BASELINE config 1 names scene-000.txt; a data fixture:
+    tests/golden/sample_data/, the reference's files byte for byte) goes through the loader and renders on the CPU oracle."""
+    files = sorted(glob.glob(os.path.join(SAMPLE_DATA, "*.txt")) + glob.glob(os.path.join(SAMPLE_DATA, "homebrew_primitives", "*.txt")))
     assert len(files) == 13
     for f in files:
         ls = rt.parse_scene_txt(f)

@@ -14,7 +14,7 @@ line() { python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); p=j['roofline']['pipeline']
 print('$1', j['value'], 'Msamples/s  closest-hit launch', j['roofline']['avg_launch_ms'], 'ms  visits/cast', p['nodes_per_cast'], ' triangle tests/cast', p['tri_tests_per_cast'], ' rt_create', j['setup_s']['rt_create_bvh_upload'], 's')"; }
-B="python bench.py --no-extras --no-cpu-baseline"
+B="python bench.py --full --no-extras --no-cpu-baseline"
 case "$1" in
 modes)
   for wl in sponza s10m; do for cfg in "--mode parity" "--mode global" "--mode wide" "--mode parity --bvh device" "--mode global --bvh device" "--mode wide --bvh device"; do

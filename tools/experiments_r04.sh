@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # tools/experiments_r04.sh <name> — the A/B measurements behind profiles/r04_variants.txt (on the GPU box; variants built by tools/variants*.sh)
 V=raytracing-course-hw-public_amd/csrc/variants
-B="python bench.py --no-extras --no-cpu-baseline --no-config4"
+B="python bench.py --full --no-extras --no-cpu-baseline --no-config4"
 line() { python -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']; print('$1', j['value'], 'Msamples/s; closest-hit launch', r['avg_launch_ms'], 'ms; nodes/cast', r['pipeline']['nodes_per_cast'], 'packet', r['packet']['packet_passes'], '/', r['packet']['passes'], r['packet']['lanes_served_per_trip'])"; }
 case "$1" in
   occupancy)  # wf_extend_wide at 4 / 5 (shipped) / 6 waves per SIMD; refill threshold 8 / 16 (shipped) / 24 / 32

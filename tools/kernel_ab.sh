@@ -5,7 +5,7 @@ set -e
 tag=$1; mode=$2; wl=$3; lib=$4
 R="$(cd "$(dirname "$0")/.." && pwd)"; O=$R/gpurun_out
 [ -n "$lib" ] && export RT_AMD_LIB=$R/raytracing-course-hw-public_amd/csrc/variants/$lib.so
-extra="--workload $wl --mode $mode --no-extras --no-cpu-baseline --no-config4 --live-pmc off --steps 2 --warmup 1"
+extra="--full --workload $wl --mode $mode --no-extras --no-cpu-baseline --no-config4 --live-pmc off --steps 2 --warmup 1"
 [ "$mode" = wide ] && extra="$extra --bvh device"
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/kab_$tag
