@@ -167,13 +167,17 @@ typedef struct rt_scene_desc {
  *       permutation) -> event counters and tie-breaking equal the reference's: the parity mode.
  *   RT_BUILD_DEVICE_LBVH: on the GPU (Morton sort + Karras radix tree + refit, csrc/rt_bvh_device.hip), tens of milliseconds
  *       for 10^7 triangles instead of seconds. Same closest hits (identical t), but a different topology: ties between
- *       equal-t triangles may resolve differently and the counters differ. Production mode for big scenes; also selected by
+ *       equal-t triangles may resolve differently and the counters differ. One exception ("Two kinds of modes"): where
+ *       coplanar triangles OVERLAP, two candidate hits lie within an ulp of each other and the reference's pruning rule lets the
+ *       tree shape pick one, so such a ray may get the other triangle's hit, <= 4 ulp closer or farther, still a true hit of the
+ *       triangle it names. Production mode for big scenes; also selected by
  *       the CLI's RT_BVH_DEVICE=1. The light BVH (emissive triangles only) is always built on the host.
  *   RT_BUILD_WIDE (may be combined with either binary builder): the binary tree is collapsed into an 8-wide tree whose nodes
  *       hold eight child boxes quantised conservatively to 8 bits per plane (80 B per node), chosen by a surface-area
  *       dynamic program; the wavefront pipeline then walks THAT tree with global-best culling and octant-ordered slots
- *       (csrc/wide_build.cpp, csrc/rt_wide.hip). Production mode: the closest hit is the reference's (t bit for bit; another
- *       index only on exact ties) with far fewer memory accesses per ray; event counters count wide nodes. The megakernel /
+ *       (csrc/wide_build.cpp, csrc/rt_wide.hip). Production mode: the closest hit over all triangles (t bit for bit the brute-force
+ *       minimum: the reference's, or closer where the reference's own pruning skips a triangle; another index only on exact ties)
+ *       with far fewer memory accesses per ray; event counters count wide nodes. The megakernel /
  *       reference-RNG parity renders are refused on such a scene (RT_ERR_UNSUPPORTED). The CLI sets it for RT_BVH_WIDE=1.
  *   RT_BUILD_WIDE_HOST_COLLAPSE (development; with RT_BUILD_DEVICE_LBVH | RT_BUILD_WIDE): read the device-built binary tree back and
  *       collapse it on the host (wide_build.cpp) instead of on the device — the cross-check of the device collapse.

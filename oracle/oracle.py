@@ -32,6 +32,8 @@ _PROTOS = {
     "rto_destroy": (None, [C.c_void_p]),
     "rto_render": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), _abi.c_float_p, C.POINTER(_abi.RtStats), C.c_int]),
     "rto_cast_rays": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_float_p]),
+    "rto_intersect_objects": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_u32_p, _abi.c_float_p]),
+    "rto_cast_rays_brute": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_float_p, C.c_int]),
     "rto_trace_pixel": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), C.c_uint32, C.c_uint32, _abi.c_float_p, _abi.c_u32_p, _abi.c_u32_p]),
     "rto_light_pdf": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_bg_at": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
@@ -111,6 +113,30 @@ class OracleScene:
         prim = np.zeros(n, dtype=np.uint32)
         bct = np.zeros((n, 3), dtype=np.float32)
         _check(lib().rto_cast_rays(self._h, _abi.fptr(rays), n, _abi.u32ptr(prim), _abi.fptr(bct)))
+        return prim, bct
+
+    def intersect_objects(self, rays, objs):
+        """Ray i against object objs[i] only (a triangle through the BVH walk's own test, an index >= n_triangles as an analytic primitive,
+        reported (0, 0, t)): (hit flags (n,) bool, bct (n, 3) float32, zero where not hit)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        objs = np.ascontiguousarray(objs, dtype=np.uint32).reshape(-1)
+        n = rays.shape[0]
+        assert objs.shape[0] == n
+        hit = np.zeros(n, dtype=np.uint32)
+        bct = np.zeros((n, 3), dtype=np.float32)
+        _check(lib().rto_intersect_objects(self._h, _abi.fptr(rays), n, _abi.u32ptr(objs), _abi.u32ptr(hit), _abi.fptr(bct)))
+        return hit != 0, bct
+
+    def cast_rays_brute(self, rays, threads=None):
+        """The closest hit over ALL objects without a tree (update_intersection's rule: strictly smaller t wins, the first index on equal t;
+        primitives as in cast_rays): (prim, bct) like cast_rays. `threads`: worker count, by default min(16, OMP_NUM_THREADS or 16)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        if threads is None:
+            threads = min(16, int(os.environ.get("OMP_NUM_THREADS") or 16))
+        prim = np.zeros(n, dtype=np.uint32)
+        bct = np.zeros((n, 3), dtype=np.float32)
+        _check(lib().rto_cast_rays_brute(self._h, _abi.fptr(rays), n, _abi.u32ptr(prim), _abi.fptr(bct), max(1, int(threads))))
         return prim, bct
 
     def trace_pixel(self, width, height, samples, pixel, seed=0):

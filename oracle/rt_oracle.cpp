@@ -1026,6 +1026,99 @@ int rto_cast_rays(rto_scene *s, const float *rays, uint32_t n, uint32_t *prim_ou
     return RT_OK;
 }
 
+// Checker aid: ray i against object objs[i] ONLY. Triangles (index < n_triangles) through the same intersect_tri(..., EPS, ...) the BVH walk
+// calls; indices n_triangles + k through rt_prim_intersect, reported as (0, 0, t) like rto_cast_rays. hit_out[i] = 1 where the object is hit
+// (bct_out then holds its (b, c, t)), 0 elsewhere (bct_out zero), also for an index that names no object. A production hit that differs from the oracle's must be reproduced here bit
+// for bit by the object it names: that is what makes a tie, or a closer hit, a real hit.
+int rto_intersect_objects(rto_scene *s, const float *rays, uint32_t n, const uint32_t *objs, uint32_t *hit_out, float *bct_out) {
+    if (!s || (n && (!rays || !objs || !hit_out || !bct_out))) {
+        g_err = "rto_intersect_objects: bad arguments";
+        return RT_ERR_INVALID_ARG;
+    }
+    const size_t n_tri = s->objects.size(), n_obj = n_tri + s->prims.size();
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *o = &rays[6 * i], *d = &rays[6 * i + 3];
+        float *out = &bct_out[3 * i];
+        out[0] = out[1] = out[2] = 0.0f;
+        hit_out[i] = 0;
+        if ((size_t)objs[i] >= n_obj)
+            continue; // no such object (RT_NONE included): not a hit
+        if (objs[i] < n_tri) {
+            Ray r{{o[0], o[1], o[2]}, {d[0], d[1], d[2]}};
+            V3 xs;
+            if (intersect_tri(r, s->objects[objs[i]].shape, EPS, xs)) {
+                hit_out[i] = 1;
+                out[0] = xs.x, out[1] = xs.y, out[2] = xs.z;
+            }
+        } else {
+            float t, nn[3];
+            if (rt_prim_intersect(&s->prims[objs[i] - n_tri], o, d, EPS, &t, nn)) {
+                hit_out[i] = 1;
+                out[2] = t;
+            }
+        }
+    }
+    return RT_OK;
+}
+
+// Checker aid: the closest hit over ALL objects, no tree: every triangle in index order with update_intersection's rule (a strictly smaller t
+// replaces; on equal t the first index stays), then the analytic primitives exactly as rto_cast_rays adds them. The lower bound no traversal can
+// beat. `threads` workers (>= 1) split the TRIANGLES into consecutive ranges and sweep them in cache-sized blocks against all rays (one pass
+// over the scene per call, not per ray); the per-range winners are merged in range order with the same rule, which keeps the first index.
+int rto_cast_rays_brute(rto_scene *s, const float *rays, uint32_t n, uint32_t *prim_out, float *bct_out, int threads) {
+    if (!s || (n && (!rays || !prim_out || !bct_out)) || threads < 1) {
+        g_err = "rto_cast_rays_brute: bad arguments";
+        return RT_ERR_INVALID_ARG;
+    }
+    const uint32_t n_tri = (uint32_t)s->objects.size();
+    const uint32_t n_ranges = std::max(1u, std::min((uint32_t)threads, n_tri));
+    std::vector<Ray> rs(n);
+    for (uint32_t i = 0; i < n; ++i)
+        rs[i] = Ray{{rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]}, {rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]}};
+    std::vector<Hit> best((size_t)n_ranges * n);
+    auto sweep = [&](uint32_t r) {
+        const uint32_t begin = (uint32_t)((uint64_t)n_tri * r / n_ranges), end = (uint32_t)((uint64_t)n_tri * (r + 1) / n_ranges);
+        Hit *mine = &best[(size_t)r * n];
+        constexpr uint32_t BLOCK = 512;
+        for (uint32_t k0 = begin; k0 < end; k0 += BLOCK) {
+            const uint32_t k1 = std::min(k0 + BLOCK, end);
+            for (uint32_t i = 0; i < n; ++i)
+                for (uint32_t k = k0; k < k1; ++k) {
+                    Hit h;
+                    if (intersect_tri(rs[i], s->objects[k].shape, EPS, h.xs)) {
+                        h.has = true;
+                        h.obj = k;
+                    }
+                    update_intersection(mine[i], h);
+                }
+        }
+    };
+    std::vector<std::thread> workers;
+    for (uint32_t r = 1; r < n_ranges; ++r)
+        workers.emplace_back(sweep, r);
+    sweep(0);
+    for (auto &t : workers)
+        t.join();
+    for (uint32_t i = 0; i < n; ++i) {
+        Hit h;
+        for (uint32_t r = 0; r < n_ranges; ++r)
+            update_intersection(h, best[(size_t)r * n + i]);
+        prim_out[i] = h.has ? h.obj : NO_CHILD;
+        bct_out[3 * i + 0] = h.has ? h.xs.x : 0.0f;
+        bct_out[3 * i + 1] = h.has ? h.xs.y : 0.0f;
+        bct_out[3 * i + 2] = h.has ? h.xs.z : 0.0f;
+        for (size_t k = 0; k < s->prims.size(); ++k) {
+            float t, nn[3];
+            if (rt_prim_intersect(&s->prims[k], &rays[6 * i], &rays[6 * i + 3], EPS, &t, nn) && (prim_out[i] == NO_CHILD || bct_out[3 * i + 2] > t)) {
+                prim_out[i] = (uint32_t)(s->objects.size() + k);
+                bct_out[3 * i + 0] = bct_out[3 * i + 1] = 0.0f;
+                bct_out[3 * i + 2] = t;
+            }
+        }
+    }
+    return RT_OK;
+}
+
 int rto_light_pdf(rto_scene *s, const float *rays, uint32_t n, float *pdf_out) {
     rt_params dummy{};
     Integrator<RngXoshiro> it(*s, 1, 1, 1);

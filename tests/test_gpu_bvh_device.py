@@ -8,9 +8,18 @@
 import numpy as np
 import pytest
 
+import hit_contract
 from conftest import random_rays
+from hit_contract import explain_pixels, summary, verify_hits
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_hit_contract_time():
+    t0 = hit_contract.STATS["seconds"]
+    yield
+    print(f"\n[hit contract] {hit_contract.STATS['seconds'] - t0:.1f} s of this module's run spent in verify_hits / explain_pixels")
 
 LEAF = 0x80000000
 MASK = 0x07FFFFFF
@@ -106,9 +115,10 @@ def _check_invariants(dump, positions, max_leaf=4):
     return max_depth
 
 
-def _compare_hits_with_oracle(orc, dev, rays, max_tie_share):
+def _compare_hits_with_oracle(orc, dev, rays, max_tie_share, brute="all"):
     """Closest hits of a device-built tree against the oracle's: t bit-equal on every ray, same hit / miss; where the index agrees
-    the barycentrics are bit-equal too; where it differs the two triangles tie exactly in t (asserted by the first check)."""
+    the barycentrics are bit-equal too; where it differs the two triangles tie exactly in t (asserted by the first check), and the returned
+    triangle's own test gives the returned (b, c, t) bit for bit (hit_contract.verify_hits, kind "exact")."""
     op, ob = orc.cast_rays(rays)
     gp, gb = dev.cast_rays(rays)
     assert np.array_equal(op == 0xFFFFFFFF, gp == 0xFFFFFFFF)
@@ -118,6 +128,9 @@ def _compare_hits_with_oracle(orc, dev, rays, max_tie_share):
     assert np.array_equal(gb[same].view(np.uint32), ob[same].view(np.uint32))
     share = float(1 - same.mean())
     assert share <= max_tie_share, f"{int((~same).sum())} index mismatches (exact ties) of {len(rays)} rays: more than {max_tie_share:.1e}"
+    c = verify_hits(orc, rays, op, ob, gp, gb, "exact", brute=brute)
+    print(f"\ndevice-built tree: {summary(c)}")
+    assert c["ties"] == int((~same).sum())
     return share
 
 
@@ -151,7 +164,7 @@ def test_device_lbvh_invariants_and_closest_hits(gpu, oracle, sg, case, monkeypa
         n_rays = 100_000 if sc.n_triangles >= 5000 else 20_000
         rays = random_rays(sc, n_rays, seed=12)
         # random triangle soups do not tie; the boxes scene does along the shared diagonal of a face's two triangles
-        ties = _compare_hits_with_oracle(orc, dev, rays, max_tie_share=2e-3 if case == "boxes" else 5e-5)
+        ties = _compare_hits_with_oracle(orc, dev, rays, max_tie_share=2e-3 if case == "boxes" else 5e-5, brute="all" if sc.n_triangles <= 50_000 else 256)
         # the render loop runs unchanged on the device-built tree: both schedules agree, and the image is the ORACLE's wherever
         # no path met an exact tie
         W, H, SPP = (96, 64, 4) if sc.n_triangles >= 5000 else (48, 32, 4)
@@ -162,6 +175,10 @@ def test_device_lbvh_invariants_and_closest_hits(gpu, oracle, sg, case, monkeypa
         rel = np.abs(a - b) / np.maximum(np.abs(a), 1e-6)
         differing = float((rel > 1e-5).any(axis=2).mean())
         assert differing <= (0.02 if case == "boxes" else 0.002), differing  # only paths through an exact tie can differ
+        # ... which every pixel that differs in ANY bit shows: the first differing hit of one of its paths is a tie, verified bit for bit
+        bits = (a.view(np.uint32) != b.view(np.uint32)).any(axis=2)
+        recs = explain_pixels(orc, dev, W, H, SPP, 5, np.argwhere(bits), "exact", packet=False, brute="all" if sc.n_triangles <= 50_000 else 0, what=case)
+        assert all(r["cause"] == "exact tie" for r in recs), recs
         t_dev = dev.build_times()
         print(f"\\n[{case}] {builder or 'ploc'}: triangles {sc.n_triangles}: device build {t_dev['build_ms']:.2f} ms (+ upload {t_dev['upload_ms']:.1f} ms), depth {depth}, "
               f"tie share vs oracle {ties:.2e}, pixels beyond 1e-5 of the oracle {differing:.2e}")

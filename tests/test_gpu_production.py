@@ -9,19 +9,33 @@ every ray; hit indices may differ only where two triangles share that exact `t` 
 traversal order); the mismatch count is asserted, not printed. The event counters must show the mode really visits fewer nodes.
 (One refinement for binary production trees on overlapping coplanar triangles, where the reference's own pruning rule lets the tree shape pick between
 two hits an ulp apart: test_overlapping_coplanar_triangles_and_the_binary_production_trees.)
+On top of the counts, every hit that differs from the oracle's is checked exactly (tests/hit_contract.py): the oracle's single-object test of the
+returned index reproduces it bit for bit, and no hit lies below the brute-force minimum — the wide tree's t IS that minimum. Every pixel of a
+production render that differs from the oracle (or the parity image) in any bit is explained by such a hit on one of its paths (explain_pixels).
 """
 import numpy as np
 import pytest
 
-from conftest import explain_differing_pixels, random_rays
+import hit_contract
+from conftest import random_rays
+from hit_contract import explain_pixels, summary, verify_hits, verify_reported_hits
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_hit_contract_time():
+    t0 = hit_contract.STATS["seconds"]
+    yield
+    print(f"\n[hit contract] {hit_contract.STATS['seconds'] - t0:.1f} s of this module's run spent in verify_hits / explain_pixels")
+
 
 FIXTURES = ["room_plain", "room_textured", "open_nolight", "boxes", "room_manylights"]
 
 
-def compare_hits_with_oracle(op, ob, gp, gb, what):
-    """`t` bit-equal on every ray; an index mismatch is legal only as an exact tie (same t bits, both hit). Returns the tie count."""
+def compare_hits_with_oracle(orc, rays, op, ob, gp, gb, what, brute="all"):
+    """`t` bit-equal on every ray; an index mismatch is legal only as an exact tie (same t bits, both hit), verified bit for bit by the oracle's
+    test of the returned triangle (hit_contract.verify_hits, kind "exact"). Returns the tie count."""
     ot, gt = ob[:, 2].view(np.uint32), gb[:, 2].view(np.uint32)
     miss_o, miss_g = op == 0xFFFFFFFF, gp == 0xFFFFFFFF
     assert np.array_equal(miss_o, miss_g), f"{what}: {int((miss_o != miss_g).sum())} rays hit on one side only"
@@ -31,15 +45,19 @@ def compare_hits_with_oracle(op, ob, gp, gb, what):
     # where the index agrees, the barycentrics are the same triangle test on the same operands: bit-equal too
     same = ~ties
     assert np.array_equal(gb[same].view(np.uint32), ob[same].view(np.uint32)), f"{what}: b/c differ on rays with the oracle's own triangle"
+    c = verify_hits(orc, rays, op, ob, gp, gb, "exact", brute=brute, what=what)
+    print(f"{what}: {summary(c)}")
+    assert c["ties"] == int(ties.sum())
     return int(ties.sum())
 
 
-def compare_superset_hits_with_oracle(op, ob, gp, gb, what, max_rel=1e-6):
+def compare_superset_hits_with_oracle(orc, rays, op, ob, gp, gb, what, max_rel=1e-6, brute="all", kind="superset"):
     """The wide traversal tests conservative SUPERSETS of the reference's boxes and culls against the global best, so it can
     only find what the reference finds, or something CLOSER that the reference's own pruning skipped: bvh.h:216-223 prunes a far
     child whose rounded slab-entry distance is >= the near hit, although a triangle inside may round to a smaller t (flat boxes
     of axis-aligned triangles; SURVEY 7 names the case). Asserts: never a farther hit, never a miss where the reference hits;
-    closer hits are rounding-sized (<= max_rel relative). Returns (exact ties resolved to another index, closer hits)."""
+    closer hits are rounding-sized (<= max_rel relative); and exactly (hit_contract.verify_hits, kind "superset"): every differing hit is the
+    returned object's own hit bit for bit, and t is the brute-force minimum. Returns (exact ties resolved to another index, closer hits)."""
     miss_o, miss_g = op == 0xFFFFFFFF, gp == 0xFFFFFFFF
     assert not (miss_g & ~miss_o).any(), f"{what}: {int((miss_g & ~miss_o).sum())} rays miss although the reference hits"
     both = ~miss_o & ~miss_g
@@ -52,6 +70,9 @@ def compare_superset_hits_with_oracle(op, ob, gp, gb, what, max_rel=1e-6):
     ties = both & (gt == ot) & (op != gp)
     same = both & (op == gp)
     assert np.array_equal(gb[same].view(np.uint32), ob[same].view(np.uint32)), f"{what}: (b, c, t) differ on a ray with the oracle's own triangle"
+    c = verify_hits(orc, rays, op, ob, gp, gb, kind, brute=brute, what=what)
+    print(f"{what}: {summary(c)}")
+    assert c["ties"] == int(ties.sum()) and c["closer"] + c["oracle_miss"] == int(closer.sum())
     return int(ties.sum()), int(closer.sum())
 
 
@@ -101,7 +122,7 @@ def test_global_best_hits_equal_the_oracle(pairs, gpu, name):
     _, _, st_ref = dev.cast_rays_ex(rays, gpu.RT_CAST_EXTEND)
     for mode in (gpu.RT_CAST_EXTEND_GLOBAL, gpu.RT_CAST_PACKET_GLOBAL):
         gp, gb, st = dev.cast_rays_ex(rays, mode)
-        ties = compare_hits_with_oracle(op, ob, gp, gb, f"{name} mode {mode}")
+        ties = compare_hits_with_oracle(orc, rays, op, ob, gp, gb, f"{name} mode {mode}")
         # random triangles never tie exactly; the boxes scene has shared edges (two triangles of a face, same t along the diagonal)
         assert ties <= (40 if name == "boxes" else 0), (name, mode, ties)
         # a subset of the reference's visits, and a real saving
@@ -119,6 +140,8 @@ def test_global_best_render_matches_oracle(pairs, gpu, name):
     ofb, ost = orc.run_raytracer(W, H, SPP, seed=5)
     rel = np.abs(gfb - ofb) / np.maximum(np.abs(ofb), 1e-6)
     assert rel.max() <= 1e-5, (name, float(rel.max()), int((rel > 1e-5).any(axis=2).sum()))
+    bits = (gfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2)
+    explain_pixels(orc, dev, W, H, SPP, 5, np.argwhere(bits), "exact", packet=False, global_best=True, what=f"{name}, global best")
     assert gst["casts"] == ost["casts"] and gst["shaded_hits"] == ost["shaded_hits"]  # same paths ...
     assert gst["nodes_visited"] <= ost["nodes_visited"]  # ... found with no more node visits
 
@@ -134,7 +157,7 @@ def test_global_best_on_the_bench_scene(gpu, oracle, sg):
         op, ob = orc.cast_rays(rays)
         _, _, st_ref = dev.cast_rays_ex(rays, gpu.RT_CAST_EXTEND)
         gp, gb, st = dev.cast_rays_ex(rays, gpu.RT_CAST_EXTEND_GLOBAL)
-        assert compare_hits_with_oracle(op, ob, gp, gb, "S-sponza, global best") == 0
+        assert compare_hits_with_oracle(orc, rays, op, ob, gp, gb, "S-sponza, global best", brute=1024) == 0
         assert st["nodes_visited"] <= st_ref["nodes_visited"], (st["nodes_visited"] / len(rays), st_ref["nodes_visited"] / len(rays))
         W = H = 1000
         gfb, gst = dev.run_raytracer(W, H, 1, seed=0x5EED5EED, global_best=True, counters=True)
@@ -187,7 +210,7 @@ def test_wide_hits_equal_the_oracle(wide_pairs, gpu, name):
     op, ob = orc.cast_rays(rays)
     for what, dev in (("host tree", devh), ("device LBVH", devd)):
         gp, gb, st = dev.cast_rays_ex(rays, gpu.RT_CAST_EXTEND)
-        ties, closer = compare_superset_hits_with_oracle(op, ob, gp, gb, f"{name}, wide, {what}")
+        ties, closer = compare_superset_hits_with_oracle(orc, rays, op, ob, gp, gb, f"{name}, wide, {what}")
         # an index mismatch at bit-equal t is an exact tie: two triangles of a box face or wall along their shared diagonal, two
         # overlapping lights in one plane. The wide tree visits in another order than the reference's binary tree, so the
         # first-found rule (bvh.h:132) may keep the other one. Both kinds must stay rare on random rays.
@@ -199,7 +222,7 @@ def test_wide_hits_equal_the_oracle(wide_pairs, gpu, name):
         # the packet kernel (one walk per 64 consecutive rays, records through the scalar cache): coherent camera rays and, as a
         # stress, incoherent random ones; same superset contract, and the same hits as the per-lane kernel wherever no tie is involved
         pp, pb, pst = dev.cast_rays_ex(rays, gpu.RT_CAST_PACKET)
-        pties, pcloser = compare_superset_hits_with_oracle(op, ob, pp, pb, f"{name}, wide packets, {what}")
+        pties, pcloser = compare_superset_hits_with_oracle(orc, rays, op, ob, pp, pb, f"{name}, wide packets, {what}")
         assert pties + pcloser <= len(rays) // 500 + (40 if name == "boxes" else 0), (name, what, pties, pcloser)
         assert np.array_equal(pb[:, 2].view(np.uint32), gb[:, 2].view(np.uint32)), "packet and per-lane wide traversal disagree on a closest-hit distance"
         assert pst["tri_tests"] > 0 and pst["nodes_visited"] >= st["nodes_visited"]  # a packet visits the union of its rays' nodes
@@ -234,6 +257,11 @@ def test_wide_degenerate_rays(wide_pairs, gpu):
     assert (gb[both, 2] <= ob[both, 2]).all()
     assert not only_orc.any(), "the wide traversal missed a hit the reference finds"
     assert differ.mean() < 0.25, float(differ.mean())
+    # and each of them exactly: every GPU-only and every closer hit is the returned triangle's own hit bit for bit, and on EVERY ray the wide
+    # traversal's t is the brute-force minimum over all triangles (the hits the reference's NaN slab semantics lose are real)
+    c = verify_hits(orc, rays, op, ob, gp, gb, "superset", what="degenerate rays")
+    print(f"degenerate rays: {summary(c)}")
+    assert c["verified"] >= int(only_gpu.sum() + both.sum()) and c["prod_ne_brute"] == 0
 
 
 @pytest.mark.parametrize("name", FIXTURES)
@@ -241,10 +269,15 @@ def test_wide_render_matches_oracle(wide_pairs, gpu, name):
     devh, devd, orc, _ = wide_pairs[name]
     W, H, SPP = 48, 40, 6
     ofb, ost = orc.run_raytracer(W, H, SPP, seed=5)
-    for dev in (devh, devd):
+    for what, dev in (("host tree", devh), ("device LBVH", devd)):
         gfb, gst = dev.run_raytracer(W, H, SPP, seed=5, counters=True)
         rel = np.abs(gfb - ofb) / np.maximum(np.abs(ofb), 1e-6)
         bad = (rel > 1e-5).any(axis=2)
+        # every pixel that differs in ANY bit: one of its paths met a tie or a closer hit, verified exactly
+        bits = (gfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2)
+        recs = explain_pixels(orc, dev, W, H, SPP, 5, np.argwhere(bits), "superset", what=f"{name}, wide, {what}")
+        print(f"{name}, wide ({what}): {len(recs)} pixels differ in some bit, all explained: "
+              f"{sum(r['cause'] == 'exact tie' for r in recs)} by a tie, {len(recs) - sum(r['cause'] == 'exact tie' for r in recs)} by a closer hit")
         # 1e-5 relative wherever every cast of the pixel found the reference's own hit. A pixel may differ where a path met an
         # exact tie or a closer hit (see compare_superset_hits_with_oracle; light sampling aims rays AT the lights, two of which
         # overlap in one plane in some fixtures): such a path continues from another triangle. Bounded, and the image as a whole
@@ -360,15 +393,17 @@ def test_wide_on_the_bench_scene(gpu, oracle, sg):
             print(f"S-sponza wide ({what}) at the bench's 64 SPP (6.4e7 samples, ~2e8 casts): {int(bits.sum())} of 10^6 pixels differ from the parity image in any bit, "
                   f"{int((rel > 1e-5).sum())} beyond 1e-5 relative")
             assert int(bits.sum()) <= 2, (what, int(bits.sum()), np.argwhere(bits)[:8].tolist())  # measured: 0
-            for rec in explain_differing_pixels(gpu, orc64, par, dev, W, H, 64, 0x5EED5EED, np.argwhere(bits)):
+            for rec in explain_pixels(orc64, dev, W, H, 64, 0x5EED5EED, np.argwhere(bits), "superset", brute=0, what=f"S-sponza wide ({what}), 64 SPP",
+                                      parity=par):
                 print(f"S-sponza wide ({what}):   {rec}")
             gp, gb, st = dev.cast_rays_ex(rays, gpu.RT_CAST_EXTEND)
-            ties, closer = compare_superset_hits_with_oracle(op, ob, gp, gb, f"S-sponza, wide, {what}")
+            ties, closer = compare_superset_hits_with_oracle(orc, rays, op, ob, gp, gb, f"S-sponza, wide, {what}", brute=1024)
             assert ties + closer <= 6, (what, ties, closer)
             gfb, gst = dev.run_raytracer(W, H, 1, seed=0x5EED5EED, counters=True)
             diff = (gfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2)
             print(f"S-sponza wide ({what}): {ties} ties + {closer} closer hits of {len(rays)} rays; {int(diff.sum())} of 10^6 pixels differ from the oracle in any bit")
             assert diff.mean() <= 0.002, f"{what}: {int(diff.sum())} of 10^6 pixels differ from the oracle"
+            explain_pixels(orc, dev, W, H, 1, 0x5EED5EED, np.argwhere(diff), "superset", packet=False, brute=0, what=f"S-sponza wide ({what}), 1 SPP")
             assert abs(gst["casts"] - ost["casts"]) <= 0.0005 * ost["casts"]
             print(f"S-sponza wide ({what}): wide nodes/cast {gst['nodes_visited'] / gst['casts']:.1f}, triangle tests/cast {gst['tri_tests'] / gst['casts']:.1f} "
                   f"(oracle, binary: {ost['nodes_visited'] / ost['casts']:.1f} / {ost['tri_tests'] / ost['casts']:.1f})")
@@ -386,8 +421,9 @@ def test_overlapping_coplanar_triangles_and_the_binary_production_trees(gpu, ora
     returns one, the same rule on a device-built binary tree (or global-best culling) may return the other, one ulp FARTHER. Neither is wrong
     geometry. The contract this test pins for such scenes:
       * every production mode: hit / miss as the oracle; a differing t differs by <= 4 ulp, belongs to ANOTHER triangle, and is a true hit of that
-        triangle (float64 recomputation written here: t within 1e-5 relative, barycentrics inside);
-      * the wide tree (conservative boxes, global best): never farther than the oracle, on any ray;
+        triangle (float64 recomputation written here: t within 1e-5 relative, barycentrics inside; and on every differing ray the oracle's own test
+        of that triangle gives the returned (b, c, t) bit for bit);
+      * the wide tree (conservative boxes, global best): never farther than the oracle, on any ray, and its t is the brute-force minimum;
       * the share of rays concerned is counted and bounded (they are rays into the overlap of two coplanar lights)."""
     sc = sg.room_scene(500, seed=1610353746, offset=1.5, n_lights=40, light_strength=5.0, n_materials=1, tex_size=0, n_tex_sets=1, alpha_fraction=0.0,
                        smooth_normals=True, camera=sg.look_camera((16.3, 14.9, -1.9), yaw_deg=42.0, yfov=1.1))
@@ -430,8 +466,16 @@ def test_overlapping_coplanar_triangles_and_the_binary_production_trees(gpu, ora
             assert (gp[diff] != op[diff]).all(), f"{what}: the SAME triangle with another t"
             for i in diff[:200]:
                 assert true_hit(int(i), int(gp[i]), float(gb[i, 2])), (what, int(i), int(gp[i]))
+            # exactly, on EVERY ray whose hit differs in any word: the returned triangle's own test gives that (b, c, t) bit for bit
+            differ = np.flatnonzero((gp != op) | (gb.view(np.uint32) != ob.view(np.uint32)).any(axis=1))
+            verify_reported_hits(orc, rays, gp, gb, differ, what=what)
             if superset:
                 assert farther == 0, f"{what}: {farther} rays return a farther hit than the oracle"
+                c = verify_hits(orc, rays, op, ob, gp, gb, "superset", what=what)  # and t is the brute-force minimum on every ray
+                report.append(f"{what}: {summary(c)}")
+            else:
+                c = verify_hits(orc, rays, op, ob, gp, gb, "exact", what=what, coplanar_ulps=4)
+                report.append(f"{what}: brute force: t_prod != t_brute on {c['prod_ne_brute']} rays, t_oracle > t_brute on {c['oracle_above_brute']}")
             assert len(diff) <= 2e-3 * n, (what, len(diff))
             ties = int(((gp != op) & (ob[:, 2].view(np.uint32) == gb[:, 2].view(np.uint32))).sum())
             report.append(f"{what}: {len(diff)} rays with another t ({farther} farther, <= 4 ulp), {ties} exact ties")
@@ -471,7 +515,7 @@ def test_wide_on_tiny_scenes(gpu, oracle, sg, n_tris):
             try:
                 for mode in (gpu.RT_CAST_EXTEND, gpu.RT_CAST_PACKET):
                     gp, gb, _ = dev.cast_rays_ex(rays, mode)
-                    ties, closer = compare_superset_hits_with_oracle(op, ob, gp, gb, f"{n_tris} triangles {kw} mode {mode}")
+                    ties, closer = compare_superset_hits_with_oracle(orc, rays, op, ob, gp, gb, f"{n_tris} triangles {kw} mode {mode}")
                     assert ties + closer == 0, (n_tris, kw, mode, ties, closer)
                 if n_tris:
                     dump = dev.bvh_wide_dump()
@@ -481,6 +525,7 @@ def test_wide_on_tiny_scenes(gpu, oracle, sg, n_tris):
                 gfb, _ = dev.run_raytracer(32, 24, 4, seed=3)
                 rel = np.abs(gfb - ofb) / np.maximum(np.abs(ofb), 1e-6)
                 assert rel.max() <= 1e-5, (n_tris, kw, float(rel.max()))
+                explain_pixels(orc, dev, 32, 24, 4, 3, np.argwhere((gfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2)), "superset", what=f"{n_tris} triangles {kw}")
             finally:
                 dev.close()
     finally:
@@ -527,7 +572,8 @@ def test_production_build_at_extreme_scales(gpu, oracle, sg, scale_log2):
             dev = gpu.DeviceScene(sc, **kw)
             try:
                 gp, gb, _ = dev.cast_rays_ex(rays, gpu.RT_CAST_EXTEND)
-                ties, closer = compare_superset_hits_with_oracle(op, ob, gp, gb, f"scale 2^{scale_log2} {kw}")
+                # the binary device tree: the superset bounds, and verified against the exact contract of a binary production tree
+                ties, closer = compare_superset_hits_with_oracle(orc, rays, op, ob, gp, gb, f"scale 2^{scale_log2} {kw}", kind="superset" if kw.get("wide") else "exact")
                 assert ties + closer <= 12, (scale_log2, kw, ties, closer)
                 if kw.get("wide"):
                     dump = dev.bvh_wide_dump()
@@ -535,8 +581,10 @@ def test_production_build_at_extreme_scales(gpu, oracle, sg, scale_log2):
 
                     walk_and_check(dump["nodes"], dump["tris"][:, 9].copy(), sc.positions)
                 gfb, _ = dev.run_raytracer(32, 24, 3, seed=3)
-                differing = int((gfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2).sum())
+                bits = (gfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2)
+                differing = int(bits.sum())
                 assert differing <= 8, (scale_log2, kw, differing)
+                explain_pixels(orc, dev, 32, 24, 3, 3, np.argwhere(bits), "superset" if kw.get("wide") else "exact", packet=False, what=f"scale 2^{scale_log2} {kw}")
             finally:
                 dev.close()
     finally:
@@ -552,11 +600,61 @@ def test_wide_with_analytic_primitives(gpu, oracle, tmp_path):
     ls = gpu.parse_scene_txt(txt)
     orc = oracle.OracleScene(ls)
     ofb, ost = orc.run_raytracer(48, 40, 6, seed=4)
-    orc.close()
-    for kw in (dict(wide=True), dict(wide=True, device_bvh=True)):
-        dev = gpu.DeviceScene(ls, **kw)
-        gfb, gst = dev.run_raytracer(48, 40, 6, seed=4, counters=True)
-        dev.close()
-        rel = np.abs(gfb - ofb) / np.maximum(np.abs(ofb), 1e-6)
-        assert (rel > 1e-5).any(axis=2).mean() <= 0.01, (kw, float(rel.max()))
-        assert abs(gst["casts"] - ost["casts"]) <= 0.002 * ost["casts"]
+    try:
+        for kw in (dict(wide=True), dict(wide=True, device_bvh=True)):
+            dev = gpu.DeviceScene(ls, **kw)
+            try:
+                gfb, gst = dev.run_raytracer(48, 40, 6, seed=4, counters=True)
+                rel = np.abs(gfb - ofb) / np.maximum(np.abs(ofb), 1e-6)
+                assert (rel > 1e-5).any(axis=2).mean() <= 0.01, (kw, float(rel.max()))
+                assert abs(gst["casts"] - ost["casts"]) <= 0.002 * ost["casts"]
+                bits = (gfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2)
+                recs = explain_pixels(orc, dev, 48, 40, 6, 4, np.argwhere(bits), "superset", what=f"cornell_mixed {kw}")
+                print(f"cornell_mixed {kw}: {len(recs)} pixels differ from the oracle in some bit, all explained")
+            finally:
+                dev.close()
+    finally:
+        orc.close()
+
+
+SCENE_TXT = ["cornell_mixed.txt", "practice3_5.txt", "scene-000.txt"]
+
+
+@pytest.mark.parametrize("txt", SCENE_TXT)
+def test_wide_hits_on_scene_txt(gpu, oracle, txt):
+    """Scene-txt scenes through the wide tree, ray by ray: BOX / TRIANGLE primitives as triangles in the tree, ELLIPSOID / PLANE (indices >=
+    n_triangles, reported (0, 0, t)) tested after it by wf_extend_prims. Both wide builds, per-lane and packet kernels, 20 000 random rays and
+    8 192 camera rays: the superset contract with every differing hit verified bit for bit and t the brute-force minimum on every ray."""
+    import os
+    import types
+
+    ls = gpu.parse_scene_txt(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "txt", txt))
+    arrays = ls.arrays()
+    orc = oracle.OracleScene(ls)
+    try:
+        pos = np.asarray(arrays["positions"], dtype=np.float32).reshape(-1, 3)
+        n_tri = len(pos) // 3
+        cam = types.SimpleNamespace(**arrays["camera"])
+        pts = np.concatenate([pos, cam.position[None, :]])
+        lo, hi = pts.min(axis=0) - 0.5, pts.max(axis=0) + 0.5
+        rng = np.random.default_rng(303)
+        o = rng.uniform(lo, hi, size=(20000, 3)).astype(np.float32)
+        d = rng.normal(size=(20000, 3)).astype(np.float32)
+        d[:1250] = np.eye(3, dtype=np.float32)[rng.integers(0, 3, size=1250)] * rng.choice([-1.0, 1.0], size=(1250, 1)).astype(np.float32)
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        rays = np.concatenate([np.concatenate([o, d], axis=1).astype(np.float32), _camera_rays(types.SimpleNamespace(camera=cam), 8192, seed=304)])
+        op, ob = orc.cast_rays(rays)
+        n_prim_hits = int(((op != 0xFFFFFFFF) & (op >= n_tri)).sum())
+        assert n_prim_hits > 0 and n_tri > 0
+        for kw in (dict(wide=True), dict(wide=True, device_bvh=True)):
+            dev = gpu.DeviceScene(ls, **kw)
+            try:
+                for mode in (gpu.RT_CAST_EXTEND, gpu.RT_CAST_PACKET):
+                    gp, gb, _ = dev.cast_rays_ex(rays, mode)
+                    c = verify_hits(orc, rays, op, ob, gp, gb, "superset", what=f"{txt} {kw} mode {mode}")
+                    print(f"{txt} {kw} mode {mode} ({n_tri} triangles, {n_prim_hits} oracle hits on analytic primitives): {summary(c)}")
+                    assert c["prod_ne_brute"] == 0
+            finally:
+                dev.close()
+    finally:
+        orc.close()

@@ -12,9 +12,18 @@ import os
 import numpy as np
 import pytest
 
-from conftest import explain_differing_pixels, random_rays
+import hit_contract
+from conftest import random_rays
+from hit_contract import explain_pixels, summary, verify_hits
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_hit_contract_time():
+    t0 = hit_contract.STATS["seconds"]
+    yield
+    print(f"\n[hit contract] {hit_contract.STATS['seconds'] - t0:.1f} s of this module's run spent in verify_hits / explain_pixels")
 
 COUNTERS = ("samples", "casts", "nodes_visited", "box_tests", "tri_tests", "shaded_hits", "light_queries", "light_nodes", "light_box_tests",
             "light_tri_tests", "light_hits", "texel_fetches")
@@ -60,20 +69,26 @@ def test_s10m_full_size_parity_and_properties(gpu, oracle, sg):
         rays = random_rays(sc, 100_000, seed=78)
         op, ob = orc.cast_rays(rays)
 
-        def check(what, scene, mode, spans=True):
+        def check(what, scene, mode, spans=True, kind="exact"):
             gp, gb, st = scene.cast_rays_ex(rays, mode)
             assert np.array_equal(op == 0xFFFFFFFF, gp == 0xFFFFFFFF), what
             bad = ob[:, 2].view(np.uint32) != gb[:, 2].view(np.uint32)
             assert not bad.any(), f"{what}: t differs from the oracle on {int(bad.sum())} of {len(rays)} rays"
             ties = int((op != gp).sum())
             assert ties <= 5, f"{what}: {ties} index mismatches (exact ties) in a random triangle soup"
-            msg = f"[S-10M] {what}: {ties} ties / {len(rays)} rays, {st['nodes_visited'] / len(rays):.1f} node visits + {st['tri_tests'] / len(rays):.1f} triangle tests per cast"
+            # every tie verified bit for bit by the returned triangle's own test; brute force on those and on a fixed sample of 128 rays
+            c = verify_hits(orc, rays, op, ob, gp, gb, kind, brute=128, what=f"S-10M {what}")
+            assert c["ties"] == ties
+            msg = f"[S-10M] {what}: {ties} ties / {len(rays)} rays, {st['nodes_visited'] / len(rays):.1f} node visits + {st['tri_tests'] / len(rays):.1f} triangle tests per cast; {summary(c)}"
             if spans:
                 pfb = np.full((H, W, 3), -1.0, dtype=np.float32)
-                scene.run_raytracer(W, H, 1, seed=0x5EED5EED, shard_index=5, shard_count=64, shard_block=256, out=pfb, global_best=mode == gpu.RT_CAST_EXTEND_GLOBAL)
-                nbad = int((pfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2).sum())
+                gb_render = mode == gpu.RT_CAST_EXTEND_GLOBAL
+                scene.run_raytracer(W, H, 1, seed=0x5EED5EED, shard_index=5, shard_count=64, shard_block=256, out=pfb, global_best=gb_render)
+                bits = (pfb.view(np.uint32) != ofb.view(np.uint32)).any(axis=2)
+                nbad = int(bits.sum())
                 assert nbad <= 8, f"{what}: {nbad} of {W * H // 64} pixels differ from the oracle"
-                msg += f", {nbad} of {W * H // 64} pixels differ from the oracle"
+                recs = explain_pixels(orc, scene, W, H, 1, 0x5EED5EED, np.argwhere(bits), kind, packet=False, global_best=gb_render, brute=0, what=f"S-10M {what}")
+                msg += f", {nbad} of {W * H // 64} pixels differ from the oracle ({len(recs)} explained)"
             print(msg)
 
         check("reference tree, global-best pruning", dev, gpu.RT_CAST_EXTEND_GLOBAL)
@@ -86,14 +101,15 @@ def test_s10m_full_size_parity_and_properties(gpu, oracle, sg):
         pfb32, _ = dev.run_raytracer(W, H, 32, seed=0x5EED5EED)
         for what, kw in (("wide tree from the reference-topology tree", dict(wide=True)), ("wide tree from the device LBVH", dict(wide=True, device_bvh=True))):
             wd = gpu.DeviceScene(sc, **kw)
-            check(what, wd, gpu.RT_CAST_EXTEND)
+            check(what, wd, gpu.RT_CAST_EXTEND, kind="superset")
             if kw.get("device_bvh"):  # the benched production build, at the depth its number is quoted at
                 wfb32, _ = wd.run_raytracer(W, H, 32, seed=0x5EED5EED)
                 bits = (wfb32.view(np.uint32) != pfb32.view(np.uint32)).any(axis=2)
                 print(f"[S-10M] production build at 32 SPP: {int(bits.sum())} of {W * H} pixels differ from the parity image in any bit")
                 # 1.3e8 samples, ~5e8 casts: measured 1 pixel. Every differing pixel must be explained by the production contract's two cases
                 assert int(bits.sum()) <= 4, (int(bits.sum()), np.argwhere(bits)[:8].tolist())
-                for rec in explain_differing_pixels(gpu, orc, dev, wd, W, H, 32, 0x5EED5EED, np.argwhere(bits)):
+                for rec in explain_pixels(orc, wd, W, H, 32, 0x5EED5EED, np.argwhere(bits), "superset", brute=0, what="S-10M production build, 32 SPP",
+                                      parity=dev):
                     print(f"[S-10M]   {rec}")
                 del wfb32
             wd.close()
