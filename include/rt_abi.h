@@ -43,7 +43,9 @@ extern "C" {
 
 #define RT_ABI_VERSION 4u /* 2: rt_scene_desc carries analytic primitives (scene-txt front end); 3: bg_texture (environment map);
                              4: every tuning knob is a field (rt_build_options, rt_params.sort_mode / packet_mode / max_paths ...): the library
-                                reads no environment variable; progress callback; packet census in rt_stats */
+                                reads no environment variable; progress callback; packet census in rt_stats. Still 4 after the development
+                                options were retired (two rt_build_options fields became reserved, unused RT_SORT_* / RT_BUILD_* values are
+                                refused): the binary layout and the meaning of every value that remains are unchanged */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
 
@@ -122,22 +124,12 @@ typedef struct rt_build_options {
                                  traversal stacks) or RT_BUILDER_LBVH (Karras radix tree + refit) */
     uint32_t ploc_radius;     /* PLOC nearest-neighbour search radius, 1..32; 0 = 8 (profiles/r03_wide.txt) */
     uint32_t lbvh_leaf_tris;  /* triangles per leaf of the device-built binary tree, 1..8; 0 = 1 */
-    uint32_t node_order;      /* order of the reference-topology tree's inner nodes in HBM: 0 pre-order (default), 1 breadth first,
-                                 2 sibling pairs. Placement only: hits and counters do not depend on it */
+    uint32_t reserved0;       /* 0 (was node_order, a development placement option) */
     float wide_cost_node;     /* surface-area cost of a wide-node visit in the collapse; 0 = 1.0 */
     float wide_cost_tri;      /* ... of a triangle test; 0 = 0.3 */
-    uint32_t wide_order;      /* order of the WideNode records in HBM: RT_WIDE_ORDER_* (placement only) */
+    uint32_t reserved1;       /* 0 (was wide_order, read by nothing) */
     uint32_t reserved;        /* 0 */
-} rt_build_options;
-/* Placement of the 8-wide tree's records (csrc/wide_build.cpp, csrc/rt_bvh_device.hip). Children of one node are always
- * consecutive (the traversal finds child i at child_base + rank); what differs is where the groups of siblings go. */
-enum {
-    RT_WIDE_ORDER_DEFAULT = 0,  /* what measured best for the builder in use */
-    RT_WIDE_ORDER_LEVEL = 1,    /* level by level (breadth first): the device builder's natural emission order */
-    RT_WIDE_ORDER_DFS = 2,      /* sibling groups in depth-first order of their parents */
-    RT_WIDE_ORDER_TREELET = 3   /* van-Emde-Boas-like: a node's children group, then recursively each child's subtree in blocks of
-                                   three levels, so that a descent of three levels stays inside one contiguous region */
-};
+} rt_build_options; /* rt_create refuses a non-zero reserved field */
 
 typedef struct rt_scene_desc {
     uint32_t abi_version; /* RT_ABI_VERSION */
@@ -181,28 +173,24 @@ typedef struct rt_scene_desc {
  *       reference-RNG parity renders are refused on such a scene (RT_ERR_UNSUPPORTED). The CLI sets it for RT_BVH_WIDE=1.
  *   RT_BUILD_WIDE_HOST_COLLAPSE (development; with RT_BUILD_DEVICE_LBVH | RT_BUILD_WIDE): read the device-built binary tree back and
  *       collapse it on the host (wide_build.cpp) instead of on the device — the cross-check of the device collapse.
- *   RT_BUILD_LIGHTS_GLOBAL (development): never stage the light BVH in wf_shade's LDS.
  *   RT_BUILD_GROUP_COPY (tests; multi-GPU scenes): replace the RCCL exchange by peer copies, which lets a one-GPU box rehearse G > 1
  *       with repeated ordinals (RCCL refuses those). RT_BUILD_GROUP_SELF_EXCHANGE (tests): the first GPU's own blocks also travel
- *       through ncclSend / ncclRecv, which exercises the RCCL path with G = 1. */
-enum { RT_BUILD_REFERENCE = 0, RT_BUILD_DEVICE_LBVH = 1, RT_BUILD_WIDE = 2, RT_BUILD_WIDE_HOST_COLLAPSE = 4, RT_BUILD_LIGHTS_GLOBAL = 8,
-       RT_BUILD_GROUP_COPY = 16, RT_BUILD_GROUP_SELF_EXCHANGE = 32 };
+ *       through ncclSend / ncclRecv, which exercises the RCCL path with G = 1.
+ * rt_create refuses any other bit (8 was a development flag). */
+enum { RT_BUILD_REFERENCE = 0, RT_BUILD_DEVICE_LBVH = 1, RT_BUILD_WIDE = 2, RT_BUILD_WIDE_HOST_COLLAPSE = 4, RT_BUILD_GROUP_COPY = 16,
+       RT_BUILD_GROUP_SELF_EXCHANGE = 32 };
 #define RT_MAX_PRIMITIVES 4096u
 
 /* Progress report of a render: called on the calling thread after every finished pass (pixel tile x sample range) of a single-GPU
  * scene, `done` of `total` passes; a multi-GPU scene reports once per GPU that finished, from that GPU's host thread (calls are
  * serialised). The reference prints "%d/%d     \r" per finished span (raytracer.h:647); the CLI does the same per pass under RT_VERBOSE. */
 typedef void (*rt_progress_fn)(uint32_t done, uint32_t total, void *user);
-/* Coherence sort of the rays of bounces >= 1 (wavefront pipeline; ordering never changes a result) */
+/* Coherence sort of the rays of bounces >= 1 (wavefront pipeline; ordering never changes a result). rt_render refuses any other value
+ * (2 - 5 and 7 were development keys). */
 enum {
-    RT_SORT_AUTO = 0,             /* octant + cell + sub-cone where the tree does not fit the caches, none for a cache-resident wide tree */
+    RT_SORT_AUTO = 0,            /* octant + cell + sub-cone where the tree does not fit the caches, none for a cache-resident wide tree */
     RT_SORT_OFF = 1,
-    RT_SORT_CELL_OCTANT = 2,      /* 64^3 origin cell, direction octant (21 bits) */
-    RT_SORT_COARSE_CELL_DIR = 3,  /* 16^3 cell, 9-bit direction code */
-    RT_SORT_OCTANT_CELL = 4,      /* octant, 64^3 cell */
-    RT_SORT_CELL_OCTANT_CONE = 5, /* cell, octant, sub-cone (24 bits) */
-    RT_SORT_OCTANT_CELL_CONE = 6, /* octant, cell, sub-cone: what AUTO picks */
-    RT_SORT_OCTANT_FINE_CELL_CONE = 7 /* octant, 128^3 cell, sub-cone (27 bits) */
+    RT_SORT_OCTANT_CELL_CONE = 6 /* direction octant, 64^3 origin cell, direction sub-cone (24 bits): what AUTO picks */
 };
 /* Primary rays as 64-ray packets (wf_extend_packet / wf_extend_wide_packet) */
 enum {

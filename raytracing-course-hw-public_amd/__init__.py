@@ -26,23 +26,13 @@ from ._ctypes_abi import (
     RT_BUILD_DEVICE_LBVH,
     RT_BUILD_WIDE,
     RT_BUILD_WIDE_HOST_COLLAPSE,
-    RT_BUILD_LIGHTS_GLOBAL,
     RT_BUILD_GROUP_COPY,
     RT_BUILD_GROUP_SELF_EXCHANGE,
     RT_BUILDER_PLOC,
     RT_BUILDER_LBVH,
-    RT_WIDE_ORDER_DEFAULT,
-    RT_WIDE_ORDER_LEVEL,
-    RT_WIDE_ORDER_DFS,
-    RT_WIDE_ORDER_TREELET,
     RT_SORT_AUTO,
     RT_SORT_OFF,
-    RT_SORT_CELL_OCTANT,
-    RT_SORT_COARSE_CELL_DIR,
-    RT_SORT_OCTANT_CELL,
-    RT_SORT_CELL_OCTANT_CONE,
     RT_SORT_OCTANT_CELL_CONE,
-    RT_SORT_OCTANT_FINE_CELL_CONE,
     RT_PACKET_AUTO,
     RT_PACKET_OFF,
     RT_PACKET_ON,
@@ -198,7 +188,7 @@ class DeviceScene:
         """`device_bvh`: build the scene BVH on the GPU (RT_BUILD_DEVICE_LBVH: production mode, different topology) instead
         of the reference-topology host build. `wide`: collapse that binary tree into the 8-wide quantised tree (RT_BUILD_WIDE:
         production traversal). `build_flags`: further RT_BUILD_* bits; `build_options`: rt_build_options fields by name (device_builder,
-        ploc_radius, lbvh_leaf_tris, node_order, wide_cost_node, wide_cost_tri, wide_order). `device`: a HIP ordinal; RT_ALL_DEVICES (-1)
+        ploc_radius, lbvh_leaf_tris, wide_cost_node, wide_cost_tri). `device`: a HIP ordinal; RT_ALL_DEVICES (-1)
         for one replica per visible GPU + an RCCL communicator; or a list of ordinals (rt_create_on). Multi-GPU scenes shard every render
         over their GPUs and gather on the first one."""
         desc, keep = _as_desc(scene)

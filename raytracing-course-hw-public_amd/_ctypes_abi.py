@@ -16,12 +16,10 @@ RT_BUILD_REFERENCE = 0
 RT_BUILD_DEVICE_LBVH = 1
 RT_BUILD_WIDE = 2
 RT_BUILD_WIDE_HOST_COLLAPSE = 4
-RT_BUILD_LIGHTS_GLOBAL = 8
 RT_BUILD_GROUP_COPY = 16
 RT_BUILD_GROUP_SELF_EXCHANGE = 32
 RT_BUILDER_PLOC, RT_BUILDER_LBVH = 0, 1
-RT_WIDE_ORDER_DEFAULT, RT_WIDE_ORDER_LEVEL, RT_WIDE_ORDER_DFS, RT_WIDE_ORDER_TREELET = range(4)
-RT_SORT_AUTO, RT_SORT_OFF, RT_SORT_CELL_OCTANT, RT_SORT_COARSE_CELL_DIR, RT_SORT_OCTANT_CELL, RT_SORT_CELL_OCTANT_CONE, RT_SORT_OCTANT_CELL_CONE, RT_SORT_OCTANT_FINE_CELL_CONE = range(8)
+RT_SORT_AUTO, RT_SORT_OFF, RT_SORT_OCTANT_CELL_CONE = 0, 1, 6
 RT_PACKET_AUTO, RT_PACKET_OFF, RT_PACKET_ON = range(3)
 RT_TEX_NONE = -1
 RT_RNG_DEVICE = 0
@@ -93,10 +91,10 @@ class RtBuildOptions(C.Structure):
         ("device_builder", C.c_uint32),
         ("ploc_radius", C.c_uint32),
         ("lbvh_leaf_tris", C.c_uint32),
-        ("node_order", C.c_uint32),
+        ("reserved0", C.c_uint32),
         ("wide_cost_node", C.c_float),
         ("wide_cost_tri", C.c_float),
-        ("wide_order", C.c_uint32),
+        ("reserved1", C.c_uint32),
         ("reserved", C.c_uint32),
     ]
 

@@ -7,7 +7,7 @@
 // RT_ENV_MAP (+ RT_ENV_MAP_INTENSITY): the environment map the reference enables at compile time (config.h:36-38, main.cpp:28-31);
 // RT_LIGHT_TRIANGLE=1 (+ RT_LIGHT_TRIANGLE_INTENSITY): its extra light source in camera coordinates (config.h:40-47, scene.h:479-498).
 // Tuning (the library itself reads NO environment variable since ABI 4; this file translates them into rt_scene_desc / rt_params
-// fields): RT_BVH_DEVICE=1, RT_BVH_WIDE=1 (production builds), RT_TRAVERSAL=global, RT_WF_SORT=<0..5>, RT_WF_PACKET=<0|1>,
+// fields): RT_BVH_DEVICE=1, RT_BVH_WIDE=1 (production builds), RT_TRAVERSAL=global, RT_WF_SORT=<0|5> (off | sorted), RT_WF_PACKET=<0|1>,
 // RT_WF_MAX_PATHS=<n>, RT_DEVICE_BUILDER=lbvh, RT_PLOC_RADIUS=<n>. RT_VERBOSE: the reference's progress line "%d/%d     \r"
 // (raytracer.h:647) per finished pass, and a timing line on stderr.
 #include <cstdio>
@@ -100,7 +100,7 @@ int main(int argc, char **argv) {
     if (const char *t = std::getenv("RT_TRAVERSAL"); t && !std::strcmp(t, "global"))
         p.flags |= RT_FLAG_GLOBAL_BEST;
     if (const char *v = std::getenv("RT_WF_SORT"))
-        p.sort_mode = (uint32_t)std::atoi(v) + 1u; // RT_SORT_OFF = 1, then the keys in the order of RT_SORT_*
+        p.sort_mode = (uint32_t)std::atoi(v) + 1u; // RT_SORT_OFF = 1, RT_SORT_OCTANT_CELL_CONE = 6
     if (const char *v = std::getenv("RT_WF_PACKET"))
         p.packet_mode = std::atoi(v) ? RT_PACKET_ON : RT_PACKET_OFF;
     if (const char *v = std::getenv("RT_WF_MAX_PATHS"))

@@ -114,48 +114,6 @@ template <> struct LaneStats<true> {
     }
 };
 
-// Development-only wave-level execution census (-DRT_DIAG, tools_variants.sh): how often each section of the
-// persistent loop runs and with how many active lanes. Reuses the DevStats words; never compiled into the product.
-#ifdef RT_DIAG
-__device__ DevStats *g_diag = nullptr;
-DEV void diag_add(int slot, unsigned long long v) {
-    const unsigned long long m = __ballot(1);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (rank == 0 && g_diag)
-        atomicAdd(reinterpret_cast<unsigned long long *>(g_diag) + slot, v);
-}
-#define DIAG(slot, v) diag_add(slot, v)
-#define DIAG_LANES(slot) diag_add(slot, (unsigned long long)__popcll(__ballot(1)))
-#else
-#define DIAG(slot, v) do { } while (0)
-#define DIAG_LANES(slot) do { } while (0)
-#endif
-
-// Development-only section census of wf_shade (-DRT_DIAG_SHADE): wave cycles (s_memtime) and active lanes between stamps,
-// accumulated per wave in LDS and flushed to the census words at kernel end. Never compiled into the product.
-#ifdef RT_DIAG_SHADE
-// A stamp at the END of a region (also inside a divergent branch or a loop body) attributes the wave cycles since the wave's previous stamp to
-// `section`, once plain and once weighted with the lanes active at the stamp: lane_cycles / cycles = the lanes that section really runs at.
-enum { SD_LOAD = 0, SD_ATTR, SD_TEX, SD_ALPHA, SD_S_VNDF, SD_S_COS, SD_S_LIGHT, SD_VNDF_PDF, SD_LPDF, SD_BRDF, SD_FOLD, SD_STORE, SD_N };
-__shared__ unsigned long long g_sd_cyc[4][SD_N], g_sd_lanes[4][SD_N], g_sd_t[4];
-DEV void sd_stamp(int section) {
-    const unsigned long long m = __ballot(1);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-    if (rank == 0) {
-        const uint32_t w = threadIdx.x >> 6;
-        const unsigned long long dt = now - g_sd_t[w];
-        g_sd_cyc[w][section] += dt;
-        g_sd_lanes[w][section] += dt * (unsigned long long)__popcll(m);
-        g_sd_t[w] = now;
-    }
-}
-#define SD_STAMP(section) sd_stamp(section)
-#else
-#define SD_STAMP(section) do { } while (0)
-#endif
-
-
 // ---------------------------------------------------------------------------------------------- RNG policy
 template <int MODE> struct Rng;
 template <> struct Rng<RT_RNG_DEVICE> {
@@ -426,7 +384,6 @@ template <int LDS_DEPTH, int WORDS = 3> struct RingStackT {
     DEV void push(int pos, uint32_t ref, float d, float loc = 0.0f) {
         const uint32_t slot = slot_of((uint32_t)pos);
         if (pos - base == LDS_DEPTH) { // ring full: the slot about to be overwritten holds position `base`, the oldest
-            DIAG(28, (unsigned long long)__popcll(__ballot(1)));
             if constexpr (WORDS == 3)
                 ov[(size_t)base * stride] = make_uint4(lds[(0 * LDS_DEPTH + slot) * 256], lds[(1 * LDS_DEPTH + slot) * 256], lds[(2 * LDS_DEPTH + slot) * 256], 0u);
             else
@@ -567,8 +524,6 @@ DEV void trav_init(Trav &T, const DevBvh &bvh, V3 o, V3 d) {
 // subtree's local best. Ends in T_DONE when the stack is empty.
 template <class STK> DEV void trav_pop(Trav &T, STK &stk) {
     while (T.cur == T_POP) {
-        DIAG(7, 1);
-        DIAG_LANES(8);
         if (T.sp == 0) {
             T.cur = T_DONE;
             break;
@@ -600,13 +555,10 @@ template <bool STATS, bool GB = false, class STK> DEV void trav_step_core(Trav &
         const uint32_t left = __float_as_uint(r3.x), right = __float_as_uint(r3.y);
         float dl, dr;
         bool hl, hr;
-        DIAG(2, 1);
-        DIAG_LANES(3);
         if (T.fast) {
             hl = box_hit_fast(lmin, lmax, T.o, T.d, T.r, min_dst, dl);
             hr = box_hit_fast(rmn, rmx, T.o, T.d, T.r, min_dst, dr);
         } else { // rare ray: a direction/origin component is 0-adjacent, huge or NaN -> reference arithmetic
-            DIAG(6, 1);
             hl = box_hit_exact(lmin, lmax, T.o, T.d, min_dst, dl);
             hr = box_hit_exact(rmn, rmx, T.o, T.d, min_dst, dr);
         }
@@ -640,8 +592,6 @@ template <bool STATS, bool GB = false, class STK> DEV void trav_step_core(Trav &
             T.cur = T_POP;
         }
     } else {
-        DIAG(4, 1);
-        DIAG_LANES(5);
         // DevTri: a.xyz v.xyz u.xyz prim flags pad
         const uint32_t flags = __float_as_uint(r2.z);
         if (flags & 2u)
@@ -746,8 +696,6 @@ DEV uint32_t wave_min_u32(uint32_t v) {
 }
 // one unwind step for every lane in T_POP, as straight-line wave code (lanes in other states pass through unchanged)
 template <bool GB = false, class STK> DEV void trav_pop_once(Trav &T, STK &stk) {
-    DIAG(7, 1);
-    DIAG(27, (unsigned long long)__popcll(__ballot(T.cur == T_POP)));
     const bool pop = T.cur == T_POP;
     const bool go = pop & (T.sp != 0);
     const int nsp = T.sp - 1;
@@ -837,7 +785,6 @@ template <bool STATS, class STK> DEV float lights_pdf(const DevScene &S, const L
             }
             if (cur == T_POP)
                 cur = sp ? stk.pop_ref(--sp) : T_DONE;
-            SD_STAMP(SD_LPDF); // (development census: one stamp per loop trip, with the lanes still walking the light BVH)
         }
     }
     return res / (float)bvh.n_tris; // res / bvh->objects.size()
@@ -1032,7 +979,6 @@ DEV Surf make_surf(const DevScene &S, const Hit &h, V3 ro, V3 rd, const float *s
         q[2] = mat_p[2];
         q[3] = mat_p[3];
     }
-    SD_STAMP(SD_ATTR);
     const float b = h.b, c = h.c;
     const float w0 = (1 - b - c); // triangle::interop geometry.h:497-502
     V3 normal = ld3(at.gn);
@@ -1060,7 +1006,6 @@ DEV Surf make_surf(const DevScene &S, const Hit &h, V3 ro, V3 rd, const float *s
         et = tex_sample(S, m.emissive_tex, TEX_DEFAULT_WHITE, tu, tv, true, s_lin, s_gam, st); // :619-621
     }
     st.shaded();
-    SD_STAMP(SD_TEX);
     {
         asm volatile("" : "+v"(mat_p)); // not before this point
         float4 *q = reinterpret_cast<float4 *>(&m);
@@ -1182,21 +1127,17 @@ template <bool STATS, bool ENV = true> DEV V3 bg_at(const DevScene &S, V3 dir, c
     return ld3(S.bg) * mk(c.r, c.g, c.b);
 }
 
-// ---- work tickets of the persistent closest-hit kernels. One head for the whole queue, or (RT_XCD_TICKETS) eight: the queue — in ray order, i.e.
-// sorted by origin cell and direction when a sort ran — is cut into eight contiguous parts and a block starts on part blockIdx.x % 8. Blocks b and
-// b + 8 are observed to share an XCD (MI355X_MICROARCH.md, workgroup dispatch), so the rays one XCD's L2 serves are neighbours in that order; a
-// block whose part has run dry moves on to the next one. Placement changes speed only: every position is handed out exactly once either way.
-// Measured (profiles/r03_variants.txt item 16): S-10M production 250.7 -> 256.2 Msamples/s, parity +0.5 %; S-sponza (cache resident) unchanged.
-#ifndef RT_XCD_TICKETS
-#define RT_XCD_TICKETS 1
-#endif
+// ---- work tickets of the persistent closest-hit kernels. Eight heads: the queue — in ray order, i.e. sorted by origin cell and direction when a
+// sort ran — is cut into eight contiguous parts and a block starts on part blockIdx.x % 8. Blocks b and b + 8 are observed to share an XCD
+// (MI355X_MICROARCH.md, workgroup dispatch), so the rays one XCD's L2 serves are neighbours in that order; a block whose part has run dry moves on
+// to the next one. Placement changes speed only: every position is handed out exactly once. Measured against one head for the whole queue
+// (profiles/r03_variants.txt item 16): S-10M production 250.7 -> 256.2 Msamples/s, parity +0.5 %; S-sponza (cache resident) unchanged.
 struct TicketState {
     uint32_t part, tried; // wave-uniform
 };
 DEV TicketState ticket_init() { return TicketState{blockIdx.x & 7u, 0u}; }
 // next range [q_lo, q_hi) of at most `chunk` queue positions; false = the whole queue has been handed out
 DEV bool ticket_take(uint32_t *counters, uint32_t n_in, uint32_t chunk, TicketState &ts, uint32_t &q_lo, uint32_t &q_hi) {
-#if RT_XCD_TICKETS
     const uint32_t n_chunks = (n_in + chunk - 1u) / chunk;
     for (;;) {
         if (ts.tried >= 8u)
@@ -1214,15 +1155,6 @@ DEV bool ticket_take(uint32_t *counters, uint32_t n_in, uint32_t chunk, TicketSt
         ts.part = (ts.part + 1u) & 7u; // this part is used up: help the next one
         ++ts.tried;
     }
-#else
-    uint32_t base = 0;
-    if ((threadIdx.x & 63u) == 0u)
-        base = atomicAdd(counters + WF_CNT_TICKET, chunk);
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    q_lo = base < n_in ? base : n_in;
-    q_hi = base + chunk < n_in ? base + chunk : n_in;
-    return q_lo != q_hi;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------- one shade() level
@@ -1266,20 +1198,16 @@ DEV ShadeResult shade_hit(const DevScene &S, const LightTabs &LT, const Hit &h, 
         out.nrd = rd;
         return out;
     }
-    SD_STAMP(SD_ALPHA);
     const float vr = pow2(rmax(ii.roughness, MIN_ROUGHNESS)); // :563-564
     V3 dir;
     if (uniform_real(rng, 0.0f, 1.0f) <= VNDF_FACTOR) { // :565
         dir = vndf_sample(rng, vr, rd, ii.shading_normal);
-        SD_STAMP(SD_S_VNDF);
     } else if (!has_lights) { // dir_dist = cosine_dist (:449)
         dir = norm(ii.normal + sphere_uniform(rng));
-        SD_STAMP(SD_S_COS);
     } else { // mix_dist{cosine, bvh_mix} (:381-393)
         const uint32_t pick = rng.below(2);
         if (pick == 0) {
             dir = norm(ii.normal + sphere_uniform(rng));
-            SD_STAMP(SD_S_COS);
         } else { // bvh_mix_dist::sample :353-361 + triangle_dist::sample :225-239
             const uint32_t id = rng.below(S.lights.n_tris);
             const float4 *lp = LT.tris + 3u * id;
@@ -1292,7 +1220,6 @@ DEV ShadeResult shade_hit(const DevScene &S, const LightTabs &LT, const Hit &h, 
             }
             V3 p = mk(l0.x, l0.y, l0.z) + mk(l0.w, l1.x, l1.y) * v + mk(l1.z, l1.w, l2.x) * u; // a + v' * v + u' * u (DevTri: a, v, u)
             dir = norm(p - pos);
-            SD_STAMP(SD_S_LIGHT);
         }
     }
     if (isnan_f(dir.x) || isnan_f(dir.y) || isnan_f(dir.z)) { // :569-571
@@ -1301,7 +1228,6 @@ DEV ShadeResult shade_hit(const DevScene &S, const LightTabs &LT, const Hit &h, 
         return out;
     }
     const float VNDF_p = vndf_pdf(vr, rd, ii.shading_normal, dir);
-    SD_STAMP(SD_VNDF_PDF);
     float MIS_p;
     const float cos_p = rmax(dot(ii.normal, dir) / PI_F, 0.0f); // cosine_dist::pdf :123-128
     if (!has_lights) {

@@ -103,11 +103,7 @@ static_assert(sizeof(DevTexture) == 32, "DevTexture must be 32 bytes");
 //   * the triangles of the node's leaf slots are consecutive DevTri records from tri_base: bit 3s + j of tri_mask says that leaf
 //     slot s holds a j-th triangle (at most 3 per slot), and that triangle is record tri_base + popcount(tri_mask below the bit).
 // An empty slot has an inverted box (qlo 255, qhi 0) that no ray hits.
-#ifdef RT_WIDE_NODE_PAD128 /* experiment: one node per 128-byte line (never straddles); same fields */
-struct alignas(128) WideNode {
-#else
 struct alignas(16) WideNode {
-#endif
     float p[3];           // grid origin = the node box's lower corner
     uint8_t e[3];         // biased exponents: cell size on axis a = 2^(e[a] - 127)
     uint8_t imask;        // bit s: slot s is an inner node
@@ -118,9 +114,7 @@ struct alignas(16) WideNode {
     uint8_t qlo[3][8];    // [axis][slot]
     uint8_t qhi[3][8];
 };
-#ifndef RT_WIDE_NODE_PAD128
 static_assert(sizeof(WideNode) == 80, "WideNode must be 80 bytes");
-#endif
 #define RT_WIDE_MAX_LEAF_TRIS 3u
 
 // ---- what the wide kernels READ: the same tree, re-encoded (round 4). An 80-byte record at an 80-byte stride crosses a 128-byte line for
@@ -221,11 +215,10 @@ enum {
     // behind them, never touched by the per-pass / per-bounce clears (round 3 kept these at words 32 and 64, i.e. INSIDE the ticket
     // lines: wf_advance's ticket reset wiped the census before the host could read it, and the packet policy never engaged)
     WF_CNT_CENSUS = WF_CNT_WORDS,       // 2 x u64: packet trips, lanes served (wf_extend_packet / wf_extend_wide_packet)
-    WF_CNT_DIAG = WF_CNT_CENSUS + 8,    // 32 x u64: development census words (-DRT_DIAG builds)
-    WF_CNT_ALLOC_WORDS = WF_CNT_DIAG + 64
+    WF_CNT_ALLOC_WORDS = WF_CNT_CENSUS + 4
 };
-static_assert(WF_CNT_XCD + 7 * WF_CNT_XCD_STRIDE < WF_CNT_WORDS && WF_CNT_CENSUS >= WF_CNT_WORDS && WF_CNT_DIAG >= WF_CNT_CENSUS + 4 && (WF_CNT_CENSUS % 2) == 0 && (WF_CNT_DIAG % 2) == 0,
-              "census / diag words must not overlap the ticket lines and must be 8-byte aligned");
+static_assert(WF_CNT_XCD + 7 * WF_CNT_XCD_STRIDE < WF_CNT_WORDS && WF_CNT_CENSUS >= WF_CNT_WORDS && (WF_CNT_CENSUS % 2) == 0,
+              "census words must not overlap the ticket lines and must be 8-byte aligned");
 // wf_shade appends a bounce's survivors to WF_STRIPES sub-queues instead of one: a returning atomic on ONE address completes
 // every ~13 ns chip-wide, and one per wave (64 rays) of a 30 M-ray bounce made that single counter the whole kernel's clock
 // (6.3 ms of 6.3 ms; profiles/r02_shade_atomic.txt). Wave slot w of the input queue (positions 64w..64w+63) appends to
@@ -264,10 +257,9 @@ struct WfLaunch {
     float *fb;               // width*height*3
     void *stack_overflow;    // wf_extend's evicted traversal-stack frames: [RT_MAX_STACK][stack_stride] records of 16 B
     uint32_t stack_stride;   // = threads of the wf_extend grid
-    uint32_t *counters;      // WF_CNT_*: IN = rays of this bounce, TICKET = wf_extend's work ticket, SLOTS = wave slots of the launch
+    uint32_t *counters;      // WF_CNT_*: IN = rays of this bounce, TICKET = the packet kernels' work ticket, SLOTS = wave slots of the launch
                              // that wrote paths_in (0: paths_in is dense, as wf_generate leaves it)
     uint32_t *stripes;       // WF_STRIPE_BUF_WORDS: the sub-queue fill counters of the running wf_shade, then run_start[] of paths_in
-    void *diag;              // development census (-DRT_DIAG), 32 x u64, else unused
     const uint32_t *order;   // optional: position q processes queue slot order[q] & WF_ORDER_SLOT_MASK (coherence sort; extend AND shade); null = identity.
                              // Bits 30-31 carry the ray's NEXT sampler class (top bits of WfPath's path word) through the sort: wf_shade's lane assignment reads them
     uint32_t *sort_keys[2];  // sort workspace: keys / slot indices, double buffered
@@ -279,7 +271,7 @@ struct WfLaunch {
     uint32_t global_best;    // 0: the reference's traversal order and pruning (parity mode); 1: prune against the global best
                              // (RT_FLAG_GLOBAL_BEST, production traversal: a subset of the reference's node visits)
     uint32_t order_classed;  // `order` came through the ray-order sort and carries the class bits; 0: identity-like order (no sort ran), slots only
-    uint32_t sort_mode;      // 0 off, 1 cell+octant, 2 coarse cell + direction code, 3 octant+cell, 4 cell+octant+sub-cone (default) (RT_WF_SORT)
+    uint32_t sort_mode;      // 0: no ray-order sort; 1: sort the secondary bounces by wf_sort_keys' key (octant, 64^3 cell, sub-cone)
     size_t sort_temp_bytes;
     DevStats *stats;         // may be null
 };

@@ -71,10 +71,6 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const De
     s_gam[threadIdx.x] = S.lut_gamma[threadIdx.x];
     __syncthreads();
 
-#ifdef RT_DIAG
-    if (STATS && threadIdx.x == 0 && blockIdx.x == 0)
-        g_diag = L.stats;
-#endif
     LaneStats<STATS> st;
     Rng<MODE> rng;
     RT_DECLARE_STACK(stk, LDS_DEPTH, s_stack);
@@ -142,8 +138,6 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const De
                 break;
             if (__popcll(tm) < TRAV_MIN_LANES && __ballot(state == ST_READY) != 0ull)
                 break;
-            DIAG(0, 1);
-            DIAG(1, (unsigned long long)__popcll(tm));
             if (state == ST_TRAV) {
                 trav_step<STATS>(T, S.scene, stk, EPS, st);
                 if (T.cur == T_DONE)
@@ -152,10 +146,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const De
         }
 
         // ---- trace_ray's hit / miss branch (:602-604) and shade (:555-591) for the lanes whose traversal finished
-        DIAG(11, 1);
         if (state == ST_READY) {
-            DIAG(9, 1);
-            DIAG_LANES(10);
             Hit h = T.best;
             if (S.n_prims)
                 prims_closest(S, T.o, T.d, h);
@@ -216,9 +207,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const De
             }
         }
     }
-#ifndef RT_DIAG
     st.flush(L.stats);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------- probe kernels

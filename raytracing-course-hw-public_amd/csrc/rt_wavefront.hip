@@ -48,15 +48,9 @@ namespace {
 #define RT_SHADE_BLOCKS_PER_CU 8 /* grid of the grid-stride kernels (wf_shade, wf_extend_prims) */
 #endif
 #ifndef RT_SHADE_LDS_DEPTH
-#ifndef RT_SHADE_RECLASS
-#define RT_SHADE_RECLASS 1 /* wf_shade hands its block's hits to the lanes sorted by sampler class */
-#endif
 #define RT_SHADE_LDS_DEPTH 4 /* only the light-BVH traversal of bvh_mix_dist::pdf uses a stack in wf_shade */
 #endif
 using ShadeStack = StackMemT<RT_SHADE_LDS_DEPTH>;
-#ifndef RT_EXT_POP_ONCE
-#define RT_EXT_POP_ONCE 1 /* bounded unwind: one stack pop per trip instead of an inner loop until no lane unwinds */
-#endif
 #ifndef RT_EXT_CHUNK
 #define RT_EXT_CHUNK 64u /* queue positions a wave takes per ticket atomic (128 until the tickets were partitioned: with eight heads the atomics are cheap
                             and the last ticket of a part is one batch of work, not two: + 0.7 % S-sponza, + 1 % S-10M, profiles/r03_variants.txt item 21) */
@@ -77,10 +71,6 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const D
     const V3 cam_pos = ld3(S.cam_pos), cam_right = ld3(S.cam_right), cam_up = ld3(S.cam_up), cam_fwd = ld3(S.cam_fwd);
     if (blockIdx.x == 0 && threadIdx.x == 0)
         L.counters[WF_CNT_IN] = L.n_paths; // the first bounce's queue is the identity: slot i holds path i
-#ifdef RT_DIAG
-    if (STATS && threadIdx.x == 0 && blockIdx.x == 0)
-        g_diag = (DevStats *)L.diag; // set a launch ahead of the kernels that count
-#endif
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
         const uint32_t lp = i / L.pass_samples;
         const uint32_t ds = i - lp * L.pass_samples;
@@ -143,11 +133,7 @@ DEV void leaf_batch(Trav &T, const DevBvh &bvh, bool at_leaf, uint16_t *s_owner,
     }
     __threadfence_block();
     const uint32_t k0 = T.cur & RT_LEAF_BEGIN_MASK;
-    DIAG(13, 1);
-    DIAG(14, (unsigned long long)__popcll(__ballot(at_leaf)));
-    DIAG(16, total);
     for (uint32_t q0 = 0; q0 < total; q0 += 64u) { // wave-uniform trip count
-        DIAG(15, 1);
         const uint32_t q = q0 + lane;
         const bool valid = q < total;
         const uint32_t ow = valid ? (uint32_t)s_owner[q] : 0u;
@@ -162,7 +148,6 @@ DEV void leaf_batch(Trav &T, const DevBvh &bvh, bool at_leaf, uint16_t *s_owner,
             V3 xs;
             if (tri_hit(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), o, d, EPS, xs)) {
                 const unsigned long long key = ((unsigned long long)__float_as_uint(xs.z) << 32) | (unsigned long long)kk;
-                DIAG(17, 1);
                 atomicMin(&s_min[src], key);
                 __threadfence_block();
                 if (s_min[src] == key) // this pair leads its leaf so far: publish its barycentrics
@@ -205,10 +190,6 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
     float2 *s_bc = s_bc_all[wave];
     LaneStats<STATS> st;
     RT_DECLARE_RING_STACK_W(stk, DEPTH, WORDS, s_stack, L.stack_overflow, L.stack_stride);
-#ifdef RT_DIAG
-    if (STATS && threadIdx.x == 0 && blockIdx.x == 0)
-        g_diag = (DevStats *)L.diag;
-#endif
     const uint32_t n_in = L.counters[WF_CNT_IN];
     Trav T;
     T.cur = T_DONE;
@@ -217,19 +198,6 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
     bool exhausted = n_in == 0; // wave-uniform
     uint32_t q_lo = 0, q_hi = 0; // this wave's private range of queue positions
     TicketState tks = ticket_init();
-#ifdef RT_DIAG_CYCLES
-    // section census of the persistent loop (development build only, no other instrumentation): wave cycles between s_memtime stamps
-    unsigned long long dg_refill = 0, dg_node = 0, dg_leaf = 0, dg_pop = 0, dg_store = 0, dg_t = __builtin_amdgcn_s_memtime();
-    const unsigned long long dg_start = dg_t;
-#define DG_STAMP(acc)                                             \
-    do {                                                          \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        acc += now_ - dg_t;                                       \
-        dg_t = now_;                                              \
-    } while (0)
-#else
-#define DG_STAMP(acc) do { } while (0)
-#endif
     for (;;) {
         const bool idle = T.cur == T_DONE;
         const unsigned long long im = __ballot(idle);
@@ -255,9 +223,6 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
             }
             q_lo += (uint32_t)n_idle < avail ? (uint32_t)n_idle : avail;
         }
-        DIAG(12, 1);
-        DG_STAMP(dg_refill);
-#if RT_EXT_POP_ONCE
         // Bounded unwind: ONE stack pop per trip for every lane that has to unwind (a lane whose pop ends in a pruned far
         // child pops again next trip and sits out one node step: ~1 in 5 unwinding lanes). The unwind used to be a loop that
         // ran until no lane of the wave was left in T_POP: 1.2 iterations per trip at ~7 of 64 lanes, each a full LDS round
@@ -268,7 +233,6 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
         trav_pop_once<GB>(T, stk);
         if (was_live && T.cur == T_DONE)
             *reinterpret_cast<float4 *>(L.hits + slot) = make_float4(__uint_as_float(T.best.k), T.best.b, T.best.c, T.best.t);
-        DG_STAMP(dg_pop);
         const bool active = T.cur != T_DONE;
         const bool popping = T.cur == T_POP; // note: T_POP has the leaf bit set, it must be told apart first
         const bool at_leaf = active && !popping && (T.cur & RT_LEAF_FLAG) != 0 && RT_LEAF_CNT(T.cur) != 0;
@@ -281,55 +245,21 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
                 break;
             continue;
         }
-#else
-        const bool active = T.cur != T_DONE;
-        const bool at_leaf = active && (T.cur & RT_LEAF_FLAG) != 0 && RT_LEAF_CNT(T.cur) != 0;
-        const bool stepper = active && !at_leaf; // inner node, or a big leaf walked triangle by triangle
-        const unsigned long long lm = __ballot(at_leaf), sm = __ballot(stepper);
-        if ((lm | sm) == 0ull) {
-            if (exhausted)
-                break;
-            continue;
-        }
-#endif
         if (sm == 0ull || __popcll(lm) >= RT_EXT_LEAF_MIN) {
             leaf_batch<STATS>(T, S.scene, at_leaf, s_owner, s_min, s_bc, st);
-            DG_STAMP(dg_leaf);
         } else {
             // the common wave: every stepping lane is on an inner node with the fast-division guarantees -> straight-line
             // node step; a wave with a big-leaf walker or a guarded ray takes the general step
             const bool plain = (T.cur & RT_LEAF_FLAG) == 0 && T.fast;
             if (__ballot(stepper && !plain) == 0ull) {
                 if (stepper) {
-                    DIAG(18, 1);
-                    DIAG_LANES(19);
                     trav_step_inner_fast<STATS, GB>(T, S.scene, stk, EPS, st);
                 }
             } else if (stepper) {
                 trav_step_core<STATS, GB>(T, S.scene, stk, EPS, st);
             }
-            DG_STAMP(dg_node);
         }
-#if !RT_EXT_POP_ONCE
-        trav_pop_wave<GB>(T, stk); // unwind after a leaf batch or a node step, all lanes of the wave together
-        DG_STAMP(dg_pop);
-        if (active && T.cur == T_DONE)
-            *reinterpret_cast<float4 *>(L.hits + slot) = make_float4(__uint_as_float(T.best.k), T.best.b, T.best.c, T.best.t);
-        DG_STAMP(dg_store);
-#endif
     }
-#ifdef RT_DIAG_CYCLES
-    if ((threadIdx.x & 63u) == 0u && L.diag) {
-        unsigned long long *dg = reinterpret_cast<unsigned long long *>(L.diag);
-        atomicAdd(dg + 20, dg_refill);
-        atomicAdd(dg + 21, dg_node);
-        atomicAdd(dg + 22, dg_leaf);
-        atomicAdd(dg + 23, dg_pop);
-        atomicAdd(dg + 24, dg_store);
-        atomicAdd(dg + 25, __builtin_amdgcn_s_memtime() - dg_start);
-        atomicAdd(dg + 26, 1ull);
-    }
-#endif
     st.flush(L.stats);
 }
 
@@ -353,10 +283,6 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
     RT_DECLARE_RING_STACK_W(stk, DEPTH, WORDS, s_stack, L.stack_overflow, L.stack_stride);
     const uint32_t n_in = L.counters[WF_CNT_IN];
     const uint32_t lane = threadIdx.x & 63u;
-#ifdef RT_DIAG
-    if (STATS && threadIdx.x == 0 && blockIdx.x == 0)
-        g_diag = (DevStats *)L.diag;
-#endif
     Trav T;
     T.o = T.d = T.r = mk(0.f, 0.f, 0.f);
     T.cur = T_DONE;
@@ -396,9 +322,6 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
                     break;
                 ++n_trips; // how coherent the packets are: the host keeps or drops this kernel on lanes per trip
                 n_lanes += (uint32_t)__popcll(mm);
-                DIAG(9, 1); // development census (tools/diag_packet.py): trips, lanes served, leaf trips
-                DIAG(10, (unsigned long long)__popcll(mm));
-                DIAG(11, (target & RT_LEAF_FLAG) ? 1ull : 0ull);
                 if ((target & RT_LEAF_FLAG) == 0u) {
                     // the record's address must stay a scalar: inside `if (mine)` the compiler knows T.cur == target and would
                     // otherwise address the node through the lane's own T.cur (a vector load per lane)
@@ -478,9 +401,7 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
     __shared__ float s_gam[256];
     __shared__ uint32_t s_stack[STACK_LDS_DWORDS_FOR(RT_SHADE_LDS_DEPTH)];
     __shared__ float4 s_lights[LIGHTS_LDS ? RT_SHADE_LIGHTS_F4 : 1];
-#if RT_SHADE_RECLASS
     __shared__ uint2 s_perm[4][256]; // per wave: (queue position, queue slot) of its 256 positions, sorted by sampler class
-#endif
     LightTabs LT = light_tabs_global(S);
     if (LIGHTS_LDS) {
         const uint32_t n_node_f4 = 4u * (S.lights.lds_inner - 1u), n_tri_f4 = 3u * S.lights.n_tris;
@@ -494,12 +415,6 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
     }
     s_lin[threadIdx.x] = S.lut_linear[threadIdx.x];
     s_gam[threadIdx.x] = S.lut_gamma[threadIdx.x];
-#ifdef RT_DIAG_SHADE
-    if (threadIdx.x < 4u * SD_N)
-        (&g_sd_cyc[0][0])[threadIdx.x] = 0ull, (&g_sd_lanes[0][0])[threadIdx.x] = 0ull;
-    if ((threadIdx.x & 63u) == 0u)
-        g_sd_t[threadIdx.x >> 6] = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();
     LaneStats<STATS> st;
     RT_DECLARE_STACK(stk, RT_SHADE_LDS_DEPTH, s_stack);
@@ -526,9 +441,7 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
             h.k = __float_as_uint(hq.x), h.b = hq.y, h.c = hq.z, h.t = hq.w;
             if (h.k != RT_NONE)
                 depth_left -= 1; // shade(..., max_depth - 1)
-            SD_STAMP(SD_LOAD);
             const ShadeResult sr = shade_hit<Rng<RT_RNG_DEVICE>, STATS, ENV>(S, LT, h, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), rng, has_lights, stk, s_lin, s_gam, st);
-            SD_STAMP(SD_BRDF);
             bool terminal = sr.terminal;
             V3 term = sr.term;
             if (sr.push) { // emission + trace_ray(...) * scl (raytracer.h:588-590), folded when the path ends
@@ -547,7 +460,6 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
                 // dependent loads (14 % of this kernel's cycles). Leave the innermost value and the frame count.
                 L.sample_out[path] = RtF4{term.x, term.y, term.z, __uint_as_float(nb)};
                 st.sample();
-                SD_STAMP(SD_FOLD);
             } else {
                 survive = true;
                 st.cast();
@@ -576,9 +488,7 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
                 *reinterpret_cast<uint4 *>(rw + 3) = nrng;
             }
         }
-        SD_STAMP(SD_STORE);
     };
-#if RT_SHADE_RECLASS
     // Which of shade()'s three samplers a hit runs is decided by its path's next draws alone (alpha coin, technique coin, mix pick:
     // raytracer.h:559,565,386): whoever wrote the path record left that class in the top bits of its path word, and the ray-order pass carried it along
     // in the top bits of `order`. A WAVE takes 256 queue positions at a time and hands them to its lanes sorted by class (a counting sort
@@ -622,28 +532,13 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
         }
         __builtin_amdgcn_wave_barrier();
     }
-#else
-    // wave-uniform trip count: the ballots in shade_wave must see the whole wave
-    for (uint32_t base = blockIdx.x * blockDim.x; base < n_in; base += gridDim.x * blockDim.x) {
-        const uint32_t jq = base + threadIdx.x; // queue position: where wf_extend left this ray's hit
-        shade_wave(jq, jq < n_in ? (L.order ? L.order[jq] & WF_ORDER_SLOT_MASK : jq) : 0u, jq >> 6);
-    }
-#endif
-#ifdef RT_DIAG_SHADE
-    __syncthreads();
-    if (threadIdx.x < 4u * SD_N && L.diag) { // census words 0..11: wave cycles per section, 12..23: lane-weighted cycles (summed over waves)
-        unsigned long long *dg = reinterpret_cast<unsigned long long *>(L.diag);
-        atomicAdd(dg + (threadIdx.x % SD_N), (&g_sd_cyc[0][0])[threadIdx.x]);
-        atomicAdd(dg + SD_N + (threadIdx.x % SD_N), (&g_sd_lanes[0][0])[threadIdx.x]);
-    }
-#endif
     st.flush(L.stats);
 }
 
-// Ray-ordering key for secondary bounces: Morton code of the origin's cell in a 64^3 grid over the scene bounds (18 bits)
-// followed by the direction octant (3 bits). Rays that start close together and head the same way end up in the same
-// wave of wf_extend, so their gathers touch the same nodes (cache lines, L2 residency). Ordering never changes a result:
-// every path's arithmetic is independent of where it sits in the queue.
+// Ray-ordering key for secondary bounces, 24 bits: the direction octant (3 bits), the Morton code of the origin's cell in a 64^3 grid
+// over the scene bounds (18 bits), then which of the octant's 8 sub-cones the direction lies in (3 bits). Rays that start close together
+// and head the same way end up in the same wave of wf_extend, so their gathers touch the same nodes (cache lines, L2 residency).
+// Ordering never changes a result: every path's arithmetic is independent of where it sits in the queue.
 DEV uint32_t spread3(uint32_t v) { // 6 bits -> every third bit
     v &= 63u;
     v = (v | (v << 8)) & 0x0300Fu;
@@ -688,30 +583,9 @@ __global__ __launch_bounds__(256) void wf_sort_keys(const DevScene S, const WfLa
         const uint32_t cx = (uint32_t)fminf(fmaxf(fx * 64.0f, 0.0f), 63.0f), cy = (uint32_t)fminf(fmaxf(fy * 64.0f, 0.0f), 63.0f), cz = (uint32_t)fminf(fmaxf(fz * 64.0f, 0.0f), 63.0f);
         const uint32_t morton = spread3(cx) | (spread3(cy) << 1) | (spread3(cz) << 2);
         const uint32_t oct = (r0.w < 0.0f ? 1u : 0u) | (r1.x < 0.0f ? 2u : 0u) | (r1.y < 0.0f ? 4u : 0u);
-        uint32_t key = (morton << 3) | oct; // mode 1: 64^3 cell, then octant
-        if (L.sort_mode == 2) { // 16^3 cell (12 bits), then a 9-bit direction code (3 bits per component)
-            const uint32_t dxq = (uint32_t)fminf(fmaxf((r0.w * 0.5f + 0.5f) * 8.0f, 0.0f), 7.0f), dyq = (uint32_t)fminf(fmaxf((r1.x * 0.5f + 0.5f) * 8.0f, 0.0f), 7.0f),
-                           dzq = (uint32_t)fminf(fmaxf((r1.y * 0.5f + 0.5f) * 8.0f, 0.0f), 7.0f);
-            const uint32_t m16 = spread3(cx >> 2) | (spread3(cy >> 2) << 1) | (spread3(cz >> 2) << 2);
-            key = (m16 << 9) | (dxq << 6) | (dyq << 3) | dzq;
-        } else if (L.sort_mode == 3) { // octant first, then the 64^3 cell
-            key = (oct << 18) | morton;
-        } else if (L.sort_mode == 4) { // 64^3 cell, octant, then which of the octant's 8 sub-cones the direction lies in (24 bits)
-            const float ax = __builtin_fabsf(r0.w), ay = __builtin_fabsf(r1.x), az = __builtin_fabsf(r1.y);
-            const uint32_t sub = (ax > ay ? 1u : 0u) | (ay > az ? 2u : 0u) | (ax > az ? 4u : 0u);
-            key = (((morton << 3) | oct) << 3) | sub;
-        } else if (L.sort_mode == 5) { // octant, 64^3 cell, then the sub-cone (24 bits)
-            const float ax = __builtin_fabsf(r0.w), ay = __builtin_fabsf(r1.x), az = __builtin_fabsf(r1.y);
-            const uint32_t sub = (ax > ay ? 1u : 0u) | (ay > az ? 2u : 0u) | (ax > az ? 4u : 0u);
-            key = (oct << 21) | (morton << 3) | sub;
-        } else if (L.sort_mode == 6) { // octant, 128^3 cell, sub-cone (27 bits): a finer origin cell for trees far beyond the caches
-            const uint32_t fx7 = (uint32_t)fminf(fmaxf(fx * 128.0f, 0.0f), 127.0f), fy7 = (uint32_t)fminf(fmaxf(fy * 128.0f, 0.0f), 127.0f), fz7 = (uint32_t)fminf(fmaxf(fz * 128.0f, 0.0f), 127.0f);
-            const uint32_t m21 = (morton << 3) | (fx7 & 1u) | ((fy7 & 1u) << 1) | ((fz7 & 1u) << 2); // the 64^3 code refined by one more bit per axis
-            const float ax = __builtin_fabsf(r0.w), ay = __builtin_fabsf(r1.x), az = __builtin_fabsf(r1.y);
-            const uint32_t sub = (ax > ay ? 1u : 0u) | (ay > az ? 2u : 0u) | (ax > az ? 4u : 0u);
-            key = (oct << 24) | (m21 << 3) | sub;
-        }
-        L.sort_keys[0][j] = key;
+        const float ax = __builtin_fabsf(r0.w), ay = __builtin_fabsf(r1.x), az = __builtin_fabsf(r1.y);
+        const uint32_t sub = (ax > ay ? 1u : 0u) | (ay > az ? 2u : 0u) | (ax > az ? 4u : 0u); // which of the octant's 8 sub-cones
+        L.sort_keys[0][j] = (oct << 21) | (morton << 3) | sub;
         L.sort_vals[0][j] = val;
     }
 }
@@ -940,7 +814,7 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             WF_LAUNCH(wf_sort_keys, dim3(kb > 0 ? kb : 1), block, 0, stream, S, L, sort ? 0 : 1, bound);
             if (sort) {
                 size_t tmp = L.sort_temp_bytes;
-                hipError_t se = rocprim::radix_sort_pairs(L.sort_temp, tmp, L.sort_keys[0], L.sort_keys[1], L.sort_vals[0], L.sort_vals[1], (size_t)bound, 0u, L.sort_mode == 6 ? 27u : L.sort_mode >= 4 ? 24u : 21u, stream);
+                hipError_t se = rocprim::radix_sort_pairs(L.sort_temp, tmp, L.sort_keys[0], L.sort_keys[1], L.sort_vals[0], L.sort_vals[1], (size_t)bound, 0u, 24u /* wf_sort_keys' key */, stream);
                 if (se != hipSuccess)
                     return se;
             }

@@ -134,12 +134,11 @@ def test_queue_shapes_match_oracle(pairs, gpu, shape):
     """wf_shade appends to 64 sub-queues whose regions are whole wave slots; the next bounce maps the dense ray index back to
     a slot (with a sort from 4096 rays up, directly below). Path counts below one wave, not multiples of 64, exactly at and
     across the 4096-ray sort threshold (a queue that shrinks below it between bounces) all give the oracle's framebuffer
-    bit for bit, with every ray-order key (rt_params.sort_mode, RT_SORT_*; OCTANT_CELL_CONE is what AUTO picks) and with sorting off."""
+    bit for bit, with the ray-order sort (rt_params.sort_mode: OCTANT_CELL_CONE, the key AUTO picks), with AUTO and with sorting off."""
     dev, orc, _ = pairs["room_manylights"]
     W, H, SPP = shape
     ofb, ost = orc.run_raytracer(W, H, SPP, rng_mode=gpu.RT_RNG_DEVICE, seed=99)
-    all_keys = (gpu.RT_SORT_OCTANT_FINE_CELL_CONE, gpu.RT_SORT_OCTANT_CELL_CONE, gpu.RT_SORT_CELL_OCTANT_CONE, gpu.RT_SORT_OCTANT_CELL, gpu.RT_SORT_COARSE_CELL_DIR, gpu.RT_SORT_CELL_OCTANT, gpu.RT_SORT_OFF,
-                gpu.RT_SORT_AUTO)
+    all_keys = (gpu.RT_SORT_OCTANT_CELL_CONE, gpu.RT_SORT_OFF, gpu.RT_SORT_AUTO)
     for sort in all_keys if shape == (96, 50, 2) else (gpu.RT_SORT_OCTANT_CELL_CONE, gpu.RT_SORT_OFF):
         gfb, gst = dev.run_raytracer(W, H, SPP, rng_mode=gpu.RT_RNG_DEVICE, seed=99, counters=True, sort_mode=sort)
         assert np.array_equal(gfb.view(np.uint32), ofb.view(np.uint32)), (shape, sort)
@@ -149,7 +148,7 @@ def test_queue_shapes_match_oracle(pairs, gpu, shape):
 @pytest.mark.parametrize("name", ["room_textured", "room_manylights"])
 def test_class_sorted_shading_windows_match_oracle(pairs, gpu, name):
     """From 2 M sorted rays up (8 blocks per CU x 1024 positions) a wave of wf_shade takes 256 queue positions at a time and hands them to its
-    lanes sorted by the sampler class the ray-order sort carried along (rt_wavefront.hip, RT_SHADE_RECLASS). Which lane shades a hit must not
+    lanes sorted by the sampler class the ray-order sort carried along (rt_wavefront.hip, wf_shade). Which lane shades a hit must not
     change a bit: 3.07 M paths (not a multiple of 256: the last window is ragged) against the oracle, framebuffer bit for bit and every event
     counter, with the counting and the plain kernel variants; sorting off takes the 64-position path over the same queue."""
     dev, orc, _ = pairs[name]
@@ -482,6 +481,9 @@ def test_errors_are_reported_not_thrown(gpu, sg):
         dev.run_raytracer(0, 8, 1)
     with pytest.raises(gpu.RtError):
         dev.run_raytracer(8, 8, 1, rng_mode=gpu.RT_RNG_REFERENCE, shard_count=2, shard_block=100)
+    with pytest.raises(gpu.RtError) as e:
+        dev.run_raytracer(8, 8, 1, sort_mode=2)  # a retired ray-order key: only AUTO, OFF and OCTANT_CELL_CONE remain
+    assert e.value.code == 1  # RT_ERR_INVALID_ARG
     dev.close()
     # non-finite vertex positions never reach a builder or a kernel (every build mode)
     for bad in (np.nan, np.inf, -np.inf):

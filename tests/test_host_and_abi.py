@@ -46,7 +46,7 @@ def test_struct_layouts_match_the_c_headers(rt, tmp_path):
         '#include <stdio.h>\n#include <stddef.h>\n#include "rt_abi.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
         "sizeof(rt_camera),sizeof(rt_texture_desc),sizeof(rt_material_desc),sizeof(rt_scene_desc),sizeof(rt_params),sizeof(rt_stats),"
         "offsetof(rt_scene_desc,camera),offsetof(rt_params,seed),sizeof(rt_primitive_desc),offsetof(rt_scene_desc,primitives),offsetof(rt_primitive_desc,rotation));"
-        'printf("%zu %zu %zu %zu %zu %zu %zu\\n",sizeof(rt_build_options),offsetof(rt_scene_desc,build),offsetof(rt_build_options,wide_order),offsetof(rt_params,sort_mode),'
+        'printf("%zu %zu %zu %zu %zu %zu %zu\\n",sizeof(rt_build_options),offsetof(rt_scene_desc,build),offsetof(rt_build_options,reserved1),offsetof(rt_params,sort_mode),'
         "offsetof(rt_params,max_paths),offsetof(rt_params,progress_user),offsetof(rt_stats,packet_passes));return 0;}\n"
     )
     exe = tmp_path / "sz"
@@ -56,7 +56,7 @@ def test_struct_layouts_match_the_c_headers(rt, tmp_path):
             ctypes.sizeof(abi.RtParams), ctypes.sizeof(abi.RtStats), abi.RtSceneDesc.camera.offset, abi.RtParams.seed.offset,
             ctypes.sizeof(abi.RtPrimitiveDesc), abi.RtSceneDesc.primitives.offset, abi.RtPrimitiveDesc.rotation.offset,
             # ABI 4: build options, tuning fields, progress callback, packet census
-            ctypes.sizeof(abi.RtBuildOptions), abi.RtSceneDesc.build.offset, abi.RtBuildOptions.wide_order.offset, abi.RtParams.sort_mode.offset,
+            ctypes.sizeof(abi.RtBuildOptions), abi.RtSceneDesc.build.offset, abi.RtBuildOptions.reserved1.offset, abi.RtParams.sort_mode.offset,
             abi.RtParams.max_paths.offset, abi.RtParams.progress_user.offset, abi.RtStats.packet_passes.offset]
     assert got == want
 
@@ -99,11 +99,18 @@ def test_sub_queue_regions_tile_the_queue(tmp_path):
 
 
 def test_no_gpu_fails_loudly(rt, sg):
-    """The product never falls back to a CPU path: without a HIP device rt_create reports RT_ERR_NO_DEVICE."""
+    """The product never falls back to a CPU path: without a HIP device rt_create reports RT_ERR_NO_DEVICE. Its argument checks come
+    first, on every machine: a non-zero reserved rt_build_options field or an undefined build_flags bit (8 was a development flag)
+    is RT_ERR_INVALID_ARG before any device is looked for."""
+    sc = sg.boxes_scene(n_boxes=1, seed=1)
+    for bad in ({"reserved0": 1}, {"reserved1": 1}, {"reserved": 1}, {"build_flags": 8}, {"build_flags": 64}):
+        with pytest.raises(rt.RtError) as e:
+            rt.DeviceScene(sc, **bad)
+        assert e.value.code == 1, bad
     if rt.device_count() > 0:
         pytest.skip("a GPU is present")
     with pytest.raises(rt.RtError) as e:
-        rt.DeviceScene(sg.boxes_scene(n_boxes=1, seed=1))
+        rt.DeviceScene(sc)
     assert e.value.code == 2 and "no CPU fallback" in str(e.value)
 
 

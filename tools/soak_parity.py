@@ -35,7 +35,7 @@ def main():
     n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 20261005)
     sg = rt.scenegen
-    sorts = (rt.RT_SORT_AUTO, rt.RT_SORT_OFF, rt.RT_SORT_CELL_OCTANT, rt.RT_SORT_OCTANT_CELL_CONE, rt.RT_SORT_OCTANT_FINE_CELL_CONE)
+    sorts = (rt.RT_SORT_AUTO, rt.RT_SORT_OFF, rt.RT_SORT_OCTANT_CELL_CONE)
     worst_prod = 0
     big = os.environ.get("SOAK_BIG") == "1"  # trees far beyond the caches: 2e5 - 3e6 triangles, every 16th 256-pixel span of a 512 x 512 image against the oracle
     only = int(os.environ.get("SOAK_ONLY", "-1"))  # replay one case of the sequence (same draws), with details on a production difference
