@@ -45,7 +45,8 @@ extern "C" {
                              4: every tuning knob is a field (rt_build_options, rt_params.sort_mode / packet_mode / max_paths ...): the library
                                 reads no environment variable; progress callback; packet census in rt_stats. Still 4 after the development
                                 options were retired (two rt_build_options fields became reserved, unused RT_SORT_* / RT_BUILD_* values are
-                                refused): the binary layout and the meaning of every value that remains are unchanged */
+                                refused): the binary layout and the meaning of every value that remains are unchanged. Still 4 after
+                                rt_view / rt_render_views / rt_render_views_rgb8 were added: new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
 
@@ -362,6 +363,28 @@ void rt_tonemap_rgb8(const float *rgb, size_t n_pixels, uint8_t *out_rgb8);
  * against, the host libm's powf when the first call is made; if that verification fails the call returns an error
  * (no approximation is ever substituted). rt_film_rgb8 applies the device film to a caller-supplied host array. */
 int rt_render_rgb8(rt_scene *scene, const rt_params *params, uint8_t *rgb8, rt_stats *stats);
+
+/* Several camera views of one built scene in one call (turntables, stereo pairs, cube maps, multi-view datasets): no rebuild and
+ * no re-upload of the BVH, the triangles or the texel pool per viewpoint. A view changes the camera and the RNG seed only.
+ *   Output: view-major, fb[v][y][x][3] (rgb8: 3 bytes per pixel), n_views * width * height pixels. width, height, samples, rng_mode,
+ *   flags, the tuning fields and progress are shared by all views and mean what they mean for rt_render; rt_params.seed is not read.
+ *   Contract, bit for bit: view v equals rt_render / rt_render_rgb8 on a scene created from the same descriptor with
+ *   camera = views[v].camera, rendered with seed = views[v].seed, in every mode (wavefront or megakernel, binary or wide tree, reference
+ *   RNG). The scene's own camera is not changed: a later rt_render uses the creation camera. What the loaders placed relative to the
+ *   creation camera stays where it is: the light triangle of rt_loaded_add_light_triangle does not follow the views.
+ *   Sharding: shard_index / shard_count / shard_block select blocks of the view-major virtual image (n_views * height rows). In
+ *   RT_RNG_REFERENCE mode, where one 256-pixel span is one sequential RNG stream of ONE view, n_views > 1 refuses shard_count > 1.
+ *   Errors: RT_ERR_INVALID_ARG for n_views == 0, views == NULL, a non-zero reserved field or n_views * width * height >= 2^31;
+ *   RT_ERR_UNSUPPORTED where rt_render would refuse the mode (a RT_BUILD_WIDE scene with the megakernel or the reference RNG).
+ *   ray_depth == 0 leaves the buffer untouched, as in rt_render. */
+typedef struct rt_view {
+    rt_camera camera;  /* as rt_scene_desc.camera */
+    uint32_t reserved; /* 0 */
+    uint64_t seed;     /* RT_RNG_DEVICE stream seed of this view (rt_params.seed is not read) */
+} rt_view;             /* 64 bytes */
+int rt_render_views(rt_scene *scene, const rt_params *params, const rt_view *views, uint32_t n_views, float *fb_rgb, rt_stats *stats);
+int rt_render_views_rgb8(rt_scene *scene, const rt_params *params, const rt_view *views, uint32_t n_views, uint8_t *rgb8, rt_stats *stats);
+
 int rt_film_rgb8(rt_scene *scene, const float *rgb, size_t n_pixels, uint8_t *out_rgb8);
 
 const char *rt_last_error(void);

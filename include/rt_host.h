@@ -41,6 +41,10 @@ int rt_loaded_add_light_triangle(rt_loaded_scene *s, const float rel[9], float i
  * does: the textures are cut down to their first texel. CLI: RT_USE_TEXTURES=0. */
 int rt_loaded_disable_textures(rt_loaded_scene *s);
 const rt_scene_desc *rt_loaded_desc(const rt_loaded_scene *s);
+/* Every camera of the file, for rt_render_views: glTF: every node with a camera, in the loader's visit order (scene.h:234-255), each
+ * computed as the reference computes the one it keeps (own aspectRatio, else the load's aspect); the last is desc.camera, bit for bit.
+ * scene-txt: the file's one camera. *n = the number of cameras; the first min(*n, cap) are written to `out` (NULL when cap = 0). */
+int rt_loaded_cameras(const rt_loaded_scene *s, rt_camera *out, uint32_t cap, uint32_t *n);
 void rt_loaded_free(rt_loaded_scene *s);
 
 /* Image::write (image.h:34-38): binary PPM "P6\n<w> <h>\n255\n" + rgb8. Creates parent directories like

@@ -48,8 +48,10 @@ from ._ctypes_abi import (
     RT_RNG_DEVICE,
     RT_RNG_REFERENCE,
     DescHolder,
+    RtCamera,
     RtParams,
     RtSceneDesc,
+    RtView,
     RtStats,
     bind,
     c_u8_p,
@@ -108,6 +110,15 @@ class LoadedScene:
         _check(lib().rt_loaded_info(self._h, C.byref(w), C.byref(h), C.byref(s), C.byref(l)))
         return {"width": w.value, "height": h.value, "samples": s.value, "ignored_lights": l.value}
 
+    def cameras(self) -> list:
+        """Every camera of the file as scenegen.Camera (rt_loaded_cameras): glTF camera nodes in the loader's visit order (the last is
+        the scene's camera, the one the reference keeps), or the one camera of a scene-txt file."""
+        n = C.c_uint32()
+        _check(lib().rt_loaded_cameras(self._h, None, 0, C.byref(n)))
+        arr = (RtCamera * max(1, n.value))()
+        _check(lib().rt_loaded_cameras(self._h, arr, n.value, C.byref(n)))
+        return [_camera_from_c(arr[i]) for i in range(n.value)]
+
     def set_env_map(self, image_path: str, intensity: float = 1.0) -> None:
         """main.cpp:28-31 under USE_ENV_MAP: scene.bg = Texture::load_img(image_path), bg_color = intensity (rt_loaded_set_env_map)."""
         _check(lib().rt_loaded_set_env_map(self._h, os.fsencode(image_path), C.c_float(intensity)))
@@ -133,6 +144,36 @@ class LoadedScene:
             self.close()
         except Exception:
             pass
+
+
+def _camera_from_c(c: RtCamera) -> "scenegen.Camera":
+    return scenegen.Camera(
+        position=np.array(list(c.position), dtype=np.float32),
+        right=np.array(list(c.right), dtype=np.float32),
+        up=np.array(list(c.up), dtype=np.float32),
+        forward=np.array(list(c.forward), dtype=np.float32),
+        fov_x=float(np.float32(c.fov_x)),
+    )
+
+
+def make_views(cameras, seeds):
+    """rt_view[] of scenegen.Camera objects (or anything with position / right / up / forward / fov_x) and one seed per camera."""
+    cameras = list(cameras)
+    if np.ndim(seeds) == 0:
+        seeds = [int(seeds)] * len(cameras)
+    seeds = list(seeds)
+    if len(seeds) != len(cameras):
+        raise ValueError(f"{len(cameras)} cameras but {len(seeds)} seeds")
+    views = (RtView * max(1, len(cameras)))()
+    for v, (cam, seed) in enumerate(zip(cameras, seeds)):
+        for k in range(3):
+            views[v].camera.position[k] = np.float32(cam.position[k])
+            views[v].camera.right[k] = np.float32(cam.right[k])
+            views[v].camera.up[k] = np.float32(cam.up[k])
+            views[v].camera.forward[k] = np.float32(cam.forward[k])
+        views[v].camera.fov_x = np.float32(cam.fov_x)
+        views[v].seed = int(seed)
+    return views
 
 
 def parse_gltf_scene(path: str, aspect: float) -> LoadedScene:
@@ -286,6 +327,47 @@ class DeviceScene:
         img = out if out is not None else np.zeros((height, width, 3), dtype=np.uint8)
         assert img.dtype == np.uint8 and img.flags["C_CONTIGUOUS"] and img.size == width * height * 3
         _check(lib().rt_render_rgb8(self._h, C.byref(p), img.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return img, st.as_dict()
+
+    def run_raytracer_views(
+        self,
+        width: int,
+        height: int,
+        samples: int,
+        cameras,
+        seeds,
+        rgb8: bool = False,
+        rng_mode: int = RT_RNG_DEVICE,
+        shard_index: int = 0,
+        shard_count: int = 1,
+        shard_block: int = 0,
+        out: Optional[np.ndarray] = None,
+        device_fb: int = 0,
+        counters: bool = False,
+        megakernel: bool = False,
+        global_best: bool = False,
+        **tuning,
+    ):
+        """Several camera views of this scene in one call (rt_render_views, or rt_render_views_rgb8 with `rgb8`): `cameras` are
+        scenegen.Camera objects, `seeds` one RT_RNG_DEVICE seed per camera (or one for all). Returns ((K, H, W, 3) float32 linear
+        framebuffers or uint8 images, or None with `device_fb`, stats dict). View v is bit for bit run_raytracer(...) of a scene created
+        with camera v and seed v. Other arguments as run_raytracer."""
+        cameras = list(cameras)
+        views = make_views(cameras, seeds)
+        k = len(cameras)
+        p = RtParams(width, height, samples, rng_mode, 0, shard_index, shard_count, shard_block,
+                     (RT_FLAG_COUNTERS if counters else 0) | (RT_FLAG_MEGAKERNEL if megakernel else 0) | (RT_FLAG_GLOBAL_BEST if global_best else 0))
+        keep_cb = _apply_tuning(p, tuning)  # noqa: F841
+        st = RtStats()
+        fn = lib().rt_render_views_rgb8 if rgb8 else lib().rt_render_views
+        if device_fb:
+            p.flags |= RT_FLAG_DEVICE_FB
+            _check(fn(self._h, C.byref(p), views, k, C.c_void_p(device_fb), C.byref(st)))
+            return None, st.as_dict()
+        dt = np.uint8 if rgb8 else np.float32
+        img = out if out is not None else np.zeros((k, height, width, 3), dtype=dt)
+        assert img.dtype == dt and img.flags["C_CONTIGUOUS"] and img.size == k * width * height * 3
+        _check(fn(self._h, C.byref(p), views, k, img.ctypes.data_as(C.c_void_p), C.byref(st)))
         return img, st.as_dict()
 
     def film_rgb8(self, fb: np.ndarray) -> np.ndarray:
@@ -459,6 +541,7 @@ __all__ = [
     "parse_gltf_scene",
     "parse_scene_txt",
     "load_scene",
+    "make_views",
     "png_decode",
     "scenegen",
     "tonemap",

@@ -58,6 +58,10 @@ class RtCamera(C.Structure):
     ]
 
 
+class RtView(C.Structure):  # rt_render_views: one camera view (64 bytes)
+    _fields_ = [("camera", RtCamera), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class RtTextureDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgba8", c_u8_p)]
 
@@ -189,6 +193,8 @@ ABI_PROTOTYPES = {
     "rt_tonemap_rgb8": (None, [c_float_p, C.c_size_t, c_u8_p]),
     "rt_render_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.c_void_p, C.POINTER(RtStats)]),
     "rt_film_rgb8": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_u8_p]),
+    "rt_render_views": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtView), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_render_views_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtView), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_last_error": (C.c_char_p, []),
     "rt_source_stamp": (C.c_char_p, []),
     "rt_abi_version": (C.c_uint32, []),
@@ -205,6 +211,7 @@ HOST_PROTOTYPES = {
     "rt_scene_load": (C.c_int, [C.c_char_p, C.c_float, C.POINTER(C.c_void_p)]),
     "rt_loaded_info": (C.c_int, [C.c_void_p, c_u32_p, c_u32_p, c_u32_p, c_u32_p]),
     "rt_loaded_desc": (C.POINTER(RtSceneDesc), [C.c_void_p]),
+    "rt_loaded_cameras": (C.c_int, [C.c_void_p, C.POINTER(RtCamera), C.c_uint32, c_u32_p]),
     "rt_loaded_set_env_map": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
     "rt_loaded_add_light_triangle": (C.c_int, [C.c_void_p, c_float_p, C.c_float]),
     "rt_loaded_disable_textures": (C.c_int, [C.c_void_p]),

@@ -295,6 +295,7 @@ void load_impl(const std::filesystem::path &gltf_path, float ar, rt_loaded_scene
             cam.up[0] = u.x, cam.up[1] = u.y, cam.up[2] = u.z;
             cam.right[0] = r.x, cam.right[1] = r.y, cam.right[2] = r.z;
             cam.fov_x = std::atan(std::tan(fov_y / 2) * aspect_ratio) * 2;
+            res.cameras.push_back(cam); // the reference keeps only the last one (scene.h:234-255); rt_loaded_cameras returns them all
         }
         if (node.contains("mesh")) {
             const Value &mesh = root["meshes"][(size_t)node["mesh"].as_int()];
@@ -510,4 +511,12 @@ extern "C" int rt_loaded_add_light_triangle(rt_loaded_scene *s, const float rel[
 }
 
 extern "C" const rt_scene_desc *rt_loaded_desc(const rt_loaded_scene *s) { return s ? &s->desc : nullptr; }
+extern "C" int rt_loaded_cameras(const rt_loaded_scene *s, rt_camera *out, uint32_t cap, uint32_t *n) {
+    if (!s || !n || (cap && !out))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_loaded_cameras: null argument");
+    *n = (uint32_t)s->cameras.size();
+    for (uint32_t i = 0; i < *n && i < cap; ++i)
+        out[i] = s->cameras[i];
+    return RT_OK;
+}
 extern "C" void rt_loaded_free(rt_loaded_scene *s) { delete s; }

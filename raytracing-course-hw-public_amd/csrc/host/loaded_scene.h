@@ -14,6 +14,7 @@ struct rt_loaded_scene {
     std::vector<rt_texture_desc> textures;
     std::vector<uint8_t *> texels;
     std::vector<rt_primitive_desc> primitives; // scene-txt only
+    std::vector<rt_camera> cameras; // every camera of the file in the loader's visit order (rt_loaded_cameras); desc.camera is the last
     // scene-txt only: what the file itself says about the image (the CLI arguments win), and what was parsed but ignored
     uint32_t file_width = 0, file_height = 0, file_samples = 0, ignored_lights = 0, ignored_light_commands = 0;
     ~rt_loaded_scene() {

@@ -10,9 +10,12 @@
 // fields): RT_BVH_DEVICE=1, RT_BVH_WIDE=1 (production builds), RT_TRAVERSAL=global, RT_WF_SORT=<0|5> (off | sorted), RT_WF_PACKET=<0|1>,
 // RT_WF_MAX_PATHS=<n>, RT_DEVICE_BUILDER=lbvh, RT_PLOC_RADIUS=<n>. RT_VERBOSE: the reference's progress line "%d/%d     \r"
 // (raytracer.h:647) per finished pass, and a timing line on stderr.
+// RT_ALL_CAMERAS=1: render EVERY camera of the file (rt_loaded_cameras; the reference keeps only the last) in one rt_render_views_rgb8
+// call, all with RT_SEED, and write camera i to <stem>_<i><ext> of the output path.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -110,22 +113,50 @@ int main(int argc, char **argv) {
         p.progress = print_progress;
     // Image::set_pixel tone-maps as pixels finish (image.h:40-42): the film runs on the device too, unless the host
     // film is asked for (RT_FILM=host) or the device film declines (RT_ERR_UNSUPPORTED: libm failed its self-check)
-    std::vector<uint8_t> rgb8((size_t)width * height * 3, 0);
+    std::vector<rt_view> views; // RT_ALL_CAMERAS: one view per camera of the file; empty: the plain render of the scene's camera
+    if (env_on("RT_ALL_CAMERAS")) {
+        uint32_t n_cams = 0;
+        rt_loaded_cameras(loaded, nullptr, 0, &n_cams);
+        std::vector<rt_camera> cams(n_cams);
+        rt_loaded_cameras(loaded, cams.data(), n_cams, &n_cams);
+        if (cams.empty())
+            cams.push_back(desc.camera);
+        for (const rt_camera &c : cams) {
+            rt_view v{};
+            v.camera = c;
+            v.seed = p.seed;
+            views.push_back(v);
+        }
+    }
+    const size_t n_out = views.empty() ? 1 : views.size();
+    const size_t view_pixels = (size_t)width * height;
+    std::vector<uint8_t> rgb8(n_out * view_pixels * 3, 0);
     rt_stats st{};
     const char *film = std::getenv("RT_FILM");
-    int rc = (film && !std::strcmp(film, "host")) ? RT_ERR_UNSUPPORTED : rt_render_rgb8(scene, &p, rgb8.data(), &st);
+    int rc = RT_ERR_UNSUPPORTED;
+    if (!(film && !std::strcmp(film, "host")))
+        rc = views.empty() ? rt_render_rgb8(scene, &p, rgb8.data(), &st) : rt_render_views_rgb8(scene, &p, views.data(), (uint32_t)views.size(), rgb8.data(), &st);
     if (rc == RT_ERR_UNSUPPORTED) {
-        std::vector<float> fb((size_t)width * height * 3, 0.0f);
-        rc = rt_render(scene, &p, fb.data(), &st);
+        std::vector<float> fb(n_out * view_pixels * 3, 0.0f);
+        rc = views.empty() ? rt_render(scene, &p, fb.data(), &st) : rt_render_views(scene, &p, views.data(), (uint32_t)views.size(), fb.data(), &st);
         if (rc == RT_OK)
-            rt_tonemap_rgb8(fb.data(), (size_t)width * height, rgb8.data());
+            rt_tonemap_rgb8(fb.data(), n_out * view_pixels, rgb8.data());
     }
     rt_destroy(scene);
     rt_loaded_free(loaded);
     if (rc != RT_OK)
         return die("rt_render");
-    if (rt_write_ppm(argv[5], width, height, rgb8.data()) != RT_OK)
-        return die("write");
+    if (views.empty()) {
+        if (rt_write_ppm(argv[5], width, height, rgb8.data()) != RT_OK)
+            return die("write");
+    } else {
+        const std::filesystem::path out(argv[5]);
+        for (size_t i = 0; i < n_out; ++i) {
+            std::filesystem::path name = out.parent_path() / (out.stem().string() + "_" + std::to_string(i) + out.extension().string());
+            if (rt_write_ppm(name.string().c_str(), width, height, rgb8.data() + i * view_pixels * 3) != RT_OK)
+                return die("write");
+        }
+    }
     if (verbose)
         std::fprintf(stderr, "samples=%llu kernel_ms=%.3f Msamples/s=%.3f\n", (unsigned long long)st.samples, st.kernel_ms,
                      st.kernel_ms > 0 ? st.samples / st.kernel_ms / 1e3 : 0.0);

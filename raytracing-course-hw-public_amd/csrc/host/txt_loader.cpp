@@ -253,6 +253,7 @@ void load_txt(const std::string &path, rt_loaded_scene &res) {
     d.n_textures = 0;
     d.textures = nullptr;
     d.camera = cam;
+    res.cameras.assign(1, cam); // a scene-txt file has one camera
     std::memcpy(d.bg_color, bg, 12);
     d.bg_texture = RT_TEX_NONE;
     d.ray_depth = ray_depth;

@@ -237,15 +237,25 @@ inline uint32_t wf_stripe_base(uint32_t k, uint32_t n_slots) {
     return 64u * (k * q + (k < r ? k : r));
 }
 
+// One camera view of a render (rt_render_views; rt_render is the one view of the scene's own camera): what gen_ray (raytracer.h:527-538)
+// reads of Camera, its two hoisted tangents and the view's RNG seed. One 64-byte record per view, a table in HBM that wf_generate indexes
+// with virtual pixel / WfLaunch::view_pixels (the virtual image is the views stacked view-major).
+struct alignas(64) WfView {
+    float pos[3], right[3], up[3], fwd[3];
+    float tan_x, tan_y; // tan(fov_x/2), tan(fov_y/2) of this view at the render's aspect (rt_scene.cpp camera_tangents)
+    uint64_t seed;      // RT_RNG_DEVICE stream seed
+};
+static_assert(sizeof(WfView) == 64, "WfView must be 64 bytes");
+
 struct WfLaunch {
-    uint32_t width, height, samples; // image, total SPP
+    uint32_t width, height, samples; // ONE view's image, total SPP
     uint32_t first_sample, pass_samples; // this pass renders samples [first_sample, first_sample + pass_samples)
-    uint32_t first_pixel, pass_pixels;   // ... of local pixels [first_pixel, first_pixel + pass_pixels) of this shard
+    uint32_t first_pixel, pass_pixels;   // ... of local pixels [first_pixel, first_pixel + pass_pixels) of this shard of the virtual image
     uint32_t n_paths;                    // pass_pixels * pass_samples
     uint32_t shard_index, shard_count, shard_block;
     uint32_t ray_depth;
-    uint64_t seed;
-    float tan_x, tan_y;
+    const WfView *views;                 // [n_views]: camera, tangents and seed of virtual pixel p's view views[p / view_pixels]
+    uint32_t view_pixels;                // width * height
     WfPath *paths_in, *paths_out; // this bounce's queue / the next one (compacted survivors)
     WfHit *hits;             // closest hit of the ray processed at queue POSITION q (position in `order` when sorted): wf_extend's
                              // waves take contiguous positions, so a line of hits is filled by one wave within one chunk and
@@ -283,7 +293,9 @@ struct RenderLaunch {
     uint32_t n_items;      // work items of THIS shard (pixels in device mode, 256-pixel spans in reference mode)
     uint32_t items_per_block; // work items per shard block
     float tan_x, tan_y;    // tan(fov_x/2), tan(fov_y/2) hoisted from gen_ray (raytracer.h:531-535)
-    float *fb;             // width*height*3, device
+    uint32_t item_base;    // rt_render_views, one launch per view: this launch's work items are items [item_base, item_base + n_items) of the
+    uint32_t pix_base;     //   shard, whose virtual pixels start at view pixel 0 = virtual pixel pix_base (0 for a single view)
+    float *fb;             // width*height*3 of this launch's view, device
     uint32_t *counter;     // work-item ticket
     DevStats *stats;       // may be null
 };

@@ -245,7 +245,7 @@ int group_create(const rt_scene_desc *desc, const int *devices, int n_devices, G
     return RT_OK;
 }
 
-int group_render(Group *g, const rt_params *p, float *fb, uint8_t *rgb8, rt_stats *stats) {
+int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_views, float *fb, uint8_t *rgb8, rt_stats *stats) {
     if (!g || !p || (!fb && !rgb8))
         return fail(RT_ERR_INVALID_ARG, "rt_render: null argument");
     if (p->shard_count > 1)
@@ -253,8 +253,46 @@ int group_render(Group *g, const rt_params *p, float *fb, uint8_t *rgb8, rt_stat
     if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= 0x7FFFFFFFull)
         return fail(RT_ERR_INVALID_ARG, "Illegal image size" + std::to_string(p->width) + "x" + std::to_string(p->height)); // image.h:26
     const auto wall0 = std::chrono::steady_clock::now();
+    if (views && n_views > 1 && p->rng_mode == RT_RNG_REFERENCE) {
+        // the reference stream is sequential per 256-pixel span of ONE view: render the views one after the other, each through the
+        // group's own block split, into its slice of the caller's buffer, and sum the statistics
+        const size_t view_bytes = (size_t)p->width * p->height * (rgb8 ? 3 : 12);
+        rt_stats sum{}, one{};
+        for (uint32_t v = 0; v < n_views; ++v) {
+            char *dst = rgb8 ? reinterpret_cast<char *>(rgb8) : reinterpret_cast<char *>(fb);
+            dst += v * view_bytes;
+            if (int rc = group_render(g, p, views + v, 1, rgb8 ? nullptr : reinterpret_cast<float *>(dst), rgb8 ? reinterpret_cast<uint8_t *>(dst) : nullptr,
+                                      stats ? &one : nullptr);
+                rc != RT_OK)
+                return rc;
+            if (stats) {
+                sum.samples += one.samples;
+                sum.casts += one.casts;
+                sum.nodes_visited += one.nodes_visited;
+                sum.box_tests += one.box_tests;
+                sum.tri_tests += one.tri_tests;
+                sum.shaded_hits += one.shaded_hits;
+                sum.light_queries += one.light_queries;
+                sum.light_nodes += one.light_nodes;
+                sum.light_box_tests += one.light_box_tests;
+                sum.light_tri_tests += one.light_tri_tests;
+                sum.light_hits += one.light_hits;
+                sum.texel_fetches += one.texel_fetches;
+                sum.kernel_ms += one.kernel_ms;
+                sum.dominant_ms += one.dominant_ms;
+                sum.dominant_launches += one.dominant_launches;
+                sum.passes += one.passes;
+                sum.packet_passes += one.packet_passes;
+            }
+        }
+        if (stats) {
+            *stats = sum;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        }
+        return RT_OK;
+    }
     const uint32_t G = (uint32_t)g->ranks.size();
-    const uint64_t n_pix = (uint64_t)p->width * p->height;
+    const uint64_t n_pix = (uint64_t)p->width * p->height * (views ? n_views : 1u); // the view-major virtual image
     const size_t es = rgb8 ? 3 : 12;
     // 8 image rows per block (cost per row is very non-uniform: interleave finely); whole 256-pixel spans in reference-RNG
     // mode, whose seed is the span index (config.h:13, raytracer.h:648)
@@ -314,8 +352,12 @@ int group_render(Group *g, const rt_params *p, float *fb, uint8_t *rgb8, rt_stat
                 q.flags |= RT_FLAG_DEVICE_FB;
                 q.progress = nullptr;
                 char *dst = r == 0 ? render0 : g->ranks[r].image;
-                rcs[r] = rgb8 ? rt_render_rgb8(g->ranks[r].scene, &q, reinterpret_cast<uint8_t *>(dst), &sts[r])
-                              : rt_render(g->ranks[r].scene, &q, reinterpret_cast<float *>(dst), &sts[r]);
+                if (views)
+                    rcs[r] = rgb8 ? rt_render_views_rgb8(g->ranks[r].scene, &q, views, n_views, reinterpret_cast<uint8_t *>(dst), &sts[r])
+                                  : rt_render_views(g->ranks[r].scene, &q, views, n_views, reinterpret_cast<float *>(dst), &sts[r]);
+                else
+                    rcs[r] = rgb8 ? rt_render_rgb8(g->ranks[r].scene, &q, reinterpret_cast<uint8_t *>(dst), &sts[r])
+                                  : rt_render(g->ranks[r].scene, &q, reinterpret_cast<float *>(dst), &sts[r]);
                 if (rcs[r] != RT_OK)
                     errs[r] = rt_last_error();
                 else if (p->progress) {

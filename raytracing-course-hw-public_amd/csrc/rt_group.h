@@ -27,7 +27,10 @@ void group_destroy(Group *g);
 int group_size(const Group *g);
 rt_scene *group_primary(Group *g); // replica on devices[0]: serves the probe entry points
 // rt_render (fb != null) / rt_render_rgb8 (rgb8 != null) over all GPUs of the group; the result lands in the caller's
-// buffer (host memory, or device memory of devices[0] with RT_FLAG_DEVICE_FB)
-int group_render(Group *g, const rt_params *p, float *fb, uint8_t *rgb8, rt_stats *stats);
+// buffer (host memory, or device memory of devices[0] with RT_FLAG_DEVICE_FB). views != null: rt_render_views / _rgb8 (the
+// blocks and the gather run over the view-major virtual image; reference RNG renders the views one after the other)
+int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_views, float *fb, uint8_t *rgb8, rt_stats *stats);
+// rt_scene.cpp: rt_render_views' checks of the arguments alone (n_views, reserved fields, size, reference-RNG sharding)
+int check_views(const rt_params *p, const rt_view *views, uint32_t n_views);
 
 } // namespace rt

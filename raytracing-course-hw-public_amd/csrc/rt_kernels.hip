@@ -32,12 +32,13 @@ struct Item {
 DEV Item map_item(const RenderLaunch &L, uint32_t item) {
     const uint32_t n_pix = L.width * L.height;
     const uint32_t unit = (L.rng_mode == RT_RNG_REFERENCE) ? RT_SPAN : 1u;
+    item += L.item_base;
     uint32_t local_block = item / L.items_per_block;
     uint32_t within = item - local_block * L.items_per_block;
     uint32_t global_block = local_block * L.shard_count + L.shard_index;
     uint32_t first_unit = global_block * L.items_per_block + within; // global pixel (device) / span (reference) index
     Item it;
-    it.pix = first_unit * unit;
+    it.pix = first_unit * unit - L.pix_base; // pixel of this launch's view (pix_base = 0 in reference mode: spans restart per view)
     uint32_t end = it.pix + unit;
     it.pix_end = end < n_pix ? end : n_pix;
     it.seed = first_unit;

@@ -68,21 +68,30 @@ DEV uint32_t wf_global_pixel(const WfLaunch &L, uint32_t local_pixel) {
 // ------------------------------------------------------------------------------------------------ generate
 template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
     LaneStats<STATS> st;
-    const V3 cam_pos = ld3(S.cam_pos), cam_right = ld3(S.cam_right), cam_up = ld3(S.cam_up), cam_fwd = ld3(S.cam_fwd);
     if (blockIdx.x == 0 && threadIdx.x == 0)
         L.counters[WF_CNT_IN] = L.n_paths; // the first bounce's queue is the identity: slot i holds path i
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
         const uint32_t lp = i / L.pass_samples;
         const uint32_t ds = i - lp * L.pass_samples;
-        const uint32_t pix = wf_global_pixel(L, L.first_pixel + lp);
+        const uint32_t vpix = wf_global_pixel(L, L.first_pixel + lp); // pixel of the virtual (view-major) image
+        const uint32_t v = vpix / L.view_pixels;
+        const uint32_t pix = vpix - v * L.view_pixels; // pixel within its view
         const uint32_t s = L.first_sample + ds;
+        // the view is wave-uniform except where a wave straddles two views: then every lane reads its own record
+        const uint32_t v0 = __builtin_amdgcn_readfirstlane(v);
+        WfView view;
+        if (__ballot(v != v0) == 0ull)
+            view = L.views[v0];
+        else
+            view = L.views[v];
+        const V3 cam_pos = ld3(view.pos), cam_right = ld3(view.right), cam_up = ld3(view.up), cam_fwd = ld3(view.fwd);
         Rng<RT_RNG_DEVICE> rng;
-        rt_xoshiro_seed(&rng.g, L.seed, pix, s);
+        rt_xoshiro_seed(&rng.g, view.seed, pix, s);
         const uint32_t x = pix % L.width, y = pix / L.width;
         float ox = uniform_real(rng, 0.0f, 1.0f);
         float oy = uniform_real(rng, 0.0f, 1.0f);
-        float sx = (2 * ((float)(int)x + ox) / (float)L.width - 1) * L.tan_x;
-        float sy = (2 * ((float)(int)y + oy) / (float)L.height - 1) * L.tan_y;
+        float sx = (2 * ((float)(int)x + ox) / (float)L.width - 1) * view.tan_x;
+        float sy = (2 * ((float)(int)y + oy) / (float)L.height - 1) * view.tan_y;
         V3 rd = norm(sx * cam_right - sy * cam_up + 1.0f * cam_fwd);
         float4 *rq = reinterpret_cast<float4 *>(L.paths_in + i);
         rq[0] = make_float4(cam_pos.x, cam_pos.y, cam_pos.z, rd.x);
