@@ -46,7 +46,8 @@ extern "C" {
                                 reads no environment variable; progress callback; packet census in rt_stats. Still 4 after the development
                                 options were retired (two rt_build_options fields became reserved, unused RT_SORT_* / RT_BUILD_* values are
                                 refused): the binary layout and the meaning of every value that remains are unchanged. Still 4 after
-                                rt_view / rt_render_views / rt_render_views_rgb8 were added: new entry points only, no existing layout changes */
+                                rt_view / rt_render_views / rt_render_views_rgb8 were added, and after the rt_accum_* accumulators and
+                                rt_adaptive were: new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
 
@@ -384,6 +385,72 @@ typedef struct rt_view {
 } rt_view;             /* 64 bytes */
 int rt_render_views(rt_scene *scene, const rt_params *params, const rt_view *views, uint32_t n_views, float *fb_rgb, rt_stats *stats);
 int rt_render_views_rgb8(rt_scene *scene, const rt_params *params, const rt_view *views, uint32_t n_views, uint8_t *rgb8, rt_stats *stats);
+
+/* Resumable sample accumulators: progressive and adaptive rendering (additive; RT_ABI_VERSION stays 4).
+ * An accumulator belongs to one scene, one image size (width x height) and one view (a camera and an RT_RNG_DEVICE seed). It keeps, in
+ * device memory, for every pixel p:
+ *   S_p  the sum of its samples 0 .. n_p - 1, added in sample order (float3; starts at +0.0),
+ *   E_p  the sum of its even-index samples 0, 2, 4, ..., added in the same order (float3; starts at +0.0),
+ *   n_p  its sample count (u32).
+ * Exactness: after any sequence of accumulator calls, pixel p of the resolved image equals, bit for bit, pixel p of rt_render with
+ *   samples = n_p on the same scene, with the same flags, camera and seed (rt_render_views with {camera, seed} for a camera other than the
+ *   scene's own): for the parity traversal and RT_FLAG_GLOBAL_BEST, binary or wide device-built trees, any max_paths, sort mode and packet
+ *   mode, and any split of the samples over calls. Sample s of pixel p is seeded from (seed, p, s) whichever call draws it, and one lane
+ *   adds a pixel's new samples onto S_p / E_p in sample order (no float atomics), so no result depends on scheduling. A pixel with
+ *   n_p = 0 resolves to 0.
+ * Scope: the RT_RNG_DEVICE wavefront pipeline on one GPU.
+ *   RT_RNG_REFERENCE -> RT_ERR_UNSUPPORTED: one minstd_rand stream runs sequentially through a whole 256-pixel span, so a pixel's later
+ *     samples cannot be drawn without replaying the span.
+ *   RT_FLAG_MEGAKERNEL -> RT_ERR_UNSUPPORTED (the megakernel renders whole pixels, not sample lists).
+ *   A multi-GPU scene (rt_create_on, RT_ALL_DEVICES) -> RT_ERR_UNSUPPORTED at rt_accum_create.
+ *   shard_count > 1 or RT_FLAG_DEVICE_FB in the render params -> RT_ERR_INVALID_ARG.
+ * An rt_render on the same scene between accumulator calls does not disturb the accumulator (it shares the scene's stream and
+ * wavefront workspace, never the accumulator's own buffers).
+ *
+ * The adaptive rule (rt_accum_render_adaptive), exactly:
+ *   error of pixel p: +inf if n_p < 2; otherwise, with h = (n_p + 1) / 2 (integer), I = S_p / n_p, A = E_p / h per component in float,
+ *     err_p = (|I.r - A.r| + |I.g - A.g| + |I.b - A.b|) / (1e-4f + sqrtf(I.r + I.g + I.b))
+ *   (the half-buffer estimate; a NaN or infinite err_p counts as not converged).
+ *   Pixel p is ACTIVE when n_p < max_samples and (n_p < min_samples or some q of the 3x3 window around p, clipped at the image border,
+ *     has !(err_q <= threshold)).
+ *   Round 0 brings every pixel below min_samples up to it (min_samples - n_p samples: these differ per pixel when the accumulator is not
+ *     fresh). Each later round judges every pixel again and adds min(step, max_samples - n_p) samples to each active pixel. The call
+ *     returns when a judge finds no active pixel (it always terminates: an active pixel gains at least one sample per round). *rounds
+ *     receives the number of rounds that added samples.
+ *   After return, for every pixel: n_p >= max_samples (a progressive call may have gone past the cap; such pixels are never active), or
+ *     every err_q of its window is <= threshold. rt_accum_read's `error` is the err of the current state: what the last judge saw.
+ *   rt_params.progress is called once per finished round with (round, total): total is 1 + ceil((max - min) / step), the rounds one pixel
+ *   can take part in; a pixel whose neighbours gained samples may become active again, and then total grows with round.
+ * RT_ERR_INVALID_ARG: a NULL argument; params->samples == 0 for rt_accum_render; params width / height other than the accumulator's;
+ *   min_samples == 1; max_samples < min_samples; a threshold that is NaN, negative or infinite; a non-zero reserved field.
+ * A scene with ray_depth == 0 makes rt_accum_render* a no-op, as it does rt_render. */
+typedef struct rt_accum rt_accum; /* opaque */
+/* camera NULL: the scene's creation camera. */
+int rt_accum_create(rt_scene *scene, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, rt_accum **out);
+void rt_accum_destroy(rt_accum *acc); /* precondition: before rt_destroy of its scene */
+/* Adds params->samples samples to EVERY pixel (a progressive step). params: width / height must equal the accumulator's, seed is not read,
+ * rng_mode must be RT_RNG_DEVICE; the flags RT_FLAG_COUNTERS / RT_FLAG_GLOBAL_BEST, the tuning fields and progress mean what they mean for
+ * rt_render. stats (may be NULL) sums over every pass of the call; stats->samples is the number of samples added. */
+int rt_accum_render(rt_accum *acc, const rt_params *params, rt_stats *stats);
+
+typedef struct rt_adaptive {
+    float threshold;       /* >= 0 and finite; 0 sends every pixel to max_samples except where a whole window has err exactly 0 */
+    uint32_t min_samples;  /* 0 = 16; otherwise >= 2 */
+    uint32_t max_samples;  /* >= min_samples */
+    uint32_t step;         /* samples added to each active pixel per round; 0 = 32 (profiles/adaptive_sponza.txt: half the rounds of 16 at
+                              the same error; every round pays ~ray_depth closest-hit launch tails) */
+    uint32_t reserved[4];  /* 0 */
+} rt_adaptive;             /* 32 bytes */
+/* params->samples is not read; everything else as rt_accum_render. `rounds` may be NULL. */
+int rt_accum_render_adaptive(rt_accum *acc, const rt_params *params, const rt_adaptive *ad, uint32_t *rounds, rt_stats *stats);
+
+/* The image: S_p / (float)n_p per pixel (0 where n_p = 0), exactly as rt_render's last pass divides. flags: 0 (host buffer) or
+ * RT_FLAG_DEVICE_FB (a device buffer). rt_accum_resolve_rgb8 applies the device film on top: == rt_tonemap_rgb8 of the float image. */
+int rt_accum_resolve(rt_accum *acc, uint32_t flags, float *fb_rgb);
+int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb8);
+/* Copies the state to host buffers (any may be NULL): S (3 floats per pixel), E (3 floats), n, and err (as the last judge computed it;
+ * +inf everywhere before the first adaptive call). */
+int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb, uint32_t *samples, float *error);
 
 int rt_film_rgb8(rt_scene *scene, const float *rgb, size_t n_pixels, uint8_t *out_rgb8);
 

@@ -48,6 +48,7 @@ from ._ctypes_abi import (
     RT_RNG_DEVICE,
     RT_RNG_REFERENCE,
     DescHolder,
+    RtAdaptive,
     RtCamera,
     RtParams,
     RtSceneDesc,
@@ -234,6 +235,7 @@ class DeviceScene:
         over their GPUs and gather on the first one."""
         desc, keep = _as_desc(scene)
         self._keep = keep
+        self._accums = []  # live Accumulators: closed before the scene (rt_accum_destroy precedes rt_destroy)
         self._h = C.c_void_p()
         if device_bvh or wide or build_flags or build_options:  # a private copy of the descriptor with the build flags set
             d2 = RtSceneDesc()
@@ -255,6 +257,8 @@ class DeviceScene:
         return int(lib().rt_scene_device_count(self._h))
 
     def close(self) -> None:
+        for acc in list(getattr(self, "_accums", [])):
+            acc.close()
         if self._h:
             lib().rt_destroy(self._h)
             self._h = None
@@ -264,6 +268,11 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+    def accumulator(self, width: int, height: int, camera=None, seed: int = 0) -> "Accumulator":
+        """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
+        RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view."""
+        return Accumulator(self, width, height, camera, seed)
 
     def run_raytracer(
         self,
@@ -453,6 +462,80 @@ class DeviceScene:
         order = np.zeros(no.value, dtype=np.uint32)
         _check(lib().rt_bvh_info(self._h, which, C.byref(nn), C.byref(no), C.byref(root), u32ptr(nodes), u32ptr(order)))
         return {"root": root.value, "nodes": nodes, "order": order}
+
+
+class Accumulator:
+    """Progressive and adaptive rendering (include/rt_abi.h rt_accum_*): per-pixel sums S, E (even-index samples) and counts n that
+    survive between calls. Keeps its DeviceScene alive; DeviceScene.close() closes it first."""
+
+    def __init__(self, scene: DeviceScene, width: int, height: int, camera=None, seed: int = 0):
+        self._scene = scene
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        cam = None
+        if camera is not None:
+            cam = make_views([camera], 0)[0].camera
+        _check(lib().rt_accum_create(scene._h, self.width, self.height, C.byref(cam) if cam is not None else None, int(seed), C.byref(self._h)))
+        scene._accums.append(self)
+
+    def _params(self, samples: int, global_best: bool, counters: bool, tuning: dict):
+        p = RtParams(self.width, self.height, samples, RT_RNG_DEVICE, 0, 0, 1, 0,
+                     (RT_FLAG_GLOBAL_BEST if global_best else 0) | (RT_FLAG_COUNTERS if counters else 0))
+        return p, _apply_tuning(p, tuning)
+
+    def render(self, samples: int, global_best: bool = False, counters: bool = False, **tuning) -> dict:
+        """rt_accum_render: `samples` more samples for every pixel. `tuning`: as DeviceScene.run_raytracer. Returns the stats dict."""
+        p, keep_cb = self._params(samples, global_best, counters, tuning)  # noqa: F841
+        st = RtStats()
+        _check(lib().rt_accum_render(self._h, C.byref(p), C.byref(st)))
+        return st.as_dict()
+
+    def render_adaptive(self, threshold: float, min_samples: int = 16, max_samples: int = 256, step: int = 32, global_best: bool = False,
+                        counters: bool = False, **tuning) -> dict:
+        """rt_accum_render_adaptive: rounds of `step` samples for the pixels whose 3x3 window holds an error above `threshold`, until none
+        does or they reach `max_samples`. Returns the stats dict with "rounds"."""
+        p, keep_cb = self._params(0, global_best, counters, tuning)  # noqa: F841
+        ad = RtAdaptive(float(threshold), int(min_samples), int(max_samples), int(step))
+        st = RtStats()
+        rounds = C.c_uint32(0)
+        _check(lib().rt_accum_render_adaptive(self._h, C.byref(p), C.byref(ad), C.byref(rounds), C.byref(st)))
+        d = st.as_dict()
+        d["rounds"] = int(rounds.value)
+        return d
+
+    def image(self, rgb8: bool = False) -> np.ndarray:
+        """The resolved image S / n: (H, W, 3) float32, or the device film's uint8 image with `rgb8`."""
+        if rgb8:
+            img = np.zeros((self.height, self.width, 3), dtype=np.uint8)
+            _check(lib().rt_accum_resolve_rgb8(self._h, 0, img.ctypes.data_as(C.c_void_p)))
+            return img
+        fb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check(lib().rt_accum_resolve(self._h, 0, fb.ctypes.data_as(C.c_void_p)))
+        return fb
+
+    def read(self) -> dict:
+        """The state: "sum" and "even_sum" (H, W, 3) float32, "samples" (H, W) uint32, "error" (H, W) float32 (the last judge's)."""
+        out = {
+            "sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
+            "even_sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
+            "samples": np.zeros((self.height, self.width), dtype=np.uint32),
+            "error": np.zeros((self.height, self.width), dtype=np.float32),
+        }
+        _check(lib().rt_accum_read(self._h, fptr(out["sum"]), fptr(out["even_sum"]), u32ptr(out["samples"]), fptr(out["error"])))
+        return out
+
+    def close(self) -> None:
+        if self._h:
+            lib().rt_accum_destroy(self._h)
+            self._h = None
+        if self in self._scene._accums:
+            self._scene._accums.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def bvh_build_host(positions: np.ndarray, subset: Optional[np.ndarray] = None) -> dict:

@@ -62,6 +62,16 @@ class RtView(C.Structure):  # rt_render_views: one camera view (64 bytes)
     _fields_ = [("camera", RtCamera), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class RtAdaptive(C.Structure):  # rt_accum_render_adaptive: the adaptive rule's parameters (32 bytes)
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("min_samples", C.c_uint32),
+        ("max_samples", C.c_uint32),
+        ("step", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class RtTextureDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgba8", c_u8_p)]
 
@@ -195,6 +205,13 @@ ABI_PROTOTYPES = {
     "rt_film_rgb8": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_u8_p]),
     "rt_render_views": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtView), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_render_views_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtView), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_accum_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtCamera), C.c_uint64, C.POINTER(C.c_void_p)]),
+    "rt_accum_destroy": (None, [C.c_void_p]),
+    "rt_accum_render": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtStats)]),
+    "rt_accum_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtAdaptive), c_u32_p, C.POINTER(RtStats)]),
+    "rt_accum_resolve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_accum_resolve_rgb8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_accum_read": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_u32_p, c_float_p]),
     "rt_last_error": (C.c_char_p, []),
     "rt_source_stamp": (C.c_char_p, []),
     "rt_abi_version": (C.c_uint32, []),

@@ -12,6 +12,10 @@
 // (raytracer.h:647) per finished pass, and a timing line on stderr.
 // RT_ALL_CAMERAS=1: render EVERY camera of the file (rt_loaded_cameras; the reference keeps only the last) in one rt_render_views_rgb8
 // call, all with RT_SEED, and write camera i to <stem>_<i><ext> of the output path.
+// RT_ADAPTIVE=<threshold>: adaptive sampling through an accumulator (rt_accum_render_adaptive) of the scene's camera on one GPU; the SPP
+// argument becomes max_samples, RT_ADAPTIVE_MIN (default 16, capped at the SPP) and RT_ADAPTIVE_STEP (default 32) set min_samples and step.
+// RT_SPP_MAP=<file.pgm> also writes the per-pixel sample counts (16-bit PGM). RT_VERBOSE adds the rounds and the mean SPP.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -67,8 +71,9 @@ int main(int argc, char **argv) {
         }
     }
     const char *dev_env = std::getenv("RT_DEVICE");
+    const char *adaptive = std::getenv("RT_ADAPTIVE"); // accumulators run on one GPU
     rt_scene *scene = nullptr;
-    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 ? RT_ALL_DEVICES : 0);
+    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !adaptive ? RT_ALL_DEVICES : 0);
     auto env_on = [](const char *name) {
         const char *v = std::getenv(name);
         return v && std::atoi(v) != 0;
@@ -134,9 +139,44 @@ int main(int argc, char **argv) {
     rt_stats st{};
     const char *film = std::getenv("RT_FILM");
     int rc = RT_ERR_UNSUPPORTED;
-    if (!(film && !std::strcmp(film, "host")))
+    uint32_t rounds = 0;
+    std::vector<uint32_t> spp_map;
+    if (adaptive) {
+        if (!views.empty()) {
+            rt_destroy(scene);
+            rt_loaded_free(loaded);
+            std::cerr << "RT_ADAPTIVE renders the scene's camera only (not with RT_ALL_CAMERAS)" << std::endl;
+            return EXIT_FAILURE;
+        }
+        rt_adaptive ad{};
+        ad.threshold = std::strtof(adaptive, nullptr);
+        ad.max_samples = samples;
+        const char *mn = std::getenv("RT_ADAPTIVE_MIN");
+        ad.min_samples = mn ? (uint32_t)std::strtoul(mn, nullptr, 10) : std::min(16u, samples);
+        if (const char *step = std::getenv("RT_ADAPTIVE_STEP"))
+            ad.step = (uint32_t)std::strtoul(step, nullptr, 10);
+        rt_accum *acc = nullptr;
+        rc = rt_accum_create(scene, width, height, nullptr, p.seed, &acc);
+        if (rc == RT_OK)
+            rc = rt_accum_render_adaptive(acc, &p, &ad, &rounds, &st);
+        if (rc == RT_OK) { // the film as for rt_render_rgb8: on the device unless RT_FILM=host or the device film declines
+            rc = (film && !std::strcmp(film, "host")) ? RT_ERR_UNSUPPORTED : rt_accum_resolve_rgb8(acc, 0, rgb8.data());
+            if (rc == RT_ERR_UNSUPPORTED) {
+                std::vector<float> fb(view_pixels * 3, 0.0f);
+                rc = rt_accum_resolve(acc, 0, fb.data());
+                if (rc == RT_OK)
+                    rt_tonemap_rgb8(fb.data(), view_pixels, rgb8.data());
+            }
+        }
+        if (rc == RT_OK) {
+            spp_map.resize(view_pixels);
+            rc = rt_accum_read(acc, nullptr, nullptr, spp_map.data(), nullptr);
+        }
+        if (acc)
+            rt_accum_destroy(acc);
+    } else if (!(film && !std::strcmp(film, "host")))
         rc = views.empty() ? rt_render_rgb8(scene, &p, rgb8.data(), &st) : rt_render_views_rgb8(scene, &p, views.data(), (uint32_t)views.size(), rgb8.data(), &st);
-    if (rc == RT_ERR_UNSUPPORTED) {
+    if (rc == RT_ERR_UNSUPPORTED && !adaptive) {
         std::vector<float> fb(n_out * view_pixels * 3, 0.0f);
         rc = views.empty() ? rt_render(scene, &p, fb.data(), &st) : rt_render_views(scene, &p, views.data(), (uint32_t)views.size(), fb.data(), &st);
         if (rc == RT_OK)
@@ -155,6 +195,26 @@ int main(int argc, char **argv) {
             std::filesystem::path name = out.parent_path() / (out.stem().string() + "_" + std::to_string(i) + out.extension().string());
             if (rt_write_ppm(name.string().c_str(), width, height, rgb8.data() + i * view_pixels * 3) != RT_OK)
                 return die("write");
+        }
+    }
+    if (adaptive) {
+        if (const char *map_path = std::getenv("RT_SPP_MAP")) { // binary 16-bit PGM, big-endian, counts clamped to 65535
+            FILE *f = std::fopen(map_path, "wb");
+            if (!f)
+                return die("RT_SPP_MAP");
+            std::fprintf(f, "P5\n%u %u\n65535\n", width, height);
+            for (uint32_t c : spp_map) {
+                const uint32_t v = std::min(c, 65535u);
+                std::fputc((int)(v >> 8), f);
+                std::fputc((int)(v & 255u), f);
+            }
+            std::fclose(f);
+        }
+        if (verbose) {
+            double total = 0;
+            for (uint32_t c : spp_map)
+                total += c;
+            std::fprintf(stderr, "adaptive: rounds=%u mean_spp=%.3f\n", rounds, spp_map.empty() ? 0.0 : total / (double)spp_map.size());
         }
     }
     if (verbose)

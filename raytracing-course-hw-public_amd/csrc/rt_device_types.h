@@ -286,6 +286,19 @@ struct WfLaunch {
     DevStats *stats;         // may be null
 };
 
+// A pass of an accumulator round (rt_accum_*, rt_accum.hip): the wavefront pipeline's first and last stages driven by a list of entries
+// (pixel p, k_p new samples) in increasing pixel order instead of a (pixel tile x sample range) rectangle. Path i of the pass belongs to
+// the entry e with off[e] <= off[first_entry] + i < off[e + 1] and draws sample n_p + (that difference). WfLaunch keeps describing the
+// pass's workspace; its n_paths is an upper bound (n_entries x the round's largest k), the exact count is off[first + n] - off[first].
+struct WfAccum {
+    float *sum, *even_sum;     // [3 * pixels]: S_p, E_p
+    uint32_t *count;           // [pixels]: n_p
+    const uint32_t *list_pix;  // [entries]: pixel of entry e
+    const uint32_t *list_base; // [entries]: n_p when the round was planned = sample index of the entry's first new sample
+    const uint32_t *list_off;  // [entries + 1]: exclusive prefix sum of k over the round's entries
+    uint32_t first_entry, n_entries; // this pass: entries [first_entry, first_entry + n_entries)
+};
+
 struct RenderLaunch {
     uint32_t width, height, samples, rng_mode;
     uint64_t seed;

@@ -55,8 +55,11 @@ struct WfHostSync {
     int n_events;
 };
 #define WF_HOST_CENSUS_WORD 40 /* 8-byte aligned, behind RT_MAX_RAY_DEPTH + 1 size words */
+// `acc` (optional): an accumulator pass (rt_accum.hip): wf_generate_list / wf_resolve_list over the round's entry list replace wf_generate /
+// wf_resolve; first_pass / last_pass are not read. Null for rt_render.
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
-                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync);
+                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
+                                 const WfAccum *acc = nullptr);
 // closest-hit probe through the renderer's own kernels: `rays` (6 floats each, device) -> queue -> wf_extend (or wf_extend_packet)
 // -> prim / bct (device). `L` carries the workspace (paths_in, hits, counters, stack_overflow, stats) and the traversal mode.
 hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *rays, uint32_t n, bool packet, bool stats, uint32_t *prim, float *bct,
@@ -66,4 +69,28 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 hipError_t launch_extend_wide(const DevScene &S, const WfLaunch &L, bool packet, bool stats, int blocks, hipStream_t stream);
 // bytes of temporary storage rocPRIM's radix sort needs for `n` (key, slot) pairs
 size_t wavefront_sort_temp_bytes(size_t n);
+// rt_accum.hip: the accumulators' per-round kernels (rt_abi.h rt_accum_*). `AccumRound` is the device state of one accumulator.
+struct AccumRound {
+    float *sum, *even_sum;     // [3 * pixels]
+    uint32_t *count;           // [pixels]
+    float *err;                // [pixels]: the last judge's err_p
+    uint32_t *target;          // [pixels]: n_p the round brings pixel p to
+    unsigned long long *scan_in, *scan; // [pixels]: (k > 0) << 32 | k per pixel, and its exclusive scan (entry index, sample offset)
+    uint32_t *list_pix, *list_base, *list_off; // [pixels], [pixels], [pixels + 1]
+    uint32_t *totals;          // [2] device: entries, samples of the planned list
+    void *scan_temp;
+    size_t scan_temp_bytes;
+    uint32_t width, height;
+};
+size_t accum_scan_temp_bytes(uint32_t pixels);
+// judge: err_p of every pixel, then target_p (round 0: max(n_p, min_samples); later: n_p + min(step, max - n_p) where active, n_p
+// elsewhere). round0 != 0 computes no err and applies no window test.
+hipError_t launch_accum_judge(const AccumRound &R, int round0, float threshold, uint32_t min_samples, uint32_t max_samples, uint32_t step,
+                              hipStream_t stream);
+// target_p = n_p + samples for every pixel (a progressive step)
+hipError_t launch_accum_uniform(const AccumRound &R, uint32_t samples, hipStream_t stream);
+// the list of entries (p, min(target_p - n_p, chunk)) with k > 0, in pixel order: exclusive scan + scatter; R.totals <- {entries, samples}
+hipError_t launch_accum_plan(const AccumRound &R, uint32_t chunk, hipStream_t stream);
+// fb[p] = S_p / (float)n_p (0 where n_p = 0)
+hipError_t launch_accum_image(const AccumRound &R, float *fb, hipStream_t stream);
 } // namespace rt

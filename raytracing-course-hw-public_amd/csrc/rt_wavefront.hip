@@ -66,6 +66,33 @@ DEV uint32_t wf_global_pixel(const WfLaunch &L, uint32_t local_pixel) {
 }
 
 // ------------------------------------------------------------------------------------------------ generate
+// gen_ray (raytracer.h:527-538) for sample s of pixel pix of view v: camera, jitter and seeding, written as the primary-ray record of queue
+// slot (= path) i. The one definition of a path's first ray: wf_generate and the accumulators' wf_generate_list both call it, so sample s of
+// pixel p is the same ray whichever of them draws it.
+DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32_t v, uint32_t pix, uint32_t s) {
+    // the view is wave-uniform except where a wave straddles two views: then every lane reads its own record
+    const uint32_t v0 = __builtin_amdgcn_readfirstlane(v);
+    WfView view;
+    if (__ballot(v != v0) == 0ull)
+        view = L.views[v0];
+    else
+        view = L.views[v];
+    const V3 cam_pos = ld3(view.pos), cam_right = ld3(view.right), cam_up = ld3(view.up), cam_fwd = ld3(view.fwd);
+    Rng<RT_RNG_DEVICE> rng;
+    rt_xoshiro_seed(&rng.g, view.seed, pix, s);
+    const uint32_t x = pix % L.width, y = pix / L.width;
+    float ox = uniform_real(rng, 0.0f, 1.0f);
+    float oy = uniform_real(rng, 0.0f, 1.0f);
+    float sx = (2 * ((float)(int)x + ox) / (float)L.width - 1) * view.tan_x;
+    float sy = (2 * ((float)(int)y + oy) / (float)L.height - 1) * view.tan_y;
+    V3 rd = norm(sx * cam_right - sy * cam_up + 1.0f * cam_fwd);
+    float4 *rq = reinterpret_cast<float4 *>(L.paths_in + i);
+    rq[0] = make_float4(cam_pos.x, cam_pos.y, cam_pos.z, rd.x);
+    rq[1] = make_float4(rd.y, rd.z, __uint_as_float(i | (next_shade_class(rng, S.lights.n_tris != 0) << WF_ORDER_CLASS_SHIFT)), __uint_as_float(L.ray_depth)); // path id (+ class); full budget, no pending frames
+    rq[2] = make_float4(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z, __uint_as_float(ray_fast_ok_ray(cam_pos, rd) ? 1u : 0u));
+    *reinterpret_cast<uint4 *>(rq + 3) = make_uint4(rng.g.s[0], rng.g.s[1], rng.g.s[2], rng.g.s[3]);
+}
+
 template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
     LaneStats<STATS> st;
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -77,28 +104,38 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const D
         const uint32_t v = vpix / L.view_pixels;
         const uint32_t pix = vpix - v * L.view_pixels; // pixel within its view
         const uint32_t s = L.first_sample + ds;
-        // the view is wave-uniform except where a wave straddles two views: then every lane reads its own record
-        const uint32_t v0 = __builtin_amdgcn_readfirstlane(v);
-        WfView view;
-        if (__ballot(v != v0) == 0ull)
-            view = L.views[v0];
-        else
-            view = L.views[v];
-        const V3 cam_pos = ld3(view.pos), cam_right = ld3(view.right), cam_up = ld3(view.up), cam_fwd = ld3(view.fwd);
-        Rng<RT_RNG_DEVICE> rng;
-        rt_xoshiro_seed(&rng.g, view.seed, pix, s);
-        const uint32_t x = pix % L.width, y = pix / L.width;
-        float ox = uniform_real(rng, 0.0f, 1.0f);
-        float oy = uniform_real(rng, 0.0f, 1.0f);
-        float sx = (2 * ((float)(int)x + ox) / (float)L.width - 1) * view.tan_x;
-        float sy = (2 * ((float)(int)y + oy) / (float)L.height - 1) * view.tan_y;
-        V3 rd = norm(sx * cam_right - sy * cam_up + 1.0f * cam_fwd);
-        float4 *rq = reinterpret_cast<float4 *>(L.paths_in + i);
-        rq[0] = make_float4(cam_pos.x, cam_pos.y, cam_pos.z, rd.x);
-        rq[1] = make_float4(rd.y, rd.z, __uint_as_float(i | (next_shade_class(rng, S.lights.n_tris != 0) << WF_ORDER_CLASS_SHIFT)), __uint_as_float(L.ray_depth)); // path id (+ class); full budget, no pending frames
-        rq[2] = make_float4(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z, __uint_as_float(ray_fast_ok_ray(cam_pos, rd) ? 1u : 0u));
-        *reinterpret_cast<uint4 *>(rq + 3) = make_uint4(rng.g.s[0], rng.g.s[1], rng.g.s[2], rng.g.s[3]);
+        wf_primary_ray(S, L, i, v, pix, s);
         st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
+    }
+    st.flush(L.stats);
+}
+
+// An accumulator pass (WfAccum): path i takes the entry whose prefix range holds off[first] + i (binary search; a pixel's paths stay
+// consecutive, so the 64 queue positions of a packet are still the samples of one or a few pixels). Paths [exact count, L.n_paths) of the
+// upper bound get an empty finished sample (no frames), so that wf_fold, which runs over L.n_paths, reads nothing stale.
+template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list(const DevScene S, const WfLaunch L, const WfAccum A) {
+    LaneStats<STATS> st;
+    const uint32_t *off = A.list_off + A.first_entry;
+    const uint32_t base = off[0], n_exact = off[A.n_entries] - base;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        L.counters[WF_CNT_IN] = n_exact;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
+        if (i >= n_exact) {
+            L.sample_out[i] = RtF4{0.f, 0.f, 0.f, __uint_as_float(0u)};
+            continue;
+        }
+        const uint32_t g = base + i;
+        uint32_t lo = 0, hi = A.n_entries - 1; // the last e with off[e] <= g (entries have k >= 1: off is strictly increasing)
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1u) >> 1;
+            if (off[mid] <= g)
+                lo = mid;
+            else
+                hi = mid - 1u;
+        }
+        const uint32_t e = A.first_entry + lo;
+        wf_primary_ray(S, L, i, 0u, A.list_pix[e], A.list_base[e] + (g - off[lo])); // an accumulator has one view
+        st.cast();
     }
     st.flush(L.stats);
 }
@@ -677,6 +714,27 @@ __global__ __launch_bounds__(256) void wf_resolve(const WfLaunch L, int first_pa
     }
 }
 
+// The same loop for an accumulator pass: one lane per entry adds its k consecutive samples onto S_p, and the even-index ones onto E_p,
+// in sample order, then n_p += k. A pixel has at most one entry per round, so the lane owns the pixel's sums; no division here.
+__global__ __launch_bounds__(256) void wf_resolve_list(const WfLaunch L, const WfAccum A) {
+    const uint32_t *off = A.list_off + A.first_entry;
+    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
+        const uint32_t e = A.first_entry + le, p = A.list_pix[e], s0 = A.list_base[e];
+        const uint32_t k = off[le + 1] - off[le];
+        V3 acc = ld3(A.sum + 3ull * p), ev = ld3(A.even_sum + 3ull * p);
+        const RtF4 *src = L.sample_out + (off[le] - off[0]);
+        for (uint32_t j = 0; j < k; ++j) {
+            const RtF4 v = src[j];
+            acc = acc + mk(v.x, v.y, v.z);
+            if (((s0 + j) & 1u) == 0u)
+                ev = ev + mk(v.x, v.y, v.z);
+        }
+        A.sum[3ull * p] = acc.x, A.sum[3ull * p + 1] = acc.y, A.sum[3ull * p + 2] = acc.z;
+        A.even_sum[3ull * p] = ev.x, A.even_sum[3ull * p + 1] = ev.y, A.even_sum[3ull * p + 2] = ev.z;
+        A.count[p] = s0 + k;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ probe: rays in, hits out
 // rt_cast_rays_ex: arbitrary rays go through the SAME closest-hit kernels the renderer launches. wf_from_rays writes them as
 // queue records (what wf_generate / wf_shade write for their rays), wf_hits_out turns the hit records into the probe's output.
@@ -769,7 +827,7 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 }
 
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
-                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync) {
+                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
@@ -782,7 +840,11 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         return e;
     if (packet_census_out)
         packet_census_out[0] = packet_census_out[1] = 0ull;
-    if (stats)
+    if (acc && stats) // an accumulator pass: the first stage follows the round's list (wf_generate_list)
+        WF_LAUNCH((wf_generate_list<true>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
+    else if (acc)
+        WF_LAUNCH((wf_generate_list<false>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
+    else if (stats)
         WF_LAUNCH((wf_generate<true>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
     else
         WF_LAUNCH((wf_generate<false>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
@@ -881,6 +943,11 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         if ((e = hipEventSynchronize(hs->events[0])) != hipSuccess)
             return e;
         std::memcpy(packet_census_out, hs->counts + WF_HOST_CENSUS_WORD, 2 * sizeof(unsigned long long));
+    }
+    if (acc) { // ... and so does the last
+        const int res_blocks = (int)((acc->n_entries + 255u) / 256u);
+        WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, *acc);
+        return hipSuccess;
     }
     const int res_blocks = (int)((L.pass_pixels + 255u) / 256u);
     WF_LAUNCH(wf_resolve, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, first_pass ? 1 : 0, last_pass ? 1 : 0);
