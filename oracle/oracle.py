@@ -35,6 +35,7 @@ _PROTOS = {
     "rto_intersect_objects": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_u32_p, _abi.c_float_p]),
     "rto_cast_rays_brute": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_float_p, C.c_int]),
     "rto_trace_pixel": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), C.c_uint32, C.c_uint32, _abi.c_float_p, _abi.c_u32_p, _abi.c_u32_p]),
+    "rto_pixel_samples": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), _abi.c_u32_p, C.c_uint32, _abi.c_float_p, C.c_int]),
     "rto_light_pdf": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_bg_at": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_bg_uv": (None, [_abi.c_float_p, C.c_uint32, C.c_int, _abi.c_float_p]),
@@ -149,6 +150,17 @@ class OracleScene:
         _check(lib().rto_trace_pixel(self._h, C.byref(p), int(pixel), cap, _abi.fptr(rays), _abi.u32ptr(smp), C.byref(n)))
         assert n.value <= cap
         return rays[: n.value].copy(), smp[: n.value].copy()
+
+    def pixel_samples(self, width, height, samples, pixels, seed=0, threads=None):
+        """Every sample's radiance for the listed pixel indices (device-RNG mode, the scene's camera): (len(pixels), samples, 3) float32, the
+        value render_pixel adds for sample s of each pixel (after sanitize_nans), seeded by (seed, pixel, s). `threads`: as cast_rays_brute."""
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        if threads is None:
+            threads = min(16, int(os.environ.get("OMP_NUM_THREADS") or 16))
+        p = _abi.RtParams(width, height, samples, _abi.RT_RNG_DEVICE, seed, 0, 1, 0, 0)
+        out = np.zeros((len(pixels), samples, 3), dtype=np.float32)
+        _check(lib().rto_pixel_samples(self._h, C.byref(p), _abi.u32ptr(pixels), len(pixels), _abi.fptr(out), max(1, int(threads))))
+        return out
 
     def light_pdf(self, rays):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)

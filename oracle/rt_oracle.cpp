@@ -791,6 +791,12 @@ template <class R> struct Integrator {
     }
 };
 
+// one term of render_pixel's sum (raytracer.h:622-624): the value `res += ...` adds, from the integrator's current RNG state
+template <class R> V3 pixel_sample(Integrator<R> &it, int x, int y) {
+    Ray ray = it.gen_ray(x, y);
+    return Integrator<R>::sanitize_nans(it.trace_ray(ray, it.sc.ray_depth));
+}
+
 // raytracer.h:618-627, RNG seeded per (pixel, sample) (device mode) or carried along the span (reference mode)
 template <class R> V3 render_pixel(Integrator<R> &it, int x, int y, uint64_t seed, uint32_t p_idx, bool per_sample_seed) {
     V3 res{0, 0, 0};
@@ -799,8 +805,7 @@ template <class R> V3 render_pixel(Integrator<R> &it, int x, int y, uint64_t see
             if (per_sample_seed)
                 rt_xoshiro_seed(&it.rng.g, seed, p_idx, s);
         }
-        Ray ray = it.gen_ray(x, y);
-        V3 v = Integrator<R>::sanitize_nans(it.trace_ray(ray, it.sc.ray_depth));
+        V3 v = pixel_sample(it, x, y);
         res = res + v;
         it.c.samples++;
     }
@@ -1000,6 +1005,46 @@ int rto_trace_pixel(rto_scene *s, const rt_params *p, uint32_t pixel, uint32_t c
             }
     }
     *n_out = n;
+    return RT_OK;
+}
+
+// Test aid: every term of render_pixel's sum for a list of pixels (device-RNG mode, the scene's camera): out[(i * samples + s) * 3 + c] is
+// what sample s of pixel pixels[i] adds (pixel_sample, after sanitize_nans), seeded from (seed, pixels[i], s). Their sequential binary32 sum
+// over s, divided by samples, is run_raytracer's pixel; the accumulator tests fold them into S_p and E_p. threads <= 0: hardware_concurrency.
+int rto_pixel_samples(rto_scene *s, const rt_params *p, const uint32_t *pixels, uint32_t n_pixels, float *out, int threads) {
+    if (!s || !p || p->rng_mode != RT_RNG_DEVICE || (n_pixels && (!pixels || !out))) {
+        g_err = "rto_pixel_samples: bad argument (device-RNG mode only)";
+        return RT_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0; i < n_pixels; ++i)
+        if ((uint64_t)pixels[i] >= (uint64_t)p->width * p->height) {
+            g_err = "rto_pixel_samples: pixel " + std::to_string(pixels[i]) + " outside the image";
+            return RT_ERR_INVALID_ARG;
+        }
+    if (threads <= 0)
+        threads = (int)std::max(std::thread::hardware_concurrency(), 1u);
+    threads = (int)std::min<uint32_t>((uint32_t)threads, std::max(n_pixels, 1u));
+    std::atomic<uint32_t> next(0);
+    std::vector<std::thread> workers;
+    for (int w = 0; w < threads; ++w) {
+        workers.emplace_back([&]() {
+            Integrator<RngXoshiro> it(*s, p->width, p->height, p->samples);
+            uint32_t i;
+            while ((i = next.fetch_add(1)) < n_pixels) {
+                const uint32_t pix = pixels[i];
+                for (unsigned smp = 0; smp < p->samples; ++smp) {
+                    rt_xoshiro_seed(&it.rng.g, p->seed, pix, smp);
+                    const V3 v = pixel_sample(it, (int)(pix % p->width), (int)(pix / p->width));
+                    float *o = out + 3 * ((size_t)i * p->samples + smp);
+                    o[0] = v.x;
+                    o[1] = v.y;
+                    o[2] = v.z;
+                }
+            }
+        });
+    }
+    for (auto &t : workers)
+        t.join();
     return RT_OK;
 }
 

@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import adaptive_replay as ar
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,8 +47,8 @@ def _assert_exact_per_level(dev, img, n, seed, **kw):
 
 
 def _assert_error_matches_state(r):
-    """err as the header defines it, recomputed from the read-back S, E and n: I and A per component in float (the division, as on the
-    device, is IEEE), the rest in float64."""
+    """err as the header defines it, recomputed from the read-back S, E and n: bit for bit the host model's binary32 err (adaptive_replay.err,
+    the header's operations in its order, correctly rounded / and sqrt), and consistent with the formula in float64."""
     n = r["samples"]
     ok = n >= 2
     h = ((n + 1) // 2).astype(np.float32)
@@ -59,6 +61,7 @@ def _assert_error_matches_state(r):
     fin = ok & np.isfinite(e64)
     assert np.allclose(err[fin], e64[fin], rtol=1e-5, atol=0.0)
     assert np.array_equal(np.isfinite(err[ok]), np.isfinite(e64[ok]))
+    ar.assert_floats_equal(r["error"], ar.err(r["sum"], r["even_sum"], n), "err")
 
 
 @pytest.mark.parametrize("mode", ["parity", "global_best", "wide"])
