@@ -3,5 +3,5 @@
 # and the checker under oracle/. Equivalent to: python -c 'import __graft_entry__ as g; g.build()'
 set -e
 DIR="$(cd "$(dirname "$0")" && pwd)"
-make -C "$DIR/raytracing-course-hw-public_amd/csrc" -j"$(nproc)" all
+make -C "$DIR/raytracing-course-hw-public_amd/csrc" -j"$(( $(nproc) < 16 ? $(nproc) : 16 ))" all
 make -C "$DIR/oracle" all

@@ -1,0 +1,285 @@
+// rt_accum_host.cpp — the host side of the accumulators (rt_abi.h rt_accum_*; their kernels are rt_accum.hip).
+//
+// An accumulator owns its per-pixel state (S, E, n, err, the round's target and list, about 64 B per pixel) and one view record; it
+// borrows the scene's stream, its wavefront workspace and its framebuffer staging. Every call ends with the stream synchronised, so an
+// rt_render on the same scene in between only ever sees an idle workspace, and never touches the accumulator's buffers.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "rt_scene_impl.h"
+
+struct rt_accum {
+    rt_scene *scene = nullptr;
+    uint32_t width = 0, height = 0;
+    WfView view{};            // camera, tangents and seed (host copy of d_view)
+    WfView *d_view = nullptr; // WfLaunch::views of its passes: the one view
+    rt::AccumRound R{};
+    std::vector<void *> owned;
+    rt::PacketPolicy pkt; // of its own passes, kept apart from rt_render's
+    ~rt_accum() {
+        (void)hipSetDevice(scene->device);
+        (void)hipStreamSynchronize(scene->stream);
+        for (void *p : owned)
+            (void)hipFree(p);
+    }
+};
+
+extern "C" int rt_accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, rt_accum **out) {
+    if (!s || !out)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create: null argument");
+    *out = nullptr;
+    if (width == 0 || height == 0 || (uint64_t)width * height >= 0x7FFFFFFFull)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create: image size " + std::to_string(width) + "x" + std::to_string(height));
+    if (s->group)
+        return rt::fail(RT_ERR_UNSUPPORTED, "rt_accum_create: accumulators run on single-GPU scenes only");
+    HIP_TRY(hipSetDevice(s->device));
+    auto a = std::make_unique<rt_accum>();
+    a->scene = s;
+    a->width = width;
+    a->height = height;
+    a->view = rt::make_view(camera ? *camera : s->cam, width, height, seed);
+    const size_t n = (size_t)width * height;
+    auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+        if (e != hipSuccess)
+            return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_accum_create: ") + hipGetErrorString(e));
+        a->owned.push_back(q);
+        *ptr = static_cast<T *>(q);
+        return RT_OK;
+    };
+    rt::AccumRound &R = a->R;
+    R.width = width;
+    R.height = height;
+    R.scan_temp_bytes = rt::accum_scan_temp_bytes((uint32_t)n);
+    int rc;
+    if ((rc = alloc(12 * n, &R.sum)) != RT_OK || (rc = alloc(12 * n, &R.even_sum)) != RT_OK || (rc = alloc(4 * n, &R.count)) != RT_OK ||
+        (rc = alloc(4 * n, &R.err)) != RT_OK || (rc = alloc(4 * n, &R.target)) != RT_OK || (rc = alloc(8 * n, &R.scan_in)) != RT_OK ||
+        (rc = alloc(8 * n, &R.scan)) != RT_OK || (rc = alloc(4 * n, &R.list_pix)) != RT_OK || (rc = alloc(4 * n, &R.list_base)) != RT_OK ||
+        (rc = alloc(4 * (n + 1), &R.list_off)) != RT_OK || (rc = alloc(8, &R.totals)) != RT_OK || (rc = alloc(R.scan_temp_bytes, &R.scan_temp)) != RT_OK ||
+        (rc = alloc(sizeof(WfView), &a->d_view)) != RT_OK)
+        return rc;
+    HIP_TRY(hipMemsetAsync(R.sum, 0, 12 * n, s->stream)); // +0.0
+    HIP_TRY(hipMemsetAsync(R.even_sum, 0, 12 * n, s->stream));
+    HIP_TRY(hipMemsetAsync(R.count, 0, 4 * n, s->stream));
+    HIP_TRY(hipMemsetD32Async(R.err, 0x7F800000 /* +inf: n_p < 2 */, n, s->stream));
+    HIP_TRY(hipMemcpyAsync(a->d_view, &a->view, sizeof(WfView), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    *out = a.release();
+    return RT_OK;
+}
+
+extern "C" void rt_accum_destroy(rt_accum *acc) { delete acc; }
+
+static int accum_check(const rt_accum *a, const rt_params *p, const char *fn) {
+    if (!a || !p)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null argument");
+    if (p->width != a->width || p->height != a->height)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": params size " + std::to_string(p->width) + "x" + std::to_string(p->height) +
+                                                " differs from the accumulator's " + std::to_string(a->width) + "x" + std::to_string(a->height));
+    if (p->shard_count > 1 || (p->flags & RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": shard_count > 1 and RT_FLAG_DEVICE_FB do not apply to an accumulator");
+    if (p->rng_mode == RT_RNG_REFERENCE)
+        return rt::fail(RT_ERR_UNSUPPORTED, std::string(fn) + ": the reference RNG draws a 256-pixel span as one sequential stream; accumulators need RT_RNG_DEVICE");
+    if (p->rng_mode != RT_RNG_DEVICE)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": unknown rng_mode");
+    if (p->flags & RT_FLAG_MEGAKERNEL)
+        return rt::fail(RT_ERR_UNSUPPORTED, std::string(fn) + ": accumulators run on the wavefront pipeline, not the megakernel");
+    return rt::check_pass_params(p, fn);
+}
+
+// rt_accum_render (ad == nullptr: params->samples more samples for every pixel) and rt_accum_render_adaptive. A judge (or the uniform step)
+// writes every pixel's target count; `fill` then plans the list of (p, k_p) in pixel order, reads back {entries, samples} and runs the
+// wavefront pipeline over it in passes of floor(max_paths / K) entries, K the list's largest k, until every pixel holds its target.
+static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uint32_t *rounds_out, rt_stats *stats) {
+    rt_scene *s = a->scene;
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (stats)
+        std::memset(stats, 0, sizeof(*stats));
+    if (rounds_out)
+        *rounds_out = 0;
+    if (s->dev.ray_depth == 0) // raytracer.h:630-631, as rt_render
+        return RT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t n_pix = a->width * a->height;
+    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+    const uint64_t max_paths = rt::wavefront_max_paths(s, p);
+    // the largest k of one list: a pass holds at least one whole entry, and a list's sample prefix stays below 2^32 (rt_accum.hip)
+    const uint32_t chunk_cap = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(max_paths, 0xFFFFFFFFull / n_pix));
+    WfLaunch W{};
+    W.width = a->width;
+    W.height = a->height;
+    W.shard_count = 1;
+    W.shard_block = n_pix;
+    W.ray_depth = s->dev.ray_depth;
+    W.views = a->d_view;
+    W.view_pixels = n_pix;
+    W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
+    W.stats = counters ? s->d_stats : nullptr;
+    s->ext_events.reset();
+    uint32_t passes = 0, packet_passes = 0, rounds = 0;
+    uint64_t added = 0;
+    // rt_accum_render's progress: per pass, of the passes the call will run (every pixel, samples in lists of at most chunk_cap)
+    const uint32_t uni_chunk = std::min(ad ? 1u : p->samples, chunk_cap);
+    const uint64_t uni_per_pass = std::max<uint64_t>(1, max_paths / uni_chunk);
+    const uint32_t uni_passes = ad ? 0u : (uint32_t)(((uint64_t)p->samples + uni_chunk - 1) / uni_chunk * ((n_pix + uni_per_pass - 1) / uni_per_pass));
+
+    auto fill = [&](uint32_t K, bool *any) -> int {
+        const uint32_t C = std::min(K, chunk_cap);
+        const uint32_t per_pass = (uint32_t)std::min<uint64_t>(n_pix, std::max<uint64_t>(1, max_paths / C));
+        for (;;) {
+            HIP_TRY(rt::launch_accum_plan(a->R, C, s->stream));
+            uint32_t tot[2] = {0u, 0u}; // entries, samples of the list
+            HIP_TRY(hipMemcpyAsync(tot, a->R.totals, sizeof(tot), hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            if (tot[0] == 0)
+                return RT_OK;
+            *any = true;
+            const uint64_t cap = std::min<uint64_t>((uint64_t)std::min(per_pass, tot[0]) * C, tot[1]);
+            if (int rc = s->ensure_wavefront(cap, std::max<uint64_t>(s->wf_pixels_cap, 1), s->dev.ray_depth); rc != RT_OK)
+                return rc;
+            s->wf_bind(W);
+            W.fb = nullptr;
+            W.accum = nullptr; // wf_resolve does not run on an accumulator pass
+            for (uint32_t e0 = 0; e0 < tot[0]; e0 += per_pass) {
+                WfAccum A{a->R.sum, a->R.even_sum, a->R.count, a->R.list_pix, a->R.list_base, a->R.list_off, e0, std::min(per_pass, tot[0] - e0)};
+                W.n_paths = (uint32_t)std::min<uint64_t>((uint64_t)A.n_entries * C, tot[1]); // an upper bound: wf_generate_list reads the exact count
+                W.first_pixel = 0, W.pass_pixels = A.n_entries;
+                W.first_sample = 0, W.pass_samples = C, W.samples = C;
+                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A));
+                passes += 1;
+                packet_passes += W.use_packet;
+                if (p->progress && !ad) {
+                    HIP_TRY(hipStreamSynchronize(s->stream));
+                    p->progress(passes, std::max(passes, uni_passes), p->progress_user);
+                }
+            }
+            added += tot[1];
+        }
+    };
+
+    auto queue = [&]() -> int {
+        if (counters)
+            HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
+        HIP_TRY(hipEventRecord(s->ev0, s->stream));
+        if (!ad) {
+            HIP_TRY(rt::launch_accum_uniform(a->R, p->samples, s->stream));
+            bool any = false;
+            if (int rc = fill(p->samples, &any); rc != RT_OK)
+                return rc;
+        } else {
+            const uint32_t mn = ad->min_samples ? ad->min_samples : 16u, st = ad->step ? ad->step : 32u, mx = ad->max_samples; // rt_abi.h rt_adaptive
+            const uint32_t bound = 1u + (mx - std::min(mn, mx) + st - 1u) / st; // rounds one pixel can take part in
+            for (uint32_t r = 0;; ++r) {
+                HIP_TRY(rt::launch_accum_judge(a->R, r == 0 ? 1 : 0, ad->threshold, mn, mx, st, s->stream));
+                bool any = false;
+                if (int rc = fill(r == 0 ? mn : st, &any); rc != RT_OK)
+                    return rc;
+                if (any) {
+                    ++rounds;
+                    if (p->progress)
+                        p->progress(rounds, std::max(rounds, bound), p->progress_user);
+                } else if (r > 0) {
+                    break; // this judge found no active pixel: err is the final state's
+                }
+            }
+        }
+        HIP_TRY(hipEventRecord(s->ev1, s->stream));
+        return RT_OK;
+    };
+    if (int rc = rt::queue_and_wait(s, queue); rc != RT_OK)
+        return rc;
+    if (rounds_out)
+        *rounds_out = rounds;
+    if (stats) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        if (int rc = rt::fill_stats(s, counters, added, ms, wall0, stats); rc != RT_OK)
+            return rc;
+        stats->packet_lanes_x100 = a->pkt.lanes_x100;
+        stats->passes = passes;
+        stats->packet_passes = packet_passes;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_accum_render(rt_accum *acc, const rt_params *params, rt_stats *stats) {
+    if (int rc = accum_check(acc, params, "rt_accum_render"); rc != RT_OK)
+        return rc;
+    if (params->samples == 0)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render: samples must be >= 1");
+    return accum_run(acc, params, nullptr, nullptr, stats);
+}
+
+extern "C" int rt_accum_render_adaptive(rt_accum *acc, const rt_params *params, const rt_adaptive *ad, uint32_t *rounds, rt_stats *stats) {
+    if (int rc = accum_check(acc, params, "rt_accum_render_adaptive"); rc != RT_OK)
+        return rc;
+    if (!ad)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render_adaptive: null argument");
+    if (!(ad->threshold >= 0.0f) || std::isinf(ad->threshold))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render_adaptive: threshold must be finite and >= 0");
+    const uint32_t mn = ad->min_samples ? ad->min_samples : 16u;
+    if (mn == 1u || ad->max_samples < mn)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render_adaptive: min_samples must be 0 or >= 2, and max_samples >= min_samples");
+    for (uint32_t r : ad->reserved)
+        if (r != 0)
+            return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render_adaptive: reserved fields must be 0");
+    return accum_run(acc, params, ad, rounds, stats);
+}
+
+extern "C" int rt_accum_resolve(rt_accum *acc, uint32_t flags, float *fb_rgb) {
+    if (!acc || !fb_rgb || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: null argument or flags other than RT_FLAG_DEVICE_FB");
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)acc->width * acc->height;
+    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
+    if (!device_fb)
+        if (int rc = s->ensure_fb(3 * n); rc != RT_OK)
+            return rc;
+    HIP_TRY(rt::launch_accum_image(acc->R, device_fb ? fb_rgb : s->d_fb, s->stream));
+    if (!device_fb)
+        HIP_TRY(hipMemcpyAsync(fb_rgb, s->d_fb, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb8) {
+    if (!acc || !rgb8 || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_rgb8: null argument or flags other than RT_FLAG_DEVICE_FB");
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t n = acc->width * acc->height;
+    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
+    int rc = s->ensure_fb(3ull * n);
+    if (rc == RT_OK)
+        rc = s->ensure_film(device_fb ? 0 : 3ull * n);
+    if (rc != RT_OK)
+        return rc;
+    uint8_t *d_rgb8 = device_fb ? rgb8 : s->d_rgb8;
+    HIP_TRY(rt::launch_accum_image(acc->R, s->d_fb, s->stream));
+    HIP_TRY(rt::launch_film(s->d_fb, d_rgb8, n, 0, 1, n, s->d_film_table, s->stream)); // image.h:49-82, as rt_render_rgb8
+    if (!device_fb)
+        HIP_TRY(hipMemcpyAsync(rgb8, d_rgb8, 3ull * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb, uint32_t *samples, float *error) {
+    if (!acc)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_read: null accumulator");
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)acc->width * acc->height;
+    if (sum_rgb)
+        HIP_TRY(hipMemcpyAsync(sum_rgb, acc->R.sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
+    if (even_sum_rgb)
+        HIP_TRY(hipMemcpyAsync(even_sum_rgb, acc->R.even_sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
+    if (samples)
+        HIP_TRY(hipMemcpyAsync(samples, acc->R.count, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    if (error)
+        HIP_TRY(hipMemcpyAsync(error, acc->R.err, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}

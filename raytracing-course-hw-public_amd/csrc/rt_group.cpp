@@ -160,6 +160,23 @@ hipError_t copy_blocks(char *slab, char *image, bool pack, const Blocks &b, uint
     return hipSuccess;
 }
 
+// the work counters of one result added to another's (views rendered one after the other; the GPUs of one render). The time and pass
+// fields are the caller's: a sum in the first case, the slowest GPU's in the second.
+void add_counters(rt_stats &sum, const rt_stats &one) {
+    sum.samples += one.samples;
+    sum.casts += one.casts;
+    sum.nodes_visited += one.nodes_visited;
+    sum.box_tests += one.box_tests;
+    sum.tri_tests += one.tri_tests;
+    sum.shaded_hits += one.shaded_hits;
+    sum.light_queries += one.light_queries;
+    sum.light_nodes += one.light_nodes;
+    sum.light_box_tests += one.light_box_tests;
+    sum.light_tri_tests += one.light_tri_tests;
+    sum.light_hits += one.light_hits;
+    sum.texel_fetches += one.texel_fetches;
+}
+
 } // namespace
 
 int group_size(const Group *g) { return g ? (int)g->ranks.size() : 0; }
@@ -266,18 +283,7 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
                 rc != RT_OK)
                 return rc;
             if (stats) {
-                sum.samples += one.samples;
-                sum.casts += one.casts;
-                sum.nodes_visited += one.nodes_visited;
-                sum.box_tests += one.box_tests;
-                sum.tri_tests += one.tri_tests;
-                sum.shaded_hits += one.shaded_hits;
-                sum.light_queries += one.light_queries;
-                sum.light_nodes += one.light_nodes;
-                sum.light_box_tests += one.light_box_tests;
-                sum.light_tri_tests += one.light_tri_tests;
-                sum.light_hits += one.light_hits;
-                sum.texel_fetches += one.texel_fetches;
+                add_counters(sum, one);
                 sum.kernel_ms += one.kernel_ms;
                 sum.dominant_ms += one.dominant_ms;
                 sum.dominant_launches += one.dominant_launches;
@@ -487,18 +493,7 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
         std::memset(stats, 0, sizeof(*stats));
         for (uint32_t r = 0; r < G; ++r) {
             const rt_stats &s = sts[r];
-            stats->samples += s.samples;
-            stats->casts += s.casts;
-            stats->nodes_visited += s.nodes_visited;
-            stats->box_tests += s.box_tests;
-            stats->tri_tests += s.tri_tests;
-            stats->shaded_hits += s.shaded_hits;
-            stats->light_queries += s.light_queries;
-            stats->light_nodes += s.light_nodes;
-            stats->light_box_tests += s.light_box_tests;
-            stats->light_tri_tests += s.light_tri_tests;
-            stats->light_hits += s.light_hits;
-            stats->texel_fetches += s.texel_fetches;
+            add_counters(*stats, s);
             stats->kernel_ms = std::max(stats->kernel_ms, s.kernel_ms); // GPUs run concurrently: the slowest one counts
             stats->dominant_ms = std::max(stats->dominant_ms, s.dominant_ms);
             stats->dominant_launches = std::max(stats->dominant_launches, s.dominant_launches);

@@ -30,7 +30,7 @@ rt_scene *group_primary(Group *g); // replica on devices[0]: serves the probe en
 // buffer (host memory, or device memory of devices[0] with RT_FLAG_DEVICE_FB). views != null: rt_render_views / _rgb8 (the
 // blocks and the gather run over the view-major virtual image; reference RNG renders the views one after the other)
 int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_views, float *fb, uint8_t *rgb8, rt_stats *stats);
-// rt_scene.cpp: rt_render_views' checks of the arguments alone (n_views, reserved fields, size, reference-RNG sharding)
+// rt_render.cpp: rt_render_views' checks of the arguments alone (n_views, reserved fields, size, reference-RNG sharding)
 int check_views(const rt_params *p, const rt_view *views, uint32_t n_views);
 
 } // namespace rt

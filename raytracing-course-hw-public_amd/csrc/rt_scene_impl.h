@@ -1,0 +1,257 @@
+// rt_scene_impl.h — what the host files behind include/rt_abi.h share (internal): the definition of rt_scene and the few helpers
+// with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_accum_host.cpp (rt_accum_*) and
+// rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through rt_group.h.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <chrono>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/rt_abi.h"
+#include "bvh_build.h"
+#include "rt_device_types.h"
+#include "rt_error.h"
+#include "rt_film.h"
+#include "rt_group.h"
+#include "rt_kernels.h"
+
+#define HIP_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess)                                                                             \
+            return rt::fail(e_ == hipErrorOutOfMemory ? RT_ERR_OOM : (e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP), \
+                            std::string(#expr) + ": " + hipGetErrorString(e_));                           \
+    } while (0)
+
+namespace rt {
+// wf_extend_packet (primary rays as coherent packets) pays off only while a wave's 64 rays stay together; its own census
+// (lanes served per trip) decides per configuration whether later passes keep using it. One per owner of passes: the scene for
+// rt_render*, every accumulator for its own (rt_render.cpp launch_pass).
+struct PacketPolicy {
+    uint64_t key = 0; // the configuration `off` was measured on
+    bool off = false;
+    uint32_t lanes_x100 = 0; // last packet census: lanes served per trip x 100 (rt_stats.packet_lanes_x100)
+};
+} // namespace rt
+
+struct rt_scene {
+    rt::Group *group = nullptr; // multi-GPU scene: replicas + RCCL communicator (rt_group.cpp); the fields below stay unused
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    rt::EventPool ext_events; // (start, stop) per wf_extend launch of the current render; reused by every render
+    DevScene dev{};
+    rt_camera cam{};
+    std::vector<void *> owned;
+    std::shared_ptr<const rt::PreparedScene> prep; // the host half of rt_create, shared by the replicas of a multi-GPU scene
+    rt::HostBvh rebuilt_bvh;   // device-built scene BVH: the reference-style node list, reconstructed from HBM on demand
+    bool device_built = false; // scene BVH built by rt_bvh_device.hip
+    bool wide_built = false;   // RT_BUILD_WIDE: the scene BVH in HBM is the 8-wide quantised tree (wide_build.cpp); host_bvh[0] is the
+                               // binary tree it was collapsed from when that one was built on the host
+    uint32_t wide_depth = 0;
+    double wide_ms = 0, wide_cost = 0;
+    uint32_t dev_n_inner[2] = {0, 0};
+    double build_ms = 0, build_upload_ms = 0;
+    uint32_t *d_counter = nullptr;
+    DevStats *d_stats = nullptr;
+    float *d_fb = nullptr;
+    size_t fb_capacity = 0; // floats
+    uint8_t *d_rgb8 = nullptr; // device film output (rt_render_rgb8 with a host destination, rt_film_rgb8)
+    size_t rgb8_capacity = 0;
+    WfView *d_views = nullptr; // the view table of the wavefront pipeline (one record per view of the render), grown on demand
+    uint32_t views_capacity = 0;
+    rt::FilmTable *d_film_table = nullptr;
+
+    int ensure_fb(size_t fb_floats) {
+        if (fb_capacity >= fb_floats)
+            return RT_OK;
+        if (d_fb)
+            (void)hipFree(d_fb);
+        d_fb = nullptr;
+        fb_capacity = 0;
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, fb_floats * sizeof(float)));
+        d_fb = static_cast<float *>(q);
+        fb_capacity = fb_floats;
+        return RT_OK;
+    }
+    // device film prerequisites: the verified threshold table (host/film.cpp) and, optionally, an rgb8 staging buffer
+    int ensure_film(size_t rgb8_bytes) {
+        if (!d_film_table) {
+            rt::FilmTable t{};
+            if (!rt::film_table(t.thr, t.special))
+                return rt::fail(RT_ERR_UNSUPPORTED, "device film: the host libm's powf failed the monotonicity check; use rt_render + rt_tonemap_rgb8");
+            void *q = nullptr;
+            HIP_TRY(hipMalloc(&q, sizeof(t)));
+            d_film_table = static_cast<rt::FilmTable *>(q);
+            HIP_TRY(hipMemcpyAsync(d_film_table, &t, sizeof(t), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipStreamSynchronize(stream)); // `t` is a local
+        }
+        if (rgb8_capacity < rgb8_bytes) {
+            if (d_rgb8)
+                (void)hipFree(d_rgb8);
+            d_rgb8 = nullptr;
+            rgb8_capacity = 0;
+            void *q = nullptr;
+            HIP_TRY(hipMalloc(&q, rgb8_bytes));
+            d_rgb8 = static_cast<uint8_t *>(q);
+            rgb8_capacity = rgb8_bytes;
+        }
+        return RT_OK;
+    }
+    int ensure_views(uint32_t n) {
+        if (views_capacity >= n)
+            return RT_OK;
+        if (d_views)
+            (void)hipFree(d_views);
+        d_views = nullptr;
+        views_capacity = 0;
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, (size_t)n * sizeof(WfView)));
+        d_views = static_cast<WfView *>(q);
+        views_capacity = n;
+        return RT_OK;
+    }
+    int num_cus = 0;
+    int blocks_per_cu = 8; // upper bound on resident 256-thread blocks per CU; surplus blocks find the ticket exhausted
+    // wavefront pipeline workspace (rt_wavefront.hip), sized for wf_paths_cap paths / wf_pixels_cap pixels per pass
+    uint64_t wf_paths_cap = 0, wf_pixels_cap = 0;
+    uint32_t wf_depth_cap = 0;
+    std::vector<void *> wf_owned;
+    WfPath *wf_paths[2] = {nullptr, nullptr};
+    uint32_t *wf_stripes = nullptr;
+    WfHit *wf_hits = nullptr;
+    WfFold *wf_fold = nullptr;
+    RtF4 *wf_samples = nullptr, *wf_accum = nullptr;
+    uint32_t *wf_counters = nullptr;
+    void *wf_stack_overflow = nullptr; // wf_extend's evicted stack frames (RingStackT): RT_MAX_STACK x grid threads x 16 B
+    uint32_t wf_stack_stride = 0;
+    uint32_t *wf_sort_keys[2] = {nullptr, nullptr}, *wf_sort_vals[2] = {nullptr, nullptr};
+    void *wf_sort_temp = nullptr;
+    size_t wf_sort_temp_bytes = 0;
+    uint32_t *wf_host_count = nullptr; // pinned, 48 words: queue size per bounce, then wf_extend_packet's census (rt_kernels.h WfHostSync)
+    std::vector<hipEvent_t> wf_count_events; // one per bounce: "the size of the queue entering this bounce has reached wf_host_count"
+    rt::PacketPolicy pkt; // of rt_render* (an accumulator keeps its own)
+    std::vector<hipEvent_t> pass_events; // rt_params.progress: one per pass
+
+    int ensure_wavefront(uint64_t paths, uint64_t pixels, uint32_t depth) {
+        if (paths <= wf_paths_cap && pixels <= wf_pixels_cap && depth <= wf_depth_cap)
+            return RT_OK;
+        for (void *p : wf_owned)
+            (void)hipFree(p);
+        wf_owned.clear();
+        wf_paths_cap = wf_pixels_cap = 0;
+        wf_depth_cap = 0;
+        auto alloc = [&](size_t bytes, void **out) -> int {
+            *out = nullptr;
+            hipError_t e = hipMalloc(out, bytes ? bytes : 16);
+            if (e != hipSuccess)
+                return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("wavefront workspace: ") + hipGetErrorString(e));
+            wf_owned.push_back(*out);
+            return RT_OK;
+        };
+        int rc;
+        // + 64: wf_shade's sub-queue regions cover whole wave slots (rt_device_types.h, WF_STRIPES)
+        if ((rc = alloc((paths + 64) * sizeof(WfPath), (void **)&wf_paths[0])) != RT_OK || (rc = alloc((paths + 64) * sizeof(WfPath), (void **)&wf_paths[1])) != RT_OK ||
+            (rc = alloc(WF_STRIPE_BUF_WORDS * sizeof(uint32_t), (void **)&wf_stripes)) != RT_OK ||
+            (rc = alloc(paths * sizeof(WfHit), (void **)&wf_hits)) != RT_OK || (rc = alloc(paths * depth * sizeof(WfFold), (void **)&wf_fold)) != RT_OK ||
+            (rc = alloc(paths * sizeof(RtF4), (void **)&wf_samples)) != RT_OK || (rc = alloc(pixels * sizeof(RtF4), (void **)&wf_accum)) != RT_OK ||
+            (rc = alloc(WF_CNT_ALLOC_WORDS * sizeof(uint32_t), (void **)&wf_counters)) != RT_OK)
+            return rc;
+        wf_stack_stride = (uint32_t)num_cus * 8u * 256u; // the wf_extend grid: 8 blocks of 256 threads per CU
+        if ((rc = alloc((size_t)RT_MAX_STACK * wf_stack_stride * 16, &wf_stack_overflow)) != RT_OK)
+            return rc;
+        wf_sort_temp_bytes = rt::wavefront_sort_temp_bytes(paths);
+        if ((rc = alloc(paths * 4, (void **)&wf_sort_keys[0])) != RT_OK || (rc = alloc(paths * 4, (void **)&wf_sort_keys[1])) != RT_OK ||
+            (rc = alloc(paths * 4, (void **)&wf_sort_vals[0])) != RT_OK || (rc = alloc(paths * 4, (void **)&wf_sort_vals[1])) != RT_OK ||
+            (rc = alloc(wf_sort_temp_bytes, &wf_sort_temp)) != RT_OK)
+            return rc;
+        // on the scene's own (non-blocking) stream: a null-stream memset is not ordered with the kernels launched there and
+        // could land after wf_generate had set the queue size
+        HIP_TRY(hipMemsetAsync(wf_counters, 0, WF_CNT_ALLOC_WORDS * sizeof(uint32_t), stream));
+        wf_paths_cap = paths;
+        wf_pixels_cap = pixels;
+        wf_depth_cap = depth;
+        return RT_OK;
+    }
+
+    // the workspace half of a WfLaunch (after ensure_wavefront): queues, hit records, counters, stack workspace, sort buffers
+    void wf_bind(WfLaunch &W) {
+        W.paths_in = wf_paths[0];
+        W.paths_out = wf_paths[1];
+        W.hits = wf_hits;
+        W.fold = wf_fold;
+        W.sample_out = wf_samples;
+        W.accum = wf_accum;
+        W.counters = wf_counters;
+        W.stripes = wf_stripes;
+        W.stack_overflow = wf_stack_overflow;
+        W.stack_stride = wf_stack_stride;
+        for (int k = 0; k < 2; ++k) { // sort_vals[1] also carries the unsorted order (sort_mode 0)
+            W.sort_keys[k] = wf_sort_keys[k];
+            W.sort_vals[k] = wf_sort_vals[k];
+        }
+        W.sort_temp = wf_sort_temp;
+        W.sort_temp_bytes = wf_sort_temp_bytes;
+        W.packet_census = reinterpret_cast<unsigned long long *>(wf_counters + WF_CNT_CENSUS);
+    }
+
+    ~rt_scene() {
+        if (group) {
+            rt::group_destroy(group);
+            return;
+        }
+        (void)hipSetDevice(device);
+        if (wf_host_count)
+            (void)hipHostFree(wf_host_count);
+        for (hipEvent_t ev : wf_count_events)
+            (void)hipEventDestroy(ev);
+        for (hipEvent_t ev : pass_events)
+            (void)hipEventDestroy(ev);
+        for (void *p : wf_owned)
+            (void)hipFree(p);
+        for (void *p : owned)
+            (void)hipFree(p);
+        if (d_fb)
+            (void)hipFree(d_fb);
+        if (d_rgb8)
+            (void)hipFree(d_rgb8);
+        if (d_views)
+            (void)hipFree(d_views);
+        if (d_film_table)
+            (void)hipFree(d_film_table);
+        ext_events.destroy();
+        if (ev0)
+            (void)hipEventDestroy(ev0);
+        if (ev1)
+            (void)hipEventDestroy(ev1);
+        if (stream)
+            (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace rt {
+// rt_scene.cpp
+const HostBvh &prepared_host_bvh(const rt_scene *s, int which); // the host-built trees kept by the scene's PreparedScene
+// rt_render.cpp: views, the check of the pass options, the wavefront pass policy and the statistics of a finished call
+WfView make_view(const rt_camera &cam, uint32_t width, uint32_t height, uint64_t seed);
+void set_camera(DevScene &D, const float *pos, const float *right, const float *up, const float *fwd);
+int check_pass_params(const rt_params *p, const char *fn);
+uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
+hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
+                       const WfAccum *acc);
+int fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats);
+
+// Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are
+// still in flight (a later ensure_wavefront / rt_destroy would free memory under them)
+template <class Queue> int queue_and_wait(rt_scene *s, Queue queue) {
+    if (int rc = queue(); rc != RT_OK) {
+        (void)hipStreamSynchronize(s->stream);
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+} // namespace rt

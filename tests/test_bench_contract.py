@@ -181,13 +181,13 @@ def test_library_carries_the_hash_of_its_sources(rt):
     """librt_amd.so is stamped at build time with the sha256 of csrc/device_sources.txt's files (rt_source_stamp); bench.py hashes the
     same list at run time and refuses to measure a library built from other sources. After a build the two must agree, and the
     list must name the kernels, the layouts, the builders, the launch policy and the Makefile (a launch-geometry change
-    in rt_scene.cpp or a flag in the Makefile used to keep quoting stale counters)."""
+    in the host launch code or a flag in the Makefile used to keep quoting stale counters)."""
     sys.path.insert(0, ROOT)
     import bench
 
     assert rt.lib().rt_source_stamp().decode() == bench.kernel_source_hash()
     names = {os.path.basename(f) for f in bench.DEVICE_SOURCES}
-    for must in ("rt_wavefront.hip", "rt_wide.hip", "rt_device_lib.h", "rt_device_types.h", "rt_kernels.h", "rt_scene.cpp", "wide_build.cpp", "rt_bvh_device.hip", "Makefile", "rt_devspec.h"):
+    for must in ("rt_wavefront.hip", "rt_wide.hip", "rt_device_lib.h", "rt_device_types.h", "rt_kernels.h", "rt_scene.cpp", "rt_scene_impl.h", "rt_render.cpp", "rt_accum_host.cpp", "rt_probe.cpp", "wide_build.cpp", "rt_bvh_device.hip", "Makefile", "rt_devspec.h"):
         assert must in names, must
     for f in bench.DEVICE_SOURCES:
         assert os.path.exists(os.path.join(bench.CSRC, f)), f
