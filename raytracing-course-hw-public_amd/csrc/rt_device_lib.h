@@ -56,6 +56,20 @@ DEV float pow5(float x) { // raytracer.h:28-38, p = 5
     return x * ((x2 * x2) * 1.0f);
 }
 DEV bool isnan_f(float x) { return x != x; }
+// number of set bits of a ballot below this lane: the lane's rank among the ballot's lanes
+DEV uint32_t lane_rank(unsigned long long mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u)); }
+// exclusive prefix sum over the wave of a per-lane count n < 16, one ballot per bit plane; `total`: the wave's sum
+DEV uint32_t wave_prefix_sum4(uint32_t n, uint32_t &total) {
+    uint32_t off = 0;
+    total = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const unsigned long long m = __ballot((n >> b) & 1u);
+        off += lane_rank(m) << b;
+        total += (uint32_t)__popcll(m) << b;
+    }
+    return off;
+}
 
 struct C4 {
     float r, g, b, a;
@@ -128,6 +142,17 @@ template <> struct Rng<RT_RNG_REFERENCE> {
 };
 // std::uniform_real_distribution<float>(a, b)(rng) = canonical * (b - a) + a
 template <class R> DEV float uniform_real(R &r, float a, float b) { return r.canonical() * (b - a) + a; }
+
+// gen_ray (raytracer.h:527-538): the two jitter draws, the screen position and the normalised direction of a sample of pixel `pix`, with the
+// tangents hoisted. The megakernel and the wavefront pipeline both call this, so their primary rays are the same operation sequence.
+template <class R> DEV V3 gen_ray_dir(R &rng, uint32_t pix, uint32_t width, uint32_t height, float tan_x, float tan_y, V3 cam_right, V3 cam_up, V3 cam_fwd) {
+    const uint32_t x = pix % width, y = pix / width;
+    float ox = uniform_real(rng, 0.0f, 1.0f);
+    float oy = uniform_real(rng, 0.0f, 1.0f);
+    float sx = (2 * ((float)(int)x + ox) / (float)width - 1) * tan_x;
+    float sy = (2 * ((float)(int)y + oy) / (float)height - 1) * tan_y;
+    return norm(sx * cam_right - sy * cam_up + 1.0f * cam_fwd);
+}
 
 // ---------------------------------------------------------------------------------------------- primitives
 // Exact quotient a/d from a precomputed r = RN(1/d): q0 = RN(a*r), one FMA residual e = a - d*q0 and one FMA correction
@@ -1154,6 +1179,31 @@ DEV bool ticket_take(uint32_t *counters, uint32_t n_in, uint32_t chunk, TicketSt
         }
         ts.part = (ts.part + 1u) & 7u; // this part is used up: help the next one
         ++ts.tried;
+    }
+}
+// The refill of the per-lane persistent kernels (wf_extend, wf_extend_wide). A wave refills its idle lanes once `refill_min` of them have finished
+// (a refill stalls the wave on the ray loads) from its private range [q_lo, q_hi) of queue positions; a new range of `chunk` positions is taken
+// with ONE atomic when it runs dry (a single ticket word saturates near 90 M atomics/s, so tickets are taken per chunk, not per refill).
+// start(jq) begins the traversal of the ray at queue position jq in the calling lane; `exhausted` (wave-uniform): the queue is used up.
+template <class START>
+DEV void ticket_refill(uint32_t *counters, uint32_t n_in, uint32_t chunk, int refill_min, bool idle, bool &exhausted, uint32_t &q_lo, uint32_t &q_hi, TicketState &tks, START start) {
+    const unsigned long long im = __ballot(idle);
+    const int n_idle = __popcll(im);
+    if (!exhausted && (n_idle >= refill_min || n_idle == (int)__popcll(__ballot(1)))) {
+        if (q_lo == q_hi)
+            exhausted = !ticket_take(counters, n_in, chunk, tks, q_lo, q_hi);
+        const uint32_t rank = lane_rank(im);
+        const uint32_t avail = q_hi - q_lo;
+        if (idle && rank < avail)
+            start(q_lo + rank);
+        q_lo += (uint32_t)n_idle < avail ? (uint32_t)n_idle : avail;
+    }
+}
+// the packet kernels' census (trips, lanes served; wave-uniform), summed over the launch's waves: what the host keeps or drops a packet kernel on
+DEV void census_flush(unsigned long long *census, unsigned long long n_trips, unsigned long long n_lanes) {
+    if ((threadIdx.x & 63u) == 0u && census && n_trips != 0ull) {
+        atomicAdd(census, n_trips);
+        atomicAdd(census + 1, n_lanes);
     }
 }
 

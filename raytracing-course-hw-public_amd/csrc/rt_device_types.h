@@ -183,6 +183,7 @@ struct DevStats { // device-side counters, see rt_stats in include/rt_abi.h
 // Queue record, one per live path (64 B = one HBM request): the ray (first 32 B), what wf_extend needs to start its traversal
 // without arithmetic (next 16 B) and the path's RNG state (last 16 B). The state of a path travels WITH its ray through the queues, so wf_shade finds ray
 // and state with one gather and writes both with the coalesced queue traffic instead of a random per-path record.
+// These structs DESCRIBE the records; the kernels read and write them only through rt_wf_records.h, which implements exactly this layout.
 struct alignas(64) WfPath {
     float o[3];
     float dx;
@@ -198,7 +199,7 @@ static_assert(sizeof(WfPath) == 64, "WfPath must be 64 bytes");
 #define WF_ORDER_SLOT_MASK 0x3FFFFFFFu /* WfLaunch::order: queue slot; max_paths <= 2^30 */
 #define WF_ORDER_CLASS_SHIFT 30
 struct alignas(16) WfHit { // 16 B: closest hit of the ray in the same queue slot
-    uint32_t k;            // DevTri index (scene-BVH order) or RT_NONE
+    uint32_t k;            // DevTri index (scene-BVH order) or RT_NONE: a miss, stored with b = c = t = 0
     float b, c, t;
 };
 struct alignas(16) RtF4 {

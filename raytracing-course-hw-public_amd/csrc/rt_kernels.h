@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "rt_device_types.h"
@@ -14,6 +15,13 @@
         hipLaunchKernelGGL(__VA_ARGS__);     \
         hipGetLastError();                   \
     })
+
+// Run-time bools -> template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}); inside f the
+// arguments are constant expressions (`kernel<A, B>`, `if constexpr (A)`). Every launcher picks its kernel instantiation this way.
+template <class F> auto with_bools(F &&f) { return f(); }
+template <class F, class... Rest> auto with_bools(F &&f, bool b, Rest... rest) {
+    return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...) : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
 
 namespace rt {
 // HIP events for per-launch timing, created once per scene and reused by every render (no create/destroy inside the

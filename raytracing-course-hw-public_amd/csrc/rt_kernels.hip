@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const De
         // ---- refill idle lanes: ballot + prefix count, one ticket atomic per wave
         if (state == ST_IDLE && !exhausted) {
             const unsigned long long m = __ballot(1);
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const uint32_t rank = lane_rank(m);
             uint32_t base = 0;
             if (rank == 0)
                 base = atomicAdd(L.counter, (uint32_t)__popcll(m));
@@ -119,12 +119,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const De
         if (state == ST_NEW) {
             if constexpr (MODE == RT_RNG_DEVICE)
                 rt_xoshiro_seed(&rng.g, L.seed, pix, s);
-            const uint32_t x = pix % L.width, y = pix / L.width;
-            float ox = uniform_real(rng, 0.0f, 1.0f);
-            float oy = uniform_real(rng, 0.0f, 1.0f);
-            float sx = (2 * ((float)(int)x + ox) / (float)L.width - 1) * L.tan_x;
-            float sy = (2 * ((float)(int)y + oy) / (float)L.height - 1) * L.tan_y;
-            V3 rd = norm(sx * cam_right - sy * cam_up + 1.0f * cam_fwd);
+            const V3 rd = gen_ray_dir(rng, pix, L.width, L.height, L.tan_x, L.tan_y, cam_right, cam_up, cam_fwd);
             depth_left = S.ray_depth;
             nb = 0;
             st.cast();
@@ -311,15 +306,9 @@ hipError_t launch_bg_at(const DevScene &S, const float *dirs, uint32_t n, float 
 }
 
 hipError_t launch_render(const DevScene &S, const RenderLaunch &L, bool stats, int blocks, hipStream_t stream) {
-    dim3 grid(blocks), block(256);
-    if (L.rng_mode == RT_RNG_REFERENCE) {
-        if (stats)
-            return RT_LAUNCH_CHECKED((render_kernel<RT_RNG_REFERENCE, true>), grid, block, 0, stream, S, L);
-        return RT_LAUNCH_CHECKED((render_kernel<RT_RNG_REFERENCE, false>), grid, block, 0, stream, S, L);
-    }
-    if (stats)
-        return RT_LAUNCH_CHECKED((render_kernel<RT_RNG_DEVICE, true>), grid, block, 0, stream, S, L);
-    return RT_LAUNCH_CHECKED((render_kernel<RT_RNG_DEVICE, false>), grid, block, 0, stream, S, L);
+    return with_bools(
+        [&](auto REF, auto ST) { return RT_LAUNCH_CHECKED((render_kernel<REF ? RT_RNG_REFERENCE : RT_RNG_DEVICE, ST>), dim3(blocks), dim3(256), 0, stream, S, L); },
+        L.rng_mode == RT_RNG_REFERENCE, stats);
 }
 
 hipError_t launch_cast(const DevScene &S, const float *rays, uint32_t n, uint32_t *prim, float *bct, hipStream_t stream) {

@@ -29,6 +29,7 @@
 
 #include "rt_device_lib.h"
 #include "rt_kernels.h"
+#include "rt_wf_records.h"
 
 namespace {
 
@@ -80,17 +81,9 @@ DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32
     const V3 cam_pos = ld3(view.pos), cam_right = ld3(view.right), cam_up = ld3(view.up), cam_fwd = ld3(view.fwd);
     Rng<RT_RNG_DEVICE> rng;
     rt_xoshiro_seed(&rng.g, view.seed, pix, s);
-    const uint32_t x = pix % L.width, y = pix / L.width;
-    float ox = uniform_real(rng, 0.0f, 1.0f);
-    float oy = uniform_real(rng, 0.0f, 1.0f);
-    float sx = (2 * ((float)(int)x + ox) / (float)L.width - 1) * view.tan_x;
-    float sy = (2 * ((float)(int)y + oy) / (float)L.height - 1) * view.tan_y;
-    V3 rd = norm(sx * cam_right - sy * cam_up + 1.0f * cam_fwd);
-    float4 *rq = reinterpret_cast<float4 *>(L.paths_in + i);
-    rq[0] = make_float4(cam_pos.x, cam_pos.y, cam_pos.z, rd.x);
-    rq[1] = make_float4(rd.y, rd.z, __uint_as_float(i | (next_shade_class(rng, S.lights.n_tris != 0) << WF_ORDER_CLASS_SHIFT)), __uint_as_float(L.ray_depth)); // path id (+ class); full budget, no pending frames
-    rq[2] = make_float4(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z, __uint_as_float(ray_fast_ok_ray(cam_pos, rd) ? 1u : 0u));
-    *reinterpret_cast<uint4 *>(rq + 3) = make_uint4(rng.g.s[0], rng.g.s[1], rng.g.s[2], rng.g.s[3]);
+    const V3 rd = gen_ray_dir(rng, pix, L.width, L.height, view.tan_x, view.tan_y, cam_right, cam_up, cam_fwd);
+    // path i in slot i: full budget, no pending frames
+    wf_store_path(L.paths_in + i, wf_pack(cam_pos, rd, i, next_shade_class(rng, S.lights.n_tris != 0), L.ray_depth, 0u, rng.g));
 }
 
 template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
@@ -156,14 +149,8 @@ template <bool STATS>
 DEV void leaf_batch(Trav &T, const DevBvh &bvh, bool at_leaf, uint16_t *s_owner, unsigned long long *s_min, float2 *s_bc, LaneStats<STATS> &st) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n = at_leaf ? RT_LEAF_CNT(T.cur) : 0u;
-    uint32_t off = 0, total = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { // exclusive prefix sum of n over the wave, one ballot per bit plane
-        const unsigned long long m = __ballot((n >> b) & 1u);
-        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        off += below << b;
-        total += (uint32_t)__popcll(m) << b;
-    }
+    uint32_t total;
+    const uint32_t off = wave_prefix_sum4(n, total);
     // Owner table: position off + t belongs to (lane, t) for t < n. Every waiting lane writes ALL RT_LEAF_COOP_MAX
     // entries, highest t first, without a per-entry predicate: an entry with t >= n lands on position off' + t' of a
     // later lane (off' > off, hence t' < t), whose own store of that position is issued LATER (a wave's LDS
@@ -245,30 +232,14 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
     uint32_t q_lo = 0, q_hi = 0; // this wave's private range of queue positions
     TicketState tks = ticket_init();
     for (;;) {
-        const bool idle = T.cur == T_DONE;
-        const unsigned long long im = __ballot(idle);
-        const int n_idle = __popcll(im);
-        if (!exhausted && (n_idle >= RT_EXT_REFILL_MIN || n_idle == (int)__popcll(__ballot(1)))) {
-            // refill from the wave's private ticket range [q_lo, q_hi); a new range of RT_EXT_CHUNK queue positions is
-            // taken with ONE atomic when it runs dry (a single ticket word saturates near 90 M atomics/s, so tickets
-            // are taken per chunk, not per refill)
-            if (q_lo == q_hi)
-                exhausted = !ticket_take(L.counters, n_in, (uint32_t)RT_EXT_CHUNK, tks, q_lo, q_hi); // false: the queue is used up
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(im >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)im, 0u));
-            const uint32_t avail = q_hi - q_lo;
-            if (idle && rank < avail) {
-                const uint32_t jq = q_lo + rank;
-                const uint32_t j = L.order ? L.order[jq] & WF_ORDER_SLOT_MASK : jq; // coherence-sorted processing order
-                const float4 *rq = reinterpret_cast<const float4 *>(L.paths_in + j);
-                const float4 r0 = rq[0], r1 = rq[1], r2 = rq[2];
-                slot = jq; // the hit goes to the queue POSITION (see WfLaunch::hits)
-                trav_init_stored<GB>(T, S.scene, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r2.x, r2.y, r2.z), __float_as_uint(r2.w) != 0u);
-                stk.reset();
-                if (T.cur == T_DONE) // no geometry at all: immediate miss
-                    *reinterpret_cast<float4 *>(L.hits + jq) = make_float4(__uint_as_float(RT_NONE), 0.f, 0.f, 0.f);
-            }
-            q_lo += (uint32_t)n_idle < avail ? (uint32_t)n_idle : avail;
-        }
+        ticket_refill(L.counters, n_in, (uint32_t)RT_EXT_CHUNK, RT_EXT_REFILL_MIN, T.cur == T_DONE, exhausted, q_lo, q_hi, tks, [&](uint32_t jq) {
+            const WfRay ray = wf_load_ray(L.paths_in + wf_order_slot(L, jq)); // coherence-sorted processing order
+            slot = jq; // the hit goes to the queue POSITION (see WfLaunch::hits)
+            trav_init_stored<GB>(T, S.scene, ray.o, ray.d, ray.r, ray.fast);
+            stk.reset();
+            if (T.cur == T_DONE) // no geometry at all: immediate miss
+                wf_store_hit(L.hits + jq, wf_miss());
+        });
         // Bounded unwind: ONE stack pop per trip for every lane that has to unwind (a lane whose pop ends in a pruned far
         // child pops again next trip and sits out one node step: ~1 in 5 unwinding lanes). The unwind used to be a loop that
         // ran until no lane of the wave was left in T_POP: 1.2 iterations per trip at ~7 of 64 lanes, each a full LDS round
@@ -278,7 +249,7 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
         const bool was_live = T.cur != T_DONE;
         trav_pop_once<GB>(T, stk);
         if (was_live && T.cur == T_DONE)
-            *reinterpret_cast<float4 *>(L.hits + slot) = make_float4(__uint_as_float(T.best.k), T.best.b, T.best.c, T.best.t);
+            wf_store_hit(L.hits + slot, T.best);
         const bool active = T.cur != T_DONE;
         const bool popping = T.cur == T_POP; // note: T_POP has the leaf bit set, it must be told apart first
         const bool at_leaf = active && !popping && (T.cur & RT_LEAF_FLAG) != 0 && RT_LEAF_CNT(T.cur) != 0;
@@ -351,10 +322,8 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
             const bool have = jq < n_in;
             T.cur = T_DONE;
             if (have) {
-                const uint32_t j = L.order ? L.order[jq] & WF_ORDER_SLOT_MASK : jq;
-                const float4 *rq = reinterpret_cast<const float4 *>(L.paths_in + j);
-                const float4 r0 = rq[0], r1 = rq[1], r2 = rq[2];
-                trav_init_stored<GB>(T, S.scene, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r2.x, r2.y, r2.z), __float_as_uint(r2.w) != 0u);
+                const WfRay ray = wf_load_ray(L.paths_in + wf_order_slot(L, jq));
+                trav_init_stored<GB>(T, S.scene, ray.o, ray.d, ray.r, ray.fast);
                 stk.reset();
             }
             for (;;) {
@@ -408,13 +377,10 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
                 }
             }
             if (have)
-                *reinterpret_cast<float4 *>(L.hits + jq) = make_float4(__uint_as_float(T.best.k), T.best.b, T.best.c, T.best.t);
+                wf_store_hit(L.hits + jq, T.best);
         }
     }
-    if (lane == 0u && L.packet_census && n_trips != 0ull) {
-        atomicAdd(L.packet_census, n_trips);
-        atomicAdd(L.packet_census + 1, n_lanes);
-    }
+    census_flush(L.packet_census, n_trips, n_lanes);
     st.flush(L.stats);
 }
 
@@ -426,16 +392,12 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
 __global__ __launch_bounds__(256) void wf_extend_prims(const DevScene S, const WfLaunch L) {
     const uint32_t n_in = L.counters[WF_CNT_IN];
     for (uint32_t jq = blockIdx.x * blockDim.x + threadIdx.x; jq < n_in; jq += gridDim.x * blockDim.x) {
-        const uint32_t j = L.order ? L.order[jq] & WF_ORDER_SLOT_MASK : jq;
-        const float4 *rq = reinterpret_cast<const float4 *>(L.paths_in + j);
-        const float4 r0 = rq[0], r1 = rq[1];
-        const float4 hq = *reinterpret_cast<const float4 *>(L.hits + jq);
-        Hit h;
-        h.k = __float_as_uint(hq.x), h.b = hq.y, h.c = hq.z, h.t = hq.w;
+        const WfHead ray = wf_load_head(L.paths_in + wf_order_slot(L, jq));
+        Hit h = wf_load_hit(L.hits + jq);
         const uint32_t k0 = h.k;
-        prims_closest(S, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), h);
+        prims_closest(S, ray.o, ray.d, h);
         if (h.k != k0)
-            *reinterpret_cast<float4 *>(L.hits + jq) = make_float4(__uint_as_float(h.k), h.b, h.c, h.t);
+            wf_store_hit(L.hits + jq, h);
     }
 }
 
@@ -472,30 +434,20 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
     auto shade_wave = [&](const uint32_t jq, const uint32_t j, const uint32_t wave_slot) {
         const bool active = jq < n_in;
         bool survive = false;
-        float4 nr0 = make_float4(0.f, 0.f, 0.f, 0.f), nr1 = nr0, nr2 = nr0;
-        uint4 nrng = make_uint4(0u, 0u, 0u, 0u);
+        WfPacked next;
         if (active) {
-            const float4 *rq = reinterpret_cast<const float4 *>(L.paths_in + j);
-            const float4 r0 = rq[0], r1 = rq[1];
-            const uint4 p0 = *reinterpret_cast<const uint4 *>(rq + 3);
-            const float4 hq = *reinterpret_cast<const float4 *>(L.hits + jq);
-            const uint32_t path = __float_as_uint(r1.z) & WF_ORDER_SLOT_MASK; // the top bits: this shade()'s sampler class (lane assignment above)
-            Rng<RT_RNG_DEVICE> rng;
-            rng.g.s[0] = p0.x, rng.g.s[1] = p0.y, rng.g.s[2] = p0.z, rng.g.s[3] = p0.w;
-            uint32_t depth_left = __float_as_uint(r1.w) & 0xFFFFu, nb = __float_as_uint(r1.w) >> 16;
-            Hit h;
-            h.k = __float_as_uint(hq.x), h.b = hq.y, h.c = hq.z, h.t = hq.w;
+            const WfHead in = wf_load_head(L.paths_in + j); // its class bits chose this lane (below); nothing here reads them
+            Rng<RT_RNG_DEVICE> rng = wf_load_rng(L.paths_in + j);
+            const Hit h = wf_load_hit(L.hits + jq);
+            const uint32_t path = in.id;
+            uint32_t depth_left = in.depth_left, nb = in.nb;
             if (h.k != RT_NONE)
                 depth_left -= 1; // shade(..., max_depth - 1)
-            const ShadeResult sr = shade_hit<Rng<RT_RNG_DEVICE>, STATS, ENV>(S, LT, h, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), rng, has_lights, stk, s_lin, s_gam, st);
+            const ShadeResult sr = shade_hit<Rng<RT_RNG_DEVICE>, STATS, ENV>(S, LT, h, in.o, in.d, rng, has_lights, stk, s_lin, s_gam, st);
             bool terminal = sr.terminal;
             V3 term = sr.term;
-            if (sr.push) { // emission + trace_ray(...) * scl (raytracer.h:588-590), folded when the path ends
-                float4 *fw = reinterpret_cast<float4 *>(L.fold + ((size_t)nb * L.n_paths + path));
-                fw[0] = make_float4(sr.emission.x, sr.emission.y, sr.emission.z, 0.f);
-                fw[1] = make_float4(sr.scl.x, sr.scl.y, sr.scl.z, 0.f);
-                ++nb;
-            }
+            if (sr.push) // emission + trace_ray(...) * scl (raytracer.h:588-590), folded when the path ends
+                wf_store_fold(wf_fold_at(L.fold, L.n_paths, nb++, path), sr.emission, sr.scl);
             if (!terminal && depth_left == 0) { // trace_ray(..., 0) returns (0,0,0) without casting (:596-598)
                 terminal = true;
                 term = mk(0, 0, 0);
@@ -509,30 +461,22 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
             } else {
                 survive = true;
                 st.cast();
-                nr0 = make_float4(sr.nro.x, sr.nro.y, sr.nro.z, sr.nrd.x);
-                nr1 = make_float4(sr.nrd.y, sr.nrd.z, __uint_as_float(path | (next_shade_class(rng, has_lights) << WF_ORDER_CLASS_SHIFT)), __uint_as_float(depth_left | (nb << 16)));
-                nr2 = make_float4(1.0f / sr.nrd.x, 1.0f / sr.nrd.y, 1.0f / sr.nrd.z, __uint_as_float(ray_fast_ok_ray(sr.nro, sr.nrd) ? 1u : 0u));
-                nrng = make_uint4(rng.g.s[0], rng.g.s[1], rng.g.s[2], rng.g.s[3]);
+                next = wf_pack(sr.nro, sr.nrd, path, next_shade_class(rng, has_lights), depth_left, nb, rng.g);
             }
         }
         // compact the survivors of this wave into the next queue: ballot + prefix sum, one atomic per wave, on the counter of
         // the sub-queue this wave slot belongs to (rt_device_types.h, WF_STRIPES)
         const unsigned long long m = __ballot(survive);
         if (m != 0ull) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const uint32_t rank = lane_rank(m);
             uint32_t obase = 0;
             const int leader = __ffsll((long long)m) - 1;
             const uint32_t stripe = /* the wave's own slot: a sub-queue holds what ITS slots can emit */ (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_slot) % WF_STRIPES;
             if ((int)(threadIdx.x & 63u) == leader)
                 obase = wf_stripe_base(stripe, n_slots) + atomicAdd(L.stripes + stripe * WF_STRIPE_WORDS, (uint32_t)__popcll(m));
             obase = __shfl(obase, leader);
-            if (survive) {
-                float4 *rw = reinterpret_cast<float4 *>(L.paths_out + obase + rank);
-                rw[0] = nr0;
-                rw[1] = nr1;
-                rw[2] = nr2;
-                *reinterpret_cast<uint4 *>(rw + 3) = nrng;
-            }
+            if (survive)
+                wf_store_path(L.paths_out + obase + rank, next);
         }
     };
     // Which of shade()'s three samplers a hit runs is decided by its path's next draws alone (alpha coin, technique coin, mix pick:
@@ -553,8 +497,8 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
             const uint32_t jq = wbase + 64u * q + lane;
             slot_of[q] = jq, cls[q] = 3u; // class 3: the positions behind the queue's (or the window's) end
             if (64u * q < win && jq < n_in) {
-                const uint32_t v = L.order ? L.order[jq] : jq;
-                slot_of[q] = v & WF_ORDER_SLOT_MASK, cls[q] = v >> WF_ORDER_CLASS_SHIFT;
+                const uint32_t v = wf_order_word(L, jq);
+                slot_of[q] = wf_word_slot(v), cls[q] = wf_word_class(v);
             }
         }
 #pragma unroll
@@ -562,7 +506,7 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
             const unsigned long long b0 = __ballot(cls[q] == 0u), b1 = __ballot(cls[q] == 1u), b2 = __ballot(cls[q] == 2u);
             const unsigned long long mine = cls[q] == 0u ? b0 : cls[q] == 1u ? b1 : cls[q] == 2u ? b2 : ~(b0 | b1 | b2);
             const uint32_t seen = cls[q] == 0u ? before[0] : cls[q] == 1u ? before[1] : cls[q] == 2u ? before[2] : 64u * q - before[0] - before[1] - before[2];
-            within[q] = seen + __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
+            within[q] = seen + lane_rank(mine);
             before[0] += (uint32_t)__popcll(b0), before[1] += (uint32_t)__popcll(b1), before[2] += (uint32_t)__popcll(b2);
         }
 #pragma unroll
@@ -618,21 +562,20 @@ __global__ __launch_bounds__(256) void wf_sort_keys(const DevScene S, const WfLa
                     k += step;
             pos = wf_stripe_base(k, n_slots) + (j - s_run[k]);
         }
-        const float4 *rq = reinterpret_cast<const float4 *>(L.paths_in + pos);
         if (direct) { // no record is read here: WfLaunch::order_classed = 0
             L.sort_vals[1][j] = pos;
             continue;
         }
-        const float4 r0 = rq[0], r1 = rq[1];
-        const uint32_t val = pos | (__float_as_uint(r1.z) & ~WF_ORDER_SLOT_MASK); // the class bits of the path word ride along above the slot (WfLaunch::order)
-        const float fx = (r0.x - S.bounds_lo[0]) * S.bounds_inv[0], fy = (r0.y - S.bounds_lo[1]) * S.bounds_inv[1], fz = (r0.z - S.bounds_lo[2]) * S.bounds_inv[2];
+        const WfHead ray = wf_load_head(L.paths_in + pos);
+        const V3 o = ray.o, d = ray.d;
+        const float fx = (o.x - S.bounds_lo[0]) * S.bounds_inv[0], fy = (o.y - S.bounds_lo[1]) * S.bounds_inv[1], fz = (o.z - S.bounds_lo[2]) * S.bounds_inv[2];
         const uint32_t cx = (uint32_t)fminf(fmaxf(fx * 64.0f, 0.0f), 63.0f), cy = (uint32_t)fminf(fmaxf(fy * 64.0f, 0.0f), 63.0f), cz = (uint32_t)fminf(fmaxf(fz * 64.0f, 0.0f), 63.0f);
         const uint32_t morton = spread3(cx) | (spread3(cy) << 1) | (spread3(cz) << 2);
-        const uint32_t oct = (r0.w < 0.0f ? 1u : 0u) | (r1.x < 0.0f ? 2u : 0u) | (r1.y < 0.0f ? 4u : 0u);
-        const float ax = __builtin_fabsf(r0.w), ay = __builtin_fabsf(r1.x), az = __builtin_fabsf(r1.y);
+        const uint32_t oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
+        const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
         const uint32_t sub = (ax > ay ? 1u : 0u) | (ay > az ? 2u : 0u) | (ax > az ? 4u : 0u); // which of the octant's 8 sub-cones
         L.sort_keys[0][j] = (oct << 21) | (morton << 3) | sub;
-        L.sort_vals[0][j] = val;
+        L.sort_vals[0][j] = wf_word(pos, ray.cls); // the class of the path word rides along above the slot (WfLaunch::order)
     }
 }
 
@@ -672,10 +615,10 @@ __global__ __launch_bounds__(256) void wf_fold(const WfLaunch L) {
         uint32_t nb = __float_as_uint(v.w);
         while (nb > 0) {
             --nb;
-            const float4 *fr = reinterpret_cast<const float4 *>(L.fold + ((size_t)nb * L.n_paths + path)); // frame level nb: adjacent lanes, adjacent records
-            const float4 fe = fr[0], fs = fr[1];
-            const V3 clr = res * mk(fs.x, fs.y, fs.z);
-            res = mk(fe.x, fe.y, fe.z) + clr;
+            V3 emission, scl;
+            wf_load_fold(wf_fold_at(L.fold, L.n_paths, nb, path), emission, scl); // frame level nb: adjacent lanes, adjacent records
+            const V3 clr = res * scl;
+            res = emission + clr;
         }
         if (isnan_f(res.x))
             res.x = 0;
@@ -744,27 +687,23 @@ __global__ __launch_bounds__(256) void wf_from_rays(const WfLaunch L, const floa
         L.counters[WF_CNT_IN] = n;
     if (i >= n)
         return;
-    const V3 o = ld3(rays + 6ull * i), d = ld3(rays + 6ull * i + 3);
-    float4 *rq = reinterpret_cast<float4 *>(L.paths_in + i);
-    rq[0] = make_float4(o.x, o.y, o.z, d.x);
-    rq[1] = make_float4(d.y, d.z, __uint_as_float(i), __uint_as_float(1u));
-    rq[2] = make_float4(1.0f / d.x, 1.0f / d.y, 1.0f / d.z, __uint_as_float(ray_fast_ok_ray(o, d) ? 1u : 0u));
-    *reinterpret_cast<uint4 *>(rq + 3) = make_uint4(0u, 0u, 0u, 0u);
+    // one cast, no class, no frames, no RNG stream: nothing shades these rays
+    wf_store_path(L.paths_in + i, wf_pack(ld3(rays + 6ull * i), ld3(rays + 6ull * i + 3), i, 0u, 1u, 0u, rt_xoshiro{{0u, 0u, 0u, 0u}}));
 }
 __global__ __launch_bounds__(256) void wf_hits_out(const DevScene S, const WfLaunch L, uint32_t n, uint32_t *prim_out, float *bct_out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    const float4 hq = *reinterpret_cast<const float4 *>(L.hits + i);
-    const uint32_t k = __float_as_uint(hq.x);
+    const Hit h = wf_load_hit(L.hits + i);
+    const uint32_t k = h.k;
     if (k == RT_NONE) {
         prim_out[i] = RT_NONE;
         bct_out[3ull * i] = bct_out[3ull * i + 1] = bct_out[3ull * i + 2] = 0.0f;
     } else {
         prim_out[i] = (k & RT_PRIM_FLAG) ? S.n_triangles + (k & ~RT_PRIM_FLAG) : S.scene.tris[k].prim;
-        bct_out[3ull * i] = hq.y;
-        bct_out[3ull * i + 1] = hq.z;
-        bct_out[3ull * i + 2] = hq.w;
+        bct_out[3ull * i] = h.b;
+        bct_out[3ull * i + 1] = h.c;
+        bct_out[3ull * i + 2] = h.t;
     }
 }
 
@@ -786,24 +725,12 @@ namespace rt {
 static hipError_t launch_extend(const DevScene &S, const WfLaunch &L, bool packet, bool stats, int ext_blocks, hipStream_t stream) {
     if (S.scene.wide) // production build (RT_BUILD_WIDE): every bounce walks the 8-wide tree (rt_wide.hip)
         return launch_extend_wide(S, L, packet, stats, ext_blocks, stream);
-    const dim3 grid(ext_blocks), block(256);
-    const bool gb = L.global_best != 0u;
-#define EXT_CASE(P, ST, G)                                                                          \
-    if (packet == P && stats == ST && gb == G) {                                                    \
-        if (P)                                                                                      \
-            return RT_LAUNCH_CHECKED((wf_extend_packet<ST, G>), grid, block, 0, stream, S, L);      \
-        return RT_LAUNCH_CHECKED((wf_extend<ST, G>), grid, block, 0, stream, S, L);                 \
-    }
-    EXT_CASE(false, false, false)
-    EXT_CASE(false, false, true)
-    EXT_CASE(false, true, false)
-    EXT_CASE(false, true, true)
-    EXT_CASE(true, false, false)
-    EXT_CASE(true, false, true)
-    EXT_CASE(true, true, false)
-    EXT_CASE(true, true, true)
-#undef EXT_CASE
-    return hipErrorInvalidValue;
+    return with_bools([&](auto P, auto ST, auto G) {
+        if constexpr (P)
+            return RT_LAUNCH_CHECKED((wf_extend_packet<ST, G>), dim3(ext_blocks), dim3(256), 0, stream, S, L);
+        else
+            return RT_LAUNCH_CHECKED((wf_extend<ST, G>), dim3(ext_blocks), dim3(256), 0, stream, S, L);
+    }, packet, stats, L.global_best != 0u);
 }
 
 // ---- closest-hit probe through the production kernels (rt_cast_rays_ex): rays -> queue -> wf_extend / wf_extend_packet -> hits
@@ -840,14 +767,13 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         return e;
     if (packet_census_out)
         packet_census_out[0] = packet_census_out[1] = 0ull;
-    if (acc && stats) // an accumulator pass: the first stage follows the round's list (wf_generate_list)
-        WF_LAUNCH((wf_generate_list<true>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
-    else if (acc)
-        WF_LAUNCH((wf_generate_list<false>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
-    else if (stats)
-        WF_LAUNCH((wf_generate<true>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
-    else
-        WF_LAUNCH((wf_generate<false>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
+    e = with_bools([&](auto ST) {
+        if (acc) // an accumulator pass: the first stage follows the round's list (wf_generate_list)
+            return RT_LAUNCH_CHECKED((wf_generate_list<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
+        return RT_LAUNCH_CHECKED((wf_generate<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
+    }, stats);
+    if (e != hipSuccess)
+        return e;
     const int ext_blocks = (int)(L.stack_stride / 256u); // rt_scene.cpp sizes the overflow workspace for exactly this grid
     const int shade_blocks = num_cus * RT_SHADE_BLOCKS_PER_CU;
     // Queue sizes reach the host one bounce LATE and without ever idling the device: after bounce b's wf_advance the size of
@@ -908,18 +834,14 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         // light tables from global memory (LIGHTS_LDS only saves latency), so a scene without one never pays for the lookup's registers
         const bool env = S.bg_tex >= 0;
         const bool lights_lds = S.lights.lds_inner != 0u && !env;
-        if (env && stats)
-            WF_LAUNCH((wf_shade<true, false, true>), dim3(shade_blocks), block, 0, stream, S, L);
-        else if (env)
-            WF_LAUNCH((wf_shade<false, false, true>), dim3(shade_blocks), block, 0, stream, S, L);
-        else if (stats && lights_lds)
-            WF_LAUNCH((wf_shade<true, true, false>), dim3(shade_blocks), block, 0, stream, S, L);
-        else if (stats)
-            WF_LAUNCH((wf_shade<true, false, false>), dim3(shade_blocks), block, 0, stream, S, L);
-        else if (lights_lds)
-            WF_LAUNCH((wf_shade<false, true, false>), dim3(shade_blocks), block, 0, stream, S, L);
-        else
-            WF_LAUNCH((wf_shade<false, false, false>), dim3(shade_blocks), block, 0, stream, S, L);
+        e = with_bools([&](auto ST, auto LDS, auto ENV) {
+            if constexpr (LDS && ENV) // never chosen (above), never instantiated
+                return hipErrorInvalidValue;
+            else
+                return RT_LAUNCH_CHECKED((wf_shade<ST, LDS, ENV>), dim3(shade_blocks), block, 0, stream, S, L);
+        }, stats, lights_lds, env);
+        if (e != hipSuccess)
+            return e;
         WF_LAUNCH(wf_advance, dim3(1), dim3(64), 0, stream, L.counters, L.stripes);
         if (hs && b == 0 && packet && packet_census_out) { // the packet kernel's census -> pinned words; read at bounce 2, or behind the loop
             if ((e = hipMemcpyAsync(hs->counts + WF_HOST_CENSUS_WORD, L.packet_census, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)) != hipSuccess)

@@ -20,6 +20,7 @@
 // tests/test_gpu_production.py (t bit-equal on every ray, index differences counted and confined to ties).
 #include "rt_device_lib.h"
 #include "rt_kernels.h"
+#include "rt_wf_records.h"
 
 namespace {
 
@@ -210,14 +211,8 @@ DEV void wide_tri_batch(WTrav &T, const uint4 *blob, bool waiting, uint16_t *s_o
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t have = waiting ? (uint32_t)__popc(T.tm) : 0u;
     const uint32_t n = have < RT_WIDE_COOP_MAX ? have : RT_WIDE_COOP_MAX;
-    uint32_t off = 0, total = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { // exclusive prefix sum of n (0..8) over the wave, one ballot per bit plane
-        const unsigned long long m = __ballot((n >> b) & 1u);
-        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        off += below << b;
-        total += (uint32_t)__popcll(m) << b;
-    }
+    uint32_t total;
+    const uint32_t off = wave_prefix_sum4(n, total);
     // Owner table: position off + t belongs to (lane, compact record offset of the lane's t-th pending triangle). Every
     // waiting lane writes all RT_WIDE_COOP_MAX entries, highest t first, without a per-entry predicate: an entry with t >= n
     // lands on a position of a later lane, whose own store of that position is issued later and wins (see leaf_batch).
@@ -305,25 +300,12 @@ template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_WAVES_PER_SIMD) 
     uint32_t q_lo = 0, q_hi = 0;
     TicketState tks = ticket_init();
     for (;;) {
-        const bool idle = T.done;
-        const unsigned long long im = __ballot(idle);
-        const int n_idle = __popcll(im);
-        if (!exhausted && (n_idle >= RT_WIDE_REFILL_MIN || n_idle == (int)__popcll(__ballot(1)))) {
-            if (q_lo == q_hi) // a new range of queue positions, one ticket atomic per chunk
-                exhausted = !ticket_take(L.counters, n_in, (uint32_t)RT_WIDE_CHUNK, tks, q_lo, q_hi);
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(im >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)im, 0u));
-            const uint32_t avail = q_hi - q_lo;
-            if (idle && rank < avail) {
-                const uint32_t jq = q_lo + rank;
-                const uint32_t j = L.order ? L.order[jq] & WF_ORDER_SLOT_MASK : jq;
-                const float4 *rq = reinterpret_cast<const float4 *>(L.paths_in + j);
-                const float4 r0 = rq[0], r1 = rq[1], r2 = rq[2];
-                slot = jq;
-                wide_init(T, S.scene, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r2.x, r2.y, r2.z));
-                stk.reset();
-            }
-            q_lo += (uint32_t)n_idle < avail ? (uint32_t)n_idle : avail;
-        }
+        ticket_refill(L.counters, n_in, (uint32_t)RT_WIDE_CHUNK, RT_WIDE_REFILL_MIN, T.done, exhausted, q_lo, q_hi, tks, [&](uint32_t jq) {
+            const WfRay ray = wf_load_ray(L.paths_in + wf_order_slot(L, jq));
+            slot = jq;
+            wide_init(T, S.scene, ray.o, ray.d, ray.r);
+            stk.reset();
+        });
         // unwind, once per trip, straight-line: a lane whose group has no pending slot and that has no pending triangle takes
         // the newest stacked group, or has finished
         {
@@ -341,7 +323,7 @@ template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_WAVES_PER_SIMD) 
             T.top_x = refill ? n_x : T.top_x;
             T.top_y = refill ? __float_as_uint(n_y) : T.top_y;
             if (fin) {
-                *reinterpret_cast<float4 *>(L.hits + slot) = make_float4(__uint_as_float(T.best.k), T.best.b, T.best.c, T.best.k == RT_NONE ? 0.0f : T.best.t);
+                wf_store_hit(L.hits + slot, wf_closed_hit(T.best));
                 T.done = true;
             }
         }
@@ -403,11 +385,9 @@ template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_PKT_WAVES_PER_SI
             uint32_t my_oct_inv = 7u;
             Hit best = Hit{RT_NONE, 0.f, 0.f, -RT_INF}; // a lane without a ray: an empty [EPS, -inf] range meets no box
             if (have) {
-                const uint32_t j = L.order ? L.order[jq] & WF_ORDER_SLOT_MASK : jq;
-                const float4 *rq = reinterpret_cast<const float4 *>(L.paths_in + j);
-                const float4 r0 = rq[0], r1 = rq[1], r2 = rq[2];
+                const WfRay ray = wf_load_ray(L.paths_in + wf_order_slot(L, jq));
                 WTrav T;
-                wide_init(T, S.scene, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r2.x, r2.y, r2.z));
+                wide_init(T, S.scene, ray.o, ray.d, ray.r);
                 o = T.o, d = T.d, w = T.w, my_oct_inv = T.oct_inv;
                 best.t = RT_INF;
             }
@@ -478,13 +458,10 @@ template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_PKT_WAVES_PER_SI
                 }
             }
             if (have)
-                *reinterpret_cast<float4 *>(L.hits + jq) = make_float4(__uint_as_float(best.k), best.b, best.c, best.k == RT_NONE ? 0.0f : best.t);
+                wf_store_hit(L.hits + jq, wf_closed_hit(best));
         }
     }
-    if (lane == 0u && L.packet_census && n_trips != 0ull) {
-        atomicAdd(L.packet_census, n_trips);
-        atomicAdd(L.packet_census + 1, n_lanes);
-    }
+    census_flush(L.packet_census, n_trips, n_lanes);
     st.flush(L.stats);
 }
 
@@ -493,14 +470,11 @@ template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_PKT_WAVES_PER_SI
 namespace rt {
 
 hipError_t launch_extend_wide(const DevScene &S, const WfLaunch &L, bool packet, bool stats, int blocks, hipStream_t stream) {
-    if (packet) {
-        if (stats)
-            return RT_LAUNCH_CHECKED((wf_extend_wide_packet<true>), dim3(blocks), dim3(256), 0, stream, S, L);
-        return RT_LAUNCH_CHECKED((wf_extend_wide_packet<false>), dim3(blocks), dim3(256), 0, stream, S, L);
-    }
-    if (stats)
-        return RT_LAUNCH_CHECKED((wf_extend_wide<true>), dim3(blocks), dim3(256), 0, stream, S, L);
-    return RT_LAUNCH_CHECKED((wf_extend_wide<false>), dim3(blocks), dim3(256), 0, stream, S, L);
+    return with_bools([&](auto ST) {
+        if (packet)
+            return RT_LAUNCH_CHECKED((wf_extend_wide_packet<ST>), dim3(blocks), dim3(256), 0, stream, S, L);
+        return RT_LAUNCH_CHECKED((wf_extend_wide<ST>), dim3(blocks), dim3(256), 0, stream, S, L);
+    }, stats);
 }
 
 } // namespace rt
