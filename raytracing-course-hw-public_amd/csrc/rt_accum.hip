@@ -9,7 +9,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "rt_device_lib.h"
+#include "rt_dev_math.h"
 #include "rt_kernels.h"
 
 namespace {

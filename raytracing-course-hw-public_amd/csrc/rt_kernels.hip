@@ -20,7 +20,8 @@
 //     against the NEAR SUBTREE's local best only (bvh.h:220-223), never against a global best.
 // Arithmetic contract: IEEE binary32, correctly rounded / and sqrt, no FMA contraction (-ffp-contract=off),
 // std::min/std::max operand order reproduced by explicit selects (fminf/fmaxf would drop NaNs differently).
-#include "rt_device_lib.h"
+#include "rt_dev_shade.h"
+#include "rt_dev_stack.h"
 #include "rt_kernels.h"
 
 namespace {
@@ -67,7 +68,7 @@ template <int MODE, bool STATS>
 __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const DevScene S, const RenderLaunch L) {
     __shared__ float s_lin[256];
     __shared__ float s_gam[256];
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(LDS_DEPTH, 3)];
     s_lin[threadIdx.x] = S.lut_linear[threadIdx.x];
     s_gam[threadIdx.x] = S.lut_gamma[threadIdx.x];
     __syncthreads();
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(256, RT_WAVES_PER_SIMD) void render_kernel(const De
 
 // ---------------------------------------------------------------------------------------------- probe kernels
 __global__ __launch_bounds__(256) void cast_kernel(const DevScene S, const float *rays, uint32_t n, uint32_t *prim_out, float *bct_out) {
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(LDS_DEPTH, 3)];
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
@@ -234,7 +235,7 @@ __global__ __launch_bounds__(256) void cast_kernel(const DevScene S, const float
 
 // rt_surface_normals: cast_kernel's closest hit, then the normals make_surf (to_intersection_info, bvh.h:80-121) gives shade()
 __global__ __launch_bounds__(256) void surface_normals_kernel(const DevScene S, const float *rays, uint32_t n, uint32_t *prim_out, float *t_out, float *normal_out, float *shading_out) {
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(LDS_DEPTH, 3)];
     __shared__ float s_lin[256];
     __shared__ float s_gam[256];
     s_lin[threadIdx.x] = S.lut_linear[threadIdx.x];
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(256) void surface_normals_kernel(const DevScene S, 
 }
 
 __global__ __launch_bounds__(256) void light_pdf_kernel(const DevScene S, const float *rays, uint32_t n, float *pdf_out) {
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(LDS_DEPTH, 3)];
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;

@@ -27,7 +27,9 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "rt_device_lib.h"
+#include "rt_dev_queue.h"
+#include "rt_dev_shade.h"
+#include "rt_dev_stack.h"
 #include "rt_kernels.h"
 #include "rt_wf_records.h"
 
@@ -145,62 +147,18 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list(co
 //                    lowest triangle index — exactly the leaf loop's strict-less replacement order (bvh.h:200-204,132).
 // This removes the inner-node / triangle divergence of a one-record-per-lane step (about 58 % / 42 % of the lanes) and
 // packs the triangle tests: a wave does ~40 node tests or ~48 triangle tests per pass instead of ~27 + ~20.
-template <bool STATS>
-DEV void leaf_batch(Trav &T, const DevBvh &bvh, bool at_leaf, uint16_t *s_owner, unsigned long long *s_min, float2 *s_bc, LaneStats<STATS> &st) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t n = at_leaf ? RT_LEAF_CNT(T.cur) : 0u;
-    uint32_t total;
-    const uint32_t off = wave_prefix_sum4(n, total);
-    // Owner table: position off + t belongs to (lane, t) for t < n. Every waiting lane writes ALL RT_LEAF_COOP_MAX
-    // entries, highest t first, without a per-entry predicate: an entry with t >= n lands on position off' + t' of a
-    // later lane (off' > off, hence t' < t), whose own store of that position is issued LATER (a wave's LDS
-    // instructions execute in order) and wins; within one instruction the waiting lanes' positions are distinct
-    // (their offsets increase strictly). Positions >= total are never read; the table has room for the overshoot.
-    if (at_leaf) {
-#pragma unroll
-        for (int t = RT_LEAF_COOP_MAX - 1; t >= 0; --t) {
-            s_owner[off + t] = (uint16_t)(lane | ((uint32_t)t << 8));
-            asm volatile("" ::: "memory"); // keep the stores in this order (compiler and machine scheduler)
-        }
-        s_min[lane] = ~0ull;
-    }
-    __threadfence_block();
-    const uint32_t k0 = T.cur & RT_LEAF_BEGIN_MASK;
-    for (uint32_t q0 = 0; q0 < total; q0 += 64u) { // wave-uniform trip count
-        const uint32_t q = q0 + lane;
-        const bool valid = q < total;
-        const uint32_t ow = valid ? (uint32_t)s_owner[q] : 0u;
-        const int src = (int)(ow & 63u);
-        const uint32_t kk = (uint32_t)__shfl((int)k0, src) + (ow >> 8);
-        const V3 o = mk(__shfl(T.o.x, src), __shfl(T.o.y, src), __shfl(T.o.z, src));
-        const V3 d = mk(__shfl(T.d.x, src), __shfl(T.d.y, src), __shfl(T.d.z, src));
-        if (valid) {
-            const float4 *p = reinterpret_cast<const float4 *>(bvh.tris + kk);
-            const float4 r0 = p[0], r1 = p[1], r2 = p[2];
-            st.tri();
-            V3 xs;
-            if (tri_hit(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), o, d, EPS, xs)) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(xs.z) << 32) | (unsigned long long)kk;
-                atomicMin(&s_min[src], key);
-                __threadfence_block();
-                if (s_min[src] == key) // this pair leads its leaf so far: publish its barycentrics
-                    s_bc[src] = make_float2(xs.x, xs.y);
-            }
-        }
-    }
-    __threadfence_block();
+// (The batch itself is coop_tri_batch, rt_dev_trav.h; here: a lane contributes its whole leaf, records are DevTri in leaf order.)
+template <bool STATS> DEV void leaf_batch(Trav &T, const DevBvh &bvh, bool at_leaf, const CoopLds<float2> &lds, LaneStats<STATS> &st) {
+    coop_tri_batch<RT_LEAF_COOP_MAX>(
+        at_leaf, at_leaf ? RT_LEAF_CNT(T.cur) : 0u, T.cur & RT_LEAF_BEGIN_MASK, T.o, T.d, bvh.tris, lds, [](int t) { return (uint32_t)t; },
+        [](uint32_t k0, uint32_t e) { return k0 + e; }, st);
     if (at_leaf) {
         st.node(); // one BVH::intersect_ray invocation on the leaf node
-        const unsigned long long key = s_min[lane];
-        if (key != ~0ull) {
-            const float t = __uint_as_float((uint32_t)(key >> 32));
-            const float2 bc = s_bc[lane];
-            if (T.best.k == RT_NONE || T.best.t > t) {
-                T.best.k = (uint32_t)key;
-                T.best.b = bc.x;
-                T.best.c = bc.y;
-                T.best.t = t;
-            }
+        float t;
+        uint32_t k;
+        float2 bc;
+        if (coop_result(lds, t, k, bc)) {
+            hit_take(T.best, k, bc.x, bc.y, t);
             T.t_loc = fminf(T.t_loc, t);
         }
         T.cur = T_POP; // unwound by the caller's trav_pop_wave
@@ -213,14 +171,12 @@ DEV void leaf_batch(Trav &T, const DevBvh &bvh, bool at_leaf, uint16_t *s_owner,
 
 template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PER_SIMD) void wf_extend(const DevScene S, const WfLaunch L) {
     constexpr int DEPTH = GB ? RT_EXT_GB_LDS_DEPTH : RT_EXT_LDS_DEPTH, WORDS = GB ? 2 : 3;
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS_W(DEPTH, WORDS)];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(DEPTH, WORDS)];
     __shared__ uint16_t s_owner_all[4][64 * RT_LEAF_COOP_MAX + RT_LEAF_COOP_MAX]; // + overshoot of the unpredicated owner stores
     __shared__ unsigned long long s_min_all[4][64];
     __shared__ float2 s_bc_all[4][64];
     const uint32_t wave = threadIdx.x >> 6;
-    uint16_t *s_owner = s_owner_all[wave];
-    unsigned long long *s_min = s_min_all[wave];
-    float2 *s_bc = s_bc_all[wave];
+    const CoopLds<float2> s_coop{s_owner_all[wave], s_min_all[wave], s_bc_all[wave]};
     LaneStats<STATS> st;
     RT_DECLARE_RING_STACK_W(stk, DEPTH, WORDS, s_stack, L.stack_overflow, L.stack_stride);
     const uint32_t n_in = L.counters[WF_CNT_IN];
@@ -263,7 +219,7 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
             continue;
         }
         if (sm == 0ull || __popcll(lm) >= RT_EXT_LEAF_MIN) {
-            leaf_batch<STATS>(T, S.scene, at_leaf, s_owner, s_min, s_bc, st);
+            leaf_batch<STATS>(T, S.scene, at_leaf, s_coop, st);
         } else {
             // the common wave: every stepping lane is on an inner node with the fast-division guarantees -> straight-line
             // node step; a wave with a big-leaf walker or a guarded ray takes the general step
@@ -295,20 +251,12 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
 #endif
 template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PER_SIMD) void wf_extend_packet(const DevScene S, const WfLaunch L) {
     constexpr int DEPTH = GB ? RT_EXT_GB_LDS_DEPTH : RT_EXT_LDS_DEPTH, WORDS = GB ? 2 : 3;
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS_W(DEPTH, WORDS)];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(DEPTH, WORDS)];
     LaneStats<STATS> st;
     RT_DECLARE_RING_STACK_W(stk, DEPTH, WORDS, s_stack, L.stack_overflow, L.stack_stride);
     const uint32_t n_in = L.counters[WF_CNT_IN];
     const uint32_t lane = threadIdx.x & 63u;
-    Trav T;
-    T.o = T.d = T.r = mk(0.f, 0.f, 0.f);
-    T.cur = T_DONE;
-    T.sp = 0;
-    T.t_loc = GB ? RT_INF : RT_NAN;
-    T.best = Hit{RT_NONE, 0.f, 0.f, 0.f};
-    T.fast = false;
-    T.top_ref = 0u;
-    T.top_d = T.top_loc = 0.f;
+    Trav T = trav_idle<GB>();
     unsigned long long n_trips = 0ull, n_lanes = 0ull; // wave-uniform
     for (;;) {
         uint32_t base = 0;
@@ -345,31 +293,25 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
                     ConstF4 p = as_const_f4(S.scene.nodes + node_index);
                     const F4v r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3];
                     if (mine)
-                        trav_inner_apply<STATS, GB>(T, stk, mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), mk(r2.y, r2.z, r2.w), __float_as_uint(r3.x),
-                                                __float_as_uint(r3.y), EPS, st);
+                        trav_inner_apply<STATS, GB>(T, stk, node_rec(r0, r1, r2, r3), EPS, st);
                 } else { // a leaf: its triangles in index order, strict-less replacement (bvh.h:200-204,132)
                     const uint32_t cnt = RT_LEAF_CNT(target);
                     uint32_t k = target & RT_LEAF_BEGIN_MASK;
                     for (uint32_t i = 0;; ++i, ++k) {
                         ConstF4 p = as_const_f4(S.scene.tris + k);
                         const F4v r0 = p[0], r1 = p[1], r2 = p[2];
-                        const uint32_t flags = __float_as_uint(r2.z);
+                        const TriRec tri = tri_rec(r0, r1, r2);
                         if (mine) {
-                            if (flags & 2u)
+                            if (tri.flags & 2u)
                                 st.node(); // one BVH::intersect_ray invocation on the leaf node
                             st.tri();
                             V3 xs;
-                            if (tri_hit(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), T.o, T.d, EPS, xs)) {
-                                if (T.best.k == RT_NONE || T.best.t > xs.z) {
-                                    T.best.k = k;
-                                    T.best.b = xs.x;
-                                    T.best.c = xs.y;
-                                    T.best.t = xs.z;
-                                }
+                            if (tri_hit(tri, T.o, T.d, EPS, xs)) {
+                                hit_take(T.best, k, xs.x, xs.y, xs.z);
                                 T.t_loc = fminf(T.t_loc, xs.z);
                             }
                         }
-                        if (cnt != 0u ? i + 1u == cnt : (flags & 1u) != 0u)
+                        if (cnt != 0u ? i + 1u == cnt : (tri.flags & 1u) != 0u)
                             break;
                     }
                     if (mine)
@@ -407,7 +349,7 @@ __global__ __launch_bounds__(256) void wf_extend_prims(const DevScene S, const W
 template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(256, RT_SHADE_WAVES_PER_SIMD) void wf_shade(const DevScene S, const WfLaunch L) {
     __shared__ float s_lin[256];
     __shared__ float s_gam[256];
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS_FOR(RT_SHADE_LDS_DEPTH)];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(RT_SHADE_LDS_DEPTH, 3)];
     __shared__ float4 s_lights[LIGHTS_LDS ? RT_SHADE_LIGHTS_F4 : 1];
     __shared__ uint2 s_perm[4][256]; // per wave: (queue position, queue slot) of its 256 positions, sorted by sampler class
     LightTabs LT = light_tabs_global(S);

@@ -4,7 +4,7 @@
 #pragma once
 #include <cstddef>
 
-#include "rt_device_lib.h"
+#include "rt_dev_trav.h"
 
 static_assert(offsetof(WfPath, o) == 0 && offsetof(WfPath, dx) == 12 && offsetof(WfPath, dy) == 16 && offsetof(WfPath, path) == 24 && offsetof(WfPath, depth) == 28 &&
                   offsetof(WfPath, r) == 32 && offsetof(WfPath, fast) == 44 && offsetof(WfPath, s) == 48,
@@ -36,14 +36,14 @@ struct WfPacked { // a whole record in registers (wf_shade computes it inside a 
 };
 DEV WfRay wf_load_ray(const WfPath *p) {
     const float4 *q = reinterpret_cast<const float4 *>(p);
-    const float4 r0 = q[0], r1 = q[1], r2 = q[2];
-    return WfRay{mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r2.x, r2.y, r2.z), __float_as_uint(r2.w) != 0u};
+    const float4 p0 = q[0], p1 = q[1], p2 = q[2];
+    return WfRay{mk(p0.x, p0.y, p0.z), mk(p0.w, p1.x, p1.y), mk(p2.x, p2.y, p2.z), __float_as_uint(p2.w) != 0u};
 }
 DEV WfHead wf_load_head(const WfPath *p) {
     const float4 *q = reinterpret_cast<const float4 *>(p);
-    const float4 r0 = q[0], r1 = q[1];
-    const uint32_t w = __float_as_uint(r1.z), dw = __float_as_uint(r1.w);
-    return WfHead{mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), wf_word_slot(w), wf_word_class(w), dw & 0xFFFFu, dw >> 16};
+    const float4 p0 = q[0], p1 = q[1];
+    const uint32_t w = __float_as_uint(p1.z), dw = __float_as_uint(p1.w);
+    return WfHead{mk(p0.x, p0.y, p0.z), mk(p0.w, p1.x, p1.y), wf_word_slot(w), wf_word_class(w), dw & 0xFFFFu, dw >> 16};
 }
 DEV Rng<RT_RNG_DEVICE> wf_load_rng(const WfPath *p) {
     const uint4 s = reinterpret_cast<const uint4 *>(p)[3];

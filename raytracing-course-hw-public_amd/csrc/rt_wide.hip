@@ -12,13 +12,15 @@
 //   * no distance sort: a node's slots are laid out by octant (wide_build.cpp), so the hit slots are visited front to back by
 //     taking them in the order of decreasing (slot ^ oct ^ 7), oct = the ray's direction signs; the pending rest of a node is
 //     ONE 8-byte stack frame {first child index, pending slots | inner-slot mask}, whatever the number of hit children;
-//   * triangles are tested exactly as everywhere else (tri_hit, rt_device_lib.h: the reference's Cramer solve, bvh.h:36-65), in
+//   * triangles are tested exactly as everywhere else (tri_hit, rt_dev_trav.h: the reference's Cramer solve, bvh.h:36-65), in
 //     wave-wide batches like wf_extend's leaf batches, so a hit's (b, c, t) are bit-equal to the reference's for that triangle.
 // The boxes are NOT the reference's (8-bit conservative supersets, slab test by fused multiply-adds with an explicit error
 // margin instead of IEEE division): a ray can only see MORE boxes than exact arithmetic would allow, never fewer, so every
 // triangle the reference finds is found; on exact ties another triangle index may win. Checked against the CPU oracle in
 // tests/test_gpu_production.py (t bit-equal on every ray, index differences counted and confined to ties).
-#include "rt_device_lib.h"
+#include "rt_dev_queue.h"
+#include "rt_dev_stack.h"
+#include "rt_dev_trav.h"
 #include "rt_kernels.h"
 #include "rt_wf_records.h"
 
@@ -102,6 +104,20 @@ DEV void wide_init(WTrav &T, const DevBvh &bvh, V3 o, V3 d, V3 r) {
     T.tbase = T.tm = T.tall = 0u;
     T.best = Hit{RT_NONE, 0.f, 0.f, RT_INF};
     T.done = false;
+}
+
+// a lane without a ray: finished, every field defined
+DEV WTrav wide_idle() {
+    WTrav T;
+    T.o = T.d = mk(0.f, 0.f, 0.f);
+    T.w.lo = T.w.hi = T.w.gi = T.w.ids = mk(0.f, 0.f, 0.f);
+    T.oct_inv = 0u;
+    T.gx = T.gy = T.top_x = T.top_y = 0u;
+    T.sp = 0;
+    T.tbase = T.tm = T.tall = 0u;
+    T.best = Hit{RT_NONE, 0.f, 0.f, RT_INF};
+    T.done = true;
+    return T;
 }
 
 DEV float ub(uint32_t w, int k) { return (float)((w >> (8 * k)) & 255u); } // v_cvt_f32_ubyteK
@@ -204,97 +220,40 @@ template <bool STATS, class STK> DEV void wide_node_step(WTrav &T, const uint4 *
     T.tm = wide_leaf_tris(h & ~imask, H.tri_mask);
 }
 
-// Triangle batch, as wf_extend's leaf batch: the pending (ray, triangle) pairs of all waiting lanes are laid out densely over
-// the wave; a lane's result is the minimum of (t bits, triangle record) over its pairs: smallest t, lowest record on equal t.
-template <bool STATS>
-DEV void wide_tri_batch(WTrav &T, const uint4 *blob, bool waiting, uint16_t *s_owner, unsigned long long *s_min, float4 *s_bc, LaneStats<STATS> &st) {
-    const uint32_t lane = threadIdx.x & 63u;
+// Triangle batch, as wf_extend's leaf batch (coop_tri_batch, rt_dev_trav.h): a lane contributes up to RT_WIDE_COOP_MAX of its pending triangles, what
+// does not fit stays pending for the next batch. An entry is the compact record offset of a pending triangle behind the node's tbase; the key's low
+// word is the 16-byte unit index of the record, and the payload carries the record's DevTri / DevAttr index (TriRec::index) along.
+template <bool STATS> DEV void wide_tri_batch(WTrav &T, const uint4 *blob, bool waiting, const CoopLds<float4> &lds, LaneStats<STATS> &st) {
     const uint32_t have = waiting ? (uint32_t)__popc(T.tm) : 0u;
-    const uint32_t n = have < RT_WIDE_COOP_MAX ? have : RT_WIDE_COOP_MAX;
-    uint32_t total;
-    const uint32_t off = wave_prefix_sum4(n, total);
-    // Owner table: position off + t belongs to (lane, compact record offset of the lane's t-th pending triangle). Every
-    // waiting lane writes all RT_WIDE_COOP_MAX entries, highest t first, without a per-entry predicate: an entry with t >= n
-    // lands on a position of a later lane, whose own store of that position is issued later and wins (see leaf_batch).
+    coop_tri_batch<(int)RT_WIDE_COOP_MAX>(
+        waiting, have < RT_WIDE_COOP_MAX ? have : RT_WIDE_COOP_MAX, T.tbase, T.o, T.d, blob, lds,
+        [&](int) { // the lowest pending bit, taken off T.tm
+            const uint32_t b = (uint32_t)(__ffs((int)T.tm) - 1) & 31u;
+            T.tm &= T.tm - 1u;
+            return (uint32_t)__popc(T.tall & ((1u << b) - 1u)); // compact index of bit b
+        },
+        [](uint32_t tbase, uint32_t e) { return tbase + RT_WIDE_TRI_UNITS * e; }, st);
     if (waiting) {
-        uint32_t m = T.tm;
-        uint16_t ent[RT_WIDE_COOP_MAX];
-#pragma unroll
-        for (int t = 0; t < (int)RT_WIDE_COOP_MAX; ++t) {
-            const uint32_t b = (uint32_t)(__ffs((int)m) - 1) & 31u;
-            const uint32_t rec = (uint32_t)__popc(T.tall & ((1u << b) - 1u)); // compact index of bit b
-            ent[t] = (uint16_t)(lane | (rec << 8));
-            m &= m - 1u;
-        }
-#pragma unroll
-        for (int t = (int)RT_WIDE_COOP_MAX - 1; t >= 0; --t) {
-            s_owner[off + t] = ent[t];
-            asm volatile("" ::: "memory"); // keep the stores in this order
-        }
-        s_min[lane] = ~0ull;
-        T.tm = m; // what did not fit this batch stays pending
-    }
-    __threadfence_block();
-    for (uint32_t q0 = 0; q0 < total; q0 += 64u) { // wave-uniform trip count
-        const uint32_t q = q0 + lane;
-        const bool valid = q < total;
-        const uint32_t ow = valid ? (uint32_t)s_owner[q] : 0u;
-        const int src = (int)(ow & 63u);
-        const uint32_t kk = (uint32_t)__shfl((int)T.tbase, src) + RT_WIDE_TRI_UNITS * (ow >> 8); // 16-byte unit index of the triangle record
-        const V3 o = mk(__shfl(T.o.x, src), __shfl(T.o.y, src), __shfl(T.o.z, src));
-        const V3 d = mk(__shfl(T.d.x, src), __shfl(T.d.y, src), __shfl(T.d.z, src));
-        if (valid) {
-            const float4 *p = reinterpret_cast<const float4 *>(blob + kk);
-            const float4 r0 = p[0], r1 = p[1], r2 = p[2];
-            st.tri();
-            V3 xs;
-            if (tri_hit(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), o, d, EPS, xs)) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(xs.z) << 32) | (unsigned long long)kk;
-                atomicMin(&s_min[src], key);
-                __threadfence_block();
-                if (s_min[src] == key) // this pair leads its ray so far: publish its barycentrics and the record's DevTri / DevAttr index (DevTri::pad)
-                    s_bc[src] = make_float4(xs.x, xs.y, r2.w, 0.0f);
-            }
-        }
-    }
-    __threadfence_block();
-    if (waiting) {
-        const unsigned long long key = s_min[lane];
-        if (key != ~0ull) {
-            const float t = __uint_as_float((uint32_t)(key >> 32));
-            const float4 bc = s_bc[lane];
-            if (T.best.t > t) { // strict: the first-found triangle keeps an exact tie (update_intersection, bvh.h:132)
-                T.best.k = __float_as_uint(bc.z);
-                T.best.b = bc.x;
-                T.best.c = bc.y;
-                T.best.t = t;
-            }
-        }
+        float t;
+        uint32_t unit;
+        float4 bc;
+        if (coop_result(lds, t, unit, bc) && T.best.t > t) // hit_take's rule (rt_dev_trav.h) with best.t = +inf for "none yet": a first hit at t = +inf stays a miss here
+            T.best = Hit{__float_as_uint(bc.z), bc.x, bc.y, t};
     }
 }
 
 template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_WAVES_PER_SIMD) void wf_extend_wide(const DevScene S, const WfLaunch L) {
-    __shared__ uint32_t s_stack[STACK_LDS_DWORDS_W(RT_WIDE_LDS_DEPTH, 2)];
+    __shared__ uint32_t s_stack[STACK_LDS_DWORDS(RT_WIDE_LDS_DEPTH, 2)];
     __shared__ uint16_t s_owner_all[4][64 * RT_WIDE_COOP_MAX + RT_WIDE_COOP_MAX]; // + overshoot of the unpredicated owner stores
     __shared__ unsigned long long s_min_all[4][64];
     __shared__ float4 s_bc_all[4][64];
     const uint32_t wave = threadIdx.x >> 6;
-    uint16_t *s_owner = s_owner_all[wave];
-    unsigned long long *s_min = s_min_all[wave];
-    float4 *s_bc = s_bc_all[wave];
+    const CoopLds<float4> s_coop{s_owner_all[wave], s_min_all[wave], s_bc_all[wave]};
     LaneStats<STATS> st;
     RT_DECLARE_RING_STACK_W(stk, RT_WIDE_LDS_DEPTH, 2, s_stack, L.stack_overflow, L.stack_stride);
     const uint32_t n_in = L.counters[WF_CNT_IN];
     const uint4 *blob = reinterpret_cast<const uint4 *>(S.scene.wide);
-    WTrav T;
-    T.o = T.d = mk(0.f, 0.f, 0.f);
-    T.w.lo = T.w.hi = T.w.gi = T.w.ids = mk(0.f, 0.f, 0.f);
-    T.oct_inv = 0u;
-    T.gx = T.gy = T.top_x = T.top_y = 0u;
-    T.sp = 0;
-    T.tbase = T.tm = T.tall = 0u;
-    T.best = Hit{RT_NONE, 0.f, 0.f, RT_INF};
-    T.done = true;
+    WTrav T = wide_idle();
     uint32_t slot = RT_NONE;
     bool exhausted = n_in == 0; // wave-uniform
     uint32_t q_lo = 0, q_hi = 0;
@@ -338,7 +297,7 @@ template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_WAVES_PER_SIMD) 
             continue;
         }
         if (sm == 0ull || __popcll(wm) >= RT_WIDE_TRI_MIN) {
-            wide_tri_batch<STATS>(T, blob, waiting, s_owner, s_min, s_bc, st);
+            wide_tri_batch<STATS>(T, blob, waiting, s_coop, st);
         } else {
             if (stepper)
                 wide_node_step<STATS>(T, blob, stk, st);
@@ -446,14 +405,11 @@ template <bool STATS> __global__ __launch_bounds__(256, RT_WIDE_PKT_WAVES_PER_SI
                     ConstF4 tp = as_const_f4(blob + k);
                     const F4v r0 = tp[0], r1 = tp[1], r2 = tp[2];
                     if ((h >> (b / 3u)) & 1u) {
+                        const TriRec tri = tri_rec(r0, r1, r2);
                         st.tri();
                         V3 xs;
-                        if (tri_hit(mk(r0.x, r0.y, r0.z), mk(r0.w, r1.x, r1.y), mk(r1.z, r1.w, r2.x), o, d, EPS, xs) && best.t > xs.z) {
-                            best.k = __float_as_uint(r2.w); // DevTri::pad of a blob record: its DevTri / DevAttr index
-                            best.b = xs.x;
-                            best.c = xs.y;
-                            best.t = xs.z;
-                        }
+                        if (tri_hit(tri, o, d, EPS, xs) && best.t > xs.z) // hit_take's rule with best.t = +inf for "none yet", as in wide_tri_batch
+                            best = Hit{tri.index, xs.x, xs.y, xs.z};
                     }
                 }
             }

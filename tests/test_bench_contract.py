@@ -187,7 +187,7 @@ def test_library_carries_the_hash_of_its_sources(rt):
 
     assert rt.lib().rt_source_stamp().decode() == bench.kernel_source_hash()
     names = {os.path.basename(f) for f in bench.DEVICE_SOURCES}
-    for must in ("rt_wavefront.hip", "rt_wide.hip", "rt_device_lib.h", "rt_device_types.h", "rt_wf_records.h", "rt_kernels.h", "rt_scene.cpp", "rt_scene_impl.h", "rt_render.cpp", "rt_accum_host.cpp", "rt_probe.cpp", "wide_build.cpp", "rt_bvh_device.hip", "Makefile", "rt_devspec.h"):
+    for must in ("rt_wavefront.hip", "rt_wide.hip", "rt_dev_math.h", "rt_dev_stack.h", "rt_dev_trav.h", "rt_dev_surface.h", "rt_dev_shade.h", "rt_dev_queue.h", "rt_device_types.h", "rt_wf_records.h", "rt_kernels.h", "rt_scene.cpp", "rt_scene_impl.h", "rt_render.cpp", "rt_accum_host.cpp", "rt_probe.cpp", "wide_build.cpp", "rt_bvh_device.hip", "Makefile", "rt_devspec.h"):
         assert must in names, must
     for f in bench.DEVICE_SOURCES:
         assert os.path.exists(os.path.join(bench.CSRC, f)), f

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import random_rays
+from guarded_rays import big_leaf_scene, degenerate_rays, fast_division_boundary_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -59,15 +60,8 @@ def test_closest_hit_bit_exact(pairs, name):
 def test_closest_hit_degenerate_rays(pairs):
     """Axis-parallel rays from points ON box planes / vertices: 0/0 and +-inf slab terms (bvh.h:141-145)."""
     dev, orc, sc = pairs["boxes"]
-    verts = sc.positions.reshape(-1, 3)[:300]
-    rays = []
-    for ax in range(3):
-        for sgn in (-1.0, 1.0):
-            d = np.zeros(3, dtype=np.float32)
-            d[ax] = sgn
-            for v in verts:
-                rays.append(np.concatenate([v + np.float32(0.0), d]))
-    rays = np.asarray(rays, dtype=np.float32)
+    rays = degenerate_rays(sc)
+    assert len(rays) == 1800
     gp, gb = dev.cast_rays(rays)
     op, ob = orc.cast_rays(rays)
     assert np.array_equal(gp, op)
@@ -75,17 +69,10 @@ def test_closest_hit_degenerate_rays(pairs):
 
 
 def test_closest_hit_fast_division_boundaries(pairs):
-    """Rays on both sides of the exact-reciprocal-division preconditions (rt_kernels.hip div_exact_fast): origin
+    """Rays on both sides of the exact-reciprocal-division preconditions (rt_dev_trav.h div_exact_fast): origin
     components that are 0, tiny (1e-30), huge (1e15); direction components that are 0, 1e-20 or dominate."""
     dev, orc, sc = pairs["room_plain"]
-    rays = random_rays(sc, 6000, seed=303)
-    rng = np.random.default_rng(8)
-    specials_o = np.array([0.0, 1e-30, -1e-30, 1e-13, 1e15, 4.0, -20.0, 16.0], dtype=np.float32)
-    specials_d = np.array([0.0, 1e-20, -1e-20, 1e-13, 1.0], dtype=np.float32)
-    for i in range(3000):
-        rays[i, rng.integers(0, 3)] = rng.choice(specials_o)
-        if i % 2:
-            rays[i, 3 + rng.integers(0, 3)] = rng.choice(specials_d)
+    rays = fast_division_boundary_rays(sc)
     gp, gb = dev.cast_rays(rays)
     op, ob = orc.cast_rays(rays)
     assert np.array_equal(gp, op)
@@ -325,15 +312,7 @@ def test_big_leaves_and_duplicate_geometry(gpu, oracle, sg):
     """Many triangles with identical centroids: the SAH sweep finds no split (bvh.h:299-312), so leaves hold dozens of
     triangles (walked with the per-triangle flags instead of the cooperative <= 8 path) and equal-t hits occur: the
     first triangle in leaf order must win (bvh.h:132)."""
-    sc = sg.boxes_scene(n_boxes=5, seed=8, n_lights=2)
-    tri = sc.positions[20:21]
-    dup = np.repeat(tri, 40, axis=0)
-    sc.positions = np.concatenate([sc.positions, dup, dup * np.float32(1.0)], axis=0).astype(np.float32)
-    n = sc.positions.shape[0]
-    sc.material_ids = np.concatenate([sc.material_ids, np.full(80, 3, dtype=np.uint32)])
-    sc.texcoords = np.zeros((n, 3, 2), dtype=np.float32)
-    sc.tangents = np.zeros((n, 3, 3), dtype=np.float32)
-    sc.tangents[..., 0] = 1
+    sc = big_leaf_scene(sg)
     dev = gpu.DeviceScene(sc)
     info = dev.bvh_info(0)
     leaf_sizes = (info["nodes"][:, 9] - info["nodes"][:, 8])[info["nodes"][:, 6] == 0xFFFFFFFF]

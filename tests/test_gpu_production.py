@@ -18,6 +18,7 @@ import pytest
 
 import hit_contract
 from conftest import random_rays
+from guarded_rays import big_leaf_scene, degenerate_rays, fast_division_boundary_rays, is_guarded
 from hit_contract import explain_pixels, summary, verify_hits, verify_reported_hits
 
 pytestmark = pytest.mark.gpu
@@ -128,6 +129,47 @@ def test_global_best_hits_equal_the_oracle(pairs, gpu, name):
         # a subset of the reference's visits, and a real saving
         assert st["nodes_visited"] <= st_ref["nodes_visited"] and st["tri_tests"] <= st_ref["tri_tests"], (name, mode, st, st_ref)
     print(f"{name}: nodes visited global-best / reference = {st['nodes_visited']} / {st_ref['nodes_visited']} = {st['nodes_visited'] / st_ref['nodes_visited']:.4f}")
+
+
+def test_guarded_rays_through_every_binary_kernel(pairs, gpu, oracle, sg):
+    """Rays that leave the exact-reciprocal fast path (axis-parallel from box vertices; origin / direction components around 2^-40, 2^-37, 2^40)
+    go through EVERY binary closest-hit kernel, shuffled among plain rays: all kernels take the guarded branch of the one inner-node step
+    (trav_inner_apply, rt_dev_trav.h). The mix is checked per 64 consecutive rays: exactly a wave of the probe and of a packet, and the
+    pool a refilling wave of wf_extend draws from. Parity modes: every field bit-equal to the oracle, and the packet kernel's counters are the per-lane
+    kernel's ("by construction", rt_wavefront.hip). Production modes: the hit contract; these rays are built to tie, so ties are not capped."""
+    big = big_leaf_scene(sg)
+    big_dev, big_orc = gpu.DeviceScene(big), oracle.OracleScene(big)
+    try:
+        info = big_dev.bvh_info(0)
+        leaf_sizes = (info["nodes"][:, 9] - info["nodes"][:, 8])[info["nodes"][:, 6] == 0xFFFFFFFF]
+        assert leaf_sizes.max() > 8, "the test needs a leaf beyond the cooperative limit (triangle-by-triangle walkers)"
+        dev, orc, sc = pairs["boxes"]
+        rdev, rorc, rsc = pairs["room_plain"]
+        sets = [
+            ("boxes", dev, orc, np.concatenate([degenerate_rays(sc), random_rays(sc, 2048 + 37, seed=511), _camera_rays(sc, 1024, seed=512)])),
+            ("room_plain", rdev, rorc, fast_division_boundary_rays(rsc)),
+            ("big_leaf", big_dev, big_orc, random_rays(big, 2000 + 37, seed=513)),
+        ]
+        for name, d, o, rays in sets:
+            rays = rays[np.random.default_rng(514).permutation(len(rays))]
+            g = is_guarded(rays)
+            assert len(rays) % 64 != 0, f"{name}: the last wave must be partial"
+            full = g[: len(g) // 64 * 64].reshape(-1, 64)
+            assert (full.any(axis=1) & ~full.all(axis=1)).sum() >= len(full) // 2, f"{name}: guarded and plain rays must be mixed within 64 consecutive rays"
+            op, ob = o.cast_rays(rays)
+            stats = {}
+            for mode in (gpu.RT_CAST_PROBE, gpu.RT_CAST_EXTEND, gpu.RT_CAST_PACKET):
+                gp, gb, stats[mode] = d.cast_rays_ex(rays, mode)
+                assert np.array_equal(gp, op), (name, mode, int((gp != op).sum()))
+                assert np.array_equal(gb.view(np.uint32), ob.view(np.uint32)), (name, mode)
+            for k in ("nodes_visited", "box_tests", "tri_tests"):
+                assert stats[gpu.RT_CAST_EXTEND][k] == stats[gpu.RT_CAST_PACKET][k], (name, k, stats[gpu.RT_CAST_EXTEND][k], stats[gpu.RT_CAST_PACKET][k])
+            for mode in (gpu.RT_CAST_EXTEND_GLOBAL, gpu.RT_CAST_PACKET_GLOBAL):
+                gp, gb, _ = d.cast_rays_ex(rays, mode)
+                compare_hits_with_oracle(o, rays, op, ob, gp, gb, f"guarded rays, {name} mode {mode}")
+    finally:
+        big_dev.close()
+        big_orc.close()
 
 
 @pytest.mark.parametrize("name", FIXTURES)

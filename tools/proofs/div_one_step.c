@@ -1,5 +1,5 @@
 /* div_one_step.c — exhaustive hard-case check of the one-step exact division used by the slab test
- * (csrc/rt_device_lib.h div_exact_fast):
+ * (csrc/rt_dev_trav.h div_exact_fast):
  *
  *     r  = RN(1/d)            (once per ray, IEEE division)
  *     q0 = RN(a*r);  e = RN(a - d*q0) (one FMA);  q1 = RN(q0 + e*r) (one FMA);   claim: q1 == RN(a/d)
