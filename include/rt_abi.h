@@ -47,7 +47,8 @@ extern "C" {
                                 options were retired (two rt_build_options fields became reserved, unused RT_SORT_* / RT_BUILD_* values are
                                 refused): the binary layout and the meaning of every value that remains are unchanged. Still 4 after
                                 rt_view / rt_render_views / rt_render_views_rgb8 were added, and after the rt_accum_* accumulators and
-                                rt_adaptive were: new entry points only, no existing layout changes */
+                                rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were:
+                                new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
 
@@ -451,6 +452,67 @@ int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb8);
 /* Copies the state to host buffers (any may be NULL): S (3 floats per pixel), E (3 floats), n, and err (as the last judge computed it;
  * +inf everywhere before the first adaptive call). */
 int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb, uint32_t *samples, float *error);
+
+/* First-hit feature sums (the auxiliary images a denoiser is guided by; additive, RT_ABI_VERSION stays 4).
+ * rt_accum_create_ex is rt_accum_create with flags: accum_flags = 0 IS rt_accum_create; RT_ACCUM_FEATURES makes the accumulator keep, for
+ * every pixel p, four more fields, each added to by the lane that adds to S_p, in the same sample order, in the same rounds (no float atomics):
+ *   AS_p  float3: sum over the samples of the albedo of the closest hit of the sample's primary ray: material.color.rgb x colour texture, the
+ *         colour to_intersection_info (bvh.h:80-121) hands to shade(). A miss adds (0, 0, 0).
+ *   NS_p  float3: sum of that hit's shading normal, facing the ray, as rt_surface_normals reports it (an analytic primitive: its normal).
+ *         A miss adds (0, 0, 0).
+ *   ZS_p  float: sum of the hit distance t. A miss adds 0.
+ *   h_p   u32: number of samples whose primary ray hit.
+ * The primary ray of sample s of pixel p is the one seeded from (seed, p, s), the first ray of that sample's path; its first hit is the closest
+ * hit the scene's own traversal returns. The alpha coin of shade() (raytracer.h:559) is not consulted: a hit that shading passes through still
+ * counts. Every call that adds samples adds their features (rt_accum_render, rt_accum_render_adaptive, any split over passes and lists), so
+ * after any sequence of calls the four sums are functions of n_p alone, like S_p. S_p, E_p, n_p, the image and the event counters of rt_stats
+ * are those of an accumulator without the flag, bit for bit. An accumulator without the flag allocates and launches nothing new.
+ * Any other bit of accum_flags -> RT_ERR_INVALID_ARG; every other refusal is rt_accum_create's. RT_ERR_OOM when the per-path feature records
+ * (32 B per path of a pass) do not fit beside the wavefront workspace. */
+enum { RT_ACCUM_FEATURES = 1 };
+int rt_accum_create_ex(rt_scene *scene, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, uint32_t accum_flags, rt_accum **out);
+/* The raw sums (any pointer may be NULL): AS, NS (3 floats per pixel), ZS (1 float), h (u32). RT_ERR_INVALID_ARG without RT_ACCUM_FEATURES. */
+int rt_accum_read_features(rt_accum *acc, float *albedo_sum, float *normal_sum, float *depth_sum, uint32_t *hits);
+/* The means (any pointer may be NULL): albedo = AS / (float)n, normal = NS / (float)n (NOT renormalised), depth = ZS / (float)h (0 where
+ * h = 0); all 0 where n = 0. flags: 0 or RT_FLAG_DEVICE_FB (all three are device buffers). RT_ERR_INVALID_ARG without RT_ACCUM_FEATURES. */
+int rt_accum_resolve_features(rt_accum *acc, uint32_t flags, float *albedo, float *normal, float *depth);
+
+/* rt_accum_denoise: an edge-avoiding a-trous filter over the accumulator's image, guided by its feature means and by the noise estimate its
+ * half buffer E gives, on the device. Needs RT_ACCUM_FEATURES (else RT_ERR_INVALID_ARG). The accumulator is not modified: denoise, add
+ * samples, denoise again. fb_rgb: width * height * 3 floats (a device buffer with RT_FLAG_DEVICE_FB; `flags` is 0 or that).
+ * The rule, exactly. Only + - * / fabsf min max and comparisons, IEEE binary32, no contraction, in the order written (sums left to right):
+ *   A pixel is VALID when n_p > 0. An invalid pixel outputs (0, 0, 0) and is never a tap. For a valid pixel, with fn = (float)n, h = h_p:
+ *     C = S / fn, alb = AS / fn, N = NS / fn (per component), Z = ZS / (float)h (0 when h = 0), m = (float)(n - h) / fn,
+ *     den_c = (alb_c + m) + 1e-3f   (1.0f for every channel with RT_DENOISE_NO_DEMODULATE),
+ *     L0 = C / den                  (the working signal: the image with the first hit's albedo divided out),
+ *     d_p = (|C.r - A.r| / den.r + |C.g - A.g| / den.g) + |C.b - A.b| / den.b with A = E / (float)((n + 1) / 2);  d_p = +inf when n < 2,
+ *     s_p = (sum of d_q over the valid pixels q of the 3x3 window around p clipped at the image border, row-major) / (float)(their number).
+ *   Iteration i = 0 .. K-1 (K = iterations) has stride t = 2^i and reads L^i, writes L^(i+1). Taps q = p + t * (dx, dy), dy = -2..2 outer,
+ *   dx = -2..2 inner, the centre included; a tap outside the image or invalid is skipped. k = (1/16, 1/4, 3/8, 1/4, 1/16).
+ *     w = (((k[dy+2] * k[dx+2]) * wn) * wz) * wc, and the centre tap has wn = wz = wc = 1. For the other taps:
+ *     wn: a = (N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z, pp and qq likewise from (N_p, N_p) and (N_q, N_q). pp == 0 and qq == 0 -> 1;
+ *         else a <= 0 or pp * qq == 0 -> 0; else c = (a * a) / (pp * qq), then c = c * c `normal_sharpness` times; wn = c.
+ *     wz: h_p == 0 and h_q == 0 -> 1; exactly one of them 0 -> 0; else
+ *         r = (Z_p - Z_q) / ((sigma_depth * (float)(t * max(|dx|, |dy|))) * max(Z_p, Z_q)), wz = 1 / (1 + r * r).
+ *     wc: e = ((|L_p.r - L_q.r| + |L_p.g - L_q.g|) + |L_p.b - L_q.b|) / ((sigma_color * s_p) * (1 / (float)t) + 1e-6f), wc = 1 / (1 + e * e)
+ *         (L of iteration i; s_p = +inf makes wc = 1: a pixel with a neighbourhood of n < 2 is filtered by geometry alone).
+ *     L^(i+1)_p = (sum of w * L^i_q) / (sum of w), both sums in tap order starting from 0; the centre makes the divisor >= 9/64.
+ *   Output: L^K * den per channel.
+ * Which lane or block computes a pixel, and whether its taps come through LDS, changes no result.
+ * rt_accum_denoise_rgb8 applies the device film on top: == rt_tonemap_rgb8 of rt_accum_denoise's image.
+ * RT_ERR_INVALID_ARG: a NULL accumulator or buffer, flags other than RT_FLAG_DEVICE_FB, iterations > 8, normal_sharpness > 8, a sigma that is
+ *   negative, NaN or infinite, an unknown bit of rt_denoise.flags, a non-zero reserved field. opt NULL = all defaults. */
+enum { RT_DENOISE_NO_DEMODULATE = 1 };
+typedef struct rt_denoise {
+    uint32_t iterations;       /* K; 0 = 5, at most 8 */
+    float sigma_color;         /* 0 = 8.0 */
+    float sigma_depth;         /* 0 = 0.5 */
+    uint32_t normal_sharpness; /* squarings of the squared cosine: 0 = 3 (cos^16); at most 8 */
+    uint32_t flags;            /* RT_DENOISE_* */
+    uint32_t reserved[3];      /* 0 */
+} rt_denoise;                  /* 32 bytes; all-zero = the defaults (measured: profiles/denoise_quality.txt) */
+int rt_accum_denoise(rt_accum *acc, const rt_denoise *opt, uint32_t flags, float *fb_rgb);
+int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint32_t flags, uint8_t *rgb8);
 
 int rt_film_rgb8(rt_scene *scene, const float *rgb, size_t n_pixels, uint8_t *out_rgb8);
 

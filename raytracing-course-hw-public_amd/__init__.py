@@ -21,6 +21,8 @@ from ._ctypes_abi import (
     ABI_PROTOTYPES,
     ERROR_NAMES,
     HOST_PROTOTYPES,
+    RT_ACCUM_FEATURES,
+    RT_DENOISE_NO_DEMODULATE,
     RT_FLAG_COUNTERS,
     RT_FLAG_DEVICE_FB,
     RT_BUILD_DEVICE_LBVH,
@@ -50,6 +52,7 @@ from ._ctypes_abi import (
     DescHolder,
     RtAdaptive,
     RtCamera,
+    RtDenoise,
     RtParams,
     RtSceneDesc,
     RtView,
@@ -269,10 +272,11 @@ class DeviceScene:
         except Exception:
             pass
 
-    def accumulator(self, width: int, height: int, camera=None, seed: int = 0) -> "Accumulator":
+    def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
-        RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view."""
-        return Accumulator(self, width, height, camera, seed)
+        RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view. `features`: keep the first-hit
+        albedo / normal / depth sums as well (rt_accum_create_ex with RT_ACCUM_FEATURES), which features(), read_features() and denoise() need."""
+        return Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0)
 
     def run_raytracer(
         self,
@@ -468,14 +472,18 @@ class Accumulator:
     """Progressive and adaptive rendering (include/rt_abi.h rt_accum_*): per-pixel sums S, E (even-index samples) and counts n that
     survive between calls. Keeps its DeviceScene alive; DeviceScene.close() closes it first."""
 
-    def __init__(self, scene: DeviceScene, width: int, height: int, camera=None, seed: int = 0):
+    def __init__(self, scene: DeviceScene, width: int, height: int, camera=None, seed: int = 0, accum_flags: int = 0):
         self._scene = scene
         self.width, self.height = int(width), int(height)
         self._h = C.c_void_p()
         cam = None
         if camera is not None:
             cam = make_views([camera], 0)[0].camera
-        _check(lib().rt_accum_create(scene._h, self.width, self.height, C.byref(cam) if cam is not None else None, int(seed), C.byref(self._h)))
+        cam_p = C.byref(cam) if cam is not None else None
+        if accum_flags:
+            _check(lib().rt_accum_create_ex(scene._h, self.width, self.height, cam_p, int(seed), int(accum_flags), C.byref(self._h)))
+        else:
+            _check(lib().rt_accum_create(scene._h, self.width, self.height, cam_p, int(seed), C.byref(self._h)))
         scene._accums.append(self)
 
     def _params(self, samples: int, global_best: bool, counters: bool, tuning: dict):
@@ -523,6 +531,53 @@ class Accumulator:
         }
         _check(lib().rt_accum_read(self._h, fptr(out["sum"]), fptr(out["even_sum"]), u32ptr(out["samples"]), fptr(out["error"])))
         return out
+
+    def read_features(self) -> dict:
+        """The raw first-hit sums (rt_accum_read_features): "albedo_sum" and "normal_sum" (H, W, 3) float32, "depth_sum" (H, W) float32,
+        "hits" (H, W) uint32. Needs accumulator(features=True)."""
+        out = {
+            "albedo_sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
+            "normal_sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
+            "depth_sum": np.zeros((self.height, self.width), dtype=np.float32),
+            "hits": np.zeros((self.height, self.width), dtype=np.uint32),
+        }
+        _check(lib().rt_accum_read_features(self._h, fptr(out["albedo_sum"]), fptr(out["normal_sum"]), fptr(out["depth_sum"]), u32ptr(out["hits"])))
+        return out
+
+    def features(self) -> dict:
+        """The feature means (rt_accum_resolve_features): "albedo" = AS / n and "normal" = NS / n (not renormalised), (H, W, 3) float32;
+        "depth" = ZS / h (0 where no sample hit), (H, W) float32."""
+        out = {
+            "albedo": np.zeros((self.height, self.width, 3), dtype=np.float32),
+            "normal": np.zeros((self.height, self.width, 3), dtype=np.float32),
+            "depth": np.zeros((self.height, self.width), dtype=np.float32),
+        }
+        _check(lib().rt_accum_resolve_features(self._h, 0, out["albedo"].ctypes.data_as(C.c_void_p), out["normal"].ctypes.data_as(C.c_void_p),
+                                               out["depth"].ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoise(self, rgb8: bool = False, **opts) -> np.ndarray:
+        """rt_accum_denoise: the image filtered by the edge-avoiding a-trous filter that the feature means and the half-buffer noise estimate
+        guide; the accumulator is not modified. `opts`: rt_denoise fields by name (iterations, sigma_color, sigma_depth, normal_sharpness,
+        flags, reserved) or demodulate=False for RT_DENOISE_NO_DEMODULATE. (H, W, 3) float32, or the device film's uint8 image with `rgb8`."""
+        o = RtDenoise()
+        for k, v in opts.items():
+            if k == "demodulate":
+                if not v:
+                    o.flags |= RT_DENOISE_NO_DEMODULATE
+            elif k == "reserved":
+                for i, r in enumerate(v):
+                    o.reserved[i] = int(r)
+            elif k in ("sigma_color", "sigma_depth"):
+                setattr(o, k, float(v))
+            elif k in ("iterations", "normal_sharpness", "flags"):
+                setattr(o, k, int(v) | (o.flags if k == "flags" else 0))
+            else:
+                raise TypeError(f"rt_denoise has no field {k!r}")
+        img = np.zeros((self.height, self.width, 3), dtype=np.uint8 if rgb8 else np.float32)
+        fn = lib().rt_accum_denoise_rgb8 if rgb8 else lib().rt_accum_denoise
+        _check(fn(self._h, C.byref(o), 0, img.ctypes.data_as(C.c_void_p)))
+        return img
 
     def close(self) -> None:
         if self._h:

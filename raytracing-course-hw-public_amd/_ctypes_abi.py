@@ -28,6 +28,8 @@ RT_FLAG_DEVICE_FB = 1
 RT_FLAG_COUNTERS = 2
 RT_FLAG_MEGAKERNEL = 4
 RT_FLAG_GLOBAL_BEST = 8
+RT_ACCUM_FEATURES = 1
+RT_DENOISE_NO_DEMODULATE = 1
 RT_CAST_PROBE, RT_CAST_EXTEND, RT_CAST_EXTEND_GLOBAL, RT_CAST_PACKET, RT_CAST_PACKET_GLOBAL = range(5)
 
 RT_OK = 0
@@ -60,6 +62,17 @@ class RtCamera(C.Structure):
 
 class RtView(C.Structure):  # rt_render_views: one camera view (64 bytes)
     _fields_ = [("camera", RtCamera), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class RtDenoise(C.Structure):  # rt_accum_denoise: the filter's options (32 bytes; all-zero = the defaults)
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("sigma_color", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("normal_sharpness", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
 
 
 class RtAdaptive(C.Structure):  # rt_accum_render_adaptive: the adaptive rule's parameters (32 bytes)
@@ -212,6 +225,11 @@ ABI_PROTOTYPES = {
     "rt_accum_resolve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_accum_resolve_rgb8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_accum_read": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_u32_p, c_float_p]),
+    "rt_accum_create_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtCamera), C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rt_accum_read_features": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_u32_p]),
+    "rt_accum_resolve_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_accum_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
+    "rt_accum_denoise_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
     "rt_last_error": (C.c_char_p, []),
     "rt_source_stamp": (C.c_char_p, []),
     "rt_abi_version": (C.c_uint32, []),

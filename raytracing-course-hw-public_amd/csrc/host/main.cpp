@@ -15,6 +15,11 @@
 // RT_ADAPTIVE=<threshold>: adaptive sampling through an accumulator (rt_accum_render_adaptive) of the scene's camera on one GPU; the SPP
 // argument becomes max_samples, RT_ADAPTIVE_MIN (default 16, capped at the SPP) and RT_ADAPTIVE_STEP (default 32) set min_samples and step.
 // RT_SPP_MAP=<file.pgm> also writes the per-pixel sample counts (16-bit PGM). RT_VERBOSE adds the rounds and the mean SPP.
+// RT_DENOISE=1: render through a feature accumulator (rt_accum_create_ex, RT_ACCUM_FEATURES) on one GPU and write the image filtered by
+// rt_accum_denoise (defaults of rt_denoise); with RT_ADAPTIVE the samples come from the adaptive call, otherwise the SPP argument is one
+// progressive call (rt_accum_render). RT_AOV=<prefix> (with or without RT_DENOISE: it renders through a feature accumulator too) also writes
+// the first-hit feature means: <prefix>_albedo.ppm (clamp(a, 0, 1) * 255 + 0.5, truncated), <prefix>_normal.ppm (0.5 * n + 0.5, quantised
+// likewise) and <prefix>_depth.pfm (one channel "Pf", little-endian floats, rows bottom to top as PFM has them).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -72,12 +77,15 @@ int main(int argc, char **argv) {
     }
     const char *dev_env = std::getenv("RT_DEVICE");
     const char *adaptive = std::getenv("RT_ADAPTIVE"); // accumulators run on one GPU
-    rt_scene *scene = nullptr;
-    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !adaptive ? RT_ALL_DEVICES : 0);
     auto env_on = [](const char *name) {
         const char *v = std::getenv(name);
         return v && std::atoi(v) != 0;
     };
+    const bool denoise = env_on("RT_DENOISE");
+    const char *aov = std::getenv("RT_AOV");
+    const bool accumulate = adaptive || denoise || aov;
+    rt_scene *scene = nullptr;
+    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !accumulate ? RT_ALL_DEVICES : 0);
     rt_scene_desc desc = *rt_loaded_desc(loaded); // the arrays stay the loader's; only the build options change
     if (env_on("RT_BVH_DEVICE"))
         desc.build_flags |= RT_BUILD_DEVICE_LBVH;
@@ -141,42 +149,51 @@ int main(int argc, char **argv) {
     int rc = RT_ERR_UNSUPPORTED;
     uint32_t rounds = 0;
     std::vector<uint32_t> spp_map;
-    if (adaptive) {
+    std::vector<float> aov_albedo, aov_normal, aov_depth;
+    if (accumulate) {
         if (!views.empty()) {
             rt_destroy(scene);
             rt_loaded_free(loaded);
-            std::cerr << "RT_ADAPTIVE renders the scene's camera only (not with RT_ALL_CAMERAS)" << std::endl;
+            std::cerr << "RT_ADAPTIVE / RT_DENOISE / RT_AOV render the scene's camera only (not with RT_ALL_CAMERAS)" << std::endl;
             return EXIT_FAILURE;
         }
-        rt_adaptive ad{};
-        ad.threshold = std::strtof(adaptive, nullptr);
-        ad.max_samples = samples;
-        const char *mn = std::getenv("RT_ADAPTIVE_MIN");
-        ad.min_samples = mn ? (uint32_t)std::strtoul(mn, nullptr, 10) : std::min(16u, samples);
-        if (const char *step = std::getenv("RT_ADAPTIVE_STEP"))
-            ad.step = (uint32_t)std::strtoul(step, nullptr, 10);
         rt_accum *acc = nullptr;
-        rc = rt_accum_create(scene, width, height, nullptr, p.seed, &acc);
-        if (rc == RT_OK)
+        rc = rt_accum_create_ex(scene, width, height, nullptr, p.seed, (denoise || aov) ? RT_ACCUM_FEATURES : 0u, &acc);
+        if (rc == RT_OK && adaptive) {
+            rt_adaptive ad{};
+            ad.threshold = std::strtof(adaptive, nullptr);
+            ad.max_samples = samples;
+            const char *mn = std::getenv("RT_ADAPTIVE_MIN");
+            ad.min_samples = mn ? (uint32_t)std::strtoul(mn, nullptr, 10) : std::min(16u, samples);
+            if (const char *step = std::getenv("RT_ADAPTIVE_STEP"))
+                ad.step = (uint32_t)std::strtoul(step, nullptr, 10);
             rc = rt_accum_render_adaptive(acc, &p, &ad, &rounds, &st);
+        } else if (rc == RT_OK) {
+            rc = rt_accum_render(acc, &p, &st); // the SPP argument as one progressive call
+        }
         if (rc == RT_OK) { // the film as for rt_render_rgb8: on the device unless RT_FILM=host or the device film declines
-            rc = (film && !std::strcmp(film, "host")) ? RT_ERR_UNSUPPORTED : rt_accum_resolve_rgb8(acc, 0, rgb8.data());
+            const bool host_film = film && !std::strcmp(film, "host");
+            rc = host_film ? RT_ERR_UNSUPPORTED : denoise ? rt_accum_denoise_rgb8(acc, nullptr, 0, rgb8.data()) : rt_accum_resolve_rgb8(acc, 0, rgb8.data());
             if (rc == RT_ERR_UNSUPPORTED) {
                 std::vector<float> fb(view_pixels * 3, 0.0f);
-                rc = rt_accum_resolve(acc, 0, fb.data());
+                rc = denoise ? rt_accum_denoise(acc, nullptr, 0, fb.data()) : rt_accum_resolve(acc, 0, fb.data());
                 if (rc == RT_OK)
                     rt_tonemap_rgb8(fb.data(), view_pixels, rgb8.data());
             }
         }
-        if (rc == RT_OK) {
+        if (rc == RT_OK && adaptive) {
             spp_map.resize(view_pixels);
             rc = rt_accum_read(acc, nullptr, nullptr, spp_map.data(), nullptr);
+        }
+        if (rc == RT_OK && aov) {
+            aov_albedo.resize(view_pixels * 3), aov_normal.resize(view_pixels * 3), aov_depth.resize(view_pixels);
+            rc = rt_accum_resolve_features(acc, 0, aov_albedo.data(), aov_normal.data(), aov_depth.data());
         }
         if (acc)
             rt_accum_destroy(acc);
     } else if (!(film && !std::strcmp(film, "host")))
         rc = views.empty() ? rt_render_rgb8(scene, &p, rgb8.data(), &st) : rt_render_views_rgb8(scene, &p, views.data(), (uint32_t)views.size(), rgb8.data(), &st);
-    if (rc == RT_ERR_UNSUPPORTED && !adaptive) {
+    if (rc == RT_ERR_UNSUPPORTED && !accumulate) {
         std::vector<float> fb(n_out * view_pixels * 3, 0.0f);
         rc = views.empty() ? rt_render(scene, &p, fb.data(), &st) : rt_render_views(scene, &p, views.data(), (uint32_t)views.size(), fb.data(), &st);
         if (rc == RT_OK)
@@ -196,6 +213,29 @@ int main(int argc, char **argv) {
             if (rt_write_ppm(name.string().c_str(), width, height, rgb8.data() + i * view_pixels * 3) != RT_OK)
                 return die("write");
         }
+    }
+    if (aov) {
+        auto quantise = [&](const std::vector<float> &v, float scale, float bias) {
+            std::vector<uint8_t> q(v.size());
+            for (size_t i = 0; i < v.size(); ++i) {
+                const float x = v[i] * scale + bias;
+                q[i] = (uint8_t)(std::min(std::max(x, 0.0f), 1.0f) * 255.0f + 0.5f);
+            }
+            return q;
+        };
+        const std::string prefix(aov);
+        if (rt_write_ppm((prefix + "_albedo.ppm").c_str(), width, height, quantise(aov_albedo, 1.0f, 0.0f).data()) != RT_OK ||
+            rt_write_ppm((prefix + "_normal.ppm").c_str(), width, height, quantise(aov_normal, 0.5f, 0.5f).data()) != RT_OK)
+            return die("RT_AOV");
+        FILE *f = std::fopen((prefix + "_depth.pfm").c_str(), "wb");
+        if (!f) {
+            std::cerr << "RT_AOV: cannot write " << prefix << "_depth.pfm" << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::fprintf(f, "Pf\n%u %u\n-1.0\n", width, height); // negative scale: little-endian
+        for (unsigned y = height; y-- > 0;)
+            std::fwrite(aov_depth.data() + (size_t)y * width, sizeof(float), width, f);
+        std::fclose(f);
     }
     if (adaptive) {
         if (const char *map_path = std::getenv("RT_SPP_MAP")) { // binary 16-bit PGM, big-endian, counts clamped to 65535

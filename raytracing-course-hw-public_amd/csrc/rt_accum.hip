@@ -116,6 +116,25 @@ __global__ __launch_bounds__(256) void accum_image_kernel(const rt::AccumRound R
     }
 }
 
+// the feature means of rt_accum_resolve_features: AS / n, NS / n (not renormalised), ZS / h; 0 where the divisor is 0
+__global__ __launch_bounds__(256) void accum_feature_means_kernel(const rt::AccumRound R, const WfFeat F, float *albedo, float *normal, float *depth) {
+    const uint32_t n_pix = R.width * R.height;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pix; p += gridDim.x * blockDim.x) {
+        const uint32_t n = R.count[p], h = F.hits[p];
+        V3 a = mk(0, 0, 0), nr = mk(0, 0, 0);
+        if (n != 0u) {
+            a = ld3(F.albedo_sum + 3ull * p) / (float)n;
+            nr = ld3(F.normal_sum + 3ull * p) / (float)n;
+        }
+        if (albedo)
+            albedo[3ull * p] = a.x, albedo[3ull * p + 1] = a.y, albedo[3ull * p + 2] = a.z;
+        if (normal)
+            normal[3ull * p] = nr.x, normal[3ull * p + 1] = nr.y, normal[3ull * p + 2] = nr.z;
+        if (depth)
+            depth[p] = h != 0u ? F.depth_sum[p] / (float)h : 0.0f;
+    }
+}
+
 dim3 accum_grid(const rt::AccumRound &R) {
     const uint64_t n_pix = (uint64_t)R.width * R.height;
     const uint64_t b = (n_pix + 255u) / 256u;
@@ -156,6 +175,10 @@ hipError_t launch_accum_plan(const AccumRound &R, uint32_t chunk, hipStream_t st
 
 hipError_t launch_accum_image(const AccumRound &R, float *fb, hipStream_t stream) {
     return RT_LAUNCH_CHECKED(accum_image_kernel, accum_grid(R), dim3(256), 0, stream, R, fb);
+}
+
+hipError_t launch_accum_feature_means(const AccumRound &R, const WfFeat &F, float *albedo, float *normal, float *depth, hipStream_t stream) {
+    return RT_LAUNCH_CHECKED(accum_feature_means_kernel, accum_grid(R), dim3(256), 0, stream, R, F, albedo, normal, depth);
 }
 
 } // namespace rt

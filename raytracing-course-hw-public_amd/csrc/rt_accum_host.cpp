@@ -17,6 +17,9 @@ struct rt_accum {
     rt::AccumRound R{};
     std::vector<void *> owned;
     rt::PacketPolicy pkt; // of its own passes, kept apart from rt_render's
+    bool features = false; // RT_ACCUM_FEATURES: F holds the four first-hit sums (F.rec is the scene's, bound per fill)
+    WfFeat F{};
+    rt::DenoiseBufs D{};   // rt_accum_denoise's workspace (64 B per pixel), allocated by its first call
     ~rt_accum() {
         (void)hipSetDevice(scene->device);
         (void)hipStreamSynchronize(scene->stream);
@@ -25,10 +28,26 @@ struct rt_accum {
     }
 };
 
+template <class T> static int accum_alloc(rt_accum *a, size_t bytes, T **ptr, const char *fn) {
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+    if (e != hipSuccess)
+        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+    a->owned.push_back(q);
+    *ptr = static_cast<T *>(q);
+    return RT_OK;
+}
+
 extern "C" int rt_accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, rt_accum **out) {
+    return rt_accum_create_ex(s, width, height, camera, seed, 0u, out);
+}
+
+extern "C" int rt_accum_create_ex(rt_scene *s, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, uint32_t accum_flags, rt_accum **out) {
     if (!s || !out)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create: null argument");
     *out = nullptr;
+    if (accum_flags & ~(uint32_t)RT_ACCUM_FEATURES)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create_ex: unknown accum_flags bit");
     if (width == 0 || height == 0 || (uint64_t)width * height >= 0x7FFFFFFFull)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create: image size " + std::to_string(width) + "x" + std::to_string(height));
     if (s->group)
@@ -40,15 +59,7 @@ extern "C" int rt_accum_create(rt_scene *s, uint32_t width, uint32_t height, con
     a->height = height;
     a->view = rt::make_view(camera ? *camera : s->cam, width, height, seed);
     const size_t n = (size_t)width * height;
-    auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-        if (e != hipSuccess)
-            return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_accum_create: ") + hipGetErrorString(e));
-        a->owned.push_back(q);
-        *ptr = static_cast<T *>(q);
-        return RT_OK;
-    };
+    auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int { return accum_alloc(a.get(), bytes, ptr, "rt_accum_create"); };
     rt::AccumRound &R = a->R;
     R.width = width;
     R.height = height;
@@ -60,6 +71,17 @@ extern "C" int rt_accum_create(rt_scene *s, uint32_t width, uint32_t height, con
         (rc = alloc(4 * (n + 1), &R.list_off)) != RT_OK || (rc = alloc(8, &R.totals)) != RT_OK || (rc = alloc(R.scan_temp_bytes, &R.scan_temp)) != RT_OK ||
         (rc = alloc(sizeof(WfView), &a->d_view)) != RT_OK)
         return rc;
+    if (accum_flags & RT_ACCUM_FEATURES) {
+        WfFeat &F = a->F;
+        if ((rc = alloc(12 * n, &F.albedo_sum)) != RT_OK || (rc = alloc(12 * n, &F.normal_sum)) != RT_OK || (rc = alloc(4 * n, &F.depth_sum)) != RT_OK ||
+            (rc = alloc(4 * n, &F.hits)) != RT_OK)
+            return rc;
+        HIP_TRY(hipMemsetAsync(F.albedo_sum, 0, 12 * n, s->stream)); // +0.0
+        HIP_TRY(hipMemsetAsync(F.normal_sum, 0, 12 * n, s->stream));
+        HIP_TRY(hipMemsetAsync(F.depth_sum, 0, 4 * n, s->stream));
+        HIP_TRY(hipMemsetAsync(F.hits, 0, 4 * n, s->stream));
+        a->features = true;
+    }
     HIP_TRY(hipMemsetAsync(R.sum, 0, 12 * n, s->stream)); // +0.0
     HIP_TRY(hipMemsetAsync(R.even_sum, 0, 12 * n, s->stream));
     HIP_TRY(hipMemsetAsync(R.count, 0, 4 * n, s->stream));
@@ -139,6 +161,11 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
             const uint64_t cap = std::min<uint64_t>((uint64_t)std::min(per_pass, tot[0]) * C, tot[1]);
             if (int rc = s->ensure_wavefront(cap, std::max<uint64_t>(s->wf_pixels_cap, 1), s->dev.ray_depth); rc != RT_OK)
                 return rc;
+            if (a->features) {
+                if (int rc = s->ensure_features(); rc != RT_OK)
+                    return rc;
+                a->F.rec = s->wf_feat;
+            }
             s->wf_bind(W);
             W.fb = nullptr;
             W.accum = nullptr; // wf_resolve does not run on an accumulator pass
@@ -147,7 +174,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 W.n_paths = (uint32_t)std::min<uint64_t>((uint64_t)A.n_entries * C, tot[1]); // an upper bound: wf_generate_list reads the exact count
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
-                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A));
+                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr));
                 passes += 1;
                 packet_passes += W.use_packet;
                 if (p->progress && !ad) {
@@ -280,6 +307,138 @@ extern "C" int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb,
         HIP_TRY(hipMemcpyAsync(samples, acc->R.count, 4 * n, hipMemcpyDeviceToHost, s->stream));
     if (error)
         HIP_TRY(hipMemcpyAsync(error, acc->R.err, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+// ---- first-hit features and the denoiser (rt_abi.h RT_ACCUM_FEATURES, rt_accum_denoise)
+static int feature_check(const rt_accum *acc, const char *fn) {
+    if (!acc)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null accumulator");
+    if (!acc->features)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator was created without RT_ACCUM_FEATURES");
+    return RT_OK;
+}
+
+extern "C" int rt_accum_read_features(rt_accum *acc, float *albedo_sum, float *normal_sum, float *depth_sum, uint32_t *hits) {
+    if (int rc = feature_check(acc, "rt_accum_read_features"); rc != RT_OK)
+        return rc;
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)acc->width * acc->height;
+    if (albedo_sum)
+        HIP_TRY(hipMemcpyAsync(albedo_sum, acc->F.albedo_sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
+    if (normal_sum)
+        HIP_TRY(hipMemcpyAsync(normal_sum, acc->F.normal_sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
+    if (depth_sum)
+        HIP_TRY(hipMemcpyAsync(depth_sum, acc->F.depth_sum, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    if (hits)
+        HIP_TRY(hipMemcpyAsync(hits, acc->F.hits, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_accum_resolve_features(rt_accum *acc, uint32_t flags, float *albedo, float *normal, float *depth) {
+    if (int rc = feature_check(acc, "rt_accum_resolve_features"); rc != RT_OK)
+        return rc;
+    if (flags & ~(uint32_t)RT_FLAG_DEVICE_FB)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_features: flags other than RT_FLAG_DEVICE_FB");
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)acc->width * acc->height;
+    if (flags & RT_FLAG_DEVICE_FB) {
+        HIP_TRY(rt::launch_accum_feature_means(acc->R, acc->F, albedo, normal, depth, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        return RT_OK;
+    }
+    if (int rc = s->ensure_fb(7 * n); rc != RT_OK) // staging: albedo, normal, depth
+        return rc;
+    float *d_a = s->d_fb, *d_n = s->d_fb + 3 * n, *d_z = s->d_fb + 6 * n;
+    HIP_TRY(rt::launch_accum_feature_means(acc->R, acc->F, d_a, d_n, d_z, s->stream));
+    if (albedo)
+        HIP_TRY(hipMemcpyAsync(albedo, d_a, 12 * n, hipMemcpyDeviceToHost, s->stream));
+    if (normal)
+        HIP_TRY(hipMemcpyAsync(normal, d_n, 12 * n, hipMemcpyDeviceToHost, s->stream));
+    if (depth)
+        HIP_TRY(hipMemcpyAsync(depth, d_z, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+// the defaults of rt_denoise: chosen by the sweep recorded in profiles/denoise_quality.txt
+static int denoise_options(const rt_accum *acc, const rt_denoise *opt, uint32_t flags, const void *out, const char *fn, rt::DenoiseOpt *O) {
+    if (int rc = feature_check(acc, fn); rc != RT_OK)
+        return rc;
+    if (!out || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null buffer or flags other than RT_FLAG_DEVICE_FB");
+    const rt_denoise zero{};
+    const rt_denoise &o = opt ? *opt : zero;
+    for (uint32_t r : o.reserved)
+        if (r != 0)
+            return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": reserved fields must be 0");
+    if (o.iterations > 8u || o.normal_sharpness > 8u || (o.flags & ~(uint32_t)RT_DENOISE_NO_DEMODULATE))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": iterations and normal_sharpness are at most 8; unknown rt_denoise.flags bit");
+    if (!(o.sigma_color >= 0.0f) || std::isinf(o.sigma_color) || !(o.sigma_depth >= 0.0f) || std::isinf(o.sigma_depth))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": sigma_color and sigma_depth must be finite and >= 0");
+    O->iterations = o.iterations ? o.iterations : 5u;
+    O->sigma_color = o.sigma_color != 0.0f ? o.sigma_color : 8.0f;
+    O->sigma_depth = o.sigma_depth != 0.0f ? o.sigma_depth : 0.5f;
+    O->sharpness = o.normal_sharpness ? o.normal_sharpness : 3u;
+    O->demodulate = (o.flags & RT_DENOISE_NO_DEMODULATE) ? 0u : 1u;
+    return RT_OK;
+}
+
+static int denoise_buffers(rt_accum *acc, const char *fn) {
+    if (acc->D.guide)
+        return RT_OK;
+    const size_t n = (size_t)acc->width * acc->height;
+    int rc;
+    if ((rc = accum_alloc(acc, 16 * n, &acc->D.sig[0], fn)) != RT_OK || (rc = accum_alloc(acc, 16 * n, &acc->D.sig[1], fn)) != RT_OK ||
+        (rc = accum_alloc(acc, 16 * n, &acc->D.den, fn)) != RT_OK)
+        return rc;
+    return accum_alloc(acc, 32 * n, &acc->D.guide, fn); // last: its pointer says the workspace is complete
+}
+
+extern "C" int rt_accum_denoise(rt_accum *acc, const rt_denoise *opt, uint32_t flags, float *fb_rgb) {
+    rt::DenoiseOpt O{};
+    if (int rc = denoise_options(acc, opt, flags, fb_rgb, "rt_accum_denoise", &O); rc != RT_OK)
+        return rc;
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)acc->width * acc->height;
+    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
+    if (int rc = denoise_buffers(acc, "rt_accum_denoise"); rc != RT_OK)
+        return rc;
+    if (!device_fb)
+        if (int rc = s->ensure_fb(3 * n); rc != RT_OK)
+            return rc;
+    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, device_fb ? fb_rgb : s->d_fb, s->stream));
+    if (!device_fb)
+        HIP_TRY(hipMemcpyAsync(fb_rgb, s->d_fb, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint32_t flags, uint8_t *rgb8) {
+    rt::DenoiseOpt O{};
+    if (int rc = denoise_options(acc, opt, flags, rgb8, "rt_accum_denoise_rgb8", &O); rc != RT_OK)
+        return rc;
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t n = acc->width * acc->height;
+    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
+    int rc = denoise_buffers(acc, "rt_accum_denoise_rgb8");
+    if (rc == RT_OK)
+        rc = s->ensure_fb(3ull * n);
+    if (rc == RT_OK)
+        rc = s->ensure_film(device_fb ? 0 : 3ull * n);
+    if (rc != RT_OK)
+        return rc;
+    uint8_t *d_rgb8 = device_fb ? rgb8 : s->d_rgb8;
+    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, s->d_fb, s->stream));
+    HIP_TRY(rt::launch_film(s->d_fb, d_rgb8, n, 0, 1, n, s->d_film_table, s->stream)); // image.h:49-82, as rt_accum_resolve_rgb8
+    if (!device_fb)
+        HIP_TRY(hipMemcpyAsync(rgb8, d_rgb8, 3ull * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RT_OK;
 }

@@ -300,6 +300,16 @@ struct WfAccum {
     uint32_t first_entry, n_entries; // this pass: entries [first_entry, first_entry + n_entries)
 };
 
+// The first-hit features of a pass of a feature accumulator (rt_abi.h RT_ACCUM_FEATURES). wf_features writes one record per path after bounce
+// 0's closest hits: rec[2 * path] = {albedo.rgb, t}, rec[2 * path + 1] = {shading normal.xyz, hit flag (u32 bits: 1 hit, 0 miss)}; a miss is
+// all zeros. wf_resolve_features adds them onto the four per-pixel sums in sample order, one lane per entry, as wf_resolve_list adds samples.
+struct WfFeat {
+    RtF4 *rec;                             // [2 * paths of the pass]: 32 B per path, in the scene's wavefront workspace
+    float *albedo_sum, *normal_sum;        // [3 * pixels]: AS_p, NS_p
+    float *depth_sum;                      // [pixels]: ZS_p
+    uint32_t *hits;                        // [pixels]: h_p
+};
+
 struct RenderLaunch {
     uint32_t width, height, samples, rng_mode;
     uint64_t seed;

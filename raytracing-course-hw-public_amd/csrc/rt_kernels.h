@@ -64,10 +64,11 @@ struct WfHostSync {
 };
 #define WF_HOST_CENSUS_WORD 40 /* 8-byte aligned, behind RT_MAX_RAY_DEPTH + 1 size words */
 // `acc` (optional): an accumulator pass (rt_accum.hip): wf_generate_list / wf_resolve_list over the round's entry list replace wf_generate /
-// wf_resolve; first_pass / last_pass are not read. Null for rt_render.
+// wf_resolve; first_pass / last_pass are not read. Null for rt_render. `feat` (optional, with `acc`): the pass of a feature accumulator:
+// wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither.
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
-                                 const WfAccum *acc = nullptr);
+                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr);
 // closest-hit probe through the renderer's own kernels: `rays` (6 floats each, device) -> queue -> wf_extend (or wf_extend_packet)
 // -> prim / bct (device). `L` carries the workspace (paths_in, hits, counters, stack_overflow, stats) and the traversal mode.
 hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *rays, uint32_t n, bool packet, bool stats, uint32_t *prim, float *bct,
@@ -101,4 +102,17 @@ hipError_t launch_accum_uniform(const AccumRound &R, uint32_t samples, hipStream
 hipError_t launch_accum_plan(const AccumRound &R, uint32_t chunk, hipStream_t stream);
 // fb[p] = S_p / (float)n_p (0 where n_p = 0)
 hipError_t launch_accum_image(const AccumRound &R, float *fb, hipStream_t stream);
+// the feature means (rt_accum_resolve_features): AS / n, NS / n, ZS / h; any output may be null
+hipError_t launch_accum_feature_means(const AccumRound &R, const WfFeat &F, float *albedo, float *normal, float *depth, hipStream_t stream);
+// rt_denoise.hip: the a-trous filter of rt_accum_denoise (the rule: rt_abi.h). `D` is the filter's workspace, owned by the accumulator.
+struct DenoiseBufs {
+    RtF4 *sig[2]; // [pixels]: the working signal L, ping-pong
+    RtF4 *den;    // [pixels]: den.rgb
+    RtF4 *guide;  // [2 * pixels]: {N.xyz, Z}, {s, flags (u32 bits: 1 valid, 2 hit), 0, 0}
+};
+struct DenoiseOpt {
+    uint32_t iterations, sharpness, demodulate;
+    float sigma_color, sigma_depth;
+};
+hipError_t launch_denoise(const AccumRound &R, const WfFeat &F, const DenoiseBufs &D, const DenoiseOpt &O, float *fb, hipStream_t stream);
 } // namespace rt

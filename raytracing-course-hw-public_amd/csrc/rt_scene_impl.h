@@ -177,6 +177,26 @@ struct rt_scene {
         return RT_OK;
     }
 
+    // the per-path feature records of a feature accumulator's passes (WfFeat::rec, 32 B per path): allocated the first time such an
+    // accumulator renders on this scene, and sized like the wavefront workspace (call after ensure_wavefront)
+    RtF4 *wf_feat = nullptr;
+    uint64_t wf_feat_cap = 0; // paths
+    int ensure_features() {
+        if (wf_feat_cap >= wf_paths_cap)
+            return RT_OK;
+        if (wf_feat)
+            (void)hipFree(wf_feat);
+        wf_feat = nullptr;
+        wf_feat_cap = 0;
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, wf_paths_cap * 2 * sizeof(RtF4));
+        if (e != hipSuccess)
+            return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("feature records: ") + hipGetErrorString(e));
+        wf_feat = static_cast<RtF4 *>(q);
+        wf_feat_cap = wf_paths_cap;
+        return RT_OK;
+    }
+
     // the workspace half of a WfLaunch (after ensure_wavefront): queues, hit records, counters, stack workspace, sort buffers
     void wf_bind(WfLaunch &W) {
         W.paths_in = wf_paths[0];
@@ -214,6 +234,8 @@ struct rt_scene {
             (void)hipFree(p);
         for (void *p : owned)
             (void)hipFree(p);
+        if (wf_feat)
+            (void)hipFree(wf_feat);
         if (d_fb)
             (void)hipFree(d_fb);
         if (d_rgb8)
@@ -241,7 +263,7 @@ void set_camera(DevScene &D, const float *pos, const float *right, const float *
 int check_pass_params(const rt_params *p, const char *fn);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
 hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                       const WfAccum *acc);
+                       const WfAccum *acc, const WfFeat *feat = nullptr);
 int fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats);
 
 // Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are

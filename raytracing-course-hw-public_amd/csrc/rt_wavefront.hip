@@ -343,6 +343,32 @@ __global__ __launch_bounds__(256) void wf_extend_prims(const DevScene S, const W
     }
 }
 
+// ------------------------------------------------------------------------------------------------ first-hit features
+// A pass of a feature accumulator (rt_abi.h RT_ACCUM_FEATURES), after bounce 0's closest hits: the albedo, shading normal and distance of every
+// primary ray's hit, from the shading record wf_shade is about to make of the same (ray, hit) pair (make_surf), one 32-byte record per path.
+// At bounce 0 queue position i holds path i (wf_generate*), and no order is in force. Counts nothing: the event counters are shade()'s.
+__global__ __launch_bounds__(256) void wf_features(const DevScene S, const WfLaunch L, const WfFeat F) {
+    __shared__ float s_lin[256];
+    __shared__ float s_gam[256];
+    s_lin[threadIdx.x] = S.lut_linear[threadIdx.x];
+    s_gam[threadIdx.x] = S.lut_gamma[threadIdx.x];
+    __syncthreads();
+    LaneStats<false> st;
+    const uint32_t n_in = L.counters[WF_CNT_IN];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_in; i += gridDim.x * blockDim.x) {
+        const WfHead in = wf_load_head(L.paths_in + i);
+        const Hit h = wf_load_hit(L.hits + i);
+        RtF4 r0{0.f, 0.f, 0.f, 0.f}, r1{0.f, 0.f, 0.f, __uint_as_float(0u)};
+        if (h.k != RT_NONE) {
+            const Surf sf = make_surf<false>(S, h, in.o, in.d, s_lin, s_gam, st);
+            r0 = RtF4{sf.color.r, sf.color.g, sf.color.b, h.t};
+            r1 = RtF4{sf.shading_normal.x, sf.shading_normal.y, sf.shading_normal.z, __uint_as_float(1u)};
+        }
+        F.rec[2ull * in.id] = r0;
+        F.rec[2ull * in.id + 1] = r1;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ shade
 // LIGHTS_LDS: the light BVH (inner nodes, triangles, aux) is small enough (DevBvh::lds_inner) to be staged in LDS once per
 // block; bvh_mix_dist's sample and pdf then read it there: a dozen dependent L1 round trips per hit become LDS reads.
@@ -620,6 +646,31 @@ __global__ __launch_bounds__(256) void wf_resolve_list(const WfLaunch L, const W
     }
 }
 
+// The feature sums of the same entries (WfFeat): the lane that owns the pixel adds its k records in sample order. Runs before
+// wf_resolve_list of the pass (it reads the entry's base count from the list, never n_p).
+__global__ __launch_bounds__(256) void wf_resolve_features(const WfAccum A, const WfFeat F) {
+    const uint32_t *off = A.list_off + A.first_entry;
+    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
+        const uint32_t p = A.list_pix[A.first_entry + le];
+        const uint32_t k = off[le + 1] - off[le];
+        V3 al = ld3(F.albedo_sum + 3ull * p), nr = ld3(F.normal_sum + 3ull * p);
+        float z = F.depth_sum[p];
+        uint32_t hits = F.hits[p];
+        const RtF4 *src = F.rec + 2ull * (off[le] - off[0]);
+        for (uint32_t j = 0; j < k; ++j) {
+            const RtF4 r0 = src[2u * j], r1 = src[2u * j + 1u];
+            al = al + mk(r0.x, r0.y, r0.z);
+            nr = nr + mk(r1.x, r1.y, r1.z);
+            z = z + r0.w;
+            hits += __float_as_uint(r1.w);
+        }
+        F.albedo_sum[3ull * p] = al.x, F.albedo_sum[3ull * p + 1] = al.y, F.albedo_sum[3ull * p + 2] = al.z;
+        F.normal_sum[3ull * p] = nr.x, F.normal_sum[3ull * p + 1] = nr.y, F.normal_sum[3ull * p + 2] = nr.z;
+        F.depth_sum[p] = z;
+        F.hits[p] = hits;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ probe: rays in, hits out
 // rt_cast_rays_ex: arbitrary rays go through the SAME closest-hit kernels the renderer launches. wf_from_rays writes them as
 // queue records (what wf_generate / wf_shade write for their rays), wf_hits_out turns the hit records into the probe's output.
@@ -696,7 +747,8 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 }
 
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
-                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc) {
+                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc,
+                                 const WfFeat *feat) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
@@ -772,6 +824,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             (void)hipEventRecord(e1, stream);
         if (S.n_prims)
             WF_LAUNCH(wf_extend_prims, dim3(shade_blocks), block, 0, stream, S, L);
+        if (b == 0 && acc && feat) // a feature accumulator's pass: the primary rays' first hits are final here
+            WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *feat);
         // ENV: the scene has an environment map (DevScene::bg_tex): the miss branch looks it up (scene.h:83-89); those instantiations read the
         // light tables from global memory (LIGHTS_LDS only saves latency), so a scene without one never pays for the lookup's registers
         const bool env = S.bg_tex >= 0;
@@ -810,6 +864,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
     }
     if (acc) { // ... and so does the last
         const int res_blocks = (int)((acc->n_entries + 255u) / 256u);
+        if (feat)
+            WF_LAUNCH(wf_resolve_features, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, *acc, *feat);
         WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, *acc);
         return hipSuccess;
     }
