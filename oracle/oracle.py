@@ -37,6 +37,7 @@ _PROTOS = {
     "rto_trace_pixel": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), C.c_uint32, C.c_uint32, _abi.c_float_p, _abi.c_u32_p, _abi.c_u32_p]),
     "rto_pixel_samples": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), _abi.c_u32_p, C.c_uint32, _abi.c_float_p, C.c_int]),
     "rto_light_pdf": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
+    "rto_walk_census": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_u32_p]),
     "rto_bg_at": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_bg_uv": (None, [_abi.c_float_p, C.c_uint32, C.c_int, _abi.c_float_p]),
     "rto_bvh_info": (C.c_int, [C.c_void_p, C.c_int, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p]),
@@ -167,6 +168,17 @@ class OracleScene:
         out = np.zeros(rays.shape[0], dtype=np.float32)
         _check(lib().rto_light_pdf(self._h, _abi.fptr(rays), rays.shape[0], _abi.fptr(out)))
         return out
+
+    def walk_census(self, rays):
+        """Per ray, the largest number of deferred far siblings pending at once: (closest (n,) uint32 for intersect_ray on the scene tree,
+        light (n,) uint32 for foreach_intersection on the light tree with the ray as (x, d) of light_pdf). A traversal stack holds exactly
+        these, so the counts say which tier of a two-tier stack a ray reaches."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        closest = np.zeros(n, dtype=np.uint32)
+        light = np.zeros(n, dtype=np.uint32)
+        _check(lib().rto_walk_census(self._h, _abi.fptr(rays), n, _abi.u32ptr(closest), _abi.u32ptr(light)))
+        return closest, light
 
     def bg_at(self, dirs):
         """Scene::bg_at (scene.h:83-89) for explicit directions -> (n, 3) rgb."""

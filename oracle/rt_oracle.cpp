@@ -187,6 +187,12 @@ struct BVHNode {
 struct Counters {
     uint64_t casts = 0, nodes = 0, box_tests = 0, tri_tests = 0, shaded = 0;
     uint64_t lq = 0, lnodes = 0, lbox = 0, ltri = 0, lhits = 0, texels = 0, samples = 0;
+    // rto_walk_census only (never summed by add): with `census` set the two recursions below keep the number of deferred far siblings
+    // pending right now and its maximum. A sibling is pending from the moment both children of its parent were hit until the walk
+    // enters it or prunes it: what a traversal without recursion has to hold on a stack.
+    bool census = false;
+    uint32_t pending = 0, max_pending = 0;
+    void defer() { max_pending = std::max(max_pending, ++pending); }
     void add(const Counters &o) {
         casts += o.casts;
         nodes += o.nodes;
@@ -282,7 +288,11 @@ struct BVH {
                 std::swap(id1, id2);
                 std::swap(d_left, d_right);
             }
+            if (c.census)
+                c.defer();
             update_intersection(intr, intersect_ray(ray, min_dst, id1, c));
+            if (c.census)
+                --c.pending; // id2 is entered or pruned now
             if (!intr.has || intr.xs.z > d_right)
                 update_intersection(intr, intersect_ray(ray, min_dst, id2, c));
         } else {
@@ -309,8 +319,17 @@ struct BVH {
         float d;
         if (node.left != NO_CHILD) {
             c.lbox++;
-            if (intersect_box(ray, nodes[node.left].box, min_dst, d))
+            if (intersect_box(ray, nodes[node.left].box, min_dst, d)) {
+                // census: the right child is deferred while the left subtree is walked iff its box is hit too (the same test as below,
+                // made early and not counted)
+                float dr;
+                const bool deferred = c.census && node.right != NO_CHILD && intersect_box(ray, nodes[node.right].box, min_dst, dr);
+                if (deferred)
+                    c.defer();
                 foreach_intersection(ray, min_dst, fn, node.left, c);
+                if (deferred)
+                    --c.pending;
+            }
         }
         if (node.right != NO_CHILD) {
             c.lbox++;
@@ -1172,6 +1191,39 @@ int rto_light_pdf(rto_scene *s, const float *rays, uint32_t n, float *pdf_out) {
         V3 x{rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]}, d{rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]};
         pdf_out[i] = it.has_lights() ? it.lights_pdf(x, d) : 0.0f;
     }
+    return RT_OK;
+}
+
+// Test aid: how much a traversal without recursion has to remember for each ray. closest_out[i]: the largest number of deferred far siblings
+// pending at once during intersect_ray on the scene tree (an ancestor counts when both its children were hit and its far side has not yet
+// been entered or pruned); light_out[i]: the same during foreach_intersection on the light tree with ray i as (x, d) of lights_pdf (an
+// ancestor counts while its left subtree is walked and its right box is hit). Counted by the recursions themselves (Counters::census).
+int rto_walk_census(rto_scene *s, const float *rays, uint32_t n, uint32_t *closest_out, uint32_t *light_out) {
+    if (!s || (n && (!rays || !closest_out || !light_out))) {
+        g_err = "rto_walk_census: bad arguments";
+        return RT_ERR_INVALID_ARG;
+    }
+    auto range = [&](uint32_t begin, uint32_t end) {
+        for (uint32_t i = begin; i < end; ++i) {
+            Ray r{{rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]}, {rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]}};
+            Counters c;
+            c.census = true;
+            if (s->scene_bvh.root != NO_CHILD)
+                (void)s->scene_bvh.intersect_ray(r, EPS, s->scene_bvh.root, c);
+            closest_out[i] = c.max_pending;
+            c.pending = c.max_pending = 0;
+            if (s->light_bvh.root != NO_CHILD && !s->light_bvh.objects.empty())
+                s->light_bvh.foreach_intersection(r, EPS, [](const Object &, float) {}, s->light_bvh.root, c);
+            light_out[i] = c.max_pending;
+        }
+    };
+    const uint32_t n_workers = std::max(1u, std::min({16u, std::thread::hardware_concurrency(), n / 256u})); // rays are independent
+    std::vector<std::thread> workers;
+    for (uint32_t w = 1; w < n_workers; ++w)
+        workers.emplace_back(range, (uint32_t)((uint64_t)n * w / n_workers), (uint32_t)((uint64_t)n * (w + 1) / n_workers));
+    range(0, (uint32_t)((uint64_t)n / n_workers));
+    for (auto &t : workers)
+        t.join();
     return RT_OK;
 }
 

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import deep_walks
 from conftest import golden_scene_specs, make_scene
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -229,3 +230,58 @@ def test_live_reference_binary_on_a_deep_tree_if_present(oracle, rt, sg, tmp_pat
     ls = rt.parse_gltf_scene(path, 96 / 64)
     fb, _ = oracle.OracleScene(ls).run_raytracer(96, 64, 2, rng_mode=rt.RT_RNG_REFERENCE)
     assert np.array_equal(oracle.tonemap(fb), ref)
+
+
+# Hop 1 of the parity chain on the trees of tests/test_gpu_deep_walks.py: everything above stops at 40 coplanar lights and at light queries
+# with 3 subtrees pending. The scenes are tests/deep_walks.py's; the reference's answers are stored by make_live_golden.py.
+def test_live_reference_binary_with_2000_volume_lights_if_present(oracle, rt, sg, tmp_path):
+    """2000 emissive triangles all through the room (a light tree of 2555 pieces; most light queries keep 5 to 11 subtrees pending): the
+    oracle's PPM is the reference binary's, byte for byte."""
+    sc = deep_walks.volume_lights_scene(sg, **deep_walks.BIG_LIGHTS)
+    path = sg.write_gltf(sc, str(tmp_path / "lights.gltf"))
+    ref = reference_ppm(oracle, path, 48, 40, 2, tmp_path, "lights2000_48x40x2.ppm")
+    orc = oracle.OracleScene(rt.parse_gltf_scene(path, 48 / 40))
+    fb, st = orc.run_raytracer(48, 40, 2, rng_mode=rt.RT_RNG_REFERENCE)
+    assert np.array_equal(oracle.tonemap(fb), ref), f"{int((oracle.tonemap(fb) != ref).any(axis=2).sum())} pixels differ"
+    assert deep_walks.inner_plus_lights(orc.bvh_info(1)) == 2555 and st["light_hits"] > 10 * st["light_queries"]  # dozens of terms per sum
+
+
+def test_live_reference_light_pdf_with_2000_volume_lights_if_present(oracle, rt, sg, tmp_path):
+    """bvh_mix_dist::pdf of the reference itself (ref_probe "lightpdf") on 2000 queries of that scene, half of them aimed at lights: the
+    oracle's sums of dozens of terms in the same DFS order, bit for bit. The census shows what these queries are."""
+    sc = deep_walks.volume_lights_scene(sg, **deep_walks.BIG_LIGHTS)
+    path = sg.write_gltf(sc, str(tmp_path / "lights.gltf"))
+    rays = deep_walks.light_query_rays(sc, 2000, 77)
+    stored = np.load(os.path.join(LIVE, "lights2000_lightpdf.npy"))
+    if oracle.have_reference_build():
+        rays.astype("<f4").tofile(str(tmp_path / "rays.bin"))
+        oracle.ref_probe("lightpdf", path, 48, 40, str(tmp_path / "rays.bin"), str(tmp_path / "lp.bin"))
+        assert np.array_equal(np.fromfile(str(tmp_path / "lp.bin"), dtype="<f4").view(np.uint32), stored.view(np.uint32))
+    orc = oracle.OracleScene(rt.parse_gltf_scene(path, 48 / 40))
+    got = orc.light_pdf(rays)
+    assert np.array_equal(got.view(np.uint32), stored.view(np.uint32)), int((got.view(np.uint32) != stored.view(np.uint32)).sum())
+    _, light = orc.walk_census(rays)
+    deep_walks.require_witnesses("2000 lights, stored light pdf", light, {deep_walks.LIGHT_SHADE_SCRATCH: 0.30})
+    assert (stored > 0).mean() > 0.9
+
+
+def test_live_reference_binary_on_emissive_needles_if_present(oracle, rt, sg, tmp_path):
+    """20 000 emissive needles: light queries with up to 14 subtrees pending and closest-hit walks with up to 20. The oracle's PPM is the
+    reference binary's."""
+    sc = deep_walks.needle_soup_scene(sg, emissive=True, **deep_walks.NEEDLES)
+    path = sg.write_gltf(sc, str(tmp_path / "needles.gltf"))
+    ref = reference_ppm(oracle, path, 48, 40, 2, tmp_path, "needles20000_48x40x2.ppm")
+    orc = oracle.OracleScene(rt.parse_gltf_scene(path, 48 / 40))
+    fb, _ = orc.run_raytracer(48, 40, 2, rng_mode=rt.RT_RNG_REFERENCE)
+    assert np.array_equal(oracle.tonemap(fb), ref), f"{int((oracle.tonemap(fb) != ref).any(axis=2).sum())} pixels differ"
+    closest, light = orc.walk_census(deep_walks.light_query_rays(sc, 2000, 78))
+    deep_walks.require_witnesses("emissive needles, light walk", light, {deep_walks.LIGHT_PROBE_SCRATCH: 0.01})
+    deep_walks.require_witnesses("emissive needles, closest hit", closest, {deep_walks.CLOSEST_PROBE_SCRATCH: 0.01})
+
+
+@pytest.mark.parametrize("total", [96, 97])
+def test_staging_edge_scenes_have_the_sums_their_names_say(oracle, sg, total):
+    """The two light counts tests/test_gpu_deep_walks.py puts on either side of wf_shade's staging rule (inner + lights <= 96), counted on the
+    oracle's tree without a GPU."""
+    orc = oracle.OracleScene(deep_walks.volume_lights_scene(sg, **deep_walks.STAGING_EDGE[total]))
+    assert deep_walks.inner_plus_lights(orc.bvh_info(1)) == total
