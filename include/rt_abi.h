@@ -514,6 +514,43 @@ typedef struct rt_denoise {
 int rt_accum_denoise(rt_accum *acc, const rt_denoise *opt, uint32_t flags, float *fb_rgb);
 int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint32_t flags, uint8_t *rgb8);
 
+/* New per-triangle arrays for a built scene (animation frames, deforming meshes, simulation steps) without rt_destroy + rt_create
+ * (additive; RT_ABI_VERSION stays 4). Blocking; runs on the scene's own stream. The call replaces the five per-triangle arrays of the
+ * creation descriptor; all five must be non-NULL when n_triangles > 0, and the caller keeps ownership of them. Everything else is the
+ * scene's as created and is neither read again nor uploaded again: materials, textures, the texel pool and the tables; the analytic
+ * primitives; the camera; bg_color, bg_texture, ray_depth, build_flags and build.
+ *   RT_UPDATE_REBUILD (every single-GPU build kind): afterwards the scene is, for every entry point, the scene rt_create would build from
+ *     the creation descriptor with those five arrays swapped in: both BVHs, the triangle, shading and light records, the ray-ordering
+ *     bounds and rt_build_times* are those of that fresh scene. A parity scene stays a parity scene (the reference's topology of the new
+ *     geometry, its image and its counters). The new buffers are built beside the live ones, then swapped in and the old ones freed.
+ *   RT_UPDATE_REFIT (scenes built with RT_BUILD_WIDE, collapsed on the host or on the device): the 8-wide tree keeps its topology: slot
+ *     states, group bases and the order of the triangle records (DevTri::prim per record) stay. Every triangle record, shading record, node
+ *     origin, cell exponent and quantised plane is recomputed for the new arrays, each by the rule the builders use for a node with those
+ *     contents (the scene grids of the new bounds, the origin snap, the cell exponent, floor / ceil planes): a pure function of the topology
+ *     and the arrays, whichever lane computes it. The light BVH and the light records are rebuilt as in REBUILD, so the set of lights
+ *     follows the new material_ids. The hit contract is the wide tree's (the closest hit over all triangles, another index only on exact
+ *     ties): a topology chosen for other positions can cost node visits, never a hit. Rebuild when the visits grow. After a
+ *     REFIT rt_bvh_info(0) returns RT_ERR_UNSUPPORTED: the binary tree the wide one was collapsed from no longer describes the scene.
+ *   Either mode resets the packet policy of rt_render* (it was measured on the old tree).
+ * RT_ERR_INVALID_ARG (checked before any device work): a NULL scene, struct or array; n_triangles other than the scene's; an unknown mode;
+ *   a non-zero reserved word; a material id >= the scene's material count; a non-finite position; a scene with a live accumulator
+ *   (rt_accum_create* without its rt_accum_destroy): its sums are of the old geometry.
+ * RT_ERR_UNSUPPORTED: a multi-GPU scene; RT_UPDATE_REFIT on a scene built without RT_BUILD_WIDE (a refitted binary tree would not be the
+ *   reference's topology); either mode on a RT_BUILD_WIDE scene whose new extent leaves the wide tree's exponent range (rt_create's test).
+ * After RT_ERR_INVALID_ARG, RT_ERR_UNSUPPORTED or RT_ERR_OOM the scene is unchanged, bit for bit. */
+enum { RT_UPDATE_REBUILD = 0, RT_UPDATE_REFIT = 1 };
+typedef struct rt_geometry_update {
+    uint32_t n_triangles;         /* must equal the scene's */
+    uint32_t mode;                /* RT_UPDATE_* */
+    const float *positions;       /* 9*n, as rt_scene_desc */
+    const float *normals;         /* 9*n */
+    const float *texcoords;       /* 6*n */
+    const float *tangents;        /* 9*n */
+    const uint32_t *material_ids; /* n */
+    uint32_t reserved[4];         /* 0 */
+} rt_geometry_update;             /* 64 bytes */
+int rt_update_geometry(rt_scene *scene, const rt_geometry_update *upd);
+
 int rt_film_rgb8(rt_scene *scene, const float *rgb, size_t n_pixels, uint8_t *out_rgb8);
 
 const char *rt_last_error(void);

@@ -68,6 +68,11 @@ int rt_bvh_build_host(const float *positions, uint32_t n_triangles, const uint32
  * triangle index of triangle record k. Pass nodes80 = NULL to query n_nodes. */
 int rt_bvh_wide_build_host(const float *positions, uint32_t n_triangles, float cost_node, float cost_tri, uint32_t *n_nodes, uint32_t *depth,
                            double *sah_cost, uint32_t *nodes80, uint32_t nodes_capacity, uint32_t *order_out);
+/* ... and its refit to new positions, in place, no GPU: the CPU model of rt_update_geometry's RT_UPDATE_REFIT (include/rt_abi.h). nodes80:
+ * n_nodes WideNode records forming a tree from node 0 (as rt_bvh_wide_build_host or rt_bvh_wide_dump give them); order[k]: original triangle
+ * of triangle record k. The topology words (inner mask, child_base, tri_base, tri_mask) stay; origins, exponents and planes are recomputed by
+ * the builder's rule for the new positions. Returns 1 (RT_ERR_INVALID_ARG) for NULL arrays or records that do not form a tree over `order`. */
+int rt_bvh_wide_refit_host(const float *positions, uint32_t n_triangles, const uint32_t *order, uint32_t n_order, uint32_t *nodes80, uint32_t n_nodes);
 
 /* Texture::load_img (geometry.h:584-598: stbi_load with 4 channels forced) for the formats this loader reads, told apart by
  * their signatures: PNG (every colour type / bit depth / Adam7 / tRNS) and JPEG (baseline, extended-sequential and progressive

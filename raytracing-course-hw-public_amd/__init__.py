@@ -47,12 +47,15 @@ from ._ctypes_abi import (
     RT_CAST_PACKET,
     RT_CAST_PACKET_GLOBAL,
     RT_OK,
+    RT_UPDATE_REBUILD,
+    RT_UPDATE_REFIT,
     RT_RNG_DEVICE,
     RT_RNG_REFERENCE,
     DescHolder,
     RtAdaptive,
     RtCamera,
     RtDenoise,
+    RtGeometryUpdate,
     RtParams,
     RtSceneDesc,
     RtView,
@@ -205,6 +208,16 @@ def _as_desc(scene) -> Tuple[RtSceneDesc, object]:
         return scene.desc, scene
     if isinstance(scene, RtSceneDesc):
         return scene, None
+    if isinstance(scene, dict):  # an arrays dict (LoadedScene.arrays(), or just the five per-triangle arrays for update_geometry)
+        if "camera" in scene:
+            scene = scenegen.scene_from_arrays(scene)
+        else:
+            zero = np.zeros(3, dtype=np.float32)
+            n = np.asarray(scene["positions"]).size // 9
+            nrm = scene.get("normals")
+            scene = scenegen.Scene(positions=np.asarray(scene["positions"], dtype=np.float32).reshape(n, 3, 3), normals=None if nrm is None else np.asarray(nrm),
+                                   texcoords=scene["texcoords"], tangents=scene["tangents"], material_ids=scene["material_ids"], materials=[],
+                                   camera=scenegen.Camera(zero, zero, zero, zero, 1.0))
     holder = DescHolder(scene)
     return holder.desc, holder
 
@@ -271,6 +284,18 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+    def update_geometry(self, scene, refit: bool = False) -> None:
+        """rt_update_geometry: new positions, normals, texcoords, tangents and material ids for this scene (same triangle count), from a
+        scenegen.Scene, a LoadedScene or an arrays dict, through the path the constructor takes (normals=None: geometric normals).
+        Materials, textures, camera and build options stay the scene's. `refit` (RT_BUILD_WIDE scenes): keep the tree's topology and refit
+        it on the device (RT_UPDATE_REFIT) instead of rebuilding it."""
+        desc, keep = _as_desc(scene)  # noqa: F841 (keeps the arrays alive for the call)
+        u = RtGeometryUpdate()
+        u.n_triangles = desc.n_triangles
+        u.mode = RT_UPDATE_REFIT if refit else RT_UPDATE_REBUILD
+        u.positions, u.normals, u.texcoords, u.tangents, u.material_ids = desc.positions, desc.normals, desc.texcoords, desc.tangents, desc.material_ids
+        _check(lib().rt_update_geometry(self._h, C.byref(u)))
 
     def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
@@ -621,6 +646,18 @@ def bvh_wide_build_host(positions: np.ndarray, cost_node: float = 1.0, cost_tri:
     if rc != RT_OK:
         raise RtError(rc, "rt_bvh_wide_build_host")
     return {"nodes": nodes, "order": order, "depth": depth.value, "sah_cost": cost.value}
+
+
+def bvh_wide_refit_host(nodes: np.ndarray, order: np.ndarray, positions: np.ndarray) -> np.ndarray:
+    """rt_bvh_wide_refit_host: (n, 20) u32 WideNode records (of bvh_wide_build_host or DeviceScene.bvh_wide_dump) refitted to new
+    positions, no GPU needed: the CPU model of update_geometry(refit=True). order[k]: original triangle of triangle record k. Returns a copy."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 9)
+    out = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 20).copy()
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    rc = lib().rt_bvh_wide_refit_host(fptr(pos), pos.shape[0], u32ptr(order), len(order), u32ptr(out), out.shape[0])
+    if rc != RT_OK:
+        raise RtError(rc, "rt_bvh_wide_refit_host")
+    return out
 
 
 def tonemap(fb: np.ndarray) -> np.ndarray:

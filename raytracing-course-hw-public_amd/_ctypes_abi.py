@@ -30,6 +30,7 @@ RT_FLAG_MEGAKERNEL = 4
 RT_FLAG_GLOBAL_BEST = 8
 RT_ACCUM_FEATURES = 1
 RT_DENOISE_NO_DEMODULATE = 1
+RT_UPDATE_REBUILD, RT_UPDATE_REFIT = 0, 1
 RT_CAST_PROBE, RT_CAST_EXTEND, RT_CAST_EXTEND_GLOBAL, RT_CAST_PACKET, RT_CAST_PACKET_GLOBAL = range(5)
 
 RT_OK = 0
@@ -150,6 +151,19 @@ class RtSceneDesc(C.Structure):
     ]
 
 
+class RtGeometryUpdate(C.Structure):  # rt_update_geometry: the five per-triangle arrays of rt_scene_desc again (64 bytes)
+    _fields_ = [
+        ("n_triangles", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("positions", c_float_p),
+        ("normals", c_float_p),
+        ("texcoords", c_float_p),
+        ("tangents", c_float_p),
+        ("material_ids", c_u32_p),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 RT_PROGRESS_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_uint32, C.c_void_p)
 
 
@@ -230,6 +244,7 @@ ABI_PROTOTYPES = {
     "rt_accum_resolve_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_accum_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
     "rt_accum_denoise_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
+    "rt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),
     "rt_last_error": (C.c_char_p, []),
     "rt_source_stamp": (C.c_char_p, []),
     "rt_abi_version": (C.c_uint32, []),
@@ -260,6 +275,7 @@ HOST_PROTOTYPES = {
     "rt_film_table": (C.c_int, [c_float_p, c_u32_p]),
     "rt_bvh_build_host": (C.c_int, [c_float_p, C.c_uint32, c_u32_p, C.c_uint32, c_u32_p, c_u32_p, c_u32_p, c_u32_p]),
     "rt_bvh_wide_build_host": (C.c_int, [c_float_p, C.c_uint32, C.c_float, C.c_float, c_u32_p, c_u32_p, C.POINTER(C.c_double), c_u32_p, C.c_uint32, c_u32_p]),
+    "rt_bvh_wide_refit_host": (C.c_int, [c_float_p, C.c_uint32, c_u32_p, C.c_uint32, c_u32_p, C.c_uint32]),
 }
 
 

@@ -25,7 +25,10 @@ struct rt_accum {
         (void)hipStreamSynchronize(scene->stream);
         for (void *p : owned)
             (void)hipFree(p);
+        if (counted)
+            --scene->live_accums;
     }
+    bool counted = false; // it is one of scene->live_accums
 };
 
 template <class T> static int accum_alloc(rt_accum *a, size_t bytes, T **ptr, const char *fn) {
@@ -88,6 +91,8 @@ extern "C" int rt_accum_create_ex(rt_scene *s, uint32_t width, uint32_t height, 
     HIP_TRY(hipMemsetD32Async(R.err, 0x7F800000 /* +inf: n_p < 2 */, n, s->stream));
     HIP_TRY(hipMemcpyAsync(a->d_view, &a->view, sizeof(WfView), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    a->counted = true;
+    ++s->live_accums; // rt_update_geometry refuses the scene while this one lives
     *out = a.release();
     return RT_OK;
 }

@@ -33,6 +33,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rt_bvh_device.h"
+#include "rt_build_dev.h"
 #include "wide_grid.h"
 #include "rt_kernels.h"
 
@@ -42,50 +43,6 @@ namespace {
 // (262 k triangles: 83 ms against 107 ms on the reference's tree; 10^7: 166 against 141 ms), 2 and 4 are slower (loose leaf
 // boxes along the Morton curve), so the default is one triangle per leaf; rt_build_options.lbvh_leaf_tris (1..8) overrides it for experiments.
 constexpr uint32_t LEAF_TRIS_DEFAULT = 1;
-
-__device__ __forceinline__ uint32_t enc_f(float f) { // order-preserving float -> uint
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__host__ __device__ __forceinline__ float dec_f(uint32_t e) {
-    const uint32_t b = (e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e;
-    float f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    f = __uint_as_float(b);
-#else
-    std::memcpy(&f, &b, 4);
-#endif
-    return f;
-}
-
-// ---- 1. bounds of all vertices: bounds[0..2] = min (encoded), bounds[3..5] = max
-__global__ __launch_bounds__(256) void k_bounds(const float *__restrict__ pos, uint32_t n, uint32_t *bounds) {
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float *p = pos + 9ull * i;
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                lo[c] = fminf(lo[c], p[3 * v + c]);
-                hi[c] = fmaxf(hi[c], p[3 * v + c]);
-            }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[c] = fminf(lo[c], __shfl_down(lo[c], off));
-            hi[c] = fmaxf(hi[c], __shfl_down(hi[c], off));
-        }
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            atomicMin(bounds + c, enc_f(lo[c]));
-            atomicMax(bounds + 3 + c, enc_f(hi[c]));
-        }
-    }
-}
 
 __device__ __forceinline__ uint32_t spread10(uint32_t v) { // 10 bits -> every third bit
     v &= 1023u;
@@ -139,11 +96,6 @@ struct BuildArrays {
     float cost_node, cost_tri;
 };
 
-__device__ __forceinline__ bool coord_fast_ok(float c) {
-    const float m = __builtin_fabsf(c);
-    return (c == 0.0f) | ((m >= 7.275957614183426e-12f) & (m <= 1099511627776.0f));
-}
-
 // ---- 3. leaves: records in sorted order, exact boxes, keys
 __global__ __launch_bounds__(256) void k_leaves(const BuildArrays A) {
     for (uint32_t leaf = blockIdx.x * blockDim.x + threadIdx.x; leaf < A.n_leaves; leaf += gridDim.x * blockDim.x) {
@@ -151,42 +103,11 @@ __global__ __launch_bounds__(256) void k_leaves(const BuildArrays A) {
         float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
         bool ok = true;
         for (uint32_t k = k0; k < k1; ++k) {
-            const uint32_t prim = A.prims_sorted[k];
-            const float *p = A.pos + 9ull * prim;
             DevTri t;
             DevAttr at;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                t.a[c] = p[c];
-                t.v[c] = p[3 + c] - p[c]; // triangle::v geometry.h:473
-                t.u[c] = p[6 + c] - p[c]; // triangle::u geometry.h:475
-#pragma unroll
-                for (int v = 0; v < 3; ++v) {
-                    lo[c] = fminf(lo[c], p[3 * v + c]);
-                    hi[c] = fmaxf(hi[c], p[3 * v + c]);
-                    ok &= coord_fast_ok(p[3 * v + c]);
-                }
-            }
-            t.prim = prim;
+            tri_records(A.pos, A.nrm, A.tan, A.uv, A.mat, A.prims_sorted[k], t, at, lo, hi, ok);
             t.flags = (k == k1 - 1 ? 1u : 0u) | (k == k0 ? 2u : 0u);
-            t.pad = 0;
             A.tris[k] = t;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                at.n[j] = A.nrm[9ull * prim + j];
-                at.tg[j] = A.tan[9ull * prim + j];
-            }
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-                at.uv[j] = A.uv[6ull * prim + j];
-            // base_normal() = norm(crs(v, u)) (geometry.h:477-479, 648-650), same float operations as the host path
-            const float cx = t.v[1] * t.u[2] - t.v[2] * t.u[1], cy = t.v[2] * t.u[0] - t.v[0] * t.u[2], cz = t.v[0] * t.u[1] - t.v[1] * t.u[0];
-            const float l = __builtin_sqrtf(cx * cx + cy * cy + cz * cz);
-            at.gn[0] = cx / l;
-            at.gn[1] = cy / l;
-            at.gn[2] = cz / l;
-            at.material = A.mat[prim];
-            at.pad[0] = at.pad[1] = at.pad[2] = at.pad[3] = 0;
             A.attrs[k] = at;
         }
 #pragma unroll
@@ -621,13 +542,13 @@ __global__ __launch_bounds__(64) void k_wide_emit(const WideEmit E) {
             hi[c] = fmaxf(hi[c], kbox[i][3 + c]);
         }
     WideNode rec;
-    int ebias[3];
+    int ecell[3];
     float org[3]; // the node's origin: its lower corner snapped down to the scene's origin grid (what the quantised planes are measured from)
+    wide_node_frame(E.grid, lo, hi, org, ecell);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        rec.p[c] = org[c] = wide_snap_origin(E.grid, c, lo[c], nullptr);
-        ebias[c] = wide_cell_exponent(E.grid, (double)hi[c] - (double)org[c]) + 127;
-        rec.e[c] = (uint8_t)ebias[c];
+        rec.p[c] = org[c];
+        rec.e[c] = (uint8_t)(ecell[c] + 127);
     }
     // ---- slots: greedy on dot(child centre - node centre, corner direction of the slot)
     int child_in[8];
@@ -715,18 +636,8 @@ __global__ __launch_bounds__(64) void k_wide_emit(const WideEmit E) {
             continue;
         }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double cell = ldexp(1.0, ebias[c] - 127);
-            double ql = floor(((double)kbox[i][c] - (double)org[c]) / cell), qh = ceil(((double)kbox[i][3 + c] - (double)org[c]) / cell);
-            ql = fmin(fmax(ql, 0.0), 255.0);
-            qh = fmin(fmax(qh, 0.0), 255.0);
-            while (ql > 0.0 && (double)org[c] + ql * cell > (double)kbox[i][c])
-                ql -= 1.0;
-            while (qh < 255.0 && (double)org[c] + qh * cell < (double)kbox[i][3 + c])
-                qh += 1.0;
-            rec.qlo[c][s] = (uint8_t)ql;
-            rec.qhi[c][s] = (uint8_t)qh;
-        }
+        for (int c = 0; c < 3; ++c)
+            wide_quantise_axis(org[c], ecell[c], kbox[i][c], kbox[i][3 + c], &rec.qlo[c][s], &rec.qhi[c][s]);
         if (!kid_leaf[i]) {
             rec.imask |= (uint8_t)(1u << s);
             E.queue_out[qbase + r_inner] = make_uint2(kid[i], first_child + r_inner);

@@ -349,6 +349,8 @@ extern "C" int rt_bvh_info(rt_scene *s, int which, uint32_t *n_nodes, uint32_t *
         return rt_bvh_info(rt::group_primary(s->group), which, n_nodes, n_objects, root, nodes_out, order_out);
     if (which == 0 && s->device_built && s->wide_built)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_bvh_info: the binary tree of a device-built wide scene is not kept");
+    if (which == 0 && s->wide_built && s->refitted)
+        return rt::fail(RT_ERR_UNSUPPORTED, "rt_bvh_info: the wide tree was refitted (RT_UPDATE_REFIT): the binary tree it was collapsed from is not kept");
     if (which == 0 && s->device_built && s->rebuilt_bvh.nodes.empty() && s->dev.scene.n_tris)
         if (int rc = reconstruct_host_bvh(s); rc != RT_OK)
             return rc;

@@ -16,6 +16,7 @@
 #include "rt_film.h"
 #include "rt_group.h"
 #include "rt_kernels.h"
+#include "wide_build.h"
 
 #define HIP_TRY(expr)                                                                                     \
     do {                                                                                                  \
@@ -34,6 +35,65 @@ struct PacketPolicy {
     bool off = false;
     uint32_t lanes_x100 = 0; // last packet census: lanes served per trip x 100 (rt_stats.packet_lanes_x100)
 };
+
+// The host half of rt_create comes in two halves. The GEOMETRY half is everything that follows from the five per-triangle arrays: both
+// trees, the triangle, shading and light records. rt_update_geometry makes a new one; the other half (below) is never copied for that.
+struct PreparedGeometry {
+    bool dev_build = false, wide_build = false;
+    HostBvh host_bvh[2];
+    FlatBvh flat[2];            // [0] empty when the scene BVH is built on the device or is wide
+    WideBvh wide;               // wide_build && !dev_build
+    std::vector<DevTri> wide_tris;
+    std::vector<DevAttr> attrs; // scene-BVH order (empty when built on the device)
+    std::vector<DevLightAux> laux;
+    double build_ms = 0, wide_ms = 0;
+};
+// ... and the rest: materials, texture views, the texel pool, tables, and how the scene asked to be built. Shared by the replicas of a
+// multi-GPU scene; a scene keeps it for life.
+struct PreparedScene {
+    std::shared_ptr<const PreparedGeometry> geo; // of the creation arrays
+    std::vector<DevMaterial> mats;
+    std::vector<DevTexture> texs;
+    std::vector<uint32_t> pool;
+    std::vector<rt_primitive_desc> prims;
+    std::vector<float> lut_lin, lut_gam;
+    int32_t bg_view = -1;       // view of rt_scene_desc.bg_texture in texs (stand-alone), -1 = the white default
+    float wide_cost_node = 1.0f, wide_cost_tri = 0.3f;
+    uint32_t build_flags = 0;   // rt_scene_desc.build_flags / .build as created: what rt_update_geometry rebuilds with
+    rt_build_options build{};
+};
+
+// What the geometry half leaves on one device (rt_scene.cpp upload_geometry): the buffers it allocated, the two trees as the kernels
+// address them, and the build facts the queries report. `owned` / `light_owned` are freed by whoever holds the struct.
+struct GeometryOnDevice {
+    std::vector<void *> owned;       // scene tree, triangle records, shading records
+    std::vector<void *> light_owned; // light tree, its triangle records, DevLightAux
+    DevBvh scene{}, lights{};
+    const DevAttr *attrs = nullptr;
+    const DevLightAux *light_aux = nullptr;
+    float bounds_lo[3] = {0, 0, 0}, bounds_inv[3] = {0, 0, 0};
+    bool device_built = false, wide_built = false;
+    uint32_t wide_depth = 0;
+    double wide_ms = 0, wide_cost = 0, build_ms = 0, build_upload_ms = 0;
+    uint32_t dev_n_inner[2] = {0, 0};
+    void free_all() {
+        for (void *p : owned)
+            (void)hipFree(p);
+        for (void *p : light_owned)
+            (void)hipFree(p);
+        owned.clear();
+        light_owned.clear();
+    }
+};
+
+// The wide kernels' exponent arithmetic stays among normal floats while the scene's largest cell exponent (e_base + 15) lies in [-60, 44]
+// (rt_scene.cpp upload_geometry states why): the one test rt_create and rt_update_geometry make on a grid.
+inline bool wide_grid_in_range(const WideGrid &grid) { return !(grid.e_base + 15 < -60 || grid.e_base + 15 > 44); }
+// one axis of the ray-ordering key's scene box: lower bound and 1 / extent (0 for a flat axis)
+inline void sort_bounds_axis(float lo, float hi, float &bounds_lo, float &bounds_inv) {
+    bounds_lo = lo;
+    bounds_inv = (hi > lo) ? 1.0f / (hi - lo) : 0.0f;
+}
 } // namespace rt
 
 struct rt_scene {
@@ -44,8 +104,13 @@ struct rt_scene {
     rt::EventPool ext_events; // (start, stop) per wf_extend launch of the current render; reused by every render
     DevScene dev{};
     rt_camera cam{};
-    std::vector<void *> owned;
+    std::vector<void *> owned;       // what lives as long as the scene: materials, textures, texels, tables, counters
+    std::vector<void *> geo_owned;   // the scene tree and its records ...
+    std::vector<void *> light_owned; // ... and the light tree's: freed when rt_update_geometry swaps new ones in
     std::shared_ptr<const rt::PreparedScene> prep; // the host half of rt_create, shared by the replicas of a multi-GPU scene
+    std::shared_ptr<const rt::PreparedGeometry> geo; // its geometry half: prep->geo until rt_update_geometry replaces it
+    uint32_t live_accums = 0;  // accumulators of this scene (rt_accum_create* / rt_accum_destroy): their sums pin the geometry
+    bool refitted = false;     // the wide tree was refitted: the binary tree it was collapsed from no longer describes the scene
     rt::HostBvh rebuilt_bvh;   // device-built scene BVH: the reference-style node list, reconstructed from HBM on demand
     bool device_built = false; // scene BVH built by rt_bvh_device.hip
     bool wide_built = false;   // RT_BUILD_WIDE: the scene BVH in HBM is the 8-wide quantised tree (wide_build.cpp); host_bvh[0] is the
@@ -234,6 +299,10 @@ struct rt_scene {
             (void)hipFree(p);
         for (void *p : owned)
             (void)hipFree(p);
+        for (void *p : geo_owned)
+            (void)hipFree(p);
+        for (void *p : light_owned)
+            (void)hipFree(p);
         if (wf_feat)
             (void)hipFree(wf_feat);
         if (d_fb)
@@ -256,7 +325,13 @@ struct rt_scene {
 
 namespace rt {
 // rt_scene.cpp
-const HostBvh &prepared_host_bvh(const rt_scene *s, int which); // the host-built trees kept by the scene's PreparedScene
+const HostBvh &prepared_host_bvh(const rt_scene *s, int which); // the host-built trees kept by the scene's PreparedGeometry
+// the two halves of the geometry build, host and device, that rt_create and rt_update_geometry (rt_update.cpp) both run
+void prepare_geometry(const rt_scene_desc *d, const std::vector<uint8_t> &emissive, float wide_cost_node, float wide_cost_tri, PreparedGeometry &P,
+                      bool lights_only = false);
+int upload_geometry(rt_scene *s, const rt_scene_desc *d, const PreparedScene &PS, const PreparedGeometry &P, GeometryOnDevice &out);
+void install_geometry(rt_scene *s, GeometryOnDevice &g);
+uint32_t light_lds_inner(const FlatBvh &f); // DevBvh::lds_inner of a light tree
 // rt_render.cpp: views, the check of the pass options, the wavefront pass policy and the statistics of a finished call
 WfView make_view(const rt_camera &cam, uint32_t width, uint32_t height, uint64_t seed);
 void set_camera(DevScene &D, const float *pos, const float *right, const float *up, const float *fwd);

@@ -380,15 +380,11 @@ WideBvh build_wide(const BinBvh &bin, const float *positions, float cost_node, f
         WideNode rec;
         std::memset(&rec, 0, sizeof(rec));
         float org[3];
-        for (int c = 0; c < 3; ++c)
-            rec.p[c] = org[c] = wide_snap_origin(out.grid, c, nb.lo[c], nullptr);
-        int ebias[3];
-        double cell[3];
+        int ecell[3];
+        wide_node_frame(out.grid, nb.lo, nb.hi, org, ecell);
         for (int c = 0; c < 3; ++c) {
-            const int e = wide_cell_exponent(out.grid, (double)nb.hi[c] - (double)org[c]);
-            ebias[c] = e + 127;
-            cell[c] = std::ldexp(1.0, e);
-            rec.e[c] = (uint8_t)ebias[c];
+            rec.p[c] = org[c];
+            rec.e[c] = (uint8_t)(ecell[c] + 127);
         }
         for (int s = 0; s < 8; ++s)
             for (int c = 0; c < 3; ++c) {
@@ -403,19 +399,8 @@ WideBvh build_wide(const BinBvh &bin, const float *positions, float cost_node, f
             if (i < 0)
                 continue;
             const Box3 &cb = N[kids[i].node].box;
-            for (int c = 0; c < 3; ++c) {
-                double ql = std::floor(((double)cb.lo[c] - (double)org[c]) / cell[c]);
-                double qh = std::ceil(((double)cb.hi[c] - (double)org[c]) / cell[c]);
-                ql = std::min(std::max(ql, 0.0), 255.0);
-                qh = std::min(std::max(qh, 0.0), 255.0);
-                // containment in exact arithmetic (doubles hold these sums exactly enough; nudge if a rounding went the wrong way)
-                while (ql > 0 && (double)org[c] + ql * cell[c] > (double)cb.lo[c])
-                    ql -= 1;
-                while (qh < 255 && (double)org[c] + qh * cell[c] < (double)cb.hi[c])
-                    qh += 1;
-                rec.qlo[c][s] = (uint8_t)ql;
-                rec.qhi[c][s] = (uint8_t)qh;
-            }
+            for (int c = 0; c < 3; ++c)
+                wide_quantise_axis(org[c], ecell[c], cb.lo[c], cb.hi[c], &rec.qlo[c][s], &rec.qhi[c][s]);
             if (kids[i].leaf) {
                 tmp.clear();
                 leaf_tris(leaf_tris, kids[i].node, tmp);
@@ -444,6 +429,85 @@ WideBvh build_wide(const BinBvh &bin, const float *positions, float cost_node, f
     return out;
 }
 
+// Refit: the same topology over new positions. Every node's box becomes the exact box of what is below it now (min / max only), and its
+// origin, exponents and planes follow from that box by the builders' rule (wide_grid.h); imask, child_base, tri_base, tri_mask stay.
+bool refit_wide(std::vector<WideNode> &nodes, const uint32_t *order, size_t n_order, const float *positions, size_t n_triangles, WideGrid *grid_out) {
+    WideGrid G{};
+    if (grid_out)
+        *grid_out = G;
+    if (nodes.empty())
+        return n_order == 0;
+    Box3 scene;
+    box_reset(scene);
+    std::vector<Box3> tb(n_order);
+    for (size_t k = 0; k < n_order; ++k) {
+        if (order[k] >= n_triangles)
+            return false;
+        tb[k] = tri_box(positions + 9 * (size_t)order[k]);
+        box_grow(scene, tb[k]);
+    }
+    G = make_wide_grid(scene.lo, scene.hi);
+    // children follow their parents in neither builder's array for certain (the device collapse numbers them by atomics): walk from the root,
+    // parents first, and fold the list backwards. Every node is reached once in a well-formed tree; anything else is refused.
+    std::vector<uint32_t> walk{0u};
+    std::vector<uint8_t> seen(nodes.size(), 0);
+    seen[0] = 1;
+    walk.reserve(nodes.size());
+    for (size_t qi = 0; qi < walk.size(); ++qi) {
+        const WideNode &nd = nodes[walk[qi]];
+        const uint32_t n_inner = (uint32_t)__builtin_popcount(nd.imask);
+        for (uint32_t r = 0; r < n_inner; ++r) {
+            const uint64_t c = (uint64_t)nd.child_base + r;
+            if (c >= nodes.size() || seen[c])
+                return false;
+            seen[c] = 1;
+            walk.push_back((uint32_t)c);
+        }
+    }
+    std::vector<Box3> nbox(nodes.size());
+    for (size_t qi = walk.size(); qi-- > 0;) {
+        WideNode &nd = nodes[walk[qi]];
+        Box3 slot[8], nb;
+        box_reset(nb);
+        uint32_t r_inner = 0, r_tri = 0, used = 0;
+        for (int s = 0; s < 8; ++s) {
+            const uint32_t tbits = (nd.tri_mask >> (3 * s)) & 7u;
+            box_reset(slot[s]);
+            if (nd.imask & (1u << s)) {
+                slot[s] = nbox[nd.child_base + r_inner++];
+            } else if (tbits) {
+                for (uint32_t j = 0; j < (uint32_t)__builtin_popcount(tbits); ++j) {
+                    const uint64_t k = (uint64_t)nd.tri_base + r_tri++;
+                    if (k >= n_order)
+                        return false;
+                    box_grow(slot[s], tb[k]);
+                }
+            } else
+                continue;
+            used |= 1u << s;
+            box_grow(nb, slot[s]);
+        }
+        nbox[walk[qi]] = nb;
+        float org[3];
+        int ecell[3];
+        wide_node_frame(G, nb.lo, nb.hi, org, ecell);
+        for (int c = 0; c < 3; ++c) {
+            nd.p[c] = org[c];
+            nd.e[c] = (uint8_t)(ecell[c] + 127);
+        }
+        for (int s = 0; s < 8; ++s)
+            for (int c = 0; c < 3; ++c) {
+                nd.qlo[c][s] = 255; // empty slot: inverted box
+                nd.qhi[c][s] = 0;
+                if (used & (1u << s))
+                    wide_quantise_axis(org[c], ecell[c], slot[s].lo[c], slot[s].hi[c], &nd.qlo[c][s], &nd.qhi[c][s]);
+            }
+    }
+    if (grid_out)
+        *grid_out = G;
+    return true;
+}
+
 } // namespace rt
 
 // Host-only entry point (include/rt_host.h): the production build without a GPU, for tests of the tree itself.
@@ -468,5 +532,20 @@ extern "C" int rt_bvh_wide_build_host(const float *positions, uint32_t n_triangl
     }
     if (order_out && !w.order.empty())
         std::memcpy(order_out, w.order.data(), w.order.size() * sizeof(uint32_t));
+    return 0;
+}
+
+// ... and its refit (rt::refit_wide): `nodes80` (n_nodes records, root = node 0) are refitted in place to `positions`; order[k] is the original
+// triangle of record k. The CPU model the device refit (rt_wide_refit.hip) is pinned to.
+extern "C" int rt_bvh_wide_refit_host(const float *positions, uint32_t n_triangles, const uint32_t *order, uint32_t n_order, uint32_t *nodes80, uint32_t n_nodes) {
+    if ((n_triangles && !positions) || (n_order && !order) || (n_nodes && !nodes80))
+        return 1; // RT_ERR_INVALID_ARG
+    std::vector<WideNode> nodes(n_nodes);
+    if (n_nodes)
+        std::memcpy(nodes.data(), nodes80, (size_t)n_nodes * sizeof(WideNode));
+    if (!rt::refit_wide(nodes, order, n_order, positions, n_triangles, nullptr))
+        return 1;
+    if (n_nodes)
+        std::memcpy(nodes80, nodes.data(), (size_t)n_nodes * sizeof(WideNode));
     return 0;
 }

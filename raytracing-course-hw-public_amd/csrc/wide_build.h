@@ -35,4 +35,10 @@ struct WideBvh {
 // `positions`: 9 floats per original triangle. cost_node / cost_tri: the model's price of one node visit and one triangle test.
 WideBvh build_wide(const BinBvh &bin, const float *positions, float cost_node = 1.0f, float cost_tri = 0.3f);
 
+// Refit `nodes` (root = node 0) in place to new positions: the topology words stay, every origin, exponent and plane is recomputed by the rule
+// build_wide uses for a node with those contents, on the WideGrid of the new bounds (*grid_out). order[k]: original triangle of record k.
+// A pure function of the topology and the positions; the model of the device refit (rt_wide_refit.hip). False: the records do not form a tree
+// over `order` (nothing meaningful is left in `nodes` then).
+bool refit_wide(std::vector<WideNode> &nodes, const uint32_t *order, size_t n_order, const float *positions, size_t n_triangles, WideGrid *grid_out);
+
 } // namespace rt

@@ -95,3 +95,33 @@ inline int wide_cell_exponent(const WideGrid &G, double ext) {
     e = e < G.e_base ? G.e_base : e;
     return e > G.e_base + 15 ? G.e_base + 15 : e; // (> e_base + 15 cannot happen for a node inside the scene box)
 }
+
+// ---- one node's own grid and its slots' planes: THE rule, used by the host collapse (build_wide), the device collapse (k_wide_emit) and both
+// refits (refit_wide, rt_wide_refit.hip). A node whose contents span [lo, hi] has its origin snapped down to the scene's origin grid and, per
+// axis, the smallest cell exponent whose 255 cells reach hi from there ...
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline void wide_node_frame(const WideGrid &G, const float lo[3], const float hi[3], float org[3], int e[3]) {
+    for (int c = 0; c < 3; ++c) {
+        org[c] = wide_snap_origin(G, c, lo[c], nullptr);
+        e[c] = wide_cell_exponent(G, (double)hi[c] - (double)org[c]);
+    }
+}
+// ... and a slot's exact box [blo, bhi] on one axis becomes the planes floor / ceil on that grid, clamped to a byte and containing the box
+// (doubles hold these sums exactly enough; nudge if a rounding went the wrong way).
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline void wide_quantise_axis(float org, int e, float blo, float bhi, uint8_t *qlo, uint8_t *qhi) {
+    const double cell = ldexp(1.0, e);
+    double ql = floor(((double)blo - (double)org) / cell), qh = ceil(((double)bhi - (double)org) / cell);
+    ql = fmin(fmax(ql, 0.0), 255.0);
+    qh = fmin(fmax(qh, 0.0), 255.0);
+    while (ql > 0.0 && (double)org + ql * cell > (double)blo)
+        ql -= 1.0;
+    while (qh < 255.0 && (double)org + qh * cell < (double)bhi)
+        qh += 1.0;
+    *qlo = (uint8_t)ql;
+    *qhi = (uint8_t)qh;
+}
