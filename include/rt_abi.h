@@ -47,7 +47,8 @@ extern "C" {
                                 options were retired (two rt_build_options fields became reserved, unused RT_SORT_* / RT_BUILD_* values are
                                 refused): the binary layout and the meaning of every value that remains are unchanged. Still 4 after
                                 rt_view / rt_render_views / rt_render_views_rgb8 were added, and after the rt_accum_* accumulators and
-                                rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were:
+                                rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were, and
+                                after rt_update_geometry and rt_ray / rt_render_rays / rt_render_rays_rgb8 were:
                                 new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
@@ -386,6 +387,44 @@ typedef struct rt_view {
 } rt_view;             /* 64 bytes */
 int rt_render_views(rt_scene *scene, const rt_params *params, const rt_view *views, uint32_t n_views, float *fb_rgb, rt_stats *stats);
 int rt_render_views_rgb8(rt_scene *scene, const rt_params *params, const rt_view *views, uint32_t n_views, uint8_t *rgb8, rt_stats *stats);
+
+/* Radiance along caller-supplied rays (additive; RT_ABI_VERSION stays 4): the integrator behind any sensor model — panoramic, fisheye,
+ * orthographic or thin-lens cameras, rolling shutters, irradiance probes, light-map texels. The rays and their RNG streams come from a
+ * buffer instead of from rt_camera; everything after a path's first ray is rt_render's pipeline.
+ * The rule, operation by operation. Let K = params->samples and G = rays_per_output (0 means 1).
+ *   Sample s (0 <= s < K) of ray r:
+ *     - the RNG is seeded with rt_xoshiro_seed(params->seed, r.stream, r.first_sample + s) (the sample index wraps mod 2^32);
+ *     - two uniform_real(rng, 0.0f, 1.0f) draws are made and discarded: gen_ray's jitter draws (raytracer.h:527-538);
+ *     - the value is sanitize_nans(trace_ray(Ray{r.origin, r.dir}, ray_depth)) (raytracer.h:593-616) with that RNG state,
+ *     - through the scene's own traversal: parity, RT_FLAG_GLOBAL_BEST, or the wide tree of RT_BUILD_WIDE.
+ *   Output j, for j < n_rays / G:
+ *     - starts from +0.0;
+ *     - adds the values of rays j*G .. j*G + G - 1 in that order, each ray's K samples in sample order;
+ *     - is divided by (float)(G * K): render_pixel's loop (raytracer.h:618-627).
+ *   out_rgb holds 3 floats per output. rt_render_rays_rgb8 is the device film on top: 3 bytes per output, byte-identical to rt_tonemap_rgb8
+ *   of the float outputs.
+ * Consequence, which is the contract: when the rays are a camera's own primary rays (origin and direction as gen_ray makes them for sample
+ *   s of pixel p) with stream = p, first_sample = s, K = 1 and G = SPP, output p is pixel p of rt_render, bit for bit, and with
+ *   RT_FLAG_COUNTERS every event counter equals rt_render's.
+ * Scheduling independence: the order of the outputs, max_paths, the sort mode, the packet mode and the neighbours of a ray in the buffer
+ *   change no bit of any output.
+ * params: samples, seed, flags, the tuning fields and progress are read (flags may hold RT_FLAG_COUNTERS, RT_FLAG_GLOBAL_BEST and
+ *   RT_FLAG_DEVICE_FB); width and height are not read; rng_mode must be RT_RNG_DEVICE; shard_count must be 0 or 1.
+ * RT_FLAG_DEVICE_FB: `rays` AND the output are device pointers on the scene's GPU, idle on entry (as rt_render's framebuffer); `rays` must
+ *   be 16-byte aligned.
+ * A degenerate ray (a zero or non-finite component) is traversed as rt_cast_rays_ex traverses it; there is no host validation pass.
+ * RT_OK and nothing written: n_rays == 0; a scene with ray_depth == 0 (as rt_render).
+ * RT_ERR_INVALID_ARG: a NULL pointer with n_rays > 0; samples == 0; n_rays not a multiple of G; G * K or n_rays / G >= 2^31; a misaligned
+ *   device ray buffer; shard_count > 1; an unknown flag; a pass option rt_render would refuse.
+ * RT_ERR_UNSUPPORTED: RT_RNG_REFERENCE; RT_FLAG_MEGAKERNEL; a multi-GPU scene. */
+typedef struct rt_ray {
+    float origin[3];
+    float dir[3];          /* used as given (no normalisation): unit length is the caller's business, as for rt_bg_at */
+    uint32_t stream;       /* takes the pixel index's place in rt_xoshiro_seed(seed, stream, sample) */
+    uint32_t first_sample; /* sample index of this ray's first sample */
+} rt_ray;                  /* 32 bytes */
+int rt_render_rays(rt_scene *scene, const rt_params *params, const rt_ray *rays, uint32_t n_rays, uint32_t rays_per_output, float *out_rgb, rt_stats *stats);
+int rt_render_rays_rgb8(rt_scene *scene, const rt_params *params, const rt_ray *rays, uint32_t n_rays, uint32_t rays_per_output, uint8_t *rgb8, rt_stats *stats);
 
 /* Resumable sample accumulators: progressive and adaptive rendering (additive; RT_ABI_VERSION stays 4).
  * An accumulator belongs to one scene, one image size (width x height) and one view (a camera and an RT_RNG_DEVICE seed). It keeps, in

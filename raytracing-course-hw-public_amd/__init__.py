@@ -16,6 +16,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from . import rays  # noqa: F401
 from . import scenegen  # noqa: F401
 from ._ctypes_abi import (
     ABI_PROTOTYPES,
@@ -51,12 +52,14 @@ from ._ctypes_abi import (
     RT_UPDATE_REFIT,
     RT_RNG_DEVICE,
     RT_RNG_REFERENCE,
+    RAY_DTYPE,
     DescHolder,
     RtAdaptive,
     RtCamera,
     RtDenoise,
     RtGeometryUpdate,
     RtParams,
+    RtRay,
     RtSceneDesc,
     RtView,
     RtStats,
@@ -181,6 +184,27 @@ def make_views(cameras, seeds):
         views[v].camera.fov_x = np.float32(cam.fov_x)
         views[v].seed = int(seed)
     return views
+
+
+def pack_rays(rays, stream=None, first_sample=None, samples: int = 1, rays_per_output: int = 1) -> np.ndarray:
+    """rt_ray records (RAY_DTYPE, contiguous) of what DeviceScene.render_rays accepts: a packed array passes through (a ctypes RtRay array is
+    viewed, not copied); an (n, 6) float array gets `stream` / `first_sample`, by default stream = index // rays_per_output and first_sample =
+    (index % rays_per_output) x samples."""
+    if isinstance(rays, C.Array) and getattr(rays, "_type_", None) is RtRay:
+        rays = np.frombuffer(rays, dtype=RAY_DTYPE)
+    if isinstance(rays, np.ndarray) and rays.dtype == RAY_DTYPE:
+        if stream is not None or first_sample is not None:
+            raise ValueError("packed rays carry their own stream / first_sample")
+        return np.ascontiguousarray(rays).reshape(-1)
+    od = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = od.shape[0]
+    idx = np.arange(n, dtype=np.uint64)
+    g = max(1, int(rays_per_output))
+    out = np.zeros(n, dtype=RAY_DTYPE)
+    out["origin"], out["dir"] = od[:, :3], od[:, 3:]
+    out["stream"] = (idx // g).astype(np.uint32) if stream is None else np.asarray(stream, dtype=np.uint32).reshape(n)
+    out["first_sample"] = ((idx % g) * np.uint64(samples)).astype(np.uint32) if first_sample is None else np.asarray(first_sample, dtype=np.uint32).reshape(n)
+    return out
 
 
 def parse_gltf_scene(path: str, aspect: float) -> LoadedScene:
@@ -407,6 +431,51 @@ class DeviceScene:
         assert img.dtype == dt and img.flags["C_CONTIGUOUS"] and img.size == k * width * height * 3
         _check(fn(self._h, C.byref(p), views, k, img.ctypes.data_as(C.c_void_p), C.byref(st)))
         return img, st.as_dict()
+
+    def render_rays(
+        self,
+        rays,
+        stream=None,
+        first_sample=None,
+        samples: int = 1,
+        rays_per_output: int = 1,
+        seed: int = 0,
+        rgb8: bool = False,
+        global_best: bool = False,
+        counters: bool = False,
+        device_rays: int = 0,
+        device_out: int = 0,
+        n_rays: Optional[int] = None,
+        **tuning,
+    ):
+        """Radiance along caller-supplied rays (rt_render_rays, or rt_render_rays_rgb8 with `rgb8`). `rays`: an (n, 6) float array
+        (origin, dir; directions are used as given) with optional `stream` / `first_sample` arrays (defaults: stream = output index,
+        first_sample = (index within the output) x samples, so every sample of an output draws from its own stream position), or a packed
+        array: RAY_DTYPE records (what the generators of rays.py return) or a ctypes RtRay array. Ray r draws `samples` samples seeded from
+        (seed, stream_r, first_sample_r + s); output j averages rays j * rays_per_output .. in order (include/rt_abi.h states the rule).
+        Returns ((n / rays_per_output, 3) float32 or uint8 outputs, stats dict).
+        The device form (RT_FLAG_DEVICE_FB): `device_rays` (a device pointer to packed records, 16-byte aligned), `n_rays` (how many records
+        it holds: required here, not read otherwise) and `device_out` (a device pointer to n_rays / rays_per_output x 3 floats, or bytes with
+        `rgb8`) go together and `rays` is not read; nothing is copied and None is returned for the outputs. Both buffers must be idle.
+        `tuning`: as run_raytracer."""
+        p = RtParams(0, 0, int(samples), RT_RNG_DEVICE, int(seed), 0, 1, 0, (RT_FLAG_COUNTERS if counters else 0) | (RT_FLAG_GLOBAL_BEST if global_best else 0))
+        keep_cb = _apply_tuning(p, tuning)  # noqa: F841
+        st = RtStats()
+        fn = lib().rt_render_rays_rgb8 if rgb8 else lib().rt_render_rays
+        g = int(rays_per_output)
+        if bool(device_rays) != bool(device_out):
+            raise ValueError("render_rays: device_rays and device_out go together (RT_FLAG_DEVICE_FB covers both buffers)")
+        if device_rays:
+            if n_rays is None:
+                raise ValueError("render_rays: device_rays needs n_rays")
+            p.flags |= RT_FLAG_DEVICE_FB
+            _check(fn(self._h, C.byref(p), C.c_void_p(device_rays), int(n_rays), g, C.c_void_p(device_out), C.byref(st)))
+            return None, st.as_dict()
+        packed = pack_rays(rays, stream, first_sample, samples=int(samples), rays_per_output=max(1, g))
+        n = len(packed)
+        out = np.zeros((n // max(1, g), 3), dtype=np.uint8 if rgb8 else np.float32)
+        _check(fn(self._h, C.byref(p), packed.ctypes.data_as(C.c_void_p), n, g, out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return out, st.as_dict()
 
     def film_rgb8(self, fb: np.ndarray) -> np.ndarray:
         """The device film (image.h:49-82 on the GPU) applied to a host float array of shape (..., 3)."""
@@ -717,6 +786,10 @@ __all__ = [
     "parse_scene_txt",
     "load_scene",
     "make_views",
+    "pack_rays",
+    "rays",
+    "RAY_DTYPE",
+    "RtRay",
     "png_decode",
     "scenegen",
     "tonemap",

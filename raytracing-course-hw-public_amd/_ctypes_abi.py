@@ -65,6 +65,14 @@ class RtView(C.Structure):  # rt_render_views: one camera view (64 bytes)
     _fields_ = [("camera", RtCamera), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class RtRay(C.Structure):  # rt_render_rays: one caller-supplied ray and its RNG stream (32 bytes)
+    _fields_ = [("origin", C.c_float * 3), ("dir", C.c_float * 3), ("stream", C.c_uint32), ("first_sample", C.c_uint32)]
+
+
+# the same record as a numpy structured dtype: what the generators of rays.py return and DeviceScene.render_rays takes
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("dir", "<f4", (3,)), ("stream", "<u4"), ("first_sample", "<u4")])
+
+
 class RtDenoise(C.Structure):  # rt_accum_denoise: the filter's options (32 bytes; all-zero = the defaults)
     _fields_ = [
         ("iterations", C.c_uint32),
@@ -232,6 +240,8 @@ ABI_PROTOTYPES = {
     "rt_film_rgb8": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_u8_p]),
     "rt_render_views": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtView), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_render_views_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtView), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_render_rays": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_render_rays_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_accum_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtCamera), C.c_uint64, C.POINTER(C.c_void_p)]),
     "rt_accum_destroy": (None, [C.c_void_p]),
     "rt_accum_render": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtStats)]),

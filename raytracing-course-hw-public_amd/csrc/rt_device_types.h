@@ -310,6 +310,17 @@ struct WfFeat {
     uint32_t *hits;                        // [pixels]: h_p
 };
 
+// A pass of rt_render_rays (rt_rays.cpp): the first stage takes its rays and RNG streams from the caller's buffer instead of a camera
+// (wf_generate_rays). The call is a virtual image of n_rays / group "pixels" (outputs) with group * samples samples each, so WfLaunch keeps
+// describing the pass (first_pixel / pass_pixels count outputs, WfLaunch::samples = group * samples) and wf_fold / wf_resolve run unchanged:
+// sample index ds of output j is sample first_sample + ds % samples of ray j * group + ds / samples.
+struct WfRays {
+    const uint4_pod *rays; // [2 * n_rays]: rt_ray records (rt_abi.h), 32 B = two 16-byte pieces {origin, dir.x}, {dir.y, dir.z, stream, first_sample}
+    uint32_t group;        // G: consecutive rays per output
+    uint32_t samples;      // K: samples per ray
+    uint64_t seed;         // rt_params.seed
+};
+
 struct RenderLaunch {
     uint32_t width, height, samples, rng_mode;
     uint64_t seed;

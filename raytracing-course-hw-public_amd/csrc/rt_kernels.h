@@ -66,9 +66,10 @@ struct WfHostSync {
 // `acc` (optional): an accumulator pass (rt_accum.hip): wf_generate_list / wf_resolve_list over the round's entry list replace wf_generate /
 // wf_resolve; first_pass / last_pass are not read. Null for rt_render. `feat` (optional, with `acc`): the pass of a feature accumulator:
 // wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither.
+// `rays` (optional, without `acc`): a pass of rt_render_rays: wf_generate_rays replaces wf_generate; wf_fold and wf_resolve are rt_render's.
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
-                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr);
+                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr);
 // closest-hit probe through the renderer's own kernels: `rays` (6 floats each, device) -> queue -> wf_extend (or wf_extend_packet)
 // -> prim / bct (device). `L` carries the workspace (paths_in, hits, counters, stack_overflow, stats) and the traversal mode.
 hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *rays, uint32_t n, bool packet, bool stats, uint32_t *prim, float *bct,

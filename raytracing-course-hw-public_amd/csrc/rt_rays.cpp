@@ -1,0 +1,172 @@
+// rt_rays.cpp — rt_render_rays / rt_render_rays_rgb8 (rt_abi.h): the wavefront pipeline over rays and RNG streams the caller supplies.
+//
+// The call is planned as rt_render plans an image: n_rays / G outputs take the place of the pixels and G * K samples per output the place
+// of the SPP, in (output tile) x (sample range) passes under wavefront_max_paths. Only the first stage differs (wf_generate_rays reads the
+// ray buffer where wf_generate asks a camera): bounces, fold and resolve are rt_render's own launches, so a camera's own primary rays give
+// rt_render's image bit for bit.
+#include <algorithm>
+#include <cstring>
+
+#include "rt_scene_impl.h"
+
+static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays, uint32_t n_rays, uint32_t rays_per_output, float *out_rgb, uint8_t *rgb8_out,
+                            rt_stats *stats, const char *fn) {
+    const std::string name(fn);
+    if (!s || !p)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": null argument");
+    if (s->group)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": a multi-GPU scene renders images only; create the scene on one device");
+    if (p->flags & ~(uint32_t)(RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST))
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown flag");
+    if (p->flags & RT_FLAG_MEGAKERNEL)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": caller rays run on the wavefront pipeline, not the megakernel");
+    if (p->rng_mode == RT_RNG_REFERENCE)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": the reference RNG draws a 256-pixel span as one sequential stream; caller rays need RT_RNG_DEVICE");
+    if (p->rng_mode != RT_RNG_DEVICE)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown rng_mode");
+    if (p->samples == 0)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": samples must be >= 1");
+    if (p->shard_count > 1)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": shard_count > 1 does not apply to a ray list (split the list instead)");
+    if (int rc = rt::check_pass_params(p, fn); rc != RT_OK)
+        return rc;
+    const uint32_t G = rays_per_output ? rays_per_output : 1u, K = p->samples;
+    if (n_rays % G != 0)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": n_rays is not a multiple of rays_per_output");
+    const uint32_t n_out = n_rays / G;
+    if ((uint64_t)G * K >= 0x80000000ull || n_out >= 0x80000000u)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": rays_per_output x samples and n_rays / rays_per_output must stay below 2^31");
+    if (stats)
+        std::memset(stats, 0, sizeof(*stats));
+    if (n_rays == 0)
+        return RT_OK;
+    if (!rays || (!out_rgb && !rgb8_out))
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": null argument");
+    const bool device_fb = (p->flags & RT_FLAG_DEVICE_FB) != 0;
+    if (device_fb && (reinterpret_cast<uintptr_t>(rays) & 15u) != 0)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": a device ray buffer must be 16-byte aligned");
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (s->dev.ray_depth == 0) // raytracer.h:630-631, as rt_render
+        return RT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+
+    const uint32_t spo = G * K; // samples per output: the virtual image's SPP
+    const size_t fb_floats = (size_t)n_out * 3;
+    float *d_fb = out_rgb;
+    if (!device_fb || rgb8_out) { // the float outputs are internal unless the caller keeps them in HBM
+        if (int rc = s->ensure_fb(fb_floats); rc != RT_OK)
+            return rc;
+        d_fb = s->d_fb;
+    }
+    uint8_t *d_rgb8 = nullptr;
+    if (rgb8_out) {
+        if (int rc = s->ensure_film(device_fb ? 0 : fb_floats); rc != RT_OK)
+            return rc;
+        d_rgb8 = device_fb ? rgb8_out : s->d_rgb8;
+    }
+    const rt_ray *d_rays = rays;
+    if (!device_fb) {
+        if (int rc = s->ensure_rays((size_t)n_rays * sizeof(rt_ray)); rc != RT_OK)
+            return rc;
+        d_rays = static_cast<const rt_ray *>(s->d_rays);
+    }
+    const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
+    rt::PacketPolicy pol; // of this call: rt_render's, measured on camera rays of its image shape, is not disturbed
+    s->ext_events.reset();
+    uint32_t passes = 0, packet_passes = 0;
+    auto queue = [&]() -> int {
+        if (counters)
+            HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
+        if (!device_fb) // once per call; the caller's buffer outlives the stream sync below
+            HIP_TRY(hipMemcpyAsync(s->d_rays, rays, (size_t)n_rays * sizeof(rt_ray), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipEventRecord(s->ev0, s->stream));
+        // (output tile) x (sample range) passes, as rt_render plans (pixel tile) x (sample range)
+        const uint64_t max_paths = rt::wavefront_max_paths(s, p);
+        const uint64_t tile = std::min<uint64_t>(n_out, max_paths);
+        const uint32_t pass_spp = (uint32_t)std::clamp<uint64_t>(max_paths / tile, 1, spo);
+        if (int rc = s->ensure_wavefront(tile * pass_spp, tile, s->dev.ray_depth); rc != RT_OK)
+            return rc;
+        WfLaunch W{};
+        W.width = n_out; // the virtual image is one row of outputs (nothing on the device reads the size: it keys the packet policy)
+        W.height = 1;
+        W.samples = spo;
+        W.shard_index = 0;
+        W.shard_count = 1;
+        W.shard_block = n_out;
+        W.ray_depth = s->dev.ray_depth;
+        W.view_pixels = n_out;
+        s->wf_bind(W);
+        W.fb = d_fb;
+        W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
+        W.stats = counters ? s->d_stats : nullptr;
+        const WfRays R{reinterpret_cast<const uint4_pod *>(d_rays), G, K, p->seed};
+        // progress: one event per pass, the host one pass ahead of the device (rt_render's discipline)
+        const uint32_t n_passes = (uint32_t)((n_out + tile - 1) / tile) * ((spo + pass_spp - 1) / pass_spp);
+        uint32_t reported = 0, pass_no = 0;
+        if (p->progress)
+            while (s->pass_events.size() < n_passes) {
+                hipEvent_t ev = nullptr;
+                if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+                    return rt::fail(RT_ERR_HIP, name + ": progress event");
+                s->pass_events.push_back(ev);
+            }
+        for (uint64_t j0 = 0; j0 < n_out; j0 += tile) {
+            W.first_pixel = (uint32_t)j0;
+            W.pass_pixels = (uint32_t)std::min<uint64_t>(tile, n_out - j0);
+            for (uint32_t s0 = 0; s0 < spo; s0 += pass_spp) {
+                W.first_sample = s0;
+                W.pass_samples = std::min<uint32_t>(pass_spp, spo - s0);
+                W.n_paths = W.pass_pixels * W.pass_samples;
+                HIP_TRY(rt::launch_pass(s, p, pol, W, 1, s0 == 0, s0 + W.pass_samples >= spo, stats != nullptr, nullptr, nullptr, &R));
+                passes += 1;
+                packet_passes += W.use_packet;
+                if (p->progress) {
+                    HIP_TRY(hipEventRecord(s->pass_events[pass_no], s->stream));
+                    if (pass_no > 0) {
+                        HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
+                        p->progress(++reported, n_passes, p->progress_user);
+                    }
+                }
+                ++pass_no;
+            }
+        }
+        if (p->progress && pass_no > 0) {
+            HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
+            p->progress(++reported, n_passes, p->progress_user);
+        }
+        if (rgb8_out) // film on the device (image.h:49-82) over the outputs
+            HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_out, 0, 1, n_out, s->d_film_table, s->stream));
+        HIP_TRY(hipEventRecord(s->ev1, s->stream));
+        return RT_OK;
+    };
+    if (int rc = rt::queue_and_wait(s, queue); rc != RT_OK)
+        return rc;
+    if (!device_fb) {
+        if (rgb8_out)
+            HIP_TRY(hipMemcpy(rgb8_out, d_rgb8, fb_floats, hipMemcpyDeviceToHost));
+        else
+            HIP_TRY(hipMemcpy(out_rgb, d_fb, fb_floats * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (stats) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        if (int rc = rt::fill_stats(s, counters, (uint64_t)n_rays * K, ms, wall0, stats); rc != RT_OK)
+            return rc;
+        stats->packet_lanes_x100 = pol.lanes_x100;
+        stats->passes = passes;
+        stats->packet_passes = packet_passes;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_render_rays(rt_scene *s, const rt_params *p, const rt_ray *rays, uint32_t n_rays, uint32_t rays_per_output, float *out_rgb, rt_stats *stats) {
+    if (n_rays && !out_rgb)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_render_rays: null argument");
+    return render_rays_impl(s, p, rays, n_rays, rays_per_output, out_rgb, nullptr, stats, "rt_render_rays");
+}
+
+extern "C" int rt_render_rays_rgb8(rt_scene *s, const rt_params *p, const rt_ray *rays, uint32_t n_rays, uint32_t rays_per_output, uint8_t *rgb8, rt_stats *stats) {
+    if (n_rays && !rgb8)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_render_rays_rgb8: null argument");
+    return render_rays_impl(s, p, rays, n_rays, rays_per_output, nullptr, rgb8, stats, "rt_render_rays_rgb8");
+}

@@ -113,10 +113,10 @@ int rt::check_pass_params(const rt_params *p, const char *fn) {
 
 // One wavefront pass: `W` carries the workspace (wf_bind) and the pass's geometry (first_pixel, pass_pixels, first_sample, pass_samples,
 // n_paths, views, ...); this picks W.sort_mode and W.use_packet, launches, and folds the packet kernel's census back into `pol`, the
-// policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*). `acc`: an accumulator pass, `feat`: of a feature
-// accumulator (rt_kernels.h).
+// policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays*). `acc`: an
+// accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays (rt_kernels.h).
 hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                           const WfAccum *acc, const WfFeat *feat) {
+                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays) {
     // Small passes are bound by launch and host latency, not by memory (a 256 x 256 x 4 render, BASELINE config 1's
     // shape, spent 5.7 ms at 0.6 ms per bounce): RT_SORT_AUTO leaves a pass of fewer than 2^20 paths unsorted, which also spares it
     // the per-bounce queue-size read-back the sort needs: the whole pass is queued without a single host wait.
@@ -140,7 +140,7 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     const rt::WfHostSync hsync = wavefront_host_sync(s);
     unsigned long long census[2] = {0ull, 0ull};
     const hipError_t e = rt::launch_wavefront_pass(s->dev, W, W.stats != nullptr, s->num_cus, first_pass, last_pass, s->stream, time_extends ? &s->ext_events : nullptr, census,
-                                                   s->wf_host_count ? &hsync : nullptr, acc, feat);
+                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays);
     if (e == hipSuccess && census[0] != 0ull) {
         pol.lanes_x100 = (uint32_t)(100.0 * (double)census[1] / (double)census[0]);
         if ((double)census[1] < min_lanes * (double)census[0])

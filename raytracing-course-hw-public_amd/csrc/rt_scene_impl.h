@@ -1,6 +1,7 @@
 // rt_scene_impl.h — what the host files behind include/rt_abi.h share (internal): the definition of rt_scene and the few helpers
-// with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_accum_host.cpp (rt_accum_*) and
-// rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through rt_group.h.
+// with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_rays.cpp (rt_render_rays*),
+// rt_accum_host.cpp (rt_accum_*) and rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through
+// rt_group.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -179,6 +180,20 @@ struct rt_scene {
         views_capacity = n;
         return RT_OK;
     }
+    // the device copy of a host ray buffer (rt_render_rays), grown on demand
+    void *d_rays = nullptr;
+    size_t rays_capacity = 0; // bytes
+    int ensure_rays(size_t bytes) {
+        if (rays_capacity >= bytes)
+            return RT_OK;
+        if (d_rays)
+            (void)hipFree(d_rays);
+        d_rays = nullptr;
+        rays_capacity = 0;
+        HIP_TRY(hipMalloc(&d_rays, bytes));
+        rays_capacity = bytes;
+        return RT_OK;
+    }
     int num_cus = 0;
     int blocks_per_cu = 8; // upper bound on resident 256-thread blocks per CU; surplus blocks find the ticket exhausted
     // wavefront pipeline workspace (rt_wavefront.hip), sized for wf_paths_cap paths / wf_pixels_cap pixels per pass
@@ -311,6 +326,8 @@ struct rt_scene {
             (void)hipFree(d_rgb8);
         if (d_views)
             (void)hipFree(d_views);
+        if (d_rays)
+            (void)hipFree(d_rays);
         if (d_film_table)
             (void)hipFree(d_film_table);
         ext_events.destroy();
@@ -338,7 +355,7 @@ void set_camera(DevScene &D, const float *pos, const float *right, const float *
 int check_pass_params(const rt_params *p, const char *fn);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
 hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                       const WfAccum *acc, const WfFeat *feat = nullptr);
+                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr);
 int fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats);
 
 // Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are

@@ -69,9 +69,15 @@ DEV uint32_t wf_global_pixel(const WfLaunch &L, uint32_t local_pixel) {
 }
 
 // ------------------------------------------------------------------------------------------------ generate
+// The first record of path i, in queue slot i: the ray (o, d) with `rng` as gen_ray left it (behind its two jitter draws), full budget, no
+// pending frames. The one definition of a path's first record: a camera's rays (wf_primary_ray) and a caller's (wf_generate_rays) both end here.
+DEV void wf_store_first(const DevScene &S, const WfLaunch &L, uint32_t i, V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) {
+    wf_store_path(L.paths_in + i, wf_pack(o, d, i, next_shade_class(rng, S.lights.n_tris != 0), L.ray_depth, 0u, rng.g));
+}
+
 // gen_ray (raytracer.h:527-538) for sample s of pixel pix of view v: camera, jitter and seeding, written as the primary-ray record of queue
-// slot (= path) i. The one definition of a path's first ray: wf_generate and the accumulators' wf_generate_list both call it, so sample s of
-// pixel p is the same ray whichever of them draws it.
+// slot (= path) i. The one definition of a camera path's first ray: wf_generate and the accumulators' wf_generate_list both call it, so sample
+// s of pixel p is the same ray whichever of them draws it.
 DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32_t v, uint32_t pix, uint32_t s) {
     // the view is wave-uniform except where a wave straddles two views: then every lane reads its own record
     const uint32_t v0 = __builtin_amdgcn_readfirstlane(v);
@@ -84,8 +90,7 @@ DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32
     Rng<RT_RNG_DEVICE> rng;
     rt_xoshiro_seed(&rng.g, view.seed, pix, s);
     const V3 rd = gen_ray_dir(rng, pix, L.width, L.height, view.tan_x, view.tan_y, cam_right, cam_up, cam_fwd);
-    // path i in slot i: full budget, no pending frames
-    wf_store_path(L.paths_in + i, wf_pack(cam_pos, rd, i, next_shade_class(rng, S.lights.n_tris != 0), L.ray_depth, 0u, rng.g));
+    wf_store_first(S, L, i, cam_pos, rd, rng);
 }
 
 template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
@@ -131,6 +136,32 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list(co
         const uint32_t e = A.first_entry + lo;
         wf_primary_ray(S, L, i, 0u, A.list_pix[e], A.list_base[e] + (g - off[lo])); // an accumulator has one view
         st.cast();
+    }
+    st.flush(L.stats);
+}
+
+// A pass of rt_render_rays (WfRays): path i is sample index first_sample + ds of output first_pixel + lp, like wf_generate's, and that is
+// sample `first_sample + ds % K` of ray `output * G + ds / K` of the caller's buffer. The lane reads its 32-byte record as two 16-byte pieces
+// (with K = 1 the lanes of a wave read consecutive records), seeds the stream the record names, makes gen_ray's two jitter draws and discards
+// them (raytracer.h:527-538: the stream then stands where a camera ray's stands), and stores the ray as given: no normalisation.
+template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_rays(const DevScene S, const WfLaunch L, const WfRays R) {
+    LaneStats<STATS> st;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        L.counters[WF_CNT_IN] = L.n_paths;
+    const uint4 *recs = reinterpret_cast<const uint4 *>(R.rays);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
+        const uint32_t lp = i / L.pass_samples;
+        const uint32_t ds = L.first_sample + (i - lp * L.pass_samples); // < G * K
+        const uint32_t sub = ds / R.samples;                            // < G
+        const size_t ray = (size_t)(L.first_pixel + lp) * R.group + sub;
+        const uint4 p0 = recs[2 * ray], p1 = recs[2 * ray + 1];
+        Rng<RT_RNG_DEVICE> rng;
+        rt_xoshiro_seed(&rng.g, R.seed, p1.z, p1.w + (ds - sub * R.samples)); // the sample index wraps mod 2^32
+        (void)uniform_real(rng, 0.0f, 1.0f);
+        (void)uniform_real(rng, 0.0f, 1.0f);
+        wf_store_first(S, L, i, mk(__uint_as_float(p0.x), __uint_as_float(p0.y), __uint_as_float(p0.z)),
+                       mk(__uint_as_float(p0.w), __uint_as_float(p1.x), __uint_as_float(p1.y)), rng);
+        st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
     }
     st.flush(L.stats);
 }
@@ -748,7 +779,7 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc,
-                                 const WfFeat *feat) {
+                                 const WfFeat *feat, const WfRays *rays) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
@@ -764,6 +795,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
     e = with_bools([&](auto ST) {
         if (acc) // an accumulator pass: the first stage follows the round's list (wf_generate_list)
             return RT_LAUNCH_CHECKED((wf_generate_list<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
+        if (rays) // a pass of rt_render_rays: the caller's rays and streams (wf_generate_rays)
+            return RT_LAUNCH_CHECKED((wf_generate_rays<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *rays);
         return RT_LAUNCH_CHECKED((wf_generate<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
     }, stats);
     if (e != hipSuccess)
