@@ -48,7 +48,8 @@ extern "C" {
                                 refused): the binary layout and the meaning of every value that remains are unchanged. Still 4 after
                                 rt_view / rt_render_views / rt_render_views_rgb8 were added, and after the rt_accum_* accumulators and
                                 rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were, and
-                                after rt_update_geometry and rt_ray / rt_render_rays / rt_render_rays_rgb8 were:
+                                after rt_update_geometry and rt_ray / rt_render_rays / rt_render_rays_rgb8 were, and after
+                                rt_update_geometry_device and rt_refit_times were:
                                 new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
@@ -589,6 +590,34 @@ typedef struct rt_geometry_update {
     uint32_t reserved[4];         /* 0 */
 } rt_geometry_update;             /* 64 bytes */
 int rt_update_geometry(rt_scene *scene, const rt_geometry_update *upd);
+
+/* rt_update_geometry for arrays that are in HBM already (a cloth solver, skinning or a physics step in torch; additive, RT_ABI_VERSION stays
+ * 4): the same struct and the same modes, but the five pointers are DEVICE pointers on the scene's GPU. Blocking.
+ *   Equivalence: after RT_OK the scene is, bit for bit and for every entry point and dump, the scene rt_update_geometry leaves when given
+ *     host copies of the same bytes in the same mode: both trees (the light tree included: rt_bvh_info(1), rt_bvh_device_dump(1)), every
+ *     record, the packet-policy reset, the rt_bvh_info(0) refusal after a REFIT. rt_build_times* report the same builds; upload_ms is 0
+ *     where nothing was uploaded (build_ms starts once the build's sort and bounds buffers are allocated, for both entry points).
+ *   Buffers: the arrays are read, never written, and not retained: the caller may overwrite or free them as soon as the call returns. They
+ *     must be idle on entry (no pending work of the caller's writes them): the library reads them on the scene's own stream and
+ *     synchronises it before returning, the rule of RT_FLAG_DEVICE_FB. Each pointer must be 4-byte aligned and nothing more: a view that
+ *     starts one element into a larger allocation is legal.
+ *   What crosses the bus: the bounds of the vertices and the verdict of the checks (8 words), then the emissive triangles alone (their
+ *     indices and positions, 40 bytes each) for the light BVH, which is still built on the host, and that tree back. RT_UPDATE_REFIT reads
+ *     the caller's arrays in place: nothing is allocated or copied for them. RT_UPDATE_REBUILD of a scene built with RT_BUILD_DEVICE_LBVH
+ *     builds from them in place. Legal, but not the fast path: RT_UPDATE_REBUILD of a scene whose build reads the arrays on the host (the
+ *     reference-topology builds, i.e. no RT_BUILD_DEVICE_LBVH; the host collapse of a wide tree, i.e. RT_BUILD_WIDE_HOST_COLLAPSE or a
+ *     RT_BUILD_WIDE scene of 8 triangles or fewer) stages one device-to-host copy of the five arrays and runs rt_update_geometry's path.
+ * Refusals: rt_update_geometry's, with the same codes. The material id and the non-finite position are found by a kernel (the message names
+ *   the lowest offending triangle, as the host loop does; no message depends on scheduling). Added, RT_ERR_INVALID_ARG both: a pointer that
+ *   is not 4-byte aligned ("misaligned"; checked with the struct, before the scene is looked at), and a pointer for which
+ *   hipPointerGetAttributes does not report device memory of the scene's GPU, pinned host memory included ("not device memory"; checked
+ *   before any launch, at the first and the last byte of each array: what lies between them is the caller's word). After any refusal the scene is unchanged, bit for bit: every check, every allocation and the exponent-range test
+ *   come before the first write to anything a render kernel reads. */
+int rt_update_geometry_device(rt_scene *scene, const rt_geometry_update *upd);
+/* Wall time of the last successful RT_UPDATE_REFIT of `scene` through either entry point (0, 0 before the first): *refit_ms the refit of records
+ * and nodes on the device, *levels_ms the part of it spent in the top-down level pass, which reads the topology alone (one launch and one
+ * host read per level). A measurement aid, like rt_build_times. RT_ERR_INVALID_ARG: a NULL argument; RT_ERR_UNSUPPORTED: a multi-GPU scene. */
+int rt_refit_times(const rt_scene *scene, double *refit_ms, double *levels_ms);
 
 int rt_film_rgb8(rt_scene *scene, const float *rgb, size_t n_pixels, uint8_t *out_rgb8);
 

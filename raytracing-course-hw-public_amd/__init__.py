@@ -246,6 +246,25 @@ def _as_desc(scene) -> Tuple[RtSceneDesc, object]:
     return holder.desc, holder
 
 
+GEOMETRY_ARRAYS = (("positions", 9, np.float32), ("normals", 9, np.float32), ("texcoords", 6, np.float32), ("tangents", 9, np.float32), ("material_ids", 1, np.uint32))
+
+
+def geometry_arrays(scene) -> dict:
+    """The five per-triangle arrays exactly as the library receives them for `scene` (a scenegen.Scene, a LoadedScene or an arrays dict), as
+    flat numpy copies keyed positions / normals / texcoords / tangents / material_ids: what _as_desc's descriptor points at, geometric normals
+    for normals=None included. DeviceScene.update_geometry(scene) and update_geometry_device(**{on the GPU}) of these are the same update.
+    The arrays are read back from the descriptor the one existing path builds (scenegen.DescHolder), so nothing here can drift from it. That
+    path normalises given normals in float32, as the reference's loader does: feeding the result through an arrays dict again normalises
+    them once more, so geometry_arrays is not a fixed point for normals (the other four arrays are)."""
+    desc, keep = _as_desc(scene)  # noqa: F841 (keeps the arrays alive while they are copied)
+    n = int(desc.n_triangles)
+    out = {}
+    for name, per, dtype in GEOMETRY_ARRAYS:
+        nbytes = n * per * 4
+        out[name] = np.frombuffer(C.string_at(getattr(desc, name), nbytes) if nbytes else b"", dtype=dtype).copy()
+    return out
+
+
 def _apply_tuning(p: RtParams, tuning: dict):
     """rt_params' ABI-4 fields from keyword arguments; returns the ctypes callback object (if any), to be kept alive by the caller."""
     cb = None
@@ -276,6 +295,7 @@ class DeviceScene:
         desc, keep = _as_desc(scene)
         self._keep = keep
         self._accums = []  # live Accumulators: closed before the scene (rt_accum_destroy precedes rt_destroy)
+        self._device = None if isinstance(device, (list, tuple)) or int(device) < 0 else int(device)  # the one GPU of a single-GPU scene
         self._h = C.c_void_p()
         if device_bvh or wide or build_flags or build_options:  # a private copy of the descriptor with the build flags set
             d2 = RtSceneDesc()
@@ -320,6 +340,52 @@ class DeviceScene:
         u.mode = RT_UPDATE_REFIT if refit else RT_UPDATE_REBUILD
         u.positions, u.normals, u.texcoords, u.tangents, u.material_ids = desc.positions, desc.normals, desc.texcoords, desc.tangents, desc.material_ids
         _check(lib().rt_update_geometry(self._h, C.byref(u)))
+
+    def update_geometry_device(self, positions, normals, texcoords, tangents, material_ids, refit: bool = False, n_triangles: Optional[int] = None) -> None:
+        """rt_update_geometry_device: update_geometry for arrays that are on this scene's GPU already. Each argument is a contiguous torch
+        CUDA tensor (float32; the ids int32 or uint32) of 9 / 9 / 6 / 9 / 1 elements per triangle, or an int device pointer, used with
+        `n_triangles`. Normals are required (the geometric-normal default of update_geometry is host code). The tensors are read, not kept
+        and not written; torch's current stream on their device is synchronised first, so that they are idle when the library reads them
+        on the scene's own stream."""
+        import torch
+
+        given = dict(positions=positions, normals=normals, texcoords=texcoords, tangents=tangents, material_ids=material_ids)
+        n, device, ptrs = n_triangles, None, {}
+        for name, per, dtype in GEOMETRY_ARRAYS:
+            a = given[name]
+            if isinstance(a, int) and not isinstance(a, bool):
+                ptrs[name] = a
+                continue
+            if not isinstance(a, torch.Tensor) or not a.is_cuda:
+                raise TypeError(f"{name}: a torch CUDA tensor or an int device pointer, not {type(a).__name__}" + (" on the CPU" if isinstance(a, torch.Tensor) else ""))
+            ok = (torch.float32,) if dtype == np.float32 else tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+            if a.dtype not in ok:
+                raise TypeError(f"{name}: dtype {a.dtype}, expected {' or '.join(str(t) for t in ok)}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: the tensor is not contiguous")
+            if a.numel() % per:
+                raise ValueError(f"{name}: {a.numel()} elements are no multiple of {per} per triangle")
+            if n is None:
+                n = a.numel() // per
+            if a.numel() != n * per:
+                raise ValueError(f"{name}: {a.numel()} elements, expected {n * per} for {n} triangles")
+            if device is None:
+                device = a.device
+            if a.device != device:
+                raise ValueError(f"{name}: on {a.device}, the other arrays are on {device}")
+            if self._device is not None and a.device.index != self._device:
+                raise ValueError(f"{name}: on {a.device}, the scene is on GPU {self._device}")
+            ptrs[name] = a.data_ptr() if a.numel() else 0
+        if n is None:
+            raise ValueError("n_triangles is needed when every array is a device pointer")
+        if device is not None:
+            torch.cuda.current_stream(device).synchronize()  # the idle precondition
+        u = RtGeometryUpdate()
+        u.n_triangles = int(n)
+        u.mode = RT_UPDATE_REFIT if refit else RT_UPDATE_REBUILD
+        for name, _, dtype in GEOMETRY_ARRAYS:
+            setattr(u, name, C.cast(C.c_void_p(ptrs[name]), C.POINTER(C.c_float if dtype == np.float32 else C.c_uint32)))
+        _check(lib().rt_update_geometry_device(self._h, C.byref(u)))
 
     def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
@@ -552,6 +618,12 @@ class DeviceScene:
         b, u, w = C.c_double(), C.c_double(), C.c_double()
         _check(lib().rt_build_times_ex(self._h, C.byref(b), C.byref(u), C.byref(w)))
         return {"build_ms": b.value, "upload_ms": u.value, "wide_ms": w.value}
+
+    def refit_times(self):
+        """rt_refit_times: wall ms of the last refit on the device, and of its top-down level pass."""
+        r, l = C.c_double(), C.c_double()
+        _check(lib().rt_refit_times(self._h, C.byref(r), C.byref(l)))
+        return {"refit_ms": r.value, "levels_ms": l.value}
 
     def bvh_info(self, which: int):
         nn, no, root = C.c_uint32(), C.c_uint32(), C.c_uint32()

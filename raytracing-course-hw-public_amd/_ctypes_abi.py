@@ -255,6 +255,8 @@ ABI_PROTOTYPES = {
     "rt_accum_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
     "rt_accum_denoise_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
     "rt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),
+    "rt_update_geometry_device": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),  # the five pointers are device pointers
+    "rt_refit_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_last_error": (C.c_char_p, []),
     "rt_source_stamp": (C.c_char_p, []),
     "rt_abi_version": (C.c_uint32, []),

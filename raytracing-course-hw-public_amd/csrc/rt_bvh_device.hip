@@ -711,18 +711,11 @@ hipError_t build_bvh_device(const rt_scene_desc *d, hipStream_t stream, DeviceBv
     out->fast_ok = true;
     if (n == 0)
         return hipSuccess;
+    // ---- obtain the five device arrays: this entry point uploads them ...
     const auto t0 = std::chrono::steady_clock::now();
     Tmp tmp;
     float *pos, *nrm, *tan, *uv;
-    uint32_t *mat, *keys[2], *vals[2], *bounds, *leaf_parent, *node_parent, *arrived, *fast_bad;
-    uint32_t leaf_tris = LEAF_TRIS_DEFAULT;
-    if (d->build.lbvh_leaf_tris)
-        leaf_tris = std::min(8u, std::max(1u, d->build.lbvh_leaf_tris));
-    // the wide collapse regroups single-triangle leaves itself; scenes of a handful of triangles take the host collapse (rt_scene.cpp)
-    wide = wide && n > 8u;
-    if (wide)
-        leaf_tris = 1;
-    const uint32_t n_leaves = (n + leaf_tris - 1) / leaf_tris;
+    uint32_t *mat;
     BUILD_TRY(tmp.alloc(&pos, 9ull * n));
     BUILD_TRY(tmp.alloc(&nrm, 9ull * n));
     BUILD_TRY(tmp.alloc(&tan, 9ull * n));
@@ -733,15 +726,45 @@ hipError_t build_bvh_device(const rt_scene_desc *d, hipStream_t stream, DeviceBv
     BUILD_TRY(hipMemcpyAsync(tan, d->tangents, 36ull * n, hipMemcpyHostToDevice, stream));
     BUILD_TRY(hipMemcpyAsync(uv, d->texcoords, 24ull * n, hipMemcpyHostToDevice, stream));
     BUILD_TRY(hipMemcpyAsync(mat, d->material_ids, 4ull * n, hipMemcpyHostToDevice, stream));
+    BUILD_TRY(hipStreamSynchronize(stream)); // uploads done = start of the device build proper
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- ... and builds from them
+    DeviceArrays in;
+    in.pos = pos, in.nrm = nrm, in.uv = uv, in.tan = tan, in.mat = mat, in.n = n;
+    const hipError_t e = build_bvh_device_arrays(in, d->build, stream, out, err, wide, cost_node, cost_tri);
+    if (e == hipSuccess)
+        out->upload_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    return e;
+}
+
+hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_options &opt, hipStream_t stream, DeviceBvh *out, const char **err, bool wide, float cost_node,
+                                   float cost_tri) {
+    const uint32_t n = in.n;
+    *out = DeviceBvh{};
+    out->root = RT_NONE;
+    out->fast_ok = true;
+    if (n == 0)
+        return hipSuccess;
+    Tmp tmp;
+    const float *pos = in.pos, *nrm = in.nrm, *tan = in.tan, *uv = in.uv;
+    const uint32_t *mat = in.mat;
+    uint32_t *keys[2], *vals[2], *bounds, *leaf_parent, *node_parent, *arrived, *fast_bad;
+    uint32_t leaf_tris = LEAF_TRIS_DEFAULT;
+    if (opt.lbvh_leaf_tris)
+        leaf_tris = std::min(8u, std::max(1u, opt.lbvh_leaf_tris));
+    // the wide collapse regroups single-triangle leaves itself; scenes of a handful of triangles take the host collapse (rt_scene.cpp)
+    wide = wide && n > 8u;
+    if (wide)
+        leaf_tris = 1;
+    const uint32_t n_leaves = (n + leaf_tris - 1) / leaf_tris;
     for (int k = 0; k < 2; ++k) {
         BUILD_TRY(tmp.alloc(&keys[k], (size_t)n));
         BUILD_TRY(tmp.alloc(&vals[k], (size_t)n));
     }
     BUILD_TRY(tmp.alloc(&bounds, (size_t)8));
-    const uint32_t init_bounds[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
+    static const uint32_t init_bounds[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
     BUILD_TRY(hipMemcpyAsync(bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
     fast_bad = bounds + 6;
-    BUILD_TRY(hipStreamSynchronize(stream)); // `init_bounds` is a local; uploads done = start of the device build proper
     const auto t1 = std::chrono::steady_clock::now();
 
     const int blocks = (int)std::min<uint64_t>(((uint64_t)n + 255) / 256, 256u * 16u);
@@ -797,14 +820,14 @@ hipError_t build_bvh_device(const rt_scene_desc *d, hipStream_t stream, DeviceBv
     // binary tree over the leaves: PLOC (default) or the Karras radix tree + refit (rt_build_options.device_builder = RT_BUILDER_LBVH; also the fallback when
     // a PLOC tree comes out deeper than the traversal stacks allow)
     uint32_t bin_root = 0u;
-    bool use_ploc = n_leaves > 1 && d->build.device_builder != RT_BUILDER_LBVH;
+    bool use_ploc = n_leaves > 1 && opt.device_builder != RT_BUILDER_LBVH;
     if (use_ploc) {
         Ploc P{};
         // search radius: 8 positions to either side measured best on both bench scenes (S-sponza / S-10M, wide tree collapsed from
         // it: radius 2: 452 / 217 Msamples/s, 4: 495 / 224, 6: 502 / 224, 8: 496 / 244, 16: 464 / 228, 32: 465 / 231; profiles/r03_wide.txt)
         int radius = 8;
-        if (d->build.ploc_radius)
-            radius = std::min(PLOC_MAX_RADIUS, std::max(1, (int)d->build.ploc_radius));
+        if (opt.ploc_radius)
+            radius = std::min(PLOC_MAX_RADIUS, std::max(1, (int)opt.ploc_radius));
         P.radius = radius;
         for (int k = 0; k < 2; ++k) {
             BUILD_TRY(tmp.alloc(&P.ref[k], (size_t)n_leaves));
@@ -940,7 +963,7 @@ hipError_t build_bvh_device(const rt_scene_desc *d, hipStream_t stream, DeviceBv
         out->lo[c] = dec_f(h_bounds[c]);
         out->hi[c] = dec_f(h_bounds[3 + c]);
     }
-    out->upload_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    out->upload_ms = 0; // the arrays were here already; build_bvh_device adds the time of its uploads
     out->build_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
     return hipSuccess;
 }

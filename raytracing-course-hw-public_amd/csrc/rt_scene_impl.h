@@ -12,6 +12,7 @@
 
 #include "../../include/rt_abi.h"
 #include "bvh_build.h"
+#include "rt_bvh_device.h"
 #include "rt_device_types.h"
 #include "rt_error.h"
 #include "rt_film.h"
@@ -120,6 +121,7 @@ struct rt_scene {
     double wide_ms = 0, wide_cost = 0;
     uint32_t dev_n_inner[2] = {0, 0};
     double build_ms = 0, build_upload_ms = 0;
+    double refit_ms = 0, refit_levels_ms = 0; // the last RT_UPDATE_REFIT: refit_wide_device in all, and its top-down level pass (rt_refit_times)
     uint32_t *d_counter = nullptr;
     DevStats *d_stats = nullptr;
     float *d_fb = nullptr;
@@ -346,7 +348,9 @@ const HostBvh &prepared_host_bvh(const rt_scene *s, int which); // the host-buil
 // the two halves of the geometry build, host and device, that rt_create and rt_update_geometry (rt_update.cpp) both run
 void prepare_geometry(const rt_scene_desc *d, const std::vector<uint8_t> &emissive, float wide_cost_node, float wide_cost_tri, PreparedGeometry &P,
                       bool lights_only = false);
-int upload_geometry(rt_scene *s, const rt_scene_desc *d, const PreparedScene &PS, const PreparedGeometry &P, GeometryOnDevice &out);
+void prepare_lights(const float *positions, uint32_t n_total, const std::vector<uint32_t> &lights, const uint32_t *original, PreparedGeometry &P);
+int upload_geometry(rt_scene *s, const rt_scene_desc *d, const PreparedScene &PS, const PreparedGeometry &P, GeometryOnDevice &out,
+                    const DeviceArrays *arrays = nullptr);
 void install_geometry(rt_scene *s, GeometryOnDevice &g);
 uint32_t light_lds_inner(const FlatBvh &f); // DevBvh::lds_inner of a light tree
 // rt_render.cpp: views, the check of the pass options, the wavefront pass policy and the statistics of a finished call

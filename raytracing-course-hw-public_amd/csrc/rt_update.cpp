@@ -6,47 +6,75 @@
 //   RT_UPDATE_REBUILD  all of it, into new buffers beside the live ones; then swap and free. The scene is the one rt_create would build.
 //   RT_UPDATE_REFIT    (RT_BUILD_WIDE) the light half on the host as in REBUILD; the scene tree keeps its topology and is refitted in
 //                      place on the device (rt_wide_refit.hip), the triangle and shading records are rewritten in place.
+// rt_update_geometry_device is the same call for arrays that are in the scene GPU's memory already. What rt_update_geometry does with two host
+// loops (the data-dependent refusals, the pick of the lights) one pass on the device does (rt_update_dev.hip); the device build and the refit
+// read the caller's arrays where they are; only the builds that read the arrays on the host stage a copy and run the host path.
 #include <cmath>
 #include <cstring>
 
 #include "rt_scene_impl.h"
+#include "rt_update_dev.h"
 #include "rt_wide_refit.h"
 #include "wide_grid.h"
 
 namespace {
 
-int check_update(const rt_scene *s, const rt_geometry_update *u) {
+// The checks of the two entry points, in the order both make them. `fn` names the entry point in the message.
+// ... of the struct alone, before the scene is looked at (`device`: the five pointers are device pointers, read by dword loads)
+int check_struct(const rt_geometry_update *u, const std::string &fn, bool device) {
     if (!u)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: null argument");
+        return rt::fail(RT_ERR_INVALID_ARG, fn + ": null argument");
     if (u->mode != RT_UPDATE_REBUILD && u->mode != RT_UPDATE_REFIT)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: unknown mode");
+        return rt::fail(RT_ERR_INVALID_ARG, fn + ": unknown mode");
     for (uint32_t r : u->reserved)
         if (r)
-            return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: reserved field is not 0");
+            return rt::fail(RT_ERR_INVALID_ARG, fn + ": reserved field is not 0");
     if (u->n_triangles && (!u->positions || !u->normals || !u->texcoords || !u->tangents || !u->material_ids))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: null geometry array");
+        return rt::fail(RT_ERR_INVALID_ARG, fn + ": null geometry array");
+    if (device)
+        for (const void *p : {(const void *)u->positions, (const void *)u->normals, (const void *)u->texcoords, (const void *)u->tangents, (const void *)u->material_ids})
+            if ((uintptr_t)p & 3u)
+                return rt::fail(RT_ERR_INVALID_ARG, fn + ": misaligned geometry array (device pointers must be 4-byte aligned)");
+    return RT_OK;
+}
+// ... of the scene against the struct
+int check_scene(const rt_scene *s, const rt_geometry_update *u, const std::string &fn) {
     if (!s)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: null scene");
+        return rt::fail(RT_ERR_INVALID_ARG, fn + ": null scene");
     if (s->group)
-        return rt::fail(RT_ERR_UNSUPPORTED, "rt_update_geometry: multi-GPU scenes cannot be updated");
+        return rt::fail(RT_ERR_UNSUPPORTED, fn + ": multi-GPU scenes cannot be updated");
     if (u->n_triangles != s->dev.n_triangles)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: n_triangles is " + std::to_string(u->n_triangles) + ", the scene has " +
-                                                std::to_string(s->dev.n_triangles));
+        return rt::fail(RT_ERR_INVALID_ARG, fn + ": n_triangles is " + std::to_string(u->n_triangles) + ", the scene has " + std::to_string(s->dev.n_triangles));
     if (s->live_accums)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: the scene has " + std::to_string(s->live_accums) +
+        return rt::fail(RT_ERR_INVALID_ARG, fn + ": the scene has " + std::to_string(s->live_accums) +
                                                 " live accumulator(s), whose sums are of the old geometry: destroy them first");
+    return RT_OK;
+}
+// ... of the arrays' contents: the host loops here, k_update_scan's findings for device arrays (the same two refusals in the same order)
+int refuse_material(const std::string &fn) { return rt::fail(RT_ERR_INVALID_ARG, fn + ": material id out of range"); }
+int refuse_non_finite(const std::string &fn, size_t triangle) {
+    return rt::fail(RT_ERR_INVALID_ARG, fn + ": non-finite vertex position (triangle " + std::to_string(triangle) + ")");
+}
+int check_data(const rt_scene *s, const rt_geometry_update *u, const std::string &fn) {
     const size_t n_mats = s->prep->mats.size();
     for (uint32_t i = 0; i < u->n_triangles; ++i)
         if (u->material_ids[i] >= n_mats)
-            return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: material id out of range");
+            return refuse_material(fn);
     for (size_t i = 0; i < (size_t)u->n_triangles * 9; ++i) // as rt_create: no builder has an answer for NaN or infinity
         if (!std::isfinite(u->positions[i]))
-            return rt::fail(RT_ERR_INVALID_ARG, "rt_update_geometry: non-finite vertex position (triangle " + std::to_string(i / 9) + ")");
-    if (u->mode == RT_UPDATE_REFIT && !(s->prep->build_flags & RT_BUILD_WIDE))
-        return rt::fail(RT_ERR_UNSUPPORTED, "rt_update_geometry: RT_UPDATE_REFIT needs a scene built with RT_BUILD_WIDE (a refitted binary tree is "
-                                            "not the reference's topology): use RT_UPDATE_REBUILD");
+            return refuse_non_finite(fn, i / 9);
     return RT_OK;
 }
+// ... and of the mode against the scene
+bool check_mode_ok(const rt_scene *s, const rt_geometry_update *u) { return !(u->mode == RT_UPDATE_REFIT && !(s->prep->build_flags & RT_BUILD_WIDE)); }
+int check_mode(const rt_scene *s, const rt_geometry_update *u, const std::string &fn) {
+    if (!check_mode_ok(s, u))
+        return rt::fail(RT_ERR_UNSUPPORTED, fn + ": RT_UPDATE_REFIT needs a scene built with RT_BUILD_WIDE (a refitted binary tree is "
+                                                 "not the reference's topology): use RT_UPDATE_REBUILD");
+    return RT_OK;
+}
+
+const std::string FN_HOST = "rt_update_geometry", FN_DEVICE = "rt_update_geometry_device";
 
 // what the geometry half reads of a descriptor: the new arrays and how the scene asked to be built
 rt_scene_desc geometry_desc(const rt_scene *s, const rt_geometry_update *u) {
@@ -79,16 +107,15 @@ void free_list(std::vector<void *> &v) {
     v.clear();
 }
 
-int rebuild(rt_scene *s, const rt_scene_desc &d) {
+// The new buffers from a prepared geometry half, beside the live ones; then swap and free. `arrays`: see rt::upload_geometry.
+int rebuild_from(rt_scene *s, const rt_scene_desc &d, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::DeviceArrays *arrays, const std::string &fn) {
     const rt::PreparedScene &P = *s->prep;
-    auto G = std::make_shared<rt::PreparedGeometry>();
-    rt::prepare_geometry(&d, emissive_materials(P), P.wide_cost_node, P.wide_cost_tri, *G);
-    // the new buffers are built beside the live ones: a refusal below leaves the scene as it was
+    // a refusal below leaves the scene as it was
     rt::GeometryOnDevice g;
-    int rc = rt::upload_geometry(s, &d, P, *G, g);
+    int rc = rt::upload_geometry(s, &d, P, *G, g, arrays);
     hipError_t se = rc == RT_OK ? hipDeviceSynchronize() : hipSuccess; // uploads went through the null stream
     if (rc == RT_OK && se != hipSuccess)
-        rc = rt::fail(RT_ERR_HIP, std::string("rt_update_geometry: ") + hipGetErrorString(se));
+        rc = rt::fail(RT_ERR_HIP, fn + ": " + hipGetErrorString(se));
     if (rc != RT_OK) {
         g.free_all();
         return rc;
@@ -102,9 +129,19 @@ int rebuild(rt_scene *s, const rt_scene_desc &d) {
     return RT_OK;
 }
 
+int rebuild(rt_scene *s, const rt_scene_desc &d, const std::string &fn) {
+    const rt::PreparedScene &P = *s->prep;
+    auto G = std::make_shared<rt::PreparedGeometry>();
+    rt::prepare_geometry(&d, emissive_materials(P), P.wide_cost_node, P.wide_cost_tri, *G);
+    return rebuild_from(s, d, G, nullptr, fn);
+}
+
+// The refit proper, from arrays on the device and the light half prepared on the host: `in` has the five arrays and the bounds of their
+// vertices, `G` the light tree and its records. Frees nothing of `in`.
+int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::RefitInput &in, const std::string &fn);
+
 int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
     const rt::PreparedScene &P = *s->prep;
-    DevScene &D = s->dev;
     if (u->n_triangles == 0)
         return RT_OK;
     // ---- host: the light tree and its records, as in REBUILD (the light set follows the new material ids)
@@ -119,9 +156,15 @@ int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
         rt::RefitInput &in;
         ~FreeInput() { in.free_all(); }
     } free_input{in};
+    return refit_from(s, G, in, FN_HOST);
+}
+
+int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::RefitInput &in, const std::string &fn) {
+    DevScene &D = s->dev;
+    const char *what = "";
     const WideGrid grid = rt::make_wide_grid(in.lo, in.hi);
     if (D.scene.n_wide != 0u && !rt::wide_grid_in_range(grid))
-        return rt::fail(RT_ERR_UNSUPPORTED, "rt_update_geometry: the new extent is outside the 8-wide tree's exponent range (2^-52 .. 2^52)");
+        return rt::fail(RT_ERR_UNSUPPORTED, fn + ": the new extent is outside the 8-wide tree's exponent range (2^-52 .. 2^52)");
     rt::GeometryOnDevice lg; // only its light half is filled
     auto upload_lights = [&]() -> int {
         auto up = [&](const void *src, size_t bytes, const void **dst) -> int {
@@ -150,12 +193,14 @@ int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
         return rc;
     }
     // ---- device, part 2: records and nodes in place (its scratch is allocated first: RT_ERR_OOM still leaves the scene as it was)
+    double levels_ms = 0;
+    const auto t_refit = std::chrono::steady_clock::now();
     if (hipError_t e = rt::refit_wide_device(in, const_cast<DevTri *>(D.scene.tris), const_cast<DevAttr *>(D.attrs), D.scene.n_tris, const_cast<uint4_pod *>(D.scene.wide),
-                                             D.scene.n_units, D.scene.n_wide, grid, s->stream, &what);
+                                             D.scene.n_units, D.scene.n_wide, grid, s->stream, &what, &levels_ms);
         e != hipSuccess) {
         (void)hipStreamSynchronize(s->stream);
         lg.free_all();
-        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_update_geometry: ") + what + ": " + hipGetErrorString(e));
+        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, fn + ": " + what + ": " + hipGetErrorString(e));
     }
     // ---- host: what the launches read of the tree besides the blob
     const rt::FlatBvh &f = G->flat[1];
@@ -176,23 +221,149 @@ int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
     D.scene.grid = grid;
     for (int k = 0; k < 3; ++k)
         rt::sort_bounds_axis(in.lo[k], in.hi[k], D.bounds_lo[k], D.bounds_inv[k]);
+    s->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_refit).count();
+    s->refit_levels_ms = levels_ms;
     s->geo = G; // (its host_bvh[0] / wide are empty: the tree the wide one was collapsed from no longer describes the scene)
     s->refitted = true;
     return RT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ arrays that are on the device already
+// "device memory of the scene's GPU": first and last byte of each array, by hipPointerGetAttributes (an unregistered host pointer is an error
+// or hipMemoryTypeUnregistered, depending on the runtime; pinned host memory is hipMemoryTypeHost; both are refused before any launch)
+int check_device_pointers(const rt_scene *s, const rt_geometry_update *u) {
+    const size_t n = u->n_triangles;
+    const struct {
+        const void *p;
+        size_t bytes;
+    } arrays[5] = {{u->positions, 36 * n}, {u->normals, 36 * n}, {u->texcoords, 24 * n}, {u->tangents, 36 * n}, {u->material_ids, 4 * n}};
+    for (const auto &a : arrays)
+        for (const char *q : {(const char *)a.p, (const char *)a.p + a.bytes - 1}) {
+            hipPointerAttribute_t at{};
+            const hipError_t e = hipPointerGetAttributes(&at, q);
+            if (e != hipSuccess)
+                (void)hipGetLastError(); // "not a pointer HIP knows" is an answer, not a failure of the library
+            if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != s->device)
+                return rt::fail(RT_ERR_INVALID_ARG, FN_DEVICE + ": a geometry array is not device memory of the scene's GPU (device " + std::to_string(s->device) + ")");
+        }
+    return RT_OK;
+}
+
+// the light half of a PreparedGeometry from the scan's compacted lights (rt::prepare_lights states why the tree is the host path's)
+int lights_from_scan(const rt::UpdateScan &scan, uint32_t n, rt::PreparedGeometry &G) {
+    const size_t nl = scan.light_prims.size();
+    for (size_t k = 0; k < nl; ++k) // ascending and in range, or the arrays were written during the call
+        if (scan.light_prims[k] >= n || (k && scan.light_prims[k] <= scan.light_prims[k - 1]))
+            return rt::fail(RT_ERR_INVALID_ARG, FN_DEVICE + ": the arrays changed during the call (they must be idle on entry)");
+    std::vector<uint32_t> all(nl);
+    for (size_t k = 0; k < nl; ++k)
+        all[k] = (uint32_t)k;
+    // (a scene without lights still has a light tree with a root: build_bvh is root-less only for a scene without triangles)
+    rt::prepare_lights(scan.light_pos.data(), n == 0 ? 0u : (uint32_t)std::max<size_t>(nl, 1), all, scan.light_prims.data(), G);
+    return RT_OK;
+}
+
+// REBUILD where a build reads the arrays on the host (the reference-topology builds; the host collapse of a wide tree): one copy to the
+// host, then the host path as it is
+int rebuild_staged(rt_scene *s, const rt_geometry_update *u) {
+    const size_t n = u->n_triangles;
+    std::vector<float> pos(9 * n), nrm(9 * n), uv(6 * n), tan(9 * n);
+    std::vector<uint32_t> mat(n);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(pos.data(), u->positions, 36 * n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(nrm.data(), u->normals, 36 * n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(uv.data(), u->texcoords, 24 * n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(tan.data(), u->tangents, 36 * n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(mat.data(), u->material_ids, 4 * n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    rt_geometry_update h = *u;
+    h.positions = pos.data(), h.normals = nrm.data(), h.texcoords = uv.data(), h.tangents = tan.data(), h.material_ids = mat.data();
+    return rebuild(s, geometry_desc(s, &h), FN_DEVICE);
+}
+
 } // namespace
 
 extern "C" int rt_update_geometry(rt_scene *s, const rt_geometry_update *u) {
-    if (int rc = check_update(s, u); rc != RT_OK) // before any HIP call
+    int rc; // before any HIP call
+    if ((rc = check_struct(u, FN_HOST, false)) != RT_OK || (rc = check_scene(s, u, FN_HOST)) != RT_OK || (rc = check_data(s, u, FN_HOST)) != RT_OK ||
+        (rc = check_mode(s, u, FN_HOST)) != RT_OK)
         return rc;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream)); // (every entry point leaves it idle: this costs nothing and says so)
     const rt_scene_desc d = geometry_desc(s, u);
-    const int rc = u->mode == RT_UPDATE_REFIT ? refit(s, u, d) : rebuild(s, d);
+    rc = u->mode == RT_UPDATE_REFIT ? refit(s, u, d) : rebuild(s, d, FN_HOST);
     if (rc == RT_OK) {
         s->pkt = rt::PacketPolicy{};   // measured on the old tree
         s->rebuilt_bvh = rt::HostBvh{}; // reconstructed from the old device tree
+    }
+    return rc;
+}
+
+extern "C" int rt_refit_times(const rt_scene *s, double *refit_ms, double *levels_ms) {
+    if (!s || !refit_ms || !levels_ms)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_refit_times: null argument");
+    if (s->group)
+        return rt::fail(RT_ERR_UNSUPPORTED, "rt_refit_times: multi-GPU scenes cannot be updated");
+    *refit_ms = s->refit_ms;
+    *levels_ms = s->refit_levels_ms;
+    return RT_OK;
+}
+
+extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *u) {
+    int rc; // before any HIP call
+    if ((rc = check_struct(u, FN_DEVICE, true)) != RT_OK || (rc = check_scene(s, u, FN_DEVICE)) != RT_OK)
+        return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t n = u->n_triangles;
+    if (n && (rc = check_device_pointers(s, u)) != RT_OK) // before any launch
+        return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const rt::PreparedScene &P = *s->prep;
+    const bool dev_build = n > 0 && (P.build_flags & RT_BUILD_DEVICE_LBVH), wide_build = n > 0 && (P.build_flags & RT_BUILD_WIDE); // as prepare_geometry
+    const bool refit = u->mode == RT_UPDATE_REFIT;
+    // a rebuild that reads the arrays on the host: the reference-topology builds, and the host collapse of a device-built binary tree
+    const bool staged = !refit && (!dev_build || (wide_build && ((P.build_flags & RT_BUILD_WIDE_HOST_COLLAPSE) || n <= 8u)));
+    rt::DeviceArrays arrays;
+    arrays.pos = u->positions, arrays.nrm = u->normals, arrays.uv = u->texcoords, arrays.tan = u->tangents, arrays.mat = u->material_ids, arrays.n = n;
+    // ---- one pass over positions and ids: the two data-dependent refusals, the bounds, the lights (writes only its own scratch)
+    rt::UpdateScan scan;
+    const char *what = "";
+    const bool want_lights = !staged && check_mode_ok(s, u); // (a call check_mode is about to refuse needs no light list)
+    if (hipError_t e = rt::scan_update_device(arrays, emissive_materials(P), want_lights, s->stream, &scan, &what); e != hipSuccess)
+        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, FN_DEVICE + ": " + what + ": " + hipGetErrorString(e));
+    if (scan.bad_material)
+        return refuse_material(FN_DEVICE);
+    if (scan.first_non_finite != RT_NONE)
+        return refuse_non_finite(FN_DEVICE, scan.first_non_finite);
+    if ((rc = check_mode(s, u, FN_DEVICE)) != RT_OK)
+        return rc;
+    if (staged)
+        rc = rebuild_staged(s, u);
+    else if (refit && n == 0)
+        rc = RT_OK;
+    else {
+        auto G = std::make_shared<rt::PreparedGeometry>();
+        G->dev_build = dev_build, G->wide_build = wide_build; // as prepare_geometry sets them
+        if ((rc = lights_from_scan(scan, n, *G)) != RT_OK)
+            return rc;
+        if (refit) { // the caller's arrays are the refit's input: nothing is allocated or copied for them
+            rt::RefitInput in;
+            in.pos = const_cast<float *>(u->positions), in.nrm = const_cast<float *>(u->normals), in.uv = const_cast<float *>(u->texcoords);
+            in.tan = const_cast<float *>(u->tangents), in.mat = const_cast<uint32_t *>(u->material_ids), in.n = n;
+            std::memcpy(in.lo, scan.lo, 12);
+            std::memcpy(in.hi, scan.hi, 12);
+            rc = refit_from(s, G, in, FN_DEVICE);
+        } else { // the device build reads them where they are
+            rt_geometry_update none = *u; // (no host code may follow these five pointers)
+            none.positions = none.normals = none.texcoords = none.tangents = nullptr;
+            none.material_ids = nullptr;
+            rc = rebuild_from(s, geometry_desc(s, &none), G, &arrays, FN_DEVICE);
+        }
+    }
+    if (rc == RT_OK) {
+        s->pkt = rt::PacketPolicy{};
+        s->rebuilt_bvh = rt::HostBvh{};
     }
     return rc;
 }

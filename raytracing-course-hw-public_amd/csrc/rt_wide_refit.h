@@ -24,8 +24,9 @@ hipError_t refit_upload(const rt_geometry_update *upd, hipStream_t stream, Refit
 // by level: exact boxes by min / max, origin / exponents / planes by the builders' rule on `grid` (wide_grid.h), the refreshed triangle
 // records copied behind their nodes. The topology words (group bases, slot states, DevTri::pad) are read, never written. Blocking; its
 // scratch (6 floats per node and per triangle, two words per node) is freed before it returns. hipErrorOutOfMemory leaves every buffer
-// as it was: the scratch is allocated before the first write.
+// as it was: the scratch is allocated before the first write. `levels_ms` (optional): wall time of the top-down level pass, k_refit_level and
+// its one host read per level — the part that depends on the topology alone.
 hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs, uint32_t n_tris, uint4_pod *blob, uint32_t n_units, uint32_t n_wide,
-                             const WideGrid &grid, hipStream_t stream, const char **err);
+                             const WideGrid &grid, hipStream_t stream, const char **err, double *levels_ms = nullptr);
 
 } // namespace rt

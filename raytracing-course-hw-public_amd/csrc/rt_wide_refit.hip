@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <vector>
 
 #include "rt_build_dev.h"
@@ -280,7 +281,9 @@ hipError_t refit_upload(const rt_geometry_update *upd, hipStream_t stream, Refit
 }
 
 hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs, uint32_t n_tris, uint4_pod *blob, uint32_t n_units, uint32_t n_wide,
-                             const WideGrid &grid, hipStream_t stream, const char **err) {
+                             const WideGrid &grid, hipStream_t stream, const char **err, double *levels_ms) {
+    if (levels_ms)
+        *levels_ms = 0;
     if (n_tris == 0 || n_wide == 0)
         return hipSuccess;
     Scratch tmp;
@@ -300,6 +303,7 @@ hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs,
     REFIT_TRY(hipMemcpyAsync(A.node_unit, init + 2, 4, hipMemcpyHostToDevice, stream));
     REFIT_TRY(hipStreamSynchronize(stream)); // `init` is a local
     // ---- levels, top down (reads the blob only)
+    const auto t_levels = std::chrono::steady_clock::now();
     std::vector<uint32_t> level_first{0u}, level_count{1u};
     for (;;) {
         A.first = level_first.back(), A.count = level_count.back();
@@ -323,6 +327,8 @@ hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs,
             *err = "wide refit: the packed tree is inconsistent";
         return hipErrorUnknown;
     }
+    if (levels_ms)
+        *levels_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_levels).count();
     // ---- records, then nodes bottom up
     REFIT_TRY(RT_LAUNCH_CHECKED(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, A));
     for (size_t l = level_first.size(); l-- > 0;) {
