@@ -36,6 +36,10 @@ _PROTOS = {
     "rto_cast_rays_brute": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_float_p, C.c_int]),
     "rto_trace_pixel": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), C.c_uint32, C.c_uint32, _abi.c_float_p, _abi.c_u32_p, _abi.c_u32_p]),
     "rto_pixel_samples": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), _abi.c_u32_p, C.c_uint32, _abi.c_float_p, C.c_int]),
+    "rto_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), C.c_void_p, C.c_uint32, _abi.c_float_p, C.POINTER(_abi.RtStats), C.c_int]),
+    "rto_shade_census": (C.c_int, [C.c_void_p, C.POINTER(_abi.RtParams), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_int]),
+    "rto_shade_slot_count": (C.c_uint32, []),
+    "rto_shade_slot_name": (C.c_char_p, [C.c_uint32]),
     "rto_light_pdf": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_walk_census": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_u32_p]),
     "rto_bg_at": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
@@ -53,6 +57,20 @@ _PROTOS = {
 }
 
 
+# The shade census' slots, in the order of RTO_SHADE_SLOTS in rt_oracle.cpp (lib() checks that the two tables agree). tex_*: Texture::sample's
+# footprint kinds, once for lookups with gamma and once without; surf_*: to_intersection_info; shade_* / light_*: shade; vndf_* / local_x_* /
+# brdf_* / spec_*: vndf_sample, vndf_pdf and the BRDF; trace_*: trace_ray; sanitize_*: sanitize_nans.
+_TEX_KINDS = ("tex_1x1", "tex_inside", "tex_x1_wraps", "tex_y1_wraps", "tex_u_up_inside", "tex_u_up_last_row", "tex_v_up", "tex_both_up", "tex_w1_x1_is_2")
+SHADE_SLOTS = tuple(f"{k}_gamma" for k in _TEX_KINDS) + tuple(f"{k}_linear" for k in _TEX_KINDS) + (
+    "surf_inside", "surf_outside", "surf_smooth_flipped", "surf_smooth_kept", "surf_shading_nan", "surf_shading_finite", "surf_analytic", "surf_triangle",
+    "shade_alpha_pass", "shade_alpha_scatter", "shade_vndf", "shade_cosine_no_lights", "shade_mix_cosine", "shade_mix_light",
+    "light_folded", "light_not_folded", "shade_nan_dir_exit", "shade_dir_finite", "shade_p_lt_eps_exit", "shade_p_ok", "shade_scl_zero_exit", "shade_push",
+    "vndf_lensq_pos", "vndf_lensq_zero", "local_x_arm_x", "local_x_arm_y", "local_x_arm_z", "vndf_pdf_vdn_le_0", "vndf_pdf_vdn_pos",
+    "brdf_metallic_0", "brdf_metallic_1", "brdf_metallic_between", "brdf_rough_clamped", "brdf_rough_kept",
+    "spec_ndh_zero", "spec_ndh_one", "spec_hdo_zero", "spec_hdo_one", "spec_hdi_zero", "spec_hdi_one",
+    "trace_miss_background", "trace_depth_exhausted", "sanitize_x", "sanitize_y", "sanitize_z")
+
+
 def build() -> None:
     subprocess.check_call(["make", "-C", _HERE, "all"], stdout=subprocess.DEVNULL)
 
@@ -64,6 +82,8 @@ def lib() -> C.CDLL:
             build()
         _lib = C.CDLL(LIB_PATH)
         _abi.bind(_lib, _PROTOS)
+        names = tuple(_lib.rto_shade_slot_name(i).decode() for i in range(_lib.rto_shade_slot_count()))
+        assert names == SHADE_SLOTS, "oracle.SHADE_SLOTS and RTO_SHADE_SLOTS (rt_oracle.cpp) differ"
     return _lib
 
 
@@ -74,6 +94,19 @@ def _check(code: int) -> None:
 
 def have_reference_build() -> bool:
     return os.path.exists(REF_BINARY) and os.path.exists(REF_PROBE)
+
+
+def _pack_rays(rays, stream=None, first_sample=None):
+    """RAY_DTYPE records: a packed array as it is, an (n, 6) float array with `stream` (default: the index) and `first_sample` (default 0)."""
+    if isinstance(rays, np.ndarray) and rays.dtype == _abi.RAY_DTYPE:
+        assert stream is None and first_sample is None, "packed rays carry their own stream / first_sample"
+        return np.ascontiguousarray(rays).reshape(-1)
+    od = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    out = np.zeros(od.shape[0], dtype=_abi.RAY_DTYPE)
+    out["origin"], out["dir"] = od[:, :3], od[:, 3:]
+    out["stream"] = np.arange(od.shape[0], dtype=np.uint32) if stream is None else np.asarray(stream, dtype=np.uint32).reshape(-1)
+    out["first_sample"] = 0 if first_sample is None else np.asarray(first_sample, dtype=np.uint32).reshape(-1)
+    return out
 
 
 class OracleScene:
@@ -163,6 +196,35 @@ class OracleScene:
         _check(lib().rto_pixel_samples(self._h, C.byref(p), _abi.u32ptr(pixels), len(pixels), _abi.fptr(out), max(1, int(threads))))
         return out
 
+    def trace_rays(self, rays, samples, seed=0, threads=None, stream=None, first_sample=None):
+        """rt_render_rays' values before the fold (include/rt_abi.h, "The rule, operation by operation"): for ray r and sample s < samples,
+        sanitize_nans(trace_ray(r, ray_depth)) seeded from (seed, r.stream, r.first_sample + s) after two discarded draws. `rays`: RAY_DTYPE
+        records, or an (n, 6) float array with `stream` / `first_sample` arrays (by default stream = index, first_sample = 0). Returns ((n, samples, 3) float32, the event counters as run_raytracer returns them). `threads`: as cast_rays_brute."""
+        packed = _pack_rays(rays, stream, first_sample)
+        if threads is None:
+            threads = min(16, int(os.environ.get("OMP_NUM_THREADS") or 16))
+        p = _abi.RtParams(0, 0, int(samples), _abi.RT_RNG_DEVICE, int(seed), 0, 1, 0, 0)
+        st = _abi.RtStats()
+        out = np.zeros((len(packed), int(samples), 3), dtype=np.float32)
+        _check(lib().rto_trace_rays(self._h, C.byref(p), packed.ctypes.data_as(C.c_void_p), len(packed), _abi.fptr(out), C.byref(st), max(1, int(threads))))
+        return out, st.as_dict()
+
+    def _census(self, p, packed):
+        counts = (C.c_uint64 * len(SHADE_SLOTS))()
+        ptr, n = (packed.ctypes.data_as(C.c_void_p), len(packed)) if packed is not None else (None, 0)
+        _check(lib().rto_shade_census(self._h, C.byref(p), ptr, n, counts, min(16, int(os.environ.get("OMP_NUM_THREADS") or 16))))
+        return {name: int(counts[i]) for i, name in enumerate(SHADE_SLOTS)}
+
+    def shade_census(self, rays, samples, seed=0, stream=None, first_sample=None):
+        """{slot name: events} over the samples trace_rays(rays, samples, seed) traces: how often each side of each branch of the shading
+        path (SHADE_SLOTS) is taken. A replay that changes and returns nothing else."""
+        packed = _pack_rays(rays, stream, first_sample)
+        return self._census(_abi.RtParams(0, 0, int(samples), _abi.RT_RNG_DEVICE, int(seed), 0, 1, 0, 0), packed)
+
+    def shade_census_render(self, width, height, samples, seed=0, rng_mode=_abi.RT_RNG_DEVICE):
+        """The same census over the samples of run_raytracer(width, height, samples, rng_mode, seed)."""
+        return self._census(_abi.RtParams(width, height, samples, rng_mode, seed, 0, 1, 0, 0), None)
+
     def light_pdf(self, rays):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
         out = np.zeros(rays.shape[0], dtype=np.float32)
@@ -194,6 +256,25 @@ class OracleScene:
         order = np.zeros(no.value, dtype=np.uint32)
         _check(lib().rto_bvh_info(self._h, which, C.byref(nn), C.byref(no), C.byref(root), _abi.u32ptr(nodes), _abi.u32ptr(order)))
         return {"root": root.value, "nodes": nodes, "order": order}
+
+
+def fold_outputs(per_sample, rays_per_output=1):
+    """rt_render_rays' output rule in float32 (render_pixel's loop, raytracer.h:618-627): `per_sample` is (n_rays, K, 3), or a sequence of
+    equal-shaped arrays to be added in that order; output j starts from +0.0, adds the values of rays j*G .. j*G + G - 1 in that order, each
+    ray's K samples in sample order, and is divided by (float)(G * K). Returns (n_rays / G, 3), or the sequence's element shape."""
+    if isinstance(per_sample, (list, tuple)):
+        values = [np.asarray(v, dtype=np.float32) for v in per_sample]
+    else:
+        a = np.asarray(per_sample, dtype=np.float32)
+        n, k = a.shape[0], a.shape[1]
+        g = max(1, int(rays_per_output))
+        assert n % g == 0
+        a = a.reshape(n // g, g * k, 3)
+        values = [a[:, i] for i in range(g * k)]
+    acc = np.zeros_like(values[0], dtype=np.float32)
+    for v in values:
+        acc = (acc + v).astype(np.float32)
+    return (acc / np.float32(len(values))).astype(np.float32)
 
 
 def tonemap(fb):

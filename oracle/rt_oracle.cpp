@@ -133,8 +133,69 @@ inline V2 interop(V2 uv, const V2 *vals) {
     return {vals[0].x * w + vals[1].x * uv.x + vals[2].x * uv.y, vals[0].y * w + vals[1].y * uv.x + vals[2].y * uv.y};
 }
 
+// ---- shade census: one slot per side of every branch of the shading path (rto_shade_census; mirrored by SHADE_SLOTS in oracle.py) ---------
+// Texture::sample's nine footprint kinds come twice: first for a lookup with gamma (colour, emissive, environment), then without (normal,
+// metallic-roughness); slot = kind + (gamma ? 0 : TEX_KINDS).
+#define RTO_SHADE_SLOTS(X)                                                                                                                    \
+    X(tex_1x1_gamma) X(tex_inside_gamma) X(tex_x1_wraps_gamma) X(tex_y1_wraps_gamma) X(tex_u_up_inside_gamma) X(tex_u_up_last_row_gamma)       \
+    X(tex_v_up_gamma) X(tex_both_up_gamma) X(tex_w1_x1_is_2_gamma)                                                                            \
+    X(tex_1x1_linear) X(tex_inside_linear) X(tex_x1_wraps_linear) X(tex_y1_wraps_linear) X(tex_u_up_inside_linear) X(tex_u_up_last_row_linear) \
+    X(tex_v_up_linear) X(tex_both_up_linear) X(tex_w1_x1_is_2_linear)                                                                         \
+    X(surf_inside) X(surf_outside) X(surf_smooth_flipped) X(surf_smooth_kept) X(surf_shading_nan) X(surf_shading_finite) X(surf_analytic)     \
+    X(surf_triangle)                                                                                                                          \
+    X(shade_alpha_pass) X(shade_alpha_scatter) X(shade_vndf) X(shade_cosine_no_lights) X(shade_mix_cosine) X(shade_mix_light)                 \
+    X(light_folded) X(light_not_folded) X(shade_nan_dir_exit) X(shade_dir_finite) X(shade_p_lt_eps_exit) X(shade_p_ok)                        \
+    X(shade_scl_zero_exit) X(shade_push)                                                                                                      \
+    X(vndf_lensq_pos) X(vndf_lensq_zero) X(local_x_arm_x) X(local_x_arm_y) X(local_x_arm_z) X(vndf_pdf_vdn_le_0) X(vndf_pdf_vdn_pos)          \
+    X(brdf_metallic_0) X(brdf_metallic_1) X(brdf_metallic_between) X(brdf_rough_clamped) X(brdf_rough_kept)                                   \
+    X(spec_ndh_zero) X(spec_ndh_one) X(spec_hdo_zero) X(spec_hdo_one) X(spec_hdi_zero) X(spec_hdi_one)                                         \
+    X(trace_miss_background) X(trace_depth_exhausted) X(sanitize_x) X(sanitize_y) X(sanitize_z)
+enum ShadeSlot {
+#define X(name) S_##name,
+    RTO_SHADE_SLOTS(X)
+#undef X
+        SHADE_SLOT_COUNT
+};
+const char *const SHADE_SLOT_NAMES[SHADE_SLOT_COUNT] = {
+#define X(name) #name,
+    RTO_SHADE_SLOTS(X)
+#undef X
+};
+constexpr int TEX_KINDS = S_tex_1x1_linear - S_tex_1x1_gamma;
+
+struct Counters {
+    uint64_t casts = 0, nodes = 0, box_tests = 0, tri_tests = 0, shaded = 0;
+    uint64_t lq = 0, lnodes = 0, lbox = 0, ltri = 0, lhits = 0, texels = 0, samples = 0;
+    // rto_walk_census only (never summed by add): with `census` set the two recursions below keep the number of deferred far siblings
+    // pending right now and its maximum. A sibling is pending from the moment both children of its parent were hit until the walk
+    // enters it or prunes it: what a traversal without recursion has to hold on a stack.
+    bool census = false;
+    uint32_t pending = 0, max_pending = 0;
+    // rto_shade_census only (never summed by add, never read by the integrator): with `shade` set, every branch listed in RTO_SHADE_SLOTS adds one
+    // to its slot each time a sample takes it. Which side of which branch a set of rays reaches is then a fact, not an assumption.
+    uint64_t *shade = nullptr;
+    void tick(int slot) {
+        if (shade)
+            shade[slot]++;
+    }
+    void defer() { max_pending = std::max(max_pending, ++pending); }
+    void add(const Counters &o) {
+        casts += o.casts;
+        nodes += o.nodes;
+        box_tests += o.box_tests;
+        tri_tests += o.tri_tests;
+        shaded += o.shaded;
+        lq += o.lq;
+        lnodes += o.lnodes;
+        lbox += o.lbox;
+        ltri += o.ltri;
+        lhits += o.lhits;
+        texels += o.texels;
+        samples += o.samples;
+    }
+};
+
 // ---- textures (geometry.h:517-599) ---------------------------------------------------------------------
-struct Counters;
 inline float wrap_repeat(float x) { return std::fmod(std::fmod(x, 1) + 1, 1); } // double fmod, geometry.h:517-519
 inline int mod_inc(int x, int mod) { return x == mod - 1 ? 0 : x + 1; }         // :521-523
 inline C4 rgba_apply_gamma(C4 a, float gamma) {                                 // :525-527
@@ -143,22 +204,45 @@ inline C4 rgba_apply_gamma(C4 a, float gamma) {                                 
 struct Texture {
     unsigned width = 1, height = 1;
     std::vector<C4> data{{1, 1, 1, 1}};
-    C4 sample(V2 xy, float gamma, uint64_t &texel_fetches) const { // :545-575
-        if (data.size() == 1)
+    C4 sample(V2 xy, float gamma, Counters &c) const { // :545-575
+        const int g = gamma != 1.0f ? 0 : TEX_KINDS; // census: which half of the texture slots
+        if (data.size() == 1) {
+            c.tick(S_tex_1x1_gamma + g);
             return data[0];
+        }
         float tx = wrap_repeat(xy.x) * width;
         float ty = wrap_repeat(xy.y) * height;
         int px = tx;
         int py = ty;
         float dx = tx - px;
         float dy = ty - py;
+        if (c.shade) { // census only: name the footprint; nothing below reads it
+            const int w = (int)width, h = (int)height;
+            const bool u_up = px >= w, v_up = py >= h; // wrap_repeat rounded up to 1.0f
+            if (u_up && v_up)
+                c.tick(S_tex_both_up_gamma + g);
+            else if (u_up)
+                c.tick((py + 1 < h ? S_tex_u_up_inside_gamma : S_tex_u_up_last_row_gamma) + g);
+            else if (v_up)
+                c.tick(S_tex_v_up_gamma + g);
+            else {
+                if (px == w - 1)
+                    c.tick(S_tex_x1_wraps_gamma + g);
+                if (py == h - 1)
+                    c.tick(S_tex_y1_wraps_gamma + g);
+                if (px != w - 1 && py != h - 1)
+                    c.tick(S_tex_inside_gamma + g);
+            }
+            if (w == 1 && px == 1) // mod_inc(1, 1) == 2
+                c.tick(S_tex_w1_x1_is_2_gamma + g);
+        }
         const size_t last = data.size() - 1; // memory-safety clamp only (the reference reads out of bounds here)
         auto at = [&](int x, int y) { return data[std::min<size_t>((size_t)(x + y * (int)width), last)]; };
         C4 p00 = rgba_apply_gamma(at(px, py), gamma);
         C4 p01 = rgba_apply_gamma(at(px, mod_inc(py, height)), gamma);
         C4 p10 = rgba_apply_gamma(at(mod_inc(px, width), py), gamma);
         C4 p11 = rgba_apply_gamma(at(mod_inc(px, width), mod_inc(py, height)), gamma);
-        texel_fetches += 4;
+        c.texels += 4;
         return (1 - dx) * ((1 - dy) * p00 + dy * p01) + dx * ((1 - dy) * p10 + dy * p11);
     }
 };
@@ -182,31 +266,6 @@ struct Object { // geometry.h:633-659
 struct BVHNode {
     Aabb box;
     uint32_t left, right, obj_begin, obj_end;
-};
-
-struct Counters {
-    uint64_t casts = 0, nodes = 0, box_tests = 0, tri_tests = 0, shaded = 0;
-    uint64_t lq = 0, lnodes = 0, lbox = 0, ltri = 0, lhits = 0, texels = 0, samples = 0;
-    // rto_walk_census only (never summed by add): with `census` set the two recursions below keep the number of deferred far siblings
-    // pending right now and its maximum. A sibling is pending from the moment both children of its parent were hit until the walk
-    // enters it or prunes it: what a traversal without recursion has to hold on a stack.
-    bool census = false;
-    uint32_t pending = 0, max_pending = 0;
-    void defer() { max_pending = std::max(max_pending, ++pending); }
-    void add(const Counters &o) {
-        casts += o.casts;
-        nodes += o.nodes;
-        box_tests += o.box_tests;
-        tri_tests += o.tri_tests;
-        shaded += o.shaded;
-        lq += o.lq;
-        lnodes += o.lnodes;
-        lbox += o.lbox;
-        ltri += o.ltri;
-        lhits += o.lhits;
-        texels += o.texels;
-        samples += o.samples;
-    }
 };
 
 struct Hit {
@@ -507,24 +566,29 @@ IntersectionInfo to_intersection_info(const rto_scene &sc, const Hit &intr, cons
     V3 normal = obj.shape.normal();
     bool is_inside = dot(normal, ray.dir) > 0;
     V3 smooth_normal = norm(interop(uv, obj.normals));
-    if (dot(normal, smooth_normal) < 0)
+    const bool flip = dot(normal, smooth_normal) < 0;
+    if (flip)
         smooth_normal = -smooth_normal;
+    c.tick(is_inside ? S_surf_inside : S_surf_outside);
+    c.tick(flip ? S_surf_smooth_flipped : S_surf_smooth_kept);
+    c.tick(S_surf_triangle);
     V2 tex_coord = interop(uv, obj.tex_coords);
     V3 tangent = norm(interop(uv, obj.tangents));
     V3 bitangent = crs(smooth_normal, tangent);
     // material::normal_at -> Texture::sample_normal (geometry.h:577-582, 628-630)
-    C4 nt = mat.normal_tex->sample(tex_coord, 1.0f, c.texels);
+    C4 nt = mat.normal_tex->sample(tex_coord, 1.0f, c);
     V3 u01{nt.r, nt.g, nt.b};
     V3 nres = u01 * 2 - 1;
     V3 normal_loc = norm(nres);
     V3 shading_normal = norm(transform3(normal_loc, tangent, bitangent, smooth_normal));
+    c.tick(std::isnan(shading_normal.x) || std::isnan(shading_normal.y) || std::isnan(shading_normal.z) ? S_surf_shading_nan : S_surf_shading_finite);
     // geometry.h:623-626
-    C4 mr = mat.mr_tex->sample(tex_coord, 1.0f, c.texels);
+    C4 mr = mat.mr_tex->sample(tex_coord, 1.0f, c);
     float metallic = mat.metallic * mr.b;
     float roughness = mat.roughness * mr.g;
     // geometry.h:615-621
-    C4 color = mat.color * mat.color_tex->sample(tex_coord, 2.2f, c.texels);
-    C4 em = mat.emissive_tex->sample(tex_coord, 2.2f, c.texels);
+    C4 color = mat.color * mat.color_tex->sample(tex_coord, 2.2f, c);
+    C4 em = mat.emissive_tex->sample(tex_coord, 2.2f, c);
     V3 emission = mat.emission * V3{em.r, em.g, em.b};
     c.shaded++;
     return {is_inside ? -normal : normal, is_inside ? -shading_normal : shading_normal, t, intr.obj, is_inside, color, emission,
@@ -585,14 +649,18 @@ template <class R> struct Integrator {
 
     static V3 halfway(V3 in_dir, V3 out_dir) { return norm(out_dir - in_dir); } // :131-134
     // raytracer.h:208-219
-    static V3 choose_local_x(V3 n) {
+    V3 choose_local_x(V3 n) {
         V3 res{1, 1, 1};
-        if (std::abs(n.x) > 0.5f)
+        if (std::abs(n.x) > 0.5f) {
+            c.tick(S_local_x_arm_x);
             res.x -= dot(res, n) / n.x;
-        else if (std::abs(n.y) > 0.5f)
+        } else if (std::abs(n.y) > 0.5f) {
+            c.tick(S_local_x_arm_y);
             res.y -= dot(res, n) / n.y;
-        else
+        } else {
+            c.tick(S_local_x_arm_z);
             res.z -= dot(res, n) / n.z;
+        }
         return norm(res);
     }
     // raytracer.h:140-173
@@ -603,6 +671,7 @@ template <class R> struct Integrator {
         V3 vh = norm(V3{roughness, roughness, 1} * v);
         float lensq = vh.x * vh.x + vh.y * vh.y;
         V3 T1 = lensq > 0 ? V3{-vh.y, vh.x, 0} / std::sqrt(lensq) : V3{1, 0, 0};
+        c.tick(lensq > 0 ? S_vndf_lensq_pos : S_vndf_lensq_zero);
         V3 T2 = crs(vh, T1);
         float r = std::sqrt(uniform_real(rng, 0, 1));
         float phi = 2.0f * PI_F * uniform_real(rng, 0, 1);
@@ -625,6 +694,7 @@ template <class R> struct Integrator {
         V3 nv = halfway(in_dir, dir);
         V3 n{dot(nx, nv), dot(ny, nv), dot(normal, nv)};
         float vdn = dot(v, n);
+        c.tick(vdn <= 0 ? S_vndf_pdf_vdn_le_0 : S_vndf_pdf_vdn_pos);
         if (vdn <= 0)
             return 0;
         float vx = v.x * roughness, vy = v.y * roughness;
@@ -643,6 +713,7 @@ template <class R> struct Integrator {
     V3 triangle_sample(const Tri &tr, V3 x) {
         float u = uniform_real(rng, 0, 1);
         float v = uniform_real(rng, 0, 1);
+        c.tick(u + v > 1 ? S_light_folded : S_light_not_folded);
         if (u + v > 1) {
             u = 1 - u;
             v = 1 - v;
@@ -667,9 +738,12 @@ template <class R> struct Integrator {
     bool has_lights() const { return !sc.light_bvh.objects.empty(); } // raytracer.h:449-453
     // dir_generator / mix_dist raytracer.h:378-432
     V3 dir_gen_sample(V3 x, V3 normal) {
-        if (!has_lights())
+        if (!has_lights()) {
+            c.tick(S_shade_cosine_no_lights);
             return cosine_sample(normal);
+        }
         uint32_t k = rng.below(2);
+        c.tick(k == 0 ? S_shade_mix_cosine : S_shade_mix_light);
         return k == 0 ? cosine_sample(normal) : lights_sample(x);
     }
     float dir_gen_pdf(V3 x, V3 normal, V3 dir) {
@@ -683,8 +757,11 @@ template <class R> struct Integrator {
 
     // BRDF raytracer.h:264-343
     static float heaviside(float x) { return x > 0 ? 1 : 0; }
-    static V3 specular_brdf(float alpha, V3 in_dir, V3 out_dir, V3 normal) {
+    V3 specular_brdf(float alpha, V3 in_dir, V3 out_dir, V3 normal) {
         V3 h = halfway(in_dir, out_dir);
+        c.tick(dot(normal, h) > 0 ? S_spec_ndh_one : S_spec_ndh_zero);
+        c.tick(dot(h, out_dir) > 0 ? S_spec_hdo_one : S_spec_hdo_zero);
+        c.tick(dot(h, -in_dir) > 0 ? S_spec_hdi_one : S_spec_hdi_zero);
         float d = pow2(alpha) * heaviside(dot(normal, h)) / PI_F / pow2(pow2(dot(normal, h)) * (pow2(alpha) - 1) + 1);
         float div1 = (std::abs(dot(normal, out_dir)) + std::sqrt(pow2(alpha) + (1 - pow2(alpha)) * pow2(dot(normal, out_dir))));
         float div2 = (std::abs(dot(normal, -in_dir)) + std::sqrt(pow2(alpha) + (1 - pow2(alpha)) * pow2(dot(normal, -in_dir))));
@@ -692,10 +769,17 @@ template <class R> struct Integrator {
         float res = v * d;
         return {res, res, res};
     }
-    static V3 pbr_brdf(V3 in_dir, V3 out_dir, const IntersectionInfo &ii) {
+    V3 pbr_brdf(V3 in_dir, V3 out_dir, const IntersectionInfo &ii) {
         V3 res{0, 0, 0};
         V3 base{ii.color.r, ii.color.g, ii.color.b};
         float alpha = pow2(std::max(ii.roughness, MIN_ROUGHNESS));
+        c.tick(ii.roughness < MIN_ROUGHNESS ? S_brdf_rough_clamped : S_brdf_rough_kept);
+        if (ii.metallic == 0)
+            c.tick(S_brdf_metallic_0);
+        else if (ii.metallic == 1)
+            c.tick(S_brdf_metallic_1);
+        else if (ii.metallic > 0 && ii.metallic < 1)
+            c.tick(S_brdf_metallic_between);
         if (ii.metallic < 1) { // dielectric_brdf + fresnel_mix
             V3 diffuse = base / PI_F;
             V3 spec = specular_brdf(alpha, in_dir, out_dir, ii.shading_normal);
@@ -741,6 +825,7 @@ template <class R> struct Integrator {
         if (prim >= 0) {
             const Material &mat = sc.materials[sc.prims[prim].material_id];
             c.shaded++;
+            c.tick(S_surf_analytic);
             V3 n{prim_n[0], prim_n[1], prim_n[2]};
             out = {n, n, prim_t, (uint32_t)(sc.objects.size() + prim), false, mat.color, mat.emission, mat.metallic, mat.roughness, mat.ior};
             return true;
@@ -755,18 +840,29 @@ template <class R> struct Integrator {
     // raytracer.h:555-591
     V3 shade(const Ray &ray, const IntersectionInfo &ii, unsigned max_depth) {
         V3 pos = ray.at(ii.t);
-        if (!coin(ii.color.a))
+        if (!coin(ii.color.a)) {
+            c.tick(S_shade_alpha_pass);
             return trace_ray({pos, ray.dir}, max_depth);
+        }
+        c.tick(S_shade_alpha_scatter);
         float vr = pow2(std::max(ii.roughness, MIN_ROUGHNESS));
-        V3 dir = coin(VNDF_factor) ? vndf_sample(vr, ray.dir, ii.shading_normal) : dir_gen_sample(pos, ii.normal);
-        if (std::isnan(dir.x) || std::isnan(dir.y) || std::isnan(dir.z))
+        const bool vndf = coin(VNDF_factor);
+        if (vndf)
+            c.tick(S_shade_vndf);
+        V3 dir = vndf ? vndf_sample(vr, ray.dir, ii.shading_normal) : dir_gen_sample(pos, ii.normal);
+        if (std::isnan(dir.x) || std::isnan(dir.y) || std::isnan(dir.z)) {
+            c.tick(S_shade_nan_dir_exit);
             return ii.emission;
+        }
+        c.tick(S_shade_dir_finite);
         float VNDF_p = vndf_pdf(vr, ray.dir, ii.shading_normal, dir);
         float MIS_p = dir_gen_pdf(pos, ii.normal, dir);
         float p = VNDF_factor * VNDF_p + (1 - VNDF_factor) * MIS_p;
+        c.tick(p < EPS ? S_shade_p_lt_eps_exit : S_shade_p_ok);
         if (p < EPS)
             return ii.emission;
         V3 scl = pbr_brdf(ray.dir, dir, ii) / p * std::max(0.0f, dot(dir, ii.shading_normal));
+        c.tick(len2(scl) == 0.0f ? S_shade_scl_zero_exit : S_shade_push);
         if (len2(scl) == 0.0f)
             return ii.emission;
         V3 clr = trace_ray({pos, dir}, max_depth) * scl;
@@ -777,16 +873,19 @@ template <class R> struct Integrator {
     V3 bg_at(V3 dir) {
         float x = 0.5 + 0.5 * std::atan2(dir.z, dir.x) / std::numbers::pi_v<float>;
         float y = 0.5 - std::asin(dir.y) / std::numbers::pi_v<float>;
-        C4 e = sc.bg->sample({x, y}, 2.2f, c.texels);
+        C4 e = sc.bg->sample({x, y}, 2.2f, c);
         return sc.bg_color * V3{e.r, e.g, e.b};
     }
     // raytracer.h:593-605
     V3 trace_ray(const Ray &ray, unsigned max_depth) {
-        if (max_depth == 0)
+        if (max_depth == 0) {
+            c.tick(S_trace_depth_exhausted);
             return {0, 0, 0};
+        }
         IntersectionInfo ii;
         if (cast_ray(ray, ii))
             return shade(ray, ii, max_depth - 1);
+        c.tick(S_trace_miss_background);
         return bg_at(ray.dir);
     }
     // raytracer.h:527-538
@@ -799,13 +898,19 @@ template <class R> struct Integrator {
         V3 dir = norm((2 * (x + ox) / width - 1) * tan_x * right - (2 * (y + oy) / height - 1) * tan_y * up + 1 * fwd);
         return {{sc.cam.position[0], sc.cam.position[1], sc.cam.position[2]}, dir};
     }
-    static V3 sanitize_nans(V3 v) { // raytracer.h:607-616
-        if (std::isnan(v.x))
+    V3 sanitize_nans(V3 v) { // raytracer.h:607-616
+        if (std::isnan(v.x)) {
+            c.tick(S_sanitize_x);
             v.x = 0;
-        if (std::isnan(v.y))
+        }
+        if (std::isnan(v.y)) {
+            c.tick(S_sanitize_y);
             v.y = 0;
-        if (std::isnan(v.z))
+        }
+        if (std::isnan(v.z)) {
+            c.tick(S_sanitize_z);
             v.z = 0;
+        }
         return v;
     }
 };
@@ -813,7 +918,7 @@ template <class R> struct Integrator {
 // one term of render_pixel's sum (raytracer.h:622-624): the value `res += ...` adds, from the integrator's current RNG state
 template <class R> V3 pixel_sample(Integrator<R> &it, int x, int y) {
     Ray ray = it.gen_ray(x, y);
-    return Integrator<R>::sanitize_nans(it.trace_ray(ray, it.sc.ray_depth));
+    return it.sanitize_nans(it.trace_ray(ray, it.sc.ray_depth));
 }
 
 // raytracer.h:618-627, RNG seeded per (pixel, sample) (device mode) or carried along the span (reference mode)
@@ -839,12 +944,14 @@ bool block_selected(const rt_params &p, size_t pixel) {
 }
 
 // raytracer.h:629-674
-template <class R> void run_raytracer(const rto_scene &sc, const rt_params &p, float *fb, Counters &total, int threads) {
+// `census`: SHADE_SLOT_COUNT sums of the shade census over the whole render, or nullptr (off: the default, and what every render call uses)
+template <class R> void run_raytracer(const rto_scene &sc, const rt_params &p, float *fb, Counters &total, int threads, uint64_t *census = nullptr) {
     size_t n_pix = (size_t)p.width * p.height;
     int span_count = (int)((n_pix + SPAN_SIZE - 1) / SPAN_SIZE);
     std::atomic_int next_span(0);
     std::vector<std::thread> workers;
     std::vector<Counters> per(threads);
+    std::vector<std::vector<uint64_t>> cen(threads, std::vector<uint64_t>(census ? SHADE_SLOT_COUNT : 0, 0));
     for (int w = 0; w < threads; ++w) {
         workers.emplace_back([&, w]() {
             int span;
@@ -853,6 +960,7 @@ template <class R> void run_raytracer(const rto_scene &sc, const rt_params &p, f
                 if (!block_selected(p, begin))
                     continue;
                 Integrator<R> it(sc, p.width, p.height, p.samples);
+                it.c.shade = census ? cen[w].data() : nullptr;
                 if constexpr (std::is_same_v<R, RngMinstd>)
                     rt_minstd_seed(&it.rng.g, (uint32_t)span); // RaytracerThreadContext(ctx, span) :648
                 for (size_t p_idx = begin; p_idx < end; ++p_idx) {
@@ -870,6 +978,69 @@ template <class R> void run_raytracer(const rto_scene &sc, const rt_params &p, f
         t.join();
     for (auto &c : per)
         total.add(c);
+    if (census)
+        for (auto &v : cen)
+            for (int k = 0; k < SHADE_SLOT_COUNT; ++k)
+                census[k] += v[k];
+}
+
+void fill_stats(rt_stats *stats, const Counters &c, double ms) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->samples = c.samples;
+    stats->casts = c.casts;
+    stats->nodes_visited = c.nodes;
+    stats->box_tests = c.box_tests;
+    stats->tri_tests = c.tri_tests;
+    stats->shaded_hits = c.shaded;
+    stats->light_queries = c.lq;
+    stats->light_nodes = c.lnodes;
+    stats->light_box_tests = c.lbox;
+    stats->light_tri_tests = c.ltri;
+    stats->light_hits = c.lhits;
+    stats->texel_fetches = c.texels;
+    stats->total_ms = ms;
+    stats->kernel_ms = ms;
+}
+
+// rt_render_rays' rule (include/rt_abi.h, "The rule, operation by operation") for every (ray, sample): out[(r * K + s) * 3 ..] is the value of
+// sample s of ray r. Workers take rays from a shared index; every sample reseeds, so the split changes nothing. `out` may be null (census only).
+void trace_rays(const rto_scene &sc, const rt_params &p, const rt_ray *rays, uint32_t n, float *out, Counters &total, uint64_t *census, int threads) {
+    threads = (int)std::min<uint32_t>((uint32_t)std::max(threads, 1), std::max(n, 1u));
+    std::atomic<uint32_t> next(0);
+    std::vector<std::thread> workers;
+    std::vector<Counters> per(threads);
+    std::vector<std::vector<uint64_t>> cen(threads, std::vector<uint64_t>(census ? SHADE_SLOT_COUNT : 0, 0));
+    for (int w = 0; w < threads; ++w) {
+        workers.emplace_back([&, w]() {
+            Integrator<RngXoshiro> it(sc, 1, 1, p.samples);
+            it.c.shade = census ? cen[w].data() : nullptr;
+            uint32_t i;
+            while ((i = next.fetch_add(1)) < n) {
+                const rt_ray &r = rays[i];
+                const Ray ray{{r.origin[0], r.origin[1], r.origin[2]}, {r.dir[0], r.dir[1], r.dir[2]}};
+                for (uint32_t smp = 0; smp < p.samples; ++smp) {
+                    rt_xoshiro_seed(&it.rng.g, p.seed, r.stream, r.first_sample + smp); // uint32 sum: wraps mod 2^32
+                    (void)uniform_real(it.rng, 0.0f, 1.0f);                              // gen_ray's two jitter draws, discarded
+                    (void)uniform_real(it.rng, 0.0f, 1.0f);
+                    const V3 v = it.sanitize_nans(it.trace_ray(ray, sc.ray_depth));
+                    it.c.samples++;
+                    if (out) {
+                        float *o = out + 3 * ((size_t)i * p.samples + smp);
+                        o[0] = v.x, o[1] = v.y, o[2] = v.z;
+                    }
+                }
+            }
+            per[w].add(it.c);
+        });
+    }
+    for (auto &t : workers)
+        t.join();
+    for (auto &c : per)
+        total.add(c);
+    if (census)
+        for (auto &v : cen)
+            for (int k = 0; k < SHADE_SLOT_COUNT; ++k)
+                census[k] += v[k];
 }
 
 } // namespace
@@ -978,22 +1149,52 @@ int rto_render(rto_scene *s, const rt_params *p, float *fb, rt_stats *stats, int
     else
         run_raytracer<RngXoshiro>(*s, *p, fb, c, threads);
     auto t1 = std::chrono::steady_clock::now();
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->samples = c.samples;
-        stats->casts = c.casts;
-        stats->nodes_visited = c.nodes;
-        stats->box_tests = c.box_tests;
-        stats->tri_tests = c.tri_tests;
-        stats->shaded_hits = c.shaded;
-        stats->light_queries = c.lq;
-        stats->light_nodes = c.lnodes;
-        stats->light_box_tests = c.lbox;
-        stats->light_tri_tests = c.ltri;
-        stats->light_hits = c.lhits;
-        stats->texel_fetches = c.texels;
-        stats->total_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        stats->kernel_ms = stats->total_ms;
+    if (stats)
+        fill_stats(stats, c, std::chrono::duration<double, std::milli>(t1 - t0).count());
+    return RT_OK;
+}
+
+// Radiance along caller-supplied rays, sample by sample: what rt_render_rays folds into its outputs (include/rt_abi.h). out_per_sample holds
+// n_rays * samples * 3 floats, ray-major. A scene with ray_depth == 0 writes zeros (trace_ray's first line). Only samples and seed of `p` are
+// read. threads <= 0: hardware_concurrency.
+int rto_trace_rays(rto_scene *s, const rt_params *p, const rt_ray *rays, uint32_t n_rays, float *out_per_sample, rt_stats *stats, int threads) {
+    if (!s || !p || p->samples == 0 || p->rng_mode != RT_RNG_DEVICE || (n_rays && (!rays || !out_per_sample))) {
+        g_err = "rto_trace_rays: bad arguments (device-RNG mode, samples >= 1)";
+        return RT_ERR_INVALID_ARG;
+    }
+    if (threads <= 0)
+        threads = (int)std::max(std::thread::hardware_concurrency(), 1u);
+    Counters c;
+    auto t0 = std::chrono::steady_clock::now();
+    trace_rays(*s, *p, rays, n_rays, out_per_sample, c, nullptr, threads);
+    auto t1 = std::chrono::steady_clock::now();
+    if (stats)
+        fill_stats(stats, c, std::chrono::duration<double, std::milli>(t1 - t0).count());
+    return RT_OK;
+}
+
+// Shade census: how often the samples of `rays` (rays != NULL: rto_trace_rays' samples) or of a camera render (rays == NULL: rto_render's, in
+// p->rng_mode) take each side of each branch of the shading path. counts_out: rto_shade_slot_count() sums, in the order of
+// rto_shade_slot_name. The scene is not changed and nothing else is returned: the census is a read-only replay.
+uint32_t rto_shade_slot_count(void) { return SHADE_SLOT_COUNT; }
+const char *rto_shade_slot_name(uint32_t i) { return i < SHADE_SLOT_COUNT ? SHADE_SLOT_NAMES[i] : ""; }
+int rto_shade_census(rto_scene *s, const rt_params *p, const rt_ray *rays, uint32_t n_rays, uint64_t *counts_out, int threads) {
+    if (!s || !p || !counts_out || p->samples == 0 || (rays && p->rng_mode != RT_RNG_DEVICE) || (!rays && (p->width == 0 || p->height == 0))) {
+        g_err = "rto_shade_census: bad arguments";
+        return RT_ERR_INVALID_ARG;
+    }
+    if (threads <= 0)
+        threads = (int)std::max(std::thread::hardware_concurrency(), 1u);
+    std::fill(counts_out, counts_out + SHADE_SLOT_COUNT, (uint64_t)0);
+    Counters c;
+    if (rays) {
+        trace_rays(*s, *p, rays, n_rays, nullptr, c, counts_out, threads);
+    } else if (s->ray_depth != 0) {
+        std::vector<float> fb((size_t)p->width * p->height * 3);
+        if (p->rng_mode == RT_RNG_REFERENCE)
+            run_raytracer<RngMinstd>(*s, *p, fb.data(), c, threads, counts_out);
+        else
+            run_raytracer<RngXoshiro>(*s, *p, fb.data(), c, threads, counts_out);
     }
     return RT_OK;
 }

@@ -112,15 +112,7 @@ def test_pass_splits_change_no_bit(gpu, scenes, camera_case, sort, packet):
     assert np.count_nonzero(np.any(out != 0, axis=1)) * 2 >= W3 * H3
 
 
-def _fold(values):
-    """render_pixel's loop in float32: +0.0, plus every value in order, divided by the count."""
-    acc = np.zeros_like(values[0], dtype=np.float32)
-    for v in values:
-        acc = (acc + v).astype(np.float32)
-    return (acc / np.float32(len(values))).astype(np.float32)
-
-
-def test_samples_per_ray_and_order_independence(gpu, scenes):
+def test_samples_per_ray_and_order_independence(gpu, oracle, scenes):
     """Arbitrary rays, arbitrary streams: K = 3 from first_sample a is the fold of the K = 1 results at a, a + 1, a + 2 (the sample index wraps
     mod 2^32); the position of a ray in the buffer and its neighbours change nothing; a sorted and a packet run give the same bits."""
     sc = scenes["room_textured"]
@@ -134,13 +126,13 @@ def test_samples_per_ray_and_order_independence(gpu, scenes):
     k3, st = dev.render_rays(od, stream=stream, first_sample=first, samples=3, seed=SEED)
     assert st["samples"] == 3 * n
     singles = [dev.render_rays(od, stream=stream, first_sample=first + np.uint32(s), samples=1, seed=SEED)[0] for s in range(3)]
-    assert np.array_equal(_bits(k3), _bits(_fold(singles)))
+    assert np.array_equal(_bits(k3), _bits(oracle.fold_outputs(singles)))
     assert np.count_nonzero(np.any(k3 != 0, axis=1)) * 2 >= n
     assert not np.array_equal(singles[0], singles[1])  # other samples, other radiance
     # G = 2 over the same buffer: output j is rays 2j, 2j + 1, each ray's K samples in order
     g2, _ = dev.render_rays(od[:6000], stream=stream[:6000], first_sample=first[:6000], samples=3, rays_per_output=2, seed=SEED)
     order = [singles[s][r:6000:2] for r in (0, 1) for s in range(3)]
-    assert np.array_equal(_bits(g2), _bits(_fold(order)))
+    assert np.array_equal(_bits(g2), _bits(oracle.fold_outputs(order)))
     # a shuffled buffer permutes the outputs and changes nothing else
     perm = rng.permutation(n)
     shuffled, _ = dev.render_rays(od[perm], stream=stream[perm], first_sample=first[perm], samples=3, seed=SEED)
@@ -167,7 +159,7 @@ def test_missing_rays_return_the_background(gpu, oracle, scenes):
     out, _ = dev.render_rays(od, stream=np.arange(len(od)) * 3, first_sample=np.arange(len(od)), samples=K, seed=SEED)
     bg = dev.bg_at(od[:, 3:])
     assert np.array_equal(_bits(bg), _bits(orc.bg_at(od[:, 3:])))
-    assert np.array_equal(_bits(out), _bits(_fold([bg] * K)))
+    assert np.array_equal(_bits(out), _bits(oracle.fold_outputs([bg] * K)))
     assert np.all(np.any(out != 0, axis=1))
 
 
