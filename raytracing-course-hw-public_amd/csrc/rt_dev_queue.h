@@ -37,8 +37,9 @@ DEV bool ticket_take(uint32_t *counters, uint32_t n_in, uint32_t chunk, TicketSt
 // (a refill stalls the wave on the ray loads) from its private range [q_lo, q_hi) of queue positions; a new range of `chunk` positions is taken
 // with ONE atomic when it runs dry (a single ticket word saturates near 90 M atomics/s, so tickets are taken per chunk, not per refill).
 // start(jq) begins the traversal of the ray at queue position jq in the calling lane; `exhausted` (wave-uniform): the queue is used up.
+// Returns the number of idle lanes it found: once `exhausted` no lane is started any more, so that is the wave's idle count.
 template <class START>
-DEV void ticket_refill(uint32_t *counters, uint32_t n_in, uint32_t chunk, int refill_min, bool idle, bool &exhausted, uint32_t &q_lo, uint32_t &q_hi, TicketState &tks, START start) {
+DEV int ticket_refill(uint32_t *counters, uint32_t n_in, uint32_t chunk, int refill_min, bool idle, bool &exhausted, uint32_t &q_lo, uint32_t &q_hi, TicketState &tks, START start) {
     const unsigned long long im = __ballot(idle);
     const int n_idle = __popcll(im);
     if (!exhausted && (n_idle >= refill_min || n_idle == (int)__popcll(__ballot(1)))) {
@@ -50,6 +51,7 @@ DEV void ticket_refill(uint32_t *counters, uint32_t n_in, uint32_t chunk, int re
             start(q_lo + rank);
         q_lo += (uint32_t)n_idle < avail ? (uint32_t)n_idle : avail;
     }
+    return n_idle;
 }
 // the packet kernels' census (trips, lanes served; wave-uniform), summed over the launch's waves: what the host keeps or drops a packet kernel on
 DEV void census_flush(unsigned long long *census, unsigned long long n_trips, unsigned long long n_lanes) {

@@ -34,9 +34,11 @@ DEV bool coord_in_fast_range(float c) { // 0, or 2^-37 <= |c| <= 2^40 (false for
 
 // intersect(ray, aabb, min_dst) bvh.h:137-152, reference form: IEEE division, std::min/max operand order kept by
 // explicit selects, component reductions as std::max_element / std::min_element (first extremum, geometry.h:42-50).
-DEV bool box_hit_exact(V3 bmin, V3 bmax, V3 o, V3 d, float min_dst, float &dist) {
-    V3 i1 = (bmin - o) / d;
-    V3 i2 = (bmax - o) / d;
+// Both slab tests take the box corners RELATIVE to the ray origin, a1 = bmin - o and a2 = bmax - o: two_box makes them from an absolute
+// record, or passes on what a camera-relative record holds (wf_camera_relative: each corner the same single IEEE subtraction, the same bits).
+DEV bool box_hit_exact_rel(V3 a1, V3 a2, V3 d, float min_dst, float &dist) {
+    V3 i1 = a1 / d;
+    V3 i2 = a2 / d;
     V3 mn = {rmin(i1.x, i2.x), rmin(i1.y, i2.y), rmin(i1.z, i2.z)};
     V3 mx = {rmax(i1.x, i2.x), rmax(i1.y, i2.y), rmax(i1.z, i2.z)};
     float t_min = mn.x;
@@ -60,8 +62,7 @@ DEV bool box_hit_exact(V3 bmin, V3 bmax, V3 o, V3 d, float min_dst, float &dist)
 // quotients (see above), so there is no NaN and no infinity among them and v_min/v_max agree with the reference's
 // select forms up to the sign of a zero, which cannot reach the result: t_min/t_max are only compared, and
 // max(t_min, min_dst) with min_dst = 1e-4 > 0 never returns a zero.
-DEV bool box_hit_fast(V3 bmin, V3 bmax, V3 o, V3 d, V3 r, float min_dst, float &dist) {
-    V3 a1 = bmin - o, a2 = bmax - o;
+DEV bool box_hit_fast_rel(V3 a1, V3 a2, V3 d, V3 r, float min_dst, float &dist) {
     float q1x = div_exact_fast(a1.x, d.x, r.x), q1y = div_exact_fast(a1.y, d.y, r.y), q1z = div_exact_fast(a1.z, d.z, r.z);
     float q2x = div_exact_fast(a2.x, d.x, r.x), q2y = div_exact_fast(a2.y, d.y, r.y), q2z = div_exact_fast(a2.z, d.z, r.z);
     float t_min = fmaxf(fmaxf(fminf(q1x, q2x), fminf(q1y, q2y)), fminf(q1z, q2z));
@@ -98,13 +99,13 @@ template <class P> DEV TriRec tri_rec(const P &r0, const P &r1, const P &r2) {
 //   or  nz' < D * min_dst * (1 - 2^-20)           (Z < min_dst beyond the rounding of RN(Z))
 // Anything else ("maybe") takes the reference's three IEEE divisions and its exact comparisons, so the filter only
 // removes work, never changes an outcome. NaN/inf operands make every comparison false -> "maybe".
-DEV bool tri_hit(const TriRec &tri, V3 o, V3 d, float min_dst, V3 &xs_out) {
-    const V3 av = tri.v, au = tri.u;
+// tri_hit_rel is the test behind everything that does not depend on the ray direction: y = o - a and nz = dot(v, crs(u, y)) are given. tri_hit
+// makes them from the record; the camera-relative records hold them (tri_rel_y / tri_rel_nz: the same operations on the same operands).
+DEV bool tri_hit_rel(V3 av, V3 au, V3 y, float nz, V3 d, float min_dst, V3 &xs_out) {
     V3 at = -d;
-    V3 y = o - tri.a;
     V3 c_ut = crs(au, at);
     float den = dot(av, c_ut);
-    float nx = dot(y, c_ut), ny = dot(av, crs(y, at)), nz = dot(av, crs(au, y));
+    float nx = dot(y, c_ut), ny = dot(av, crs(y, at));
     const uint32_t sgn = __float_as_uint(den) & 0x80000000u;
     const float D = __builtin_fabsf(den);
     const float nxs = __uint_as_float(__float_as_uint(nx) ^ sgn), nys = __uint_as_float(__float_as_uint(ny) ^ sgn),
@@ -121,6 +122,14 @@ DEV bool tri_hit(const TriRec &tri, V3 o, V3 d, float min_dst, V3 &xs_out) {
     }
     return false;
 }
+DEV V3 tri_rel_y(V3 a, V3 o) { return o - a; }
+DEV float tri_rel_nz(V3 av, V3 au, V3 y) { return dot(av, crs(au, y)); }
+DEV bool tri_hit(const TriRec &tri, V3 o, V3 d, float min_dst, V3 &xs_out) {
+    const V3 y = tri_rel_y(tri.a, o);
+    return tri_hit_rel(tri.v, tri.u, y, tri_rel_nz(tri.v, tri.u, y), d, min_dst, xs_out);
+}
+// a camera-relative triangle record (wf_camera_relative): y in the place of a, the bits of nz in the place of DevTri::pad
+DEV bool tri_hit_folded(const TriRec &tri, V3 d, float min_dst, V3 &xs_out) { return tri_hit_rel(tri.v, tri.u, tri.a, __uint_as_float(tri.index), d, min_dst, xs_out); }
 
 struct Hit {
     uint32_t k; // DevTri index (BVH order) or RT_NONE
@@ -252,14 +261,16 @@ struct TwoBox {
     bool hl, hr;
     float dl, dr;
 };
-template <bool KNOWN_FAST = false> DEV TwoBox two_box(const NodeRec &n, V3 o, V3 d, V3 r, bool fast, float min_dst) {
+// REL: the record's four corners are relative to the ray origin already (a camera-relative record): `o` is not read.
+template <bool KNOWN_FAST = false, bool REL = false> DEV TwoBox two_box(const NodeRec &n, V3 o, V3 d, V3 r, bool fast, float min_dst) {
+    const V3 l1 = REL ? n.lmin : n.lmin - o, l2 = REL ? n.lmax : n.lmax - o, r1 = REL ? n.rmn : n.rmn - o, r2 = REL ? n.rmx : n.rmx - o;
     TwoBox b;
     if (KNOWN_FAST || fast) {
-        b.hl = box_hit_fast(n.lmin, n.lmax, o, d, r, min_dst, b.dl);
-        b.hr = box_hit_fast(n.rmn, n.rmx, o, d, r, min_dst, b.dr);
+        b.hl = box_hit_fast_rel(l1, l2, d, r, min_dst, b.dl);
+        b.hr = box_hit_fast_rel(r1, r2, d, r, min_dst, b.dr);
     } else { // rare ray: a direction/origin component is 0-adjacent, huge or NaN -> reference arithmetic
-        b.hl = box_hit_exact(n.lmin, n.lmax, o, d, min_dst, b.dl);
-        b.hr = box_hit_exact(n.rmn, n.rmx, o, d, min_dst, b.dr);
+        b.hl = box_hit_exact_rel(l1, l2, d, min_dst, b.dl);
+        b.hr = box_hit_exact_rel(r1, r2, d, min_dst, b.dr);
     }
     return b;
 }
@@ -267,11 +278,11 @@ template <bool KNOWN_FAST = false> DEV TwoBox two_box(const NodeRec &n, V3 o, V3
 // runs one straight-line sequence (selects instead of per-lane branches: no exec-mask nesting and no register copies at control-flow joins).
 // Leaves T.cur == T_POP when the lane has to unwind; the caller chooses how (trav_pop: per-lane loop; trav_pop_once / trav_pop_wave: all
 // lanes of the wave together).
-template <bool STATS, bool GB = false, bool KNOWN_FAST = false, class STK>
+template <bool STATS, bool GB = false, bool KNOWN_FAST = false, bool REL = false, class STK>
 DEV void trav_inner_apply(Trav &T, STK &stk, const NodeRec &n, float min_dst, LaneStats<STATS> &st) {
     st.node();
     st.box(2);
-    const TwoBox bx = two_box<KNOWN_FAST>(n, T.o, T.d, T.r, T.fast, min_dst);
+    const TwoBox bx = two_box<KNOWN_FAST, REL>(n, T.o, T.d, T.r, T.fast, min_dst);
     bool hl = bx.hl, hr = bx.hr;
     const float dl = bx.dl, dr = bx.dr;
     if constexpr (GB) { // cull against the global best

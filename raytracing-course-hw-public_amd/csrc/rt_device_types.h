@@ -279,6 +279,9 @@ struct WfLaunch {
     uint32_t use_packet;     // this pass's primary rays go through wf_extend_packet (rt_scene.cpp decides: RT_WF_PACKET, samples per
                              // pixel, and what the kernel's own census said on an earlier pass)
     unsigned long long *packet_census; // [2] device: trips, lanes served (summed over the launch's waves)
+    const DevNode *rel_nodes; // both non-null: every primary ray of this pass starts at ONE camera position, and these are the binary tree's
+    const DevTri *rel_tris;   // records with that position folded in (rt_wavefront.hip wf_camera_relative); wf_extend_packet walks them.
+                              // Null: any origins, the kernel reads the tree's own records (rt_render.cpp launch_pass decides)
     uint32_t global_best;    // 0: the reference's traversal order and pruning (parity mode); 1: prune against the global best
                              // (RT_FLAG_GLOBAL_BEST, production traversal: a subset of the reference's node visits)
     uint32_t order_classed;  // `order` came through the ray-order sort and carries the class bits; 0: identity-like order (no sort ran), slots only

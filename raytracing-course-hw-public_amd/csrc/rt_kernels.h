@@ -74,6 +74,9 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
 // -> prim / bct (device). `L` carries the workspace (paths_in, hits, counters, stack_overflow, stats) and the traversal mode.
 hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *rays, uint32_t n, bool packet, bool stats, uint32_t *prim, float *bct,
                                  hipStream_t stream);
+// The camera-relative copy of a binary scene tree's records (WfLaunch::rel_nodes / rel_tris) for the camera position o[3]: one kernel on
+// `stream`; `rel_nodes` has room for n_nodes records, `rel_tris` for bvh.n_tris.
+hipError_t launch_camera_relative(const DevBvh &bvh, uint32_t n_nodes, const float *o, DevNode *rel_nodes, DevTri *rel_tris, int num_cus, hipStream_t stream);
 // rt_wide.hip: the closest-hit kernel of scenes built with RT_BUILD_WIDE (same queue protocol as wf_extend)
 // `packet`: the wave walks the tree once for its 64 consecutive rays (coherent primary rays), records through the scalar cache
 hipError_t launch_extend_wide(const DevScene &S, const WfLaunch &L, bool packet, bool stats, int blocks, hipStream_t stream);

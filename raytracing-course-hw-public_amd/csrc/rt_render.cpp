@@ -111,12 +111,66 @@ int rt::check_pass_params(const rt_params *p, const char *fn) {
     return RT_OK;
 }
 
+// Camera-relative records for the packet kernel (rt_wavefront.hip wf_camera_relative, WfLaunch::rel_nodes / rel_tris) of a pass whose primary
+// rays all start at `cam_pos`. The copy is made on the scene's stream, ahead of the pass, when the camera position (compared as bits) or the
+// tree (rt_scene::geo_generation) differs from what the kept copy was made of; otherwise the kept copy is handed out and nothing is launched.
+// No copy, and the absolute kernel (W.rel_* stay null), when
+//   * the scene tree is not the binary one (RT_BUILD_WIDE has its own packet kernel) or is empty;
+//   * the copy would be larger than RT_REL_MAX_BYTES (1 GiB: S-10M's 0.8 GB tree still gets one) or than RT_REL_BYTES_PER_PATH (16) bytes
+//     per path of the pass. Measured on S-sponza (profiles/camera_relative_sparse_drain.txt): the 21 MB copy takes 12.4 us, 0.6 ps per
+//     byte, and the relative records save 1.45 ms per 64 M primary rays, 23 ps per ray; at 16 bytes per path the copy costs 40 % of what
+//     it saves when it serves ONE pass, and nothing when the camera stays (later passes, accumulator rounds, the next frame of a still);
+//   * its allocation fails (the error is dropped: the render does not need the copy).
+#ifndef RT_REL_MAX_BYTES
+#define RT_REL_MAX_BYTES (1ull << 30)
+#endif
+#ifndef RT_REL_BYTES_PER_PATH
+#define RT_REL_BYTES_PER_PATH 16ull
+#endif
+static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float *cam_pos) {
+    const DevBvh &B = s->dev.scene;
+    const uint32_t n_nodes = s->dev_n_inner[0];
+    if (s->wide_built || B.wide || !B.nodes || !B.tris || B.root == RT_NONE || n_nodes == 0 || B.n_tris == 0)
+        return hipSuccess;
+    const size_t node_bytes = (size_t)n_nodes * sizeof(DevNode), bytes = node_bytes + (size_t)B.n_tris * sizeof(DevTri);
+    if (bytes > RT_REL_MAX_BYTES || bytes > RT_REL_BYTES_PER_PATH * W.n_paths)
+        return hipSuccess;
+    uint32_t pos[3];
+    std::memcpy(pos, cam_pos, 12);
+    const bool same = s->wf_rel_gen == s->geo_generation && std::memcmp(pos, s->wf_rel_pos, 12) == 0;
+    if (!same) {
+        s->wf_rel_gen = 0;
+        if (s->wf_rel_bytes < bytes) {
+            if (s->wf_rel_nodes)
+                (void)hipFree(s->wf_rel_nodes); // (the stream is idle between calls, and within a call the copy's size does not change)
+            s->wf_rel_nodes = nullptr, s->wf_rel_tris = nullptr, s->wf_rel_bytes = 0;
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return hipSuccess;
+            }
+            s->wf_rel_nodes = static_cast<DevNode *>(q);
+            s->wf_rel_bytes = bytes;
+        }
+        s->wf_rel_tris = reinterpret_cast<DevTri *>(reinterpret_cast<char *>(s->wf_rel_nodes) + node_bytes); // 64-byte records first: 16-byte aligned
+        if (hipError_t e = rt::launch_camera_relative(B, n_nodes, cam_pos, s->wf_rel_nodes, s->wf_rel_tris, s->num_cus, s->stream); e != hipSuccess)
+            return e;
+        std::memcpy(s->wf_rel_pos, pos, 12);
+        s->wf_rel_gen = s->geo_generation;
+    }
+    W.rel_nodes = s->wf_rel_nodes;
+    W.rel_tris = s->wf_rel_tris;
+    return hipSuccess;
+}
+
 // One wavefront pass: `W` carries the workspace (wf_bind) and the pass's geometry (first_pixel, pass_pixels, first_sample, pass_samples,
 // n_paths, views, ...); this picks W.sort_mode and W.use_packet, launches, and folds the packet kernel's census back into `pol`, the
 // policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays*). `acc`: an
 // accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays (rt_kernels.h).
+// `cam_pos`: the pass's primary rays are camera rays of ONE view and this is its position, the three floats wf_primary_ray stores as every
+// ray's origin; null where no such position exists (several views, a caller's rays).
 hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays) {
+                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos) {
     // Small passes are bound by launch and host latency, not by memory (a 256 x 256 x 4 render, BASELINE config 1's
     // shape, spent 5.7 ms at 0.6 ms per bounce): RT_SORT_AUTO leaves a pass of fewer than 2^20 paths unsorted, which also spares it
     // the per-bounce queue-size read-back the sort needs: the whole pass is queued without a single host wait.
@@ -137,6 +191,10 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     }
     const uint32_t pkt_min_spp = s->wide_built ? 4u : 16u; // measured break-even of the two packet kernels
     W.use_packet = p->packet_mode == RT_PACKET_OFF ? 0u : p->packet_mode == RT_PACKET_ON ? 1u : (W.pass_samples >= pkt_min_spp && !pol.off) ? 1u : 0u;
+    W.rel_nodes = nullptr, W.rel_tris = nullptr;
+    if (W.use_packet && cam_pos && n_views == 1 && !rays)
+        if (hipError_t e = camera_relative_records(s, W, cam_pos); e != hipSuccess)
+            return e;
     const rt::WfHostSync hsync = wavefront_host_sync(s);
     unsigned long long census[2] = {0ull, 0ull};
     const hipError_t e = rt::launch_wavefront_pass(s->dev, W, W.stats != nullptr, s->num_cus, first_pass, last_pass, s->stream, time_extends ? &s->ext_events : nullptr, census,
@@ -324,7 +382,8 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
                 W.first_sample = s0;
                 W.pass_samples = std::min<uint32_t>(pass_spp, p->samples - s0);
                 W.n_paths = W.pass_pixels * W.pass_samples;
-                HIP_TRY(rt::launch_pass(s, p, s->pkt, W, n_views, s0 == 0, s0 + W.pass_samples >= p->samples, stats != nullptr, nullptr));
+                HIP_TRY(rt::launch_pass(s, p, s->pkt, W, n_views, s0 == 0, s0 + W.pass_samples >= p->samples, stats != nullptr, nullptr, nullptr, nullptr,
+                                        n_views == 1 ? vt[0].pos : nullptr));
                 passes += 1;
                 packet_passes += W.use_packet;
                 if (p->progress) {

@@ -218,6 +218,15 @@ struct rt_scene {
     rt::PacketPolicy pkt; // of rt_render* (an accumulator keeps its own)
     std::vector<hipEvent_t> pass_events; // rt_params.progress: one per pass
 
+    // The camera-relative copy of the binary scene tree's records (WfLaunch::rel_nodes / rel_tris): part of the wavefront workspace, made by
+    // launch_pass for the passes whose primary rays share one origin and kept while (camera position, tree) stay the same. `rel_gen` is the
+    // geo_generation the copy was made of; every swap or in-place rewrite of the tree (install_geometry, a refit) moves geo_generation on.
+    DevNode *wf_rel_nodes = nullptr;
+    DevTri *wf_rel_tris = nullptr;
+    size_t wf_rel_bytes = 0;       // capacity of the one allocation behind both
+    uint64_t geo_generation = 1, wf_rel_gen = 0; // 0: no valid copy
+    uint32_t wf_rel_pos[3] = {0, 0, 0}; // the camera position of the copy, as bits
+
     int ensure_wavefront(uint64_t paths, uint64_t pixels, uint32_t depth) {
         if (paths <= wf_paths_cap && pixels <= wf_pixels_cap && depth <= wf_depth_cap)
             return RT_OK;
@@ -322,6 +331,8 @@ struct rt_scene {
             (void)hipFree(p);
         if (wf_feat)
             (void)hipFree(wf_feat);
+        if (wf_rel_nodes)
+            (void)hipFree(wf_rel_nodes);
         if (d_fb)
             (void)hipFree(d_fb);
         if (d_rgb8)
@@ -359,7 +370,7 @@ void set_camera(DevScene &D, const float *pos, const float *right, const float *
 int check_pass_params(const rt_params *p, const char *fn);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
 hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr);
+                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr);
 int fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats);
 
 // Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are

@@ -225,6 +225,7 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
     s->refit_levels_ms = levels_ms;
     s->geo = G; // (its host_bvh[0] / wide are empty: the tree the wide one was collapsed from no longer describes the scene)
     s->refitted = true;
+    ++s->geo_generation; // records rewritten in place: nothing derived from the old ones may be used again
     return RT_OK;
 }
 

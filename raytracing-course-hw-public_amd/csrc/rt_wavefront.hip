@@ -22,6 +22,7 @@
 // order; the stream's state, the remaining depth and the count of pending frames travel with the ray through the queues
 // (WfPath), so the image is independent of queue order, tiling and GPU count, and bit-identical to the persistent
 // megakernel of rt_kernels.hip and to the CPU oracle in device-RNG mode.
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -199,6 +200,23 @@ template <bool STATS> DEV void leaf_batch(Trav &T, const DevBvh &bvh, bool at_le
 #ifndef RT_EXT_LEAF_MIN
 #define RT_EXT_LEAF_MIN 20 /* run a leaf batch once this many lanes wait on a leaf */
 #endif
+#ifndef RT_EXT_SPARSE_MAX
+#define RT_EXT_SPARSE_MAX 32 /* a wave whose queue is used up drains eagerly once this many lanes or fewer still walk (swept 0 / 4 .. 64:
+                                profiles/camera_relative_sparse_drain.txt) */
+#endif
+
+// One record for every `stepper` lane of the wave. The common wave: every stepping lane is on an inner node with the fast-division
+// guarantees -> straight-line node step; a wave with a big-leaf walker or a guarded ray takes the general step.
+template <bool STATS, bool GB, class STK> DEV void node_step(Trav &T, const DevBvh &bvh, STK &stk, bool stepper, LaneStats<STATS> &st) {
+    const bool plain = (T.cur & RT_LEAF_FLAG) == 0 && T.fast;
+    if (__ballot(stepper && !plain) == 0ull) {
+        if (stepper) {
+            trav_step_inner_fast<STATS, GB>(T, bvh, stk, EPS, st);
+        }
+    } else if (stepper) {
+        trav_step_core<STATS, GB>(T, bvh, stk, EPS, st);
+    }
+}
 
 template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PER_SIMD) void wf_extend(const DevScene S, const WfLaunch L) {
     constexpr int DEPTH = GB ? RT_EXT_GB_LDS_DEPTH : RT_EXT_LDS_DEPTH, WORDS = GB ? 2 : 3;
@@ -219,7 +237,7 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
     uint32_t q_lo = 0, q_hi = 0; // this wave's private range of queue positions
     TicketState tks = ticket_init();
     for (;;) {
-        ticket_refill(L.counters, n_in, (uint32_t)RT_EXT_CHUNK, RT_EXT_REFILL_MIN, T.cur == T_DONE, exhausted, q_lo, q_hi, tks, [&](uint32_t jq) {
+        const int n_idle = ticket_refill(L.counters, n_in, (uint32_t)RT_EXT_CHUNK, RT_EXT_REFILL_MIN, T.cur == T_DONE, exhausted, q_lo, q_hi, tks, [&](uint32_t jq) {
             const WfRay ray = wf_load_ray(L.paths_in + wf_order_slot(L, jq)); // coherence-sorted processing order
             slot = jq; // the hit goes to the queue POSITION (see WfLaunch::hits)
             trav_init_stored<GB>(T, S.scene, ray.o, ray.d, ray.r, ray.fast);
@@ -251,18 +269,41 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
         }
         if (sm == 0ull || __popcll(lm) >= RT_EXT_LEAF_MIN) {
             leaf_batch<STATS>(T, S.scene, at_leaf, s_coop, st);
+            // The one place that looks whether the wave has become sparse: a scalar test on the trips that ran a batch (a sparse wave runs
+            // one every few trips: its steppers are few), so the loop head and the node step stay what they were. n_idle is this trip's count
+            // from before the unwind: with the queue used up lanes only ever finish, so it can only be too small. (A block is 4 full waves.)
+            if (exhausted && n_idle >= 64 - RT_EXT_SPARSE_MAX)
+                break; // -> the sparse drain behind the loop
         } else {
-            // the common wave: every stepping lane is on an inner node with the fast-division guarantees -> straight-line
-            // node step; a wave with a big-leaf walker or a guarded ray takes the general step
-            const bool plain = (T.cur & RT_LEAF_FLAG) == 0 && T.fast;
-            if (__ballot(stepper && !plain) == 0ull) {
-                if (stepper) {
-                    trav_step_inner_fast<STATS, GB>(T, S.scene, stk, EPS, st);
-                }
-            } else if (stepper) {
-                trav_step_core<STATS, GB>(T, S.scene, stk, EPS, st);
-            }
+            node_step<STATS, GB>(T, S.scene, stk, stepper, st);
         }
+    }
+    // Sparse drain: the queue is used up and at most RT_EXT_SPARSE_MAX lanes still walk. Nothing is left to keep busy, so the throughput
+    // policies of the loop above (wait for 20 leaves, one pop per trip, a leaf batch OR a node step) only lengthen the chain of the wave's
+    // slowest ray, and that chain is the launch's tail. A trip here unwinds until no lane is left in T_POP, tests the leaves of the lanes
+    // that stand on one at once, unwinds again, and steps every lane that stands on an inner node. Each lane runs the same state machine in
+    // the same order as above: hits and counters are unchanged by construction.
+    bool live = T.cur != T_DONE;
+    auto unwind = [&]() {
+        trav_pop_wave<GB>(T, stk);
+        if (live && T.cur == T_DONE) {
+            wf_store_hit(L.hits + slot, T.best);
+            live = false;
+        }
+    };
+    for (;;) {
+        unwind();
+        if (__ballot(live) == 0ull)
+            break;
+        const bool at_leaf = live && (T.cur & RT_LEAF_FLAG) != 0 && RT_LEAF_CNT(T.cur) != 0; // (no lane is in T_POP here)
+        if (__ballot(at_leaf) != 0ull) {
+            leaf_batch<STATS>(T, S.scene, at_leaf, s_coop, st);
+            unwind();
+        }
+        // an inner node, or a big leaf walked triangle by triangle; a lane the unwind has just put on a small leaf waits one trip
+        const bool stepper = live && !((T.cur & RT_LEAF_FLAG) != 0 && RT_LEAF_CNT(T.cur) != 0);
+        if (__ballot(stepper) != 0ull)
+            node_step<STATS, GB>(T, S.scene, stk, stepper, st);
     }
     st.flush(L.stats);
 }
@@ -280,13 +321,18 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
 #ifndef RT_PKT_CHUNK
 #define RT_PKT_CHUNK 256u /* queue positions per ticket atomic (4 packets) */
 #endif
-template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PER_SIMD) void wf_extend_packet(const DevScene S, const WfLaunch L) {
+// REL: the pass's primary rays all start at ONE camera position, bit for bit, and WfLaunch::rel_nodes / rel_tris hold the tree's records with
+// that position folded in (wf_camera_relative below): the trips fetch those and skip what a lane would compute from the origin. The host
+// decides (rt_render.cpp launch_pass); the kernel never compares origins.
+template <bool STATS, bool GB, bool REL> __global__ __launch_bounds__(256, RT_EXT_WAVES_PER_SIMD) void wf_extend_packet(const DevScene S, const WfLaunch L) {
     constexpr int DEPTH = GB ? RT_EXT_GB_LDS_DEPTH : RT_EXT_LDS_DEPTH, WORDS = GB ? 2 : 3;
     __shared__ uint32_t s_stack[STACK_LDS_DWORDS(DEPTH, WORDS)];
     LaneStats<STATS> st;
     RT_DECLARE_RING_STACK_W(stk, DEPTH, WORDS, s_stack, L.stack_overflow, L.stack_stride);
     const uint32_t n_in = L.counters[WF_CNT_IN];
     const uint32_t lane = threadIdx.x & 63u;
+    const DevNode *const nodes = REL ? L.rel_nodes : S.scene.nodes;
+    const DevTri *const tris = REL ? L.rel_tris : S.scene.tris;
     Trav T = trav_idle<GB>();
     unsigned long long n_trips = 0ull, n_lanes = 0ull; // wave-uniform
     for (;;) {
@@ -321,15 +367,15 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
                     // otherwise address the node through the lane's own T.cur (a vector load per lane)
                     uint32_t node_index = target;
                     asm volatile("" : "+s"(node_index));
-                    ConstF4 p = as_const_f4(S.scene.nodes + node_index);
+                    ConstF4 p = as_const_f4(nodes + node_index);
                     const F4v r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3];
                     if (mine)
-                        trav_inner_apply<STATS, GB>(T, stk, node_rec(r0, r1, r2, r3), EPS, st);
+                        trav_inner_apply<STATS, GB, false, REL>(T, stk, node_rec(r0, r1, r2, r3), EPS, st);
                 } else { // a leaf: its triangles in index order, strict-less replacement (bvh.h:200-204,132)
                     const uint32_t cnt = RT_LEAF_CNT(target);
                     uint32_t k = target & RT_LEAF_BEGIN_MASK;
                     for (uint32_t i = 0;; ++i, ++k) {
-                        ConstF4 p = as_const_f4(S.scene.tris + k);
+                        ConstF4 p = as_const_f4(tris + k);
                         const F4v r0 = p[0], r1 = p[1], r2 = p[2];
                         const TriRec tri = tri_rec(r0, r1, r2);
                         if (mine) {
@@ -337,7 +383,7 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
                                 st.node(); // one BVH::intersect_ray invocation on the leaf node
                             st.tri();
                             V3 xs;
-                            if (tri_hit(tri, T.o, T.d, EPS, xs)) {
+                            if (REL ? tri_hit_folded(tri, T.d, EPS, xs) : tri_hit(tri, T.o, T.d, EPS, xs)) {
                                 hit_take(T.best, k, xs.x, xs.y, xs.z);
                                 T.t_loc = fminf(T.t_loc, xs.z);
                             }
@@ -355,6 +401,41 @@ template <bool STATS, bool GB> __global__ __launch_bounds__(256, RT_EXT_WAVES_PE
     }
     census_flush(L.packet_census, n_trips, n_lanes);
     st.flush(L.stats);
+}
+
+// The camera-relative copy of the binary tree's records for wf_extend_packet<.., REL>: what a lane computes from a record and the ray ORIGIN
+// alone, computed once per (camera position, tree) instead of once per lane and trip. Same layouts, same indices:
+//   node      the four corners become lmin - o, lmax - o, rmin - o, rmax - o (two_box's subtractions); child references unchanged
+//   triangle  a becomes y = o - a (tri_rel_y), DevTri::pad (unused by the binary tree's kernels) the bits of nz = dot(v, crs(u, y)) (tri_rel_nz);
+//             v, u, prim, flags unchanged
+// Every value is the chain of single-rounding operations the lanes run on the same operands (-ffp-contract=off), hence the same bits.
+// Grid-stride over 16-byte pieces would split a record's arithmetic; one lane per record, four / three 16-byte loads and stores each.
+__global__ __launch_bounds__(256) void wf_camera_relative(const DevNode *nodes, uint32_t n_nodes, const DevTri *tris, uint32_t n_tris, V3 o, DevNode *rel_nodes, DevTri *rel_tris) {
+    const uint32_t n = n_nodes + n_tris;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        if (i < n_nodes) {
+            const float4 *p = reinterpret_cast<const float4 *>(nodes + i);
+            const float4 r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3];
+            const NodeRec r = node_rec(r0, r1, r2, r3);
+            const V3 a = r.lmin - o, b = r.lmax - o, c = r.rmn - o, d = r.rmx - o;
+            float4 *q = reinterpret_cast<float4 *>(rel_nodes + i);
+            q[0] = make_float4(a.x, a.y, a.z, b.x);
+            q[1] = make_float4(b.y, b.z, c.x, c.y);
+            q[2] = make_float4(c.z, d.x, d.y, d.z);
+            q[3] = r3;
+        } else {
+            const uint32_t k = i - n_nodes;
+            const float4 *p = reinterpret_cast<const float4 *>(tris + k);
+            const float4 r0 = p[0], r1 = p[1], r2 = p[2];
+            const TriRec t = tri_rec(r0, r1, r2);
+            const V3 y = tri_rel_y(t.a, o);
+            const float nz = tri_rel_nz(t.v, t.u, y);
+            float4 *q = reinterpret_cast<float4 *>(rel_tris + k);
+            q[0] = make_float4(y.x, y.y, y.z, r0.w);
+            q[1] = r1;
+            q[2] = make_float4(r2.x, r2.y, r2.z, nz);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ extend: analytic primitives
@@ -749,12 +830,18 @@ namespace rt {
 static hipError_t launch_extend(const DevScene &S, const WfLaunch &L, bool packet, bool stats, int ext_blocks, hipStream_t stream) {
     if (S.scene.wide) // production build (RT_BUILD_WIDE): every bounce walks the 8-wide tree (rt_wide.hip)
         return launch_extend_wide(S, L, packet, stats, ext_blocks, stream);
-    return with_bools([&](auto P, auto ST, auto G) {
+    return with_bools([&](auto P, auto ST, auto G, auto R) {
         if constexpr (P)
-            return RT_LAUNCH_CHECKED((wf_extend_packet<ST, G>), dim3(ext_blocks), dim3(256), 0, stream, S, L);
+            return RT_LAUNCH_CHECKED((wf_extend_packet<ST, G, R>), dim3(ext_blocks), dim3(256), 0, stream, S, L);
         else
             return RT_LAUNCH_CHECKED((wf_extend<ST, G>), dim3(ext_blocks), dim3(256), 0, stream, S, L);
-    }, packet, stats, L.global_best != 0u);
+    }, packet, stats, L.global_best != 0u, packet && L.rel_nodes != nullptr && L.rel_tris != nullptr);
+}
+
+hipError_t launch_camera_relative(const DevBvh &bvh, uint32_t n_nodes, const float *o, DevNode *rel_nodes, DevTri *rel_tris, int num_cus, hipStream_t stream) {
+    const uint32_t n = n_nodes + bvh.n_tris;
+    const uint32_t blocks = std::min<uint32_t>((n + 255u) / 256u, (uint32_t)num_cus * 16u);
+    return RT_LAUNCH_CHECKED(wf_camera_relative, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, bvh.nodes, n_nodes, bvh.tris, bvh.n_tris, V3{o[0], o[1], o[2]}, rel_nodes, rel_tris);
 }
 
 // ---- closest-hit probe through the production kernels (rt_cast_rays_ex): rays -> queue -> wf_extend / wf_extend_packet -> hits
@@ -767,6 +854,7 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
     L.n_paths = n;
     L.order = nullptr, L.order_classed = 0u;
     L.packet_census = nullptr;
+    L.rel_nodes = nullptr, L.rel_tris = nullptr; // a caller's rays: any origin
     const int blocks = (int)((n + 255u) / 256u);
     WF_LAUNCH(wf_from_rays, dim3(blocks), block, 0, stream, L, rays, n);
     if ((e = launch_extend(S, L, packet, stats, (int)(L.stack_stride / 256u), stream)) != hipSuccess)
