@@ -427,6 +427,68 @@ typedef struct rt_ray {
 int rt_render_rays(rt_scene *scene, const rt_params *params, const rt_ray *rays, uint32_t n_rays, uint32_t rays_per_output, float *out_rgb, rt_stats *stats);
 int rt_render_rays_rgb8(rt_scene *scene, const rt_params *params, const rt_ray *rays, uint32_t n_rays, uint32_t rays_per_output, uint8_t *rgb8, rt_stats *stats);
 
+/* Sensor models evaluated on the device (additive; RT_ABI_VERSION stays 4): panoramic (equirectangular), equidistant fisheye,
+ * orthographic and thin-lens cameras next to the reference's pinhole, for every entry point that makes an image. The sensor is evaluated in
+ * the first stage of the wavefront pipeline, so sample s of pixel p is a pure function of (sensor, p, s) whichever call draws it.
+ * The rule, operation by operation: IEEE binary32, evaluated as written, no contraction; vector expressions per component, left to right.
+ * P, R, U, F are camera.position / right / up / forward, used as given. For sample s of pixel pix of a W x H image, x = pix % W, y = pix / W:
+ *     rt_xoshiro_seed(&rng, seed, pix, s)
+ *     ox = uniform_real(rng, 0, 1);  oy = uniform_real(rng, 0, 1)                  gen_ray's two draws, in gen_ray's order
+ *     nx = 2 * ((float)x + ox) / (float)W - 1;   ny = 2 * ((float)y + oy) / (float)H - 1         gen_ray's own terms, in [-1, 1]
+ *     tan_x = tanf(fov_x / 2), tan_y = tanf(fov_y / 2) with fov_y = atanf(tanf(fov_x / 2) * H / W) * 2   (host, as rt_render's)
+ *     half_fov = fov_x / 2  (host, float)
+ *   PINHOLE       o = P;  d = gen_ray's: norm((nx*tan_x)*R - (ny*tan_y)*U + 1.0f*F)
+ *   EQUIRECT      a = PI_F * (nx + 1);  p = (PI_F * 0.5f) * (ny + 1)       azimuth + pi in [0, 2 pi]; polar angle from +U in [0, pi]
+ *                 (sa, ca) = rt_sincos_libm(a);  (sp, cp) = rt_sincos_libm(p)
+ *                 o = P;  d = norm((-(sp*sa))*R + cp*U + (-(sp*ca))*F)     the image centre looks along F, columns grow towards R, the top row towards U
+ *   FISHEYE       px = nx;  py = ny * ((float)H / (float)W);  r = sqrtf(px*px + py*py);  th = r * half_fov     equidistant, fov_x across the width
+ *                 (st, ct) = rt_sincos_libm(th)
+ *                 o = P;  d = r == 0 ? norm(F) : norm((st*(px/r))*R - (st*(py/r))*U + ct*F)
+ *   ORTHOGRAPHIC  half_h = half_width * (float)H / (float)W  (host, float)
+ *                 o = P + (nx*half_width)*R - (ny*half_h)*U;  d = norm(F)
+ *   THIN_LENS     q = (nx*tan_x)*R - (ny*tan_y)*U + 1.0f*F                 gen_ray's screen point, not normalised
+ *                 rt_xoshiro_seed(&lens, seed ^ 0x9E3779B97F4A7C15, pix, s)  a second generator: the path's own stream is not advanced
+ *                 l0 = uniform_real(lens, 0, 1);  l1 = uniform_real(lens, 0, 1)
+ *                 rad = lens_radius * sqrtf(l0);  (sl, cl) = rt_sincos_libm((2 * PI_F) * l1)
+ *                 e = (rad*cl)*R + (rad*sl)*U;  o = P + e;  d = norm(focus_distance * q - e)
+ *   In every kind the path continues with `rng` as it stands after the two jitter draws and nothing else: where gen_ray leaves it.
+ *   (rt_sincos_libm, uniform_real, rt_xoshiro_seed: rt_devspec.h. Every rt_sincos_libm argument lies in [0, 2 pi], the range on which
+ *   that restatement equals libm's sinf / cosf on every float.)
+ * Contracts, bit for bit:
+ *   Sensor equals rays: view v of rt_render_sensors with samples = SPP equals rt_render_rays (K = 1, G = SPP, params->seed = sensor.seed) over
+ *     the records rt_sensor_rays writes for that sensor; with RT_FLAG_COUNTERS every event counter agrees.
+ *   Pinhole equals views: a RT_SENSOR_PINHOLE sensor gives view {camera, seed} of rt_render_views, counters included.
+ *   Scheduling independence: max_paths, the sort mode, the packet mode and which other sensors share the call change no bit.
+ * rt_render_sensors*: output view-major, fb[v][y][x][3] (rgb8: 3 bytes per pixel), like rt_render_views; the sensors of one call may be of
+ *   different kinds. width, height, samples, the flags RT_FLAG_COUNTERS | RT_FLAG_GLOBAL_BEST | RT_FLAG_DEVICE_FB, the tuning fields and
+ *   progress mean what they mean for rt_render; rt_params.seed is not read. Every single-GPU tree kind. ray_depth == 0: RT_OK, nothing written.
+ *   RT_ERR_INVALID_ARG: a NULL argument or n_sensors == 0; an unknown kind; a non-zero reserved word; half_width, lens_radius or
+ *     focus_distance outside the range stated at the field (for the kind that reads it); FISHEYE with fov_x not finite and > 0 or with
+ *     (double)half_fov * sqrt(1 + (H/W)^2) > pi (a corner would look more than 180 degrees off axis: the library renders no dead pixels);
+ *     n_sensors * width * height >= 2^31; shard_count > 1; samples == 0; an unknown flag; a pass option rt_render refuses.
+ *   RT_ERR_UNSUPPORTED: RT_RNG_REFERENCE; RT_FLAG_MEGAKERNEL; a multi-GPU scene.
+ * rt_sensor_rays: the same device function writes the n_pixels * samples rt_ray records of pixels [first_pixel, first_pixel + n_pixels) and
+ *   samples [first_sample, first_sample + samples) of a width x height image: pixel-major, each pixel's samples adjacent, stream = pix,
+ *   first_sample = s. flags: 0 (rays_out is a host buffer) or RT_FLAG_DEVICE_FB (a device buffer on the scene's GPU, 16-byte aligned, idle
+ *   on entry). RT_ERR_INVALID_ARG: a NULL argument, what rt_render_sensors refuses of a sensor, an empty image, a pixel range past
+ *   width * height, n_pixels * samples >= 2^31, a misaligned device buffer, any other flag. n_pixels == 0 or samples == 0 writes nothing.
+ * rt_accum_create_sensor: rt_accum_create_ex with a sensor in place of {camera, seed}; everything else about the accumulator is unchanged.
+ *   Its exactness contract reads: pixel p equals pixel p of rt_render_sensors with samples = n_p; the feature sums are those of each sample's
+ *   primary ray as defined above. */
+enum { RT_SENSOR_PINHOLE = 0, RT_SENSOR_EQUIRECT = 1, RT_SENSOR_FISHEYE = 2, RT_SENSOR_ORTHOGRAPHIC = 3, RT_SENSOR_THIN_LENS = 4 };
+typedef struct rt_sensor {
+    rt_camera camera;     /* position P and frame R = right, U = up, F = forward, used as given; fov_x read by PINHOLE, FISHEYE, THIN_LENS */
+    uint32_t kind;        /* RT_SENSOR_* */
+    float half_width;     /* ORTHOGRAPHIC: half the film width in world units, finite, > 0 */
+    float lens_radius;    /* THIN_LENS: finite, >= 0 */
+    float focus_distance; /* THIN_LENS: distance of the focal plane along F, finite, > 0 */
+    uint32_t reserved[5]; /* 0 */
+    uint64_t seed;        /* RT_RNG_DEVICE stream seed of this view */
+} rt_sensor;              /* 96 bytes; fields a kind does not read are ignored */
+int rt_render_sensors(rt_scene *scene, const rt_params *params, const rt_sensor *sensors, uint32_t n_sensors, float *fb_rgb, rt_stats *stats);
+int rt_render_sensors_rgb8(rt_scene *scene, const rt_params *params, const rt_sensor *sensors, uint32_t n_sensors, uint8_t *rgb8, rt_stats *stats);
+int rt_sensor_rays(rt_scene *scene, const rt_sensor *sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t n_pixels, uint32_t first_sample, uint32_t samples, uint32_t flags, rt_ray *rays_out);
+
 /* Resumable sample accumulators: progressive and adaptive rendering (additive; RT_ABI_VERSION stays 4).
  * An accumulator belongs to one scene, one image size (width x height) and one view (a camera and an RT_RNG_DEVICE seed). It keeps, in
  * device memory, for every pixel p:
@@ -511,6 +573,8 @@ int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb, uint32_t *
  * (32 B per path of a pass) do not fit beside the wavefront workspace. */
 enum { RT_ACCUM_FEATURES = 1 };
 int rt_accum_create_ex(rt_scene *scene, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, uint32_t accum_flags, rt_accum **out);
+/* rt_accum_create_ex for a sensor (rt_sensor above: the rule, the refusals): the view is {sensor, sensor->seed}. */
+int rt_accum_create_sensor(rt_scene *scene, uint32_t width, uint32_t height, const rt_sensor *sensor, uint32_t accum_flags, rt_accum **out);
 /* The raw sums (any pointer may be NULL): AS, NS (3 floats per pixel), ZS (1 float), h (u32). RT_ERR_INVALID_ARG without RT_ACCUM_FEATURES. */
 int rt_accum_read_features(rt_accum *acc, float *albedo_sum, float *normal_sum, float *depth_sum, uint32_t *hits);
 /* The means (any pointer may be NULL): albedo = AS / (float)n, normal = NS / (float)n (NOT renormalised), depth = ZS / (float)h (0 where

@@ -11,6 +11,7 @@ the call raises.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 from typing import Optional, Tuple
 
@@ -61,6 +62,7 @@ from ._ctypes_abi import (
     RtParams,
     RtRay,
     RtSceneDesc,
+    RtSensor,
     RtView,
     RtStats,
     bind,
@@ -184,6 +186,62 @@ def make_views(cameras, seeds):
         views[v].camera.fov_x = np.float32(cam.fov_x)
         views[v].seed = int(seed)
     return views
+
+
+RT_SENSOR_PINHOLE, RT_SENSOR_EQUIRECT, RT_SENSOR_FISHEYE, RT_SENSOR_ORTHOGRAPHIC, RT_SENSOR_THIN_LENS = range(5)
+
+
+@dataclasses.dataclass
+class Sensor:
+    """One sensor of DeviceScene.render_sensors / sensor_rays / accumulator(sensor=...) (include/rt_abi.h rt_sensor states the rule of every
+    kind): `camera` a scenegen.Camera (or anything with position / right / up / forward / fov_x), `kind` an RT_SENSOR_* value, `seed` the
+    RT_RNG_DEVICE seed of the view. Use the constructors."""
+
+    camera: object
+    kind: int = RT_SENSOR_PINHOLE
+    half_width: float = 0.0
+    lens_radius: float = 0.0
+    focus_distance: float = 0.0
+    seed: int = 0
+
+    @classmethod
+    def pinhole(cls, camera, seed: int = 0) -> "Sensor":
+        return cls(camera, RT_SENSOR_PINHOLE, seed=seed)
+
+    @classmethod
+    def equirect(cls, camera, seed: int = 0) -> "Sensor":
+        """The full sphere: the image centre looks along forward, columns grow towards right, the top row looks along up."""
+        return cls(camera, RT_SENSOR_EQUIRECT, seed=seed)
+
+    @classmethod
+    def fisheye(cls, camera, seed: int = 0) -> "Sensor":
+        """Equidistant fisheye, camera.fov_x across the image width."""
+        return cls(camera, RT_SENSOR_FISHEYE, seed=seed)
+
+    @classmethod
+    def orthographic(cls, camera, half_width: float, seed: int = 0) -> "Sensor":
+        return cls(camera, RT_SENSOR_ORTHOGRAPHIC, half_width=half_width, seed=seed)
+
+    @classmethod
+    def thin_lens(cls, camera, lens_radius: float, focus_distance: float, seed: int = 0) -> "Sensor":
+        return cls(camera, RT_SENSOR_THIN_LENS, lens_radius=lens_radius, focus_distance=focus_distance, seed=seed)
+
+
+def make_sensors(sensors):
+    """rt_sensor[] of Sensor objects (ctypes RtSensor records pass through)."""
+    sensors = list(sensors)
+    out = (RtSensor * max(1, len(sensors)))()
+    for v, sn in enumerate(sensors):
+        if isinstance(sn, RtSensor):
+            C.memmove(C.byref(out[v]), C.byref(sn), C.sizeof(RtSensor))
+            continue
+        out[v].camera = make_views([sn.camera], 0)[0].camera
+        out[v].kind = int(sn.kind)
+        out[v].half_width = np.float32(sn.half_width)
+        out[v].lens_radius = np.float32(sn.lens_radius)
+        out[v].focus_distance = np.float32(sn.focus_distance)
+        out[v].seed = int(sn.seed)
+    return out
 
 
 def pack_rays(rays, stream=None, first_sample=None, samples: int = 1, rays_per_output: int = 1) -> np.ndarray:
@@ -387,11 +445,52 @@ class DeviceScene:
             setattr(u, name, C.cast(C.c_void_p(ptrs[name]), C.POINTER(C.c_float if dtype == np.float32 else C.c_uint32)))
         _check(lib().rt_update_geometry_device(self._h, C.byref(u)))
 
-    def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False) -> "Accumulator":
+    def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False, sensor=None) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
         RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view. `features`: keep the first-hit
-        albedo / normal / depth sums as well (rt_accum_create_ex with RT_ACCUM_FEATURES), which features(), read_features() and denoise() need."""
-        return Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0)
+        albedo / normal / depth sums as well (rt_accum_create_ex with RT_ACCUM_FEATURES), which features(), read_features() and denoise() need.
+        `sensor`: a Sensor in place of `camera` and `seed` (rt_accum_create_sensor): pixel p is then render_sensors(samples = n_p) of it."""
+        if sensor is not None and camera is not None:
+            raise ValueError("accumulator: give a camera or a sensor, not both (the sensor carries its camera and seed)")
+        return Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0, sensor=sensor)
+
+    def render_sensors(self, width: int, height: int, samples: int, sensors, rgb8: bool = False, counters: bool = False, global_best: bool = False,
+                       device_out: Optional[int] = None, **tuning):
+        """Images of this scene through Sensor objects, one view each, in one call (rt_render_sensors, or rt_render_sensors_rgb8 with `rgb8`):
+        pinhole, equirectangular, fisheye, orthographic and thin-lens cameras, evaluated on the device. Returns ((K, H, W, 3) float32 linear
+        framebuffers or uint8 images, stats dict); with `device_out` (a device pointer, RT_FLAG_DEVICE_FB) the images stay in HBM and None is
+        returned for them. `tuning`: as run_raytracer."""
+        sensors = list(sensors)
+        recs = make_sensors(sensors)
+        k = len(sensors)
+        p = RtParams(width, height, samples, RT_RNG_DEVICE, 0, 0, 1, 0, (RT_FLAG_COUNTERS if counters else 0) | (RT_FLAG_GLOBAL_BEST if global_best else 0))
+        keep_cb = _apply_tuning(p, tuning)  # noqa: F841
+        st = RtStats()
+        fn = lib().rt_render_sensors_rgb8 if rgb8 else lib().rt_render_sensors
+        if device_out:
+            p.flags |= RT_FLAG_DEVICE_FB
+            _check(fn(self._h, C.byref(p), recs, k, C.c_void_p(device_out), C.byref(st)))
+            return None, st.as_dict()
+        img = np.zeros((k, height, width, 3), dtype=np.uint8 if rgb8 else np.float32)
+        _check(fn(self._h, C.byref(p), recs, k, img.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return img, st.as_dict()
+
+    def sensor_rays(self, sensor, width: int, height: int, samples: int, first_pixel: int = 0, n_pixels: Optional[int] = None, first_sample: int = 0,
+                    device_out: Optional[int] = None):
+        """The primary rays of a Sensor as the device makes them (rt_sensor_rays): RAY_DTYPE records for samples [first_sample, first_sample +
+        samples) of pixels [first_pixel, first_pixel + n_pixels) (default: to the image's end), pixel-major, stream = pixel, first_sample =
+        sample index: what render_rays(samples=1, rays_per_output=samples, seed=sensor.seed) turns into render_sensors' image. With
+        `device_out` (a device pointer to 32 bytes per record, 16-byte aligned, idle) the records stay in HBM and None is returned."""
+        if n_pixels is None:
+            n_pixels = int(width) * int(height) - int(first_pixel)
+        recs = make_sensors([sensor])
+        args = (self._h, recs, int(width), int(height), int(first_pixel), int(n_pixels), int(first_sample), int(samples))
+        if device_out:
+            _check(lib().rt_sensor_rays(*args, RT_FLAG_DEVICE_FB, C.c_void_p(device_out)))
+            return None
+        out = np.zeros(int(n_pixels) * int(samples), dtype=RAY_DTYPE)
+        _check(lib().rt_sensor_rays(*args, 0, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def run_raytracer(
         self,
@@ -638,10 +737,14 @@ class Accumulator:
     """Progressive and adaptive rendering (include/rt_abi.h rt_accum_*): per-pixel sums S, E (even-index samples) and counts n that
     survive between calls. Keeps its DeviceScene alive; DeviceScene.close() closes it first."""
 
-    def __init__(self, scene: DeviceScene, width: int, height: int, camera=None, seed: int = 0, accum_flags: int = 0):
+    def __init__(self, scene: DeviceScene, width: int, height: int, camera=None, seed: int = 0, accum_flags: int = 0, sensor=None):
         self._scene = scene
         self.width, self.height = int(width), int(height)
         self._h = C.c_void_p()
+        if sensor is not None:
+            _check(lib().rt_accum_create_sensor(scene._h, self.width, self.height, make_sensors([sensor]), int(accum_flags), C.byref(self._h)))
+            scene._accums.append(self)
+            return
         cam = None
         if camera is not None:
             cam = make_views([camera], 0)[0].camera
@@ -858,6 +961,9 @@ __all__ = [
     "parse_scene_txt",
     "load_scene",
     "make_views",
+    "make_sensors",
+    "Sensor",
+    "RtSensor",
     "pack_rays",
     "rays",
     "RAY_DTYPE",

@@ -65,6 +65,18 @@ class RtView(C.Structure):  # rt_render_views: one camera view (64 bytes)
     _fields_ = [("camera", RtCamera), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class RtSensor(C.Structure):  # rt_render_sensors / rt_sensor_rays / rt_accum_create_sensor: one sensor (96 bytes)
+    _fields_ = [
+        ("camera", RtCamera),
+        ("kind", C.c_uint32),
+        ("half_width", C.c_float),
+        ("lens_radius", C.c_float),
+        ("focus_distance", C.c_float),
+        ("reserved", C.c_uint32 * 5),
+        ("seed", C.c_uint64),
+    ]
+
+
 class RtRay(C.Structure):  # rt_render_rays: one caller-supplied ray and its RNG stream (32 bytes)
     _fields_ = [("origin", C.c_float * 3), ("dir", C.c_float * 3), ("stream", C.c_uint32), ("first_sample", C.c_uint32)]
 
@@ -242,6 +254,10 @@ ABI_PROTOTYPES = {
     "rt_render_views_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtView), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_render_rays": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_render_rays_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_render_sensors": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtSensor), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_render_sensors_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtSensor), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_sensor_rays": (C.c_int, [C.c_void_p, C.POINTER(RtSensor), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_accum_create_sensor": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtSensor), C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_accum_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtCamera), C.c_uint64, C.POINTER(C.c_void_p)]),
     "rt_accum_destroy": (None, [C.c_void_p]),
     "rt_accum_render": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtStats)]),

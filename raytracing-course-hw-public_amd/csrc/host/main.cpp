@@ -20,6 +20,10 @@
 // progressive call (rt_accum_render). RT_AOV=<prefix> (with or without RT_DENOISE: it renders through a feature accumulator too) also writes
 // the first-hit feature means: <prefix>_albedo.ppm (clamp(a, 0, 1) * 255 + 0.5, truncated), <prefix>_normal.ppm (0.5 * n + 0.5, quantised
 // likewise) and <prefix>_depth.pfm (one channel "Pf", little-endian floats, rows bottom to top as PFM has them).
+// RT_CAMERA=pinhole|equirect|fisheye|ortho|thinlens: render the file's camera through a sensor model evaluated on the device (rt_abi.h
+// rt_sensor), on one GPU, with RT_SEED as its seed: rt_render_sensors_rgb8, or rt_accum_create_sensor where RT_ADAPTIVE / RT_DENOISE / RT_AOV ask
+// for an accumulator. RT_CAMERA_FOV_DEG replaces the camera's horizontal field of view (pinhole, fisheye, thinlens); RT_ORTHO_HALF_WIDTH
+// (default 1), RT_LENS_RADIUS (default 0) and RT_FOCUS_DISTANCE (default 1) are the sensor's fields. Unset: exactly the path above.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -84,8 +88,9 @@ int main(int argc, char **argv) {
     const bool denoise = env_on("RT_DENOISE");
     const char *aov = std::getenv("RT_AOV");
     const bool accumulate = adaptive || denoise || aov;
+    const char *camera_kind = std::getenv("RT_CAMERA"); // sensors are evaluated on one GPU
     rt_scene *scene = nullptr;
-    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !accumulate ? RT_ALL_DEVICES : 0);
+    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !accumulate && !camera_kind ? RT_ALL_DEVICES : 0);
     rt_scene_desc desc = *rt_loaded_desc(loaded); // the arrays stay the loader's; only the build options change
     if (env_on("RT_BVH_DEVICE"))
         desc.build_flags |= RT_BUILD_DEVICE_LBVH;
@@ -147,6 +152,28 @@ int main(int argc, char **argv) {
     rt_stats st{};
     const char *film = std::getenv("RT_FILM");
     int rc = RT_ERR_UNSUPPORTED;
+    rt_sensor sensor{};
+    if (camera_kind) {
+        static const char *const names[] = {"pinhole", "equirect", "fisheye", "ortho", "thinlens"};
+        uint32_t kind = 0;
+        while (kind < 5 && std::strcmp(camera_kind, names[kind]) != 0)
+            ++kind;
+        if (kind == 5 || !views.empty() || p.rng_mode != RT_RNG_DEVICE) {
+            rt_destroy(scene);
+            rt_loaded_free(loaded);
+            std::cerr << "RT_CAMERA: pinhole, equirect, fisheye, ortho or thinlens; the scene's camera only (not with RT_ALL_CAMERAS), device RNG only" << std::endl;
+            return EXIT_FAILURE;
+        }
+        sensor.camera = desc.camera;
+        if (const char *v = std::getenv("RT_CAMERA_FOV_DEG"))
+            sensor.camera.fov_x = std::strtof(v, nullptr) * (3.14159265358979323846f / 180.0f);
+        sensor.kind = kind;
+        const char *hw = std::getenv("RT_ORTHO_HALF_WIDTH"), *lr = std::getenv("RT_LENS_RADIUS"), *fd = std::getenv("RT_FOCUS_DISTANCE");
+        sensor.half_width = hw ? std::strtof(hw, nullptr) : 1.0f;
+        sensor.lens_radius = lr ? std::strtof(lr, nullptr) : 0.0f;
+        sensor.focus_distance = fd ? std::strtof(fd, nullptr) : 1.0f;
+        sensor.seed = p.seed;
+    }
     uint32_t rounds = 0;
     std::vector<uint32_t> spp_map;
     std::vector<float> aov_albedo, aov_normal, aov_depth;
@@ -158,7 +185,8 @@ int main(int argc, char **argv) {
             return EXIT_FAILURE;
         }
         rt_accum *acc = nullptr;
-        rc = rt_accum_create_ex(scene, width, height, nullptr, p.seed, (denoise || aov) ? RT_ACCUM_FEATURES : 0u, &acc);
+        const uint32_t accum_flags = (denoise || aov) ? RT_ACCUM_FEATURES : 0u;
+        rc = camera_kind ? rt_accum_create_sensor(scene, width, height, &sensor, accum_flags, &acc) : rt_accum_create_ex(scene, width, height, nullptr, p.seed, accum_flags, &acc);
         if (rc == RT_OK && adaptive) {
             rt_adaptive ad{};
             ad.threshold = std::strtof(adaptive, nullptr);
@@ -191,9 +219,17 @@ int main(int argc, char **argv) {
         }
         if (acc)
             rt_accum_destroy(acc);
+    } else if (camera_kind) {
+        rc = (film && !std::strcmp(film, "host")) ? RT_ERR_UNSUPPORTED : rt_render_sensors_rgb8(scene, &p, &sensor, 1, rgb8.data(), &st);
+        if (rc == RT_ERR_UNSUPPORTED) { // RT_FILM=host, or the device film declined: the float image and the host film
+            std::vector<float> fb(view_pixels * 3, 0.0f);
+            rc = rt_render_sensors(scene, &p, &sensor, 1, fb.data(), &st);
+            if (rc == RT_OK)
+                rt_tonemap_rgb8(fb.data(), view_pixels, rgb8.data());
+        }
     } else if (!(film && !std::strcmp(film, "host")))
         rc = views.empty() ? rt_render_rgb8(scene, &p, rgb8.data(), &st) : rt_render_views_rgb8(scene, &p, views.data(), (uint32_t)views.size(), rgb8.data(), &st);
-    if (rc == RT_ERR_UNSUPPORTED && !accumulate) {
+    if (rc == RT_ERR_UNSUPPORTED && !accumulate && !camera_kind) {
         std::vector<float> fb(n_out * view_pixels * 3, 0.0f);
         rc = views.empty() ? rt_render(scene, &p, fb.data(), &st) : rt_render_views(scene, &p, views.data(), (uint32_t)views.size(), fb.data(), &st);
         if (rc == RT_OK)

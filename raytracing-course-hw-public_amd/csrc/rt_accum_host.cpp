@@ -14,6 +14,9 @@ struct rt_accum {
     uint32_t width = 0, height = 0;
     WfView view{};            // camera, tangents and seed (host copy of d_view)
     WfView *d_view = nullptr; // WfLaunch::views of its passes: the one view
+    bool has_sensor = false;  // rt_accum_create_sensor: the passes read `d_sensor` (WfSensors::table) instead of d_view
+    WfSensor sensor{};        // host copy of d_sensor
+    WfSensor *d_sensor = nullptr;
     rt::AccumRound R{};
     std::vector<void *> owned;
     rt::PacketPolicy pkt; // of its own passes, kept apart from rt_render's
@@ -45,7 +48,8 @@ extern "C" int rt_accum_create(rt_scene *s, uint32_t width, uint32_t height, con
     return rt_accum_create_ex(s, width, height, camera, seed, 0u, out);
 }
 
-extern "C" int rt_accum_create_ex(rt_scene *s, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, uint32_t accum_flags, rt_accum **out) {
+// rt_accum_create_ex ({camera, seed}; `sensor` null) and rt_accum_create_sensor (`sensor`; camera and seed not read)
+static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, const rt_sensor *sensor, uint32_t accum_flags, rt_accum **out) {
     if (!s || !out)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create: null argument");
     *out = nullptr;
@@ -60,7 +64,15 @@ extern "C" int rt_accum_create_ex(rt_scene *s, uint32_t width, uint32_t height, 
     a->scene = s;
     a->width = width;
     a->height = height;
-    a->view = rt::make_view(camera ? *camera : s->cam, width, height, seed);
+    if (sensor) {
+        if (int rc = rt::check_sensor(*sensor, width, height, "rt_accum_create_sensor"); rc != RT_OK)
+            return rc;
+        a->has_sensor = true;
+        a->sensor = rt::make_sensor(*sensor, width, height);
+        a->view = rt::make_view(sensor->camera, width, height, sensor->seed);
+    } else {
+        a->view = rt::make_view(camera ? *camera : s->cam, width, height, seed);
+    }
     const size_t n = (size_t)width * height;
     auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int { return accum_alloc(a.get(), bytes, ptr, "rt_accum_create"); };
     rt::AccumRound &R = a->R;
@@ -72,7 +84,7 @@ extern "C" int rt_accum_create_ex(rt_scene *s, uint32_t width, uint32_t height, 
         (rc = alloc(4 * n, &R.err)) != RT_OK || (rc = alloc(4 * n, &R.target)) != RT_OK || (rc = alloc(8 * n, &R.scan_in)) != RT_OK ||
         (rc = alloc(8 * n, &R.scan)) != RT_OK || (rc = alloc(4 * n, &R.list_pix)) != RT_OK || (rc = alloc(4 * n, &R.list_base)) != RT_OK ||
         (rc = alloc(4 * (n + 1), &R.list_off)) != RT_OK || (rc = alloc(8, &R.totals)) != RT_OK || (rc = alloc(R.scan_temp_bytes, &R.scan_temp)) != RT_OK ||
-        (rc = alloc(sizeof(WfView), &a->d_view)) != RT_OK)
+        (rc = alloc(sizeof(WfView), &a->d_view)) != RT_OK || (rc = alloc(sizeof(WfSensor), &a->d_sensor)) != RT_OK)
         return rc;
     if (accum_flags & RT_ACCUM_FEATURES) {
         WfFeat &F = a->F;
@@ -90,11 +102,24 @@ extern "C" int rt_accum_create_ex(rt_scene *s, uint32_t width, uint32_t height, 
     HIP_TRY(hipMemsetAsync(R.count, 0, 4 * n, s->stream));
     HIP_TRY(hipMemsetD32Async(R.err, 0x7F800000 /* +inf: n_p < 2 */, n, s->stream));
     HIP_TRY(hipMemcpyAsync(a->d_view, &a->view, sizeof(WfView), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(a->d_sensor, &a->sensor, sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     a->counted = true;
     ++s->live_accums; // rt_update_geometry refuses the scene while this one lives
     *out = a.release();
     return RT_OK;
+}
+
+extern "C" int rt_accum_create_ex(rt_scene *s, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, uint32_t accum_flags, rt_accum **out) {
+    return accum_create(s, width, height, camera, seed, nullptr, accum_flags, out);
+}
+
+extern "C" int rt_accum_create_sensor(rt_scene *s, uint32_t width, uint32_t height, const rt_sensor *sensor, uint32_t accum_flags, rt_accum **out) {
+    if (out)
+        *out = nullptr;
+    if (!sensor)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create_sensor: null argument");
+    return accum_create(s, width, height, nullptr, 0, sensor, accum_flags, out);
 }
 
 extern "C" void rt_accum_destroy(rt_accum *acc) { delete acc; }
@@ -144,6 +169,9 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
     W.view_pixels = n_pix;
     W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
     W.stats = counters ? s->d_stats : nullptr;
+    const WfSensors sensor_table{a->d_sensor};
+    // the one origin of the pass's rays, where it has one (rt_render.cpp launch_pass)
+    const float *cam_pos = !a->has_sensor ? a->view.pos : rt::sensor_single_origin(a->sensor.kind) ? a->sensor.pos : nullptr;
     s->ext_events.reset();
     uint32_t passes = 0, packet_passes = 0, rounds = 0;
     uint64_t added = 0;
@@ -179,7 +207,8 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 W.n_paths = (uint32_t)std::min<uint64_t>((uint64_t)A.n_entries * C, tot[1]); // an upper bound: wf_generate_list reads the exact count
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
-                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr, nullptr, a->view.pos));
+                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr, nullptr, cam_pos,
+                                        a->has_sensor ? &sensor_table : nullptr));
                 passes += 1;
                 packet_passes += W.use_packet;
                 if (p->progress && !ad) {

@@ -6,13 +6,24 @@ namespace {
 
 // gen_ray (raytracer.h:527-538): the two jitter draws, the screen position and the normalised direction of a sample of pixel `pix`, with the
 // tangents hoisted. The megakernel and the wavefront pipeline both call this, so their primary rays are the same operation sequence.
-template <class R> DEV V3 gen_ray_dir(R &rng, uint32_t pix, uint32_t width, uint32_t height, float tan_x, float tan_y, V3 cam_right, V3 cam_up, V3 cam_fwd) {
+// In three steps, each with one definition, because the sensor models (rt_dev_sensor.h) share the first with every kind and the second with
+// the thin lens: the jittered film position in [-1, 1]^2, the screen point in front of the camera, its normalisation.
+template <class R> DEV void gen_ray_film(R &rng, uint32_t pix, uint32_t width, uint32_t height, float &nx, float &ny) {
     const uint32_t x = pix % width, y = pix / width;
     float ox = uniform_real(rng, 0.0f, 1.0f);
     float oy = uniform_real(rng, 0.0f, 1.0f);
-    float sx = (2 * ((float)(int)x + ox) / (float)width - 1) * tan_x;
-    float sy = (2 * ((float)(int)y + oy) / (float)height - 1) * tan_y;
-    return norm(sx * cam_right - sy * cam_up + 1.0f * cam_fwd);
+    nx = 2 * ((float)(int)x + ox) / (float)width - 1;
+    ny = 2 * ((float)(int)y + oy) / (float)height - 1;
+}
+DEV V3 gen_ray_screen(float nx, float ny, float tan_x, float tan_y, V3 cam_right, V3 cam_up, V3 cam_fwd) {
+    float sx = nx * tan_x;
+    float sy = ny * tan_y;
+    return sx * cam_right - sy * cam_up + 1.0f * cam_fwd;
+}
+template <class R> DEV V3 gen_ray_dir(R &rng, uint32_t pix, uint32_t width, uint32_t height, float tan_x, float tan_y, V3 cam_right, V3 cam_up, V3 cam_fwd) {
+    float nx, ny;
+    gen_ray_film(rng, pix, width, height, nx, ny);
+    return norm(gen_ray_screen(nx, ny, tan_x, tan_y, cam_right, cam_up, cam_fwd));
 }
 
 // ---------------------------------------------------------------------------------------------- sampling + BRDF

@@ -324,6 +324,27 @@ struct WfRays {
     uint64_t seed;         // rt_params.seed
 };
 
+// One sensor of rt_render_sensors / rt_accum_create_sensor (rt_abi.h rt_sensor: the rule): WfView's fields in WfView's places, then the kind
+// and what the host hoists for it (rt_sensor.cpp make_sensor, the one place that fills it). One 128-byte record per sensor, a table in HBM
+// beside the view table; the sensor first stages (rt_wavefront.hip wf_generate_sensor*) and the rt_sensor_rays writer take it as their own
+// argument, so WfLaunch, WfView and the camera kernels do not know about it.
+struct alignas(64) WfSensor {
+    float pos[3], right[3], up[3], fwd[3];
+    float tan_x, tan_y;   // rt::make_view's
+    uint64_t seed;
+    uint32_t kind;        // RT_SENSOR_*
+    float half_fov;       // fov_x / 2 (FISHEYE)
+    float half_width;     // ORTHOGRAPHIC
+    float half_h;         // half_width * (float)H / (float)W
+    float lens_radius;    // THIN_LENS
+    float focus_distance; // THIN_LENS
+    uint32_t pad[10];
+};
+static_assert(sizeof(WfSensor) == 128, "WfSensor must be 128 bytes");
+struct WfSensors {
+    const WfSensor *table; // [n_sensors]: the sensor of virtual pixel p is table[p / WfLaunch::view_pixels]
+};
+
 struct RenderLaunch {
     uint32_t width, height, samples, rng_mode;
     uint64_t seed;

@@ -67,9 +67,16 @@ struct WfHostSync {
 // wf_resolve; first_pass / last_pass are not read. Null for rt_render. `feat` (optional, with `acc`): the pass of a feature accumulator:
 // wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither.
 // `rays` (optional, without `acc`): a pass of rt_render_rays: wf_generate_rays replaces wf_generate; wf_fold and wf_resolve are rt_render's.
+// `sensors` (optional, without `rays`): the pass's primary rays come from the sensor table (rt_abi.h rt_sensor) instead of L.views:
+// wf_generate_sensor / wf_generate_list_sensor replace wf_generate / wf_generate_list; everything behind the first stage is unchanged.
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
-                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr);
+                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr,
+                                 const WfSensors *sensors = nullptr);
+// rt_sensor_rays: the n = pixels x samples rt_ray records of pixels [first_pixel, ..) x samples [first_sample, first_sample + samples) of
+// the sensor record `d_sensor` (device) -> `d_rays_out` (device, 32 B per record, 16-byte aligned)
+hipError_t launch_sensor_rays(const WfSensor *d_sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples, uint32_t n,
+                              void *d_rays_out, int num_cus, hipStream_t stream);
 // closest-hit probe through the renderer's own kernels: `rays` (6 floats each, device) -> queue -> wf_extend (or wf_extend_packet)
 // -> prim / bct (device). `L` carries the workspace (paths_in, hits, counters, stack_overflow, stats) and the traversal mode.
 hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *rays, uint32_t n, bool packet, bool stats, uint32_t *prim, float *bct,

@@ -168,9 +168,10 @@ static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float 
 // policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays*). `acc`: an
 // accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays (rt_kernels.h).
 // `cam_pos`: the pass's primary rays are camera rays of ONE view and this is its position, the three floats wf_primary_ray stores as every
-// ray's origin; null where no such position exists (several views, a caller's rays).
+// ray's origin; null where no such position exists (several views, a caller's rays, a sensor whose rays start on a film or a lens).
+// `sensors`: the primary rays come from this sensor table instead of W.views (rt_sensor.cpp).
 hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos) {
+                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos, const WfSensors *sensors) {
     // Small passes are bound by launch and host latency, not by memory (a 256 x 256 x 4 render, BASELINE config 1's
     // shape, spent 5.7 ms at 0.6 ms per bounce): RT_SORT_AUTO leaves a pass of fewer than 2^20 paths unsorted, which also spares it
     // the per-bounce queue-size read-back the sort needs: the whole pass is queued without a single host wait.
@@ -198,7 +199,7 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     const rt::WfHostSync hsync = wavefront_host_sync(s);
     unsigned long long census[2] = {0ull, 0ull};
     const hipError_t e = rt::launch_wavefront_pass(s->dev, W, W.stats != nullptr, s->num_cus, first_pass, last_pass, s->stream, time_extends ? &s->ext_events : nullptr, census,
-                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays);
+                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays, sensors);
     if (e == hipSuccess && census[0] != 0ull) {
         pol.lanes_x100 = (uint32_t)(100.0 * (double)census[1] / (double)census[0]);
         if ((double)census[1] < min_lanes * (double)census[0])
@@ -243,7 +244,10 @@ int rt::fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms
 // views == nullptr: rt_render, the one view of the scene's own camera with rt_params.seed. Otherwise the n_views views render as ONE
 // view-major virtual image of n_views * height rows: the wavefront pipeline plans its passes over it and reads each path's camera from
 // the view table; the megakernel runs view by view.
-static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, uint32_t n_views, float *fb_rgb, uint8_t *rgb8_out, rt_stats *stats) {
+// `sensors`: rt_render_sensors*: the sensor table takes the view table's place (views is null; n_views counts the sensors), the passes are
+// wavefront passes (rt_sensor.cpp has refused everything else) and the packet policy is the scene's own for sensors of that kind.
+int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, const std::vector<WfSensor> *sensors, uint32_t n_views, float *fb_rgb, uint8_t *rgb8_out,
+                     rt_stats *stats) {
     if (!s || !p || (!fb_rgb && !rgb8_out))
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render: null argument");
     if (views)
@@ -251,7 +255,7 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
             return rc;
     if (s->group)
         return rt::group_render(s->group, p, views, n_views, fb_rgb, rgb8_out, stats);
-    if (!views)
+    if (!views && !sensors)
         n_views = 1;
     if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= 0x7FFFFFFFull)
         return rt::fail(RT_ERR_INVALID_ARG, "Illegal image size" + std::to_string(p->width) + "x" + std::to_string(p->height)); // image.h:26
@@ -299,7 +303,7 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
     L.n_items = (uint32_t)items;
     // the view table: camera, tangents and seed per view
     std::vector<WfView> vt(n_views);
-    for (uint32_t v = 0; v < n_views; ++v)
+    for (uint32_t v = 0; v < n_views && !sensors; ++v)
         vt[v] = views ? rt::make_view(views[v].camera, p->width, p->height, views[v].seed) : rt::make_view(s->cam, p->width, p->height, p->seed);
     L.tan_x = vt[0].tan_x;
     L.tan_y = vt[0].tan_y;
@@ -334,6 +338,7 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
                                             "the reference-RNG parity mode walk the reference's binary tree: create the scene without RT_BUILD_WIDE)");
     s->ext_events.reset();
     uint32_t passes = 0, packet_passes = 0; // rt_stats.passes / packet_passes
+    rt::PacketPolicy &pol = !sensors ? s->pkt : s->pkt_sensor[n_views == 1 ? (*sensors)[0].kind : 5u];
     auto queue_render = [&]() -> int {
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
     if (L.n_items > 0 && wavefront) {
@@ -343,10 +348,16 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
         const uint32_t pass_spp = (uint32_t)std::clamp<uint64_t>(max_paths / tile_pixels, 1, p->samples);
         int rc = s->ensure_wavefront(tile_pixels * pass_spp, tile_pixels, s->dev.ray_depth);
         if (rc == RT_OK)
-            rc = s->ensure_views(n_views);
+            rc = sensors ? s->ensure_sensors(n_views) : s->ensure_views(n_views);
         if (rc != RT_OK)
             return rc;
-        HIP_TRY(hipMemcpyAsync(s->d_views, vt.data(), n_views * sizeof(WfView), hipMemcpyHostToDevice, s->stream)); // `vt` outlives the stream sync below
+        if (sensors) // the caller's table outlives the stream sync below, and so does `vt`
+            HIP_TRY(hipMemcpyAsync(s->d_sensors, sensors->data(), n_views * sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
+        else
+            HIP_TRY(hipMemcpyAsync(s->d_views, vt.data(), n_views * sizeof(WfView), hipMemcpyHostToDevice, s->stream));
+        const WfSensors sensor_table{s->d_sensors};
+        // one origin for every ray of the pass: one view, or one sensor of a kind that keeps the camera position as the origin
+        const float *cam_pos = n_views != 1 ? nullptr : !sensors ? vt[0].pos : rt::sensor_single_origin((*sensors)[0].kind) ? (*sensors)[0].pos : nullptr;
         WfLaunch W{};
         W.width = p->width;
         W.height = p->height;
@@ -355,7 +366,7 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
         W.shard_count = L.shard_count;
         W.shard_block = L.shard_block;
         W.ray_depth = s->dev.ray_depth;
-        W.views = s->d_views;
+        W.views = sensors ? nullptr : s->d_views;
         W.view_pixels = view_pixels;
         s->wf_bind(W);
         W.fb = d_fb;
@@ -382,8 +393,8 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
                 W.first_sample = s0;
                 W.pass_samples = std::min<uint32_t>(pass_spp, p->samples - s0);
                 W.n_paths = W.pass_pixels * W.pass_samples;
-                HIP_TRY(rt::launch_pass(s, p, s->pkt, W, n_views, s0 == 0, s0 + W.pass_samples >= p->samples, stats != nullptr, nullptr, nullptr, nullptr,
-                                        n_views == 1 ? vt[0].pos : nullptr));
+                HIP_TRY(rt::launch_pass(s, p, pol, W, n_views, s0 == 0, s0 + W.pass_samples >= p->samples, stats != nullptr, nullptr, nullptr, nullptr, cam_pos,
+                                        sensors ? &sensor_table : nullptr));
                 passes += 1;
                 packet_passes += W.use_packet;
                 if (p->progress) {
@@ -475,7 +486,7 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
             stats->dominant_launches = passes;
             stats->dominant_ms = ms;
         }
-        stats->packet_lanes_x100 = wavefront ? s->pkt.lanes_x100 : 0u; // the packet kernel's census (lanes served per trip x 100; 0 = it did not run)
+        stats->packet_lanes_x100 = wavefront ? pol.lanes_x100 : 0u; // the packet kernel's census (lanes served per trip x 100; 0 = it did not run)
         stats->passes = passes;
         stats->packet_passes = packet_passes;
     }
@@ -485,25 +496,25 @@ static int render_impl(rt_scene *s, const rt_params *p, const rt_view *views, ui
 extern "C" int rt_render(rt_scene *s, const rt_params *p, float *fb_rgb, rt_stats *stats) {
     if (!fb_rgb)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render: null argument");
-    return render_impl(s, p, nullptr, 0, fb_rgb, nullptr, stats);
+    return rt::render_image(s, p, nullptr, nullptr, 0, fb_rgb, nullptr, stats);
 }
 
 extern "C" int rt_render_rgb8(rt_scene *s, const rt_params *p, uint8_t *rgb8, rt_stats *stats) {
     if (!rgb8)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render_rgb8: null argument");
-    return render_impl(s, p, nullptr, 0, nullptr, rgb8, stats);
+    return rt::render_image(s, p, nullptr, nullptr, 0, nullptr, rgb8, stats);
 }
 
 extern "C" int rt_render_views(rt_scene *s, const rt_params *p, const rt_view *views, uint32_t n_views, float *fb_rgb, rt_stats *stats) {
     if (!fb_rgb || !views || n_views == 0)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render_views: null argument or no view");
-    return render_impl(s, p, views, n_views, fb_rgb, nullptr, stats);
+    return rt::render_image(s, p, views, nullptr, n_views, fb_rgb, nullptr, stats);
 }
 
 extern "C" int rt_render_views_rgb8(rt_scene *s, const rt_params *p, const rt_view *views, uint32_t n_views, uint8_t *rgb8, rt_stats *stats) {
     if (!rgb8 || !views || n_views == 0)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render_views_rgb8: null argument or no view");
-    return render_impl(s, p, views, n_views, nullptr, rgb8, stats);
+    return rt::render_image(s, p, views, nullptr, n_views, nullptr, rgb8, stats);
 }
 
 extern "C" int rt_film_rgb8(rt_scene *s, const float *rgb, size_t n_pixels, uint8_t *out_rgb8) {

@@ -182,6 +182,22 @@ struct rt_scene {
         views_capacity = n;
         return RT_OK;
     }
+    // the sensor table of rt_render_sensors* / the one record of rt_sensor_rays (WfSensors::table), grown on demand
+    WfSensor *d_sensors = nullptr;
+    uint32_t sensors_capacity = 0;
+    int ensure_sensors(uint32_t n) {
+        if (sensors_capacity >= n)
+            return RT_OK;
+        if (d_sensors)
+            (void)hipFree(d_sensors);
+        d_sensors = nullptr;
+        sensors_capacity = 0;
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, (size_t)n * sizeof(WfSensor)));
+        d_sensors = static_cast<WfSensor *>(q);
+        sensors_capacity = n;
+        return RT_OK;
+    }
     // the device copy of a host ray buffer (rt_render_rays), grown on demand
     void *d_rays = nullptr;
     size_t rays_capacity = 0; // bytes
@@ -216,6 +232,7 @@ struct rt_scene {
     uint32_t *wf_host_count = nullptr; // pinned, 48 words: queue size per bounce, then wf_extend_packet's census (rt_kernels.h WfHostSync)
     std::vector<hipEvent_t> wf_count_events; // one per bounce: "the size of the queue entering this bounce has reached wf_host_count"
     rt::PacketPolicy pkt; // of rt_render* (an accumulator keeps its own)
+    rt::PacketPolicy pkt_sensor[6]; // of rt_render_sensors*: one per kind for a single sensor, [5] for several: a panorama's census never switches rt_render's packets off
     std::vector<hipEvent_t> pass_events; // rt_params.progress: one per pass
 
     // The camera-relative copy of the binary scene tree's records (WfLaunch::rel_nodes / rel_tris): part of the wavefront workspace, made by
@@ -341,6 +358,8 @@ struct rt_scene {
             (void)hipFree(d_views);
         if (d_rays)
             (void)hipFree(d_rays);
+        if (d_sensors)
+            (void)hipFree(d_sensors);
         if (d_film_table)
             (void)hipFree(d_film_table);
         ext_events.destroy();
@@ -370,7 +389,16 @@ void set_camera(DevScene &D, const float *pos, const float *right, const float *
 int check_pass_params(const rt_params *p, const char *fn);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
 hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr);
+                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr,
+                       const WfSensors *sensors = nullptr);
+// rt_render / rt_render_views (`views`, may be null) / rt_render_sensors (`sensors`, may be null: the checked records of rt_sensor.cpp; then
+// `views` is null and n_views counts the sensors): the one pass loop behind every entry point that renders an image
+int render_image(rt_scene *s, const rt_params *p, const rt_view *views, const std::vector<WfSensor> *sensors, uint32_t n_views, float *fb_rgb, uint8_t *rgb8_out,
+                 rt_stats *stats);
+// rt_sensor.cpp: the argument checks of one rt_sensor, its device record, and which kinds share one ray origin
+int check_sensor(const rt_sensor &sn, uint32_t width, uint32_t height, const char *fn);
+WfSensor make_sensor(const rt_sensor &sn, uint32_t width, uint32_t height);
+bool sensor_single_origin(uint32_t kind);
 int fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats);
 
 // Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are

@@ -1,0 +1,127 @@
+// rt_sensor.cpp — the sensor models of rt_abi.h rt_sensor on the host: the argument checks, the one place that fills a sensor record
+// (make_sensor, next to rt::make_view whose fields it starts with), rt_render_sensors* (rt_render's own pass loop, rt_render.cpp
+// render_image, with the sensor table in the view table's place) and rt_sensor_rays. rt_accum_create_sensor is in rt_accum_host.cpp.
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+
+#include "rt_scene_impl.h"
+
+// What every entry point refuses of a sensor at a width x height image (`fn`: its name). Needs no device.
+int rt::check_sensor(const rt_sensor &sn, uint32_t width, uint32_t height, const char *fn) {
+    const std::string name(fn);
+    if (sn.kind > RT_SENSOR_THIN_LENS)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown sensor kind " + std::to_string(sn.kind));
+    for (uint32_t r : sn.reserved)
+        if (r != 0)
+            return rt::fail(RT_ERR_INVALID_ARG, name + ": reserved words of rt_sensor must be 0");
+    if (sn.kind == RT_SENSOR_ORTHOGRAPHIC && !(std::isfinite(sn.half_width) && sn.half_width > 0.0f))
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": an orthographic sensor needs a finite half_width > 0");
+    if (sn.kind == RT_SENSOR_THIN_LENS && (!(std::isfinite(sn.lens_radius) && sn.lens_radius >= 0.0f) || !(std::isfinite(sn.focus_distance) && sn.focus_distance > 0.0f)))
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": a thin-lens sensor needs a finite lens_radius >= 0 and a finite focus_distance > 0");
+    if (sn.kind == RT_SENSOR_FISHEYE) {
+        // the angle off axis is r * half_fov with r up to the corner's sqrt(1 + (H/W)^2): it must stay a valid sine argument and a live pixel
+        const float half_fov = sn.camera.fov_x / 2;
+        const double aspect = width ? (double)height / (double)width : 0.0;
+        if (!(std::isfinite(half_fov) && half_fov > 0.0f) || (double)half_fov * std::sqrt(1.0 + aspect * aspect) > 3.14159265358979323846)
+            return rt::fail(RT_ERR_INVALID_ARG, name + ": a fisheye sensor needs fov_x > 0 and a corner at most 180 degrees off axis: (fov_x / 2) * sqrt(1 + (H/W)^2) <= pi");
+    }
+    return RT_OK;
+}
+
+// The sensor record of one rt_sensor at a width x height image: WfView's fields from rt::make_view, the kind and its hoisted terms.
+WfSensor rt::make_sensor(const rt_sensor &sn, uint32_t width, uint32_t height) {
+    const WfView v = rt::make_view(sn.camera, width, height, sn.seed);
+    WfSensor r{};
+    static_assert(offsetof(WfSensor, kind) == sizeof(WfView), "WfSensor starts with WfView's fields");
+    std::memcpy(&r, &v, sizeof(v));
+    r.kind = sn.kind;
+    r.half_fov = sn.camera.fov_x / 2;
+    r.half_width = sn.half_width;
+    r.half_h = sn.half_width * (float)height / (float)width;
+    r.lens_radius = sn.lens_radius;
+    r.focus_distance = sn.focus_distance;
+    return r;
+}
+
+// the kinds whose rays all start at the camera position, bit for bit: their packets may walk the camera-relative records
+bool rt::sensor_single_origin(uint32_t kind) { return kind == RT_SENSOR_PINHOLE || kind == RT_SENSOR_EQUIRECT || kind == RT_SENSOR_FISHEYE; }
+
+static int render_sensors_impl(rt_scene *s, const rt_params *p, const rt_sensor *sensors, uint32_t n_sensors, float *fb_rgb, uint8_t *rgb8, rt_stats *stats, const char *fn) {
+    const std::string name(fn);
+    if (!s || !p || !sensors || n_sensors == 0 || (!fb_rgb && !rgb8))
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": null argument or no sensor");
+    if (s->group)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": sensors render on single-GPU scenes only");
+    if (p->flags & ~(uint32_t)(RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST))
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown flag");
+    if (p->flags & RT_FLAG_MEGAKERNEL)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": sensors are evaluated by the wavefront pipeline, not the megakernel");
+    if (p->rng_mode == RT_RNG_REFERENCE)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": the reference RNG draws a 256-pixel span as one sequential stream; sensors need RT_RNG_DEVICE");
+    if (p->shard_count > 1)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": shard_count > 1 does not apply to a sensor render");
+    if (p->width == 0 || p->height == 0 || (uint64_t)n_sensors * p->width * p->height >= 0x7FFFFFFFull)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": the image is empty, or n_sensors x width x height reaches 2^31");
+    for (uint32_t v = 0; v < n_sensors; ++v)
+        if (int rc = rt::check_sensor(sensors[v], p->width, p->height, fn); rc != RT_OK)
+            return rc;
+    std::vector<WfSensor> table(n_sensors);
+    for (uint32_t v = 0; v < n_sensors; ++v)
+        table[v] = rt::make_sensor(sensors[v], p->width, p->height);
+    return rt::render_image(s, p, nullptr, &table, n_sensors, fb_rgb, rgb8, stats); // rng_mode, samples and the pass options: rt_render's checks
+}
+
+extern "C" int rt_render_sensors(rt_scene *s, const rt_params *p, const rt_sensor *sensors, uint32_t n_sensors, float *fb_rgb, rt_stats *stats) {
+    if (!fb_rgb)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_render_sensors: null argument");
+    return render_sensors_impl(s, p, sensors, n_sensors, fb_rgb, nullptr, stats, "rt_render_sensors");
+}
+
+extern "C" int rt_render_sensors_rgb8(rt_scene *s, const rt_params *p, const rt_sensor *sensors, uint32_t n_sensors, uint8_t *rgb8, rt_stats *stats) {
+    if (!rgb8)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_render_sensors_rgb8: null argument");
+    return render_sensors_impl(s, p, sensors, n_sensors, nullptr, rgb8, stats, "rt_render_sensors_rgb8");
+}
+
+extern "C" int rt_sensor_rays(rt_scene *s, const rt_sensor *sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t n_pixels, uint32_t first_sample,
+                              uint32_t samples, uint32_t flags, rt_ray *rays_out) {
+    if (!s || !sensor)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_sensor_rays: null argument");
+    if (s->group)
+        return rt::fail(RT_ERR_UNSUPPORTED, "rt_sensor_rays: sensors are evaluated on single-GPU scenes only");
+    if (flags & ~(uint32_t)RT_FLAG_DEVICE_FB)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_sensor_rays: flags other than RT_FLAG_DEVICE_FB");
+    if (width == 0 || height == 0 || (uint64_t)width * height >= 0x7FFFFFFFull)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_sensor_rays: image size " + std::to_string(width) + "x" + std::to_string(height));
+    if ((uint64_t)first_pixel + n_pixels > (uint64_t)width * height)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_sensor_rays: the pixel range ends past width x height");
+    const uint64_t n = (uint64_t)n_pixels * samples;
+    if (n >= 0x80000000ull)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_sensor_rays: n_pixels x samples must stay below 2^31");
+    if (int rc = rt::check_sensor(*sensor, width, height, "rt_sensor_rays"); rc != RT_OK)
+        return rc;
+    if (n == 0)
+        return RT_OK;
+    const bool device_out = (flags & RT_FLAG_DEVICE_FB) != 0;
+    if (!rays_out || (device_out && (reinterpret_cast<uintptr_t>(rays_out) & 15u) != 0))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_sensor_rays: null output, or a device buffer that is not 16-byte aligned");
+    HIP_TRY(hipSetDevice(s->device));
+    const WfSensor rec = rt::make_sensor(*sensor, width, height);
+    if (int rc = s->ensure_sensors(1); rc != RT_OK)
+        return rc;
+    void *d_out = rays_out;
+    if (!device_out) {
+        if (int rc = s->ensure_rays((size_t)n * sizeof(rt_ray)); rc != RT_OK)
+            return rc;
+        d_out = s->d_rays;
+    }
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(s->d_sensors, &rec, sizeof(rec), hipMemcpyHostToDevice, s->stream)); // `rec` outlives the stream sync below
+        HIP_TRY(rt::launch_sensor_rays(s->d_sensors, width, height, first_pixel, first_sample, samples, (uint32_t)n, d_out, s->num_cus, s->stream));
+        if (!device_out)
+            HIP_TRY(hipMemcpyAsync(rays_out, d_out, (size_t)n * sizeof(rt_ray), hipMemcpyDeviceToHost, s->stream));
+        return RT_OK;
+    };
+    return rt::queue_and_wait(s, queue);
+}

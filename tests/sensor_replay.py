@@ -1,0 +1,148 @@
+"""The sensor rule of include/rt_abi.h (rt_sensor) restated in numpy float32, one operation per statement: the CPU model the GPU's sensor
+rays are held to bit for bit (tests/test_gpu_sensors.py) and that is itself anchored to the oracle and to an independent float64
+evaluation (tests/test_sensor_replay.py).
+
+Every array is float32 and every scalar operand an np.float32, so each statement rounds once, as the device's statement does
+(-ffp-contract=off). The random draws come from oracle.xoshiro_sequence, sines and cosines from oracle.sincos (the restatement of
+rt_devspec.h the device evaluates), the two tangents from the host libm's tanf / atanf through rt::make_view's expression."""
+import ctypes
+import importlib
+
+import numpy as np
+
+f32 = np.float32
+PI_F = f32(3.14159265358979323846)
+LENS_XOR = 0x9E3779B97F4A7C15
+PINHOLE, EQUIRECT, FISHEYE, ORTHOGRAPHIC, THIN_LENS = range(5)
+KIND_NAMES = ("pinhole", "equirect", "fisheye", "orthographic", "thin_lens")
+
+_libm = ctypes.CDLL("libm.so.6")
+for _fn in (_libm.tanf, _libm.atanf):
+    _fn.restype = ctypes.c_float
+    _fn.argtypes = [ctypes.c_float]
+
+
+def ray_dtype():
+    return importlib.import_module("raytracing-course-hw-public_amd._ctypes_abi").RAY_DTYPE
+
+
+def tangents(fov_x, W, H):
+    """rt::make_view: tan_x = tan(fov_x / 2); fov_y = atan(tan(fov_x / 2) * H / W) * 2; tan_y = tan(fov_y / 2), float overloads."""
+    half = f32(f32(fov_x) / f32(2))
+    tan_x = f32(_libm.tanf(half))
+    t = f32(tan_x * f32(H))
+    t = f32(t / f32(W))
+    fov_y = f32(f32(_libm.atanf(t)) * f32(2))
+    tan_y = f32(_libm.tanf(f32(fov_y / f32(2))))
+    return tan_x, tan_y
+
+
+def _scale(a, v):
+    """a * V per component: (n,) x (3,) -> (n, 3)"""
+    return (a[:, None] * v[None, :]).astype(f32)
+
+
+def _norm(v):
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    xx = x * x
+    yy = y * y
+    zz = z * z
+    s = xx + yy
+    s = s + zz
+    ln = np.sqrt(s)
+    return (v / ln[:, None]).astype(f32)
+
+
+def _screen(nx, ny, tan_x, tan_y, R, U, F):
+    """gen_ray's screen point: (nx * tan_x) * R - (ny * tan_y) * U + 1.0f * F"""
+    sx = nx * tan_x
+    sy = ny * tan_y
+    q = _scale(sx, R) - _scale(sy, U)
+    return (q + (f32(1.0) * F)[None, :]).astype(f32)
+
+
+def sensor_rays(oracle, sensor, W, H, samples, first_pixel=0, n_pixels=None, first_sample=0, with_draws=False):
+    """RAY_DTYPE records of samples [first_sample, first_sample + samples) of pixels [first_pixel, first_pixel + n_pixels) of `sensor` (an
+    object with camera / kind / half_width / lens_radius / focus_distance / seed, e.g. the package's Sensor) at a W x H image: pixel-major,
+    stream = pixel, first_sample = sample index. `with_draws`: also a dict of the float32 draws and film terms the rays were made of."""
+    if n_pixels is None:
+        n_pixels = W * H - first_pixel
+    cam, kind, seed = sensor.camera, int(sensor.kind), int(sensor.seed)
+    P, R, U, F = (np.asarray(v, dtype=f32).reshape(3) for v in (cam.position, cam.right, cam.up, cam.forward))
+    n = n_pixels * samples
+    pix = (first_pixel + np.arange(n, dtype=np.int64) // samples).astype(np.uint32)
+    smp = (first_sample + np.arange(n, dtype=np.int64) % samples).astype(np.uint32)
+    jit = np.zeros((n, 2), dtype=f32)
+    for i in range(n):
+        jit[i] = oracle.xoshiro_sequence(seed, int(pix[i]), int(smp[i]), 2)
+    ox, oy = jit[:, 0], jit[:, 1]
+    x = (pix % np.uint32(W)).astype(f32)
+    y = (pix // np.uint32(W)).astype(f32)
+    nx = x + ox
+    nx = f32(2) * nx
+    nx = nx / f32(W)
+    nx = nx - f32(1)
+    ny = y + oy
+    ny = f32(2) * ny
+    ny = ny / f32(H)
+    ny = ny - f32(1)
+    tan_x, tan_y = tangents(cam.fov_x, W, H)
+    draws = dict(ox=ox, oy=oy, nx=nx, ny=ny, tan_x=tan_x, tan_y=tan_y, pix=pix, smp=smp)
+    o = np.tile(P, (n, 1)).astype(f32)
+    if kind == PINHOLE:
+        d = _norm(_screen(nx, ny, tan_x, tan_y, R, U, F))
+    elif kind == EQUIRECT:
+        a = nx + f32(1)
+        a = PI_F * a
+        p = ny + f32(1)
+        p = f32(PI_F * f32(0.5)) * p
+        sa, ca = oracle.sincos(a)
+        sp, cp = oracle.sincos(p)
+        cr = sp * sa
+        cf = sp * ca
+        v = _scale(-cr, R) + _scale(cp, U)
+        v = v + _scale(-cf, F)
+        d = _norm(v.astype(f32))
+    elif kind == FISHEYE:
+        half_fov = f32(f32(cam.fov_x) / f32(2))
+        px = nx
+        py = ny * f32(f32(H) / f32(W))
+        r = px * px
+        r = r + py * py
+        r = np.sqrt(r)
+        th = r * half_fov
+        st, ct = oracle.sincos(th)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ux = px / r
+            uy = py / r
+            v = _scale(st * ux, R) - _scale(st * uy, U)
+            v = v + _scale(ct, F)
+        v = np.where((r == 0)[:, None], F[None, :], v).astype(f32)
+        d = _norm(v)
+        draws.update(r=r, th=th)
+    elif kind == ORTHOGRAPHIC:
+        hw = f32(sensor.half_width)
+        hh = f32(hw * f32(H))
+        hh = f32(hh / f32(W))
+        o = o + _scale(nx * hw, R)
+        o = (o - _scale(ny * hh, U)).astype(f32)
+        d = np.tile(_norm(F[None, :]), (n, 1)).astype(f32)
+    elif kind == THIN_LENS:
+        q = _screen(nx, ny, tan_x, tan_y, R, U, F)
+        lens = np.zeros((n, 2), dtype=f32)
+        for i in range(n):
+            lens[i] = oracle.xoshiro_sequence(seed ^ LENS_XOR, int(pix[i]), int(smp[i]), 2)
+        l0, l1 = lens[:, 0], lens[:, 1]
+        rad = f32(sensor.lens_radius) * np.sqrt(l0)
+        sl, cl = oracle.sincos(f32(f32(2) * PI_F) * l1)
+        e = (_scale(rad * cl, R) + _scale(rad * sl, U)).astype(f32)
+        o = (o + e).astype(f32)
+        v = (f32(sensor.focus_distance) * q).astype(f32) - e
+        d = _norm(v.astype(f32))
+        draws.update(l0=l0, l1=l1, e=e)
+    else:
+        raise ValueError(f"unknown sensor kind {kind}")
+    out = np.zeros(n, dtype=ray_dtype())
+    out["origin"], out["dir"], out["stream"], out["first_sample"] = o, d, pix, smp
+    assert o.dtype == f32 and d.dtype == f32
+    return (out, draws) if with_draws else out
