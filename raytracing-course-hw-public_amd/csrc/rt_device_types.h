@@ -224,8 +224,9 @@ static_assert(WF_CNT_XCD + 7 * WF_CNT_XCD_STRIDE < WF_CNT_WORDS && WF_CNT_CENSUS
 // every ~13 ns chip-wide, and one per wave (64 rays) of a 30 M-ray bounce made that single counter the whole kernel's clock
 // (6.3 ms of 6.3 ms; profiles/r02_shade_atomic.txt). Wave slot w of the input queue (positions 64w..64w+63) appends to
 // sub-queue w % WF_STRIPES, whose region of paths_out is sized for all of its slots (nothing can overflow) and whose counter
-// has a cache line to itself. The regions' fill levels become a dense prefix (run_start) in wf_advance; the next bounce's
-// ray-order pass (wf_sort_keys) maps dense index -> physical slot, and wf_extend / wf_shade reach rays through `order` anyway.
+// has a cache line to itself. wf_extend / wf_shade reach rays through `order` anyway: a sorted bounce sorts the physical positions (the
+// gaps at the regions' ends hold pad keys, WfLaunch::emit_keys); for an unsorted one the regions' fill levels become a dense prefix
+// (run_start) in wf_advance and wf_sort_keys maps dense index -> physical slot.
 #define WF_STRIPES 64u
 #define WF_STRIPE_WORDS 32u /* one counter per 128-byte line */
 #define WF_STRIPE_BUF_WORDS (WF_STRIPES * WF_STRIPE_WORDS + WF_STRIPES + 1u) /* counters, then run_start[WF_STRIPES + 1] */
@@ -273,7 +274,7 @@ struct WfLaunch {
     uint32_t *stripes;       // WF_STRIPE_BUF_WORDS: the sub-queue fill counters of the running wf_shade, then run_start[] of paths_in
     const uint32_t *order;   // optional: position q processes queue slot order[q] & WF_ORDER_SLOT_MASK (coherence sort; extend AND shade); null = identity.
                              // Bits 30-31 carry the ray's NEXT sampler class (top bits of WfPath's path word) through the sort: wf_shade's lane assignment reads them
-    uint32_t *sort_keys[2];  // sort workspace: keys / slot indices, double buffered
+    uint32_t *sort_keys[2];  // sort workspace: keys / slot indices, double buffered; paths + 64 entries each (the sort covers whole wave slots)
     uint32_t *sort_vals[2];
     void *sort_temp;
     uint32_t use_packet;     // this pass's primary rays go through wf_extend_packet (rt_scene.cpp decides: RT_WF_PACKET, samples per
@@ -285,7 +286,10 @@ struct WfLaunch {
     uint32_t global_best;    // 0: the reference's traversal order and pruning (parity mode); 1: prune against the global best
                              // (RT_FLAG_GLOBAL_BEST, production traversal: a subset of the reference's node visits)
     uint32_t order_classed;  // `order` came through the ray-order sort and carries the class bits; 0: identity-like order (no sort ran), slots only
-    uint32_t sort_mode;      // 0: no ray-order sort; 1: sort the secondary bounces by wf_sort_keys' key (octant, 64^3 cell, sub-cone)
+    uint32_t emit_keys;      // wf_shade only: the next bounce may be sorted, so write the sort's input where the ray is made: sort_keys[0][p] = the ray-order
+                             // key (rt_ray_key.h), sort_vals[0][p] = slot p with the class above it, p = the physical slot of paths_out. The host has
+                             // filled sort_keys[0] with pad keys over every position the sub-queue regions can span (launch_wavefront_pass)
+    uint32_t sort_mode;      // 0: no ray-order sort; 1: sort the secondary bounces by the ray-order key (rt_ray_key.h: octant, 64^3 cell, sub-cone)
     size_t sort_temp_bytes;
     DevStats *stats;         // may be null
 };

@@ -271,9 +271,10 @@ struct rt_scene {
         wf_stack_stride = (uint32_t)num_cus * 8u * 256u; // the wf_extend grid: 8 blocks of 256 threads per CU
         if ((rc = alloc((size_t)RT_MAX_STACK * wf_stack_stride * 16, &wf_stack_overflow)) != RT_OK)
             return rc;
-        wf_sort_temp_bytes = rt::wavefront_sort_temp_bytes(paths);
-        if ((rc = alloc(paths * 4, (void **)&wf_sort_keys[0])) != RT_OK || (rc = alloc(paths * 4, (void **)&wf_sort_keys[1])) != RT_OK ||
-            (rc = alloc(paths * 4, (void **)&wf_sort_vals[0])) != RT_OK || (rc = alloc(paths * 4, (void **)&wf_sort_vals[1])) != RT_OK ||
+        // + 64: the ray-order sort runs over the queue's physical positions, whole wave slots like the queues above
+        wf_sort_temp_bytes = rt::wavefront_sort_temp_bytes(paths + 64);
+        if ((rc = alloc((paths + 64) * 4, (void **)&wf_sort_keys[0])) != RT_OK || (rc = alloc((paths + 64) * 4, (void **)&wf_sort_keys[1])) != RT_OK ||
+            (rc = alloc((paths + 64) * 4, (void **)&wf_sort_vals[0])) != RT_OK || (rc = alloc((paths + 64) * 4, (void **)&wf_sort_vals[1])) != RT_OK ||
             (rc = alloc(wf_sort_temp_bytes, &wf_sort_temp)) != RT_OK)
             return rc;
         // on the scene's own (non-blocking) stream: a null-stream memset is not ordered with the kernels launched there and

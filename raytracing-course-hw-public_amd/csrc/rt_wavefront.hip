@@ -33,6 +33,7 @@
 #include "rt_dev_shade.h"
 #include "rt_dev_stack.h"
 #include "rt_kernels.h"
+#include "rt_ray_key.h"
 #include "rt_wf_records.h"
 
 namespace {
@@ -577,6 +578,7 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
         const bool active = jq < n_in;
         bool survive = false;
         WfPacked next;
+        uint32_t next_key = 0u; // the ray-order key of `next`, made only when the next bounce may be sorted (WfLaunch::emit_keys)
         if (active) {
             const WfHead in = wf_load_head(L.paths_in + j); // its class bits chose this lane (below); nothing here reads them
             Rng<RT_RNG_DEVICE> rng = wf_load_rng(L.paths_in + j);
@@ -604,6 +606,8 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
                 survive = true;
                 st.cast();
                 next = wf_pack(sr.nro, sr.nrd, path, next_shade_class(rng, has_lights), depth_left, nb, rng.g);
+                if (L.emit_keys)
+                    next_key = rt_ray_order_key(sr.nro.x, sr.nro.y, sr.nro.z, sr.nrd.x, sr.nrd.y, sr.nrd.z, S.bounds_lo, S.bounds_inv);
             }
         }
         // compact the survivors of this wave into the next queue: ballot + prefix sum, one atomic per wave, on the counter of
@@ -617,8 +621,14 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
             if ((int)(threadIdx.x & 63u) == leader)
                 obase = wf_stripe_base(stripe, n_slots) + atomicAdd(L.stripes + stripe * WF_STRIPE_WORDS, (uint32_t)__popcll(m));
             obase = __shfl(obase, leader);
-            if (survive)
-                wf_store_path(L.paths_out + obase + rank, next);
+            if (survive) {
+                const uint32_t p = obase + rank;
+                wf_store_path(L.paths_out + p, next);
+                if (L.emit_keys) { // the sort's input, at the ray's physical slot: nobody reads the record again to make it
+                    L.sort_keys[0][p] = next_key;
+                    L.sort_vals[0][p] = wf_word(p, wf_word_class(__float_as_uint(next.p1.z))); // the class of the path word rides along above the slot (WfLaunch::order)
+                }
+            }
         }
     };
     // Which of shade()'s three samplers a hit runs is decided by its path's next draws alone (alpha coin, technique coin, mix pick:
@@ -667,33 +677,16 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
     st.flush(L.stats);
 }
 
-// Ray-ordering key for secondary bounces, 24 bits: the direction octant (3 bits), the Morton code of the origin's cell in a 64^3 grid
-// over the scene bounds (18 bits), then which of the octant's 8 sub-cones the direction lies in (3 bits). Rays that start close together
-// and head the same way end up in the same wave of wf_extend, so their gathers touch the same nodes (cache lines, L2 residency).
-// Ordering never changes a result: every path's arithmetic is independent of where it sits in the queue.
-DEV uint32_t spread3(uint32_t v) { // 6 bits -> every third bit
-    v &= 63u;
-    v = (v | (v << 8)) & 0x0300Fu;
-    v = (v | (v << 4)) & 0x030C3u;
-    v = (v | (v << 2)) & 0x09249u;
-    return v;
-}
-// `direct`: no sort follows (sorting off or a tiny queue): the identity order over the dense index goes straight to sort_vals[1].
-// Either way this pass turns the dense ray index j < n into the physical slot of paths_in (sub-queue regions, WF_STRIPES).
-// `bound` >= n is what the HOST knows about the queue size when it launches this bounce (the size of the previous bounce's
-// queue, read back without stalling the device): the sort that follows runs over `bound` pairs, so positions [n, bound) get
-// the largest key and end up behind every real ray (nobody reads their order entries: consumers stop at n).
-__global__ __launch_bounds__(256) void wf_sort_keys(const DevScene S, const WfLaunch L, int direct, uint32_t bound) {
+// The order of a bounce no sort runs over (sorting off, or a queue below the sort's threshold): the identity over the dense ray index, as the
+// physical slot of paths_in (wf_shade's sub-queue regions, WF_STRIPES), straight to sort_vals[1]. No record is read: WfLaunch::order_classed = 0.
+// A bounce that IS sorted needs no such pass: its producer wrote key and slot at every filled physical slot (wf_shade, WfLaunch::emit_keys; the
+// key is rt_ray_key.h's), the unfilled ends of the regions hold pad keys, and the sort runs over the physical positions.
+__global__ __launch_bounds__(256) void wf_sort_keys(const WfLaunch L) {
     __shared__ uint32_t s_run[WF_STRIPES + 1u];
     const uint32_t n = L.counters[WF_CNT_IN], n_slots = L.counters[WF_CNT_SLOTS];
     if (threadIdx.x <= WF_STRIPES)
         s_run[threadIdx.x] = L.stripes[WF_STRIPES * WF_STRIPE_WORDS + threadIdx.x];
     __syncthreads();
-    if (!direct)
-        for (uint32_t j = n + blockIdx.x * blockDim.x + threadIdx.x; j < bound; j += gridDim.x * blockDim.x) {
-            L.sort_keys[0][j] = 0xFFFFFFFFu;
-            L.sort_vals[0][j] = 0u;
-        }
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
         uint32_t pos = j;
         if (n_slots != 0u) { // run k holds dense indices [s_run[k], s_run[k+1])
@@ -704,20 +697,7 @@ __global__ __launch_bounds__(256) void wf_sort_keys(const DevScene S, const WfLa
                     k += step;
             pos = wf_stripe_base(k, n_slots) + (j - s_run[k]);
         }
-        if (direct) { // no record is read here: WfLaunch::order_classed = 0
-            L.sort_vals[1][j] = pos;
-            continue;
-        }
-        const WfHead ray = wf_load_head(L.paths_in + pos);
-        const V3 o = ray.o, d = ray.d;
-        const float fx = (o.x - S.bounds_lo[0]) * S.bounds_inv[0], fy = (o.y - S.bounds_lo[1]) * S.bounds_inv[1], fz = (o.z - S.bounds_lo[2]) * S.bounds_inv[2];
-        const uint32_t cx = (uint32_t)fminf(fmaxf(fx * 64.0f, 0.0f), 63.0f), cy = (uint32_t)fminf(fmaxf(fy * 64.0f, 0.0f), 63.0f), cz = (uint32_t)fminf(fmaxf(fz * 64.0f, 0.0f), 63.0f);
-        const uint32_t morton = spread3(cx) | (spread3(cy) << 1) | (spread3(cz) << 2);
-        const uint32_t oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-        const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
-        const uint32_t sub = (ax > ay ? 1u : 0u) | (ay > az ? 2u : 0u) | (ax > az ? 4u : 0u); // which of the octant's 8 sub-cones
-        L.sort_keys[0][j] = (oct << 21) | (morton << 3) | sub;
-        L.sort_vals[0][j] = wf_word(pos, ray.cls); // the class of the path word rides along above the slot (WfLaunch::order)
+        L.sort_vals[1][j] = pos;
     }
 }
 
@@ -887,6 +867,9 @@ namespace rt {
             return le_;                                 \
     } while (0)
 
+// positions the sub-queue regions written by a wf_shade over at most `bound` rays can span: whole wave slots (rt_device_types.h, WF_STRIPES)
+static size_t wf_key_span(uint32_t bound) { return ((size_t)bound + 63u) / 64u * 64u; }
+
 // the closest-hit kernel of one bounce: packets for coherent primary rays or the per-lane persistent kernel, each in the
 // reference's traversal order (near-local pruning, the parity mode) or with global-best pruning (L.global_best, production)
 static hipError_t launch_extend(const DevScene &S, const WfLaunch &L, bool packet, bool stats, int ext_blocks, hipStream_t stream) {
@@ -986,15 +969,17 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
                 if (bound == 0)
                     break;
             }
+            // bound >= 4096 here implies bound >= 4096 at the bounce before (queues only shrink; bounce 1's bound is bounce 0's): the wf_shade
+            // that wrote this queue was told to emit keys (below), over a pad fill at least as long as this sort
             const bool sort = want_bound && bound >= 4096u;
-            // dense ray index -> slot of paths_in (wf_shade's sub-queue regions), with the coherence keys when a sort follows
-            const uint32_t kb = (bound + 255u) / 256u < (uint32_t)num_cus * 16u ? (bound + 255u) / 256u : (uint32_t)num_cus * 16u;
-            WF_LAUNCH(wf_sort_keys, dim3(kb > 0 ? kb : 1), block, 0, stream, S, L, sort ? 0 : 1, bound);
-            if (sort) {
+            if (sort) { // over the PHYSICAL positions of the queue: the producer had at most `bound` rays = wf_key_span(bound) / 64 wave slots
                 size_t tmp = L.sort_temp_bytes;
-                hipError_t se = rocprim::radix_sort_pairs(L.sort_temp, tmp, L.sort_keys[0], L.sort_keys[1], L.sort_vals[0], L.sort_vals[1], (size_t)bound, 0u, 24u /* wf_sort_keys' key */, stream);
+                hipError_t se = rocprim::radix_sort_pairs(L.sort_temp, tmp, L.sort_keys[0], L.sort_keys[1], L.sort_vals[0], L.sort_vals[1], wf_key_span(bound), 0u, RT_RAY_KEY_BITS, stream);
                 if (se != hipSuccess)
                     return se;
+            } else { // dense ray index -> slot of paths_in (wf_shade's sub-queue regions)
+                const uint32_t kb = (bound + 255u) / 256u < (uint32_t)num_cus * 16u ? (bound + 255u) / 256u : (uint32_t)num_cus * 16u;
+                WF_LAUNCH(wf_sort_keys, dim3(kb > 0 ? kb : 1), block, 0, stream, L);
             }
             L.order = L.sort_vals[1];
             L.order_classed = sort ? 1u : 0u;
@@ -1013,6 +998,14 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             WF_LAUNCH(wf_extend_prims, dim3(shade_blocks), block, 0, stream, S, L);
         if (b == 0 && acc && feat) // a feature accumulator's pass: the primary rays' first hits are final here
             WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *feat);
+        // Will the next bounce be sorted? Its own bound is not known yet (it arrives one bounce late) but cannot exceed this one, so: may it be.
+        // Then this wf_shade writes the sort's input itself, key and slot at the physical slot of every ray it makes, and every slot it leaves
+        // empty (the ends of the 64 sub-queue regions) must already hold a pad: RT_RAY_KEY_PAD in the compared bits, behind every real key
+        // wherever it stands. The regions of at most `bound` input rays end at wf_key_span(bound). (A byte fill of the range at HBM rate, a
+        // few tens of microseconds; the bounce's own sort has read sort_keys[0] by now: it is earlier in the stream.)
+        L.emit_keys = want_bound && b + 1 < L.ray_depth && bound >= 4096u ? 1u : 0u;
+        if (L.emit_keys && (e = hipMemsetAsync(L.sort_keys[0], 0xFF, sizeof(uint32_t) * wf_key_span(bound), stream)) != hipSuccess)
+            return e;
         // ENV: the scene has an environment map (DevScene::bg_tex): the miss branch looks it up (scene.h:83-89); those instantiations read the
         // light tables from global memory (LIGHTS_LDS only saves latency), so a scene without one never pays for the lookup's registers
         const bool env = S.bg_tex >= 0;
