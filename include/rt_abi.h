@@ -49,7 +49,7 @@ extern "C" {
                                 rt_view / rt_render_views / rt_render_views_rgb8 were added, and after the rt_accum_* accumulators and
                                 rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were, and
                                 after rt_update_geometry and rt_ray / rt_render_rays / rt_render_rays_rgb8 were, and after
-                                rt_update_geometry_device and rt_refit_times were:
+                                rt_update_geometry_device and rt_refit_times were, and after rt_set_environment / rt_env_pdf / rt_env_sample were:
                                 new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
@@ -682,6 +682,61 @@ int rt_update_geometry_device(rt_scene *scene, const rt_geometry_update *upd);
  * and nodes on the device, *levels_ms the part of it spent in the top-down level pass, which reads the topology alone (one launch and one
  * host read per level). A measurement aid, like rt_build_times. RT_ERR_INVALID_ARG: a NULL argument; RT_ERR_UNSUPPORTED: a multi-GPU scene. */
 int rt_refit_times(const rt_scene *scene, double *refit_ms, double *levels_ms);
+
+/* Image-based lighting: a float radiance map as the scene's environment, optionally importance-sampled (additive; RT_ABI_VERSION stays 4).
+ * rt_create's bg_texture is the reference's Scene::bg: an 8-bit texture with gamma, which clips an .hdr file to [0, 1]. rt_set_environment
+ * replaces that lookup by a float map for a built scene. The texels are copied to device memory (float4 each); the caller keeps `rgb`.
+ * The rule, operation by operation: IEEE binary32 evaluated as written, no contraction, unless double is named. W = width, H = height.
+ *   Radiance   Le(dir) = bg_color * env(u, v), per component, with (u, v) = rt_bg_uv(dir) (rt_devspec.h), unchanged. env is Texture::sample's
+ *     lookup (geometry.h:545-575) over the float texels: tx = wrap_repeat(u) * (float)W, ty = wrap_repeat(v) * (float)H, x0 = (int)tx,
+ *     y0 = (int)ty, dx = tx - (float)x0, dy = ty - (float)y0, x1 = x0 + 1 (0 behind the last column), y1 likewise (row H - 1 wraps to row 0,
+ *     as the reference's does), env = (1 - dx) * ((1 - dy) * t[y0][x0] + dy * t[y1][x0]) + dx * ((1 - dy) * t[y0][x1] + dy * t[y1][x1]).
+ *     No 8-bit decode, no gamma. A 1x1 map returns bg_color * its texel without evaluating (u, v), like the reference's 1x1 path.
+ *   Distribution (RT_ENV_IMPORTANCE), piecewise constant over the W x H cells; cell (i, j) = (y0, x0) of the lookup above, i.e.
+ *     u in [j/W, (j+1)/W), v in [i/H, (i+1)/H) up to the float rounding of tx, ty.
+ *     M_ij = max(0, lum(t[i][j]), lum(t[i1][j]), lum(t[i][j1]), lum(t[i1][j1])), i1 / j1 the wrapped successors: every texel a lookup inside
+ *       the cell can read; lum(t) = (0.2126f * (bg.r * t.r) + 0.7152f * (bg.g * t.g)) + 0.0722f * (bg.b * t.b). So pdf > 0 wherever Le > 0.
+ *     Omega_i = (2 pi / W) * (c_i - c_(i+1)) in double on the host, c_i = cos(pi * i / H) in double (c_0 = 1, c_H = -1): the solid angle
+ *       of a cell of row i. w_ij = (double)M_ij * Omega_i.
+ *     Prefix sums in double, in this order, for a sequence a_0 .. a_(n-1) (a row's w_ij, n = W; then the H row totals, n = H): C = ceil(n / 256);
+ *       chunk c holds a_(cC) .. a_(cC + C - 1); L_k = the sum of its chunk's elements up to a_k, left to right; B_c = the sum of the totals of
+ *       chunks 0 .. c-1, left to right; P_k = B_c + L_k. cdf[0] = 0, cdf[k+1] = (float)(P_k / P_(n-1)), cdf[n] = 1; a row of total 0 gets
+ *       cdf[k+1] = (float)(k+1) / (float)n (its marginal cell is empty: nothing selects it).
+ *     Tables: row_i[0..W] for every row, each normalised on its own, and marg[0..H] over the row totals. p_ij is DEFINED from the stored float
+ *       tables, p_ij = (marg[i+1] - marg[i]) * (row_i[j+1] - row_i[j]), and pdf(dir) = p_ij / (float)Omega_i with (i, j) the cell of dir:
+ *       a solid-angle density. Sampling and pdf agree by construction. A cell lighter than the float spacing of its table has p_ij = 0.
+ *     A map whose weights are all zero has no distribution: the flag then acts as if it were not set.
+ *   Sample, from four uniforms x0 .. x3 in [0, 1) (uniform_real(rng, 0, 1), in this order):
+ *     i = the last index in [0, H) with marg[i] <= x0;  j = the last index in [0, W) with row_i[j] <= x1   (binary searches; never an empty cell)
+ *     u = ((float)j + x2) / (float)W;  dy = c_i - x3 * (c_i - c_(i+1)) with the float edges   (uniform in solid angle inside the cell)
+ *     r = sqrtf(max(0, 1 - dy * dy));  (s, c) = rt_sincos_libm((2 * PI_F) * u);  dir = (-(r * c), dy, -(r * s))   (inverts rt_bg_uv; the argument
+ *     lies in [0, 2 pi], where rt_sincos_libm is verified). Only the direction is made: every pdf is evaluated from it afterwards.
+ *   Mixture: with a distribution, shade()'s mix_dist (raytracer.h:381-407) gains the environment as one more equally weighted component, the
+ *     last: {cosine, env} (k = 2) without emissive triangles, {cosine, lights, env} (k = 3) with them. pick = rng.below(k) where the reference
+ *     draws its pick (a scene without lights draws none today and draws one now); the env sampler then makes its four draws;
+ *     MIS_p = (sum of the k component pdfs) / (float)k. The alpha and technique coins keep their order; the VNDF branch and VNDF_FACTOR are untouched.
+ *   Without a distribution only the miss branch changes: the random stream of every path is the one it has today.
+ * Who sees it: every wavefront entry point (rt_render*, rt_render_views*, rt_render_rays*, rt_render_sensors*, rt_accum_*) through the one
+ *   shade(); rt_bg_at returns the float lookup. rt_update_geometry* leaves the environment untouched. bg_color is the creation descriptor's.
+ *   rt_set_environment(scene, NULL): back to what rt_create made of bg_texture; every entry point gives the bits it gave before.
+ * RT_ERR_INVALID_ARG: a NULL scene; width outside 1..8192 or height outside 1..4096; NULL rgb; a texel that is NaN, infinite or negative; a bit
+ *   of flags other than RT_ENV_IMPORTANCE; reserved != 0; a scene with a live accumulator (its sums are of the old environment: destroy it
+ *   first; an accumulator created afterwards sees the new one). RT_ERR_UNSUPPORTED: a multi-GPU scene. After any refusal the scene is unchanged.
+ * On a scene with a float environment RT_FLAG_MEGAKERNEL and RT_RNG_REFERENCE renders return RT_ERR_UNSUPPORTED (they are the reference's
+ *   Scene::bg_at), as they do on a RT_BUILD_WIDE scene.
+ * rt_env_pdf / rt_env_sample: probes of the distribution on the device's own tables: pdf(dir) for n directions (3 floats each, used as
+ *   given), and the direction of n quadruples x0 .. x3. RT_ERR_INVALID_ARG without a distribution (no float environment, no flag, an all-zero
+ *   map), for a NULL argument with n > 0, and for a uniform outside [0, 1). */
+enum { RT_ENV_IMPORTANCE = 1 }; /* rt_environment.flags */
+typedef struct rt_environment {
+    uint32_t width, height; /* 1 .. 8192 x 1 .. 4096 */
+    const float *rgb;       /* width*height*3 linear radiance, row 0 = +y pole; finite, >= 0 (else RT_ERR_INVALID_ARG) */
+    uint32_t flags;         /* RT_ENV_*; any other bit refused */
+    uint32_t reserved;      /* 0 */
+} rt_environment;
+int rt_set_environment(rt_scene *scene, const rt_environment *env); /* NULL: back to what rt_create made of desc.bg_texture */
+int rt_env_pdf(rt_scene *scene, const float *dirs, uint32_t n, float *pdf_out);    /* probe: solid-angle pdf of the env distribution */
+int rt_env_sample(rt_scene *scene, const float *xi4, uint32_t n, float *dirs_out); /* probe: 4 uniforms in [0,1) per direction */
 
 int rt_film_rgb8(rt_scene *scene, const float *rgb, size_t n_pixels, uint8_t *out_rgb8);
 

@@ -85,6 +85,12 @@ int rt_image_decode_file(const char *path, uint32_t *w, uint32_t *h, uint8_t **r
 int rt_hdr_decode_file(const char *path, uint32_t *w, uint32_t *h, uint8_t **rgba8);
 int rt_png_decode_file(const char *path, uint32_t *w, uint32_t *h, uint8_t **rgba8);
 int rt_jpeg_decode_file(const char *path, uint32_t *w, uint32_t *h, uint8_t **rgba8);
+/* The same pictures as RADIANCE, for rt_set_environment (rt_abi.h): width * height * 3 floats, row-major, top row first. rt_hdr_decode_file_float:
+ * the values of a Radiance HDR picture themselves, mantissa * 2^(e - 136) exactly, zeros for e = 0: no 8-bit conversion, nothing clipped.
+ * rt_image_decode_radiance: an .hdr through it; a PNG or JPEG as its 8-bit texels decoded with the gamma an environment lookup applies,
+ * powf(k / 255.0f, 2.2f). Caller frees with rt_free. */
+int rt_hdr_decode_file_float(const char *path, uint32_t *w, uint32_t *h, float **rgb);
+int rt_image_decode_radiance(const char *path, uint32_t *w, uint32_t *h, float **rgb);
 void rt_free(void *p);
 
 #ifdef __cplusplus

@@ -51,6 +51,7 @@ from ._ctypes_abi import (
     RT_OK,
     RT_UPDATE_REBUILD,
     RT_UPDATE_REFIT,
+    RT_ENV_IMPORTANCE,
     RT_RNG_DEVICE,
     RT_RNG_REFERENCE,
     RAY_DTYPE,
@@ -58,6 +59,7 @@ from ._ctypes_abi import (
     RtAdaptive,
     RtCamera,
     RtDenoise,
+    RtEnvironment,
     RtGeometryUpdate,
     RtParams,
     RtRay,
@@ -66,6 +68,7 @@ from ._ctypes_abi import (
     RtView,
     RtStats,
     bind,
+    c_float_p,
     c_u8_p,
     desc_to_arrays,
     fptr,
@@ -695,6 +698,36 @@ class DeviceScene:
         _check(lib().rt_bg_at(self._h, fptr(dirs), n, fptr(out)))
         return out
 
+    def set_environment(self, rgb: Optional[np.ndarray], importance: bool = False) -> None:
+        """rt_set_environment: an (H, W, 3) float32 array of linear radiance (row 0 = the +y pole; finite, >= 0) becomes this scene's
+        background for every wavefront entry point and for bg_at, in place of the 8-bit bg_texture; `importance` adds RT_ENV_IMPORTANCE:
+        shade()'s mix_dist samples the map. None: back to what the scene was created with. The array is copied."""
+        if rgb is None:
+            _check(lib().rt_set_environment(self._h, None))
+            return
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("set_environment: expected an (H, W, 3) array")
+        e = RtEnvironment()
+        e.height, e.width = rgb.shape[0], rgb.shape[1]
+        e.rgb = fptr(rgb)
+        e.flags = RT_ENV_IMPORTANCE if importance else 0
+        _check(lib().rt_set_environment(self._h, C.byref(e)))
+
+    def env_pdf(self, dirs: np.ndarray) -> np.ndarray:
+        """rt_env_pdf: the solid-angle pdf of the environment distribution for (n, 3) directions, from the device's own tables."""
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(dirs.shape[0], dtype=np.float32)
+        _check(lib().rt_env_pdf(self._h, fptr(dirs), dirs.shape[0], fptr(out)))
+        return out
+
+    def env_sample(self, xi: np.ndarray) -> np.ndarray:
+        """rt_env_sample: the directions (n, 3) the environment sampler makes of (n, 4) uniforms in [0, 1)."""
+        xi = np.ascontiguousarray(xi, dtype=np.float32).reshape(-1, 4)
+        out = np.zeros((xi.shape[0], 3), dtype=np.float32)
+        _check(lib().rt_env_sample(self._h, fptr(xi), xi.shape[0], fptr(out)))
+        return out
+
     def bvh_device_dump(self, which: int = 0):
         """The BVH as the kernels see it, read back from HBM: {root, nodes (n_inner,16) u32, tris (n_tris,12) u32}."""
         ni, nt, root = C.c_uint32(), C.c_uint32(), C.c_uint32()
@@ -938,6 +971,18 @@ def image_decode(path: str) -> np.ndarray:
         lib().rt_free(p)
 
 
+def load_hdr(path: str) -> np.ndarray:
+    """A picture as radiance for DeviceScene.set_environment: (H, W, 3) float32. A Radiance .hdr gives its values exactly (mantissa *
+    2^(e - 136), nothing clipped); a PNG or JPEG its 8-bit texels decoded with the gamma an environment lookup applies."""
+    w, h = C.c_uint32(), C.c_uint32()
+    p = c_float_p()
+    _check(lib().rt_image_decode_radiance(os.fsencode(path), C.byref(w), C.byref(h), C.byref(p)))
+    try:
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).copy()
+    finally:
+        lib().rt_free(p)
+
+
 def png_decode(path: str) -> np.ndarray:
     w, h = C.c_uint32(), C.c_uint32()
     p = c_u8_p()
@@ -968,6 +1013,7 @@ __all__ = [
     "rays",
     "RAY_DTYPE",
     "RtRay",
+    "load_hdr",
     "png_decode",
     "scenegen",
     "tonemap",

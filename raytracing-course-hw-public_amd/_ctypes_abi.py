@@ -31,6 +31,7 @@ RT_FLAG_GLOBAL_BEST = 8
 RT_ACCUM_FEATURES = 1
 RT_DENOISE_NO_DEMODULATE = 1
 RT_UPDATE_REBUILD, RT_UPDATE_REFIT = 0, 1
+RT_ENV_IMPORTANCE = 1  # rt_environment.flags
 RT_CAST_PROBE, RT_CAST_EXTEND, RT_CAST_EXTEND_GLOBAL, RT_CAST_PACKET, RT_CAST_PACKET_GLOBAL = range(5)
 
 RT_OK = 0
@@ -184,6 +185,16 @@ class RtGeometryUpdate(C.Structure):  # rt_update_geometry: the five per-triangl
     ]
 
 
+class RtEnvironment(C.Structure):  # rt_set_environment: a float radiance map (24 bytes)
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("rgb", c_float_p),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 RT_PROGRESS_FN = C.CFUNCTYPE(None, C.c_uint32, C.c_uint32, C.c_void_p)
 
 
@@ -273,6 +284,9 @@ ABI_PROTOTYPES = {
     "rt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),
     "rt_update_geometry_device": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),  # the five pointers are device pointers
     "rt_refit_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rt_set_environment": (C.c_int, [C.c_void_p, C.POINTER(RtEnvironment)]),  # NULL: back to the creation background
+    "rt_env_pdf": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, c_float_p]),
+    "rt_env_sample": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, c_float_p]),
     "rt_last_error": (C.c_char_p, []),
     "rt_source_stamp": (C.c_char_p, []),
     "rt_abi_version": (C.c_uint32, []),
@@ -299,6 +313,8 @@ HOST_PROTOTYPES = {
     "rt_png_decode_file": (C.c_int, [C.c_char_p, c_u32_p, c_u32_p, C.POINTER(c_u8_p)]),
     "rt_jpeg_decode_file": (C.c_int, [C.c_char_p, c_u32_p, c_u32_p, C.POINTER(c_u8_p)]),
     "rt_image_decode_file": (C.c_int, [C.c_char_p, c_u32_p, c_u32_p, C.POINTER(c_u8_p)]),
+    "rt_hdr_decode_file_float": (C.c_int, [C.c_char_p, c_u32_p, c_u32_p, C.POINTER(c_float_p)]),
+    "rt_image_decode_radiance": (C.c_int, [C.c_char_p, c_u32_p, c_u32_p, C.POINTER(c_float_p)]),
     "rt_free": (None, [C.c_void_p]),
     "rt_film_table": (C.c_int, [c_float_p, c_u32_p]),
     "rt_bvh_build_host": (C.c_int, [c_float_p, C.c_uint32, c_u32_p, C.c_uint32, c_u32_p, c_u32_p, c_u32_p, c_u32_p]),

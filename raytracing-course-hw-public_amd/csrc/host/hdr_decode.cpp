@@ -9,6 +9,9 @@
 //     (count > 128: count - 128 copies of the next byte) and dumps (count bytes)); a first scanline that does not start with 2 2
 //     switches the WHOLE picture to flat r g b e quadruples (that quirk of stb_image is kept); other widths are flat;
 //   * value: mantissa * 2^(e - 136), e = 0 -> black.
+// rt_hdr_decode_file_float is the same reader without that conversion: the values themselves, three floats per pixel, exact (an 8-bit
+// mantissa times a power of two), for rt_set_environment. rt_image_decode_radiance gives any supported picture as radiance: an .hdr through
+// it, a PNG or JPEG as the 8-bit texels decoded with the gamma an environment lookup applies.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -60,6 +63,14 @@ uint8_t to_ldr(float v) { // stbi__hdr_to_ldr with the default gamma 2.2 and sca
     return (uint8_t)(int)z;
 }
 
+// mantissa * 2^(e - 136), exact in binary32 for every e (the smallest, 2^-135, is a subnormal with bits to spare); zeros for e = 0
+void put_pixel(float *out, const uint8_t rgbe[4]) {
+    const float f1 = rgbe[3] != 0 ? (float)std::ldexp(1.0f, (int)rgbe[3] - (128 + 8)) : 0.0f;
+    out[0] = rgbe[0] * f1;
+    out[1] = rgbe[1] * f1;
+    out[2] = rgbe[2] * f1;
+}
+
 void put_pixel(uint8_t *out, const uint8_t rgbe[4]) {
     if (rgbe[3] != 0) {
         const float f1 = (float)std::ldexp(1.0f, (int)rgbe[3] - (128 + 8));
@@ -72,9 +83,9 @@ void put_pixel(uint8_t *out, const uint8_t rgbe[4]) {
     out[3] = 255; // alpha 1.0f * 255 + 0.5f
 }
 
-} // namespace
-
-extern "C" int rt_hdr_decode_file(const char *path, uint32_t *w_out, uint32_t *h_out, uint8_t **rgba_out) {
+// One reader for both outputs: PX = uint8_t writes stb_image's 8-bit conversion (4 bytes per pixel), PX = float the values (3 floats)
+template <class PX> int hdr_decode(const char *path, uint32_t *w_out, uint32_t *h_out, PX **rgba_out) {
+    constexpr size_t NC = sizeof(PX) == 1 ? 4 : 3;
     if (!path || !w_out || !h_out || !rgba_out)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_hdr_decode_file: null argument");
     std::vector<uint8_t> file;
@@ -87,7 +98,7 @@ extern "C" int rt_hdr_decode_file(const char *path, uint32_t *w_out, uint32_t *h
     } else {
         return rt::fail(RT_ERR_IO, std::string("Failed to load image from ") + path);
     }
-    uint8_t *px = nullptr;
+    PX *px = nullptr;
     try {
         Reader r(file);
         const std::string first = r.line();
@@ -122,7 +133,7 @@ extern "C" int rt_hdr_decode_file(const char *path, uint32_t *w_out, uint32_t *h
         // seconds of pow() over pixels that do not exist.
         if ((uint64_t)width * (uint64_t)height > 16ull * (uint64_t)(file.size() - r.pos) + 16ull)
             throw HdrError{"HDR picture larger than its data can hold"};
-        px = static_cast<uint8_t *>(std::malloc((size_t)width * height * 4));
+        px = static_cast<PX *>(std::malloc((size_t)width * height * NC * sizeof(PX)));
         if (!px)
             return rt::fail(RT_ERR_OOM, "HDR: out of memory");
         auto flat_from = [&](long j0, long i0) { // the rest of the picture as r g b e quadruples
@@ -131,7 +142,7 @@ extern "C" int rt_hdr_decode_file(const char *path, uint32_t *w_out, uint32_t *h
                     uint8_t q[4];
                     for (int k = 0; k < 4; ++k)
                         q[k] = (uint8_t)r.get8();
-                    put_pixel(px + ((size_t)j * width + i) * 4, q);
+                    put_pixel(px + ((size_t)j * width + i) * NC, q);
                 }
         };
         if (width < 8 || width >= 32768) {
@@ -172,7 +183,7 @@ extern "C" int rt_hdr_decode_file(const char *path, uint32_t *w_out, uint32_t *h
                     }
                 }
                 for (long i = 0; i < width; ++i)
-                    put_pixel(px + ((size_t)j * width + i) * 4, &scan[(size_t)i * 4]);
+                    put_pixel(px + ((size_t)j * width + i) * NC, &scan[(size_t)i * 4]);
             }
         }
         *w_out = (uint32_t)width;
@@ -185,5 +196,43 @@ extern "C" int rt_hdr_decode_file(const char *path, uint32_t *w_out, uint32_t *h
         std::free(px);
         return rt::fail(RT_ERR_OOM, "HDR: out of memory");
     }
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" int rt_hdr_decode_file(const char *path, uint32_t *w_out, uint32_t *h_out, uint8_t **rgba_out) { return hdr_decode<uint8_t>(path, w_out, h_out, rgba_out); }
+extern "C" int rt_hdr_decode_file_float(const char *path, uint32_t *w_out, uint32_t *h_out, float **rgb_out) { return hdr_decode<float>(path, w_out, h_out, rgb_out); }
+
+extern "C" int rt_image_decode_radiance(const char *path, uint32_t *w_out, uint32_t *h_out, float **rgb_out) {
+    if (!path || !w_out || !h_out || !rgb_out)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_image_decode_radiance: null argument");
+    uint8_t sig[2] = {0, 0};
+    if (FILE *f = std::fopen(path, "rb")) {
+        const size_t n = std::fread(sig, 1, 2, f);
+        (void)n;
+        std::fclose(f);
+    } else {
+        return rt::fail(RT_ERR_IO, std::string("Failed to load image from ") + path);
+    }
+    if (sig[0] == '#' && sig[1] == '?')
+        return rt_hdr_decode_file_float(path, w_out, h_out, rgb_out);
+    uint8_t *px = nullptr; // an 8-bit picture: the texel an environment lookup decodes, powf(k / 255.0f, 2.2f) (geometry.h:525-527, 593-594)
+    if (int rc = rt_image_decode_file(path, w_out, h_out, &px); rc != RT_OK)
+        return rc;
+    const size_t n = (size_t)*w_out * *h_out;
+    float *out = static_cast<float *>(std::malloc(n * 3 * sizeof(float)));
+    if (!out) {
+        rt_free(px);
+        return rt::fail(RT_ERR_OOM, "rt_image_decode_radiance: out of memory");
+    }
+    float gam[256];
+    for (int k = 0; k < 256; ++k)
+        gam[k] = std::pow(k / 255.0f, 2.2f);
+    for (size_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c)
+            out[3 * i + c] = gam[px[4 * i + c]];
+    rt_free(px);
+    *rgb_out = out;
     return RT_OK;
 }

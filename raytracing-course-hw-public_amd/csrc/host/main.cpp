@@ -5,6 +5,8 @@
 // Optional environment: RT_DEVICE (HIP ordinal; unset = every visible GPU: replicas + RCCL gather inside the library, the
 // node-scale counterpart of the thread pool of raytracer.h:636-665), RT_RNG_MODE (device|reference), RT_SEED,
 // RT_ENV_MAP (+ RT_ENV_MAP_INTENSITY): the environment map the reference enables at compile time (config.h:36-38, main.cpp:28-31);
+// RT_ENV_RADIANCE=1 (with RT_ENV_MAP): the map lights the scene as float radiance (rt_set_environment after rt_create, on one GPU): an .hdr
+// keeps the values the 8-bit load clips to [0, 1]; RT_ENV_IMPORTANCE=1 adds RT_ENV_IMPORTANCE, which importance-samples it.
 // RT_LIGHT_TRIANGLE=1 (+ RT_LIGHT_TRIANGLE_INTENSITY): its extra light source in camera coordinates (config.h:40-47, scene.h:479-498).
 // Tuning (the library itself reads NO environment variable since ABI 4; this file translates them into rt_scene_desc / rt_params
 // fields): RT_BVH_DEVICE=1, RT_BVH_WIDE=1 (production builds), RT_TRAVERSAL=global, RT_WF_SORT=<0|5> (off | sorted), RT_WF_PACKET=<0|1>,
@@ -62,7 +64,12 @@ int main(int argc, char **argv) {
     // *.txt: the scene-txt front end (BASELINE configs 1-2; no parser at the reference's HEAD), anything else: glTF (main.cpp:27)
     if (rt_scene_load(argv[1], static_cast<float>(width) / height, &loaded) != RT_OK)
         return die("load");
-    if (const char *env_map = std::getenv("RT_ENV_MAP")) { // USE_ENV_MAP / ENV_MAP_PATH / ENV_MAP_INTENSITY, config.h:36-38
+    auto env_on = [](const char *name) {
+        const char *v = std::getenv(name);
+        return v && std::atoi(v) != 0;
+    };
+    const char *env_radiance = env_on("RT_ENV_RADIANCE") ? std::getenv("RT_ENV_MAP") : nullptr; // the map as float radiance, set after rt_create
+    if (const char *env_map = env_radiance ? nullptr : std::getenv("RT_ENV_MAP")) { // USE_ENV_MAP / ENV_MAP_PATH / ENV_MAP_INTENSITY, config.h:36-38
         const char *k = std::getenv("RT_ENV_MAP_INTENSITY");
         if (rt_loaded_set_env_map(loaded, env_map, k ? std::strtof(k, nullptr) : 1.0f) != RT_OK) {
             rt_loaded_free(loaded);
@@ -81,16 +88,12 @@ int main(int argc, char **argv) {
     }
     const char *dev_env = std::getenv("RT_DEVICE");
     const char *adaptive = std::getenv("RT_ADAPTIVE"); // accumulators run on one GPU
-    auto env_on = [](const char *name) {
-        const char *v = std::getenv(name);
-        return v && std::atoi(v) != 0;
-    };
     const bool denoise = env_on("RT_DENOISE");
     const char *aov = std::getenv("RT_AOV");
     const bool accumulate = adaptive || denoise || aov;
     const char *camera_kind = std::getenv("RT_CAMERA"); // sensors are evaluated on one GPU
     rt_scene *scene = nullptr;
-    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !accumulate && !camera_kind ? RT_ALL_DEVICES : 0);
+    const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !accumulate && !camera_kind && !env_radiance ? RT_ALL_DEVICES : 0);
     rt_scene_desc desc = *rt_loaded_desc(loaded); // the arrays stay the loader's; only the build options change
     if (env_on("RT_BVH_DEVICE"))
         desc.build_flags |= RT_BUILD_DEVICE_LBVH;
@@ -100,6 +103,10 @@ int main(int argc, char **argv) {
         desc.build.device_builder = RT_BUILDER_LBVH;
     if (const char *r = std::getenv("RT_PLOC_RADIUS"))
         desc.build.ploc_radius = (uint32_t)std::atoi(r);
+    if (env_radiance) { // bg_color = intensity, as rt_loaded_set_env_map sets it for the 8-bit map (main.cpp:28)
+        const char *k = std::getenv("RT_ENV_MAP_INTENSITY");
+        desc.bg_color[0] = desc.bg_color[1] = desc.bg_color[2] = k ? std::strtof(k, nullptr) : 1.0f;
+    }
     int crc = rt_create(&desc, device, &scene);
     if (crc == RT_ERR_COMM && device == RT_ALL_DEVICES) {
         // the multi-GPU group could not be formed (librccl missing, or it refuses this device set): one GPU still renders
@@ -109,6 +116,21 @@ int main(int argc, char **argv) {
     if (crc != RT_OK) {
         rt_loaded_free(loaded);
         return die("rt_create");
+    }
+    if (env_radiance) {
+        rt_environment env{};
+        float *texels = nullptr;
+        int erc = rt_image_decode_radiance(env_radiance, &env.width, &env.height, &texels);
+        env.rgb = texels;
+        env.flags = env_on("RT_ENV_IMPORTANCE") ? RT_ENV_IMPORTANCE : 0u;
+        if (erc == RT_OK)
+            erc = rt_set_environment(scene, &env);
+        rt_free(texels);
+        if (erc != RT_OK) {
+            rt_destroy(scene);
+            rt_loaded_free(loaded);
+            return die("environment map");
+        }
     }
     rt_params p{};
     p.width = width;

@@ -1,6 +1,6 @@
 // rt_dev_shade.h — one shade() level: primary-ray generation, the sampling distributions, the BRDF, the background and shade_hit.
 #pragma once
-#include "rt_dev_surface.h"
+#include "rt_dev_env.h"
 
 namespace {
 
@@ -120,9 +120,12 @@ DEV V3 pbr_brdf(V3 in_dir, V3 out_dir, const Surf &ii) { // :300-343
 // Scene::bg_at (scene.h:83-89): bg_color * bg.sample({x, y}, 2.2f).rgb(). With the default 1x1 WHITE_TEXTURE (USE_ENV_MAP = false,
 // config.h:37) Texture::sample returns its only texel before looking at the coordinates, so nothing is evaluated. With an environment
 // map the direction goes through the reference's own atan2f / asinf (rt_devspec.h rt_bg_uv) and the ordinary texture lookup with gamma.
-// ENV = false compiles the lookup out (wf_shade's default instantiations keep their register budget; the launcher picks ENV by scene).
-template <bool STATS, bool ENV = true> DEV V3 bg_at(const DevScene &S, V3 dir, const float *s_lin, const float *s_gam, LaneStats<STATS> &st) {
-    if (!ENV || S.bg_tex < 0)
+// ENV (rt_dev_env.h) = ENV_NONE compiles the lookup out (wf_shade's default instantiations keep their register budget; the launcher picks
+// ENV by scene). ENV_FLOAT / ENV_FLOAT_DIST: the float map of rt_set_environment takes the texture's place (env_radiance).
+template <bool STATS, int ENV = ENV_TEX8> DEV V3 bg_at(const DevScene &S, V3 dir, const float *s_lin, const float *s_gam, LaneStats<STATS> &st) {
+    if constexpr (ENV == ENV_FLOAT || ENV == ENV_FLOAT_DIST)
+        return env_radiance<STATS>(S, dir, st);
+    if (ENV == ENV_NONE || S.bg_tex < 0)
         return ld3(S.bg) * mk(1, 1, 1);
     float u, v;
     rt_bg_uv(dir.x, dir.y, dir.z, &u, &v);
@@ -140,18 +143,36 @@ template <bool STATS, bool ENV = true> DEV V3 bg_at(const DevScene &S, V3 dir, c
 // Which sampler the NEXT shade() of a path will run, from the generator state the path record stores (taken by value): the alpha coin
 // is drawn first whatever the material (:559), the technique coin second (:565), mix_dist's pick third (:386). 0 VNDF, 1 cosine, 2 light
 // triangle. A scheduling hint for wf_shade's lane assignment only: a miss or an alpha pass-through never gets that far, and nothing
-// computed depends on it.
-template <class R> DEV uint32_t next_shade_class(R rng, bool has_lights) {
+// computed depends on it. ENV_DIST: mix_dist has the environment as its last component (ENV_FLOAT_DIST); its sampler is handed out with
+// class 2: two dependent binary searches through the tables in HBM cost what the light sampler's record fetch costs, not what the
+// arithmetic-only cosine lobe does, and in a scene without emissive triangles class 2 is otherwise empty.
+template <bool ENV_DIST = false, class R> DEV uint32_t next_shade_class(R rng, bool has_lights) {
     (void)uniform_real(rng, 0.0f, 1.0f);
     if (uniform_real(rng, 0.0f, 1.0f) <= VNDF_FACTOR)
         return 0u;
+    if constexpr (ENV_DIST)
+        return rng.below(has_lights ? 3u : 2u) == 0u ? 1u : 2u;
     return (!has_lights || rng.below(2) == 0u) ? 1u : 2u;
+}
+// bvh_mix_dist::sample :353-361 + triangle_dist::sample :225-239: a uniformly picked light triangle, a uniform point on it
+template <class R> DEV V3 light_sample(const DevScene &S, const LightTabs &LT, V3 pos, R &rng) {
+    const uint32_t id = rng.below(S.lights.n_tris);
+    const float4 *lp = LT.tris + 3u * id;
+    const TriRec lt = tri_rec(lp[0], lp[1], lp[2]);
+    float u = uniform_real(rng, 0, 1);
+    float v = uniform_real(rng, 0, 1);
+    if (u + v > 1) {
+        u = 1 - u;
+        v = 1 - v;
+    }
+    V3 p = lt.a + lt.v * v + lt.u * u; // a + v' * v + u' * u
+    return norm(p - pos);
 }
 struct ShadeResult {
     bool terminal, push;
     V3 term, emission, scl, nro, nrd;
 };
-template <class R, bool STATS, bool ENV = true, class STK>
+template <class R, bool STATS, int ENV = ENV_TEX8, class STK>
 DEV ShadeResult shade_hit(const DevScene &S, const LightTabs &LT, const Hit &h, V3 ro, V3 rd, R &rng, bool has_lights, STK &stk, const float *s_lin,
                           const float *s_gam, LaneStats<STATS> &st) {
     ShadeResult out;
@@ -173,26 +194,27 @@ DEV ShadeResult shade_hit(const DevScene &S, const LightTabs &LT, const Hit &h, 
     }
     const float vr = pow2(rmax(ii.roughness, MIN_ROUGHNESS)); // :563-564
     V3 dir;
+    constexpr bool ENV_DIST = ENV == ENV_FLOAT_DIST; // mix_dist gains the environment as one more equally weighted component
+    const uint32_t mix_k = has_lights ? 3u : 2u;     // ... {cosine, lights, env} or {cosine, env}
     if (uniform_real(rng, 0.0f, 1.0f) <= VNDF_FACTOR) { // :565
         dir = vndf_sample(rng, vr, rd, ii.shading_normal);
+    } else if (ENV_DIST) {
+        const uint32_t pick = rng.below(mix_k);
+        if (pick == 0) {
+            dir = norm(ii.normal + sphere_uniform(rng));
+        } else if (pick + 1u == mix_k) {
+            dir = env_sample(S.env, rng);
+        } else {
+            dir = light_sample(S, LT, pos, rng);
+        }
     } else if (!has_lights) { // dir_dist = cosine_dist (:449)
         dir = norm(ii.normal + sphere_uniform(rng));
     } else { // mix_dist{cosine, bvh_mix} (:381-393)
         const uint32_t pick = rng.below(2);
         if (pick == 0) {
             dir = norm(ii.normal + sphere_uniform(rng));
-        } else { // bvh_mix_dist::sample :353-361 + triangle_dist::sample :225-239
-            const uint32_t id = rng.below(S.lights.n_tris);
-            const float4 *lp = LT.tris + 3u * id;
-            const TriRec lt = tri_rec(lp[0], lp[1], lp[2]);
-            float u = uniform_real(rng, 0, 1);
-            float v = uniform_real(rng, 0, 1);
-            if (u + v > 1) {
-                u = 1 - u;
-                v = 1 - v;
-            }
-            V3 p = lt.a + lt.v * v + lt.u * u; // a + v' * v + u' * u
-            dir = norm(p - pos);
+        } else {
+            dir = light_sample(S, LT, pos, rng);
         }
     }
     if (isnan_f(dir.x) || isnan_f(dir.y) || isnan_f(dir.z)) { // :569-571
@@ -203,7 +225,14 @@ DEV ShadeResult shade_hit(const DevScene &S, const LightTabs &LT, const Hit &h, 
     const float VNDF_p = vndf_pdf(vr, rd, ii.shading_normal, dir);
     float MIS_p;
     const float cos_p = rmax(dot(ii.normal, dir) / PI_F, 0.0f); // cosine_dist::pdf :123-128
-    if (!has_lights) {
+    if (ENV_DIST) { // mix_dist::pdf over k components: (sum of the component pdfs) / k
+        float r = 0;
+        r += cos_p;
+        if (has_lights)
+            r += lights_pdf<STATS>(S, LT, pos, dir, stk, st);
+        r += env_pdf(S.env, dir);
+        MIS_p = r / (float)mix_k;
+    } else if (!has_lights) {
         MIS_p = cos_p;
     } else { // mix_dist::pdf :395-407
         float r = 0;

@@ -154,6 +154,16 @@ struct DevBvh {
 };
 #define RT_SHADE_LIGHTS_F4 384 /* 6 KB of LDS in wf_shade: 4 pieces per inner node + 4 per light triangle (e.g. 31 nodes + 64 lights) */
 
+// The float environment of rt_set_environment (rt_abi.h: the rule; DESIGN.md "Environment lighting"). texels == null: none, the background
+// is DevScene::bg_tex's. marg == null: a float map without a distribution (no RT_ENV_IMPORTANCE, or every weight zero).
+struct DevEnv {
+    const float *texels; // [height][width] float4 {r, g, b, 0}, row-major, row 0 = the +y pole; 16-byte aligned
+    const float *marg;   // [height + 1] marginal CDF over rows: marg[0] = 0, marg[height] = 1
+    const float *rows;   // [height][width + 1] one CDF per row, each normalised on its own: row[0] = 0, row[width] = 1
+    const float *band;   // [height + 1] cos(pi i / height), the row edges; then [height] the cell solid angles of row i, as floats
+    uint32_t width, height;
+};
+
 struct DevScene {
     DevBvh scene;
     DevBvh lights;
@@ -173,6 +183,7 @@ struct DevScene {
     uint32_t n_triangles;           // scene.objects.size(): rt_cast_rays reports analytic primitive i as n_triangles + i
     int32_t bg_tex;                 // Scene::bg (scene.h:81): view of the environment map in `textures`, -1 = the 1x1 WHITE_TEXTURE default
     uint32_t pad_bg;
+    DevEnv env;                     // rt_set_environment's float map: when set it takes bg_tex's place in every wavefront lookup
 };
 
 struct DevStats { // device-side counters, see rt_stats in include/rt_abi.h

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "rt_env.h"
 #include "rt_scene_impl.h"
 
 namespace {
@@ -158,6 +159,39 @@ extern "C" int rt_bg_at(rt_scene *s, const float *dirs, uint32_t n, float *rgb_o
     const ProbeOut out[] = {{rgb_out, (size_t)n * 12}};
     return probe_round_trip(s, "rt_bg_at", dirs, (size_t)n * 12, out,
                             [&](const float *d_dirs, void *const *d) { return rt::launch_bg_at(s->dev, d_dirs, n, static_cast<float *>(d[0]), s->stream); });
+}
+
+// The two probes of a float environment's distribution (rt_set_environment with RT_ENV_IMPORTANCE): env_pdf / env_sample_xi of rt_dev_env.h
+static int check_env_probe(const rt_scene *s, const char *fn, const void *in, uint32_t n, const void *out) {
+    if (!s || (n && (!in || !out)))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null argument");
+    if (s->group)
+        return rt::fail(RT_ERR_UNSUPPORTED, std::string(fn) + ": a multi-GPU scene has no float environment");
+    if (!s->dev.env.texels || !s->dev.env.marg)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the scene has no environment distribution (rt_set_environment with RT_ENV_IMPORTANCE and a map "
+                                                              "that is not all zero)");
+    return RT_OK;
+}
+extern "C" int rt_env_pdf(rt_scene *s, const float *dirs, uint32_t n, float *pdf_out) {
+    if (int rc = check_env_probe(s, "rt_env_pdf", dirs, n, pdf_out); rc != RT_OK)
+        return rc;
+    if (n == 0)
+        return RT_OK;
+    const ProbeOut out[] = {{pdf_out, (size_t)n * 4}};
+    return probe_round_trip(s, "rt_env_pdf", dirs, (size_t)n * 12, out,
+                            [&](const float *d_dirs, void *const *d) { return rt::launch_env_pdf(s->dev.env, d_dirs, n, static_cast<float *>(d[0]), s->stream); });
+}
+extern "C" int rt_env_sample(rt_scene *s, const float *xi4, uint32_t n, float *dirs_out) {
+    if (int rc = check_env_probe(s, "rt_env_sample", xi4, n, dirs_out); rc != RT_OK)
+        return rc;
+    if (n == 0)
+        return RT_OK;
+    for (size_t k = 0; k < (size_t)n * 4; ++k) // the binary searches rely on it: 1.0 would select the cell behind the last
+        if (!(xi4[k] >= 0.0f && xi4[k] < 1.0f))
+            return rt::fail(RT_ERR_INVALID_ARG, "rt_env_sample: a uniform outside [0, 1)");
+    const ProbeOut out[] = {{dirs_out, (size_t)n * 12}};
+    return probe_round_trip(s, "rt_env_sample", xi4, (size_t)n * 16, out,
+                            [&](const float *d_xi, void *const *d) { return rt::launch_env_sample(s->dev.env, d_xi, n, static_cast<float *>(d[0]), s->stream); });
 }
 
 extern "C" int rt_bvh_device_dump(rt_scene *s, int which, uint32_t *n_inner, uint32_t *n_tris, uint32_t *root, uint32_t *nodes64, uint32_t *tris48) {

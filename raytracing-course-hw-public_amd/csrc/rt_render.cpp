@@ -336,6 +336,9 @@ int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, cons
     if (s->wide_built && !wavefront)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_render: a scene built with RT_BUILD_WIDE renders through the wavefront pipeline only (the megakernel and "
                                             "the reference-RNG parity mode walk the reference's binary tree: create the scene without RT_BUILD_WIDE)");
+    if (s->dev.env.texels && !wavefront)
+        return rt::fail(RT_ERR_UNSUPPORTED, "rt_render: a scene with a float environment (rt_set_environment) renders through the wavefront pipeline only (the "
+                                            "megakernel and the reference-RNG parity mode are the reference's Scene::bg_at: rt_set_environment(scene, NULL) first)");
     s->ext_events.reset();
     uint32_t passes = 0, packet_passes = 0; // rt_stats.passes / packet_passes
     rt::PacketPolicy &pol = !sensors ? s->pkt : s->pkt_sensor[n_views == 1 ? (*sensors)[0].kind : 5u];

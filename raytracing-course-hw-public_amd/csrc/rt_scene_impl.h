@@ -109,6 +109,7 @@ struct rt_scene {
     std::vector<void *> owned;       // what lives as long as the scene: materials, textures, texels, tables, counters
     std::vector<void *> geo_owned;   // the scene tree and its records ...
     std::vector<void *> light_owned; // ... and the light tree's: freed when rt_update_geometry swaps new ones in
+    std::vector<void *> env_owned;   // the float environment of rt_set_environment (DevScene::env): texels and tables; empty without one
     std::shared_ptr<const rt::PreparedScene> prep; // the host half of rt_create, shared by the replicas of a multi-GPU scene
     std::shared_ptr<const rt::PreparedGeometry> geo; // its geometry half: prep->geo until rt_update_geometry replaces it
     uint32_t live_accums = 0;  // accumulators of this scene (rt_accum_create* / rt_accum_destroy): their sums pin the geometry
@@ -346,6 +347,8 @@ struct rt_scene {
         for (void *p : geo_owned)
             (void)hipFree(p);
         for (void *p : light_owned)
+            (void)hipFree(p);
+        for (void *p : env_owned)
             (void)hipFree(p);
         if (wf_feat)
             (void)hipFree(wf_feat);

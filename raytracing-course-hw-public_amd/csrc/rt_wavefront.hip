@@ -74,14 +74,15 @@ DEV uint32_t wf_global_pixel(const WfLaunch &L, uint32_t local_pixel) {
 // ------------------------------------------------------------------------------------------------ generate
 // The first record of path i, in queue slot i: the ray (o, d) with `rng` as gen_ray left it (behind its two jitter draws), full budget, no
 // pending frames. The one definition of a path's first record: a camera's rays (wf_primary_ray) and a caller's (wf_generate_rays) both end here.
-DEV void wf_store_first(const DevScene &S, const WfLaunch &L, uint32_t i, V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) {
-    wf_store_path(L.paths_in + i, wf_pack(o, d, i, next_shade_class(rng, S.lights.n_tris != 0), L.ray_depth, 0u, rng.g));
+// ENVD (every first stage): the scene's mix_dist has the environment as a component (ENV_FLOAT_DIST), which next_shade_class must know.
+template <bool ENVD> DEV void wf_store_first(const DevScene &S, const WfLaunch &L, uint32_t i, V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) {
+    wf_store_path(L.paths_in + i, wf_pack(o, d, i, next_shade_class<ENVD>(rng, S.lights.n_tris != 0), L.ray_depth, 0u, rng.g));
 }
 
 // gen_ray (raytracer.h:527-538) for sample s of pixel pix of view v: camera, jitter and seeding, written as the primary-ray record of queue
 // slot (= path) i. The one definition of a camera path's first ray: wf_generate and the accumulators' wf_generate_list both call it, so sample
 // s of pixel p is the same ray whichever of them draws it.
-DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32_t v, uint32_t pix, uint32_t s) {
+template <bool ENVD> DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32_t v, uint32_t pix, uint32_t s) {
     // the view is wave-uniform except where a wave straddles two views: then every lane reads its own record
     const uint32_t v0 = __builtin_amdgcn_readfirstlane(v);
     WfView view;
@@ -93,10 +94,10 @@ DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32
     Rng<RT_RNG_DEVICE> rng;
     rt_xoshiro_seed(&rng.g, view.seed, pix, s);
     const V3 rd = gen_ray_dir(rng, pix, L.width, L.height, view.tan_x, view.tan_y, cam_right, cam_up, cam_fwd);
-    wf_store_first(S, L, i, cam_pos, rd, rng);
+    wf_store_first<ENVD>(S, L, i, cam_pos, rd, rng);
 }
 
-template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
+template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
     LaneStats<STATS> st;
     if (blockIdx.x == 0 && threadIdx.x == 0)
         L.counters[WF_CNT_IN] = L.n_paths; // the first bounce's queue is the identity: slot i holds path i
@@ -107,7 +108,7 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const D
         const uint32_t v = vpix / L.view_pixels;
         const uint32_t pix = vpix - v * L.view_pixels; // pixel within its view
         const uint32_t s = L.first_sample + ds;
-        wf_primary_ray(S, L, i, v, pix, s);
+        wf_primary_ray<ENVD>(S, L, i, v, pix, s);
         st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
     }
     st.flush(L.stats);
@@ -116,7 +117,7 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate(const D
 // An accumulator pass (WfAccum): path i takes the entry whose prefix range holds off[first] + i (binary search; a pixel's paths stay
 // consecutive, so the 64 queue positions of a packet are still the samples of one or a few pixels). Paths [exact count, L.n_paths) of the
 // upper bound get an empty finished sample (no frames), so that wf_fold, which runs over L.n_paths, reads nothing stale.
-template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list(const DevScene S, const WfLaunch L, const WfAccum A) {
+template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_list(const DevScene S, const WfLaunch L, const WfAccum A) {
     LaneStats<STATS> st;
     const uint32_t *off = A.list_off + A.first_entry;
     const uint32_t base = off[0], n_exact = off[A.n_entries] - base;
@@ -137,7 +138,7 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list(co
                 hi = mid - 1u;
         }
         const uint32_t e = A.first_entry + lo;
-        wf_primary_ray(S, L, i, 0u, A.list_pix[e], A.list_base[e] + (g - off[lo])); // an accumulator has one view
+        wf_primary_ray<ENVD>(S, L, i, 0u, A.list_pix[e], A.list_base[e] + (g - off[lo])); // an accumulator has one view
         st.cast();
     }
     st.flush(L.stats);
@@ -147,7 +148,7 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list(co
 // sample `first_sample + ds % K` of ray `output * G + ds / K` of the caller's buffer. The lane reads its 32-byte record as two 16-byte pieces
 // (with K = 1 the lanes of a wave read consecutive records), seeds the stream the record names, makes gen_ray's two jitter draws and discards
 // them (raytracer.h:527-538: the stream then stands where a camera ray's stands), and stores the ray as given: no normalisation.
-template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_rays(const DevScene S, const WfLaunch L, const WfRays R) {
+template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_rays(const DevScene S, const WfLaunch L, const WfRays R) {
     LaneStats<STATS> st;
     if (blockIdx.x == 0 && threadIdx.x == 0)
         L.counters[WF_CNT_IN] = L.n_paths;
@@ -162,7 +163,7 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_rays(co
         rt_xoshiro_seed(&rng.g, R.seed, p1.z, p1.w + (ds - sub * R.samples)); // the sample index wraps mod 2^32
         (void)uniform_real(rng, 0.0f, 1.0f);
         (void)uniform_real(rng, 0.0f, 1.0f);
-        wf_store_first(S, L, i, mk(__uint_as_float(p0.x), __uint_as_float(p0.y), __uint_as_float(p0.z)),
+        wf_store_first<ENVD>(S, L, i, mk(__uint_as_float(p0.x), __uint_as_float(p0.y), __uint_as_float(p0.z)),
                        mk(__uint_as_float(p0.w), __uint_as_float(p1.x), __uint_as_float(p1.y)), rng);
         st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
     }
@@ -171,7 +172,7 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_rays(co
 
 // The sensor siblings of wf_generate and wf_generate_list (rt_render_sensors, rt_accum_create_sensor): the same path numbering, the ray from
 // sensor_ray (rt_dev_sensor.h) of the sensor table instead of wf_primary_ray of the view table. L.views is not read.
-template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_sensor(const DevScene S, const WfLaunch L, const WfSensors T) {
+template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_sensor(const DevScene S, const WfLaunch L, const WfSensors T) {
     LaneStats<STATS> st;
     if (blockIdx.x == 0 && threadIdx.x == 0)
         L.counters[WF_CNT_IN] = L.n_paths;
@@ -181,13 +182,13 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_sensor(
         const uint32_t vpix = wf_global_pixel(L, L.first_pixel + lp);
         const uint32_t v = vpix / L.view_pixels;
         sensor_ray_of(T, v, L.width, L.height, vpix - v * L.view_pixels, L.first_sample + ds,
-                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first(S, L, i, o, d, rng); });
+                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
         st.cast();
     }
     st.flush(L.stats);
 }
 
-template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list_sensor(const DevScene S, const WfLaunch L, const WfAccum A, const WfSensors T) {
+template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_list_sensor(const DevScene S, const WfLaunch L, const WfAccum A, const WfSensors T) {
     LaneStats<STATS> st;
     const uint32_t *off = A.list_off + A.first_entry;
     const uint32_t base = off[0], n_exact = off[A.n_entries] - base;
@@ -209,7 +210,7 @@ template <bool STATS> __global__ __launch_bounds__(256) void wf_generate_list_se
         }
         const uint32_t e = A.first_entry + lo;
         sensor_ray_of(T, 0u, L.width, L.height, A.list_pix[e], A.list_base[e] + (g - off[lo]), // an accumulator has one sensor
-                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first(S, L, i, o, d, rng); });
+                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
         st.cast();
     }
     st.flush(L.stats);
@@ -547,7 +548,7 @@ __global__ __launch_bounds__(256) void wf_features(const DevScene S, const WfLau
 // ------------------------------------------------------------------------------------------------ shade
 // LIGHTS_LDS: the light BVH (inner nodes, triangles, aux) is small enough (DevBvh::lds_inner) to be staged in LDS once per
 // block; bvh_mix_dist's sample and pdf then read it there: a dozen dependent L1 round trips per hit become LDS reads.
-template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(256, RT_SHADE_WAVES_PER_SIMD) void wf_shade(const DevScene S, const WfLaunch L) {
+template <bool STATS, bool LIGHTS_LDS, int ENV> __global__ __launch_bounds__(256, RT_SHADE_WAVES_PER_SIMD) void wf_shade(const DevScene S, const WfLaunch L) {
     __shared__ float s_lin[256];
     __shared__ float s_gam[256];
     __shared__ uint32_t s_stack[STACK_LDS_DWORDS(RT_SHADE_LDS_DEPTH, 3)];
@@ -605,7 +606,7 @@ template <bool STATS, bool LIGHTS_LDS, bool ENV> __global__ __launch_bounds__(25
             } else {
                 survive = true;
                 st.cast();
-                next = wf_pack(sr.nro, sr.nrd, path, next_shade_class(rng, has_lights), depth_left, nb, rng.g);
+                next = wf_pack(sr.nro, sr.nrd, path, next_shade_class<ENV == ENV_FLOAT_DIST>(rng, has_lights), depth_left, nb, rng.g);
                 if (L.emit_keys)
                     next_key = rt_ray_order_key(sr.nro.x, sr.nro.y, sr.nro.z, sr.nrd.x, sr.nrd.y, sr.nrd.z, S.bounds_lo, S.bounds_inv);
             }
@@ -925,17 +926,17 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         return e;
     if (packet_census_out)
         packet_census_out[0] = packet_census_out[1] = 0ull;
-    e = with_bools([&](auto ST) {
+    e = with_bools([&](auto ST, auto ED) {
         if (sensors && acc) // a sensor's accumulator pass, a sensor render: the sensor table takes the view table's place
-            return RT_LAUNCH_CHECKED((wf_generate_list_sensor<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc, *sensors);
+            return RT_LAUNCH_CHECKED((wf_generate_list_sensor<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc, *sensors);
         if (sensors)
-            return RT_LAUNCH_CHECKED((wf_generate_sensor<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *sensors);
+            return RT_LAUNCH_CHECKED((wf_generate_sensor<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *sensors);
         if (acc) // an accumulator pass: the first stage follows the round's list (wf_generate_list)
-            return RT_LAUNCH_CHECKED((wf_generate_list<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
+            return RT_LAUNCH_CHECKED((wf_generate_list<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
         if (rays) // a pass of rt_render_rays: the caller's rays and streams (wf_generate_rays)
-            return RT_LAUNCH_CHECKED((wf_generate_rays<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *rays);
-        return RT_LAUNCH_CHECKED((wf_generate<ST>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
-    }, stats);
+            return RT_LAUNCH_CHECKED((wf_generate_rays<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *rays);
+        return RT_LAUNCH_CHECKED((wf_generate<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
+    }, stats, S.env.texels != nullptr && S.env.marg != nullptr);
     if (e != hipSuccess)
         return e;
     const int ext_blocks = (int)(L.stack_stride / 256u); // rt_scene.cpp sizes the overflow workspace for exactly this grid
@@ -1008,14 +1009,18 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             return e;
         // ENV: the scene has an environment map (DevScene::bg_tex): the miss branch looks it up (scene.h:83-89); those instantiations read the
         // light tables from global memory (LIGHTS_LDS only saves latency), so a scene without one never pays for the lookup's registers
-        const bool env = S.bg_tex >= 0;
-        const bool lights_lds = S.lights.lds_inner != 0u && !env;
-        e = with_bools([&](auto ST, auto LDS, auto ENV) {
-            if constexpr (LDS && ENV) // never chosen (above), never instantiated
+        // A float map (rt_set_environment, DevScene::env) takes the texture's place: ENV_FLOAT, or ENV_FLOAT_DIST when it has a distribution
+        // and mix_dist samples it. A scene without one launches what it always launched.
+        const bool fenv = S.env.texels != nullptr;
+        const bool env = fenv ? S.env.marg != nullptr : S.bg_tex >= 0;
+        const bool lights_lds = S.lights.lds_inner != 0u && !env && !fenv;
+        e = with_bools([&](auto ST, auto LDS, auto FENV, auto ENV) {
+            constexpr int KIND = FENV ? (ENV ? ENV_FLOAT_DIST : ENV_FLOAT) : (ENV ? ENV_TEX8 : ENV_NONE);
+            if constexpr (LDS && KIND != ENV_NONE) // never chosen (above), never instantiated
                 return hipErrorInvalidValue;
             else
-                return RT_LAUNCH_CHECKED((wf_shade<ST, LDS, ENV>), dim3(shade_blocks), block, 0, stream, S, L);
-        }, stats, lights_lds, env);
+                return RT_LAUNCH_CHECKED((wf_shade<ST, LDS, KIND>), dim3(shade_blocks), block, 0, stream, S, L);
+        }, stats, lights_lds, fenv, env);
         if (e != hipSuccess)
             return e;
         WF_LAUNCH(wf_advance, dim3(1), dim3(64), 0, stream, L.counters, L.stripes);
