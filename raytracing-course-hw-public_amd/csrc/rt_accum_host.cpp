@@ -1,6 +1,6 @@
 // rt_accum_host.cpp — the host side of the accumulators (rt_abi.h rt_accum_*; their kernels are rt_accum.hip).
 //
-// An accumulator owns its per-pixel state (S, E, n, err, the round's target and list, about 64 B per pixel) and one view record; it
+// An accumulator owns its per-pixel state (S, E, n, err, the round's target and list, about 64 B per pixel) and one camera record; it
 // borrows the scene's stream, its wavefront workspace and its framebuffer staging. Every call ends with the stream synchronised, so an
 // rt_render on the same scene in between only ever sees an idle workspace, and never touches the accumulator's buffers.
 #include <algorithm>
@@ -12,11 +12,8 @@
 struct rt_accum {
     rt_scene *scene = nullptr;
     uint32_t width = 0, height = 0;
-    WfView view{};            // camera, tangents and seed (host copy of d_view)
-    WfView *d_view = nullptr; // WfLaunch::views of its passes: the one view
-    bool has_sensor = false;  // rt_accum_create_sensor: the passes read `d_sensor` (WfSensors::table) instead of d_view
-    WfSensor sensor{};        // host copy of d_sensor
-    WfSensor *d_sensor = nullptr;
+    WfSensor sensor{};            // its camera: rt_accum_create_sensor's, or the pinhole record of {camera, seed} (host copy of d_sensor)
+    WfSensor *d_sensor = nullptr; // WfLaunch::sensors of its passes: the one record
     rt::AccumRound R{};
     std::vector<void *> owned;
     rt::PacketPolicy pkt; // of its own passes, kept apart from rt_render's
@@ -67,11 +64,9 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
     if (sensor) {
         if (int rc = rt::check_sensor(*sensor, width, height, "rt_accum_create_sensor"); rc != RT_OK)
             return rc;
-        a->has_sensor = true;
         a->sensor = rt::make_sensor(*sensor, width, height);
-        a->view = rt::make_view(sensor->camera, width, height, sensor->seed);
     } else {
-        a->view = rt::make_view(camera ? *camera : s->cam, width, height, seed);
+        a->sensor = rt::make_sensor(camera ? *camera : s->cam, seed, width, height);
     }
     const size_t n = (size_t)width * height;
     auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int { return accum_alloc(a.get(), bytes, ptr, "rt_accum_create"); };
@@ -84,7 +79,7 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
         (rc = alloc(4 * n, &R.err)) != RT_OK || (rc = alloc(4 * n, &R.target)) != RT_OK || (rc = alloc(8 * n, &R.scan_in)) != RT_OK ||
         (rc = alloc(8 * n, &R.scan)) != RT_OK || (rc = alloc(4 * n, &R.list_pix)) != RT_OK || (rc = alloc(4 * n, &R.list_base)) != RT_OK ||
         (rc = alloc(4 * (n + 1), &R.list_off)) != RT_OK || (rc = alloc(8, &R.totals)) != RT_OK || (rc = alloc(R.scan_temp_bytes, &R.scan_temp)) != RT_OK ||
-        (rc = alloc(sizeof(WfView), &a->d_view)) != RT_OK || (rc = alloc(sizeof(WfSensor), &a->d_sensor)) != RT_OK)
+        (rc = alloc(sizeof(WfSensor), &a->d_sensor)) != RT_OK)
         return rc;
     if (accum_flags & RT_ACCUM_FEATURES) {
         WfFeat &F = a->F;
@@ -101,7 +96,6 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
     HIP_TRY(hipMemsetAsync(R.even_sum, 0, 12 * n, s->stream));
     HIP_TRY(hipMemsetAsync(R.count, 0, 4 * n, s->stream));
     HIP_TRY(hipMemsetD32Async(R.err, 0x7F800000 /* +inf: n_p < 2 */, n, s->stream));
-    HIP_TRY(hipMemcpyAsync(a->d_view, &a->view, sizeof(WfView), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(a->d_sensor, &a->sensor, sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     a->counted = true;
@@ -165,13 +159,11 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
     W.shard_count = 1;
     W.shard_block = n_pix;
     W.ray_depth = s->dev.ray_depth;
-    W.views = a->d_view;
+    W.sensors = a->d_sensor;
     W.view_pixels = n_pix;
     W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
     W.stats = counters ? s->d_stats : nullptr;
-    const WfSensors sensor_table{a->d_sensor};
-    // the one origin of the pass's rays, where it has one (rt_render.cpp launch_pass)
-    const float *cam_pos = !a->has_sensor ? a->view.pos : rt::sensor_single_origin(a->sensor.kind) ? a->sensor.pos : nullptr;
+    const float *cam_pos = rt::single_origin(&a->sensor, 1); // the one origin of the pass's rays, where it has one (rt_render.cpp launch_pass)
     s->ext_events.reset();
     uint32_t passes = 0, packet_passes = 0, rounds = 0;
     uint64_t added = 0;
@@ -207,8 +199,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 W.n_paths = (uint32_t)std::min<uint64_t>((uint64_t)A.n_entries * C, tot[1]); // an upper bound: wf_generate_list reads the exact count
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
-                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr, nullptr, cam_pos,
-                                        a->has_sensor ? &sensor_table : nullptr));
+                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr, nullptr, cam_pos));
                 passes += 1;
                 packet_passes += W.use_packet;
                 if (p->progress && !ad) {

@@ -1,7 +1,7 @@
-// rt_dev_sensor.h — the sensor models of rt_abi.h rt_sensor on the device: ONE function that makes (origin, direction, RNG state) of sample s
-// of pixel pix from a sensor record. The rectangle first stage (wf_generate_sensor), the list first stage of the accumulators
-// (wf_generate_list_sensor) and the writer of rt_sensor_rays (wf_sensor_rays) all call it, so sample s of pixel p is the same ray whoever
-// draws it. The rule is stated operation by operation in rt_abi.h; every line here is one line of it.
+// rt_dev_sensor.h — the cameras of the wavefront pipeline on the device (rt_abi.h rt_sensor; a view of rt_render* is a pinhole record): ONE
+// function that makes (origin, direction, RNG state) of sample s of pixel pix from a sensor record. The rectangle first stage (wf_generate),
+// the list first stage of the accumulators (wf_generate_list) and the writer of rt_sensor_rays (wf_sensor_rays) all call it, so sample s of
+// pixel p is the same ray whoever draws it. The rule is stated operation by operation in rt_abi.h; every line here is one line of it.
 #pragma once
 #include "rt_dev_shade.h"
 
@@ -66,15 +66,15 @@ DEV void sensor_ray(const WfSensor &sn, uint32_t width, uint32_t height, uint32_
 }
 
 // The sensor of a lane: wave-uniform except where a wave straddles two sensors of a multi-sensor call. The uniform wave reads the record
-// through scalar loads and branches on a scalar kind; the straddling wave reads per lane (wf_primary_ray's idiom). `emit(o, d, rng)`.
-template <class Emit> DEV void sensor_ray_of(const WfSensors &T, uint32_t v, uint32_t width, uint32_t height, uint32_t pix, uint32_t s, Emit emit) {
+// through scalar loads and branches on a scalar kind; the straddling wave reads per lane. `emit(o, d, rng)`.
+template <class Emit> DEV void sensor_ray_of(const WfSensor *table, uint32_t v, uint32_t width, uint32_t height, uint32_t pix, uint32_t s, Emit emit) {
     const uint32_t v0 = __builtin_amdgcn_readfirstlane(v);
     V3 o, d;
     Rng<RT_RNG_DEVICE> rng;
     if (__ballot(v != v0) == 0ull)
-        sensor_ray(T.table[v0], width, height, pix, s, o, d, rng);
+        sensor_ray(table[v0], width, height, pix, s, o, d, rng);
     else
-        sensor_ray(T.table[v], width, height, pix, s, o, d, rng);
+        sensor_ray(table[v], width, height, pix, s, o, d, rng);
     emit(o, d, rng);
 }
 

@@ -11,6 +11,7 @@
 // Every lane of a wavefront follows its own ray, so accesses are per-lane gathers: records are sized and aligned
 // so that one gather touches the minimum number of 64/128-byte lines.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/rt_abi.h"
@@ -250,15 +251,24 @@ inline uint32_t wf_stripe_base(uint32_t k, uint32_t n_slots) {
     return 64u * (k * q + (k < r ? k : r));
 }
 
-// One camera view of a render (rt_render_views; rt_render is the one view of the scene's own camera): what gen_ray (raytracer.h:527-538)
-// reads of Camera, its two hoisted tangents and the view's RNG seed. One 64-byte record per view, a table in HBM that wf_generate indexes
-// with virtual pixel / WfLaunch::view_pixels (the virtual image is the views stacked view-major).
-struct alignas(64) WfView {
+// One camera of a pass: a view of rt_render / rt_render_views (a pinhole record), a sensor of rt_render_sensors, the one camera of an
+// accumulator (rt_abi.h rt_sensor: the rule). What gen_ray (raytracer.h:527-538) reads of Camera, its two hoisted tangents and the RNG seed,
+// then the kind and what the host hoists for it (rt_sensor.cpp make_sensor, the one place that fills it). One 128-byte record per camera, a
+// table in HBM (WfLaunch::sensors) that the first stages index with virtual pixel / WfLaunch::view_pixels (the virtual image is the views
+// stacked view-major); the rt_sensor_rays writer takes one record as its own argument.
+struct alignas(64) WfSensor {
     float pos[3], right[3], up[3], fwd[3];
-    float tan_x, tan_y; // tan(fov_x/2), tan(fov_y/2) of this view at the render's aspect (rt_scene.cpp camera_tangents)
-    uint64_t seed;      // RT_RNG_DEVICE stream seed
+    float tan_x, tan_y;   // tan(fov_x/2), tan(fov_y/2) of this camera at the render's aspect
+    uint64_t seed;        // RT_RNG_DEVICE stream seed
+    uint32_t kind;        // RT_SENSOR_*
+    float half_fov;       // fov_x / 2 (FISHEYE)
+    float half_width;     // ORTHOGRAPHIC
+    float half_h;         // half_width * (float)H / (float)W
+    float lens_radius;    // THIN_LENS
+    float focus_distance; // THIN_LENS
+    uint32_t pad[10];
 };
-static_assert(sizeof(WfView) == 64, "WfView must be 64 bytes");
+static_assert(sizeof(WfSensor) == 128, "WfSensor must be 128 bytes");
 
 struct WfLaunch {
     uint32_t width, height, samples; // ONE view's image, total SPP
@@ -267,7 +277,7 @@ struct WfLaunch {
     uint32_t n_paths;                    // pass_pixels * pass_samples
     uint32_t shard_index, shard_count, shard_block;
     uint32_t ray_depth;
-    const WfView *views;                 // [n_views]: camera, tangents and seed of virtual pixel p's view views[p / view_pixels]
+    const WfSensor *sensors;             // [n_views]: the camera of virtual pixel p is sensors[p / view_pixels] (null in a pass of rt_render_rays)
     uint32_t view_pixels;                // width * height
     WfPath *paths_in, *paths_out; // this bounce's queue / the next one (compacted survivors)
     WfHit *hits;             // closest hit of the ray processed at queue POSITION q (position in `order` when sorted): wf_extend's
@@ -304,6 +314,8 @@ struct WfLaunch {
     size_t sort_temp_bytes;
     DevStats *stats;         // may be null
 };
+// every kernel takes WfLaunch by value: its layout is part of their argument layout
+static_assert(sizeof(WfLaunch) == 264 && offsetof(WfLaunch, sensors) == 48 && offsetof(WfLaunch, view_pixels) == 56, "WfLaunch must not move");
 
 // A pass of an accumulator round (rt_accum_*, rt_accum.hip): the wavefront pipeline's first and last stages driven by a list of entries
 // (pixel p, k_p new samples) in increasing pixel order instead of a (pixel tile x sample range) rectangle. Path i of the pass belongs to
@@ -337,27 +349,6 @@ struct WfRays {
     uint32_t group;        // G: consecutive rays per output
     uint32_t samples;      // K: samples per ray
     uint64_t seed;         // rt_params.seed
-};
-
-// One sensor of rt_render_sensors / rt_accum_create_sensor (rt_abi.h rt_sensor: the rule): WfView's fields in WfView's places, then the kind
-// and what the host hoists for it (rt_sensor.cpp make_sensor, the one place that fills it). One 128-byte record per sensor, a table in HBM
-// beside the view table; the sensor first stages (rt_wavefront.hip wf_generate_sensor*) and the rt_sensor_rays writer take it as their own
-// argument, so WfLaunch, WfView and the camera kernels do not know about it.
-struct alignas(64) WfSensor {
-    float pos[3], right[3], up[3], fwd[3];
-    float tan_x, tan_y;   // rt::make_view's
-    uint64_t seed;
-    uint32_t kind;        // RT_SENSOR_*
-    float half_fov;       // fov_x / 2 (FISHEYE)
-    float half_width;     // ORTHOGRAPHIC
-    float half_h;         // half_width * (float)H / (float)W
-    float lens_radius;    // THIN_LENS
-    float focus_distance; // THIN_LENS
-    uint32_t pad[10];
-};
-static_assert(sizeof(WfSensor) == 128, "WfSensor must be 128 bytes");
-struct WfSensors {
-    const WfSensor *table; // [n_sensors]: the sensor of virtual pixel p is table[p / WfLaunch::view_pixels]
 };
 
 struct RenderLaunch {

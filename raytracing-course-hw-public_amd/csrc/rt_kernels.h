@@ -67,12 +67,10 @@ struct WfHostSync {
 // wf_resolve; first_pass / last_pass are not read. Null for rt_render. `feat` (optional, with `acc`): the pass of a feature accumulator:
 // wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither.
 // `rays` (optional, without `acc`): a pass of rt_render_rays: wf_generate_rays replaces wf_generate; wf_fold and wf_resolve are rt_render's.
-// `sensors` (optional, without `rays`): the pass's primary rays come from the sensor table (rt_abi.h rt_sensor) instead of L.views:
-// wf_generate_sensor / wf_generate_list_sensor replace wf_generate / wf_generate_list; everything behind the first stage is unchanged.
+// Without `rays` the primary rays come from the camera table L.sensors (a view is a pinhole record), whatever the entry point.
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
-                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr,
-                                 const WfSensors *sensors = nullptr);
+                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr);
 // rt_sensor_rays: the n = pixels x samples rt_ray records of pixels [first_pixel, ..) x samples [first_sample, first_sample + samples) of
 // the sensor record `d_sensor` (device) -> `d_rays_out` (device, 32 B per record, 16-byte aligned)
 hipError_t launch_sensor_rays(const WfSensor *d_sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples, uint32_t n,

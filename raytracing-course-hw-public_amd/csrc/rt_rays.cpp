@@ -1,9 +1,9 @@
 // rt_rays.cpp — rt_render_rays / rt_render_rays_rgb8 (rt_abi.h): the wavefront pipeline over rays and RNG streams the caller supplies.
 //
-// The call is planned as rt_render plans an image: n_rays / G outputs take the place of the pixels and G * K samples per output the place
-// of the SPP, in (output tile) x (sample range) passes under wavefront_max_paths. Only the first stage differs (wf_generate_rays reads the
-// ray buffer where wf_generate asks a camera): bounces, fold and resolve are rt_render's own launches, so a camera's own primary rays give
-// rt_render's image bit for bit.
+// The call runs rt_render's own pass loop (rt_render.cpp run_passes): n_rays / G outputs take the place of the pixels and G * K samples per
+// output the place of the SPP, in (output tile) x (sample range) passes under wavefront_max_paths. Only the first stage differs
+// (wf_generate_rays reads the ray buffer where wf_generate asks a camera): bounces, fold and resolve are rt_render's own launches, so a
+// camera's own primary rays give rt_render's image bit for bit.
 #include <algorithm>
 #include <cstring>
 
@@ -73,19 +73,12 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     rt::PacketPolicy pol; // of this call: rt_render's, measured on camera rays of its image shape, is not disturbed
     s->ext_events.reset();
-    uint32_t passes = 0, packet_passes = 0;
     auto queue = [&]() -> int {
         if (counters)
             HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
         if (!device_fb) // once per call; the caller's buffer outlives the stream sync below
             HIP_TRY(hipMemcpyAsync(s->d_rays, rays, (size_t)n_rays * sizeof(rt_ray), hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipEventRecord(s->ev0, s->stream));
-        // (output tile) x (sample range) passes, as rt_render plans (pixel tile) x (sample range)
-        const uint64_t max_paths = rt::wavefront_max_paths(s, p);
-        const uint64_t tile = std::min<uint64_t>(n_out, max_paths);
-        const uint32_t pass_spp = (uint32_t)std::clamp<uint64_t>(max_paths / tile, 1, spo);
-        if (int rc = s->ensure_wavefront(tile * pass_spp, tile, s->dev.ray_depth); rc != RT_OK)
-            return rc;
         WfLaunch W{};
         W.width = n_out; // the virtual image is one row of outputs (nothing on the device reads the size: it keys the packet policy)
         W.height = 1;
@@ -95,45 +88,12 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
         W.shard_block = n_out;
         W.ray_depth = s->dev.ray_depth;
         W.view_pixels = n_out;
-        s->wf_bind(W);
         W.fb = d_fb;
         W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
         W.stats = counters ? s->d_stats : nullptr;
         const WfRays R{reinterpret_cast<const uint4_pod *>(d_rays), G, K, p->seed};
-        // progress: one event per pass, the host one pass ahead of the device (rt_render's discipline)
-        const uint32_t n_passes = (uint32_t)((n_out + tile - 1) / tile) * ((spo + pass_spp - 1) / pass_spp);
-        uint32_t reported = 0, pass_no = 0;
-        if (p->progress)
-            while (s->pass_events.size() < n_passes) {
-                hipEvent_t ev = nullptr;
-                if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-                    return rt::fail(RT_ERR_HIP, name + ": progress event");
-                s->pass_events.push_back(ev);
-            }
-        for (uint64_t j0 = 0; j0 < n_out; j0 += tile) {
-            W.first_pixel = (uint32_t)j0;
-            W.pass_pixels = (uint32_t)std::min<uint64_t>(tile, n_out - j0);
-            for (uint32_t s0 = 0; s0 < spo; s0 += pass_spp) {
-                W.first_sample = s0;
-                W.pass_samples = std::min<uint32_t>(pass_spp, spo - s0);
-                W.n_paths = W.pass_pixels * W.pass_samples;
-                HIP_TRY(rt::launch_pass(s, p, pol, W, 1, s0 == 0, s0 + W.pass_samples >= spo, stats != nullptr, nullptr, nullptr, &R));
-                passes += 1;
-                packet_passes += W.use_packet;
-                if (p->progress) {
-                    HIP_TRY(hipEventRecord(s->pass_events[pass_no], s->stream));
-                    if (pass_no > 0) {
-                        HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
-                        p->progress(++reported, n_passes, p->progress_user);
-                    }
-                }
-                ++pass_no;
-            }
-        }
-        if (p->progress && pass_no > 0) {
-            HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
-            p->progress(++reported, n_passes, p->progress_user);
-        }
+        if (int rc = rt::run_passes(s, p, pol, W, n_out, spo, nullptr, &R, stats, fn); rc != RT_OK)
+            return rc;
         if (rgb8_out) // film on the device (image.h:49-82) over the outputs
             HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_out, 0, 1, n_out, s->d_film_table, s->stream));
         HIP_TRY(hipEventRecord(s->ev1, s->stream));
@@ -153,8 +113,6 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
         if (int rc = rt::fill_stats(s, counters, (uint64_t)n_rays * K, ms, wall0, stats); rc != RT_OK)
             return rc;
         stats->packet_lanes_x100 = pol.lanes_x100;
-        stats->passes = passes;
-        stats->packet_passes = packet_passes;
     }
     return RT_OK;
 }

@@ -1,5 +1,7 @@
-// rt_render.cpp — rt_render / rt_render_views and their rgb8 forms, rt_film_rgb8, and what every wavefront pass shares with the
-// accumulators (rt_accum_host.cpp): views, the check of the pass options, the pass policy (launch_pass) and the statistics.
+// rt_render.cpp — rt_render / rt_render_views and their rgb8 forms, rt_film_rgb8, the pass loop of every call that renders a rectangle of
+// pixels x samples (run_passes: render_image here, rt_render_rays in rt_rays.cpp), and what every wavefront pass shares with the
+// accumulators (rt_accum_host.cpp): the check of the pass options, the pass policy (launch_pass) and the statistics. The cameras of a pass
+// are ONE table of sensor records (rt_sensor.cpp make_sensor): a view of rt_render* is a pinhole record.
 //
 // rt_render  replaces run_raytracer(scene, image) (src/raytracer.h:629-674): the wavefront pipeline over (pixel tile) x (sample range)
 //            passes, or the persistent megakernel (reference-RNG parity mode, RT_FLAG_MEGAKERNEL).
@@ -16,21 +18,6 @@
 // a power-of-two binary search (rt_wavefront.hip)
 static_assert(WF_STRIPES == 64u && (WF_STRIPES & (WF_STRIPES - 1u)) == 0u, "WF_STRIPES must equal the wave size (64)");
 
-// The view record of one camera. gen_ray's tan terms (raytracer.h:531-535) and Camera::fov_y (scene.h:69-71), float overloads: the one
-// place the single render, every view of rt_render_views and an accumulator take them from, so that view v of a batch gets the bits a
-// scene created with its camera gets
-WfView rt::make_view(const rt_camera &cam, uint32_t width, uint32_t height, uint64_t seed) {
-    WfView v{};
-    std::memcpy(v.pos, cam.position, 12);
-    std::memcpy(v.right, cam.right, 12);
-    std::memcpy(v.up, cam.up, 12);
-    std::memcpy(v.fwd, cam.forward, 12);
-    v.tan_x = std::tan(cam.fov_x / 2);
-    const float fov_y = std::atan(std::tan(cam.fov_x / 2) * height / width) * 2;
-    v.tan_y = std::tan(fov_y / 2);
-    v.seed = seed;
-    return v;
-}
 // the camera the megakernel and the probes read from their DevScene argument
 void rt::set_camera(DevScene &D, const float *pos, const float *right, const float *up, const float *fwd) {
     std::memcpy(D.cam_pos, pos, 12);
@@ -164,14 +151,13 @@ static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float 
 }
 
 // One wavefront pass: `W` carries the workspace (wf_bind) and the pass's geometry (first_pixel, pass_pixels, first_sample, pass_samples,
-// n_paths, views, ...); this picks W.sort_mode and W.use_packet, launches, and folds the packet kernel's census back into `pol`, the
+// n_paths, sensors, ...); this picks W.sort_mode and W.use_packet, launches, and folds the packet kernel's census back into `pol`, the
 // policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays*). `acc`: an
 // accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays (rt_kernels.h).
-// `cam_pos`: the pass's primary rays are camera rays of ONE view and this is its position, the three floats wf_primary_ray stores as every
-// ray's origin; null where no such position exists (several views, a caller's rays, a sensor whose rays start on a film or a lens).
-// `sensors`: the primary rays come from this sensor table instead of W.views (rt_sensor.cpp).
+// `cam_pos`: rt::single_origin of the pass's camera table: the three floats sensor_ray stores as every ray's origin, or null where no such
+// position exists (several cameras, a caller's rays, a sensor whose rays start on a film or a lens).
 hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos, const WfSensors *sensors) {
+                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos) {
     // Small passes are bound by launch and host latency, not by memory (a 256 x 256 x 4 render, BASELINE config 1's
     // shape, spent 5.7 ms at 0.6 ms per bounce): RT_SORT_AUTO leaves a pass of fewer than 2^20 paths unsorted, which also spares it
     // the per-bounce queue-size read-back the sort needs: the whole pass is queued without a single host wait.
@@ -199,13 +185,75 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     const rt::WfHostSync hsync = wavefront_host_sync(s);
     unsigned long long census[2] = {0ull, 0ull};
     const hipError_t e = rt::launch_wavefront_pass(s->dev, W, W.stats != nullptr, s->num_cus, first_pass, last_pass, s->stream, time_extends ? &s->ext_events : nullptr, census,
-                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays, sensors);
+                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays);
     if (e == hipSuccess && census[0] != 0ull) {
         pol.lanes_x100 = (uint32_t)(100.0 * (double)census[1] / (double)census[0]);
         if ((double)census[1] < min_lanes * (double)census[0])
             pol.off = true;
     }
     return e;
+}
+
+// The pass loop of a call that renders `n_pixels` local pixels (outputs, for rt_render_rays) x `samples` samples each: (pixel tile) x
+// (sample range) passes under wavefront_max_paths, all stream-ordered. `W` carries the caller's geometry, output buffer and flags; this grows
+// and binds the workspace and sets each pass's range. `table`: the cameras of the call, uploaded here as W.sensors (it outlives the caller's
+// stream sync; its one origin, if any, lets the packets walk camera-relative records); null for a pass of `rays`.
+// Progress (rt_params.progress): one event per pass; the host stays ONE pass ahead of the device (after queueing pass k it waits for pass
+// k - 1 and reports it), so reporting never leaves the GPU idle. `stats` (may be null) receives passes / packet_passes. `fn`: the entry
+// point's name.
+int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint64_t n_pixels, uint32_t samples, const std::vector<WfSensor> *table,
+                   const WfRays *rays, rt_stats *stats, const char *fn) {
+    const uint64_t max_paths = rt::wavefront_max_paths(s, p);
+    const uint64_t tile_pixels = std::min<uint64_t>(n_pixels, max_paths);
+    const uint32_t pass_spp = (uint32_t)std::clamp<uint64_t>(max_paths / tile_pixels, 1, samples);
+    if (int rc = s->ensure_wavefront(tile_pixels * pass_spp, tile_pixels, s->dev.ray_depth); rc != RT_OK)
+        return rc;
+    s->wf_bind(W);
+    const uint32_t n_views = table ? (uint32_t)table->size() : 1u;
+    const float *cam_pos = table ? rt::single_origin(table->data(), n_views) : nullptr;
+    if (table) {
+        if (int rc = s->ensure_sensors(n_views); rc != RT_OK)
+            return rc;
+        HIP_TRY(hipMemcpyAsync(s->d_sensors, table->data(), n_views * sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
+        W.sensors = s->d_sensors;
+    }
+    const uint32_t n_passes = (uint32_t)((n_pixels + tile_pixels - 1) / tile_pixels) * ((samples + pass_spp - 1) / pass_spp);
+    if (p->progress)
+        while (s->pass_events.size() < n_passes) {
+            hipEvent_t ev = nullptr;
+            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+                return rt::fail(RT_ERR_HIP, std::string(fn) + ": progress event");
+            s->pass_events.push_back(ev);
+        }
+    uint32_t pass_no = 0, reported = 0, packet_passes = 0;
+    for (uint64_t p0 = 0; p0 < n_pixels; p0 += tile_pixels) {
+        W.first_pixel = (uint32_t)p0;
+        W.pass_pixels = (uint32_t)std::min<uint64_t>(tile_pixels, n_pixels - p0);
+        for (uint32_t s0 = 0; s0 < samples; s0 += pass_spp) {
+            W.first_sample = s0;
+            W.pass_samples = std::min<uint32_t>(pass_spp, samples - s0);
+            W.n_paths = W.pass_pixels * W.pass_samples;
+            HIP_TRY(rt::launch_pass(s, p, pol, W, n_views, s0 == 0, s0 + W.pass_samples >= samples, stats != nullptr, nullptr, nullptr, rays, cam_pos));
+            packet_passes += W.use_packet;
+            if (p->progress) {
+                HIP_TRY(hipEventRecord(s->pass_events[pass_no], s->stream));
+                if (pass_no > 0) {
+                    HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
+                    p->progress(++reported, n_passes, p->progress_user);
+                }
+            }
+            ++pass_no;
+        }
+    }
+    if (p->progress && pass_no > 0) { // the last pass (and, for a single-pass call, the only one)
+        HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
+        p->progress(++reported, n_passes, p->progress_user);
+    }
+    if (stats) {
+        stats->passes = pass_no;
+        stats->packet_passes = packet_passes;
+    }
+    return RT_OK;
 }
 
 // rt_stats of a call that has finished on the scene's stream: the device counters (`counters`; else `samples` is what the call knows it
@@ -240,23 +288,14 @@ int rt::fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms
     return RT_OK;
 }
 
-// rt_render / rt_render_views (fb_rgb: linear float3) and their rgb8 forms (rgb8_out: the tone-mapped image, film on the device).
-// views == nullptr: rt_render, the one view of the scene's own camera with rt_params.seed. Otherwise the n_views views render as ONE
-// view-major virtual image of n_views * height rows: the wavefront pipeline plans its passes over it and reads each path's camera from
-// the view table; the megakernel runs view by view.
-// `sensors`: rt_render_sensors*: the sensor table takes the view table's place (views is null; n_views counts the sensors), the passes are
-// wavefront passes (rt_sensor.cpp has refused everything else) and the packet policy is the scene's own for sensors of that kind.
-int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, const std::vector<WfSensor> *sensors, uint32_t n_views, float *fb_rgb, uint8_t *rgb8_out,
-                     rt_stats *stats) {
-    if (!s || !p || (!fb_rgb && !rgb8_out))
+// The image of a single-GPU scene through the cameras of `table` (fb_rgb: linear float3; rgb8_out: the tone-mapped image, film on the
+// device): rt_render* and rt_render_views* (pinhole records, below), rt_render_sensors* (rt_sensor.cpp). The cameras render as ONE view-major
+// virtual image of table.size() * height rows: the wavefront pipeline plans its passes over it (run_passes) and reads each path's camera
+// from the table; the megakernel (pinhole records only: rt_sensor.cpp refuses it) runs view by view. `pol`: the packet policy of the caller.
+int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor> &table, PacketPolicy &pol, float *fb_rgb, uint8_t *rgb8_out, rt_stats *stats) {
+    if (!s || !p || (!fb_rgb && !rgb8_out) || table.empty())
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render: null argument");
-    if (views)
-        if (int rc = rt::check_views(p, views, n_views); rc != RT_OK)
-            return rc;
-    if (s->group)
-        return rt::group_render(s->group, p, views, n_views, fb_rgb, rgb8_out, stats);
-    if (!views && !sensors)
-        n_views = 1;
+    const uint32_t n_views = (uint32_t)table.size();
     if (p->width == 0 || p->height == 0 || (uint64_t)p->width * p->height >= 0x7FFFFFFFull)
         return rt::fail(RT_ERR_INVALID_ARG, "Illegal image size" + std::to_string(p->width) + "x" + std::to_string(p->height)); // image.h:26
     if (p->rng_mode != RT_RNG_DEVICE && p->rng_mode != RT_RNG_REFERENCE)
@@ -301,12 +340,8 @@ int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, cons
         local_pixels += last - first;
     }
     L.n_items = (uint32_t)items;
-    // the view table: camera, tangents and seed per view
-    std::vector<WfView> vt(n_views);
-    for (uint32_t v = 0; v < n_views && !sensors; ++v)
-        vt[v] = views ? rt::make_view(views[v].camera, p->width, p->height, views[v].seed) : rt::make_view(s->cam, p->width, p->height, p->seed);
-    L.tan_x = vt[0].tan_x;
-    L.tan_y = vt[0].tan_y;
+    L.tan_x = table[0].tan_x;
+    L.tan_y = table[0].tan_y;
 
     const bool device_fb = (p->flags & RT_FLAG_DEVICE_FB) != 0;
     const size_t fb_floats = (size_t)n_pix * 3;
@@ -340,27 +375,11 @@ int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, cons
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_render: a scene with a float environment (rt_set_environment) renders through the wavefront pipeline only (the "
                                             "megakernel and the reference-RNG parity mode are the reference's Scene::bg_at: rt_set_environment(scene, NULL) first)");
     s->ext_events.reset();
-    uint32_t passes = 0, packet_passes = 0; // rt_stats.passes / packet_passes
-    rt::PacketPolicy &pol = !sensors ? s->pkt : s->pkt_sensor[n_views == 1 ? (*sensors)[0].kind : 5u];
+    uint32_t launched = 0; // megakernel launches
     auto queue_render = [&]() -> int {
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
     if (L.n_items > 0 && wavefront) {
         // ---- production path: wavefront pipeline over (pixel tile) x (sample range) passes, all stream-ordered
-        const uint64_t max_paths = rt::wavefront_max_paths(s, p);
-        const uint64_t tile_pixels = std::min<uint64_t>(local_pixels, max_paths);
-        const uint32_t pass_spp = (uint32_t)std::clamp<uint64_t>(max_paths / tile_pixels, 1, p->samples);
-        int rc = s->ensure_wavefront(tile_pixels * pass_spp, tile_pixels, s->dev.ray_depth);
-        if (rc == RT_OK)
-            rc = sensors ? s->ensure_sensors(n_views) : s->ensure_views(n_views);
-        if (rc != RT_OK)
-            return rc;
-        if (sensors) // the caller's table outlives the stream sync below, and so does `vt`
-            HIP_TRY(hipMemcpyAsync(s->d_sensors, sensors->data(), n_views * sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
-        else
-            HIP_TRY(hipMemcpyAsync(s->d_views, vt.data(), n_views * sizeof(WfView), hipMemcpyHostToDevice, s->stream));
-        const WfSensors sensor_table{s->d_sensors};
-        // one origin for every ray of the pass: one view, or one sensor of a kind that keeps the camera position as the origin
-        const float *cam_pos = n_views != 1 ? nullptr : !sensors ? vt[0].pos : rt::sensor_single_origin((*sensors)[0].kind) ? (*sensors)[0].pos : nullptr;
         WfLaunch W{};
         W.width = p->width;
         W.height = p->height;
@@ -369,51 +388,13 @@ int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, cons
         W.shard_count = L.shard_count;
         W.shard_block = L.shard_block;
         W.ray_depth = s->dev.ray_depth;
-        W.views = sensors ? nullptr : s->d_views;
         W.view_pixels = view_pixels;
-        s->wf_bind(W);
         W.fb = d_fb;
         // production traversal: global-best pruning (rt_abi.h RT_FLAG_GLOBAL_BEST)
         W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
         W.stats = L.stats;
-        // progress (rt_params.progress): one event per pass; the host stays ONE pass ahead of the device (after queueing pass k it
-        // waits for pass k - 1 and reports it), so reporting never leaves the GPU idle
-        uint32_t n_passes = 0, reported = 0;
-        for (uint64_t p0 = 0; p0 < local_pixels; p0 += tile_pixels)
-            n_passes += (p->samples + pass_spp - 1) / pass_spp;
-        if (p->progress)
-            while (s->pass_events.size() < n_passes) {
-                hipEvent_t ev = nullptr;
-                if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-                    return rt::fail(RT_ERR_HIP, "rt_render: progress event");
-                s->pass_events.push_back(ev);
-            }
-        uint32_t pass_no = 0;
-        for (uint64_t p0 = 0; p0 < local_pixels; p0 += tile_pixels) {
-            W.first_pixel = (uint32_t)p0;
-            W.pass_pixels = (uint32_t)std::min<uint64_t>(tile_pixels, local_pixels - p0);
-            for (uint32_t s0 = 0; s0 < p->samples; s0 += pass_spp) {
-                W.first_sample = s0;
-                W.pass_samples = std::min<uint32_t>(pass_spp, p->samples - s0);
-                W.n_paths = W.pass_pixels * W.pass_samples;
-                HIP_TRY(rt::launch_pass(s, p, pol, W, n_views, s0 == 0, s0 + W.pass_samples >= p->samples, stats != nullptr, nullptr, nullptr, nullptr, cam_pos,
-                                        sensors ? &sensor_table : nullptr));
-                passes += 1;
-                packet_passes += W.use_packet;
-                if (p->progress) {
-                    HIP_TRY(hipEventRecord(s->pass_events[pass_no], s->stream));
-                    if (pass_no > 0) {
-                        HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
-                        p->progress(++reported, n_passes, p->progress_user);
-                    }
-                }
-                ++pass_no;
-            }
-        }
-        if (p->progress && pass_no > 0) { // the last pass (and, for a single-pass render, the only one)
-            HIP_TRY(hipEventSynchronize(s->pass_events[pass_no - 1]));
-            p->progress(++reported, n_passes, p->progress_user);
-        }
+        if (int rc = rt::run_passes(s, p, pol, W, local_pixels, p->samples, &table, nullptr, stats, "rt_render"); rc != RT_OK)
+            return rc;
     } else if (L.n_items > 0) {
         // ---- persistent megakernel: reference-RNG parity mode, or RT_FLAG_MEGAKERNEL cross-check (one launch = one pass), one launch per
         // view. The kernel reads the camera from its DevScene argument, passed by value: each launch gets a copy with the view's camera.
@@ -425,14 +406,13 @@ int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, cons
             const uint64_t full = x / blk, r = x % blk;
             return (full / L.shard_count) * blk + ((full % L.shard_count) > L.shard_index ? blk : 0) + ((full % L.shard_count) == L.shard_index ? r : 0);
         };
-        uint32_t launched = 0;
         for (uint32_t v = 0; v < n_views; ++v) {
             RenderLaunch Lv = L;
             DevScene Sv = s->dev;
-            rt::set_camera(Sv, vt[v].pos, vt[v].right, vt[v].up, vt[v].fwd);
-            Lv.tan_x = vt[v].tan_x;
-            Lv.tan_y = vt[v].tan_y;
-            Lv.seed = vt[v].seed;
+            rt::set_camera(Sv, table[v].pos, table[v].right, table[v].up, table[v].fwd);
+            Lv.tan_x = table[v].tan_x;
+            Lv.tan_y = table[v].tan_y;
+            Lv.seed = table[v].seed;
             Lv.fb = d_fb + (size_t)v * view_pixels * 3;
             if (n_views > 1 && p->rng_mode == RT_RNG_REFERENCE) {
                 const uint32_t spans = (view_pixels + RT_SPAN - 1) / RT_SPAN;
@@ -453,7 +433,6 @@ int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, cons
             HIP_TRY(rt::launch_render(Sv, Lv, counters, vblocks, s->stream));
             ++launched;
         }
-        passes = launched;
         if (p->progress) {
             HIP_TRY(hipStreamSynchronize(s->stream));
             p->progress(launched, launched, p->progress_user);
@@ -485,39 +464,53 @@ int rt::render_image(rt_scene *s, const rt_params *p, const rt_view *views, cons
     if (stats) {
         if (int rc = rt::fill_stats(s, counters, local_pixels * p->samples, ms, wall0, stats); rc != RT_OK)
             return rc;
-        if (!wavefront) { // the megakernel: its launches are the dominant ones
-            stats->dominant_launches = passes;
+        if (!wavefront) { // the megakernel: its launches are the passes and the dominant ones
+            stats->passes = stats->dominant_launches = launched;
             stats->dominant_ms = ms;
         }
         stats->packet_lanes_x100 = wavefront ? pol.lanes_x100 : 0u; // the packet kernel's census (lanes served per trip x 100; 0 = it did not run)
-        stats->passes = passes;
-        stats->packet_passes = packet_passes;
     }
     return RT_OK;
+}
+
+// rt_render* (`views` null: the one view of the scene's own camera with rt_params.seed) and rt_render_views*: the checks that need no
+// device, the hand-off of a multi-GPU scene, and the views as pinhole records under the scene's own packet policy
+static int render_views(rt_scene *s, const rt_params *p, const rt_view *views, uint32_t n_views, float *fb_rgb, uint8_t *rgb8_out, rt_stats *stats) {
+    if (!s || !p)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_render: null argument");
+    if (views)
+        if (int rc = rt::check_views(p, views, n_views); rc != RT_OK)
+            return rc;
+    if (s->group)
+        return rt::group_render(s->group, p, views, n_views, fb_rgb, rgb8_out, stats);
+    std::vector<WfSensor> table(views ? n_views : 1u);
+    for (uint32_t v = 0; v < table.size(); ++v)
+        table[v] = views ? rt::make_sensor(views[v].camera, views[v].seed, p->width, p->height) : rt::make_sensor(s->cam, p->seed, p->width, p->height);
+    return rt::render_image(s, p, table, s->pkt, fb_rgb, rgb8_out, stats);
 }
 
 extern "C" int rt_render(rt_scene *s, const rt_params *p, float *fb_rgb, rt_stats *stats) {
     if (!fb_rgb)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render: null argument");
-    return rt::render_image(s, p, nullptr, nullptr, 0, fb_rgb, nullptr, stats);
+    return render_views(s, p, nullptr, 0, fb_rgb, nullptr, stats);
 }
 
 extern "C" int rt_render_rgb8(rt_scene *s, const rt_params *p, uint8_t *rgb8, rt_stats *stats) {
     if (!rgb8)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render_rgb8: null argument");
-    return rt::render_image(s, p, nullptr, nullptr, 0, nullptr, rgb8, stats);
+    return render_views(s, p, nullptr, 0, nullptr, rgb8, stats);
 }
 
 extern "C" int rt_render_views(rt_scene *s, const rt_params *p, const rt_view *views, uint32_t n_views, float *fb_rgb, rt_stats *stats) {
     if (!fb_rgb || !views || n_views == 0)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render_views: null argument or no view");
-    return rt::render_image(s, p, views, nullptr, n_views, fb_rgb, nullptr, stats);
+    return render_views(s, p, views, n_views, fb_rgb, nullptr, stats);
 }
 
 extern "C" int rt_render_views_rgb8(rt_scene *s, const rt_params *p, const rt_view *views, uint32_t n_views, uint8_t *rgb8, rt_stats *stats) {
     if (!rgb8 || !views || n_views == 0)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_render_views_rgb8: null argument or no view");
-    return rt::render_image(s, p, views, nullptr, n_views, nullptr, rgb8, stats);
+    return render_views(s, p, views, n_views, nullptr, rgb8, stats);
 }
 
 extern "C" int rt_film_rgb8(rt_scene *s, const float *rgb, size_t n_pixels, uint8_t *out_rgb8) {

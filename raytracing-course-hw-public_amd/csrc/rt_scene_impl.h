@@ -129,8 +129,6 @@ struct rt_scene {
     size_t fb_capacity = 0; // floats
     uint8_t *d_rgb8 = nullptr; // device film output (rt_render_rgb8 with a host destination, rt_film_rgb8)
     size_t rgb8_capacity = 0;
-    WfView *d_views = nullptr; // the view table of the wavefront pipeline (one record per view of the render), grown on demand
-    uint32_t views_capacity = 0;
     rt::FilmTable *d_film_table = nullptr;
 
     int ensure_fb(size_t fb_floats) {
@@ -170,20 +168,8 @@ struct rt_scene {
         }
         return RT_OK;
     }
-    int ensure_views(uint32_t n) {
-        if (views_capacity >= n)
-            return RT_OK;
-        if (d_views)
-            (void)hipFree(d_views);
-        d_views = nullptr;
-        views_capacity = 0;
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, (size_t)n * sizeof(WfView)));
-        d_views = static_cast<WfView *>(q);
-        views_capacity = n;
-        return RT_OK;
-    }
-    // the sensor table of rt_render_sensors* / the one record of rt_sensor_rays (WfSensors::table), grown on demand
+    // the camera table of a render's wavefront passes (WfLaunch::sensors: one record per view or sensor) / the one record of rt_sensor_rays,
+    // grown on demand
     WfSensor *d_sensors = nullptr;
     uint32_t sensors_capacity = 0;
     int ensure_sensors(uint32_t n) {
@@ -358,8 +344,6 @@ struct rt_scene {
             (void)hipFree(d_fb);
         if (d_rgb8)
             (void)hipFree(d_rgb8);
-        if (d_views)
-            (void)hipFree(d_views);
         if (d_rays)
             (void)hipFree(d_rays);
         if (d_sensors)
@@ -387,22 +371,21 @@ int upload_geometry(rt_scene *s, const rt_scene_desc *d, const PreparedScene &PS
                     const DeviceArrays *arrays = nullptr);
 void install_geometry(rt_scene *s, GeometryOnDevice &g);
 uint32_t light_lds_inner(const FlatBvh &f); // DevBvh::lds_inner of a light tree
-// rt_render.cpp: views, the check of the pass options, the wavefront pass policy and the statistics of a finished call
-WfView make_view(const rt_camera &cam, uint32_t width, uint32_t height, uint64_t seed);
+// rt_render.cpp: the check of the pass options, the wavefront pass policy, the pass loop and the statistics of a finished call
 void set_camera(DevScene &D, const float *pos, const float *right, const float *up, const float *fwd);
 int check_pass_params(const rt_params *p, const char *fn);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
 hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr,
-                       const WfSensors *sensors = nullptr);
-// rt_render / rt_render_views (`views`, may be null) / rt_render_sensors (`sensors`, may be null: the checked records of rt_sensor.cpp; then
-// `views` is null and n_views counts the sensors): the one pass loop behind every entry point that renders an image
-int render_image(rt_scene *s, const rt_params *p, const rt_view *views, const std::vector<WfSensor> *sensors, uint32_t n_views, float *fb_rgb, uint8_t *rgb8_out,
-                 rt_stats *stats);
-// rt_sensor.cpp: the argument checks of one rt_sensor, its device record, and which kinds share one ray origin
+                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr);
+int run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint64_t n_pixels, uint32_t samples, const std::vector<WfSensor> *table,
+               const WfRays *rays, rt_stats *stats, const char *fn);
+// the image of a single-GPU scene through the cameras of `table` (views as pinhole records, or the checked records of rt_sensor.cpp)
+int render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor> &table, PacketPolicy &pol, float *fb_rgb, uint8_t *rgb8_out, rt_stats *stats);
+// rt_sensor.cpp: the argument checks of one rt_sensor, the device record of a sensor or of a view {camera, seed}, the one ray origin of a table
 int check_sensor(const rt_sensor &sn, uint32_t width, uint32_t height, const char *fn);
 WfSensor make_sensor(const rt_sensor &sn, uint32_t width, uint32_t height);
-bool sensor_single_origin(uint32_t kind);
+WfSensor make_sensor(const rt_camera &cam, uint64_t seed, uint32_t width, uint32_t height);
+const float *single_origin(const WfSensor *table, uint32_t n);
 int fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats);
 
 // Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are

@@ -1,6 +1,7 @@
-// rt_sensor.cpp — the sensor models of rt_abi.h rt_sensor on the host: the argument checks, the one place that fills a sensor record
-// (make_sensor, next to rt::make_view whose fields it starts with), rt_render_sensors* (rt_render's own pass loop, rt_render.cpp
-// render_image, with the sensor table in the view table's place) and rt_sensor_rays. rt_accum_create_sensor is in rt_accum_host.cpp.
+// rt_sensor.cpp — the cameras of the wavefront pipeline on the host (rt_abi.h rt_sensor; a view of rt_render* and the camera of
+// rt_accum_create are pinhole records): the argument checks, the one place that fills a sensor record (make_sensor), rt_render_sensors*
+// (rt_render.cpp render_image over its table, under the scene's policy for sensors of that kind) and rt_sensor_rays.
+// rt_accum_create_sensor is in rt_accum_host.cpp.
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -29,23 +30,43 @@ int rt::check_sensor(const rt_sensor &sn, uint32_t width, uint32_t height, const
     return RT_OK;
 }
 
-// The sensor record of one rt_sensor at a width x height image: WfView's fields from rt::make_view, the kind and its hoisted terms.
+// The sensor record of one rt_sensor at a width x height image: the camera, gen_ray's tan terms (raytracer.h:531-535) and Camera::fov_y
+// (scene.h:69-71) as float overloads, the seed, the kind and its hoisted terms. The one place every render, every view of rt_render_views
+// and every accumulator take them from, so that view v of a batch gets the bits a scene created with its camera gets.
 WfSensor rt::make_sensor(const rt_sensor &sn, uint32_t width, uint32_t height) {
-    const WfView v = rt::make_view(sn.camera, width, height, sn.seed);
+    const rt_camera &cam = sn.camera;
     WfSensor r{};
-    static_assert(offsetof(WfSensor, kind) == sizeof(WfView), "WfSensor starts with WfView's fields");
-    std::memcpy(&r, &v, sizeof(v));
+    std::memcpy(r.pos, cam.position, 12);
+    std::memcpy(r.right, cam.right, 12);
+    std::memcpy(r.up, cam.up, 12);
+    std::memcpy(r.fwd, cam.forward, 12);
+    r.tan_x = std::tan(cam.fov_x / 2);
+    const float fov_y = std::atan(std::tan(cam.fov_x / 2) * height / width) * 2;
+    r.tan_y = std::tan(fov_y / 2);
+    r.seed = sn.seed;
     r.kind = sn.kind;
-    r.half_fov = sn.camera.fov_x / 2;
+    r.half_fov = cam.fov_x / 2;
     r.half_width = sn.half_width;
     r.half_h = sn.half_width * (float)height / (float)width;
     r.lens_radius = sn.lens_radius;
     r.focus_distance = sn.focus_distance;
     return r;
 }
+// the pinhole record of a view {camera, seed}
+WfSensor rt::make_sensor(const rt_camera &cam, uint64_t seed, uint32_t width, uint32_t height) {
+    rt_sensor sn{};
+    sn.camera = cam;
+    sn.kind = RT_SENSOR_PINHOLE;
+    sn.seed = seed;
+    return rt::make_sensor(sn, width, height);
+}
 
-// the kinds whose rays all start at the camera position, bit for bit: their packets may walk the camera-relative records
-bool rt::sensor_single_origin(uint32_t kind) { return kind == RT_SENSOR_PINHOLE || kind == RT_SENSOR_EQUIRECT || kind == RT_SENSOR_FISHEYE; }
+// The one origin of every ray of a pass over `table`, where it has one: a single camera of a kind whose rays all start at the camera
+// position, bit for bit. Their packets may walk the camera-relative records (rt_render.cpp launch_pass). Null otherwise.
+const float *rt::single_origin(const WfSensor *table, uint32_t n) {
+    const bool at_pos = n == 1 && (table[0].kind == RT_SENSOR_PINHOLE || table[0].kind == RT_SENSOR_EQUIRECT || table[0].kind == RT_SENSOR_FISHEYE);
+    return at_pos ? table[0].pos : nullptr;
+}
 
 static int render_sensors_impl(rt_scene *s, const rt_params *p, const rt_sensor *sensors, uint32_t n_sensors, float *fb_rgb, uint8_t *rgb8, rt_stats *stats, const char *fn) {
     const std::string name(fn);
@@ -69,7 +90,8 @@ static int render_sensors_impl(rt_scene *s, const rt_params *p, const rt_sensor 
     std::vector<WfSensor> table(n_sensors);
     for (uint32_t v = 0; v < n_sensors; ++v)
         table[v] = rt::make_sensor(sensors[v], p->width, p->height);
-    return rt::render_image(s, p, nullptr, &table, n_sensors, fb_rgb, rgb8, stats); // rng_mode, samples and the pass options: rt_render's checks
+    // rng_mode, samples and the pass options: rt_render's checks. The policy: one per kind for a single sensor, [5] for several
+    return rt::render_image(s, p, table, s->pkt_sensor[n_sensors == 1 ? table[0].kind : 5u], fb_rgb, rgb8, stats);
 }
 
 extern "C" int rt_render_sensors(rt_scene *s, const rt_params *p, const rt_sensor *sensors, uint32_t n_sensors, float *fb_rgb, rt_stats *stats) {

@@ -73,30 +73,16 @@ DEV uint32_t wf_global_pixel(const WfLaunch &L, uint32_t local_pixel) {
 
 // ------------------------------------------------------------------------------------------------ generate
 // The first record of path i, in queue slot i: the ray (o, d) with `rng` as gen_ray left it (behind its two jitter draws), full budget, no
-// pending frames. The one definition of a path's first record: a camera's rays (wf_primary_ray) and a caller's (wf_generate_rays) both end here.
+// pending frames. The one definition of a path's first record: a camera's rays (sensor_ray) and a caller's (wf_generate_rays) both end here.
 // ENVD (every first stage): the scene's mix_dist has the environment as a component (ENV_FLOAT_DIST), which next_shade_class must know.
 template <bool ENVD> DEV void wf_store_first(const DevScene &S, const WfLaunch &L, uint32_t i, V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) {
     wf_store_path(L.paths_in + i, wf_pack(o, d, i, next_shade_class<ENVD>(rng, S.lights.n_tris != 0), L.ray_depth, 0u, rng.g));
 }
 
-// gen_ray (raytracer.h:527-538) for sample s of pixel pix of view v: camera, jitter and seeding, written as the primary-ray record of queue
-// slot (= path) i. The one definition of a camera path's first ray: wf_generate and the accumulators' wf_generate_list both call it, so sample
+// A camera pass: path i is sample first_sample + ds of local pixel first_pixel + lp; its ray is sensor_ray (rt_dev_sensor.h) of the camera
+// that holds the pixel in the virtual (view-major) image, L.sensors[vpix / view_pixels]. A view of rt_render* is a pinhole record, whose
+// branch of sensor_ray is gen_ray (raytracer.h:527-538) itself. The accumulators' wf_generate_list draws from the same function, so sample
 // s of pixel p is the same ray whichever of them draws it.
-template <bool ENVD> DEV void wf_primary_ray(const DevScene &S, const WfLaunch &L, uint32_t i, uint32_t v, uint32_t pix, uint32_t s) {
-    // the view is wave-uniform except where a wave straddles two views: then every lane reads its own record
-    const uint32_t v0 = __builtin_amdgcn_readfirstlane(v);
-    WfView view;
-    if (__ballot(v != v0) == 0ull)
-        view = L.views[v0];
-    else
-        view = L.views[v];
-    const V3 cam_pos = ld3(view.pos), cam_right = ld3(view.right), cam_up = ld3(view.up), cam_fwd = ld3(view.fwd);
-    Rng<RT_RNG_DEVICE> rng;
-    rt_xoshiro_seed(&rng.g, view.seed, pix, s);
-    const V3 rd = gen_ray_dir(rng, pix, L.width, L.height, view.tan_x, view.tan_y, cam_right, cam_up, cam_fwd);
-    wf_store_first<ENVD>(S, L, i, cam_pos, rd, rng);
-}
-
 template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
     LaneStats<STATS> st;
     if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -106,9 +92,8 @@ template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_gener
         const uint32_t ds = i - lp * L.pass_samples;
         const uint32_t vpix = wf_global_pixel(L, L.first_pixel + lp); // pixel of the virtual (view-major) image
         const uint32_t v = vpix / L.view_pixels;
-        const uint32_t pix = vpix - v * L.view_pixels; // pixel within its view
-        const uint32_t s = L.first_sample + ds;
-        wf_primary_ray<ENVD>(S, L, i, v, pix, s);
+        sensor_ray_of(L.sensors, v, L.width, L.height, vpix - v * L.view_pixels, L.first_sample + ds,
+                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
         st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
     }
     st.flush(L.stats);
@@ -138,7 +123,8 @@ template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_gener
                 hi = mid - 1u;
         }
         const uint32_t e = A.first_entry + lo;
-        wf_primary_ray<ENVD>(S, L, i, 0u, A.list_pix[e], A.list_base[e] + (g - off[lo])); // an accumulator has one view
+        sensor_ray_of(L.sensors, 0u, L.width, L.height, A.list_pix[e], A.list_base[e] + (g - off[lo]), // an accumulator has one camera
+                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
         st.cast();
     }
     st.flush(L.stats);
@@ -170,61 +156,15 @@ template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_gener
     st.flush(L.stats);
 }
 
-// The sensor siblings of wf_generate and wf_generate_list (rt_render_sensors, rt_accum_create_sensor): the same path numbering, the ray from
-// sensor_ray (rt_dev_sensor.h) of the sensor table instead of wf_primary_ray of the view table. L.views is not read.
-template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_sensor(const DevScene S, const WfLaunch L, const WfSensors T) {
-    LaneStats<STATS> st;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        L.counters[WF_CNT_IN] = L.n_paths;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
-        const uint32_t lp = i / L.pass_samples;
-        const uint32_t ds = i - lp * L.pass_samples;
-        const uint32_t vpix = wf_global_pixel(L, L.first_pixel + lp);
-        const uint32_t v = vpix / L.view_pixels;
-        sensor_ray_of(T, v, L.width, L.height, vpix - v * L.view_pixels, L.first_sample + ds,
-                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
-        st.cast();
-    }
-    st.flush(L.stats);
-}
-
-template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_list_sensor(const DevScene S, const WfLaunch L, const WfAccum A, const WfSensors T) {
-    LaneStats<STATS> st;
-    const uint32_t *off = A.list_off + A.first_entry;
-    const uint32_t base = off[0], n_exact = off[A.n_entries] - base;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        L.counters[WF_CNT_IN] = n_exact;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
-        if (i >= n_exact) {
-            L.sample_out[i] = RtF4{0.f, 0.f, 0.f, __uint_as_float(0u)};
-            continue;
-        }
-        const uint32_t g = base + i;
-        uint32_t lo = 0, hi = A.n_entries - 1; // the last e with off[e] <= g, as wf_generate_list
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1u) >> 1;
-            if (off[mid] <= g)
-                lo = mid;
-            else
-                hi = mid - 1u;
-        }
-        const uint32_t e = A.first_entry + lo;
-        sensor_ray_of(T, 0u, L.width, L.height, A.list_pix[e], A.list_base[e] + (g - off[lo]), // an accumulator has one sensor
-                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
-        st.cast();
-    }
-    st.flush(L.stats);
-}
-
-// rt_sensor_rays: record i of the output is sample first_sample + i % samples of pixel first_pixel + i / samples of the one sensor T.table[0],
+// rt_sensor_rays: record i of the output is sample first_sample + i % samples of pixel first_pixel + i / samples of the one sensor `sensor[0]`,
 // as an rt_ray {o, d, stream = pix, first_sample = s}, stored as two 16-byte pieces per lane (consecutive lanes, consecutive records). The
 // RNG state is not kept: wf_generate_rays reseeds from (stream, first_sample) and repeats the two draws.
-__global__ __launch_bounds__(256) void wf_sensor_rays(const WfSensors T, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples,
+__global__ __launch_bounds__(256) void wf_sensor_rays(const WfSensor *sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples,
                                                       uint32_t n, uint4 *out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t lp = i / samples;
         const uint32_t pix = first_pixel + lp, s = first_sample + (i - lp * samples);
-        sensor_ray_of(T, 0u, width, height, pix, s, [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &) {
+        sensor_ray_of(sensor, 0u, width, height, pix, s, [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &) {
             out[2ull * i] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
             out[2ull * i + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), pix, s);
         });
@@ -913,7 +853,7 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc,
-                                 const WfFeat *feat, const WfRays *rays, const WfSensors *sensors) {
+                                 const WfFeat *feat, const WfRays *rays) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
@@ -927,10 +867,6 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
     if (packet_census_out)
         packet_census_out[0] = packet_census_out[1] = 0ull;
     e = with_bools([&](auto ST, auto ED) {
-        if (sensors && acc) // a sensor's accumulator pass, a sensor render: the sensor table takes the view table's place
-            return RT_LAUNCH_CHECKED((wf_generate_list_sensor<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc, *sensors);
-        if (sensors)
-            return RT_LAUNCH_CHECKED((wf_generate_sensor<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *sensors);
         if (acc) // an accumulator pass: the first stage follows the round's list (wf_generate_list)
             return RT_LAUNCH_CHECKED((wf_generate_list<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
         if (rays) // a pass of rt_render_rays: the caller's rays and streams (wf_generate_rays)
@@ -1062,7 +998,7 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
 hipError_t launch_sensor_rays(const WfSensor *d_sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples, uint32_t n,
                               void *d_rays_out, int num_cus, hipStream_t stream) {
     const uint32_t blocks = std::min<uint32_t>((n + 255u) / 256u, (uint32_t)num_cus * 16u);
-    return RT_LAUNCH_CHECKED(wf_sensor_rays, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, WfSensors{d_sensor}, width, height, first_pixel, first_sample, samples, n,
+    return RT_LAUNCH_CHECKED(wf_sensor_rays, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, d_sensor, width, height, first_pixel, first_sample, samples, n,
                              static_cast<uint4 *>(d_rays_out));
 }
 

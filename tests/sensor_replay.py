@@ -4,7 +4,7 @@ evaluation (tests/test_sensor_replay.py).
 
 Every array is float32 and every scalar operand an np.float32, so each statement rounds once, as the device's statement does
 (-ffp-contract=off). The random draws come from oracle.xoshiro_sequence, sines and cosines from oracle.sincos (the restatement of
-rt_devspec.h the device evaluates), the two tangents from the host libm's tanf / atanf through rt::make_view's expression."""
+rt_devspec.h the device evaluates), the two tangents from the host libm's tanf / atanf through rt::make_sensor's expression."""
 import ctypes
 import importlib
 
@@ -27,7 +27,7 @@ def ray_dtype():
 
 
 def tangents(fov_x, W, H):
-    """rt::make_view: tan_x = tan(fov_x / 2); fov_y = atan(tan(fov_x / 2) * H / W) * 2; tan_y = tan(fov_y / 2), float overloads."""
+    """rt::make_sensor: tan_x = tan(fov_x / 2); fov_y = atan(tan(fov_x / 2) * H / W) * 2; tan_y = tan(fov_y / 2), float overloads."""
     half = f32(f32(fov_x) / f32(2))
     tan_x = f32(_libm.tanf(half))
     t = f32(tan_x * f32(H))

@@ -266,6 +266,33 @@ def test_accumulator_features_and_denoise(gpu, oracle, scenes, devs, kind):
     acc.close()
 
 
+@pytest.mark.parametrize("features", [False, True])
+def test_camera_and_pinhole_sensor_accumulators_are_one_path(gpu, scenes, devs, features):
+    """An accumulator made of {camera, seed} and one made of Sensor.pinhole(camera, seed) hold the same bits after the same calls: a uniform
+    render, an adaptive render whose threshold (1e-6, far below any two-sample error of a lit pixel) keeps pixels active through a second
+    round, and one more uniform render."""
+    dev = devs["room_textured"]
+    cam = scenes["room_textured"].camera
+    accs = [dev.accumulator(W, H, camera=cam, seed=SEED, features=features), dev.accumulator(W, H, sensor=gpu.Sensor.pinhole(cam, seed=SEED), features=features)]
+    rounds = []
+    for acc in accs:
+        acc.render(SPP)
+        rounds.append(acc.render_adaptive(1e-6, min_samples=SPP + 1, max_samples=SPP + 5, step=2)["rounds"])
+        acc.render(3)
+    assert rounds[0] == rounds[1] and rounds[0] >= 2, rounds
+    a, b = accs[0].read(), accs[1].read()
+    assert a["samples"].min() >= SPP + 4 and a["samples"].max() <= SPP + 8
+    for k in ("sum", "even_sum", "samples", "error"):
+        assert np.array_equal(_bits(a[k]), _bits(b[k])), k
+    assert np.array_equal(_bits(accs[0].image()), _bits(accs[1].image()))
+    if features:
+        fa, fb = accs[0].read_features(), accs[1].read_features()
+        for k in ("albedo_sum", "normal_sum", "depth_sum", "hits"):
+            assert np.array_equal(_bits(fa[k]), _bits(fb[k])), k
+    for acc in accs:
+        acc.close()
+
+
 # ------------------------------------------------------------------------------------------------ 7: rgb8 and device output
 def test_rgb8_and_device_framebuffer(gpu, scenes, devs):
     import torch
