@@ -15,16 +15,14 @@ struct rt_accum {
     WfSensor sensor{};            // its camera: rt_accum_create_sensor's, or the pinhole record of {camera, seed} (host copy of d_sensor)
     WfSensor *d_sensor = nullptr; // WfLaunch::sensors of its passes: the one record
     rt::AccumRound R{};
-    std::vector<void *> owned;
+    rt::DevArena owned{16};
     rt::PacketPolicy pkt; // of its own passes, kept apart from rt_render's
     bool features = false; // RT_ACCUM_FEATURES: F holds the four first-hit sums (F.rec is the scene's, bound per fill)
     WfFeat F{};
     rt::DenoiseBufs D{};   // rt_accum_denoise's workspace (64 B per pixel), allocated by its first call
     ~rt_accum() {
         (void)hipSetDevice(scene->device);
-        (void)hipStreamSynchronize(scene->stream);
-        for (void *p : owned)
-            (void)hipFree(p);
+        (void)hipStreamSynchronize(scene->stream); // `owned` frees after this body: on this device, behind this synchronise
         if (counted)
             --scene->live_accums;
     }
@@ -32,12 +30,8 @@ struct rt_accum {
 };
 
 template <class T> static int accum_alloc(rt_accum *a, size_t bytes, T **ptr, const char *fn) {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-    if (e != hipSuccess)
-        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
-    a->owned.push_back(q);
-    *ptr = static_cast<T *>(q);
+    if (hipError_t e = a->owned.alloc_bytes(ptr, bytes); e != hipSuccess)
+        return rt::hip_fail(e, fn);
     return RT_OK;
 }
 
@@ -189,7 +183,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
             if (a->features) {
                 if (int rc = s->ensure_features(); rc != RT_OK)
                     return rc;
-                a->F.rec = s->wf_feat;
+                a->F.rec = s->wf_feat.get();
             }
             s->wf_bind(W);
             W.fb = nullptr;
@@ -290,9 +284,9 @@ extern "C" int rt_accum_resolve(rt_accum *acc, uint32_t flags, float *fb_rgb) {
     if (!device_fb)
         if (int rc = s->ensure_fb(3 * n); rc != RT_OK)
             return rc;
-    HIP_TRY(rt::launch_accum_image(acc->R, device_fb ? fb_rgb : s->d_fb, s->stream));
+    HIP_TRY(rt::launch_accum_image(acc->R, device_fb ? fb_rgb : s->fb.get(), s->stream));
     if (!device_fb)
-        HIP_TRY(hipMemcpyAsync(fb_rgb, s->d_fb, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(fb_rgb, s->fb.get(), 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RT_OK;
 }
@@ -309,9 +303,9 @@ extern "C" int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb
         rc = s->ensure_film(device_fb ? 0 : 3ull * n);
     if (rc != RT_OK)
         return rc;
-    uint8_t *d_rgb8 = device_fb ? rgb8 : s->d_rgb8;
-    HIP_TRY(rt::launch_accum_image(acc->R, s->d_fb, s->stream));
-    HIP_TRY(rt::launch_film(s->d_fb, d_rgb8, n, 0, 1, n, s->d_film_table, s->stream)); // image.h:49-82, as rt_render_rgb8
+    uint8_t *d_rgb8 = device_fb ? rgb8 : s->rgb8.get();
+    HIP_TRY(rt::launch_accum_image(acc->R, s->fb.get(), s->stream));
+    HIP_TRY(rt::launch_film(s->fb.get(), d_rgb8, n, 0, 1, n, s->film_table.get(), s->stream)); // image.h:49-82, as rt_render_rgb8
     if (!device_fb)
         HIP_TRY(hipMemcpyAsync(rgb8, d_rgb8, 3ull * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -378,7 +372,7 @@ extern "C" int rt_accum_resolve_features(rt_accum *acc, uint32_t flags, float *a
     }
     if (int rc = s->ensure_fb(7 * n); rc != RT_OK) // staging: albedo, normal, depth
         return rc;
-    float *d_a = s->d_fb, *d_n = s->d_fb + 3 * n, *d_z = s->d_fb + 6 * n;
+    float *d_a = s->fb.get(), *d_n = s->fb.get() + 3 * n, *d_z = s->fb.get() + 6 * n;
     HIP_TRY(rt::launch_accum_feature_means(acc->R, acc->F, d_a, d_n, d_z, s->stream));
     if (albedo)
         HIP_TRY(hipMemcpyAsync(albedo, d_a, 12 * n, hipMemcpyDeviceToHost, s->stream));
@@ -437,9 +431,9 @@ extern "C" int rt_accum_denoise(rt_accum *acc, const rt_denoise *opt, uint32_t f
     if (!device_fb)
         if (int rc = s->ensure_fb(3 * n); rc != RT_OK)
             return rc;
-    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, device_fb ? fb_rgb : s->d_fb, s->stream));
+    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, device_fb ? fb_rgb : s->fb.get(), s->stream));
     if (!device_fb)
-        HIP_TRY(hipMemcpyAsync(fb_rgb, s->d_fb, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(fb_rgb, s->fb.get(), 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RT_OK;
 }
@@ -459,9 +453,9 @@ extern "C" int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint3
         rc = s->ensure_film(device_fb ? 0 : 3ull * n);
     if (rc != RT_OK)
         return rc;
-    uint8_t *d_rgb8 = device_fb ? rgb8 : s->d_rgb8;
-    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, s->d_fb, s->stream));
-    HIP_TRY(rt::launch_film(s->d_fb, d_rgb8, n, 0, 1, n, s->d_film_table, s->stream)); // image.h:49-82, as rt_accum_resolve_rgb8
+    uint8_t *d_rgb8 = device_fb ? rgb8 : s->rgb8.get();
+    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, s->fb.get(), s->stream));
+    HIP_TRY(rt::launch_film(s->fb.get(), d_rgb8, n, 0, 1, n, s->film_table.get(), s->stream)); // image.h:49-82, as rt_accum_resolve_rgb8
     if (!device_fb)
         HIP_TRY(hipMemcpyAsync(rgb8, d_rgb8, 3ull * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));

@@ -3,12 +3,14 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/rt_abi.h"
+#include "rt_dev_mem.h"
 #include "rt_device_types.h"
 
 namespace rt {
 
 struct DeviceBvh {
-    DevNode *nodes = nullptr; // device memory, owned by the caller after a successful build (null when `wide` was built)
+    DevArena mem{16};         // owns what the pointers below name; the caller moves it (or single buffers of it) to where they are to live
+    DevNode *nodes = nullptr; // (null when `wide` was built)
     WideNode *wide = nullptr; // the 8-wide tree, collapsed on the device (tris / attrs are then in ITS order)
     uint32_t n_wide = 0, wide_depth = 0;
     WideGrid wide_grid{};     // the grids its nodes were snapped to (wide_grid.h)

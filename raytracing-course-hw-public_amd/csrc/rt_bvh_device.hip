@@ -674,35 +674,9 @@ __global__ __launch_bounds__(64) void k_wide_emit(const WideEmit E) {
     E.wide[widx] = rec;
 }
 
-struct Tmp { // device allocations of the build, freed on every return path
-    std::vector<void *> ptrs;
-    template <class T> hipError_t alloc(T **p, size_t count) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess)
-            ptrs.push_back(q);
-        *p = static_cast<T *>(q);
-        return e;
-    }
-    ~Tmp() {
-        for (void *p : ptrs)
-            (void)hipFree(p);
-    }
-};
-
 } // namespace
 
 namespace rt {
-
-#define BUILD_TRY(expr)            \
-    do {                           \
-        hipError_t e_ = (expr);    \
-        if (e_ != hipSuccess) {    \
-            if (err)               \
-                *err = #expr;      \
-            return e_;             \
-        }                          \
-    } while (0)
 
 hipError_t build_bvh_device(const rt_scene_desc *d, hipStream_t stream, DeviceBvh *out, const char **err, bool wide, float cost_node, float cost_tri) {
     const uint32_t n = d->n_triangles;
@@ -713,20 +687,20 @@ hipError_t build_bvh_device(const rt_scene_desc *d, hipStream_t stream, DeviceBv
         return hipSuccess;
     // ---- obtain the five device arrays: this entry point uploads them ...
     const auto t0 = std::chrono::steady_clock::now();
-    Tmp tmp;
+    DevArena tmp; // scratch of the build, freed on every return path
     float *pos, *nrm, *tan, *uv;
     uint32_t *mat;
-    BUILD_TRY(tmp.alloc(&pos, 9ull * n));
-    BUILD_TRY(tmp.alloc(&nrm, 9ull * n));
-    BUILD_TRY(tmp.alloc(&tan, 9ull * n));
-    BUILD_TRY(tmp.alloc(&uv, 6ull * n));
-    BUILD_TRY(tmp.alloc(&mat, (size_t)n));
-    BUILD_TRY(hipMemcpyAsync(pos, d->positions, 36ull * n, hipMemcpyHostToDevice, stream));
-    BUILD_TRY(hipMemcpyAsync(nrm, d->normals, 36ull * n, hipMemcpyHostToDevice, stream));
-    BUILD_TRY(hipMemcpyAsync(tan, d->tangents, 36ull * n, hipMemcpyHostToDevice, stream));
-    BUILD_TRY(hipMemcpyAsync(uv, d->texcoords, 24ull * n, hipMemcpyHostToDevice, stream));
-    BUILD_TRY(hipMemcpyAsync(mat, d->material_ids, 4ull * n, hipMemcpyHostToDevice, stream));
-    BUILD_TRY(hipStreamSynchronize(stream)); // uploads done = start of the device build proper
+    HIP_TRY_ERR(tmp.alloc(&pos, 9ull * n));
+    HIP_TRY_ERR(tmp.alloc(&nrm, 9ull * n));
+    HIP_TRY_ERR(tmp.alloc(&tan, 9ull * n));
+    HIP_TRY_ERR(tmp.alloc(&uv, 6ull * n));
+    HIP_TRY_ERR(tmp.alloc(&mat, (size_t)n));
+    HIP_TRY_ERR(hipMemcpyAsync(pos, d->positions, 36ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(nrm, d->normals, 36ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(tan, d->tangents, 36ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(uv, d->texcoords, 24ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(mat, d->material_ids, 4ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream)); // uploads done = start of the device build proper
     const auto t1 = std::chrono::steady_clock::now();
     // ---- ... and builds from them
     DeviceArrays in;
@@ -745,7 +719,7 @@ hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_option
     out->fast_ok = true;
     if (n == 0)
         return hipSuccess;
-    Tmp tmp;
+    DevArena tmp; // scratch of the build, freed on every return path
     const float *pos = in.pos, *nrm = in.nrm, *tan = in.tan, *uv = in.uv;
     const uint32_t *mat = in.mat;
     uint32_t *keys[2], *vals[2], *bounds, *leaf_parent, *node_parent, *arrived, *fast_bad;
@@ -758,65 +732,51 @@ hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_option
         leaf_tris = 1;
     const uint32_t n_leaves = (n + leaf_tris - 1) / leaf_tris;
     for (int k = 0; k < 2; ++k) {
-        BUILD_TRY(tmp.alloc(&keys[k], (size_t)n));
-        BUILD_TRY(tmp.alloc(&vals[k], (size_t)n));
+        HIP_TRY_ERR(tmp.alloc(&keys[k], (size_t)n));
+        HIP_TRY_ERR(tmp.alloc(&vals[k], (size_t)n));
     }
-    BUILD_TRY(tmp.alloc(&bounds, (size_t)8));
+    HIP_TRY_ERR(tmp.alloc(&bounds, (size_t)8));
     static const uint32_t init_bounds[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-    BUILD_TRY(hipMemcpyAsync(bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
     fast_bad = bounds + 6;
     const auto t1 = std::chrono::steady_clock::now();
 
     const int blocks = (int)std::min<uint64_t>(((uint64_t)n + 255) / 256, 256u * 16u);
-    BUILD_TRY(RT_LAUNCH_CHECKED(k_bounds, dim3(blocks), dim3(256), 0, stream, pos, n, bounds));
-    BUILD_TRY(RT_LAUNCH_CHECKED(k_keys, dim3(blocks), dim3(256), 0, stream, pos, n, bounds, keys[0], vals[0]));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_bounds, dim3(blocks), dim3(256), 0, stream, pos, n, bounds));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_keys, dim3(blocks), dim3(256), 0, stream, pos, n, bounds, keys[0], vals[0]));
     size_t sort_bytes = 0;
-    BUILD_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys[0], keys[1], vals[0], vals[1], (size_t)n, 0u, 30u, stream));
+    HIP_TRY_ERR(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys[0], keys[1], vals[0], vals[1], (size_t)n, 0u, 30u, stream));
     char *sort_tmp;
-    BUILD_TRY(tmp.alloc(&sort_tmp, sort_bytes));
-    BUILD_TRY(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, keys[0], keys[1], vals[0], vals[1], (size_t)n, 0u, 30u, stream));
+    HIP_TRY_ERR(tmp.alloc(&sort_tmp, sort_bytes));
+    HIP_TRY_ERR(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, keys[0], keys[1], vals[0], vals[1], (size_t)n, 0u, 30u, stream));
 
-    // outputs (owned by the caller on success)
-    std::vector<void *> outs;
-    auto out_alloc = [&](void **p, size_t bytes) {
-        hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-        if (e == hipSuccess)
-            outs.push_back(*p);
-        return e;
-    };
-    struct OutGuard {
-        std::vector<void *> &v;
-        bool keep = false;
-        ~OutGuard() {
-            if (!keep)
-                for (void *p : v)
-                    (void)hipFree(p);
-        }
-    } guard{outs};
+    // outputs: out->mem owns them, so a failure below leaves nothing behind once the caller lets `out` go. For the wide tree the binary
+    // tree and the Morton-ordered records are scaffolding, freed with the scratch: only the wide tree stays.
+    DevArena &outs = out->mem, &bin = wide ? tmp : out->mem;
     BuildArrays A{};
     A.pos = pos, A.nrm = nrm, A.tan = tan, A.uv = uv, A.mat = mat;
     A.keys_sorted = keys[1], A.prims_sorted = vals[1];
     A.n = n, A.n_leaves = n_leaves, A.leaf_tris = leaf_tris;
-    BUILD_TRY(out_alloc((void **)&A.tris, sizeof(DevTri) * (size_t)n));
-    BUILD_TRY(out_alloc((void **)&A.attrs, sizeof(DevAttr) * (size_t)n));
-    BUILD_TRY(out_alloc((void **)&A.nodes, sizeof(DevNode) * (size_t)(n_leaves > 1 ? n_leaves - 1 : 1)));
-    BUILD_TRY(tmp.alloc(&A.leaf_keys, (size_t)n_leaves));
-    BUILD_TRY(tmp.alloc(&A.leaf_box, 6ull * n_leaves));
-    BUILD_TRY(tmp.alloc(&A.node_box, 6ull * n_leaves));
-    BUILD_TRY(tmp.alloc(&leaf_parent, (size_t)n_leaves));
-    BUILD_TRY(tmp.alloc(&node_parent, (size_t)n_leaves));
-    BUILD_TRY(tmp.alloc(&arrived, (size_t)n_leaves));
+    HIP_TRY_ERR(bin.alloc(&A.tris, (size_t)n));
+    HIP_TRY_ERR(bin.alloc(&A.attrs, (size_t)n));
+    HIP_TRY_ERR(bin.alloc(&A.nodes, (size_t)(n_leaves > 1 ? n_leaves - 1 : 1)));
+    HIP_TRY_ERR(tmp.alloc(&A.leaf_keys, (size_t)n_leaves));
+    HIP_TRY_ERR(tmp.alloc(&A.leaf_box, 6ull * n_leaves));
+    HIP_TRY_ERR(tmp.alloc(&A.node_box, 6ull * n_leaves));
+    HIP_TRY_ERR(tmp.alloc(&leaf_parent, (size_t)n_leaves));
+    HIP_TRY_ERR(tmp.alloc(&node_parent, (size_t)n_leaves));
+    HIP_TRY_ERR(tmp.alloc(&arrived, (size_t)n_leaves));
     A.leaf_parent = leaf_parent, A.node_parent = node_parent, A.arrived = arrived, A.fast_bad = fast_bad;
     A.cost_node = cost_node, A.cost_tri = cost_tri;
     if (wide) {
-        BUILD_TRY(tmp.alloc(&A.dp_cost, 7ull * n_leaves));
-        BUILD_TRY(tmp.alloc(&A.dp_dec, (size_t)n_leaves));
-        BUILD_TRY(tmp.alloc(&A.dp_ntris, (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&A.dp_cost, 7ull * n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&A.dp_dec, (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&A.dp_ntris, (size_t)n_leaves));
     }
-    BUILD_TRY(hipMemsetAsync(arrived, 0, 4ull * n_leaves, stream));
-    BUILD_TRY(hipMemsetAsync(leaf_parent, 0xFF, 4ull * n_leaves, stream)); // RT_NONE: a single leaf has no parent
+    HIP_TRY_ERR(hipMemsetAsync(arrived, 0, 4ull * n_leaves, stream));
+    HIP_TRY_ERR(hipMemsetAsync(leaf_parent, 0xFF, 4ull * n_leaves, stream)); // RT_NONE: a single leaf has no parent
     const int lblocks = (int)std::min<uint64_t>(((uint64_t)n_leaves + 255) / 256, 256u * 16u);
-    BUILD_TRY(RT_LAUNCH_CHECKED(k_leaves, dim3(lblocks), dim3(256), 0, stream, A));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_leaves, dim3(lblocks), dim3(256), 0, stream, A));
     // binary tree over the leaves: PLOC (default) or the Karras radix tree + refit (rt_build_options.device_builder = RT_BUILDER_LBVH; also the fallback when
     // a PLOC tree comes out deeper than the traversal stacks allow)
     uint32_t bin_root = 0u;
@@ -830,34 +790,34 @@ hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_option
             radius = std::min(PLOC_MAX_RADIUS, std::max(1, (int)opt.ploc_radius));
         P.radius = radius;
         for (int k = 0; k < 2; ++k) {
-            BUILD_TRY(tmp.alloc(&P.ref[k], (size_t)n_leaves));
-            BUILD_TRY(tmp.alloc(&P.box[k], 6ull * n_leaves));
+            HIP_TRY_ERR(tmp.alloc(&P.ref[k], (size_t)n_leaves));
+            HIP_TRY_ERR(tmp.alloc(&P.box[k], 6ull * n_leaves));
         }
-        BUILD_TRY(tmp.alloc(&P.nn, (size_t)n_leaves));
-        BUILD_TRY(tmp.alloc(&P.valid, (size_t)n_leaves));
-        BUILD_TRY(tmp.alloc(&P.pos, (size_t)n_leaves));
-        BUILD_TRY(tmp.alloc(&P.depth, (size_t)n_leaves));
-        BUILD_TRY(tmp.alloc(&P.counters, (size_t)4));
-        BUILD_TRY(hipMemsetAsync(P.counters, 0, 4 * sizeof(uint32_t), stream));
+        HIP_TRY_ERR(tmp.alloc(&P.nn, (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&P.valid, (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&P.pos, (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&P.depth, (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&P.counters, (size_t)4));
+        HIP_TRY_ERR(hipMemsetAsync(P.counters, 0, 4 * sizeof(uint32_t), stream));
         size_t scan_bytes = 0;
-        BUILD_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, P.valid, P.pos, 0u, (size_t)n_leaves, rocprim::plus<uint32_t>(), stream));
+        HIP_TRY_ERR(rocprim::exclusive_scan(nullptr, scan_bytes, P.valid, P.pos, 0u, (size_t)n_leaves, rocprim::plus<uint32_t>(), stream));
         char *scan_tmp;
-        BUILD_TRY(tmp.alloc(&scan_tmp, scan_bytes));
-        BUILD_TRY(RT_LAUNCH_CHECKED(k_ploc_init, dim3((n_leaves + 255u) / 256u), dim3(256), 0, stream, P, A)); // one thread per leaf (not grid-stride)
+        HIP_TRY_ERR(tmp.alloc(&scan_tmp, scan_bytes));
+        HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_ploc_init, dim3((n_leaves + 255u) / 256u), dim3(256), 0, stream, P, A)); // one thread per leaf (not grid-stride)
         P.m = n_leaves;
         P.cur = 0;
         int rounds = 0;
         while (P.m > 1) {
             const dim3 grid((P.m + 255u) / 256u);
-            BUILD_TRY(RT_LAUNCH_CHECKED(k_ploc_nn, grid, dim3(256), 0, stream, P));
-            BUILD_TRY(RT_LAUNCH_CHECKED(k_ploc_merge, grid, dim3(256), 0, stream, P, A));
+            HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_ploc_nn, grid, dim3(256), 0, stream, P));
+            HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_ploc_merge, grid, dim3(256), 0, stream, P, A));
             size_t sb = scan_bytes;
-            BUILD_TRY(rocprim::exclusive_scan(scan_tmp, sb, P.valid, P.pos, 0u, (size_t)P.m, rocprim::plus<uint32_t>(), stream));
-            BUILD_TRY(RT_LAUNCH_CHECKED(k_ploc_compact, grid, dim3(256), 0, stream, P));
+            HIP_TRY_ERR(rocprim::exclusive_scan(scan_tmp, sb, P.valid, P.pos, 0u, (size_t)P.m, rocprim::plus<uint32_t>(), stream));
+            HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_ploc_compact, grid, dim3(256), 0, stream, P));
             uint32_t last[2];
-            BUILD_TRY(hipMemcpyAsync(&last[0], P.pos + (P.m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            BUILD_TRY(hipMemcpyAsync(&last[1], P.valid + (P.m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            BUILD_TRY(hipStreamSynchronize(stream));
+            HIP_TRY_ERR(hipMemcpyAsync(&last[0], P.pos + (P.m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY_ERR(hipMemcpyAsync(&last[1], P.valid + (P.m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY_ERR(hipStreamSynchronize(stream));
             const uint32_t m_new = last[0] + last[1];
             P.force = (uint64_t)(P.m - m_new) * 32u < P.m ? 1 : 0; // (next to) no progress — a healthy round merges a quarter of the clusters —: pair neighbours next round
             P.m = m_new;
@@ -869,24 +829,24 @@ hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_option
             }
         }
         uint32_t h_root, h_counters[4];
-        BUILD_TRY(hipMemcpyAsync(&h_root, P.ref[P.cur], sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        BUILD_TRY(hipMemcpyAsync(h_counters, P.counters, sizeof(h_counters), hipMemcpyDeviceToHost, stream));
-        BUILD_TRY(hipStreamSynchronize(stream));
+        HIP_TRY_ERR(hipMemcpyAsync(&h_root, P.ref[P.cur], sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY_ERR(hipMemcpyAsync(h_counters, P.counters, sizeof(h_counters), hipMemcpyDeviceToHost, stream));
+        HIP_TRY_ERR(hipStreamSynchronize(stream));
         bin_root = h_root;
         out->rounds = (uint32_t)rounds;
         if (h_counters[0] != n_leaves - 1u || h_counters[1] > 60u) // deeper than the traversal stacks (RT_MAX_STACK 64): take the depth-bounded radix tree
             use_ploc = false;
     }
     if (n_leaves > 1 && !use_ploc) {
-        BUILD_TRY(hipMemsetAsync(arrived, 0, 4ull * n_leaves, stream));
-        BUILD_TRY(RT_LAUNCH_CHECKED(k_radix_tree, dim3(lblocks), dim3(256), 0, stream, A));
-        BUILD_TRY(RT_LAUNCH_CHECKED(k_refit, dim3(lblocks), dim3(256), 0, stream, A));
+        HIP_TRY_ERR(hipMemsetAsync(arrived, 0, 4ull * n_leaves, stream));
+        HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_radix_tree, dim3(lblocks), dim3(256), 0, stream, A));
+        HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_refit, dim3(lblocks), dim3(256), 0, stream, A));
         bin_root = 0u;
     }
     out->ploc = use_ploc;
     uint32_t h_bounds[8];
-    BUILD_TRY(hipMemcpyAsync(h_bounds, bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, stream));
-    BUILD_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(hipMemcpyAsync(h_bounds, bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream));
     const auto t2 = std::chrono::steady_clock::now();
 
     // ---- wide collapse on the device: level by level from the root; the host only reads each level's size
@@ -897,17 +857,17 @@ hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_option
     if (wide) {
         uint2 *queue[2];
         uint32_t *counters;
-        BUILD_TRY(out_alloc((void **)&wide_nodes, sizeof(WideNode) * (size_t)n_leaves)); // <= one wide node per binary inner node
-        BUILD_TRY(out_alloc((void **)&wide_tris, sizeof(DevTri) * (size_t)n));
-        BUILD_TRY(out_alloc((void **)&wide_attrs, sizeof(DevAttr) * (size_t)n));
-        BUILD_TRY(tmp.alloc(&queue[0], (size_t)n_leaves));
-        BUILD_TRY(tmp.alloc(&queue[1], (size_t)n_leaves));
-        BUILD_TRY(tmp.alloc(&counters, (size_t)4));
+        HIP_TRY_ERR(outs.alloc(&wide_nodes, (size_t)n_leaves)); // <= one wide node per binary inner node
+        HIP_TRY_ERR(outs.alloc(&wide_tris, (size_t)n));
+        HIP_TRY_ERR(outs.alloc(&wide_attrs, (size_t)n));
+        HIP_TRY_ERR(tmp.alloc(&queue[0], (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&queue[1], (size_t)n_leaves));
+        HIP_TRY_ERR(tmp.alloc(&counters, (size_t)4));
         const uint32_t init_counters[4] = {1u, 0u, 0u, 0u}; // record 0 = the root
         const uint2 root_entry = make_uint2(bin_root, 0u);   // the binary root (Karras: node 0; PLOC: the last merge) -> wide record 0
-        BUILD_TRY(hipMemcpyAsync(counters, init_counters, sizeof(init_counters), hipMemcpyHostToDevice, stream));
-        BUILD_TRY(hipMemcpyAsync(queue[0], &root_entry, sizeof(root_entry), hipMemcpyHostToDevice, stream));
-        BUILD_TRY(hipStreamSynchronize(stream));
+        HIP_TRY_ERR(hipMemcpyAsync(counters, init_counters, sizeof(init_counters), hipMemcpyHostToDevice, stream));
+        HIP_TRY_ERR(hipMemcpyAsync(queue[0], &root_entry, sizeof(root_entry), hipMemcpyHostToDevice, stream));
+        HIP_TRY_ERR(hipStreamSynchronize(stream));
         WideEmit E{};
         {
             float s_lo[3], s_hi[3];
@@ -922,11 +882,11 @@ hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_option
         while (level_n > 0) {
             ++wide_depth;
             E.queue_in = queue[cur], E.queue_out = queue[cur ^ 1], E.n_in = level_n;
-            BUILD_TRY(hipMemsetAsync(counters + 2, 0, sizeof(uint32_t), stream));
-            BUILD_TRY(RT_LAUNCH_CHECKED(k_wide_emit, dim3((level_n + 63u) / 64u), dim3(64), 0, stream, E));
+            HIP_TRY_ERR(hipMemsetAsync(counters + 2, 0, sizeof(uint32_t), stream));
+            HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_wide_emit, dim3((level_n + 63u) / 64u), dim3(64), 0, stream, E));
             uint32_t h_counters[4];
-            BUILD_TRY(hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, stream));
-            BUILD_TRY(hipStreamSynchronize(stream));
+            HIP_TRY_ERR(hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, stream));
+            HIP_TRY_ERR(hipStreamSynchronize(stream));
             level_n = h_counters[2];
             n_wide = h_counters[0];
             if (wide_depth > 200u) { // cannot happen (a level always consumes its queue); never spin
@@ -939,15 +899,11 @@ hipError_t build_bvh_device_arrays(const DeviceArrays &in, const rt_build_option
     }
     const auto t3 = std::chrono::steady_clock::now();
 
-    guard.keep = true;
     out->wide = wide_nodes;
     out->n_wide = n_wide;
     out->wide_depth = wide_depth;
     out->wide_ms = std::chrono::duration<double, std::milli>(t3 - t2).count();
-    if (wide) { // the binary tree and the Morton-ordered records were scaffolding: only the wide tree stays
-        (void)hipFree(A.nodes);
-        (void)hipFree(A.tris);
-        (void)hipFree(A.attrs);
+    if (wide) {
         A.nodes = nullptr;
         A.tris = wide_tris;
         A.attrs = wide_attrs;

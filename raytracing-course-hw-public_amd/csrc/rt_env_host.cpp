@@ -10,26 +10,8 @@
 
 namespace {
 
-struct DevBufs { // everything a build allocates; what is not handed to the scene is freed on every return path
-    std::vector<void *> p;
-    int alloc(size_t bytes, void **out) {
-        *out = nullptr;
-        const hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-        if (e != hipSuccess)
-            return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_set_environment: ") + hipGetErrorString(e));
-        p.push_back(*out);
-        return RT_OK;
-    }
-    ~DevBufs() {
-        for (void *q : p)
-            (void)hipFree(q);
-    }
-};
-
 void drop_environment(rt_scene *s) {
-    for (void *q : s->env_owned)
-        (void)hipFree(q);
-    s->env_owned.clear();
+    s->env_owned.reset();
     s->dev.env = DevEnv{};
 }
 
@@ -80,17 +62,24 @@ extern "C" int rt_set_environment(rt_scene *s, const rt_environment *env) {
         }
     }
 
-    DevBufs keep, temp;
+    // what a build allocates: the texels and the tables are for the scene, `temp` is the build's own; what is not handed to the scene is
+    // freed on every return path
+    rt::DevArena keep{16}, tables{16}, temp{16};
     DevEnv E{};
     rt::EnvBuild B{};
     E.width = W, E.height = H;
     int rc;
-    if ((rc = keep.alloc(n * 16, (void **)&E.texels)) != RT_OK || (rc = temp.alloc(n * 12, (void **)&B.rgb)) != RT_OK)
+    auto alloc = [](rt::DevArena &a, size_t bytes, auto **out) -> int {
+        if (hipError_t e = a.alloc_bytes(out, bytes); e != hipSuccess)
+            return rt::hip_fail(e, "rt_set_environment");
+        return RT_OK;
+    };
+    if ((rc = alloc(keep, n * 16, &E.texels)) != RT_OK || (rc = alloc(temp, n * 12, &B.rgb)) != RT_OK)
         return rc;
-    if (dist && ((rc = keep.alloc(((size_t)H + 1) * 4, (void **)&E.marg)) != RT_OK || (rc = keep.alloc((size_t)H * (W + 1) * 4, (void **)&E.rows)) != RT_OK ||
-                 (rc = keep.alloc(band.size() * 4, (void **)&E.band)) != RT_OK || (rc = temp.alloc((size_t)H * 8, (void **)&B.omega)) != RT_OK ||
-                 (rc = temp.alloc(n * 8, (void **)&B.weights)) != RT_OK || (rc = temp.alloc((size_t)H * 8, (void **)&B.row_total)) != RT_OK ||
-                 (rc = temp.alloc(8, (void **)&B.total)) != RT_OK))
+    if (dist && ((rc = alloc(tables, ((size_t)H + 1) * 4, &E.marg)) != RT_OK || (rc = alloc(tables, (size_t)H * (W + 1) * 4, &E.rows)) != RT_OK ||
+                 (rc = alloc(tables, band.size() * 4, &E.band)) != RT_OK || (rc = alloc(temp, (size_t)H * 8, &B.omega)) != RT_OK ||
+                 (rc = alloc(temp, n * 8, &B.weights)) != RT_OK || (rc = alloc(temp, (size_t)H * 8, &B.row_total)) != RT_OK ||
+                 (rc = alloc(temp, 8, &B.total)) != RT_OK))
         return rc;
     double total = 0.0;
     rc = rt::queue_and_wait(s, [&]() -> int {
@@ -106,15 +95,12 @@ extern "C" int rt_set_environment(rt_scene *s, const rt_environment *env) {
     });
     if (rc != RT_OK)
         return rc;
-    if (dist && !(total > 0.0)) // every weight is zero: no distribution, the flag acts as if it were not set (the tables go with `keep`)
+    if (dist && !(total > 0.0)) // every weight is zero: no distribution, the flag acts as if it were not set (the tables die with `tables`)
         E.marg = E.rows = E.band = nullptr;
+    else
+        keep.adopt(tables);
     drop_environment(s); // the stream is idle: nothing reads the old map
-    for (void *q : keep.p)
-        if (q == E.texels || E.marg)
-            s->env_owned.push_back(q);
-        else
-            (void)hipFree(q);
-    keep.p.clear();
+    s->env_owned = std::move(keep);
     s->dev.env = E;
     return RT_OK;
 }

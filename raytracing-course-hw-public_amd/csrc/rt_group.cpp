@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "rt_dev_mem.h"
 #include "rt_device_types.h"
 #include "rt_error.h"
 #include "rt_group.h"
@@ -82,9 +83,8 @@ struct Replica {
     rt_scene *scene = nullptr;
     hipStream_t stream = nullptr; // pack / send / recv / unpack of this rank
     ncclComm_t comm = nullptr;
-    char *image = nullptr; // full-size image of this rank (only its own blocks are written)
-    char *slab = nullptr;  // its blocks, packed
-    size_t image_cap = 0, slab_cap = 0;
+    DevBuf<char> image; // full-size image of this rank (only its own blocks are written)
+    DevBuf<char> slab;  // its blocks, packed
 };
 
 // the blocks of rank r: b = r, r + G, ... < n_blocks; all full except possibly the image's last block
@@ -113,8 +113,7 @@ struct Group {
     std::vector<Replica> ranks;
     bool use_rccl = true;       // false: RT_BUILD_GROUP_COPY (peer copies; rehearsal of the flow where RCCL cannot run)
     bool self_exchange = false; // RT_BUILD_GROUP_SELF_EXCHANGE: rank 0's own blocks also travel through ncclSend/ncclRecv (N = 1 test)
-    char *recv = nullptr;       // on ranks[0].device: the other ranks' slabs
-    size_t recv_cap = 0;
+    DevBuf<char> recv;          // on ranks[0].device: the other ranks' slabs
     bool comm_broken = false;   // an exchange failed and the communicators were aborted: later renders report RT_ERR_COMM at once
 };
 
@@ -123,21 +122,9 @@ namespace {
 int nccl_fail(const char *what, ncclResult_t r) {
     return fail(RT_ERR_COMM, std::string(what) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(r) : "RCCL error"));
 }
-int hip_fail(const char *what, hipError_t e) { return fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-int ensure(char **buf, size_t *cap, size_t bytes) {
-    if (*cap >= bytes)
-        return RT_OK;
-    if (*buf)
-        (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess)
-        return hip_fail("rt group: buffer", e);
-    *buf = static_cast<char *>(p);
-    *cap = bytes;
+int ensure(DevBuf<char> &buf, size_t bytes) {
+    if (hipError_t e = buf.reserve(bytes); e != hipSuccess)
+        return hip_fail(e, "rt group: buffer");
     return RT_OK;
 }
 
@@ -189,18 +176,16 @@ void group_destroy(Group *g) {
         (void)hipSetDevice(r.device);
         if (r.comm && rccl().CommDestroy)
             (void)rccl().CommDestroy(r.comm);
-        if (r.image)
-            (void)hipFree(r.image);
-        if (r.slab)
-            (void)hipFree(r.slab);
+        r.image.reset(); // with this replica's device current, not whichever is when `g` dies
+        r.slab.reset();
         if (r.stream)
             (void)hipStreamDestroy(r.stream);
         if (r.scene)
             rt_destroy(r.scene);
     }
-    if (g->recv && !g->ranks.empty()) {
+    if (g->recv.get() && !g->ranks.empty()) {
         (void)hipSetDevice(g->ranks[0].device);
-        (void)hipFree(g->recv);
+        g->recv.reset();
     }
     delete g;
 }
@@ -323,21 +308,21 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
     for (uint32_t r = 0; r < G; ++r) {
         Replica &R = g->ranks[r];
         if (hipError_t e = hipSetDevice(R.device); e != hipSuccess)
-            return hip_fail("hipSetDevice", e);
+            return hip_fail(e, "hipSetDevice");
         const bool needs_image = r > 0 || !device_out || exchange0;
-        if (int rc = needs_image ? ensure(&R.image, &R.image_cap, n_pix * es) : RT_OK; rc != RT_OK)
+        if (int rc = needs_image ? ensure(R.image, n_pix * es) : RT_OK; rc != RT_OK)
             return rc;
         if (r > 0 || exchange0)
-            if (int rc = ensure(&R.slab, &R.slab_cap, blk[r].pixels(block) * es); rc != RT_OK)
+            if (int rc = ensure(R.slab, blk[r].pixels(block) * es); rc != RT_OK)
                 return rc;
     }
     (void)hipSetDevice(g->ranks[0].device);
-    if (int rc = ensure(&g->recv, &g->recv_cap, recv_bytes); rc != RT_OK)
+    if (int rc = ensure(g->recv, recv_bytes); rc != RT_OK)
         return rc;
     // where rank 0 assembles the final image: the caller's device buffer, or its own
-    char *final_img = device_out ? caller : g->ranks[0].image;
+    char *final_img = device_out ? caller : g->ranks[0].image.get();
     // where rank 0 renders: straight into the final image, unless its blocks are to be exchanged as well
-    char *render0 = exchange0 ? g->ranks[0].image : final_img;
+    char *render0 = exchange0 ? g->ranks[0].image.get() : final_img;
     if (exchange0 && device_out && render0 == final_img)
         return fail(RT_ERR_INVALID_ARG, "rt group: internal buffer aliasing");
 
@@ -357,7 +342,7 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
                 q.shard_block = (uint32_t)block;
                 q.flags |= RT_FLAG_DEVICE_FB;
                 q.progress = nullptr;
-                char *dst = r == 0 ? render0 : g->ranks[r].image;
+                char *dst = r == 0 ? render0 : g->ranks[r].image.get();
                 if (views)
                     rcs[r] = rgb8 ? rt_render_views_rgb8(g->ranks[r].scene, &q, views, n_views, reinterpret_cast<uint8_t *>(dst), &sts[r])
                                   : rt_render_views(g->ranks[r].scene, &q, views, n_views, reinterpret_cast<float *>(dst), &sts[r]);
@@ -387,7 +372,7 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
         return fail(RT_ERR_COMM, "rt group: the communicator was aborted by an earlier failed exchange; create the scene again");
     for (uint32_t r = 0; r < G; ++r)
         if (hipError_t e = hipSetDevice(g->ranks[r].device); e != hipSuccess)
-            return hip_fail("rt group: hipSetDevice before the exchange", e);
+            return hip_fail(e, "rt group: hipSetDevice before the exchange");
     // The rank threads work on a COPY of the communicator handles taken here, before any of them starts; a failing rank sets `broken`
     // and aborts every communicator of that copy once (abort completes the peers' pending operations with an error). Replica::comm is
     // only written after the join, so no thread ever reads a handle another one is clearing, and a rank that has not posted yet when the
@@ -434,7 +419,7 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
                 const bool sends = r > 0 || exchange0;
                 const size_t bytes = blk[r].pixels(block) * es;
                 if (sends && bytes)
-                    hip_try(copy_blocks(R.slab, r == 0 ? render0 : R.image, true, blk[r], block, r, G, es, R.stream), "pack");
+                    hip_try(copy_blocks(R.slab.get(), r == 0 ? render0 : R.image.get(), true, blk[r], block, r, G, es, R.stream), "pack");
                 if (g->use_rccl && broken.load()) {
                     if (rcs[r] == RT_OK) {
                         rcs[r] = RT_ERR_COMM;
@@ -445,13 +430,13 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
                     if (r == 0) {
                         nccl_try(N.GroupStart(), "ncclGroupStart");
                         if (exchange0 && bytes)
-                            nccl_try(N.Send(R.slab, bytes, ncclUint8, 0, comm, R.stream), "ncclSend");
+                            nccl_try(N.Send(R.slab.get(), bytes, ncclUint8, 0, comm, R.stream), "ncclSend");
                         for (uint32_t q = exchange0 ? 0 : 1; q < G; ++q)
                             if (const size_t qb = blk[q].pixels(block) * es)
-                                nccl_try(N.Recv(g->recv + recv_off[q], qb, ncclUint8, (int)q, comm, R.stream), "ncclRecv");
+                                nccl_try(N.Recv(g->recv.get() + recv_off[q], qb, ncclUint8, (int)q, comm, R.stream), "ncclRecv");
                         nccl_try(N.GroupEnd(), "ncclGroupEnd");
                     } else if (bytes) {
-                        nccl_try(N.Send(R.slab, bytes, ncclUint8, 0, comm, R.stream), "ncclSend");
+                        nccl_try(N.Send(R.slab.get(), bytes, ncclUint8, 0, comm, R.stream), "ncclSend");
                     }
                     if (comm_failed)
                         abort_all(); // the peers' matching operations would never complete
@@ -472,22 +457,22 @@ int group_render(Group *g, const rt_params *p, const rt_view *views, uint32_t n_
             return fail(rcs[r], "GPU " + std::to_string(g->ranks[r].device) + " (gather): " + errs[r]);
     Replica &R0 = g->ranks[0];
     if (hipError_t e = hipSetDevice(R0.device); e != hipSuccess)
-        return hip_fail("hipSetDevice", e);
+        return hip_fail(e, "hipSetDevice");
     if (!g->use_rccl) // rehearsal transport: peer copies of the packed slabs (same packing, same unpacking), ordered on rank
                       // 0's stream with the unpacking below (a device-to-device hipMemcpyPeer may return before it is done)
         for (uint32_t q = 1; q < G; ++q)
             if (const size_t qb = blk[q].pixels(block) * es)
-                if (hipError_t e = hipMemcpyPeerAsync(g->recv + recv_off[q], R0.device, g->ranks[q].slab, g->ranks[q].device, qb, R0.stream); e != hipSuccess)
-                    return hip_fail("hipMemcpyPeerAsync", e);
+                if (hipError_t e = hipMemcpyPeerAsync(g->recv.get() + recv_off[q], R0.device, g->ranks[q].slab.get(), g->ranks[q].device, qb, R0.stream); e != hipSuccess)
+                    return hip_fail(e, "hipMemcpyPeerAsync");
     for (uint32_t q = exchange0 ? 0 : 1; q < G; ++q)
         if (blk[q].pixels(block))
-            if (hipError_t e = copy_blocks(g->recv + recv_off[q], final_img, false, blk[q], block, q, G, es, R0.stream); e != hipSuccess)
-                return hip_fail("unpack", e);
+            if (hipError_t e = copy_blocks(g->recv.get() + recv_off[q], final_img, false, blk[q], block, q, G, es, R0.stream); e != hipSuccess)
+                return hip_fail(e, "unpack");
     if (!device_out)
         if (hipError_t e = hipMemcpyAsync(caller, final_img, n_pix * es, hipMemcpyDeviceToHost, R0.stream); e != hipSuccess)
-            return hip_fail("image copy", e);
+            return hip_fail(e, "image copy");
     if (hipError_t e = hipStreamSynchronize(R0.stream); e != hipSuccess)
-        return hip_fail("gather", e);
+        return hip_fail(e, "gather");
 
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));

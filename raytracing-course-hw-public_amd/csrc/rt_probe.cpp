@@ -9,20 +9,6 @@
 
 namespace {
 
-// device allocation that is released on every return path of the probe entry points
-struct DevBuf {
-    void *p = nullptr;
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <class T> T *as() const { return static_cast<T *>(p); }
-    ~DevBuf() {
-        if (p)
-            (void)hipFree(p);
-    }
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-};
-
 // One probe round trip on the scene's own (non-blocking) stream, every copy ordered with the kernel: `in` goes up, `launch(d_in, d_out)`
 // queues the kernel(s) that fill the device buffers d_out[k] (out[k].bytes each), those with a host destination come back in the order
 // of `out`. The stream is synchronised also after a failed call: nothing may stay in flight over the DevBufs.
@@ -33,17 +19,18 @@ struct ProbeOut {
 };
 template <size_t N, class Launch> int probe_round_trip(rt_scene *s, const char *fn, const float *in, size_t in_bytes, const ProbeOut (&out)[N], Launch launch) {
     HIP_TRY(hipSetDevice(s->device));
-    DevBuf b_in, b_out[N];
+    rt::DevBuf<float> b_in; // released on every return path, like b_out
+    rt::DevBuf<char> b_out[N];
     void *d_out[N];
-    HIP_TRY(b_in.alloc(in_bytes));
+    HIP_TRY(b_in.reserve(in_bytes ? in_bytes / sizeof(float) : 4));
     for (size_t k = 0; k < N; ++k) {
         if (!out[k].dev)
-            HIP_TRY(b_out[k].alloc(out[k].bytes));
-        d_out[k] = out[k].dev ? out[k].dev : b_out[k].p;
+            HIP_TRY(b_out[k].reserve(out[k].bytes ? out[k].bytes : 16));
+        d_out[k] = out[k].dev ? out[k].dev : b_out[k].get();
     }
-    hipError_t e = hipMemcpyAsync(b_in.p, in, in_bytes, hipMemcpyHostToDevice, s->stream);
+    hipError_t e = hipMemcpyAsync(b_in.get(), in, in_bytes, hipMemcpyHostToDevice, s->stream);
     if (e == hipSuccess)
-        e = launch(b_in.as<float>(), d_out);
+        e = launch(b_in.get(), d_out);
     for (size_t k = 0; k < N; ++k)
         if (e == hipSuccess && out[k].host)
             e = hipMemcpyAsync(out[k].host, d_out[k], out[k].bytes, hipMemcpyDeviceToHost, s->stream);

@@ -56,19 +56,19 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
     if (!device_fb || rgb8_out) { // the float outputs are internal unless the caller keeps them in HBM
         if (int rc = s->ensure_fb(fb_floats); rc != RT_OK)
             return rc;
-        d_fb = s->d_fb;
+        d_fb = s->fb.get();
     }
     uint8_t *d_rgb8 = nullptr;
     if (rgb8_out) {
         if (int rc = s->ensure_film(device_fb ? 0 : fb_floats); rc != RT_OK)
             return rc;
-        d_rgb8 = device_fb ? rgb8_out : s->d_rgb8;
+        d_rgb8 = device_fb ? rgb8_out : s->rgb8.get();
     }
     const rt_ray *d_rays = rays;
     if (!device_fb) {
         if (int rc = s->ensure_rays((size_t)n_rays * sizeof(rt_ray)); rc != RT_OK)
             return rc;
-        d_rays = static_cast<const rt_ray *>(s->d_rays);
+        d_rays = reinterpret_cast<const rt_ray *>(s->rays.get());
     }
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     rt::PacketPolicy pol; // of this call: rt_render's, measured on camera rays of its image shape, is not disturbed
@@ -77,7 +77,7 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
         if (counters)
             HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
         if (!device_fb) // once per call; the caller's buffer outlives the stream sync below
-            HIP_TRY(hipMemcpyAsync(s->d_rays, rays, (size_t)n_rays * sizeof(rt_ray), hipMemcpyHostToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(s->rays.get(), rays, (size_t)n_rays * sizeof(rt_ray), hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipEventRecord(s->ev0, s->stream));
         WfLaunch W{};
         W.width = n_out; // the virtual image is one row of outputs (nothing on the device reads the size: it keys the packet policy)
@@ -95,7 +95,7 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
         if (int rc = rt::run_passes(s, p, pol, W, n_out, spo, nullptr, &R, stats, fn); rc != RT_OK)
             return rc;
         if (rgb8_out) // film on the device (image.h:49-82) over the outputs
-            HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_out, 0, 1, n_out, s->d_film_table, s->stream));
+            HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_out, 0, 1, n_out, s->film_table.get(), s->stream));
         HIP_TRY(hipEventRecord(s->ev1, s->stream));
         return RT_OK;
     };

@@ -127,25 +127,19 @@ static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float 
     const bool same = s->wf_rel_gen == s->geo_generation && std::memcmp(pos, s->wf_rel_pos, 12) == 0;
     if (!same) {
         s->wf_rel_gen = 0;
-        if (s->wf_rel_bytes < bytes) {
-            if (s->wf_rel_nodes)
-                (void)hipFree(s->wf_rel_nodes); // (the stream is idle between calls, and within a call the copy's size does not change)
-            s->wf_rel_nodes = nullptr, s->wf_rel_tris = nullptr, s->wf_rel_bytes = 0;
-            void *q = nullptr;
-            if (hipMalloc(&q, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                return hipSuccess;
-            }
-            s->wf_rel_nodes = static_cast<DevNode *>(q);
-            s->wf_rel_bytes = bytes;
+        // (the stream is idle between calls, and within a call the copy's size does not change: growing frees nothing that is in use)
+        if (s->wf_rel.reserve(bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return hipSuccess;
         }
-        s->wf_rel_tris = reinterpret_cast<DevTri *>(reinterpret_cast<char *>(s->wf_rel_nodes) + node_bytes); // 64-byte records first: 16-byte aligned
-        if (hipError_t e = rt::launch_camera_relative(B, n_nodes, cam_pos, s->wf_rel_nodes, s->wf_rel_tris, s->num_cus, s->stream); e != hipSuccess)
+        DevNode *rel_nodes = reinterpret_cast<DevNode *>(s->wf_rel.get());
+        s->wf_rel_tris = reinterpret_cast<DevTri *>(s->wf_rel.get() + node_bytes); // 64-byte records first: 16-byte aligned
+        if (hipError_t e = rt::launch_camera_relative(B, n_nodes, cam_pos, rel_nodes, s->wf_rel_tris, s->num_cus, s->stream); e != hipSuccess)
             return e;
         std::memcpy(s->wf_rel_pos, pos, 12);
         s->wf_rel_gen = s->geo_generation;
     }
-    W.rel_nodes = s->wf_rel_nodes;
+    W.rel_nodes = reinterpret_cast<DevNode *>(s->wf_rel.get());
     W.rel_tris = s->wf_rel_tris;
     return hipSuccess;
 }
@@ -214,8 +208,8 @@ int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch 
     if (table) {
         if (int rc = s->ensure_sensors(n_views); rc != RT_OK)
             return rc;
-        HIP_TRY(hipMemcpyAsync(s->d_sensors, table->data(), n_views * sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
-        W.sensors = s->d_sensors;
+        HIP_TRY(hipMemcpyAsync(s->sensors.get(), table->data(), n_views * sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
+        W.sensors = s->sensors.get();
     }
     const uint32_t n_passes = (uint32_t)((n_pixels + tile_pixels - 1) / tile_pixels) * ((samples + pass_spp - 1) / pass_spp);
     if (p->progress)
@@ -350,14 +344,14 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
         int rc = s->ensure_fb(fb_floats);
         if (rc != RT_OK)
             return rc;
-        d_fb = s->d_fb;
+        d_fb = s->fb.get();
     }
     uint8_t *d_rgb8 = nullptr;
     if (rgb8_out) {
         int rc = s->ensure_film(device_fb ? 0 : fb_floats);
         if (rc != RT_OK)
             return rc;
-        d_rgb8 = device_fb ? rgb8_out : s->d_rgb8;
+        d_rgb8 = device_fb ? rgb8_out : s->rgb8.get();
     }
     L.fb = d_fb;
     L.counter = s->d_counter;
@@ -439,7 +433,7 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
         }
     }
     if (rgb8_out && L.n_items > 0) // film on the device: this shard's pixels -> rgb8 (image.h:49-82)
-        HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_pix, L.shard_index, L.shard_count, block, s->d_film_table, s->stream));
+        HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_pix, L.shard_index, L.shard_count, block, s->film_table.get(), s->stream));
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
     return RT_OK;
     };
@@ -526,9 +520,9 @@ extern "C" int rt_film_rgb8(rt_scene *s, const float *rgb, size_t n_pixels, uint
         rc = s->ensure_film(n_pixels * 3);
     if (rc != RT_OK)
         return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_fb, rgb, n_pixels * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(rt::launch_film(s->d_fb, s->d_rgb8, (uint32_t)n_pixels, 0, 1, (uint32_t)n_pixels, s->d_film_table, s->stream));
-    HIP_TRY(hipMemcpyAsync(out_rgb8, s->d_rgb8, n_pixels * 3, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->fb.get(), rgb, n_pixels * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(rt::launch_film(s->fb.get(), s->rgb8.get(), (uint32_t)n_pixels, 0, 1, (uint32_t)n_pixels, s->film_table.get(), s->stream));
+    HIP_TRY(hipMemcpyAsync(out_rgb8, s->rgb8.get(), n_pixels * 3, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RT_OK;
 }

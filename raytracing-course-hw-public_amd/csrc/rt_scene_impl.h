@@ -13,20 +13,13 @@
 #include "../../include/rt_abi.h"
 #include "bvh_build.h"
 #include "rt_bvh_device.h"
+#include "rt_dev_mem.h"
 #include "rt_device_types.h"
 #include "rt_error.h"
 #include "rt_film.h"
 #include "rt_group.h"
 #include "rt_kernels.h"
 #include "wide_build.h"
-
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return rt::fail(e_ == hipErrorOutOfMemory ? RT_ERR_OOM : (e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP), \
-                            std::string(#expr) + ": " + hipGetErrorString(e_));                           \
-    } while (0)
 
 namespace rt {
 // wf_extend_packet (primary rays as coherent packets) pays off only while a wave's 64 rays stay together; its own census
@@ -66,10 +59,10 @@ struct PreparedScene {
 };
 
 // What the geometry half leaves on one device (rt_scene.cpp upload_geometry): the buffers it allocated, the two trees as the kernels
-// address them, and the build facts the queries report. `owned` / `light_owned` are freed by whoever holds the struct.
+// address them, and the build facts the queries report. The buffers die with the struct unless install_geometry hands them to the scene.
 struct GeometryOnDevice {
-    std::vector<void *> owned;       // scene tree, triangle records, shading records
-    std::vector<void *> light_owned; // light tree, its triangle records, DevLightAux
+    DevArena owned;       // scene tree, triangle records, shading records
+    DevArena light_owned; // light tree, its triangle records, DevLightAux
     DevBvh scene{}, lights{};
     const DevAttr *attrs = nullptr;
     const DevLightAux *light_aux = nullptr;
@@ -78,14 +71,6 @@ struct GeometryOnDevice {
     uint32_t wide_depth = 0;
     double wide_ms = 0, wide_cost = 0, build_ms = 0, build_upload_ms = 0;
     uint32_t dev_n_inner[2] = {0, 0};
-    void free_all() {
-        for (void *p : owned)
-            (void)hipFree(p);
-        for (void *p : light_owned)
-            (void)hipFree(p);
-        owned.clear();
-        light_owned.clear();
-    }
 };
 
 // The wide kernels' exponent arithmetic stays among normal floats while the scene's largest cell exponent (e_base + 15) lies in [-60, 44]
@@ -106,10 +91,10 @@ struct rt_scene {
     rt::EventPool ext_events; // (start, stop) per wf_extend launch of the current render; reused by every render
     DevScene dev{};
     rt_camera cam{};
-    std::vector<void *> owned;       // what lives as long as the scene: materials, textures, texels, tables, counters
-    std::vector<void *> geo_owned;   // the scene tree and its records ...
-    std::vector<void *> light_owned; // ... and the light tree's: freed when rt_update_geometry swaps new ones in
-    std::vector<void *> env_owned;   // the float environment of rt_set_environment (DevScene::env): texels and tables; empty without one
+    rt::DevArena owned;       // what lives as long as the scene: materials, textures, texels, tables, counters
+    rt::DevArena geo_owned;   // the scene tree and its records ...
+    rt::DevArena light_owned; // ... and the light tree's: freed when rt_update_geometry swaps new ones in
+    rt::DevArena env_owned;   // the float environment of rt_set_environment (DevScene::env): texels and tables; empty without one
     std::shared_ptr<const rt::PreparedScene> prep; // the host half of rt_create, shared by the replicas of a multi-GPU scene
     std::shared_ptr<const rt::PreparedGeometry> geo; // its geometry half: prep->geo until rt_update_geometry replaces it
     uint32_t live_accums = 0;  // accumulators of this scene (rt_accum_create* / rt_accum_destroy): their sums pin the geometry
@@ -123,80 +108,39 @@ struct rt_scene {
     uint32_t dev_n_inner[2] = {0, 0};
     double build_ms = 0, build_upload_ms = 0;
     double refit_ms = 0, refit_levels_ms = 0; // the last RT_UPDATE_REFIT: refit_wide_device in all, and its top-down level pass (rt_refit_times)
-    uint32_t *d_counter = nullptr;
+    uint32_t *d_counter = nullptr; // both of `owned`
     DevStats *d_stats = nullptr;
-    float *d_fb = nullptr;
-    size_t fb_capacity = 0; // floats
-    uint8_t *d_rgb8 = nullptr; // device film output (rt_render_rgb8 with a host destination, rt_film_rgb8)
-    size_t rgb8_capacity = 0;
-    rt::FilmTable *d_film_table = nullptr;
+    // Buffers grown on demand (rt::DevBuf: the content does not survive growth, a failed growth leaves them empty):
+    rt::DevBuf<float> fb;             // framebuffer staging, in floats
+    rt::DevBuf<uint8_t> rgb8;         // device film output (rt_render_rgb8 with a host destination, rt_film_rgb8)
+    rt::DevBuf<rt::FilmTable> film_table; // the verified threshold table (host/film.cpp), uploaded by the first ensure_film
+    rt::DevBuf<WfSensor> sensors;     // the camera table of a render's wavefront passes (WfLaunch::sensors: one record per view or sensor) / the one
+                                      // record of rt_sensor_rays
+    rt::DevBuf<uint8_t> rays;         // the device copy of a host ray buffer (rt_render_rays), in bytes
 
     int ensure_fb(size_t fb_floats) {
-        if (fb_capacity >= fb_floats)
-            return RT_OK;
-        if (d_fb)
-            (void)hipFree(d_fb);
-        d_fb = nullptr;
-        fb_capacity = 0;
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, fb_floats * sizeof(float)));
-        d_fb = static_cast<float *>(q);
-        fb_capacity = fb_floats;
+        HIP_TRY(fb.reserve(fb_floats));
         return RT_OK;
     }
-    // device film prerequisites: the verified threshold table (host/film.cpp) and, optionally, an rgb8 staging buffer
+    // device film prerequisites: the threshold table and, optionally, an rgb8 staging buffer
     int ensure_film(size_t rgb8_bytes) {
-        if (!d_film_table) {
+        if (!film_table.get()) {
             rt::FilmTable t{};
             if (!rt::film_table(t.thr, t.special))
                 return rt::fail(RT_ERR_UNSUPPORTED, "device film: the host libm's powf failed the monotonicity check; use rt_render + rt_tonemap_rgb8");
-            void *q = nullptr;
-            HIP_TRY(hipMalloc(&q, sizeof(t)));
-            d_film_table = static_cast<rt::FilmTable *>(q);
-            HIP_TRY(hipMemcpyAsync(d_film_table, &t, sizeof(t), hipMemcpyHostToDevice, stream));
+            HIP_TRY(film_table.reserve(1));
+            HIP_TRY(hipMemcpyAsync(film_table.get(), &t, sizeof(t), hipMemcpyHostToDevice, stream));
             HIP_TRY(hipStreamSynchronize(stream)); // `t` is a local
         }
-        if (rgb8_capacity < rgb8_bytes) {
-            if (d_rgb8)
-                (void)hipFree(d_rgb8);
-            d_rgb8 = nullptr;
-            rgb8_capacity = 0;
-            void *q = nullptr;
-            HIP_TRY(hipMalloc(&q, rgb8_bytes));
-            d_rgb8 = static_cast<uint8_t *>(q);
-            rgb8_capacity = rgb8_bytes;
-        }
+        HIP_TRY(rgb8.reserve(rgb8_bytes));
         return RT_OK;
     }
-    // the camera table of a render's wavefront passes (WfLaunch::sensors: one record per view or sensor) / the one record of rt_sensor_rays,
-    // grown on demand
-    WfSensor *d_sensors = nullptr;
-    uint32_t sensors_capacity = 0;
     int ensure_sensors(uint32_t n) {
-        if (sensors_capacity >= n)
-            return RT_OK;
-        if (d_sensors)
-            (void)hipFree(d_sensors);
-        d_sensors = nullptr;
-        sensors_capacity = 0;
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, (size_t)n * sizeof(WfSensor)));
-        d_sensors = static_cast<WfSensor *>(q);
-        sensors_capacity = n;
+        HIP_TRY(sensors.reserve(n));
         return RT_OK;
     }
-    // the device copy of a host ray buffer (rt_render_rays), grown on demand
-    void *d_rays = nullptr;
-    size_t rays_capacity = 0; // bytes
     int ensure_rays(size_t bytes) {
-        if (rays_capacity >= bytes)
-            return RT_OK;
-        if (d_rays)
-            (void)hipFree(d_rays);
-        d_rays = nullptr;
-        rays_capacity = 0;
-        HIP_TRY(hipMalloc(&d_rays, bytes));
-        rays_capacity = bytes;
+        HIP_TRY(rays.reserve(bytes));
         return RT_OK;
     }
     int num_cus = 0;
@@ -204,7 +148,7 @@ struct rt_scene {
     // wavefront pipeline workspace (rt_wavefront.hip), sized for wf_paths_cap paths / wf_pixels_cap pixels per pass
     uint64_t wf_paths_cap = 0, wf_pixels_cap = 0;
     uint32_t wf_depth_cap = 0;
-    std::vector<void *> wf_owned;
+    rt::DevArena wf_owned{16};
     WfPath *wf_paths[2] = {nullptr, nullptr};
     uint32_t *wf_stripes = nullptr;
     WfHit *wf_hits = nullptr;
@@ -225,26 +169,20 @@ struct rt_scene {
     // The camera-relative copy of the binary scene tree's records (WfLaunch::rel_nodes / rel_tris): part of the wavefront workspace, made by
     // launch_pass for the passes whose primary rays share one origin and kept while (camera position, tree) stay the same. `rel_gen` is the
     // geo_generation the copy was made of; every swap or in-place rewrite of the tree (install_geometry, a refit) moves geo_generation on.
-    DevNode *wf_rel_nodes = nullptr;
-    DevTri *wf_rel_tris = nullptr;
-    size_t wf_rel_bytes = 0;       // capacity of the one allocation behind both
+    rt::DevBuf<uint8_t> wf_rel;    // the one allocation behind both: node records first, then triangle records (bytes)
+    DevTri *wf_rel_tris = nullptr; // where the triangle records of the current copy begin
     uint64_t geo_generation = 1, wf_rel_gen = 0; // 0: no valid copy
     uint32_t wf_rel_pos[3] = {0, 0, 0}; // the camera position of the copy, as bits
 
     int ensure_wavefront(uint64_t paths, uint64_t pixels, uint32_t depth) {
         if (paths <= wf_paths_cap && pixels <= wf_pixels_cap && depth <= wf_depth_cap)
             return RT_OK;
-        for (void *p : wf_owned)
-            (void)hipFree(p);
-        wf_owned.clear();
+        wf_owned.reset();
         wf_paths_cap = wf_pixels_cap = 0;
         wf_depth_cap = 0;
         auto alloc = [&](size_t bytes, void **out) -> int {
-            *out = nullptr;
-            hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-            if (e != hipSuccess)
-                return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("wavefront workspace: ") + hipGetErrorString(e));
-            wf_owned.push_back(*out);
+            if (hipError_t e = wf_owned.alloc_bytes(out, bytes); e != hipSuccess)
+                return rt::hip_fail(e, "wavefront workspace");
             return RT_OK;
         };
         int rc;
@@ -275,24 +213,12 @@ struct rt_scene {
 
     // the per-path feature records of a feature accumulator's passes (WfFeat::rec, 32 B per path): allocated the first time such an
     // accumulator renders on this scene, and sized like the wavefront workspace (call after ensure_wavefront)
-    RtF4 *wf_feat = nullptr;
-    uint64_t wf_feat_cap = 0; // paths
+    rt::DevBuf<RtF4> wf_feat; // two records per path
     int ensure_features() {
-        if (wf_feat_cap >= wf_paths_cap)
-            return RT_OK;
-        if (wf_feat)
-            (void)hipFree(wf_feat);
-        wf_feat = nullptr;
-        wf_feat_cap = 0;
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, wf_paths_cap * 2 * sizeof(RtF4));
-        if (e != hipSuccess)
-            return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("feature records: ") + hipGetErrorString(e));
-        wf_feat = static_cast<RtF4 *>(q);
-        wf_feat_cap = wf_paths_cap;
+        if (hipError_t e = wf_feat.reserve(wf_paths_cap * 2); e != hipSuccess)
+            return rt::hip_fail(e, "feature records");
         return RT_OK;
     }
-
     // the workspace half of a WfLaunch (after ensure_wavefront): queues, hit records, counters, stack workspace, sort buffers
     void wf_bind(WfLaunch &W) {
         W.paths_in = wf_paths[0];
@@ -326,30 +252,12 @@ struct rt_scene {
             (void)hipEventDestroy(ev);
         for (hipEvent_t ev : pass_events)
             (void)hipEventDestroy(ev);
-        for (void *p : wf_owned)
-            (void)hipFree(p);
-        for (void *p : owned)
-            (void)hipFree(p);
-        for (void *p : geo_owned)
-            (void)hipFree(p);
-        for (void *p : light_owned)
-            (void)hipFree(p);
-        for (void *p : env_owned)
-            (void)hipFree(p);
-        if (wf_feat)
-            (void)hipFree(wf_feat);
-        if (wf_rel_nodes)
-            (void)hipFree(wf_rel_nodes);
-        if (d_fb)
-            (void)hipFree(d_fb);
-        if (d_rgb8)
-            (void)hipFree(d_rgb8);
-        if (d_rays)
-            (void)hipFree(d_rays);
-        if (d_sensors)
-            (void)hipFree(d_sensors);
-        if (d_film_table)
-            (void)hipFree(d_film_table);
+        // Device memory goes before the stream it was used on, as it always has: the members' own destructors run after this body, that is
+        // after hipStreamDestroy (an owner not named here is still freed then, with `device` current). Nothing is in flight: every entry
+        // point returns with the stream synchronised. In a group's handle all of them are empty.
+        for (rt::DevArena *a : {&wf_owned, &owned, &geo_owned, &light_owned, &env_owned})
+            a->reset();
+        wf_feat.reset(), wf_rel.reset(), fb.reset(), rgb8.reset(), rays.reset(), sensors.reset(), film_table.reset();
         ext_events.destroy();
         if (ev0)
             (void)hipEventDestroy(ev0);

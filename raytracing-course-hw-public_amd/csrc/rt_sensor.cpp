@@ -136,11 +136,11 @@ extern "C" int rt_sensor_rays(rt_scene *s, const rt_sensor *sensor, uint32_t wid
     if (!device_out) {
         if (int rc = s->ensure_rays((size_t)n * sizeof(rt_ray)); rc != RT_OK)
             return rc;
-        d_out = s->d_rays;
+        d_out = s->rays.get();
     }
     auto queue = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(s->d_sensors, &rec, sizeof(rec), hipMemcpyHostToDevice, s->stream)); // `rec` outlives the stream sync below
-        HIP_TRY(rt::launch_sensor_rays(s->d_sensors, width, height, first_pixel, first_sample, samples, (uint32_t)n, d_out, s->num_cus, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->sensors.get(), &rec, sizeof(rec), hipMemcpyHostToDevice, s->stream)); // `rec` outlives the stream sync below
+        HIP_TRY(rt::launch_sensor_rays(s->sensors.get(), width, height, first_pixel, first_sample, samples, (uint32_t)n, d_out, s->num_cus, s->stream));
         if (!device_out)
             HIP_TRY(hipMemcpyAsync(rays_out, d_out, (size_t)n * sizeof(rt_ray), hipMemcpyDeviceToHost, s->stream));
         return RT_OK;

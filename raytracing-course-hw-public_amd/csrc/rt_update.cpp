@@ -101,29 +101,18 @@ std::vector<uint8_t> emissive_materials(const rt::PreparedScene &P) {
     return em;
 }
 
-void free_list(std::vector<void *> &v) {
-    for (void *p : v)
-        (void)hipFree(p);
-    v.clear();
-}
-
 // The new buffers from a prepared geometry half, beside the live ones; then swap and free. `arrays`: see rt::upload_geometry.
 int rebuild_from(rt_scene *s, const rt_scene_desc &d, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::DeviceArrays *arrays, const std::string &fn) {
     const rt::PreparedScene &P = *s->prep;
-    // a refusal below leaves the scene as it was
+    // a refusal below leaves the scene as it was (`g` frees what was built)
     rt::GeometryOnDevice g;
     int rc = rt::upload_geometry(s, &d, P, *G, g, arrays);
     hipError_t se = rc == RT_OK ? hipDeviceSynchronize() : hipSuccess; // uploads went through the null stream
     if (rc == RT_OK && se != hipSuccess)
         rc = rt::fail(RT_ERR_HIP, fn + ": " + hipGetErrorString(se));
-    if (rc != RT_OK) {
-        g.free_all();
+    if (rc != RT_OK)
         return rc;
-    }
-    std::vector<void *> old_geo = std::move(s->geo_owned), old_light = std::move(s->light_owned);
-    rt::install_geometry(s, g);
-    free_list(old_geo);
-    free_list(old_light);
+    rt::install_geometry(s, g); // swaps, then frees the old buffers
     s->geo = G;
     s->refitted = false;
     return RT_OK;
@@ -137,7 +126,7 @@ int rebuild(rt_scene *s, const rt_scene_desc &d, const std::string &fn) {
 }
 
 // The refit proper, from arrays on the device and the light half prepared on the host: `in` has the five arrays and the bounds of their
-// vertices, `G` the light tree and its records. Frees nothing of `in`.
+// vertices, `G` the light tree and its records.
 int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::RefitInput &in, const std::string &fn);
 
 int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
@@ -151,11 +140,7 @@ int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
     rt::RefitInput in;
     const char *what = "";
     if (hipError_t e = rt::refit_upload(u, s->stream, &in, &what); e != hipSuccess)
-        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_update_geometry: ") + what + ": " + hipGetErrorString(e));
-    struct FreeInput {
-        rt::RefitInput &in;
-        ~FreeInput() { in.free_all(); }
-    } free_input{in};
+        return rt::hip_fail(e, std::string("rt_update_geometry: ") + what);
     return refit_from(s, G, in, FN_HOST);
 }
 
@@ -172,8 +157,7 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
             if (!bytes)
                 return RT_OK;
             void *p = nullptr;
-            HIP_TRY(hipMalloc(&p, bytes));
-            lg.light_owned.push_back(p);
+            HIP_TRY(lg.light_owned.alloc_bytes(&p, bytes));
             HIP_TRY(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s->stream));
             *dst = p;
             return RT_OK;
@@ -188,8 +172,7 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
         return RT_OK;
     };
     if (int rc = upload_lights(); rc != RT_OK) {
-        (void)hipStreamSynchronize(s->stream);
-        lg.free_all();
+        (void)hipStreamSynchronize(s->stream); // before `lg` frees what the copies write
         return rc;
     }
     // ---- device, part 2: records and nodes in place (its scratch is allocated first: RT_ERR_OOM still leaves the scene as it was)
@@ -199,8 +182,7 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
                                              D.scene.n_units, D.scene.n_wide, grid, s->stream, &what, &levels_ms);
         e != hipSuccess) {
         (void)hipStreamSynchronize(s->stream);
-        lg.free_all();
-        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, fn + ": " + what + ": " + hipGetErrorString(e));
+        return rt::hip_fail(e, fn + ": " + what);
     }
     // ---- host: what the launches read of the tree besides the blob
     const rt::FlatBvh &f = G->flat[1];
@@ -216,8 +198,7 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
     L.lds_inner = rt::light_lds_inner(f);
     D.light_aux = lg.light_aux;
     s->dev_n_inner[1] = (uint32_t)f.nodes.size();
-    free_list(s->light_owned);
-    s->light_owned = std::move(lg.light_owned);
+    s->light_owned = std::move(lg.light_owned); // frees the old light buffers
     D.scene.grid = grid;
     for (int k = 0; k < 3; ++k)
         rt::sort_bounds_axis(in.lo[k], in.hi[k], D.bounds_lo[k], D.bounds_inv[k]);
@@ -332,7 +313,7 @@ extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *
     const char *what = "";
     const bool want_lights = !staged && check_mode_ok(s, u); // (a call check_mode is about to refuse needs no light list)
     if (hipError_t e = rt::scan_update_device(arrays, emissive_materials(P), want_lights, s->stream, &scan, &what); e != hipSuccess)
-        return rt::fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, FN_DEVICE + ": " + what + ": " + hipGetErrorString(e));
+        return rt::hip_fail(e, FN_DEVICE + ": " + what);
     if (scan.bad_material)
         return refuse_material(FN_DEVICE);
     if (scan.first_non_finite != RT_NONE)
@@ -348,7 +329,7 @@ extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *
         G->dev_build = dev_build, G->wide_build = wide_build; // as prepare_geometry sets them
         if ((rc = lights_from_scan(scan, n, *G)) != RT_OK)
             return rc;
-        if (refit) { // the caller's arrays are the refit's input: nothing is allocated or copied for them
+        if (refit) { // the caller's arrays are the refit's input: nothing is allocated or copied for them, and `in` owns nothing
             rt::RefitInput in;
             in.pos = const_cast<float *>(u->positions), in.nrm = const_cast<float *>(u->normals), in.uv = const_cast<float *>(u->texcoords);
             in.tan = const_cast<float *>(u->tangents), in.mat = const_cast<uint32_t *>(u->material_ids), in.n = n;

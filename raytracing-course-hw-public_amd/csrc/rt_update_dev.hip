@@ -140,35 +140,9 @@ __global__ __launch_bounds__(256) void k_update_compact(const ScanArgs A) {
     }
 }
 
-struct Scratch { // device allocations of a scan, freed on every return path
-    std::vector<void *> ptrs;
-    template <class T> hipError_t alloc(T **p, size_t count) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess)
-            ptrs.push_back(q);
-        *p = static_cast<T *>(q);
-        return e;
-    }
-    ~Scratch() {
-        for (void *p : ptrs)
-            (void)hipFree(p);
-    }
-};
-
 } // namespace
 
 namespace rt {
-
-#define SCAN_TRY(expr)             \
-    do {                           \
-        hipError_t e_ = (expr);    \
-        if (e_ != hipSuccess) {    \
-            if (err)               \
-                *err = #expr;      \
-            return e_;             \
-        }                          \
-    } while (0)
 
 hipError_t scan_update_device(const DeviceArrays &in, const std::vector<uint8_t> &emissive, bool want_lights, hipStream_t stream, UpdateScan *out, const char **err) {
     *out = UpdateScan{};
@@ -180,8 +154,8 @@ hipError_t scan_update_device(const DeviceArrays &in, const std::vector<uint8_t>
         hipStream_t s;
         ~Drain() { (void)hipStreamSynchronize(s); }
     };
-    Scratch tmp;
-    Drain drain{stream};
+    DevArena tmp; // scratch of the scan
+    Drain drain{stream}; // after `tmp`: it runs first
     ScanArgs A{};
     A.pos = in.pos, A.mat = in.mat, A.n = n;
     A.n_mats = (uint32_t)emissive.size();
@@ -190,25 +164,25 @@ hipError_t scan_update_device(const DeviceArrays &in, const std::vector<uint8_t>
     uint32_t *chunk_first;
     char *scan_tmp;
     size_t scan_bytes = 0;
-    SCAN_TRY(tmp.alloc(&d_em, emissive.size()));
-    SCAN_TRY(tmp.alloc(&A.words, (size_t)8));
-    SCAN_TRY(tmp.alloc(&A.chunk_lights, (size_t)A.n_chunks));
-    SCAN_TRY(tmp.alloc(&chunk_first, (size_t)A.n_chunks));
-    SCAN_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, A.chunk_lights, chunk_first, 0u, (size_t)A.n_chunks, rocprim::plus<uint32_t>(), stream));
-    SCAN_TRY(tmp.alloc(&scan_tmp, scan_bytes));
+    HIP_TRY_ERR(tmp.alloc(&d_em, emissive.size()));
+    HIP_TRY_ERR(tmp.alloc(&A.words, (size_t)8));
+    HIP_TRY_ERR(tmp.alloc(&A.chunk_lights, (size_t)A.n_chunks));
+    HIP_TRY_ERR(tmp.alloc(&chunk_first, (size_t)A.n_chunks));
+    HIP_TRY_ERR(rocprim::exclusive_scan(nullptr, scan_bytes, A.chunk_lights, chunk_first, 0u, (size_t)A.n_chunks, rocprim::plus<uint32_t>(), stream));
+    HIP_TRY_ERR(tmp.alloc(&scan_tmp, scan_bytes));
     A.emissive = d_em;
     static const uint32_t init_words[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, RT_NONE, 0u};
-    SCAN_TRY(hipMemcpyAsync(A.words, init_words, sizeof(init_words), hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(A.words, init_words, sizeof(init_words), hipMemcpyHostToDevice, stream));
     if (!emissive.empty())
-        SCAN_TRY(hipMemcpyAsync(d_em, emissive.data(), emissive.size(), hipMemcpyHostToDevice, stream)); // (the caller's vector outlives the call)
+        HIP_TRY_ERR(hipMemcpyAsync(d_em, emissive.data(), emissive.size(), hipMemcpyHostToDevice, stream)); // (the caller's vector outlives the call)
     const dim3 grid(std::min<uint32_t>(A.n_chunks, 256u * 16u));
-    SCAN_TRY(RT_LAUNCH_CHECKED(k_update_scan, grid, dim3(CHUNK), 0, stream, A));
-    SCAN_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, A.chunk_lights, chunk_first, 0u, (size_t)A.n_chunks, rocprim::plus<uint32_t>(), stream));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_update_scan, grid, dim3(CHUNK), 0, stream, A));
+    HIP_TRY_ERR(rocprim::exclusive_scan(scan_tmp, scan_bytes, A.chunk_lights, chunk_first, 0u, (size_t)A.n_chunks, rocprim::plus<uint32_t>(), stream));
     uint32_t h_words[8], h_last[2];
-    SCAN_TRY(hipMemcpyAsync(h_words, A.words, sizeof(h_words), hipMemcpyDeviceToHost, stream));
-    SCAN_TRY(hipMemcpyAsync(&h_last[0], chunk_first + (A.n_chunks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SCAN_TRY(hipMemcpyAsync(&h_last[1], A.chunk_lights + (A.n_chunks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SCAN_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(hipMemcpyAsync(h_words, A.words, sizeof(h_words), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(&h_last[0], chunk_first + (A.n_chunks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(&h_last[1], A.chunk_lights + (A.n_chunks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream));
     out->bad_material = h_words[7] != 0u;
     out->first_non_finite = h_words[6];
     for (int c = 0; c < 3; ++c) {
@@ -225,14 +199,14 @@ hipError_t scan_update_device(const DeviceArrays &in, const std::vector<uint8_t>
     }
     A.chunk_first = chunk_first;
     A.n_lights = (uint32_t)n_lights;
-    SCAN_TRY(tmp.alloc(&A.out_prim, (size_t)n_lights));
-    SCAN_TRY(tmp.alloc(&A.out_pos, 9ull * n_lights));
+    HIP_TRY_ERR(tmp.alloc(&A.out_prim, (size_t)n_lights));
+    HIP_TRY_ERR(tmp.alloc(&A.out_pos, 9ull * n_lights));
     out->light_prims.resize(n_lights);
     out->light_pos.resize(9ull * n_lights);
-    SCAN_TRY(RT_LAUNCH_CHECKED(k_update_compact, grid, dim3(CHUNK), 0, stream, A));
-    SCAN_TRY(hipMemcpyAsync(out->light_prims.data(), A.out_prim, 4ull * n_lights, hipMemcpyDeviceToHost, stream));
-    SCAN_TRY(hipMemcpyAsync(out->light_pos.data(), A.out_pos, 36ull * n_lights, hipMemcpyDeviceToHost, stream));
-    SCAN_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_update_compact, grid, dim3(CHUNK), 0, stream, A));
+    HIP_TRY_ERR(hipMemcpyAsync(out->light_prims.data(), A.out_prim, 4ull * n_lights, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(out->light_pos.data(), A.out_pos, 36ull * n_lights, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream));
     return hipSuccess;
 }
 

@@ -15,6 +15,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "rt_dev_mem.h"
 #include "rt_kernels.h"
 #include "rt_wide_pack.h"
 #include "wide_grid.h"
@@ -97,67 +98,43 @@ __global__ __launch_bounds__(256) void k_pack_write(const PackArgs A) {
 
 namespace rt {
 
-#define PACK_TRY(expr)                 \
-    do {                               \
-        hipError_t e_ = (expr);        \
-        if (e_ != hipSuccess) {        \
-            if (err)                   \
-                *err = #expr;          \
-            for (void *q_ : scratch)   \
-                (void)hipFree(q_);     \
-            if (blob)                  \
-                (void)hipFree(blob);   \
-            return e_;                 \
-        }                              \
-    } while (0)
-
 hipError_t pack_wide_device(const WideNode *d_nodes, uint32_t n_wide, const DevTri *d_tris, const WideGrid &grid, hipStream_t stream, uint4_pod **blob_out,
                             uint32_t *n_units_out, const char **err) {
     *blob_out = nullptr;
     *n_units_out = 0;
     if (n_wide == 0)
         return hipSuccess;
-    std::vector<void *> scratch;
+    DevArena scratch{16}; // everything allocated here, the blob included until it is handed out: freed on every return path
     void *blob = nullptr;
-    auto alloc = [&](void **p, size_t bytes) {
-        hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-        if (e == hipSuccess)
-            scratch.push_back(*p);
-        return e;
-    };
     PackArgs A{};
     A.nodes = d_nodes, A.n = n_wide, A.tris = d_tris, A.grid = grid;
-    PACK_TRY(alloc((void **)&A.units, 4ull * n_wide));
-    PACK_TRY(alloc((void **)&A.base, 4ull * n_wide));
-    PACK_TRY(alloc((void **)&A.pos, 4ull * n_wide));
+    HIP_TRY_ERR(scratch.alloc_bytes(&A.units, 4ull * n_wide));
+    HIP_TRY_ERR(scratch.alloc_bytes(&A.base, 4ull * n_wide));
+    HIP_TRY_ERR(scratch.alloc_bytes(&A.pos, 4ull * n_wide));
     const dim3 grid_dim((n_wide + 255u) / 256u), block(256);
-    PACK_TRY(RT_LAUNCH_CHECKED(k_pack_sizes, grid_dim, block, 0, stream, A));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_pack_sizes, grid_dim, block, 0, stream, A));
     size_t scan_bytes = 0;
-    PACK_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, A.units, A.base, 0u, (size_t)n_wide, rocprim::plus<uint32_t>(), stream));
+    HIP_TRY_ERR(rocprim::exclusive_scan(nullptr, scan_bytes, A.units, A.base, 0u, (size_t)n_wide, rocprim::plus<uint32_t>(), stream));
     void *scan_tmp = nullptr;
-    PACK_TRY(alloc(&scan_tmp, scan_bytes));
-    PACK_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, A.units, A.base, 0u, (size_t)n_wide, rocprim::plus<uint32_t>(), stream));
+    HIP_TRY_ERR(scratch.alloc_bytes(&scan_tmp, scan_bytes));
+    HIP_TRY_ERR(rocprim::exclusive_scan(scan_tmp, scan_bytes, A.units, A.base, 0u, (size_t)n_wide, rocprim::plus<uint32_t>(), stream));
     uint32_t last[2] = {0u, 0u};
-    PACK_TRY(hipMemcpyAsync(&last[0], A.base + (n_wide - 1u), 4, hipMemcpyDeviceToHost, stream));
-    PACK_TRY(hipMemcpyAsync(&last[1], A.units + (n_wide - 1u), 4, hipMemcpyDeviceToHost, stream));
-    PACK_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(hipMemcpyAsync(&last[0], A.base + (n_wide - 1u), 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(&last[1], A.units + (n_wide - 1u), 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream));
     const uint64_t n_units = (uint64_t)RT_WIDE_NODE_UNITS + last[0] + last[1];
     if (n_units >= 0xFFFFFFF0ull) { // 64 GB of blob: beyond the 32-bit unit index
         if (err)
             *err = "wide blob exceeds 2^32 units";
-        for (void *q : scratch)
-            (void)hipFree(q);
         return hipErrorOutOfMemory;
     }
-    PACK_TRY(hipMalloc(&blob, n_units * 16ull));
+    HIP_TRY_ERR(scratch.alloc_bytes(&blob, n_units * 16ull));
     A.blob = static_cast<uint4 *>(blob);
-    PACK_TRY(hipMemsetAsync(blob, 0, n_units * 16ull, stream)); // the padding units between groups
-    PACK_TRY(RT_LAUNCH_CHECKED(k_pack_positions, grid_dim, block, 0, stream, A));
-    PACK_TRY(RT_LAUNCH_CHECKED(k_pack_write, grid_dim, block, 0, stream, A));
-    PACK_TRY(hipStreamSynchronize(stream));
-    for (void *q : scratch)
-        (void)hipFree(q);
-    *blob_out = static_cast<uint4_pod *>(blob);
+    HIP_TRY_ERR(hipMemsetAsync(blob, 0, n_units * 16ull, stream)); // the padding units between groups
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_pack_positions, grid_dim, block, 0, stream, A));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_pack_write, grid_dim, block, 0, stream, A));
+    HIP_TRY_ERR(hipStreamSynchronize(stream));
+    *blob_out = static_cast<uint4_pod *>(scratch.release(blob)); // the caller's from here on
     *n_units_out = (uint32_t)n_units;
     return hipSuccess;
 }

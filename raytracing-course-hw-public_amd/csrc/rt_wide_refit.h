@@ -3,21 +3,22 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/rt_abi.h"
+#include "rt_dev_mem.h"
 #include "rt_device_types.h"
 
 namespace rt {
 
 // The raw per-triangle arrays on the device (as rt_scene_desc / rt_geometry_update name them) and the bounds of all their vertices.
 struct RefitInput {
+    DevArena owned; // refit_upload's allocations; empty where the arrays are the caller's (rt_update_geometry_device): then nothing is freed
     float *pos = nullptr, *nrm = nullptr, *uv = nullptr, *tan = nullptr;
     uint32_t *mat = nullptr;
     uint32_t *bounds = nullptr; // k_bounds' words
     uint32_t n = 0;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    void free_all();
 };
 // Step 1, which writes nothing a render kernel reads: uploads the five arrays of `upd` and reduces the vertex bounds (blocking). The caller
-// derives the new WideGrid from lo / hi and may still refuse the update. On failure everything is freed.
+// derives the new WideGrid from lo / hi and may still refuse the update. The arrays live as long as `in` (in->owned).
 hipError_t refit_upload(const rt_geometry_update *upd, hipStream_t stream, RefitInput *in, const char **err);
 
 // Step 2: rewrites DevTri[k] / DevAttr[k] of every record for the triangle it names (DevTri::prim), then every node of the blob bottom-up, level

@@ -199,45 +199,9 @@ __global__ __launch_bounds__(64) void k_refit_nodes(const RefitArgs A) {
     }
 }
 
-struct Scratch { // device allocations of a refit, freed on every return path
-    std::vector<void *> ptrs;
-    template <class T> hipError_t alloc(T **p, size_t count) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess)
-            ptrs.push_back(q);
-        *p = static_cast<T *>(q);
-        return e;
-    }
-    ~Scratch() {
-        for (void *p : ptrs)
-            (void)hipFree(p);
-    }
-};
-
 } // namespace
 
 namespace rt {
-
-#define REFIT_TRY(expr)            \
-    do {                           \
-        hipError_t e_ = (expr);    \
-        if (e_ != hipSuccess) {    \
-            if (err)               \
-                *err = #expr;      \
-            return e_;             \
-        }                          \
-    } while (0)
-
-void RefitInput::free_all() {
-    void *all[6] = {pos, nrm, uv, tan, mat, bounds};
-    for (void *p : all)
-        if (p)
-            (void)hipFree(p);
-    pos = nrm = uv = tan = nullptr;
-    mat = nullptr;
-    bounds = nullptr;
-}
 
 hipError_t refit_upload(const rt_geometry_update *upd, hipStream_t stream, RefitInput *in, const char **err) {
     const uint32_t n = upd->n_triangles;
@@ -245,38 +209,29 @@ hipError_t refit_upload(const rt_geometry_update *upd, hipStream_t stream, Refit
     in->n = n;
     if (n == 0)
         return hipSuccess;
-    struct Guard {
-        RefitInput *in;
-        bool keep = false;
-        ~Guard() {
-            if (!keep)
-                in->free_all();
-        }
-    } guard{in};
-    REFIT_TRY(hipMalloc((void **)&in->pos, 36ull * n));
-    REFIT_TRY(hipMalloc((void **)&in->nrm, 36ull * n));
-    REFIT_TRY(hipMalloc((void **)&in->tan, 36ull * n));
-    REFIT_TRY(hipMalloc((void **)&in->uv, 24ull * n));
-    REFIT_TRY(hipMalloc((void **)&in->mat, 4ull * n));
-    REFIT_TRY(hipMalloc((void **)&in->bounds, 8 * sizeof(uint32_t)));
+    HIP_TRY_ERR(in->owned.alloc_bytes(&in->pos, 36ull * n));
+    HIP_TRY_ERR(in->owned.alloc_bytes(&in->nrm, 36ull * n));
+    HIP_TRY_ERR(in->owned.alloc_bytes(&in->tan, 36ull * n));
+    HIP_TRY_ERR(in->owned.alloc_bytes(&in->uv, 24ull * n));
+    HIP_TRY_ERR(in->owned.alloc_bytes(&in->mat, 4ull * n));
+    HIP_TRY_ERR(in->owned.alloc_bytes(&in->bounds, 8 * sizeof(uint32_t)));
     const uint32_t init_bounds[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-    REFIT_TRY(hipMemcpyAsync(in->pos, upd->positions, 36ull * n, hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMemcpyAsync(in->nrm, upd->normals, 36ull * n, hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMemcpyAsync(in->tan, upd->tangents, 36ull * n, hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMemcpyAsync(in->uv, upd->texcoords, 24ull * n, hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMemcpyAsync(in->mat, upd->material_ids, 4ull * n, hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMemcpyAsync(in->bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipStreamSynchronize(stream)); // `init_bounds` is a local
+    HIP_TRY_ERR(hipMemcpyAsync(in->pos, upd->positions, 36ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(in->nrm, upd->normals, 36ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(in->tan, upd->tangents, 36ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(in->uv, upd->texcoords, 24ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(in->mat, upd->material_ids, 4ull * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(in->bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream)); // `init_bounds` is a local
     const int blocks = (int)std::min<uint64_t>(((uint64_t)n + 255) / 256, 256u * 16u);
-    REFIT_TRY(RT_LAUNCH_CHECKED(k_bounds, dim3(blocks), dim3(256), 0, stream, in->pos, n, in->bounds));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_bounds, dim3(blocks), dim3(256), 0, stream, in->pos, n, in->bounds));
     uint32_t h_bounds[8];
-    REFIT_TRY(hipMemcpyAsync(h_bounds, in->bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, stream));
-    REFIT_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(hipMemcpyAsync(h_bounds, in->bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream));
     for (int c = 0; c < 3; ++c) {
         in->lo[c] = dec_f(h_bounds[c]);
         in->hi[c] = dec_f(h_bounds[3 + c]);
     }
-    guard.keep = true;
     return hipSuccess;
 }
 
@@ -286,31 +241,31 @@ hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs,
         *levels_ms = 0;
     if (n_tris == 0 || n_wide == 0)
         return hipSuccess;
-    Scratch tmp;
+    DevArena tmp; // scratch of the refit, freed on every return path
     RefitArgs A{};
     A.pos = in.pos, A.nrm = in.nrm, A.tan = in.tan, A.uv = in.uv, A.mat = in.mat;
     A.tris = tris, A.attrs = attrs, A.n_tris = n_tris;
     A.blob = reinterpret_cast<uint4 *>(blob), A.n_units = n_units, A.n_wide = n_wide;
     A.grid = grid;
     // every allocation comes before the first write to anything the render kernels read
-    REFIT_TRY(tmp.alloc(&A.tri_box, 6ull * n_tris));
-    REFIT_TRY(tmp.alloc(&A.node_box, 6ull * n_wide));
-    REFIT_TRY(tmp.alloc(&A.node_unit, (size_t)n_wide));
-    REFIT_TRY(tmp.alloc(&A.child_first, (size_t)n_wide));
-    REFIT_TRY(tmp.alloc(&A.counters, (size_t)2));
+    HIP_TRY_ERR(tmp.alloc(&A.tri_box, 6ull * n_tris));
+    HIP_TRY_ERR(tmp.alloc(&A.node_box, 6ull * n_wide));
+    HIP_TRY_ERR(tmp.alloc(&A.node_unit, (size_t)n_wide));
+    HIP_TRY_ERR(tmp.alloc(&A.child_first, (size_t)n_wide));
+    HIP_TRY_ERR(tmp.alloc(&A.counters, (size_t)2));
     const uint32_t init[3] = {1u, 0u, 0u}; // id 0 = the root, at unit 0
-    REFIT_TRY(hipMemcpyAsync(A.counters, init, 8, hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMemcpyAsync(A.node_unit, init + 2, 4, hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipStreamSynchronize(stream)); // `init` is a local
+    HIP_TRY_ERR(hipMemcpyAsync(A.counters, init, 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipMemcpyAsync(A.node_unit, init + 2, 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream)); // `init` is a local
     // ---- levels, top down (reads the blob only)
     const auto t_levels = std::chrono::steady_clock::now();
     std::vector<uint32_t> level_first{0u}, level_count{1u};
     for (;;) {
         A.first = level_first.back(), A.count = level_count.back();
-        REFIT_TRY(RT_LAUNCH_CHECKED(k_refit_level, dim3((A.count + 255u) / 256u), dim3(256), 0, stream, A));
+        HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_refit_level, dim3((A.count + 255u) / 256u), dim3(256), 0, stream, A));
         uint32_t h[2];
-        REFIT_TRY(hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, stream));
-        REFIT_TRY(hipStreamSynchronize(stream));
+        HIP_TRY_ERR(hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, stream));
+        HIP_TRY_ERR(hipStreamSynchronize(stream));
         const uint32_t end = A.first + A.count;
         if (h[1] != 0u || h[0] > n_wide || h[0] < end || level_first.size() > 4096u) {
             if (err)
@@ -330,14 +285,14 @@ hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs,
     if (levels_ms)
         *levels_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_levels).count();
     // ---- records, then nodes bottom up
-    REFIT_TRY(RT_LAUNCH_CHECKED(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, A));
+    HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, A));
     for (size_t l = level_first.size(); l-- > 0;) {
         A.first = level_first[l], A.count = level_count[l];
-        REFIT_TRY(RT_LAUNCH_CHECKED(k_refit_nodes, dim3((A.count + 63u) / 64u), dim3(64), 0, stream, A));
+        HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_refit_nodes, dim3((A.count + 63u) / 64u), dim3(64), 0, stream, A));
     }
     uint32_t h[2];
-    REFIT_TRY(hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, stream));
-    REFIT_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_ERR(hipStreamSynchronize(stream));
     if (h[1] != 0u) {
         if (err)
             *err = "wide refit: the packed tree is inconsistent";

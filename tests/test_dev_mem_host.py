@@ -1,0 +1,43 @@
+"""csrc/rt_dev_mem.h on the CPU: the owners of device memory (rt::DevArena, rt::DevBuf) and the two try macros, run against a stub allocator
+under the address and undefined-behaviour sanitizers. The failure paths they replace (a free on every return path of every builder) are run
+by no GPU test, since nothing there makes an allocation fail; here every allocation of a sequence fails in turn."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "raytracing-course-hw-public_amd", "csrc")
+MAIN = os.path.join(ROOT, "tests", "dev_mem_host_main.cpp")  # the stand-alone program: the stub runtime, the scenarios and their checks
+HIP_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")  # headers only: no HIP runtime is linked
+
+
+def test_owners_free_everything_on_every_path(tmp_path):
+    exe = str(tmp_path / "dev_mem_host")
+    subprocess.check_call(["g++", "-std=c++20", "-g", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", HIP_INCLUDE, "-I", CSRC,
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", MAIN, "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    print(r.stderr)
+    assert r.returncode == 0, r.stderr  # a failed CHECK, the stub's abort (double free, unknown pointer) or a sanitizer report
+    assert r.stderr == ""
+    lines = r.stdout.splitlines()
+    assert re.fullmatch(r"dev_mem ok: \d+ checks", lines[-1])
+    # one line per failing position of the six-allocation sequence, and one for none: the allocations before the failure, the failure, one
+    # free for each of them
+    seq = [l for l in lines if l.startswith("arena sequence")]
+    assert len(seq) == 7
+    for k, l in enumerate(seq):
+        calls = l.rsplit(" ", 1)[1]
+        assert calls == ("M" * k + "x" + "F" * k if k < 6 else "M" * 6 + "F" * 6), l
+
+
+def test_only_the_header_allocates_device_memory():
+    """The owners are the only callers of the allocator: a new call site elsewhere would bring back a hand-written free path."""
+    offenders = []
+    for dirpath, _, names in os.walk(CSRC):
+        for n in names:
+            if n.endswith((".cpp", ".hip", ".h")) and n != "rt_dev_mem.h":
+                text = open(os.path.join(dirpath, n), encoding="utf-8", errors="replace").read()
+                if re.search(r"\bhip(Malloc|Free)\(", text):
+                    offenders.append(n)
+    assert offenders == []
