@@ -49,7 +49,8 @@ extern "C" {
                                 rt_view / rt_render_views / rt_render_views_rgb8 were added, and after the rt_accum_* accumulators and
                                 rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were, and
                                 after rt_update_geometry and rt_ray / rt_render_rays / rt_render_rays_rgb8 were, and after
-                                rt_update_geometry_device and rt_refit_times were, and after rt_set_environment / rt_env_pdf / rt_env_sample were:
+                                rt_update_geometry_device and rt_refit_times were, and after rt_set_environment / rt_env_pdf / rt_env_sample were,
+                                and after rt_bake / rt_bake_rays / rt_lightmap_points were:
                                 new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
@@ -488,6 +489,85 @@ typedef struct rt_sensor {
 int rt_render_sensors(rt_scene *scene, const rt_params *params, const rt_sensor *sensors, uint32_t n_sensors, float *fb_rgb, rt_stats *stats);
 int rt_render_sensors_rgb8(rt_scene *scene, const rt_params *params, const rt_sensor *sensors, uint32_t n_sensors, uint8_t *rgb8, rt_stats *stats);
 int rt_sensor_rays(rt_scene *scene, const rt_sensor *sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t n_pixels, uint32_t first_sample, uint32_t samples, uint32_t flags, rt_ray *rays_out);
+
+/* Baking on the device (additive; RT_ABI_VERSION stays 4): irradiance at surface points, spherical-harmonic light probes and light-map
+ * texels. The first ray of every sample is made in the first stage of the wavefront pipeline from (seed, point.stream, sample), so a bake is
+ * reproducible the way an image is, and the samples are folded on the device; everything in between is rt_render's pipeline.
+ * The rule, operation by operation: IEEE binary32, evaluated as written, no contraction; vector expressions per component, left to right.
+ * Let K = params->samples. Sample s (0 <= s < K) of point j, with S = bake->first_sample + s (wraps mod 2^32), p = position, n = normal, both
+ * used as given:
+ *     rt_xoshiro_seed(&rng, params->seed, stream, S)
+ *     uniform_real(rng, 0, 1);  uniform_real(rng, 0, 1)                           made and discarded: the stream stands where a camera ray's stands
+ *     rt_xoshiro_seed(&dg, params->seed ^ 0xD6E8FEB86659FD93, stream, S)          a second generator: the path's own stream is not advanced
+ *     z = uniform_real(dg, -1, 1);  co_z = sqrtf(max(0, 1 - z*z))                 sphere_uniform (raytracer.h:94-105)
+ *     phi = uniform_real(dg, 0, 2 * PI_F);  (sn, cs) = rt_sincos_libm(phi)
+ *     v = (co_z*cs, co_z*sn, z)
+ *   IRRADIANCE    d = norm(n + v);  o = p + offset * n                            the reference's cosine lobe, as shade() samples it
+ *   SH9           d = v;  o = p                                                   normal and offset are not read
+ *     L = sanitize_nans(trace_ray(Ray{o, d}, ray_depth)) with `rng`, through the scene's own traversal (parity, RT_FLAG_GLOBAL_BEST, wide).
+ *   A degenerate ray (n + v = 0, a non-finite component) is traversed as rt_cast_rays_ex traverses it; no host pass validates positions or
+ *   normals.
+ * The fold: one owner per output float, samples in order s = 0, 1, ..., starting from +0.0, no float atomics.
+ *   IRRADIANCE    out[j][c], 3 floats per point:    E   = (sum_s L_s.c / (float)K) * PI_F
+ *   SH9           out[j][k][c], 27 floats per point: C_k = (sum_s (L_s.c * Y_k(d_s)) / (float)K) * (4.0f * PI_F), with d = (x, y, z):
+ *     Y0 = 0.282094792f            Y1 = 0.488602512f*y          Y2 = 0.488602512f*z
+ *     Y3 = 0.488602512f*x          Y4 = 1.092548431f*(x*y)      Y5 = 1.092548431f*(y*z)
+ *     Y6 = 0.315391565f*(3.0f*(z*z) - 1.0f)                     Y7 = 1.092548431f*(x*z)      Y8 = 0.546274215f*(x*x - y*y)
+ *   When the samples of a point are split over several passes (max_paths) the sums continue in pass order; between passes they stand in `out`.
+ * rt_bake_rays: the same device function writes the n_points * samples records rt_ray{o, d, stream, first_sample = S} of samples
+ *   [bake->first_sample, + samples): point-major, each point's samples adjacent. flags: 0 (points and rays_out are host buffers) or
+ *   RT_FLAG_DEVICE_FB (both are device buffers on the scene's GPU, 16-byte aligned, idle on entry).
+ * Contracts, bit for bit:
+ *   Bake equals rays: IRRADIANCE equals PI_F * the outputs of rt_render_rays (K = 1, G = samples, the same seed) over rt_bake_rays' records;
+ *     SH9 equals the fold above applied to the per-ray outputs (G = 1) of those records. With RT_FLAG_COUNTERS every event counter equals
+ *     rt_render_rays'.
+ *   Scheduling independence: max_paths, the sort mode, the packet mode and the neighbours of a point in the buffer change no bit.
+ * params: samples, seed, flags (RT_FLAG_COUNTERS | RT_FLAG_GLOBAL_BEST | RT_FLAG_DEVICE_FB), the tuning fields and progress are read; width
+ *   and height are not; rng_mode must be RT_RNG_DEVICE. RT_FLAG_DEVICE_FB: `points` and `out` are device pointers on the scene's GPU, idle on
+ *   entry; `points` must be 16-byte aligned, `out` 4-byte.
+ * RT_OK and nothing written: n_points == 0; a scene with ray_depth == 0.
+ * RT_ERR_INVALID_ARG: a NULL pointer with n_points > 0; an unknown kind; a non-zero reserved word of rt_bake_desc (and, for host points, of a
+ *   point: device points are not read back); a non-finite offset; samples == 0; samples or n_points >= 2^31 (rt_bake_rays: n_points * samples
+ *   >= 2^31); a misaligned device buffer; shard_count > 1; an unknown flag; a pass option rt_render refuses.
+ * RT_ERR_UNSUPPORTED: RT_RNG_REFERENCE; RT_FLAG_MEGAKERNEL; a multi-GPU scene. */
+typedef struct rt_bake_point {
+    float position[3];
+    float normal[3];   /* used as given (no normalisation) */
+    uint32_t stream;   /* takes the pixel index's place in rt_xoshiro_seed(seed, stream, sample) */
+    uint32_t reserved; /* 0 */
+} rt_bake_point;       /* 32 bytes */
+enum { RT_BAKE_IRRADIANCE = 0, RT_BAKE_SH9 = 1 };
+typedef struct rt_bake_desc {
+    uint32_t kind;         /* RT_BAKE_* */
+    uint32_t first_sample; /* sample index of every point's first sample */
+    float offset;          /* IRRADIANCE: the origin is lifted by offset * normal; finite */
+    uint32_t reserved[5];  /* 0 */
+} rt_bake_desc;            /* 32 bytes (a C identifier names the entry point or the record, not both) */
+int rt_bake(rt_scene *scene, const rt_params *params, const rt_bake_desc *bake, const rt_bake_point *points, uint32_t n_points, float *out, rt_stats *stats);
+int rt_bake_rays(rt_scene *scene, const rt_bake_desc *bake, uint64_t seed, const rt_bake_point *points, uint32_t n_points, uint32_t samples, uint32_t flags, rt_ray *rays_out);
+
+/* The texel centres of a light-map atlas as bake points (additive). The scene supplies the device and the stream only; the arrays are the
+ * caller's: per triangle 9 position floats, 9 normal floats (one normal per corner) and 6 atlas coordinates (u, v per corner, the atlas
+ * spans [0, 1]^2, v grows with the row).
+ * The rule, in IEEE binary32 as written. Texel q = y*W + x has the centre cx = ((float)x + 0.5f) / (float)W, cy = ((float)y + 0.5f) / (float)H.
+ * For triangle t with atlas corners a, b, c, corner positions A, B, C and corner normals Na, Nb, Nc:
+ *     area = (b.x-a.x)*(c.y-a.y) - (b.y-a.y)*(c.x-a.x)                            0 or not finite: the triangle covers nothing
+ *     w1 = ((cx-a.x)*(c.y-a.y) - (cy-a.y)*(c.x-a.x)) / area
+ *     w2 = ((b.x-a.x)*(cy-a.y) - (b.y-a.y)*(cx-a.x)) / area
+ *     w0 = 1.0f - w1 - w2
+ *     covered iff w0 >= 0 && w1 >= 0 && w2 >= 0                                   either winding; edges are inclusive
+ *   The owner of q is the lowest covering t (as if every (t, q) pair were tested). The point of an owned texel:
+ *     position = w0*A + w1*B + w2*C;  normal = norm(w0*Na + w1*Nb + w2*Nc);  stream = q;  reserved = 0
+ *   Points are written in increasing q, texels_out[i] = q of point i. *n_points (a host word in either form) receives the number of owned
+ *   texels even when it exceeds `capacity`; then the first `capacity` points are written and the call returns RT_OK.
+ * flags: 0 (host arrays) or RT_FLAG_DEVICE_FB: the three inputs are device pointers as rt_update_geometry_device takes them (4-byte aligned,
+ *   idle, read in place) and points_out / texels_out are device pointers, points_out 16-byte aligned.
+ * RT_ERR_INVALID_ARG: a NULL argument (the inputs only with n_tris > 0, the outputs only with capacity > 0); width or height 0;
+ *   width * height >= 2^31; a misaligned device pointer; any other flag. RT_ERR_UNSUPPORTED: a multi-GPU scene. n_tris == 0 writes no point
+ *   and *n_points = 0.
+ * Not covered: conservative coverage of texels a triangle only touches, seam dilation, packing and unwrapping. */
+int rt_lightmap_points(rt_scene *scene, const float *positions, const float *normals, const float *lm_uv, uint32_t n_tris, uint32_t width, uint32_t height,
+                       uint32_t flags, rt_bake_point *points_out, uint32_t *texels_out, uint32_t capacity, uint32_t *n_points);
 
 /* Resumable sample accumulators: progressive and adaptive rendering (additive; RT_ABI_VERSION stays 4).
  * An accumulator belongs to one scene, one image size (width x height) and one view (a camera and an RT_RNG_DEVICE seed). It keeps, in

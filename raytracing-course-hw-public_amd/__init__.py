@@ -55,8 +55,13 @@ from ._ctypes_abi import (
     RT_RNG_DEVICE,
     RT_RNG_REFERENCE,
     RAY_DTYPE,
+    BAKE_POINT_DTYPE,
+    RT_BAKE_IRRADIANCE,
+    RT_BAKE_SH9,
     DescHolder,
     RtAdaptive,
+    RtBake,
+    RtBakePoint,
     RtCamera,
     RtDenoise,
     RtEnvironment,
@@ -265,6 +270,26 @@ def pack_rays(rays, stream=None, first_sample=None, samples: int = 1, rays_per_o
     out["origin"], out["dir"] = od[:, :3], od[:, 3:]
     out["stream"] = (idx // g).astype(np.uint32) if stream is None else np.asarray(stream, dtype=np.uint32).reshape(n)
     out["first_sample"] = ((idx % g) * np.uint64(samples)).astype(np.uint32) if first_sample is None else np.asarray(first_sample, dtype=np.uint32).reshape(n)
+    return out
+
+
+def pack_bake_points(positions, normals=None, stream=None) -> np.ndarray:
+    """rt_bake_point records (BAKE_POINT_DTYPE, contiguous) of what DeviceScene.bake_irradiance / bake_sh / bake_rays accept: a packed array
+    passes through (a ctypes RtBakePoint array is viewed, not copied); (n, 3) `positions` get `normals` (default: zeros, which bake_sh does
+    not read) and `stream` (default: the index)."""
+    if isinstance(positions, C.Array) and getattr(positions, "_type_", None) is RtBakePoint:
+        positions = np.frombuffer(positions, dtype=BAKE_POINT_DTYPE)
+    if isinstance(positions, np.ndarray) and positions.dtype == BAKE_POINT_DTYPE:
+        if normals is not None or stream is not None:
+            raise ValueError("packed bake points carry their own normal / stream")
+        return np.ascontiguousarray(positions).reshape(-1)
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    n = pos.shape[0]
+    out = np.zeros(n, dtype=BAKE_POINT_DTYPE)
+    out["position"] = pos
+    if normals is not None:
+        out["normal"] = np.asarray(normals, dtype=np.float32).reshape(n, 3)
+    out["stream"] = np.arange(n, dtype=np.uint32) if stream is None else np.asarray(stream, dtype=np.uint32).reshape(n)
     return out
 
 
@@ -645,6 +670,108 @@ class DeviceScene:
         _check(fn(self._h, C.byref(p), packed.ctypes.data_as(C.c_void_p), n, g, out.ctypes.data_as(C.c_void_p), C.byref(st)))
         return out, st.as_dict()
 
+    def _bake(self, kind, points, samples, seed, offset, first_sample, device_points, n_points, device_out, global_best, counters, tuning):
+        p = RtParams(0, 0, int(samples), RT_RNG_DEVICE, int(seed), 0, 1, 0, (RT_FLAG_COUNTERS if counters else 0) | (RT_FLAG_GLOBAL_BEST if global_best else 0))
+        keep_cb = _apply_tuning(p, tuning)  # noqa: F841
+        b = RtBake(int(kind), int(first_sample) & 0xFFFFFFFF, float(offset))
+        st = RtStats()
+        shape = (9, 3) if kind == RT_BAKE_SH9 else (3,)
+        if bool(device_points) != bool(device_out):
+            raise ValueError("bake: device_points and device_out go together (RT_FLAG_DEVICE_FB covers both buffers)")
+        if device_points:
+            if n_points is None:
+                raise ValueError("bake: device_points needs n_points")
+            p.flags |= RT_FLAG_DEVICE_FB
+            _check(lib().rt_bake(self._h, C.byref(p), C.byref(b), C.c_void_p(device_points), int(n_points), C.c_void_p(device_out), C.byref(st)))
+            return None, st.as_dict()
+        packed = pack_bake_points(points)
+        out = np.zeros((len(packed),) + shape, dtype=np.float32)
+        _check(lib().rt_bake(self._h, C.byref(p), C.byref(b), packed.ctypes.data_as(C.c_void_p), len(packed), out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return out, st.as_dict()
+
+    def bake_irradiance(self, points, samples: int, seed: int = 0, offset: float = 0.0, first_sample: int = 0, device_points: Optional[int] = None,
+                        n_points: Optional[int] = None, device_out: Optional[int] = None, global_best: bool = False, counters: bool = False, **tuning):
+        """Irradiance at surface points (rt_bake, RT_BAKE_IRRADIANCE): `points` are BAKE_POINT_DTYPE records (pack_bake_points makes them from
+        positions and normals; lightmap_points from an atlas). Sample s of point j is seeded from (seed, stream_j, first_sample + s), leaves
+        position + offset * normal along the reference's cosine lobe around the normal and is path-traced as a camera ray is;
+        E_j = pi x the mean radiance (include/rt_abi.h states the rule). Returns ((n, 3) float32, stats dict).
+        The device form (RT_FLAG_DEVICE_FB): `device_points` (a device pointer to packed records, 16-byte aligned), `n_points` and
+        `device_out` (a device pointer to n x 3 floats) go together and `points` is not read; nothing is copied and None is returned for the
+        outputs. Both buffers must be idle. `tuning`: as run_raytracer."""
+        return self._bake(RT_BAKE_IRRADIANCE, points, samples, seed, offset, first_sample, device_points, n_points, device_out, global_best, counters, tuning)
+
+    def bake_sh(self, points, samples: int, seed: int = 0, first_sample: int = 0, device_points: Optional[int] = None, n_points: Optional[int] = None,
+                device_out: Optional[int] = None, global_best: bool = False, counters: bool = False, **tuning):
+        """Spherical-harmonic light probes (rt_bake, RT_BAKE_SH9): the radiance arriving at each point from the whole sphere, projected on the
+        nine real SH basis functions of bands 0..2 in the order rt_abi.h lists them. Normals are not read. Returns ((n, 9, 3) float32, stats
+        dict); the device form is bake_irradiance's with n x 27 floats of output."""
+        return self._bake(RT_BAKE_SH9, points, samples, seed, 0.0, first_sample, device_points, n_points, device_out, global_best, counters, tuning)
+
+    def bake_rays(self, points, samples: int, seed: int = 0, sh: bool = False, offset: float = 0.0, first_sample: int = 0, device_points: Optional[int] = None,
+                  n_points: Optional[int] = None, device_out: Optional[int] = None):
+        """The first rays of a bake as the device makes them (rt_bake_rays): RAY_DTYPE records for samples [first_sample, first_sample +
+        samples) of every point, point-major, stream = the point's, first_sample = the sample index: what render_rays(samples=1,
+        rays_per_output=samples, seed=seed) turns into bake_irradiance / pi. `sh`: the rays of bake_sh. With `device_points`, `n_points` and
+        `device_out` (device pointers, 16-byte aligned, idle; 32 bytes per record) the records stay in HBM and None is returned."""
+        b = RtBake(RT_BAKE_SH9 if sh else RT_BAKE_IRRADIANCE, int(first_sample) & 0xFFFFFFFF, float(offset))
+        if bool(device_points) != bool(device_out):
+            raise ValueError("bake_rays: device_points and device_out go together (RT_FLAG_DEVICE_FB covers both buffers)")
+        if device_points:
+            if n_points is None:
+                raise ValueError("bake_rays: device_points needs n_points")
+            _check(lib().rt_bake_rays(self._h, C.byref(b), int(seed), C.c_void_p(device_points), int(n_points), int(samples), RT_FLAG_DEVICE_FB, C.c_void_p(device_out)))
+            return None
+        packed = pack_bake_points(points)
+        out = np.zeros(len(packed) * int(samples), dtype=RAY_DTYPE)
+        _check(lib().rt_bake_rays(self._h, C.byref(b), int(seed), packed.ctypes.data_as(C.c_void_p), len(packed), int(samples), 0, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def lightmap_points(self, positions, normals, lm_uv, width: int, height: int, capacity: Optional[int] = None, n_triangles: Optional[int] = None,
+                        device_points: Optional[int] = None, device_texels: Optional[int] = None):
+        """The covered texel centres of a width x height light-map atlas as bake points (rt_lightmap_points): `positions` / `normals` (9 floats
+        per triangle) and `lm_uv` (6: the corners' atlas coordinates in [0, 1]^2). A texel belongs to the lowest triangle whose atlas
+        triangle holds its centre (edges included); its point is the interpolated position and normalised normal, stream = texel index.
+        Returns (points (BAKE_POINT_DTYPE), texels (uint32: y * width + x)) in increasing texel order; scatter a bake's rows to
+        image.reshape(-1, 3)[texels]. With `capacity` at most that many are written (the first ones) and the number of owned texels is
+        returned as a third element.
+        The device form (RT_FLAG_DEVICE_FB): the three arrays are contiguous float32 torch CUDA tensors (or int device pointers, with
+        `n_triangles`), `device_points` / `device_texels` device pointers with room for `capacity` records (points 16-byte aligned); all idle.
+        Returns the count of owned texels."""
+        cap = int(width) * int(height) if capacity is None else int(capacity)
+        count = C.c_uint32()
+        if device_points or device_texels:
+            ptrs, n = [], n_triangles
+            for name, a, per in (("positions", positions, 9), ("normals", normals, 9), ("lm_uv", lm_uv, 6)):
+                if isinstance(a, int) and not isinstance(a, bool):
+                    ptrs.append(a)
+                    continue
+                import torch
+
+                if not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype != torch.float32 or not a.is_contiguous():
+                    raise TypeError(f"{name}: a contiguous float32 torch CUDA tensor or an int device pointer")
+                if n is None:
+                    n = a.numel() // per
+                if a.numel() != n * per:
+                    raise ValueError(f"{name}: {a.numel()} elements, expected {n * per} for {n} triangles")
+                torch.cuda.current_stream(a.device).synchronize()  # the idle precondition
+                ptrs.append(a.data_ptr() if a.numel() else 0)
+            if n is None:
+                raise ValueError("n_triangles is needed when every array is a device pointer")
+            _check(lib().rt_lightmap_points(self._h, *(C.c_void_p(q) for q in ptrs), int(n), int(width), int(height), RT_FLAG_DEVICE_FB,
+                                            C.c_void_p(device_points), C.c_void_p(device_texels), cap, C.byref(count)))
+            return int(count.value)
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 9)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 9)
+        uv = np.ascontiguousarray(lm_uv, dtype=np.float32).reshape(-1, 6)
+        if not (len(pos) == len(nrm) == len(uv)):
+            raise ValueError(f"lightmap_points: {len(pos)} / {len(nrm)} / {len(uv)} triangles in positions / normals / lm_uv")
+        pts = np.zeros(max(cap, 1), dtype=BAKE_POINT_DTYPE)
+        tex = np.zeros(max(cap, 1), dtype=np.uint32)
+        _check(lib().rt_lightmap_points(self._h, pos.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p), len(pos), int(width),
+                                        int(height), 0, pts.ctypes.data_as(C.c_void_p), tex.ctypes.data_as(C.c_void_p), cap, C.byref(count)))
+        k = min(int(count.value), cap)
+        return (pts[:k].copy(), tex[:k].copy()) if capacity is None else (pts[:k].copy(), tex[:k].copy(), int(count.value))
+
     def film_rgb8(self, fb: np.ndarray) -> np.ndarray:
         """The device film (image.h:49-82 on the GPU) applied to a host float array of shape (..., 3)."""
         fb = np.ascontiguousarray(fb, dtype=np.float32)
@@ -1013,6 +1140,12 @@ __all__ = [
     "rays",
     "RAY_DTYPE",
     "RtRay",
+    "pack_bake_points",
+    "BAKE_POINT_DTYPE",
+    "RtBakePoint",
+    "RtBake",
+    "RT_BAKE_IRRADIANCE",
+    "RT_BAKE_SH9",
     "load_hdr",
     "png_decode",
     "scenegen",

@@ -86,6 +86,19 @@ class RtRay(C.Structure):  # rt_render_rays: one caller-supplied ray and its RNG
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("dir", "<f4", (3,)), ("stream", "<u4"), ("first_sample", "<u4")])
 
 
+class RtBakePoint(C.Structure):  # rt_bake / rt_bake_rays / rt_lightmap_points: one bake point and its RNG stream (32 bytes)
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("stream", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# the same record as a numpy structured dtype: what pack_bake_points and DeviceScene.lightmap_points return
+BAKE_POINT_DTYPE = np.dtype([("position", "<f4", (3,)), ("normal", "<f4", (3,)), ("stream", "<u4"), ("reserved", "<u4")])
+RT_BAKE_IRRADIANCE, RT_BAKE_SH9 = 0, 1
+
+
+class RtBake(C.Structure):  # rt_bake_desc: what a bake computes per point (32 bytes)
+    _fields_ = [("kind", C.c_uint32), ("first_sample", C.c_uint32), ("offset", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 class RtDenoise(C.Structure):  # rt_accum_denoise: the filter's options (32 bytes; all-zero = the defaults)
     _fields_ = [
         ("iterations", C.c_uint32),
@@ -268,6 +281,10 @@ ABI_PROTOTYPES = {
     "rt_render_sensors": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtSensor), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_render_sensors_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtSensor), C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
     "rt_sensor_rays": (C.c_int, [C.c_void_p, C.POINTER(RtSensor), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_bake": (C.c_int, [C.c_void_p, C.POINTER(RtParams), C.POINTER(RtBake), C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_bake_rays": (C.c_int, [C.c_void_p, C.POINTER(RtBake), C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_lightmap_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     c_u32_p]),
     "rt_accum_create_sensor": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtSensor), C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_accum_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtCamera), C.c_uint64, C.POINTER(C.c_void_p)]),
     "rt_accum_destroy": (None, [C.c_void_p]),

@@ -351,6 +351,19 @@ struct WfRays {
     uint64_t seed;         // rt_params.seed
 };
 
+// A pass of rt_bake (rt_bake.cpp): the first stage makes sample first_sample + s of every bake point itself (wf_generate_bake, through
+// rt_dev_bake.h bake_ray) and the last stage folds the samples as the kind asks (wf_resolve_bake in place of wf_resolve). WfLaunch keeps
+// describing the pass: its "pixels" are the points, WfLaunch::samples = rt_params.samples. `out` holds the running sums between the sample
+// passes of a tile (3 floats per point, or 27 laid out [k][c]) and the scaled result after the last one: WfLaunch::accum and fb are not used.
+struct WfBake {
+    const uint4_pod *points; // [2 * n_points]: rt_bake_point records (rt_abi.h), 32 B = two 16-byte pieces {position, normal.x}, {normal.y, normal.z, stream, 0}
+    uint32_t kind;           // RT_BAKE_*
+    uint32_t first_sample;   // rt_bake_desc.first_sample
+    float offset;            // rt_bake_desc.offset
+    uint64_t seed;           // rt_params.seed
+    float *out;              // device
+};
+
 struct RenderLaunch {
     uint32_t width, height, samples, rng_mode;
     uint64_t seed;

@@ -67,10 +67,15 @@ struct WfHostSync {
 // wf_resolve; first_pass / last_pass are not read. Null for rt_render. `feat` (optional, with `acc`): the pass of a feature accumulator:
 // wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither.
 // `rays` (optional, without `acc`): a pass of rt_render_rays: wf_generate_rays replaces wf_generate; wf_fold and wf_resolve are rt_render's.
-// Without `rays` the primary rays come from the camera table L.sensors (a view is a pinhole record), whatever the entry point.
+// `bake` (optional, without `acc` and `rays`): a pass of rt_bake: wf_generate_bake replaces wf_generate and wf_resolve_bake replaces wf_resolve.
+// Without `rays` and `bake` the primary rays come from the camera table L.sensors (a view is a pinhole record), whatever the entry point.
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
-                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr);
+                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr,
+                                 const WfBake *bake = nullptr);
+// rt_bake_rays: the n = points x samples rt_ray records of samples [B.first_sample, B.first_sample + samples) of the points of `B` (device;
+// B.out is not read) -> `d_rays_out` (device, 32 B per record, 16-byte aligned)
+hipError_t launch_bake_rays(const WfBake &B, uint32_t samples, uint32_t n, void *d_rays_out, int num_cus, hipStream_t stream);
 // rt_sensor_rays: the n = pixels x samples rt_ray records of pixels [first_pixel, ..) x samples [first_sample, first_sample + samples) of
 // the sensor record `d_sensor` (device) -> `d_rays_out` (device, 32 B per record, 16-byte aligned)
 hipError_t launch_sensor_rays(const WfSensor *d_sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples, uint32_t n,
@@ -113,6 +118,14 @@ hipError_t launch_accum_plan(const AccumRound &R, uint32_t chunk, hipStream_t st
 hipError_t launch_accum_image(const AccumRound &R, float *fb, hipStream_t stream);
 // the feature means (rt_accum_resolve_features): AS / n, NS / n, ZS / h; any output may be null
 hipError_t launch_accum_feature_means(const AccumRound &R, const WfFeat &F, float *albedo, float *normal, float *depth, hipStream_t stream);
+// rt_lightmap.hip: rt_lightmap_points. The texel centres of a width x height atlas that the triangles (device arrays: 9 / 9 / 6 floats each) cover,
+// as bake points in increasing texel order: owner per texel (integer atomicMin), exclusive scan, scatter. `owner` and `offs` have room for
+// width * height words, `scan_temp` for lightmap_scan_temp_bytes(width * height); `count` (device, one word) receives the number of owned
+// texels, of which the first `capacity` are written to `points_out` (32 B each) and `texels_out`.
+size_t lightmap_scan_temp_bytes(size_t texels);
+hipError_t launch_lightmap_points(const float *positions, const float *normals, const float *lm_uv, uint32_t n_tris, uint32_t width, uint32_t height, uint32_t *owner,
+                                  uint32_t *offs, void *scan_temp, size_t scan_temp_bytes, void *points_out, uint32_t *texels_out, uint32_t capacity, uint32_t *count,
+                                  int num_cus, hipStream_t stream);
 // rt_denoise.hip: the a-trous filter of rt_accum_denoise (the rule: rt_abi.h). `D` is the filter's workspace, owned by the accumulator.
 struct DenoiseBufs {
     RtF4 *sig[2]; // [pixels]: the working signal L, ping-pong

@@ -147,11 +147,11 @@ static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float 
 // One wavefront pass: `W` carries the workspace (wf_bind) and the pass's geometry (first_pixel, pass_pixels, first_sample, pass_samples,
 // n_paths, sensors, ...); this picks W.sort_mode and W.use_packet, launches, and folds the packet kernel's census back into `pol`, the
 // policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays*). `acc`: an
-// accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays (rt_kernels.h).
+// accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays, `bake`: a pass of rt_bake (rt_kernels.h).
 // `cam_pos`: rt::single_origin of the pass's camera table: the three floats sensor_ray stores as every ray's origin, or null where no such
 // position exists (several cameras, a caller's rays, a sensor whose rays start on a film or a lens).
 hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos) {
+                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos, const WfBake *bake) {
     // Small passes are bound by launch and host latency, not by memory (a 256 x 256 x 4 render, BASELINE config 1's
     // shape, spent 5.7 ms at 0.6 ms per bounce): RT_SORT_AUTO leaves a pass of fewer than 2^20 paths unsorted, which also spares it
     // the per-bounce queue-size read-back the sort needs: the whole pass is queued without a single host wait.
@@ -171,7 +171,9 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
         pol.off = false;
     }
     const uint32_t pkt_min_spp = s->wide_built ? 4u : 16u; // measured break-even of the two packet kernels
-    W.use_packet = p->packet_mode == RT_PACKET_OFF ? 0u : p->packet_mode == RT_PACKET_ON ? 1u : (W.pass_samples >= pkt_min_spp && !pol.off) ? 1u : 0u;
+    // (a bake point's samples share an origin and nothing else: a hemisphere or the whole sphere of directions is no packet, so RT_PACKET_AUTO
+    // never picks the packet kernel for a pass of rt_bake; RT_PACKET_ON still does, and changes no bit)
+    W.use_packet = p->packet_mode == RT_PACKET_OFF ? 0u : p->packet_mode == RT_PACKET_ON ? 1u : (W.pass_samples >= pkt_min_spp && !pol.off && !bake) ? 1u : 0u;
     W.rel_nodes = nullptr, W.rel_tris = nullptr;
     if (W.use_packet && cam_pos && n_views == 1 && !rays)
         if (hipError_t e = camera_relative_records(s, W, cam_pos); e != hipSuccess)
@@ -179,7 +181,7 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     const rt::WfHostSync hsync = wavefront_host_sync(s);
     unsigned long long census[2] = {0ull, 0ull};
     const hipError_t e = rt::launch_wavefront_pass(s->dev, W, W.stats != nullptr, s->num_cus, first_pass, last_pass, s->stream, time_extends ? &s->ext_events : nullptr, census,
-                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays);
+                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays, bake);
     if (e == hipSuccess && census[0] != 0ull) {
         pol.lanes_x100 = (uint32_t)(100.0 * (double)census[1] / (double)census[0]);
         if ((double)census[1] < min_lanes * (double)census[0])
@@ -191,12 +193,12 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
 // The pass loop of a call that renders `n_pixels` local pixels (outputs, for rt_render_rays) x `samples` samples each: (pixel tile) x
 // (sample range) passes under wavefront_max_paths, all stream-ordered. `W` carries the caller's geometry, output buffer and flags; this grows
 // and binds the workspace and sets each pass's range. `table`: the cameras of the call, uploaded here as W.sensors (it outlives the caller's
-// stream sync; its one origin, if any, lets the packets walk camera-relative records); null for a pass of `rays`.
+// stream sync; its one origin, if any, lets the packets walk camera-relative records); null for a pass of `rays` or of `bake`.
 // Progress (rt_params.progress): one event per pass; the host stays ONE pass ahead of the device (after queueing pass k it waits for pass
 // k - 1 and reports it), so reporting never leaves the GPU idle. `stats` (may be null) receives passes / packet_passes. `fn`: the entry
 // point's name.
 int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint64_t n_pixels, uint32_t samples, const std::vector<WfSensor> *table,
-                   const WfRays *rays, rt_stats *stats, const char *fn) {
+                   const WfRays *rays, rt_stats *stats, const char *fn, const WfBake *bake) {
     const uint64_t max_paths = rt::wavefront_max_paths(s, p);
     const uint64_t tile_pixels = std::min<uint64_t>(n_pixels, max_paths);
     const uint32_t pass_spp = (uint32_t)std::clamp<uint64_t>(max_paths / tile_pixels, 1, samples);
@@ -227,7 +229,7 @@ int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch 
             W.first_sample = s0;
             W.pass_samples = std::min<uint32_t>(pass_spp, samples - s0);
             W.n_paths = W.pass_pixels * W.pass_samples;
-            HIP_TRY(rt::launch_pass(s, p, pol, W, n_views, s0 == 0, s0 + W.pass_samples >= samples, stats != nullptr, nullptr, nullptr, rays, cam_pos));
+            HIP_TRY(rt::launch_pass(s, p, pol, W, n_views, s0 == 0, s0 + W.pass_samples >= samples, stats != nullptr, nullptr, nullptr, rays, cam_pos, bake));
             packet_passes += W.use_packet;
             if (p->progress) {
                 HIP_TRY(hipEventRecord(s->pass_events[pass_no], s->stream));

@@ -1,5 +1,5 @@
 // rt_scene_impl.h — what the host files behind include/rt_abi.h share (internal): the definition of rt_scene and the few helpers
-// with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_rays.cpp (rt_render_rays*),
+// with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_rays.cpp (rt_render_rays*), rt_bake.cpp (rt_bake*, rt_lightmap_points),
 // rt_accum_host.cpp (rt_accum_*) and rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through
 // rt_group.h.
 #pragma once
@@ -284,9 +284,10 @@ void set_camera(DevScene &D, const float *pos, const float *right, const float *
 int check_pass_params(const rt_params *p, const char *fn);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
 hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr);
+                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr,
+                       const WfBake *bake = nullptr);
 int run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint64_t n_pixels, uint32_t samples, const std::vector<WfSensor> *table,
-               const WfRays *rays, rt_stats *stats, const char *fn);
+               const WfRays *rays, rt_stats *stats, const char *fn, const WfBake *bake = nullptr);
 // the image of a single-GPU scene through the cameras of `table` (views as pinhole records, or the checked records of rt_sensor.cpp)
 int render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor> &table, PacketPolicy &pol, float *fb_rgb, uint8_t *rgb8_out, rt_stats *stats);
 // rt_sensor.cpp: the argument checks of one rt_sensor, the device record of a sensor or of a view {camera, seed}, the one ray origin of a table

@@ -28,6 +28,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "rt_dev_bake.h"
 #include "rt_dev_queue.h"
 #include "rt_dev_sensor.h"
 #include "rt_dev_shade.h"
@@ -154,6 +155,46 @@ template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_gener
         st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
     }
     st.flush(L.stats);
+}
+
+// A pass of rt_bake (WfBake): path i is sample S = bake.first_sample + first_sample + ds of point first_pixel + lp. The lane reads the point's
+// 32-byte record as two 16-byte pieces, seeds the path's stream from (seed, point.stream, S) and makes gen_ray's two jitter draws as
+// wf_generate_rays does, then asks bake_ray (rt_dev_bake.h) for the ray: the rt_ray record rt_bake_rays writes for (point, S) is this ray.
+template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_bake(const DevScene S, const WfLaunch L, const WfBake B) {
+    LaneStats<STATS> st;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        L.counters[WF_CNT_IN] = L.n_paths;
+    const uint4 *recs = reinterpret_cast<const uint4 *>(B.points);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
+        const uint32_t lp = i / L.pass_samples;
+        const uint32_t smp = B.first_sample + (L.first_sample + (i - lp * L.pass_samples)); // the sample index wraps mod 2^32
+        const size_t pt = (size_t)(L.first_pixel + lp);
+        const uint4 p0 = recs[2 * pt], p1 = recs[2 * pt + 1];
+        Rng<RT_RNG_DEVICE> rng;
+        rt_xoshiro_seed(&rng.g, B.seed, p1.z, smp);
+        (void)uniform_real(rng, 0.0f, 1.0f);
+        (void)uniform_real(rng, 0.0f, 1.0f);
+        V3 o, d;
+        bake_ray(B.kind, B.offset, B.seed, p0, p1, smp, o, d);
+        wf_store_first<ENVD>(S, L, i, o, d, rng);
+        st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
+    }
+    st.flush(L.stats);
+}
+
+// rt_bake_rays: record i of the output is sample first_sample + i % samples of point i / samples, as an rt_ray {o, d, stream = point.stream,
+// first_sample = S}, stored as two 16-byte pieces per lane like wf_sensor_rays' records.
+__global__ __launch_bounds__(256) void wf_bake_rays(const WfBake B, uint32_t samples, uint32_t n, uint4 *out) {
+    const uint4 *recs = reinterpret_cast<const uint4 *>(B.points);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t pt = i / samples;
+        const uint32_t smp = B.first_sample + (i - pt * samples);
+        const uint4 p0 = recs[2ull * pt], p1 = recs[2ull * pt + 1];
+        V3 o, d;
+        bake_ray(B.kind, B.offset, B.seed, p0, p1, smp, o, d);
+        out[2ull * i] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
+        out[2ull * i + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), p1.z, smp);
+    }
 }
 
 // rt_sensor_rays: record i of the output is sample first_sample + i % samples of pixel first_pixel + i / samples of the one sensor `sensor[0]`,
@@ -720,6 +761,44 @@ __global__ __launch_bounds__(256) void wf_resolve(const WfLaunch L, int first_pa
     }
 }
 
+// The fold of a pass of rt_bake (WfBake), in wf_resolve's place: one lane per output (point, k) with k < 1 (IRRADIANCE) or k < 9 (SH9) owns its
+// three sums and adds the pass's samples in sample order; the nine lanes of an SH point read the same sample records. The sums of earlier
+// sample passes are in `out` itself; the last pass divides by the sample count and scales. SH9 weighs sample s by Y_k of its own direction,
+// which bake_ray makes again from (seed, stream, S): no direction buffer is kept between the stages.
+__global__ __launch_bounds__(256) void wf_resolve_bake(const WfLaunch L, const WfBake B, int first_pass, int last_pass) {
+    const bool sh = B.kind == RT_BAKE_SH9;
+    const uint32_t nk = sh ? 9u : 1u;
+    const uint64_t n = (uint64_t)L.pass_pixels * nk;
+    const uint4 *recs = reinterpret_cast<const uint4 *>(B.points);
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t lp = (uint32_t)(t / nk), k = (uint32_t)(t - (uint64_t)lp * nk);
+        const size_t pt = (size_t)(L.first_pixel + lp);
+        float *dst = B.out + (pt * nk + k) * 3u;
+        V3 acc = first_pass ? mk(0, 0, 0) : ld3(dst);
+        const RtF4 *src = L.sample_out + (size_t)lp * L.pass_samples;
+        if (sh) {
+            const uint4 p0 = recs[2 * pt], p1 = recs[2 * pt + 1];
+            for (uint32_t ds = 0; ds < L.pass_samples; ++ds) {
+                const RtF4 v = src[ds];
+                V3 o, d;
+                bake_ray(B.kind, B.offset, B.seed, p0, p1, B.first_sample + (L.first_sample + ds), o, d);
+                const float y = bake_sh9(k, d);
+                acc = acc + mk(v.x * y, v.y * y, v.z * y);
+            }
+        } else {
+            for (uint32_t ds = 0; ds < L.pass_samples; ++ds) {
+                const RtF4 v = src[ds];
+                acc = acc + mk(v.x, v.y, v.z);
+            }
+        }
+        if (last_pass)
+            acc = (acc / (float)L.samples) * (sh ? 4.0f * PI_F : PI_F);
+        dst[0] = acc.x;
+        dst[1] = acc.y;
+        dst[2] = acc.z;
+    }
+}
+
 // The same loop for an accumulator pass: one lane per entry adds its k consecutive samples onto S_p, and the even-index ones onto E_p,
 // in sample order, then n_p += k. A pixel has at most one entry per round, so the lane owns the pixel's sums; no division here.
 __global__ __launch_bounds__(256) void wf_resolve_list(const WfLaunch L, const WfAccum A) {
@@ -853,7 +932,7 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc,
-                                 const WfFeat *feat, const WfRays *rays) {
+                                 const WfFeat *feat, const WfRays *rays, const WfBake *bake) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
@@ -871,6 +950,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             return RT_LAUNCH_CHECKED((wf_generate_list<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
         if (rays) // a pass of rt_render_rays: the caller's rays and streams (wf_generate_rays)
             return RT_LAUNCH_CHECKED((wf_generate_rays<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *rays);
+        if (bake) // a pass of rt_bake: the samples of the bake points (wf_generate_bake)
+            return RT_LAUNCH_CHECKED((wf_generate_bake<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *bake);
         return RT_LAUNCH_CHECKED((wf_generate<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
     }, stats, S.env.texels != nullptr && S.env.marg != nullptr);
     if (e != hipSuccess)
@@ -990,6 +1071,12 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, *acc);
         return hipSuccess;
     }
+    if (bake) { // the fold the kind asks for, one lane per (point, k)
+        const uint64_t lanes = (uint64_t)L.pass_pixels * (bake->kind == RT_BAKE_SH9 ? 9u : 1u);
+        const uint32_t bake_blocks = (uint32_t)std::min<uint64_t>((lanes + 255u) / 256u, (uint64_t)num_cus * 64u);
+        WF_LAUNCH(wf_resolve_bake, dim3(bake_blocks > 0 ? bake_blocks : 1), block, 0, stream, L, *bake, first_pass ? 1 : 0, last_pass ? 1 : 0);
+        return hipSuccess;
+    }
     const int res_blocks = (int)((L.pass_pixels + 255u) / 256u);
     WF_LAUNCH(wf_resolve, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, first_pass ? 1 : 0, last_pass ? 1 : 0);
     return hipSuccess;
@@ -1000,6 +1087,11 @@ hipError_t launch_sensor_rays(const WfSensor *d_sensor, uint32_t width, uint32_t
     const uint32_t blocks = std::min<uint32_t>((n + 255u) / 256u, (uint32_t)num_cus * 16u);
     return RT_LAUNCH_CHECKED(wf_sensor_rays, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, d_sensor, width, height, first_pixel, first_sample, samples, n,
                              static_cast<uint4 *>(d_rays_out));
+}
+
+hipError_t launch_bake_rays(const WfBake &B, uint32_t samples, uint32_t n, void *d_rays_out, int num_cus, hipStream_t stream) {
+    const uint32_t blocks = std::min<uint32_t>((n + 255u) / 256u, (uint32_t)num_cus * 16u);
+    return RT_LAUNCH_CHECKED(wf_bake_rays, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, B, samples, n, static_cast<uint4 *>(d_rays_out));
 }
 
 size_t wavefront_sort_temp_bytes(size_t n) {
