@@ -50,7 +50,7 @@ extern "C" {
                                 rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were, and
                                 after rt_update_geometry and rt_ray / rt_render_rays / rt_render_rays_rgb8 were, and after
                                 rt_update_geometry_device and rt_refit_times were, and after rt_set_environment / rt_env_pdf / rt_env_sample were,
-                                and after rt_bake / rt_bake_rays / rt_lightmap_points were:
+                                and after rt_bake / rt_bake_rays / rt_lightmap_points were, and after rt_accum_attach_ids and the id reads were:
                                 new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
@@ -697,6 +697,59 @@ typedef struct rt_denoise {
 } rt_denoise;                  /* 32 bytes; all-zero = the defaults (measured: profiles/denoise_quality.txt) */
 int rt_accum_denoise(rt_accum *acc, const rt_denoise *opt, uint32_t flags, float *fb_rgb);
 int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint32_t flags, uint8_t *rgb8);
+
+/* Id mattes: which object, material or triangle a pixel shows, and with what coverage (additive; RT_ABI_VERSION stays 4).
+ * rt_accum_attach_ids makes an accumulator keep, for every pixel, a table of the ids its samples saw. Ids are attached by this call, not by a
+ * bit of accum_flags; they may be combined with RT_ACCUM_FEATURES.
+ * The id of a sample. The id of sample s of pixel p belongs to the closest hit of that sample's primary ray: the ray seeded from (seed, p, s),
+ *   or the sensor's ray, as the scene's own traversal returns it (parity, RT_FLAG_GLOBAL_BEST, wide): the hit the feature sums use. The alpha
+ *   coin of shade() (raytracer.h:559) is not consulted. A miss gives RT_ID_MISS.
+ *   RT_ID_PRIMITIVE: what rt_cast_rays reports as `prim`: the original triangle index, or n_triangles + i for analytic primitive i.
+ *   RT_ID_MATERIAL:  that triangle's material_ids entry, or primitives[i].material_id.
+ *   RT_ID_USER:      table[prim]. The table is copied at attach and the caller keeps theirs. An entry equal to RT_ID_MISS is legal and counts
+ *                    with the misses.
+ * The table of a pixel. Each pixel has K slots (id_j, c_j), j = 0 .. K-1, and a counter `other`; all start at (0, 0) and 0. The pixel's samples
+ *   are taken in sample order s = 0, 1, ...; for the id of each:
+ *     if some slot j with c_j > 0 has id_j == id:  c_j += 1;
+ *     else if some slot has c_j == 0:              the lowest such j takes (id, 1);
+ *     else:                                        other += 1.
+ *   Slots fill in first-seen order and nothing is ever evicted, so (sum of c_j) + other = n_p, a slot with c_j == 0 reads id_j == 0, and the
+ *   table is exact for the ids it holds: only the samples counted in `other` are unaccounted for. After any sequence of rt_accum_render /
+ *   rt_accum_render_adaptive calls the table is a function of n_p alone, like S_p: for any split over calls, passes and lists, any max_paths,
+ *   sort mode and packet mode. One lane owns a pixel's table for a list entry and walks its new samples in order; there are no atomics.
+ * What stays the same. S_p, E_p, n_p, the feature sums, the image, err and every event counter of an accumulator with ids are, bit for bit,
+ *   those of one without. An accumulator without ids allocates and launches nothing new.
+ * rt_accum_attach_ids: once per accumulator, before any call has added samples to it.
+ *   RT_ERR_INVALID_ARG: a NULL accumulator or desc; an unknown kind; slots > RT_ID_MAX_SLOTS; a non-zero reserved word; a flag other than
+ *   RT_FLAG_DEVICE_FB; RT_ID_USER with a NULL table or n_table != n_triangles + n_primitives of the scene; another kind with a table or a
+ *   non-zero n_table; a device table that is not 4-byte aligned; a second attach; an attach after samples were added.
+ *   RT_ERR_OOM (from a later render call): the per-path id records (4 B per path of a pass) do not fit beside the wavefront workspace.
+ *   After any refusal the accumulator is unchanged.
+ * rt_accum_read_ids: the tables on the host, any pointer may be NULL: ids [p][K], counts [p][K] (u32 each), other [p].
+ * rt_accum_resolve_labels: label_p = the id_j of the slot with the largest c_j, ties to the lowest j; coverage_p = (float)c_j / (float)n_p.
+ *   With n_p = 0: RT_ID_MISS and 0. `other` is not consulted: a pixel whose table overflowed may have a more frequent id that never got a
+ *   slot; a caller who cares checks `other` from rt_accum_read_ids (or attaches more slots). Either output may be NULL. flags: 0 (host
+ *   buffers) or RT_FLAG_DEVICE_FB (both are device buffers on the scene's GPU, 4-byte aligned, idle on entry).
+ * rt_accum_resolve_matte: matte_p = (float)(sum of c_j over the slots with c_j > 0 whose id_j is one of ids[0 .. n_ids-1]) / (float)n_p: an
+ *   integer sum, then one division; 0 with n_p = 0. Duplicates in `ids` count once; RT_ID_MISS is an id like any other. `ids` is always a
+ *   host array, 1 <= n_ids <= 4096; `matte` is a host buffer, or a device buffer with RT_FLAG_DEVICE_FB.
+ * The three reads: RT_ERR_INVALID_ARG for a NULL accumulator, an accumulator without ids, a flag other than RT_FLAG_DEVICE_FB, a NULL `ids`
+ *   or `matte`, n_ids outside 1..4096. */
+enum { RT_ID_PRIMITIVE = 0, RT_ID_MATERIAL = 1, RT_ID_USER = 2 };
+#define RT_ID_MISS 0xFFFFFFFFu
+#define RT_ID_MAX_SLOTS 16u
+typedef struct rt_id_desc {
+    uint32_t kind;         /* RT_ID_* */
+    uint32_t slots;        /* K: 1..16; 0 = 4 */
+    const uint32_t *table; /* RT_ID_USER: n_table words, the id of original triangle i, then of analytic primitive i; else NULL */
+    uint32_t n_table;      /* RT_ID_USER: must equal n_triangles + n_primitives of the scene; else 0 */
+    uint32_t flags;        /* 0, or RT_FLAG_DEVICE_FB: table is a device pointer on the scene's GPU, 4-byte aligned, idle on entry */
+    uint32_t reserved[2];  /* 0 */
+} rt_id_desc;              /* 32 bytes */
+int rt_accum_attach_ids(rt_accum *acc, const rt_id_desc *desc);
+int rt_accum_read_ids(rt_accum *acc, uint32_t *ids, uint32_t *counts, uint32_t *other);
+int rt_accum_resolve_labels(rt_accum *acc, uint32_t flags, uint32_t *label, float *coverage);
+int rt_accum_resolve_matte(rt_accum *acc, uint32_t flags, const uint32_t *ids, uint32_t n_ids, float *matte);
 
 /* New per-triangle arrays for a built scene (animation frames, deforming meshes, simulation steps) without rt_destroy + rt_create
  * (additive; RT_ABI_VERSION stays 4). Blocking; runs on the scene's own stream. The call replaces the five per-triangle arrays of the

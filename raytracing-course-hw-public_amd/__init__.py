@@ -25,6 +25,11 @@ from ._ctypes_abi import (
     HOST_PROTOTYPES,
     RT_ACCUM_FEATURES,
     RT_DENOISE_NO_DEMODULATE,
+    RT_ID_PRIMITIVE,
+    RT_ID_MATERIAL,
+    RT_ID_USER,
+    RT_ID_MISS,
+    RT_ID_MAX_SLOTS,
     RT_FLAG_COUNTERS,
     RT_FLAG_DEVICE_FB,
     RT_BUILD_DEVICE_LBVH,
@@ -66,6 +71,7 @@ from ._ctypes_abi import (
     RtDenoise,
     RtEnvironment,
     RtGeometryUpdate,
+    RtIdDesc,
     RtParams,
     RtRay,
     RtSceneDesc,
@@ -473,14 +479,23 @@ class DeviceScene:
             setattr(u, name, C.cast(C.c_void_p(ptrs[name]), C.POINTER(C.c_float if dtype == np.float32 else C.c_uint32)))
         _check(lib().rt_update_geometry_device(self._h, C.byref(u)))
 
-    def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False, sensor=None) -> "Accumulator":
+    def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False, sensor=None, ids=None,
+                    id_slots: int = 4) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
         RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view. `features`: keep the first-hit
         albedo / normal / depth sums as well (rt_accum_create_ex with RT_ACCUM_FEATURES), which features(), read_features() and denoise() need.
-        `sensor`: a Sensor in place of `camera` and `seed` (rt_accum_create_sensor): pixel p is then render_sensors(samples = n_p) of it."""
+        `sensor`: a Sensor in place of `camera` and `seed` (rt_accum_create_sensor): pixel p is then render_sensors(samples = n_p) of it.
+        `ids` (not None): Accumulator.attach_ids(ids, slots=id_slots) on the new accumulator, for read_ids(), labels() and matte()."""
         if sensor is not None and camera is not None:
             raise ValueError("accumulator: give a camera or a sensor, not both (the sensor carries its camera and seed)")
-        return Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0, sensor=sensor)
+        acc = Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0, sensor=sensor)
+        if ids is not None:
+            try:
+                acc.attach_ids(ids, slots=id_slots)
+            except Exception:
+                acc.close()
+                raise
+        return acc
 
     def render_sensors(self, width: int, height: int, samples: int, sensors, rgb8: bool = False, counters: bool = False, global_best: bool = False,
                        device_out: Optional[int] = None, **tuning):
@@ -1007,6 +1022,64 @@ class Accumulator:
         fn = lib().rt_accum_denoise_rgb8 if rgb8 else lib().rt_accum_denoise
         _check(fn(self._h, C.byref(o), 0, img.ctypes.data_as(C.c_void_p)))
         return img
+
+    def attach_ids(self, kind="primitive", slots: int = 4, n_table: Optional[int] = None) -> None:
+        """rt_accum_attach_ids: keep, per pixel, a table of `slots` (id, count) pairs of the ids its samples' primary rays hit, first seen first,
+        and a count of the samples that found the table full. `kind`: "primitive" (what cast_rays reports), "material", or a table of user
+        ids, one per original triangle and then per analytic primitive: a uint32 array (copied), or a device pointer (an int, with `n_table`
+        entries; RT_FLAG_DEVICE_FB). Once, before the first render."""
+        d = RtIdDesc()
+        d.slots = int(slots)
+        keep = None
+        if isinstance(kind, str):
+            if kind not in ("primitive", "material"):
+                raise ValueError(f"attach_ids: kind {kind!r} is not 'primitive', 'material', an array or a device pointer")
+            d.kind = RT_ID_PRIMITIVE if kind == "primitive" else RT_ID_MATERIAL
+        elif isinstance(kind, (int, np.integer)):
+            if n_table is None:
+                raise ValueError("attach_ids: a device pointer needs n_table")
+            d.kind, d.table, d.n_table, d.flags = RT_ID_USER, int(kind), int(n_table), RT_FLAG_DEVICE_FB
+        else:
+            keep = np.ascontiguousarray(kind, dtype=np.uint32).reshape(-1)
+            d.kind, d.table, d.n_table = RT_ID_USER, keep.ctypes.data, keep.size
+        _check(lib().rt_accum_attach_ids(self._h, C.byref(d)))
+        self.id_slots = int(d.slots) if d.slots else 4
+
+    def read_ids(self) -> dict:
+        """The id tables (rt_accum_read_ids): "ids" and "counts" (H, W, K) uint32 in first-seen order (an empty slot reads id 0, count 0),
+        "other" (H, W) uint32: the samples no slot was left for. Needs attach_ids."""
+        k = getattr(self, "id_slots", 1)
+        out = {
+            "ids": np.zeros((self.height, self.width, k), dtype=np.uint32),
+            "counts": np.zeros((self.height, self.width, k), dtype=np.uint32),
+            "other": np.zeros((self.height, self.width), dtype=np.uint32),
+        }
+        _check(lib().rt_accum_read_ids(self._h, u32ptr(out["ids"]), u32ptr(out["counts"]), u32ptr(out["other"])))
+        return out
+
+    def labels(self, device_out=None):
+        """rt_accum_resolve_labels: (label (H, W) uint32: the id of each pixel's fullest slot, RT_ID_MISS where n = 0; coverage (H, W) float32:
+        that slot's count / n). `device_out`: a pair of device pointers (label, coverage; either may be None or 0) that receive them in HBM
+        (RT_FLAG_DEVICE_FB); then (None, None) is returned."""
+        if device_out is not None:
+            lp, cp = device_out
+            _check(lib().rt_accum_resolve_labels(self._h, RT_FLAG_DEVICE_FB, C.c_void_p(lp or None), C.c_void_p(cp or None)))
+            return None, None
+        label = np.zeros((self.height, self.width), dtype=np.uint32)
+        cov = np.zeros((self.height, self.width), dtype=np.float32)
+        _check(lib().rt_accum_resolve_labels(self._h, 0, label.ctypes.data_as(C.c_void_p), cov.ctypes.data_as(C.c_void_p)))
+        return label, cov
+
+    def matte(self, ids, device_out: Optional[int] = None):
+        """rt_accum_resolve_matte: (H, W) float32, the share of each pixel's samples whose id is one of `ids` (1..4096 of them; duplicates count
+        once), as far as the pixel's slots hold it. `device_out`: a device pointer that receives it in HBM; then None is returned."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if device_out:
+            _check(lib().rt_accum_resolve_matte(self._h, RT_FLAG_DEVICE_FB, u32ptr(ids), ids.size, C.c_void_p(device_out)))
+            return None
+        out = np.zeros((self.height, self.width), dtype=np.float32)
+        _check(lib().rt_accum_resolve_matte(self._h, 0, u32ptr(ids), ids.size, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def close(self) -> None:
         if self._h:

@@ -120,6 +120,22 @@ class RtAdaptive(C.Structure):  # rt_accum_render_adaptive: the adaptive rule's 
     ]
 
 
+RT_ID_PRIMITIVE, RT_ID_MATERIAL, RT_ID_USER = range(3)  # rt_id_desc.kind
+RT_ID_MISS = 0xFFFFFFFF
+RT_ID_MAX_SLOTS = 16
+
+
+class RtIdDesc(C.Structure):  # rt_accum_attach_ids: which ids an accumulator keeps, in how many slots (32 bytes)
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("slots", C.c_uint32),
+        ("table", C.c_void_p),
+        ("n_table", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 class RtTextureDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgba8", c_u8_p)]
 
@@ -298,6 +314,10 @@ ABI_PROTOTYPES = {
     "rt_accum_resolve_features": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_accum_denoise": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
     "rt_accum_denoise_rgb8": (C.c_int, [C.c_void_p, C.POINTER(RtDenoise), C.c_uint32, C.c_void_p]),
+    "rt_accum_attach_ids": (C.c_int, [C.c_void_p, C.POINTER(RtIdDesc)]),
+    "rt_accum_read_ids": (C.c_int, [C.c_void_p, c_u32_p, c_u32_p, c_u32_p]),
+    "rt_accum_resolve_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_accum_resolve_matte": (C.c_int, [C.c_void_p, C.c_uint32, c_u32_p, C.c_uint32, C.c_void_p]),
     "rt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),
     "rt_update_geometry_device": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),  # the five pointers are device pointers
     "rt_refit_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

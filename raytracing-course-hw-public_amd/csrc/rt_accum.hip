@@ -135,6 +135,50 @@ __global__ __launch_bounds__(256) void accum_feature_means_kernel(const rt::Accu
     }
 }
 
+// rt_accum_resolve_labels: the id of the fullest slot (ties: the lowest slot) and its share of n_p; RT_ID_MISS and 0 where n_p = 0
+__global__ __launch_bounds__(256) void accum_labels_kernel(const rt::AccumRound R, const WfIds I, uint32_t *label, float *coverage) {
+    const uint32_t n_pix = R.width * R.height;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pix; p += gridDim.x * blockDim.x) {
+        const uint32_t n = R.count[p];
+        uint32_t best = 0u, best_j = 0u;
+        for (uint32_t j = 0; j < I.k; ++j) {
+            const uint32_t c = I.slot_count[(size_t)j * n_pix + p];
+            if (c > best)
+                best = c, best_j = j;
+        }
+        if (label)
+            label[p] = n != 0u ? I.slot_id[(size_t)best_j * n_pix + p] : RT_ID_MISS;
+        if (coverage)
+            coverage[p] = n != 0u ? (float)best / (float)n : 0.0f;
+    }
+}
+
+// rt_accum_resolve_matte: the counts of the slots whose id is in `set` (sorted, no duplicates), summed as integers, over n_p
+__global__ __launch_bounds__(256) void accum_matte_kernel(const rt::AccumRound R, const WfIds I, const uint32_t *set, uint32_t n_set, float *matte) {
+    const uint32_t n_pix = R.width * R.height;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pix; p += gridDim.x * blockDim.x) {
+        const uint32_t n = R.count[p];
+        uint32_t sum = 0u;
+        for (uint32_t j = 0; j < I.k; ++j) {
+            const uint32_t c = I.slot_count[(size_t)j * n_pix + p];
+            if (c == 0u)
+                break; // slots fill from 0 up: the rest are empty too
+            const uint32_t id = I.slot_id[(size_t)j * n_pix + p];
+            uint32_t lo = 0u, hi = n_set; // the first element >= id
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2u;
+                if (set[mid] < id)
+                    lo = mid + 1u;
+                else
+                    hi = mid;
+            }
+            if (lo < n_set && set[lo] == id)
+                sum += c;
+        }
+        matte[p] = n != 0u ? (float)sum / (float)n : 0.0f;
+    }
+}
+
 dim3 accum_grid(const rt::AccumRound &R) {
     const uint64_t n_pix = (uint64_t)R.width * R.height;
     const uint64_t b = (n_pix + 255u) / 256u;
@@ -179,6 +223,14 @@ hipError_t launch_accum_image(const AccumRound &R, float *fb, hipStream_t stream
 
 hipError_t launch_accum_feature_means(const AccumRound &R, const WfFeat &F, float *albedo, float *normal, float *depth, hipStream_t stream) {
     return RT_LAUNCH_CHECKED(accum_feature_means_kernel, accum_grid(R), dim3(256), 0, stream, R, F, albedo, normal, depth);
+}
+
+hipError_t launch_accum_labels(const AccumRound &R, const WfIds &I, uint32_t *label, float *coverage, hipStream_t stream) {
+    return RT_LAUNCH_CHECKED(accum_labels_kernel, accum_grid(R), dim3(256), 0, stream, R, I, label, coverage);
+}
+
+hipError_t launch_accum_matte(const AccumRound &R, const WfIds &I, const uint32_t *set, uint32_t n_set, float *matte, hipStream_t stream) {
+    return RT_LAUNCH_CHECKED(accum_matte_kernel, accum_grid(R), dim3(256), 0, stream, R, I, set, n_set, matte);
 }
 
 } // namespace rt

@@ -20,6 +20,10 @@ struct rt_accum {
     bool features = false; // RT_ACCUM_FEATURES: F holds the four first-hit sums (F.rec is the scene's, bound per fill)
     WfFeat F{};
     rt::DenoiseBufs D{};   // rt_accum_denoise's workspace (64 B per pixel), allocated by its first call
+    bool ids = false;      // rt_accum_attach_ids: I holds the per-pixel id tables (I.rec is the scene's, bound per fill)
+    WfIds I{};
+    rt::DevBuf<uint32_t> matte_set; // rt_accum_resolve_matte's id set on the device
+    bool has_samples = false; // a call has queued a pass of this accumulator: ids can no longer be attached
     ~rt_accum() {
         (void)hipSetDevice(scene->device);
         (void)hipStreamSynchronize(scene->stream); // `owned` frees after this body: on this device, behind this synchronise
@@ -185,6 +189,11 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                     return rc;
                 a->F.rec = s->wf_feat.get();
             }
+            if (a->ids) {
+                if (int rc = s->ensure_ids(); rc != RT_OK)
+                    return rc;
+                a->I.rec = s->wf_ids.get();
+            }
             s->wf_bind(W);
             W.fb = nullptr;
             W.accum = nullptr; // wf_resolve does not run on an accumulator pass
@@ -193,7 +202,9 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 W.n_paths = (uint32_t)std::min<uint64_t>((uint64_t)A.n_entries * C, tot[1]); // an upper bound: wf_generate_list reads the exact count
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
-                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr, nullptr, cam_pos));
+                a->has_samples = true;
+                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr, nullptr, cam_pos, nullptr,
+                                        a->ids ? &a->I : nullptr));
                 passes += 1;
                 packet_passes += W.use_packet;
                 if (p->progress && !ad) {
@@ -460,4 +471,139 @@ extern "C" int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint3
         HIP_TRY(hipMemcpyAsync(rgb8, d_rgb8, 3ull * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RT_OK;
+}
+
+// ---- id mattes (rt_abi.h rt_accum_attach_ids: the rule; the kernels: rt_wavefront.hip wf_ids / wf_resolve_ids, rt_accum.hip)
+extern "C" int rt_accum_attach_ids(rt_accum *acc, const rt_id_desc *desc) {
+    if (!acc || !desc)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: null argument");
+    rt_scene *s = acc->scene;
+    const bool user = desc->kind == RT_ID_USER, device_table = (desc->flags & RT_FLAG_DEVICE_FB) != 0;
+    if (desc->kind > (uint32_t)RT_ID_USER)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: unknown kind " + std::to_string(desc->kind));
+    if (desc->slots > RT_ID_MAX_SLOTS)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: slots must be 0 (= 4) or 1..16");
+    if (desc->reserved[0] != 0 || desc->reserved[1] != 0 || (desc->flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: reserved fields must be 0; flags other than RT_FLAG_DEVICE_FB");
+    const uint32_t n_table = s->dev.n_triangles + s->dev.n_prims;
+    if (user && (!desc->table || desc->n_table != n_table))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: RT_ID_USER needs a table of n_triangles + n_primitives = " + std::to_string(n_table) + " ids");
+    if (!user && (desc->table || desc->n_table != 0))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: only RT_ID_USER takes a table");
+    if (user && device_table && (reinterpret_cast<uintptr_t>(desc->table) & 3u))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: the device table must be 4-byte aligned");
+    if (acc->ids)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: the accumulator already has ids");
+    if (acc->has_samples)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: the accumulator already holds samples; attach ids before the first render");
+    HIP_TRY(hipSetDevice(s->device));
+    WfIds I{};
+    I.kind = desc->kind;
+    I.k = desc->slots ? desc->slots : 4u;
+    I.pixels = acc->width * acc->height;
+    const size_t n = I.pixels, words = n * I.k;
+    uint32_t *table = nullptr;
+    int rc;
+    if ((rc = accum_alloc(acc, 4 * words, &I.slot_id, "rt_accum_attach_ids")) != RT_OK || (rc = accum_alloc(acc, 4 * words, &I.slot_count, "rt_accum_attach_ids")) != RT_OK ||
+        (rc = accum_alloc(acc, 4 * n, &I.other, "rt_accum_attach_ids")) != RT_OK ||
+        (user && (rc = accum_alloc(acc, 4 * (size_t)n_table, &table, "rt_accum_attach_ids")) != RT_OK))
+        return rc; // what was allocated stays with the accumulator's arena, unused, until rt_accum_destroy
+    auto queue = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(I.slot_id, 0, 4 * words, s->stream));
+        HIP_TRY(hipMemsetAsync(I.slot_count, 0, 4 * words, s->stream));
+        HIP_TRY(hipMemsetAsync(I.other, 0, 4 * n, s->stream));
+        if (user && n_table)
+            HIP_TRY(hipMemcpyAsync(table, desc->table, 4 * (size_t)n_table, device_table ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+        return RT_OK;
+    };
+    if ((rc = rt::queue_and_wait(s, queue)) != RT_OK)
+        return rc;
+    I.table = table;
+    acc->I = I;
+    acc->ids = true;
+    return RT_OK;
+}
+
+static int ids_check(const rt_accum *acc, const char *fn) {
+    if (!acc)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null accumulator");
+    if (!acc->ids)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no ids (rt_accum_attach_ids)");
+    return RT_OK;
+}
+
+extern "C" int rt_accum_read_ids(rt_accum *acc, uint32_t *ids, uint32_t *counts, uint32_t *other) {
+    if (int rc = ids_check(acc, "rt_accum_read_ids"); rc != RT_OK)
+        return rc;
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = acc->I.pixels, K = acc->I.k;
+    std::vector<uint32_t> slot_major; // the device keeps slot j of pixel p at j * pixels + p
+    for (auto [dst, src] : {std::pair{ids, acc->I.slot_id}, std::pair{counts, acc->I.slot_count}}) {
+        if (!dst)
+            continue;
+        slot_major.resize(n * K);
+        HIP_TRY(hipMemcpyAsync(slot_major.data(), src, 4 * n * K, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for (size_t p = 0; p < n; ++p)
+            for (size_t j = 0; j < K; ++j)
+                dst[p * K + j] = slot_major[j * n + p];
+    }
+    if (other)
+        HIP_TRY(hipMemcpyAsync(other, acc->I.other, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_accum_resolve_labels(rt_accum *acc, uint32_t flags, uint32_t *label, float *coverage) {
+    if (int rc = ids_check(acc, "rt_accum_resolve_labels"); rc != RT_OK)
+        return rc;
+    if (flags & ~(uint32_t)RT_FLAG_DEVICE_FB)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_labels: flags other than RT_FLAG_DEVICE_FB");
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = acc->I.pixels;
+    if (flags & RT_FLAG_DEVICE_FB) {
+        HIP_TRY(rt::launch_accum_labels(acc->R, acc->I, label, coverage, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        return RT_OK;
+    }
+    if (int rc = s->ensure_fb(2 * n); rc != RT_OK) // staging: label (u32 words), coverage
+        return rc;
+    uint32_t *d_label = reinterpret_cast<uint32_t *>(s->fb.get());
+    float *d_cov = s->fb.get() + n;
+    HIP_TRY(rt::launch_accum_labels(acc->R, acc->I, d_label, d_cov, s->stream));
+    if (label)
+        HIP_TRY(hipMemcpyAsync(label, d_label, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    if (coverage)
+        HIP_TRY(hipMemcpyAsync(coverage, d_cov, 4 * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_accum_resolve_matte(rt_accum *acc, uint32_t flags, const uint32_t *ids, uint32_t n_ids, float *matte) {
+    if (int rc = ids_check(acc, "rt_accum_resolve_matte"); rc != RT_OK)
+        return rc;
+    if (!ids || !matte || n_ids == 0 || n_ids > 4096u || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_matte: null ids or matte, n_ids outside 1..4096, or flags other than RT_FLAG_DEVICE_FB");
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = acc->I.pixels;
+    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
+    std::vector<uint32_t> set(ids, ids + n_ids); // sorted, each id once: the kernel's binary search
+    std::sort(set.begin(), set.end());
+    set.erase(std::unique(set.begin(), set.end()), set.end());
+    HIP_TRY(acc->matte_set.reserve(set.size()));
+    if (!device_fb)
+        if (int rc = s->ensure_fb(n); rc != RT_OK)
+            return rc;
+    float *d_matte = device_fb ? matte : s->fb.get();
+    auto queue = [&]() -> int { // `set` is a local: nothing of this may be in flight when it dies
+        HIP_TRY(hipMemcpyAsync(acc->matte_set.get(), set.data(), 4 * set.size(), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(rt::launch_accum_matte(acc->R, acc->I, acc->matte_set.get(), (uint32_t)set.size(), d_matte, s->stream));
+        if (!device_fb)
+            HIP_TRY(hipMemcpyAsync(matte, d_matte, 4 * n, hipMemcpyDeviceToHost, s->stream));
+        return RT_OK;
+    };
+    return rt::queue_and_wait(s, queue);
 }

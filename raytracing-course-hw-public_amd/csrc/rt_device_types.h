@@ -340,6 +340,21 @@ struct WfFeat {
     uint32_t *hits;                        // [pixels]: h_p
 };
 
+// The id table of an accumulator with ids (rt_abi.h rt_accum_attach_ids). wf_ids writes one id per path after bounce 0's closest hits, from
+// the same hit records wf_features reads; wf_resolve_ids folds them into the pixel's K slots in sample order, one lane per entry, as
+// wf_resolve_list adds samples. The slots are slot-major (slot j of pixel p is word j * pixels + p): the lanes of a wave own neighbouring
+// pixels and walk the slots in step, so every access of a uniform round is coalesced; rt_accum_read_ids delivers [p][K].
+struct WfIds {
+    uint32_t *rec;         // [paths of the pass]: the id of each path's sample, in the scene's wavefront workspace
+    uint32_t *slot_id;     // [K * pixels]: id_j of pixel p at j * pixels + p; 0 while c_j == 0
+    uint32_t *slot_count;  // [K * pixels]: c_j
+    uint32_t *other;       // [pixels]: samples that found every slot taken by another id
+    const uint32_t *table; // RT_ID_USER: [n_triangles + n_primitives], the accumulator's copy; else null
+    uint32_t kind;         // RT_ID_*
+    uint32_t k;            // K: 1..RT_ID_MAX_SLOTS
+    uint32_t pixels;       // width * height
+};
+
 // A pass of rt_render_rays (rt_rays.cpp): the first stage takes its rays and RNG streams from the caller's buffer instead of a camera
 // (wf_generate_rays). The call is a virtual image of n_rays / group "pixels" (outputs) with group * samples samples each, so WfLaunch keeps
 // describing the pass (first_pixel / pass_pixels count outputs, WfLaunch::samples = group * samples) and wf_fold / wf_resolve run unchanged:

@@ -65,14 +65,15 @@ struct WfHostSync {
 #define WF_HOST_CENSUS_WORD 40 /* 8-byte aligned, behind RT_MAX_RAY_DEPTH + 1 size words */
 // `acc` (optional): an accumulator pass (rt_accum.hip): wf_generate_list / wf_resolve_list over the round's entry list replace wf_generate /
 // wf_resolve; first_pass / last_pass are not read. Null for rt_render. `feat` (optional, with `acc`): the pass of a feature accumulator:
-// wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither.
+// wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither. `ids` (optional, with `acc`):
+// the pass of an accumulator with ids: wf_ids next to wf_features and wf_resolve_ids before wf_resolve_list; null launches neither.
 // `rays` (optional, without `acc`): a pass of rt_render_rays: wf_generate_rays replaces wf_generate; wf_fold and wf_resolve are rt_render's.
 // `bake` (optional, without `acc` and `rays`): a pass of rt_bake: wf_generate_bake replaces wf_generate and wf_resolve_bake replaces wf_resolve.
 // Without `rays` and `bake` the primary rays come from the camera table L.sensors (a view is a pinhole record), whatever the entry point.
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
                                  const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr,
-                                 const WfBake *bake = nullptr);
+                                 const WfBake *bake = nullptr, const WfIds *ids = nullptr);
 // rt_bake_rays: the n = points x samples rt_ray records of samples [B.first_sample, B.first_sample + samples) of the points of `B` (device;
 // B.out is not read) -> `d_rays_out` (device, 32 B per record, 16-byte aligned)
 hipError_t launch_bake_rays(const WfBake &B, uint32_t samples, uint32_t n, void *d_rays_out, int num_cus, hipStream_t stream);
@@ -118,6 +119,10 @@ hipError_t launch_accum_plan(const AccumRound &R, uint32_t chunk, hipStream_t st
 hipError_t launch_accum_image(const AccumRound &R, float *fb, hipStream_t stream);
 // the feature means (rt_accum_resolve_features): AS / n, NS / n, ZS / h; any output may be null
 hipError_t launch_accum_feature_means(const AccumRound &R, const WfFeat &F, float *albedo, float *normal, float *depth, hipStream_t stream);
+// the reads of an id table (rt_accum_resolve_labels, rt_accum_resolve_matte): device outputs, one word per pixel; `label` or `coverage` may be
+// null. `set`: the matte's ids sorted ascending without duplicates, device, n_set >= 1.
+hipError_t launch_accum_labels(const AccumRound &R, const WfIds &I, uint32_t *label, float *coverage, hipStream_t stream);
+hipError_t launch_accum_matte(const AccumRound &R, const WfIds &I, const uint32_t *set, uint32_t n_set, float *matte, hipStream_t stream);
 // rt_lightmap.hip: rt_lightmap_points. The texel centres of a width x height atlas that the triangles (device arrays: 9 / 9 / 6 floats each) cover,
 // as bake points in increasing texel order: owner per texel (integer atomicMin), exclusive scan, scatter. `owner` and `offs` have room for
 // width * height words, `scan_temp` for lightmap_scan_temp_bytes(width * height); `count` (device, one word) receives the number of owned

@@ -147,11 +147,11 @@ static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float 
 // One wavefront pass: `W` carries the workspace (wf_bind) and the pass's geometry (first_pixel, pass_pixels, first_sample, pass_samples,
 // n_paths, sensors, ...); this picks W.sort_mode and W.use_packet, launches, and folds the packet kernel's census back into `pol`, the
 // policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays*). `acc`: an
-// accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays, `bake`: a pass of rt_bake (rt_kernels.h).
+// accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays, `bake`: a pass of rt_bake, `ids`: of an accumulator with ids (rt_kernels.h).
 // `cam_pos`: rt::single_origin of the pass's camera table: the three floats sensor_ray stores as every ray's origin, or null where no such
 // position exists (several cameras, a caller's rays, a sensor whose rays start on a film or a lens).
 hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos, const WfBake *bake) {
+                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos, const WfBake *bake, const WfIds *ids) {
     // Small passes are bound by launch and host latency, not by memory (a 256 x 256 x 4 render, BASELINE config 1's
     // shape, spent 5.7 ms at 0.6 ms per bounce): RT_SORT_AUTO leaves a pass of fewer than 2^20 paths unsorted, which also spares it
     // the per-bounce queue-size read-back the sort needs: the whole pass is queued without a single host wait.
@@ -181,7 +181,7 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     const rt::WfHostSync hsync = wavefront_host_sync(s);
     unsigned long long census[2] = {0ull, 0ull};
     const hipError_t e = rt::launch_wavefront_pass(s->dev, W, W.stats != nullptr, s->num_cus, first_pass, last_pass, s->stream, time_extends ? &s->ext_events : nullptr, census,
-                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays, bake);
+                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays, bake, ids);
     if (e == hipSuccess && census[0] != 0ull) {
         pol.lanes_x100 = (uint32_t)(100.0 * (double)census[1] / (double)census[0]);
         if ((double)census[1] < min_lanes * (double)census[0])

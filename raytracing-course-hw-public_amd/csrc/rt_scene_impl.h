@@ -219,6 +219,13 @@ struct rt_scene {
             return rt::hip_fail(e, "feature records");
         return RT_OK;
     }
+    // the per-path id records of the passes of an accumulator with ids (WfIds::rec, 4 B per path): as the feature records
+    rt::DevBuf<uint32_t> wf_ids;
+    int ensure_ids() {
+        if (hipError_t e = wf_ids.reserve(wf_paths_cap); e != hipSuccess)
+            return rt::hip_fail(e, "id records");
+        return RT_OK;
+    }
     // the workspace half of a WfLaunch (after ensure_wavefront): queues, hit records, counters, stack workspace, sort buffers
     void wf_bind(WfLaunch &W) {
         W.paths_in = wf_paths[0];
@@ -257,7 +264,7 @@ struct rt_scene {
         // point returns with the stream synchronised. In a group's handle all of them are empty.
         for (rt::DevArena *a : {&wf_owned, &owned, &geo_owned, &light_owned, &env_owned})
             a->reset();
-        wf_feat.reset(), wf_rel.reset(), fb.reset(), rgb8.reset(), rays.reset(), sensors.reset(), film_table.reset();
+        wf_feat.reset(), wf_ids.reset(), wf_rel.reset(), fb.reset(), rgb8.reset(), rays.reset(), sensors.reset(), film_table.reset();
         ext_events.destroy();
         if (ev0)
             (void)hipEventDestroy(ev0);
@@ -285,7 +292,7 @@ int check_pass_params(const rt_params *p, const char *fn);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
 hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
                        const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr,
-                       const WfBake *bake = nullptr);
+                       const WfBake *bake = nullptr, const WfIds *ids = nullptr);
 int run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint64_t n_pixels, uint32_t samples, const std::vector<WfSensor> *table,
                const WfRays *rays, rt_stats *stats, const char *fn, const WfBake *bake = nullptr);
 // the image of a single-GPU scene through the cameras of `table` (views as pinhole records, or the checked records of rt_sensor.cpp)

@@ -526,6 +526,30 @@ __global__ __launch_bounds__(256) void wf_features(const DevScene S, const WfLau
     }
 }
 
+// The ids of the same hits (rt_abi.h rt_accum_attach_ids), for a pass of an accumulator with ids: one u32 per path. Queue position i holds
+// path i here, as for wf_features. PRIMITIVE is what wf_hits_out reports as `prim`; MATERIAL the material of that triangle or primitive;
+// USER the accumulator's table at `prim`.
+__global__ __launch_bounds__(256) void wf_ids(const DevScene S, const WfLaunch L, const WfIds I) {
+    const uint32_t n_in = L.counters[WF_CNT_IN];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_in; i += gridDim.x * blockDim.x) {
+        const WfHead in = wf_load_head(L.paths_in + i);
+        const uint32_t k = wf_load_hit(L.hits + i).k;
+        uint32_t id = RT_ID_MISS;
+        if (k != RT_NONE) {
+            const bool analytic = (k & RT_PRIM_FLAG) != 0u;
+            const uint32_t pi = k & ~RT_PRIM_FLAG;
+            if (I.kind == RT_ID_MATERIAL) {
+                id = analytic ? S.prims[pi].material_id : S.attrs[k].material;
+            } else {
+                id = analytic ? S.n_triangles + pi : S.scene.tris[k].prim;
+                if (I.kind == RT_ID_USER)
+                    id = I.table[id];
+            }
+        }
+        I.rec[in.id] = id;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ shade
 // LIGHTS_LDS: the light BVH (inner nodes, triangles, aux) is small enough (DevBvh::lds_inner) to be staged in LDS once per
 // block; bvh_mix_dist's sample and pdf then read it there: a dozen dependent L1 round trips per hit become LDS reads.
@@ -845,6 +869,47 @@ __global__ __launch_bounds__(256) void wf_resolve_features(const WfAccum A, cons
     }
 }
 
+// The id tables of the same entries (WfIds; the rule: rt_abi.h rt_accum_attach_ids): the lane that owns the pixel takes its k ids in sample
+// order. Runs before wf_resolve_list of the pass, like wf_resolve_features, and reads neither n_p nor the base count: the table itself is the
+// state. K is a run-time value, so the slots are walked in memory (slot-major: a wave's lanes stay coalesced), never in a private array. A
+// sample equal to the one before it, the common case, goes to the slot that one went to without a walk.
+__global__ __launch_bounds__(256) void wf_resolve_ids(const WfAccum A, const WfIds I) {
+    const uint32_t *off = A.list_off + A.first_entry;
+    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
+        const uint32_t p = A.list_pix[A.first_entry + le];
+        const uint32_t k = off[le + 1] - off[le];
+        const uint32_t *src = I.rec + (off[le] - off[0]);
+        uint32_t *sid = I.slot_id + p, *cnt = I.slot_count + p;
+        uint32_t other = I.other[p];
+        uint32_t last_id = 0u, last_j = I.k; // last_j == K: no slot known for last_id
+        for (uint32_t s = 0; s < k; ++s) {
+            const uint32_t id = src[s];
+            if (last_j < I.k && id == last_id) {
+                cnt[(size_t)last_j * I.pixels] += 1u;
+                continue;
+            }
+            uint32_t j = 0;
+            for (; j < I.k; ++j) {
+                const size_t w = (size_t)j * I.pixels;
+                const uint32_t c = cnt[w];
+                if (c == 0u) { // the lowest empty slot: every slot below it holds another id
+                    sid[w] = id;
+                    cnt[w] = 1u;
+                    break;
+                }
+                if (sid[w] == id) {
+                    cnt[w] = c + 1u;
+                    break;
+                }
+            }
+            if (j == I.k)
+                other += 1u;
+            last_id = id, last_j = j;
+        }
+        I.other[p] = other;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ probe: rays in, hits out
 // rt_cast_rays_ex: arbitrary rays go through the SAME closest-hit kernels the renderer launches. wf_from_rays writes them as
 // queue records (what wf_generate / wf_shade write for their rays), wf_hits_out turns the hit records into the probe's output.
@@ -932,7 +997,7 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 
 hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc,
-                                 const WfFeat *feat, const WfRays *rays, const WfBake *bake) {
+                                 const WfFeat *feat, const WfRays *rays, const WfBake *bake, const WfIds *ids) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
@@ -1016,6 +1081,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             WF_LAUNCH(wf_extend_prims, dim3(shade_blocks), block, 0, stream, S, L);
         if (b == 0 && acc && feat) // a feature accumulator's pass: the primary rays' first hits are final here
             WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *feat);
+        if (b == 0 && acc && ids) // ... and so are their ids
+            WF_LAUNCH(wf_ids, dim3(shade_blocks), block, 0, stream, S, L, *ids);
         // Will the next bounce be sorted? Its own bound is not known yet (it arrives one bounce late) but cannot exceed this one, so: may it be.
         // Then this wf_shade writes the sort's input itself, key and slot at the physical slot of every ray it makes, and every slot it leaves
         // empty (the ends of the 64 sub-queue regions) must already hold a pad: RT_RAY_KEY_PAD in the compared bits, behind every real key
@@ -1068,6 +1135,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         const int res_blocks = (int)((acc->n_entries + 255u) / 256u);
         if (feat)
             WF_LAUNCH(wf_resolve_features, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, *acc, *feat);
+        if (ids)
+            WF_LAUNCH(wf_resolve_ids, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, *acc, *ids);
         WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, *acc);
         return hipSuccess;
     }
