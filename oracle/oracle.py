@@ -42,6 +42,7 @@ _PROTOS = {
     "rto_shade_slot_name": (C.c_char_p, [C.c_uint32]),
     "rto_light_pdf": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_walk_census": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_u32_p]),
+    "rto_dump_census": (C.c_int, [_abi.c_u32_p, C.c_uint32, _abi.c_u32_p, C.c_uint32, C.c_uint32, _abi.c_float_p, C.c_uint32, _abi.c_u32_p]),
     "rto_bg_at": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_bg_uv": (None, [_abi.c_float_p, C.c_uint32, C.c_int, _abi.c_float_p]),
     "rto_bvh_info": (C.c_int, [C.c_void_p, C.c_int, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p]),
@@ -256,6 +257,19 @@ class OracleScene:
         order = np.zeros(no.value, dtype=np.uint32)
         _check(lib().rto_bvh_info(self._h, which, C.byref(nn), C.byref(no), C.byref(root), _abi.u32ptr(nodes), _abi.u32ptr(order)))
         return {"root": root.value, "nodes": nodes, "order": order}
+
+
+def dump_census(dump, rays):
+    """walk_census's closest-hit count for a binary tree given as the records the device holds (DeviceScene.bvh_device_dump: {root, nodes
+    (n, 16) uint32, tris (n, 12) uint32}): per ray, the largest number of deferred siblings pending at once when the reference's closest-hit
+    recursion walks THAT tree (rto_dump_census). The way to a census of trees the reference builder does not build."""
+    nodes = np.ascontiguousarray(dump["nodes"], dtype=np.uint32).reshape(-1, 16)
+    tris = np.ascontiguousarray(dump["tris"], dtype=np.uint32).reshape(-1, 12)
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    out = np.zeros(rays.shape[0], dtype=np.uint32)
+    _check(lib().rto_dump_census(_abi.u32ptr(nodes), nodes.shape[0], _abi.u32ptr(tris), tris.shape[0], int(dump["root"]), _abi.fptr(rays), rays.shape[0],
+                                 _abi.u32ptr(out)))
+    return out
 
 
 def fold_outputs(per_sample, rays_per_output=1):

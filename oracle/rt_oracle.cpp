@@ -275,11 +275,10 @@ struct Hit {
 };
 
 // bvh.h:36-65
-inline bool intersect_tri(const Ray &ray, const Tri &tr, float min_dst, V3 &xs_out) {
-    V3 av = tr.v();
-    V3 au = tr.u();
+// (on the triangle as a, v = b - a, u = c - a: the operands the test starts from, and what a DevTri record holds)
+inline bool intersect_avu(const Ray &ray, V3 a, V3 av, V3 au, float min_dst, V3 &xs_out) {
     V3 at = -ray.dir;
-    V3 y = ray.start - tr.a();
+    V3 y = ray.start - a;
     V3 xs = V3{det(y, au, at), det(av, y, at), det(av, au, y)} / det(av, au, at);
     if (xs.x >= 0 && xs.y >= 0 && xs.x + xs.y <= 1 && xs.z >= min_dst) {
         xs_out = xs;
@@ -287,6 +286,7 @@ inline bool intersect_tri(const Ray &ray, const Tri &tr, float min_dst, V3 &xs_o
     }
     return false;
 }
+inline bool intersect_tri(const Ray &ray, const Tri &tr, float min_dst, V3 &xs_out) { return intersect_avu(ray, tr.a(), tr.v(), tr.u(), min_dst, xs_out); }
 // bvh.h:137-152
 inline bool intersect_box(const Ray &ray, const Aabb &box, float min_dst, float &d_out) {
     V3 i1 = (box.lo - ray.start) / ray.dir;
@@ -1269,25 +1269,34 @@ int rto_pixel_samples(rto_scene *s, const rt_params *p, const uint32_t *pixels, 
 }
 
 int rto_cast_rays(rto_scene *s, const float *rays, uint32_t n, uint32_t *prim_out, float *bct_out) {
-    Counters c;
-    for (uint32_t i = 0; i < n; ++i) {
-        Ray r{{rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]}, {rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]}};
-        Hit h;
-        if (s->scene_bvh.root != NO_CHILD)
-            h = s->scene_bvh.intersect_ray(r, EPS, s->scene_bvh.root, c);
-        prim_out[i] = h.has ? h.obj : NO_CHILD;
-        bct_out[3 * i + 0] = h.has ? h.xs.x : 0.0f;
-        bct_out[3 * i + 1] = h.has ? h.xs.y : 0.0f;
-        bct_out[3 * i + 2] = h.has ? h.xs.z : 0.0f;
-        for (size_t k = 0; k < s->prims.size(); ++k) { // analytic primitives: index n_triangles + k, (0, 0, t)
-            float t, nn[3];
-            if (rt_prim_intersect(&s->prims[k], &rays[6 * i], &rays[6 * i + 3], EPS, &t, nn) && (prim_out[i] == NO_CHILD || bct_out[3 * i + 2] > t)) {
-                prim_out[i] = (uint32_t)(s->objects.size() + k);
-                bct_out[3 * i + 0] = bct_out[3 * i + 1] = 0.0f;
-                bct_out[3 * i + 2] = t;
+    auto range = [&](uint32_t begin, uint32_t end) {
+        Counters c;
+        for (uint32_t i = begin; i < end; ++i) {
+            Ray r{{rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]}, {rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]}};
+            Hit h;
+            if (s->scene_bvh.root != NO_CHILD)
+                h = s->scene_bvh.intersect_ray(r, EPS, s->scene_bvh.root, c);
+            prim_out[i] = h.has ? h.obj : NO_CHILD;
+            bct_out[3 * i + 0] = h.has ? h.xs.x : 0.0f;
+            bct_out[3 * i + 1] = h.has ? h.xs.y : 0.0f;
+            bct_out[3 * i + 2] = h.has ? h.xs.z : 0.0f;
+            for (size_t k = 0; k < s->prims.size(); ++k) { // analytic primitives: index n_triangles + k, (0, 0, t)
+                float t, nn[3];
+                if (rt_prim_intersect(&s->prims[k], &rays[6 * i], &rays[6 * i + 3], EPS, &t, nn) && (prim_out[i] == NO_CHILD || bct_out[3 * i + 2] > t)) {
+                    prim_out[i] = (uint32_t)(s->objects.size() + k);
+                    bct_out[3 * i + 0] = bct_out[3 * i + 1] = 0.0f;
+                    bct_out[3 * i + 2] = t;
+                }
             }
         }
-    }
+    };
+    const uint32_t n_workers = std::max(1u, std::min({16u, std::thread::hardware_concurrency(), n / 256u})); // rays are independent
+    std::vector<std::thread> workers;
+    for (uint32_t w = 1; w < n_workers; ++w)
+        workers.emplace_back(range, (uint32_t)((uint64_t)n * w / n_workers), (uint32_t)((uint64_t)n * (w + 1) / n_workers));
+    range(0, (uint32_t)((uint64_t)n / n_workers));
+    for (auto &t : workers)
+        t.join();
     return RT_OK;
 }
 
@@ -1425,6 +1434,101 @@ int rto_walk_census(rto_scene *s, const float *rays, uint32_t n, uint32_t *close
     range(0, (uint32_t)((uint64_t)n / n_workers));
     for (auto &t : workers)
         t.join();
+    return RT_OK;
+}
+
+// Test aid: rto_walk_census's closest-hit count for a binary tree given as the records the device holds (rt_bvh_device_dump: node records of 16
+// words, child boxes in words 0..11 and child references in words 12, 13; triangle records of 12 words, a, b - a, c - a in words 0..8, leaf flags
+// in word 10; a reference is an inner index, or 0x80000000 | count << 27 | first record, count 0 = up to the record flagged last). The walk is
+// intersect_ray's (bvh.h:195-235) with its own box and triangle tests: both children hit = the nearer first (the left one unless d_left >
+// d_right), the other deferred, and pruned when the near subtree found a hit no farther than its d. This is how the census reaches trees the
+// reference builder does not build (the device builders'); on the flattened reference tree it is rto_walk_census (tests/test_walk_census.py).
+namespace {
+struct DumpWalk {
+    const uint32_t *nodes, *tris;
+    uint32_t n_inner, n_tris;
+    static constexpr uint32_t LEAF_FLAG = 0x80000000u, LEAF_BEGIN_MASK = 0x07FFFFFFu;
+    uint32_t pending = 0, max_pending = 0, depth = 0;
+    bool bad = false;
+    static V3 v3(const uint32_t *w) {
+        V3 v;
+        std::memcpy(&v, w, sizeof(v));
+        return v;
+    }
+    // the closest t below `ref` (INFINITY: none): all the pruning rule looks at
+    float walk(const Ray &ray, uint32_t ref) {
+        float best = INFINITY;
+        if (ref & LEAF_FLAG) {
+            uint32_t k = ref & LEAF_BEGIN_MASK, cnt = (ref >> 27) & 15u;
+            for (;; ++k) {
+                if (k >= n_tris) {
+                    bad = true;
+                    return best;
+                }
+                const uint32_t *t = tris + 12ull * k;
+                V3 xs;
+                if (intersect_avu(ray, v3(t), v3(t + 3), v3(t + 6), EPS, xs) && best > xs.z)
+                    best = xs.z;
+                if (cnt ? --cnt == 0 : (t[10] & 1u) != 0)
+                    return best;
+            }
+        }
+        if (ref >= n_inner || ++depth > 4096u) {
+            bad = true;
+            return best;
+        }
+        const uint32_t *nd = nodes + 16ull * ref;
+        float d_left = 0, d_right = 0;
+        const bool hl = intersect_box(ray, Aabb{v3(nd), v3(nd + 3)}, EPS, d_left), hr = intersect_box(ray, Aabb{v3(nd + 6), v3(nd + 9)}, EPS, d_right);
+        if (hl && hr) {
+            uint32_t id1 = nd[12], id2 = nd[13];
+            if (d_left > d_right) {
+                std::swap(id1, id2);
+                std::swap(d_left, d_right);
+            }
+            max_pending = std::max(max_pending, ++pending);
+            best = walk(ray, id1);
+            --pending;
+            if (best > d_right) // !intr.has || intr.xs.z > d_right
+                best = std::min(best, walk(ray, id2));
+        } else if (hl) {
+            best = walk(ray, nd[12]);
+        } else if (hr) {
+            best = walk(ray, nd[13]);
+        }
+        --depth;
+        return best;
+    }
+};
+} // namespace
+int rto_dump_census(const uint32_t *nodes, uint32_t n_inner, const uint32_t *tris, uint32_t n_tris, uint32_t root, const float *rays, uint32_t n, uint32_t *pending_out) {
+    if ((n_inner && !nodes) || (n_tris && !tris) || (n && (!rays || !pending_out))) {
+        g_err = "rto_dump_census: bad arguments";
+        return RT_ERR_INVALID_ARG;
+    }
+    std::atomic<bool> bad{false};
+    auto range = [&](uint32_t begin, uint32_t end) {
+        for (uint32_t i = begin; i < end; ++i) {
+            Ray r{{rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]}, {rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]}};
+            DumpWalk w{nodes, tris, n_inner, n_tris};
+            if (root != NO_CHILD)
+                (void)w.walk(r, root);
+            pending_out[i] = w.max_pending;
+            if (w.bad)
+                bad = true;
+        }
+    };
+    const uint32_t n_workers = std::max(1u, std::min({16u, std::thread::hardware_concurrency(), n / 256u})); // rays are independent
+    std::vector<std::thread> workers;
+    for (uint32_t w = 1; w < n_workers; ++w)
+        workers.emplace_back(range, (uint32_t)((uint64_t)n * w / n_workers), (uint32_t)((uint64_t)n * (w + 1) / n_workers));
+    range(0, (uint32_t)((uint64_t)n / n_workers));
+    for (auto &t : workers)
+        t.join();
+    if (bad) {
+        g_err = "rto_dump_census: a reference points outside the records, or the records are no tree";
+        return RT_ERR_INVALID_ARG;
+    }
     return RT_OK;
 }
 

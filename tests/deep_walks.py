@@ -5,6 +5,8 @@ with large overlapping triangles, or the scene is a soup of long needles whose b
 
 Shared by tests/test_gpu_deep_walks.py, tests/test_oracle_golden.py and tests/golden/make_live_golden.py. Which tier a ray reaches is not
 assumed: OracleScene.walk_census counts it, and `tier_shares` / `require_witnesses` turn the counts into the conditions the tests assert.
+The second half of the file goes beyond what a reference-built tree can reach (19 frames): a scene that makes the device's radix tree 41 or
+46 deep, and a census of the tree the device built (tests/test_gpu_deep_device_trees.py, tests/test_walk_census.py).
 
 Pending counts f (deferred far siblings at once) and the tier they enter:
   light walk    f >= 5   wf_shade's scratch half (4 LDS positions)            f >= 13  the probe's / megakernel's scratch half (12 LDS positions)
@@ -13,6 +15,7 @@ Pending counts f (deferred far siblings at once) and the tier they enter:
 """
 import numpy as np
 
+from bvh_dump import LEAF, MASK, NONE
 from conftest import random_rays
 
 LIGHT_SHADE_SCRATCH = 5    # lights_pdf through StackMemT<4>: position 4 is the first in scratch
@@ -138,3 +141,276 @@ def require_witnesses(what, counts, required):
     for t, need in required.items():
         assert shares[int(t)] >= need, f"{what}: only {100 * shares[int(t)]:.2f} % of the rays keep {t} siblings pending, the test needs {100 * need:.0f} %"
     return shares, most
+
+
+# ------------------------------------------------------------------------------------------------ deep trees from the device's radix builder
+# The reference builder's SAH tree cannot be made deep, so no scene above keeps more than 19 frames pending. The Karras radix tree of
+# csrc/rt_bvh_device.hip (RT_BUILDER_LBVH) can: it splits at the bits of a 30-bit Morton code and, inside a run of equal codes, at the bits of
+# the leaf index. `corner_ladder_scene` gives every one of the 30 code bits a split whose two boxes both hold the scene's corner, and ends the
+# chain in a run of 2^log2_soup equal codes around that corner: a ray that starts there defers a sibling at every level. Which count a ray
+# really reaches is read off the tree the device built (`dump_census`), and `radix_tree_dump` restates the builder, so that the depth is a
+# prediction a CPU test pins.
+LADDER_BITS = 10           # Morton bits per axis (k_keys: 1024 cells along every axis)
+CORNER_EXTENT = 32.0
+CORNER_CELL = CORNER_EXTENT / 1024.0
+CORNER_MAIN = dict(log2_soup=10, seed=61)    # 1 056 triangles: radix tree 41 deep, up to 40 frames pending
+CORNER_SECOND = dict(log2_soup=15, seed=62)  # 32 800 triangles: 46 deep, up to 45 pending
+CORNER_DEPTH = {10: 41, 15: 46}              # 30 Morton bits, the corner pin against the soup, log2_soup index bits
+
+
+def corner_ladder_scene(sg, log2_soup, seed, extent=CORNER_EXTENT):
+    """A scene whose radix tree is 31 + log2_soup deep, with cell = extent / 1024 (one Morton cell when the far pin bounds the scene):
+      * a ladder of 30 triangles, one per Morton bit b = 0..9 and axis a = 0..2: centroid c with c[a] = 1.1 * 2^b cells and 0.4 * 2^b cells on
+        the other two axes, vertices 0, 1.5 c + w and 1.5 c - w with w uniform in +-0.5 c per component. The highest set bit of the
+        centroid's Morton code is bit b of axis a, and the triangle's box has the corner (0, 0, 0) as its minimum;
+      * two pins of 1e-3 cell, at the corner and at (extent, extent, extent);
+      * a soup of 2^log2_soup triangles with vertices uniform in [0.02, 0.98]^3 cells: one Morton cell, split by leaf-index bits alone.
+    (A ladder vertex of bit 9 may reach 1.1 * extent: the cells then shrink by up to 1 / 1.1, which keeps every centroid's highest bit.) Every
+    coordinate is 0 or within the exact fast-division range [2^-37, 2^40] of the traversal. The camera sits at 0.5 cell (1, 1, 1) and looks
+    along (1, 1, 1). Material 0 is plain, material 1 emits: the ladder's first triangle (bit 0, axis 0: it crosses the soup's cell) and every
+    4th soup triangle. The ladder triangle alone leaves every render black, whichever of the 30 it is: no ladder triangle comes nearer than
+    0.4 cell to the camera, and a path in the soup moves 0.005 cell per bounce (the oracle, 48x32x2: no pixel above 0, no ray of the
+    replayed paths reaches the emitter), so an image could not tell a wrong hit from a right one. Triangle order: soup, corner pin, far pin, ladder (bit-major): the run of equal codes is then leaves 0 .. 2^log2_soup (the
+    corner pin last), which the leaf-index bits halve log2_soup times."""
+    rng = np.random.default_rng(seed)
+    cell = extent / 1024.0
+    ladder = np.zeros((3 * LADDER_BITS, 3, 3))
+    for b in range(LADDER_BITS):
+        for a in range(3):
+            c = np.full(3, 0.4 * 2.0 ** b)
+            c[a] = 1.1 * 2.0 ** b
+            w = rng.uniform(-0.5, 0.5, size=3) * c
+            ladder[3 * b + a, 1], ladder[3 * b + a, 2] = 1.5 * c + w, 1.5 * c - w
+    e = 1e-3
+    pins = np.array([[[0, 0, 0], [e, 0, 0], [0, e, 0]], [[1024, 1024, 1024], [1024 - e, 1024, 1024], [1024, 1024 - e, 1024]]], dtype=np.float64)
+    soup = rng.uniform(0.02, 0.98, size=(2 ** log2_soup, 3, 3))
+    pos = (np.concatenate([soup, pins, ladder]) * cell).astype(np.float32)
+    n = len(pos)
+    nz = np.abs(pos[pos != 0])
+    assert (pos >= 0).all() and nz.min() >= 2.0 ** -37 and nz.max() <= 2.0 ** 40
+    tan = np.zeros((n, 3, 3), dtype=np.float32)
+    tan[..., 0] = 1.0
+    ids = np.zeros(n, dtype=np.uint32)
+    ids[len(soup) + len(pins)] = 1
+    ids[0 : len(soup) : 4] = 1
+    mats = [sg.Material(color=(0.8, 0.8, 0.8, 1.0), roughness=1.0, metallic=0.0),
+            sg.Material(color=(1.0, 1.0, 1.0, 1.0), emission=(1.0, 0.9, 0.8), emissive_strength=2.0, roughness=1.0, metallic=0.0)]
+    f32 = lambda v: (np.asarray(v, dtype=np.float64) / np.linalg.norm(v)).astype(np.float32)  # noqa: E731
+    fwd, right = f32([1, 1, 1]), f32([-1, 0, 1])  # right = forward x (0, 1, 0), up = right x forward, as scenegen.look_camera's basis
+    cam = sg.Camera(position=np.full(3, 0.5 * cell, dtype=np.float32), right=right, up=f32(np.cross([-1, 0, 1], [1, 1, 1])), forward=fwd,
+                    fov_x=sg.look_camera((0, 0, 0)).fov_x)
+    return sg.Scene(positions=pos, normals=None, texcoords=np.zeros((n, 3, 2), dtype=np.float32), tangents=tan, material_ids=ids, materials=mats,
+                    textures=[], camera=cam)
+
+
+def corner_rays(cell, n, seed):
+    """Rays that start inside every box on the path to the soup of a corner_ladder_scene: origins uniform in [0.3, 0.7]^3 cells, directions
+    in the positive octant (components uniform in [0.3, 1] before normalising: at least 0.2 after)."""
+    rng = np.random.default_rng(seed)
+    o = rng.uniform(0.3, 0.7, size=(n, 3)) * cell
+    d = rng.uniform(0.3, 1.0, size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return np.concatenate([o, d], axis=1).astype(np.float32)
+
+
+def _spread10(v):
+    v = v.astype(np.uint32) & np.uint32(1023)
+    for shift, mask in ((16, 0x030000FF), (8, 0x0300F00F), (4, 0x030C30C3), (2, 0x09249249)):
+        v = (v | (v << np.uint32(shift))) & np.uint32(mask)
+    return v
+
+
+def morton_keys(positions):
+    """k_keys of csrc/rt_bvh_device.hip in float32: the 30-bit Morton code of every triangle's centre, (p0 + p1 + p2) / 3, on the 1024^3 grid of
+    the bounds of all vertices (x in bits 0, 3, ..., y one above, z two above)."""
+    p = np.ascontiguousarray(positions, dtype=np.float32)
+    lo, hi = p.reshape(-1, 3).min(axis=0), p.reshape(-1, 3).max(axis=0)
+    ext = hi - lo
+    with np.errstate(divide="ignore"):
+        inv = np.where(ext > 0, np.float32(1024.0) / ext, np.float32(0.0)).astype(np.float32)
+    ctr = ((p[:, 0] + p[:, 1]) + p[:, 2]) / np.float32(3.0)
+    q = np.minimum(np.maximum((ctr - lo) * inv, np.float32(0.0)), np.float32(1023.0)).astype(np.uint32)
+    return _spread10(q[:, 0]) | (_spread10(q[:, 1]) << np.uint32(1)) | (_spread10(q[:, 2]) << np.uint32(2))
+
+
+def radix_tree_dump(positions):
+    """The tree RT_BUILDER_LBVH builds of `positions` (one triangle per leaf), restated in numpy and returned as a bvh_device_dump record set
+    {root, nodes, tris} plus "order" (the leaf order) and "keys" (the Morton codes, in triangle order):
+      * the leaves are the triangles in the stable order of their Morton codes (radix_sort_pairs); leaf k has the 64-bit key code << 32 | k;
+      * Karras 2012: the node over leaves [lo, hi] splits after the last leaf that shares with leaf lo more leading key bits than leaf hi does;
+        an inner child takes the index of the end of its range that touches the split (left: its last leaf, right: its first), the root is 0;
+      * every stored child box is the box of the vertices below (k_refit)."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32)
+    n = len(pos)
+    codes = morton_keys(pos)
+    order = np.argsort(codes, kind="stable").astype(np.uint32)
+    keys = (codes[order].astype(np.uint64) << np.uint64(32)) | np.arange(n, dtype=np.uint64)
+    p = pos[order]
+    tris = np.zeros((n, 12), dtype=np.uint32)
+    tris[:, 0:3] = p[:, 0].view(np.uint32)
+    tris[:, 3:6] = (p[:, 1] - p[:, 0]).astype(np.float32).view(np.uint32)
+    tris[:, 6:9] = (p[:, 2] - p[:, 0]).astype(np.float32).view(np.uint32)
+    tris[:, 9] = order
+    tris[:, 10] = 3  # first and last triangle of its leaf
+    out = {"order": order, "keys": codes, "tris": tris, "nodes": np.zeros((max(n - 1, 0), 16), dtype=np.uint32)}
+    if n <= 1:
+        out["root"] = (LEAF | (1 << 27)) if n else NONE
+        return out
+    tlo, thi = p.min(axis=1), p.max(axis=1)
+    nodes = out["nodes"]
+    boxes = nodes[:, :12].view(np.float32)
+    todo = [(0, 0, n - 1)]
+    while todo:
+        i, lo, hi = todo.pop()
+        top = int(keys[lo] ^ keys[hi]).bit_length() - 1  # the highest bit in which the range's keys differ
+        first_set = ((int(keys[lo]) >> top) | 1) << top  # the smallest key with lo's prefix and that bit set
+        g = int(np.searchsorted(keys, np.uint64(first_set), side="left")) - 1
+        assert lo <= g < hi
+        for side, (a, b, idx) in enumerate(((lo, g, g), (g + 1, hi, g + 1))):
+            boxes[i, 6 * side : 6 * side + 3] = tlo[a : b + 1].min(axis=0)
+            boxes[i, 6 * side + 3 : 6 * side + 6] = thi[a : b + 1].max(axis=0)
+            if a == b:
+                nodes[i, 12 + side] = LEAF | (1 << 27) | a
+            else:
+                nodes[i, 12 + side] = idx
+                todo.append((idx, a, b))
+    out["root"] = 0
+    return out
+
+
+def dump_depth(dump):
+    """Edges on the longest path from the root of a bvh_device_dump record set to a leaf."""
+    if dump["root"] == NONE or dump["root"] & LEAF:
+        return 0
+    refs = dump["nodes"][:, 12:14]
+    level, depth = np.array([dump["root"]], dtype=np.uint32), 0
+    while len(level):
+        depth += 1
+        kids = refs[level].reshape(-1)
+        level = kids[(kids & LEAF) == 0]
+    return depth
+
+
+def _first_max(v):  # *std::max_element over the last axis: the FIRST largest, by operator<
+    m = v[..., 0]
+    for k in (1, 2):
+        m = np.where(m < v[..., k], v[..., k], m)
+    return m
+
+
+def _first_min(v):
+    m = v[..., 0]
+    for k in (1, 2):
+        m = np.where(v[..., k] < m, v[..., k], m)
+    return m
+
+
+def _det(c1, c2, c3):  # dot(c1, crs(c2, c3)) with the reference's operation order, float32
+    x = c2[:, 1] * c3[:, 2] - c2[:, 2] * c3[:, 1]
+    y = c2[:, 2] * c3[:, 0] - c2[:, 0] * c3[:, 2]
+    z = c2[:, 0] * c3[:, 1] - c2[:, 1] * c3[:, 0]
+    return c1[:, 0] * x + c1[:, 1] * y + c1[:, 2] * z
+
+
+def dump_census(dump, rays):
+    """OracleScene.walk_census's closest-hit count for the tree the DEVICE built: per ray, the largest number of deferred siblings pending at
+    once when the reference's traversal rule (oracle/rt_oracle.cpp BVH::intersect_ray, which every binary closest-hit kernel follows) walks a
+    bvh_device_dump record set. The oracle's own box and triangle tests walk the records (oracle.dump_census); `dump_census_numpy` states the
+    rule a second time, and tests/test_walk_census.py holds both to walk_census on flattened reference trees."""
+    import oracle
+
+    return oracle.dump_census(dump, rays).astype(np.int64)
+
+
+def dump_census_numpy(dump, rays, eps=1e-4, max_stack=256):
+    """dump_census restated in numpy (slow: for a few thousand rays on small trees). OracleScene.walk_census's closest-hit count for a tree given as a bvh_device_dump record set (child boxes in words 0..11 of a node record,
+    child references in words 12 and 13, triangles as a, b - a, c - a): for every ray the largest number of deferred siblings pending at once
+    under the reference's traversal rule (oracle/rt_oracle.cpp BVH::intersect_ray), which every binary closest-hit kernel follows:
+      * a child is hit when t_min <= t_max and t_max >= eps of the float32 slabs (intersect_box), its distance is d = max(t_min, eps);
+      * both children hit: the left one is walked first unless d_left > d_right, and the other is deferred (one more pending);
+      * when the near subtree is done the deferred child is entered, unless the near subtree found a hit with t <= its d (pruned).
+    All of it in float32 with the reference's operation order (min / max and the first-largest rule of std::max_element included), so the counts
+    ARE walk_census's when the dump is the flattened reference tree (tests/test_walk_census.py). All rays walk in lockstep, one node or one
+    triangle per step."""
+    nodes, tris, root = dump["nodes"], dump["tris"], int(dump["root"])
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = len(rays)
+    most = np.zeros(n, dtype=np.int64)
+    if root == NONE or n == 0:
+        return most
+    eps = np.float32(eps)
+    boxes = np.ascontiguousarray(nodes[:, :12]).view(np.float32).reshape(-1, 2, 2, 3)  # [node, child, lo / hi, axis]
+    refs = np.ascontiguousarray(nodes[:, 12:14])
+    tf = np.ascontiguousarray(tris[:, :9]).view(np.float32)
+    ta, tv, tu = tf[:, 0:3], tf[:, 3:6], tf[:, 6:9]
+    last = (tris[:, 10] & 1) != 0
+    # per ray, by original index: the stack of deferred children, and best[r, k] = the closest hit found since k frames were pending
+    sp = np.zeros(n, dtype=np.int64)
+    st_ref = np.zeros((n, max_stack), dtype=np.uint32)
+    st_d = np.zeros((n, max_stack), dtype=np.float32)
+    best = np.full((n, max_stack + 1), np.inf, dtype=np.float32)
+    # the rays still walking (compacted): original index, origin, direction, current reference
+    idx = np.arange(n)
+    o, d = rays[:, :3].copy(), rays[:, 3:].copy()
+    cur = np.full(n, root, dtype=np.uint32)
+    with np.errstate(all="ignore"):
+        while len(idx):
+            is_leaf = (cur & LEAF) != 0
+            pop = np.zeros(len(idx), dtype=bool)
+            L = np.flatnonzero(is_leaf)
+            if len(L):  # one triangle of the leaf: the reference's intersect_tri
+                ref = cur[L]
+                k = (ref & MASK).astype(np.int64)
+                cnt = (ref >> 27) & 15
+                av, au, at, y = tv[k], tu[k], -d[L], o[L] - ta[k]
+                den = _det(av, au, at)
+                xb, xc, xt = _det(y, au, at) / den, _det(av, y, at) / den, _det(av, au, y) / den
+                hit = (xb >= 0) & (xc >= 0) & (xb + xc <= 1) & (xt >= eps)
+                r = idx[L[hit]]
+                best[r, sp[r]] = np.minimum(best[r, sp[r]], xt[hit])
+                done = np.where(cnt > 0, cnt == 1, last[k])
+                cur[L] = np.where(cnt > 0, LEAF | ((cnt - 1) << 27) | (k + 1).astype(np.uint32), LEAF | (k + 1).astype(np.uint32)).astype(np.uint32)
+                pop[L[done]] = True
+            I = np.flatnonzero(~is_leaf)
+            if len(I):  # an inner node: the reference's intersect_box on both children
+                nd = cur[I]
+                b = boxes[nd]
+                i12 = (b - o[I][:, None, None, :]) / d[I][:, None, None, :]
+                i1, i2 = i12[:, :, 0], i12[:, :, 1]
+                t_min = _first_max(np.where(i2 < i1, i2, i1))  # std::min(a, b) = b < a ? b : a
+                t_max = _first_min(np.where(i1 < i2, i2, i1))  # std::max(a, b) = a < b ? b : a
+                hit = (t_min <= t_max) & (t_max >= eps)
+                dist = np.where(t_min < eps, eps, t_min)
+                kid = refs[nd]
+                both = hit[:, 0] & hit[:, 1]
+                right_first = (both & (dist[:, 0] > dist[:, 1])) | (~hit[:, 0] & hit[:, 1])
+                near = np.where(right_first, kid[:, 1], kid[:, 0])
+                cur[I] = near
+                pop[I[~hit[:, 0] & ~hit[:, 1]]] = True
+                B = np.flatnonzero(both)
+                if len(B):
+                    r = idx[I[B]]
+                    s = sp[r]
+                    assert s.max() < max_stack, "dump_census_numpy: more frames pending than max_stack"
+                    st_ref[r, s] = np.where(right_first[B], kid[B, 0], kid[B, 1])
+                    st_d[r, s] = np.where(right_first[B], dist[B, 0], dist[B, 1])
+                    best[r, s + 1] = np.inf
+                    sp[r] = s + 1
+                    most[r] = np.maximum(most[r], s + 1)
+            P = np.flatnonzero(pop)
+            finished = np.zeros(len(idx), dtype=bool)
+            while len(P):  # the subtree is done: enter the newest deferred child, or prune it and look at the next
+                r = idx[P]
+                s = sp[r]
+                finished[P[s == 0]] = True
+                P, r, s = P[s > 0], r[s > 0], s[s > 0]
+                found = best[r, s]
+                sp[r] = s - 1
+                best[r, s - 1] = np.minimum(best[r, s - 1], found)
+                enter = ~(found <= st_d[r, s - 1])  # bvh.h: if (!intr.has || intr.t > d_right)
+                cur[P[enter]] = st_ref[r[enter], s[enter] - 1]
+                P = P[~enter]
+            if finished.any():
+                keep = ~finished
+                idx, o, d, cur = idx[keep], o[keep], d[keep], cur[keep]
+    return most

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import hit_contract
+from bvh_dump import LEAF, MASK, flatten_reference
 from conftest import random_rays
 from hit_contract import explain_pixels, summary, verify_hits
 
@@ -21,43 +22,6 @@ def _report_hit_contract_time():
     yield
     print(f"\n[hit contract] {hit_contract.STATS['seconds'] - t0:.1f} s of this module's run spent in verify_hits / explain_pixels")
 
-LEAF = 0x80000000
-MASK = 0x07FFFFFF
-
-
-def _flatten_reference(info, positions):
-    """numpy restatement of the DevNode / DevTri layout (DESIGN.md 'Data layout in HBM') from rt_bvh_info's node list."""
-    nodes, order = info["nodes"], info["order"]
-    inner = nodes[:, 6] != 0xFFFFFFFF
-    dev_index = np.cumsum(inner) - 1
-
-    def ref(i):
-        if inner[i]:
-            return int(dev_index[i])
-        b, e = int(nodes[i, 8]), int(nodes[i, 9])
-        cnt = e - b
-        return LEAF | ((cnt << 27) if 1 <= cnt <= 8 else 0) | b
-
-    out = np.zeros((int(inner.sum()), 16), dtype=np.uint32)
-    for i in np.nonzero(inner)[0]:
-        l, r = int(nodes[i, 6]), int(nodes[i, 7])
-        out[dev_index[i], 0:6] = nodes[l, 0:6]
-        out[dev_index[i], 6:12] = nodes[r, 0:6]
-        out[dev_index[i], 12] = ref(l)
-        out[dev_index[i], 13] = ref(r)
-    p = positions[order].astype(np.float32)
-    tris = np.zeros((len(order), 12), dtype=np.uint32)
-    tris[:, 0:3] = p[:, 0].view(np.uint32)
-    tris[:, 3:6] = (p[:, 1] - p[:, 0]).astype(np.float32).view(np.uint32)
-    tris[:, 6:9] = (p[:, 2] - p[:, 0]).astype(np.float32).view(np.uint32)
-    tris[:, 9] = order
-    leaves = nodes[~inner]
-    leaves = leaves[leaves[:, 9] > leaves[:, 8]]
-    tris[leaves[:, 9] - 1, 10] |= 1
-    tris[leaves[:, 8], 10] |= 2
-    return out, tris, ref(info["root"]) if info["root"] != 0xFFFFFFFF else 0xFFFFFFFF
-
-
 @pytest.mark.parametrize("name", ["room_plain", "boxes", "room_manylights"])
 def test_device_memory_holds_the_reference_topology(gpu, scenes, name):
     sc = scenes[name]
@@ -65,7 +29,7 @@ def test_device_memory_holds_the_reference_topology(gpu, scenes, name):
     try:
         for which in (0, 1):
             info, dump = dev.bvh_info(which), dev.bvh_device_dump(which)
-            nodes, tris, root = _flatten_reference(info, sc.positions)
+            nodes, tris, root = flatten_reference(info, sc.positions)
             assert dump["root"] == root
             assert np.array_equal(dump["nodes"][:, :14], nodes[:, :14]), which
             assert np.array_equal(dump["tris"][:, :11], tris[:, :11]), which
