@@ -1,7 +1,7 @@
 // rt_accum.hip — the per-round kernels of the sample accumulators (include/rt_abi.h rt_accum_*).
 //
 // A round of an accumulator is: judge (which pixels get how many new samples), plan (the list of entries (p, k_p) in pixel order and the
-// exclusive prefix of k_p), then the wavefront pipeline's passes over that list (rt_wavefront.hip: wf_generate_list, the unchanged
+// exclusive prefix of k_p), then the wavefront pipeline's passes over that list (rt_wf_stages.h: the first stage over WfFromList, the unchanged
 // extend / shade / fold kernels, wf_resolve_list). Everything here is O(pixels) with one lane per pixel and no float atomics: the list
 // comes out of a deterministic scan, so the same state always plans the same list.
 #include <cmath>

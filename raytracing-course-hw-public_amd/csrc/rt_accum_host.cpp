@@ -116,21 +116,13 @@ extern "C" int rt_accum_create_sensor(rt_scene *s, uint32_t width, uint32_t heig
 
 extern "C" void rt_accum_destroy(rt_accum *acc) { delete acc; }
 
-static int accum_check(const rt_accum *a, const rt_params *p, const char *fn) {
+static int accum_check(const rt_accum *a, const rt_params *p, const char *fn, bool reads_samples) {
     if (!a || !p)
         return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null argument");
     if (p->width != a->width || p->height != a->height)
         return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": params size " + std::to_string(p->width) + "x" + std::to_string(p->height) +
                                                 " differs from the accumulator's " + std::to_string(a->width) + "x" + std::to_string(a->height));
-    if (p->shard_count > 1 || (p->flags & RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": shard_count > 1 and RT_FLAG_DEVICE_FB do not apply to an accumulator");
-    if (p->rng_mode == RT_RNG_REFERENCE)
-        return rt::fail(RT_ERR_UNSUPPORTED, std::string(fn) + ": the reference RNG draws a 256-pixel span as one sequential stream; accumulators need RT_RNG_DEVICE");
-    if (p->rng_mode != RT_RNG_DEVICE)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": unknown rng_mode");
-    if (p->flags & RT_FLAG_MEGAKERNEL)
-        return rt::fail(RT_ERR_UNSUPPORTED, std::string(fn) + ": accumulators run on the wavefront pipeline, not the megakernel");
-    return rt::check_pass_params(p, fn);
+    return rt::check_wavefront_entry(p, fn, "accumulators", ~(uint32_t)RT_FLAG_DEVICE_FB, reads_samples); // every flag but the one that does not apply
 }
 
 // rt_accum_render (ad == nullptr: params->samples more samples for every pixel) and rt_accum_render_adaptive. A judge (or the uniform step)
@@ -161,8 +153,6 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
     W.view_pixels = n_pix;
     W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
     W.stats = counters ? s->d_stats : nullptr;
-    const float *cam_pos = rt::single_origin(&a->sensor, 1); // the one origin of the pass's rays, where it has one (rt_render.cpp launch_pass)
-    s->ext_events.reset();
     uint32_t passes = 0, packet_passes = 0, rounds = 0;
     uint64_t added = 0;
     // rt_accum_render's progress: per pass, of the passes the call will run (every pixel, samples in lists of at most chunk_cap)
@@ -199,12 +189,12 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
             W.accum = nullptr; // wf_resolve does not run on an accumulator pass
             for (uint32_t e0 = 0; e0 < tot[0]; e0 += per_pass) {
                 WfAccum A{a->R.sum, a->R.even_sum, a->R.count, a->R.list_pix, a->R.list_base, a->R.list_off, e0, std::min(per_pass, tot[0] - e0)};
-                W.n_paths = (uint32_t)std::min<uint64_t>((uint64_t)A.n_entries * C, tot[1]); // an upper bound: wf_generate_list reads the exact count
+                W.n_paths = (uint32_t)std::min<uint64_t>((uint64_t)A.n_entries * C, tot[1]); // an upper bound: the first stage reads the exact count
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
                 a->has_samples = true;
-                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, 1, true, true, stats != nullptr, &A, a->features ? &a->F : nullptr, nullptr, cam_pos, nullptr,
-                                        a->ids ? &a->I : nullptr));
+                const rt::WfPassKind kind = rt::WfPassKind::list(A, a->features ? &a->F : nullptr, a->ids ? &a->I : nullptr, a->sensor);
+                HIP_TRY(rt::launch_pass(s, p, a->pkt, W, kind, rt::WfPassStep{true, true, stats != nullptr}));
                 passes += 1;
                 packet_passes += W.use_packet;
                 if (p->progress && !ad) {
@@ -216,10 +206,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
         }
     };
 
-    auto queue = [&]() -> int {
-        if (counters)
-            HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
-        HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    auto rounds_of_call = [&]() -> int {
         if (!ad) {
             HIP_TRY(rt::launch_accum_uniform(a->R, p->samples, s->stream));
             bool any = false;
@@ -242,19 +229,15 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 }
             }
         }
-        HIP_TRY(hipEventRecord(s->ev1, s->stream));
         return RT_OK;
     };
-    if (int rc = rt::queue_and_wait(s, queue); rc != RT_OK)
+    if (int rc = rt::timed_call(s, counters, [] { return RT_OK; }, rounds_of_call); rc != RT_OK)
         return rc;
     if (rounds_out)
         *rounds_out = rounds;
     if (stats) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-        if (int rc = rt::fill_stats(s, counters, added, ms, wall0, stats); rc != RT_OK)
+        if (int rc = rt::fill_stats(s, counters, added, wall0, a->pkt.lanes_x100, stats); rc != RT_OK)
             return rc;
-        stats->packet_lanes_x100 = a->pkt.lanes_x100;
         stats->passes = passes;
         stats->packet_passes = packet_passes;
     }
@@ -262,15 +245,13 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
 }
 
 extern "C" int rt_accum_render(rt_accum *acc, const rt_params *params, rt_stats *stats) {
-    if (int rc = accum_check(acc, params, "rt_accum_render"); rc != RT_OK)
+    if (int rc = accum_check(acc, params, "rt_accum_render", true); rc != RT_OK)
         return rc;
-    if (params->samples == 0)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render: samples must be >= 1");
     return accum_run(acc, params, nullptr, nullptr, stats);
 }
 
 extern "C" int rt_accum_render_adaptive(rt_accum *acc, const rt_params *params, const rt_adaptive *ad, uint32_t *rounds, rt_stats *stats) {
-    if (int rc = accum_check(acc, params, "rt_accum_render_adaptive"); rc != RT_OK)
+    if (int rc = accum_check(acc, params, "rt_accum_render_adaptive", false); rc != RT_OK)
         return rc;
     if (!ad)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render_adaptive: null argument");

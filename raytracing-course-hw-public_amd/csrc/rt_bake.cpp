@@ -1,8 +1,9 @@
 // rt_bake.cpp — rt_bake / rt_bake_rays / rt_lightmap_points (rt_abi.h): irradiance, SH probes and light-map texels on the device.
 //
 // rt_bake has rt_rays.cpp's shape: validate, stage host points through the scene's ray staging buffer, rt_render's own pass loop
-// (rt_render.cpp run_passes) over n_points "pixels" x samples, copy out. Only the first stage (wf_generate_bake makes each sample's ray from
-// the point, rt_dev_bake.h) and the last (wf_resolve_bake folds as the kind asks) differ; bounces and wf_fold are rt_render's own launches.
+// (rt_render.cpp run_passes) over n_points "pixels" x samples, copy out. The passes are of the kind WfPassKind::bake (rt_kernels.h): only the
+// first stage's source (each sample's ray is made from the point, rt_dev_bake.h) and the last stage (wf_resolve_bake folds as the bake's kind
+// asks) differ; bounces and wf_fold are rt_render's own launches.
 // rt_bake_rays writes the same rays as rt_ray records, so rt_render_rays over them gives the bake's samples bit for bit.
 #include <algorithm>
 #include <cmath>
@@ -31,19 +32,7 @@ extern "C" int rt_bake(rt_scene *s, const rt_params *p, const rt_bake_desc *bake
         return rt::fail(RT_ERR_INVALID_ARG, name + ": null argument");
     if (s->group)
         return rt::fail(RT_ERR_UNSUPPORTED, name + ": a multi-GPU scene renders images only; create the scene on one device");
-    if (p->flags & ~(uint32_t)(RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST))
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown flag");
-    if (p->flags & RT_FLAG_MEGAKERNEL)
-        return rt::fail(RT_ERR_UNSUPPORTED, name + ": bake points run on the wavefront pipeline, not the megakernel");
-    if (p->rng_mode == RT_RNG_REFERENCE)
-        return rt::fail(RT_ERR_UNSUPPORTED, name + ": the reference RNG draws a 256-pixel span as one sequential stream; bake points need RT_RNG_DEVICE");
-    if (p->rng_mode != RT_RNG_DEVICE)
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown rng_mode");
-    if (p->samples == 0)
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": samples must be >= 1");
-    if (p->shard_count > 1)
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": shard_count > 1 does not apply to a point list (split the list instead)");
-    if (int rc = rt::check_pass_params(p, "rt_bake"); rc != RT_OK)
+    if (int rc = rt::check_wavefront_entry(p, "rt_bake", "bake points", RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST, true); rc != RT_OK)
         return rc;
     if (p->samples >= 0x80000000u || n_points >= 0x80000000u)
         return rt::fail(RT_ERR_INVALID_ARG, name + ": samples and n_points must stay below 2^31");
@@ -77,42 +66,22 @@ extern "C" int rt_bake(rt_scene *s, const rt_params *p, const rt_bake_desc *bake
     }
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     rt::PacketPolicy pol; // of this call, as rt_render_rays keeps its own
-    s->ext_events.reset();
-    auto queue = [&]() -> int {
-        if (counters)
-            HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
+    auto upload = [&]() -> int {
         if (!device_fb) // once per call; the caller's buffer outlives the stream sync below
             HIP_TRY(hipMemcpyAsync(s->rays.get(), points, (size_t)n_points * sizeof(rt_bake_point), hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipEventRecord(s->ev0, s->stream));
-        WfLaunch W{};
-        W.width = n_points; // the virtual image is one row of points, as rt_render_rays' is one row of outputs
-        W.height = 1;
-        W.samples = K;
-        W.shard_index = 0;
-        W.shard_count = 1;
-        W.shard_block = n_points;
-        W.ray_depth = s->dev.ray_depth;
-        W.view_pixels = n_points;
-        W.fb = nullptr; // wf_resolve_bake writes WfBake::out
-        W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
-        W.stats = counters ? s->d_stats : nullptr;
-        const WfBake B{reinterpret_cast<const uint4_pod *>(d_points), bake->kind, bake->first_sample, bake->offset, p->seed, d_out};
-        if (int rc = rt::run_passes(s, p, pol, W, n_points, K, nullptr, nullptr, stats, "rt_bake", &B); rc != RT_OK)
-            return rc;
-        HIP_TRY(hipEventRecord(s->ev1, s->stream));
         return RT_OK;
     };
-    if (int rc = rt::queue_and_wait(s, queue); rc != RT_OK)
+    auto passes = [&]() -> int {
+        WfLaunch W = rt::one_row_launch(s, p, n_points, K, nullptr, counters); // no fb: wf_resolve_bake writes WfBake::out
+        const WfBake B{reinterpret_cast<const uint4_pod *>(d_points), bake->kind, bake->first_sample, bake->offset, p->seed, d_out};
+        return rt::run_passes(s, p, pol, W, rt::WfPassKind::bake(B), n_points, K, stats, "rt_bake");
+    };
+    if (int rc = rt::timed_call(s, counters, upload, passes); rc != RT_OK)
         return rc;
     if (!device_fb)
         HIP_TRY(hipMemcpy(out, d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost));
-    if (stats) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-        if (int rc = rt::fill_stats(s, counters, (uint64_t)n_points * K, ms, wall0, stats); rc != RT_OK)
-            return rc;
-        stats->packet_lanes_x100 = pol.lanes_x100;
-    }
+    if (stats)
+        return rt::fill_stats(s, counters, (uint64_t)n_points * K, wall0, pol.lanes_x100, stats);
     return RT_OK;
 }
 

@@ -1,5 +1,5 @@
 // rt_dev_bake.h — the first ray of a bake sample on the device (rt_abi.h rt_bake): ONE function that makes (origin, direction) of sample S
-// of a bake point. The first stage of rt_bake (wf_generate_bake), the writer of rt_bake_rays (wf_bake_rays) and the SH resolve
+// of a bake point. The first stage of rt_bake (rt_wf_stages.h WfFromBake), the writer of rt_bake_rays (wf_bake_rays) and the SH resolve
 // (wf_resolve_bake, which needs the direction again for the basis) all call it, so sample S of point j is the same ray whoever draws it.
 // The rule is stated operation by operation in rt_abi.h; every line here is one line of it.
 #pragma once

@@ -1,6 +1,6 @@
 // rt_dev_sensor.h — the cameras of the wavefront pipeline on the device (rt_abi.h rt_sensor; a view of rt_render* is a pinhole record): ONE
-// function that makes (origin, direction, RNG state) of sample s of pixel pix from a sensor record. The rectangle first stage (wf_generate),
-// the list first stage of the accumulators (wf_generate_list) and the writer of rt_sensor_rays (wf_sensor_rays) all call it, so sample s of
+// function that makes (origin, direction, RNG state) of sample s of pixel pix from a sensor record. The camera source of the first
+// stage (rt_wf_stages.h WfFromCameras), the list source of the accumulators (WfFromList) and the writer of rt_sensor_rays (wf_sensor_rays) all call it, so sample s of
 // pixel p is the same ray whoever draws it. The rule is stated operation by operation in rt_abi.h; every line here is one line of it.
 #pragma once
 #include "rt_dev_shade.h"

@@ -203,7 +203,7 @@ struct alignas(64) WfPath {
     uint32_t path;  // path id within the pass = index into fold / sample_out (& WF_ORDER_SLOT_MASK); bits 30-31: the sampler class of the path's
                     //   next shade() (next_shade_class), a scheduling hint for wf_shade
     uint32_t depth; // low 16 bits: remaining trace_ray budget (raytracer.h:596); high 16 bits: pending shade() frames
-    float r[3];     // 1 / d, IEEE division, computed where the ray is made (wf_generate / wf_shade are latency bound; wf_extend,
+    float r[3];     // 1 / d, IEEE division, computed where the ray is made (the first stage / wf_shade are latency bound; wf_extend,
     uint32_t fast;  //   the issue-bound kernel, just loads it) + the per-ray half of div_exact_fast's preconditions
     uint32_t s[4];  // xoshiro128++ state
 };
@@ -291,7 +291,7 @@ struct WfLaunch {
     void *stack_overflow;    // wf_extend's evicted traversal-stack frames: [RT_MAX_STACK][stack_stride] records of 16 B
     uint32_t stack_stride;   // = threads of the wf_extend grid
     uint32_t *counters;      // WF_CNT_*: IN = rays of this bounce, TICKET = the packet kernels' work ticket, SLOTS = wave slots of the launch
-                             // that wrote paths_in (0: paths_in is dense, as wf_generate leaves it)
+                             // that wrote paths_in (0: paths_in is dense, as the first stage leaves it)
     uint32_t *stripes;       // WF_STRIPE_BUF_WORDS: the sub-queue fill counters of the running wf_shade, then run_start[] of paths_in
     const uint32_t *order;   // optional: position q processes queue slot order[q] & WF_ORDER_SLOT_MASK (coherence sort; extend AND shade); null = identity.
                              // Bits 30-31 carry the ray's NEXT sampler class (top bits of WfPath's path word) through the sort: wf_shade's lane assignment reads them
@@ -356,7 +356,7 @@ struct WfIds {
 };
 
 // A pass of rt_render_rays (rt_rays.cpp): the first stage takes its rays and RNG streams from the caller's buffer instead of a camera
-// (wf_generate_rays). The call is a virtual image of n_rays / group "pixels" (outputs) with group * samples samples each, so WfLaunch keeps
+// (rt_wf_stages.h WfFromRays). The call is a virtual image of n_rays / group "pixels" (outputs) with group * samples samples each, so WfLaunch keeps
 // describing the pass (first_pixel / pass_pixels count outputs, WfLaunch::samples = group * samples) and wf_fold / wf_resolve run unchanged:
 // sample index ds of output j is sample first_sample + ds % samples of ray j * group + ds / samples.
 struct WfRays {
@@ -366,7 +366,7 @@ struct WfRays {
     uint64_t seed;         // rt_params.seed
 };
 
-// A pass of rt_bake (rt_bake.cpp): the first stage makes sample first_sample + s of every bake point itself (wf_generate_bake, through
+// A pass of rt_bake (rt_bake.cpp): the first stage makes sample first_sample + s of every bake point itself (rt_wf_stages.h WfFromBake, through
 // rt_dev_bake.h bake_ray) and the last stage folds the samples as the kind asks (wf_resolve_bake in place of wf_resolve). WfLaunch keeps
 // describing the pass: its "pixels" are the points, WfLaunch::samples = rt_params.samples. `out` holds the running sums between the sample
 // passes of a tile (3 floats per point, or 27 laid out [k][c]) and the scaled result after the last one: WfLaunch::accum and fb are not used.

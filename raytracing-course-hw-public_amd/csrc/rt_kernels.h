@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <type_traits>
+#include <variant>
 #include <vector>
 
 #include "rt_device_types.h"
@@ -53,7 +54,7 @@ hipError_t launch_surface_normals(const DevScene &S, const float *rays, uint32_t
 hipError_t launch_light_pdf(const DevScene &S, const float *rays, uint32_t n, float *pdf, hipStream_t stream);
 hipError_t launch_bg_at(const DevScene &S, const float *dirs, uint32_t n, float *rgb, hipStream_t stream);
 // rt_wavefront.hip: one pass (pixel tile x sample range) of the wavefront pipeline, stream-ordered
-// `extend_events` (optional): one (start, stop) event pair per wf_extend launch is taken from the pool and recorded on `stream`
+// `extend_events`: with WfPassStep::time_extends, one (start, stop) event pair per wf_extend launch is taken from the pool and recorded on `stream`
 // `packet_census_out` (optional, host, 2 words): trips and lanes served of this pass's wf_extend_packet launch (0, 0 if it did not run)
 // `host_sync` (optional): pinned words + events for the one-bounce-late read-back of the queue sizes (coherence sort and the
 // early stop need an upper bound of the queue on the host); without it bounces >= 1 run unsorted over the full pass
@@ -63,17 +64,66 @@ struct WfHostSync {
     int n_events;
 };
 #define WF_HOST_CENSUS_WORD 40 /* 8-byte aligned, behind RT_MAX_RAY_DEPTH + 1 size words */
-// `acc` (optional): an accumulator pass (rt_accum.hip): wf_generate_list / wf_resolve_list over the round's entry list replace wf_generate /
-// wf_resolve; first_pass / last_pass are not read. Null for rt_render. `feat` (optional, with `acc`): the pass of a feature accumulator:
-// wf_features after bounce 0's closest hits and wf_resolve_features before wf_resolve_list; null launches neither. `ids` (optional, with `acc`):
-// the pass of an accumulator with ids: wf_ids next to wf_features and wf_resolve_ids before wf_resolve_list; null launches neither.
-// `rays` (optional, without `acc`): a pass of rt_render_rays: wf_generate_rays replaces wf_generate; wf_fold and wf_resolve are rt_render's.
-// `bake` (optional, without `acc` and `rays`): a pass of rt_bake: wf_generate_bake replaces wf_generate and wf_resolve_bake replaces wf_resolve.
-// Without `rays` and `bake` the primary rays come from the camera table L.sensors (a view is a pinhole record), whatever the entry point.
-hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
-                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync,
-                                 const WfAccum *acc = nullptr, const WfFeat *feat = nullptr, const WfRays *rays = nullptr,
-                                 const WfBake *bake = nullptr, const WfIds *ids = nullptr);
+// The kind of a wavefront pass: where a path's first ray comes from and where its finished samples go. Every pass runs the same pipeline
+// (first stage, ray_depth x (extend, shade, advance), wf_fold, last stage); the kind names the first stage's source, the launches that
+// follow bounce 0's closest hits and the last stage, and carries exactly what those read. Made by one of the four named constructors only:
+//   cameras  the camera table WfLaunch::sensors (a view is a pinhole record), whatever the entry point; wf_resolve adds onto the image
+//   list     an accumulator round's entry list; wf_resolve_list adds onto the accumulator's sums, behind the feature sums and the id tables
+//            of an accumulator that keeps them (wf_features / wf_ids after bounce 0, wf_resolve_features / wf_resolve_ids before the sums)
+//   rays     the caller's rays and streams (rt_render_rays); wf_resolve adds onto the outputs
+//   bake     the samples of bake points (rt_bake); wf_resolve_bake folds them as the bake's kind asks
+// A camera source is made of the call's camera table on the host (run_passes uploads it as WfLaunch::sensors), a list of its accumulator's one
+// camera record; both keep rt::single_origin of it (rt_sensor.cpp): the three floats every ray of the pass starts at, or null.
+const float *single_origin(const WfSensor *table, uint32_t n);
+class WfPassKind {
+public:
+    enum Source { CAMERAS, LIST, RAYS, BAKE };
+    static WfPassKind cameras(const WfSensor *table, uint32_t n_views) { return WfPassKind(Cameras{table, n_views, single_origin(table, n_views)}); }
+    static WfPassKind list(const WfAccum &entries, const WfFeat *features, const WfIds *ids, const WfSensor &camera) {
+        return WfPassKind(List{entries, features, ids, single_origin(&camera, 1)});
+    }
+    static WfPassKind rays(const WfRays &rays) { return WfPassKind(rays); }
+    static WfPassKind bake(const WfBake &bake) { return WfPassKind(bake); }
+
+    Source source() const { return (Source)v.index(); }
+    // what the source's first and last stages read (the source is the caller's to ask for: std::get throws on another)
+    const WfAccum &entries() const { return std::get<List>(v).entries; }
+    const WfRays &ray_buffer() const { return std::get<WfRays>(v); }
+    const WfBake &bake_points() const { return std::get<WfBake>(v); }
+    // the launches behind bounce 0's closest hits, whose results are final there: a list's first-hit features and ids; null: none
+    const WfFeat *features() const { return source() == LIST ? std::get<List>(v).features : nullptr; }
+    const WfIds *ids() const { return source() == LIST ? std::get<List>(v).ids : nullptr; }
+    // the cameras of the pass: part of the packet policy's key (a caller's rays and bake points count as one)
+    uint32_t n_views() const { return source() == CAMERAS ? std::get<Cameras>(v).n_views : 1u; }
+    const WfSensor *camera_table() const { return source() == CAMERAS ? std::get<Cameras>(v).table : nullptr; } // [n_views], host; null: no table to upload
+    // Camera-relative records are for the one view of a camera source (a list has one camera) whose rays share an origin: that origin, else null
+    const float *relative_origin() const { return source() == CAMERAS ? std::get<Cameras>(v).origin : source() == LIST ? std::get<List>(v).origin : nullptr; }
+    // RT_PACKET_AUTO never picks packets for a bake: a point's samples share an origin and nothing else (a hemisphere or the whole sphere of
+    // directions is no packet); RT_PACKET_ON still does, and changes no bit
+    bool auto_packets() const { return source() != BAKE; }
+
+private:
+    struct Cameras {
+        const WfSensor *table;
+        uint32_t n_views;
+        const float *origin;
+    };
+    struct List {
+        WfAccum entries;
+        const WfFeat *features;
+        const WfIds *ids;
+        const float *origin;
+    };
+    std::variant<Cameras, List, WfRays, WfBake> v; // in the order of Source
+    template <class T> explicit WfPassKind(const T &t) : v(t) {}
+};
+// This pass of its call: the first / last sample pass of its pixel tile (wf_resolve and wf_resolve_bake start from zero / divide and write
+// out; a list's passes are each both), and whether the extend launches are timed (rt_stats::dominant_ms).
+struct WfPassStep {
+    bool first_pass, last_pass, time_extends;
+};
+hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind &kind, const WfPassStep &step, bool stats, int num_cus, hipStream_t stream,
+                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync);
 // rt_bake_rays: the n = points x samples rt_ray records of samples [B.first_sample, B.first_sample + samples) of the points of `B` (device;
 // B.out is not read) -> `d_rays_out` (device, 32 B per record, 16-byte aligned)
 hipError_t launch_bake_rays(const WfBake &B, uint32_t samples, uint32_t n, void *d_rays_out, int num_cus, hipStream_t stream);

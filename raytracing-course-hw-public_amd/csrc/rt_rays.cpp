@@ -1,9 +1,9 @@
 // rt_rays.cpp — rt_render_rays / rt_render_rays_rgb8 (rt_abi.h): the wavefront pipeline over rays and RNG streams the caller supplies.
 //
 // The call runs rt_render's own pass loop (rt_render.cpp run_passes): n_rays / G outputs take the place of the pixels and G * K samples per
-// output the place of the SPP, in (output tile) x (sample range) passes under wavefront_max_paths. Only the first stage differs
-// (wf_generate_rays reads the ray buffer where wf_generate asks a camera): bounces, fold and resolve are rt_render's own launches, so a
-// camera's own primary rays give rt_render's image bit for bit.
+// output the place of the SPP, in (output tile) x (sample range) passes under wavefront_max_paths. The passes are of the kind
+// WfPassKind::rays (rt_kernels.h): only the first stage's source differs (it reads the ray buffer where a camera source asks a camera);
+// bounces, fold and resolve are rt_render's own launches, so a camera's own primary rays give rt_render's image bit for bit.
 #include <algorithm>
 #include <cstring>
 
@@ -16,19 +16,7 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
         return rt::fail(RT_ERR_INVALID_ARG, name + ": null argument");
     if (s->group)
         return rt::fail(RT_ERR_UNSUPPORTED, name + ": a multi-GPU scene renders images only; create the scene on one device");
-    if (p->flags & ~(uint32_t)(RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST))
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown flag");
-    if (p->flags & RT_FLAG_MEGAKERNEL)
-        return rt::fail(RT_ERR_UNSUPPORTED, name + ": caller rays run on the wavefront pipeline, not the megakernel");
-    if (p->rng_mode == RT_RNG_REFERENCE)
-        return rt::fail(RT_ERR_UNSUPPORTED, name + ": the reference RNG draws a 256-pixel span as one sequential stream; caller rays need RT_RNG_DEVICE");
-    if (p->rng_mode != RT_RNG_DEVICE)
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown rng_mode");
-    if (p->samples == 0)
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": samples must be >= 1");
-    if (p->shard_count > 1)
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": shard_count > 1 does not apply to a ray list (split the list instead)");
-    if (int rc = rt::check_pass_params(p, fn); rc != RT_OK)
+    if (int rc = rt::check_wavefront_entry(p, fn, "caller rays", RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST, true); rc != RT_OK)
         return rc;
     const uint32_t G = rays_per_output ? rays_per_output : 1u, K = p->samples;
     if (n_rays % G != 0)
@@ -72,34 +60,21 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
     }
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     rt::PacketPolicy pol; // of this call: rt_render's, measured on camera rays of its image shape, is not disturbed
-    s->ext_events.reset();
-    auto queue = [&]() -> int {
-        if (counters)
-            HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
+    auto upload = [&]() -> int {
         if (!device_fb) // once per call; the caller's buffer outlives the stream sync below
             HIP_TRY(hipMemcpyAsync(s->rays.get(), rays, (size_t)n_rays * sizeof(rt_ray), hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipEventRecord(s->ev0, s->stream));
-        WfLaunch W{};
-        W.width = n_out; // the virtual image is one row of outputs (nothing on the device reads the size: it keys the packet policy)
-        W.height = 1;
-        W.samples = spo;
-        W.shard_index = 0;
-        W.shard_count = 1;
-        W.shard_block = n_out;
-        W.ray_depth = s->dev.ray_depth;
-        W.view_pixels = n_out;
-        W.fb = d_fb;
-        W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
-        W.stats = counters ? s->d_stats : nullptr;
+        return RT_OK;
+    };
+    auto passes = [&]() -> int {
+        WfLaunch W = rt::one_row_launch(s, p, n_out, spo, d_fb, counters);
         const WfRays R{reinterpret_cast<const uint4_pod *>(d_rays), G, K, p->seed};
-        if (int rc = rt::run_passes(s, p, pol, W, n_out, spo, nullptr, &R, stats, fn); rc != RT_OK)
+        if (int rc = rt::run_passes(s, p, pol, W, rt::WfPassKind::rays(R), n_out, spo, stats, fn); rc != RT_OK)
             return rc;
         if (rgb8_out) // film on the device (image.h:49-82) over the outputs
             HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_out, 0, 1, n_out, s->film_table.get(), s->stream));
-        HIP_TRY(hipEventRecord(s->ev1, s->stream));
         return RT_OK;
     };
-    if (int rc = rt::queue_and_wait(s, queue); rc != RT_OK)
+    if (int rc = rt::timed_call(s, counters, upload, passes); rc != RT_OK)
         return rc;
     if (!device_fb) {
         if (rgb8_out)
@@ -107,13 +82,8 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
         else
             HIP_TRY(hipMemcpy(out_rgb, d_fb, fb_floats * sizeof(float), hipMemcpyDeviceToHost));
     }
-    if (stats) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-        if (int rc = rt::fill_stats(s, counters, (uint64_t)n_rays * K, ms, wall0, stats); rc != RT_OK)
-            return rc;
-        stats->packet_lanes_x100 = pol.lanes_x100;
-    }
+    if (stats)
+        return rt::fill_stats(s, counters, (uint64_t)n_rays * K, wall0, pol.lanes_x100, stats);
     return RT_OK;
 }
 

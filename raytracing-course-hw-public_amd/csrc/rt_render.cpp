@@ -1,7 +1,9 @@
 // rt_render.cpp — rt_render / rt_render_views and their rgb8 forms, rt_film_rgb8, the pass loop of every call that renders a rectangle of
-// pixels x samples (run_passes: render_image here, rt_render_rays in rt_rays.cpp), and what every wavefront pass shares with the
-// accumulators (rt_accum_host.cpp): the check of the pass options, the pass policy (launch_pass) and the statistics. The cameras of a pass
-// are ONE table of sensor records (rt_sensor.cpp make_sensor): a view of rt_render* is a pinhole record.
+// pixels x samples (run_passes: render_image here, rt_render_rays in rt_rays.cpp, rt_bake in rt_bake.cpp), and what every wavefront pass
+// shares with the accumulators (rt_accum_host.cpp): the checks of rt_params (check_wavefront_entry, check_pass_params), the pass policy
+// (launch_pass) and the statistics. What kind of pass it is (cameras, an accumulator's list, a caller's rays, bake points) is ONE record,
+// rt_kernels.h WfPassKind, made by the entry point and asked here under one name per decision. The cameras of a camera pass are ONE table
+// of sensor records (rt_sensor.cpp make_sensor): a view of rt_render* is a pinhole record.
 //
 // rt_render  replaces run_raytracer(scene, image) (src/raytracer.h:629-674): the wavefront pipeline over (pixel tile) x (sample range)
 //            passes, or the persistent megakernel (reference-RNG parity mode, RT_FLAG_MEGAKERNEL).
@@ -98,6 +100,44 @@ int rt::check_pass_params(const rt_params *p, const char *fn) {
     return RT_OK;
 }
 
+// What an entry point that runs on the wavefront pipeline only, with the device RNG, and does not shard refuses of rt_params, then the pass
+// options: rt_render_rays*, rt_bake, rt_render_sensors* and the accumulators. `subject`: what the entry point runs ("caller rays");
+// `flags_taken`: the flags it knows and that apply to it; `reads_samples`: rt_params.samples is the call's sample count.
+int rt::check_wavefront_entry(const rt_params *p, const char *fn, const char *subject, uint32_t flags_taken, bool reads_samples) {
+    const std::string name(fn), what(subject);
+    if (p->flags & ~flags_taken)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown flag, or one that does not apply to " + what);
+    if (p->flags & RT_FLAG_MEGAKERNEL)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": " + what + " run on the wavefront pipeline, not the megakernel");
+    if (p->rng_mode == RT_RNG_REFERENCE)
+        return rt::fail(RT_ERR_UNSUPPORTED, name + ": the reference RNG draws a 256-pixel span as one sequential stream; " + what + " need RT_RNG_DEVICE");
+    if (p->rng_mode != RT_RNG_DEVICE)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown rng_mode");
+    if (reads_samples && p->samples == 0)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": samples must be >= 1");
+    if (p->shard_count > 1)
+        return rt::fail(RT_ERR_INVALID_ARG, name + ": shard_count > 1 does not apply to " + what + " (split the work instead)");
+    return rt::check_pass_params(p, fn);
+}
+
+// The WfLaunch of a call over a list of `n` outputs x `samples` samples each (a caller's rays, bake points): the virtual image is one row of
+// outputs in one shard (nothing on the device reads the size: it keys the packet policy). `fb`: where wf_resolve writes, if it runs.
+WfLaunch rt::one_row_launch(const rt_scene *s, const rt_params *p, uint32_t n, uint32_t samples, float *fb, bool counters) {
+    WfLaunch W{};
+    W.width = n;
+    W.height = 1;
+    W.samples = samples;
+    W.shard_index = 0;
+    W.shard_count = 1;
+    W.shard_block = n;
+    W.ray_depth = s->dev.ray_depth;
+    W.view_pixels = n;
+    W.fb = fb;
+    W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
+    W.stats = counters ? s->d_stats : nullptr;
+    return W;
+}
+
 // Camera-relative records for the packet kernel (rt_wavefront.hip wf_camera_relative, WfLaunch::rel_nodes / rel_tris) of a pass whose primary
 // rays all start at `cam_pos`. The copy is made on the scene's stream, ahead of the pass, when the camera position (compared as bits) or the
 // tree (rt_scene::geo_generation) differs from what the kept copy was made of; otherwise the kept copy is handed out and nothing is launched.
@@ -146,12 +186,9 @@ static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float 
 
 // One wavefront pass: `W` carries the workspace (wf_bind) and the pass's geometry (first_pixel, pass_pixels, first_sample, pass_samples,
 // n_paths, sensors, ...); this picks W.sort_mode and W.use_packet, launches, and folds the packet kernel's census back into `pol`, the
-// policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays*). `acc`: an
-// accumulator pass, `feat`: of a feature accumulator, `rays`: a pass of rt_render_rays, `bake`: a pass of rt_bake, `ids`: of an accumulator with ids (rt_kernels.h).
-// `cam_pos`: rt::single_origin of the pass's camera table: the three floats sensor_ray stores as every ray's origin, or null where no such
-// position exists (several cameras, a caller's rays, a sensor whose rays start on a film or a lens).
-hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                           const WfAccum *acc, const WfFeat *feat, const WfRays *rays, const float *cam_pos, const WfBake *bake, const WfIds *ids) {
+// policy of whoever owns the pass (the scene for rt_render*, the accumulator for rt_accum_*, the call for rt_render_rays* and rt_bake).
+// `kind`: where the pass's rays come from and its samples go (rt_kernels.h WfPassKind); `step`: this pass of the call.
+hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, const WfPassKind &kind, const WfPassStep &step) {
     // Small passes are bound by launch and host latency, not by memory (a 256 x 256 x 4 render, BASELINE config 1's
     // shape, spent 5.7 ms at 0.6 ms per bounce): RT_SORT_AUTO leaves a pass of fewer than 2^20 paths unsorted, which also spares it
     // the per-bounce queue-size read-back the sort needs: the whole pass is queued without a single host wait.
@@ -165,23 +202,20 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     // A key is only ever compared with the previous key of the SAME owner, so the terms that are constant for an accumulator (one shard,
     // one view; pass_samples is its list chunk) change none of its reset decisions
     const uint64_t key = ((uint64_t)W.width << 44) ^ ((uint64_t)W.height << 24) ^ ((uint64_t)W.pass_samples << 8) ^ (uint64_t)W.shard_count ^
-                         ((uint64_t)min_lanes_bits * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(n_views - 1) * 0xC2B2AE3D27D4EB4Full);
+                         ((uint64_t)min_lanes_bits * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(kind.n_views() - 1) * 0xC2B2AE3D27D4EB4Full);
     if (key != pol.key) {
         pol.key = key;
         pol.off = false;
     }
     const uint32_t pkt_min_spp = s->wide_built ? 4u : 16u; // measured break-even of the two packet kernels
-    // (a bake point's samples share an origin and nothing else: a hemisphere or the whole sphere of directions is no packet, so RT_PACKET_AUTO
-    // never picks the packet kernel for a pass of rt_bake; RT_PACKET_ON still does, and changes no bit)
-    W.use_packet = p->packet_mode == RT_PACKET_OFF ? 0u : p->packet_mode == RT_PACKET_ON ? 1u : (W.pass_samples >= pkt_min_spp && !pol.off && !bake) ? 1u : 0u;
+    W.use_packet = p->packet_mode == RT_PACKET_OFF ? 0u : p->packet_mode == RT_PACKET_ON ? 1u : (W.pass_samples >= pkt_min_spp && !pol.off && kind.auto_packets()) ? 1u : 0u;
     W.rel_nodes = nullptr, W.rel_tris = nullptr;
-    if (W.use_packet && cam_pos && n_views == 1 && !rays)
-        if (hipError_t e = camera_relative_records(s, W, cam_pos); e != hipSuccess)
+    if (const float *origin = kind.relative_origin(); W.use_packet && origin)
+        if (hipError_t e = camera_relative_records(s, W, origin); e != hipSuccess)
             return e;
     const rt::WfHostSync hsync = wavefront_host_sync(s);
     unsigned long long census[2] = {0ull, 0ull};
-    const hipError_t e = rt::launch_wavefront_pass(s->dev, W, W.stats != nullptr, s->num_cus, first_pass, last_pass, s->stream, time_extends ? &s->ext_events : nullptr, census,
-                                                   s->wf_host_count ? &hsync : nullptr, acc, feat, rays, bake, ids);
+    const hipError_t e = rt::launch_wavefront_pass(s->dev, W, kind, step, W.stats != nullptr, s->num_cus, s->stream, &s->ext_events, census, s->wf_host_count ? &hsync : nullptr);
     if (e == hipSuccess && census[0] != 0ull) {
         pol.lanes_x100 = (uint32_t)(100.0 * (double)census[1] / (double)census[0]);
         if ((double)census[1] < min_lanes * (double)census[0])
@@ -190,27 +224,24 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
     return e;
 }
 
-// The pass loop of a call that renders `n_pixels` local pixels (outputs, for rt_render_rays) x `samples` samples each: (pixel tile) x
-// (sample range) passes under wavefront_max_paths, all stream-ordered. `W` carries the caller's geometry, output buffer and flags; this grows
-// and binds the workspace and sets each pass's range. `table`: the cameras of the call, uploaded here as W.sensors (it outlives the caller's
-// stream sync; its one origin, if any, lets the packets walk camera-relative records); null for a pass of `rays` or of `bake`.
+// The pass loop of a call that renders `n_pixels` local pixels (outputs, for rt_render_rays; points, for rt_bake) x `samples` samples each:
+// (pixel tile) x (sample range) passes of `kind` under wavefront_max_paths, all stream-ordered. `W` carries the caller's geometry, output
+// buffer and flags; this grows and binds the workspace, uploads a camera source's table as W.sensors and sets each pass's range.
 // Progress (rt_params.progress): one event per pass; the host stays ONE pass ahead of the device (after queueing pass k it waits for pass
 // k - 1 and reports it), so reporting never leaves the GPU idle. `stats` (may be null) receives passes / packet_passes. `fn`: the entry
 // point's name.
-int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint64_t n_pixels, uint32_t samples, const std::vector<WfSensor> *table,
-                   const WfRays *rays, rt_stats *stats, const char *fn, const WfBake *bake) {
+int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, const WfPassKind &kind, uint64_t n_pixels, uint32_t samples, rt_stats *stats,
+                   const char *fn) {
     const uint64_t max_paths = rt::wavefront_max_paths(s, p);
     const uint64_t tile_pixels = std::min<uint64_t>(n_pixels, max_paths);
     const uint32_t pass_spp = (uint32_t)std::clamp<uint64_t>(max_paths / tile_pixels, 1, samples);
     if (int rc = s->ensure_wavefront(tile_pixels * pass_spp, tile_pixels, s->dev.ray_depth); rc != RT_OK)
         return rc;
     s->wf_bind(W);
-    const uint32_t n_views = table ? (uint32_t)table->size() : 1u;
-    const float *cam_pos = table ? rt::single_origin(table->data(), n_views) : nullptr;
-    if (table) {
-        if (int rc = s->ensure_sensors(n_views); rc != RT_OK)
+    if (const WfSensor *table = kind.camera_table()) { // it outlives the caller's stream sync
+        if (int rc = s->ensure_sensors(kind.n_views()); rc != RT_OK)
             return rc;
-        HIP_TRY(hipMemcpyAsync(s->sensors.get(), table->data(), n_views * sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->sensors.get(), table, kind.n_views() * sizeof(WfSensor), hipMemcpyHostToDevice, s->stream));
         W.sensors = s->sensors.get();
     }
     const uint32_t n_passes = (uint32_t)((n_pixels + tile_pixels - 1) / tile_pixels) * ((samples + pass_spp - 1) / pass_spp);
@@ -229,7 +260,7 @@ int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch 
             W.first_sample = s0;
             W.pass_samples = std::min<uint32_t>(pass_spp, samples - s0);
             W.n_paths = W.pass_pixels * W.pass_samples;
-            HIP_TRY(rt::launch_pass(s, p, pol, W, n_views, s0 == 0, s0 + W.pass_samples >= samples, stats != nullptr, nullptr, nullptr, rays, cam_pos, bake));
+            HIP_TRY(rt::launch_pass(s, p, pol, W, kind, WfPassStep{s0 == 0, s0 + W.pass_samples >= samples, stats != nullptr}));
             packet_passes += W.use_packet;
             if (p->progress) {
                 HIP_TRY(hipEventRecord(s->pass_events[pass_no], s->stream));
@@ -252,10 +283,12 @@ int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch 
     return RT_OK;
 }
 
-// rt_stats of a call that has finished on the scene's stream: the device counters (`counters`; else `samples` is what the call knows it
-// drew), the ev0..ev1 time, the extend launches of the event pool and the wall time since `wall0`. passes / packet_passes /
-// packet_lanes_x100 are the caller's.
-int rt::fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats) {
+// rt_stats of a call that has finished on the scene's stream (timed_call): the device counters (`counters`; else `samples` is what the call
+// knows it drew), the ev0..ev1 time, the extend launches of the event pool, the wall time since `wall0` and the packet census of the call's
+// policy (lanes served per trip x 100; 0 = the packet kernel did not run). passes / packet_passes are the caller's.
+int rt::fill_stats(rt_scene *s, bool counters, uint64_t samples, std::chrono::steady_clock::time_point wall0, uint32_t packet_lanes_x100, rt_stats *stats) {
+    float kernel_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&kernel_ms, s->ev0, s->ev1));
     DevStats h{};
     if (counters)
         HIP_TRY(hipMemcpy(&h, s->d_stats, sizeof(h), hipMemcpyDeviceToHost));
@@ -272,6 +305,7 @@ int rt::fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms
     stats->light_hits = h.lhits;
     stats->texel_fetches = h.texels;
     stats->kernel_ms = kernel_ms;
+    stats->packet_lanes_x100 = packet_lanes_x100;
     const std::vector<hipEvent_t> &xe = s->ext_events.ev;
     const size_t n_xe = s->ext_events.used & ~size_t(1);
     stats->dominant_launches = (uint32_t)(n_xe / 2);
@@ -360,8 +394,6 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     L.stats = counters ? s->d_stats : nullptr;
     HIP_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(uint32_t), s->stream));
-    if (counters)
-        HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
 
     const bool wavefront = p->rng_mode == RT_RNG_DEVICE && !(p->flags & RT_FLAG_MEGAKERNEL);
     if (s->wide_built && !wavefront)
@@ -370,10 +402,8 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
     if (s->dev.env.texels && !wavefront)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_render: a scene with a float environment (rt_set_environment) renders through the wavefront pipeline only (the "
                                             "megakernel and the reference-RNG parity mode are the reference's Scene::bg_at: rt_set_environment(scene, NULL) first)");
-    s->ext_events.reset();
     uint32_t launched = 0; // megakernel launches
     auto queue_render = [&]() -> int {
-    HIP_TRY(hipEventRecord(s->ev0, s->stream));
     if (L.n_items > 0 && wavefront) {
         // ---- production path: wavefront pipeline over (pixel tile) x (sample range) passes, all stream-ordered
         WfLaunch W{};
@@ -389,7 +419,7 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
         // production traversal: global-best pruning (rt_abi.h RT_FLAG_GLOBAL_BEST)
         W.global_best = (p->flags & RT_FLAG_GLOBAL_BEST) ? 1u : 0u;
         W.stats = L.stats;
-        if (int rc = rt::run_passes(s, p, pol, W, local_pixels, p->samples, &table, nullptr, stats, "rt_render"); rc != RT_OK)
+        if (int rc = rt::run_passes(s, p, pol, W, rt::WfPassKind::cameras(table.data(), n_views), local_pixels, p->samples, stats, "rt_render"); rc != RT_OK)
             return rc;
     } else if (L.n_items > 0) {
         // ---- persistent megakernel: reference-RNG parity mode, or RT_FLAG_MEGAKERNEL cross-check (one launch = one pass), one launch per
@@ -436,13 +466,10 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
     }
     if (rgb8_out && L.n_items > 0) // film on the device: this shard's pixels -> rgb8 (image.h:49-82)
         HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_pix, L.shard_index, L.shard_count, block, s->film_table.get(), s->stream));
-    HIP_TRY(hipEventRecord(s->ev1, s->stream));
     return RT_OK;
     };
-    if (int rc = rt::queue_and_wait(s, queue_render); rc != RT_OK)
+    if (int rc = rt::timed_call(s, counters, [] { return RT_OK; }, queue_render); rc != RT_OK)
         return rc;
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
 
     if (!device_fb && L.n_items > 0) { // copy back only this shard's blocks; other pixels of the destination stay untouched
         const size_t elem = rgb8_out ? 1 : sizeof(float);
@@ -458,13 +485,12 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
         }
     }
     if (stats) {
-        if (int rc = rt::fill_stats(s, counters, local_pixels * p->samples, ms, wall0, stats); rc != RT_OK)
+        if (int rc = rt::fill_stats(s, counters, local_pixels * p->samples, wall0, wavefront ? pol.lanes_x100 : 0u, stats); rc != RT_OK)
             return rc;
         if (!wavefront) { // the megakernel: its launches are the passes and the dominant ones
             stats->passes = stats->dominant_launches = launched;
-            stats->dominant_ms = ms;
+            stats->dominant_ms = stats->kernel_ms;
         }
-        stats->packet_lanes_x100 = wavefront ? pol.lanes_x100 : 0u; // the packet kernel's census (lanes served per trip x 100; 0 = it did not run)
     }
     return RT_OK;
 }

@@ -203,7 +203,7 @@ struct rt_scene {
             (rc = alloc(wf_sort_temp_bytes, &wf_sort_temp)) != RT_OK)
             return rc;
         // on the scene's own (non-blocking) stream: a null-stream memset is not ordered with the kernels launched there and
-        // could land after wf_generate had set the queue size
+        // could land after the first stage had set the queue size
         HIP_TRY(hipMemsetAsync(wf_counters, 0, WF_CNT_ALLOC_WORDS * sizeof(uint32_t), stream));
         wf_paths_cap = paths;
         wf_pixels_cap = pixels;
@@ -286,23 +286,22 @@ int upload_geometry(rt_scene *s, const rt_scene_desc *d, const PreparedScene &PS
                     const DeviceArrays *arrays = nullptr);
 void install_geometry(rt_scene *s, GeometryOnDevice &g);
 uint32_t light_lds_inner(const FlatBvh &f); // DevBvh::lds_inner of a light tree
-// rt_render.cpp: the check of the pass options, the wavefront pass policy, the pass loop and the statistics of a finished call
+// rt_render.cpp: the checks of rt_params, the wavefront pass policy, the pass loop and the statistics of a finished call
 void set_camera(DevScene &D, const float *pos, const float *right, const float *up, const float *fwd);
 int check_pass_params(const rt_params *p, const char *fn);
+int check_wavefront_entry(const rt_params *p, const char *fn, const char *subject, uint32_t flags_taken, bool reads_samples);
 uint64_t wavefront_max_paths(rt_scene *s, const rt_params *p);
-hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint32_t n_views, bool first_pass, bool last_pass, bool time_extends,
-                       const WfAccum *acc, const WfFeat *feat = nullptr, const WfRays *rays = nullptr, const float *cam_pos = nullptr,
-                       const WfBake *bake = nullptr, const WfIds *ids = nullptr);
-int run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, uint64_t n_pixels, uint32_t samples, const std::vector<WfSensor> *table,
-               const WfRays *rays, rt_stats *stats, const char *fn, const WfBake *bake = nullptr);
+WfLaunch one_row_launch(const rt_scene *s, const rt_params *p, uint32_t n, uint32_t samples, float *fb, bool counters);
+hipError_t launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, const WfPassKind &kind, const WfPassStep &step);
+int run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch &W, const WfPassKind &kind, uint64_t n_pixels, uint32_t samples, rt_stats *stats,
+               const char *fn);
 // the image of a single-GPU scene through the cameras of `table` (views as pinhole records, or the checked records of rt_sensor.cpp)
 int render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor> &table, PacketPolicy &pol, float *fb_rgb, uint8_t *rgb8_out, rt_stats *stats);
-// rt_sensor.cpp: the argument checks of one rt_sensor, the device record of a sensor or of a view {camera, seed}, the one ray origin of a table
+// rt_sensor.cpp: the argument checks of one rt_sensor, the device record of a sensor or of a view {camera, seed} (single_origin: rt_kernels.h)
 int check_sensor(const rt_sensor &sn, uint32_t width, uint32_t height, const char *fn);
 WfSensor make_sensor(const rt_sensor &sn, uint32_t width, uint32_t height);
 WfSensor make_sensor(const rt_camera &cam, uint64_t seed, uint32_t width, uint32_t height);
-const float *single_origin(const WfSensor *table, uint32_t n);
-int fill_stats(rt_scene *s, bool counters, uint64_t samples, float kernel_ms, std::chrono::steady_clock::time_point wall0, rt_stats *stats);
+int fill_stats(rt_scene *s, bool counters, uint64_t samples, std::chrono::steady_clock::time_point wall0, uint32_t packet_lanes_x100, rt_stats *stats);
 
 // Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are
 // still in flight (a later ensure_wavefront / rt_destroy would free memory under them)
@@ -313,5 +312,23 @@ template <class Queue> int queue_and_wait(rt_scene *s, Queue queue) {
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RT_OK;
+}
+
+// The bracket of a call that runs wavefront passes and reports rt_stats: the device counters start from zero (`counters`), `stage` queues what
+// the passes read but the kernel time does not count (an upload of staged input), then ev0, `body` (the passes and what belongs to their
+// time), ev1, and the wait. fill_stats reads the events and the counters afterwards.
+template <class Stage, class Body> int timed_call(rt_scene *s, bool counters, Stage stage, Body body) {
+    s->ext_events.reset();
+    return queue_and_wait(s, [&]() -> int {
+        if (counters)
+            HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
+        if (int rc = stage(); rc != RT_OK)
+            return rc;
+        HIP_TRY(hipEventRecord(s->ev0, s->stream));
+        if (int rc = body(); rc != RT_OK)
+            return rc;
+        HIP_TRY(hipEventRecord(s->ev1, s->stream));
+        return RT_OK;
+    });
 }
 } // namespace rt

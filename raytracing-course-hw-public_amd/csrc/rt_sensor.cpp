@@ -62,7 +62,7 @@ WfSensor rt::make_sensor(const rt_camera &cam, uint64_t seed, uint32_t width, ui
 }
 
 // The one origin of every ray of a pass over `table`, where it has one: a single camera of a kind whose rays all start at the camera
-// position, bit for bit. Their packets may walk the camera-relative records (rt_render.cpp launch_pass). Null otherwise.
+// position, bit for bit. Their packets may walk the camera-relative records (rt_kernels.h WfPassKind::relative_origin). Null otherwise.
 const float *rt::single_origin(const WfSensor *table, uint32_t n) {
     const bool at_pos = n == 1 && (table[0].kind == RT_SENSOR_PINHOLE || table[0].kind == RT_SENSOR_EQUIRECT || table[0].kind == RT_SENSOR_FISHEYE);
     return at_pos ? table[0].pos : nullptr;
@@ -74,14 +74,8 @@ static int render_sensors_impl(rt_scene *s, const rt_params *p, const rt_sensor 
         return rt::fail(RT_ERR_INVALID_ARG, name + ": null argument or no sensor");
     if (s->group)
         return rt::fail(RT_ERR_UNSUPPORTED, name + ": sensors render on single-GPU scenes only");
-    if (p->flags & ~(uint32_t)(RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST))
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": unknown flag");
-    if (p->flags & RT_FLAG_MEGAKERNEL)
-        return rt::fail(RT_ERR_UNSUPPORTED, name + ": sensors are evaluated by the wavefront pipeline, not the megakernel");
-    if (p->rng_mode == RT_RNG_REFERENCE)
-        return rt::fail(RT_ERR_UNSUPPORTED, name + ": the reference RNG draws a 256-pixel span as one sequential stream; sensors need RT_RNG_DEVICE");
-    if (p->shard_count > 1)
-        return rt::fail(RT_ERR_INVALID_ARG, name + ": shard_count > 1 does not apply to a sensor render");
+    if (int rc = rt::check_wavefront_entry(p, fn, "sensors", RT_FLAG_DEVICE_FB | RT_FLAG_COUNTERS | RT_FLAG_MEGAKERNEL | RT_FLAG_GLOBAL_BEST, true); rc != RT_OK)
+        return rc;
     if (p->width == 0 || p->height == 0 || (uint64_t)n_sensors * p->width * p->height >= 0x7FFFFFFFull)
         return rt::fail(RT_ERR_INVALID_ARG, name + ": the image is empty, or n_sensors x width x height reaches 2^31");
     for (uint32_t v = 0; v < n_sensors; ++v)
@@ -90,7 +84,7 @@ static int render_sensors_impl(rt_scene *s, const rt_params *p, const rt_sensor 
     std::vector<WfSensor> table(n_sensors);
     for (uint32_t v = 0; v < n_sensors; ++v)
         table[v] = rt::make_sensor(sensors[v], p->width, p->height);
-    // rng_mode, samples and the pass options: rt_render's checks. The policy: one per kind for a single sensor, [5] for several
+    // The policy: one per kind for a single sensor, [5] for several
     return rt::render_image(s, p, table, s->pkt_sensor[n_sensors == 1 ? table[0].kind : 5u], fb_rgb, rgb8, stats);
 }
 

@@ -5,7 +5,7 @@
 // idle: traversal lengths are heavy-tailed and a lane that finishes early waits for the wave's slowest ray before it may
 // shade. Here a path = one (pixel, sample) and the recursion is cut into stages that each run over ALL live paths:
 //
-//   wf_generate : gen_ray (raytracer.h:527-538) for every path of the pass -> ray queue
+//   first stage : gen_ray (raytracer.h:527-538) for every path of the pass -> ray queue (wf_first_stage over the source of the pass's kind)
 //   per bounce (ray_depth times):
 //     wf_extend : closest hit (BVH::intersect_ray, bvh.h:195-235) for every queued ray. Persistent wavefronts; a lane
 //                 whose traversal ends stores its hit and is refilled from the queue (wave ballot + prefix count out of
@@ -15,8 +15,11 @@
 //                 traversal), BRDF. Finished paths fold their (emission, scale) frames back-to-front (the Horner order of
 //                 raytracer.h:588-590) and store the sample; surviving paths are COMPACTED into the next ray queue with
 //                 a wave ballot + prefix sum (one atomic per wave).
-//   wf_resolve  : per pixel, the samples of the pass are added in sample order s = 0,1,2,... onto the running sum, so the
-//                 float sum has exactly the reference's order (raytracer.h:621-626) although samples ran in parallel.
+//   last stage  : per pixel, the samples of the pass are added in sample order s = 0,1,2,... onto the running sum, so the
+//                 float sum has exactly the reference's order (raytracer.h:621-626) although samples ran in parallel (wf_resolve, or
+//                 what the pass's kind keeps its samples in).
+// The two ends of a pass, which depend on its kind (rt_kernels.h WfPassKind), are rt_wf_stages.h; this file has what runs between them for
+// every kind alike (extend, shade, sort, advance), the closest-hit probe and the launchers.
 //
 // Every path owns an xoshiro128++ stream seeded from (seed, pixel, sample) and consumes it in the reference's draw
 // order; the stream's state, the remaining depth and the count of pending frames travel with the ray through the queues
@@ -28,14 +31,13 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "rt_dev_bake.h"
 #include "rt_dev_queue.h"
-#include "rt_dev_sensor.h"
 #include "rt_dev_shade.h"
 #include "rt_dev_stack.h"
 #include "rt_kernels.h"
 #include "rt_ray_key.h"
 #include "rt_wf_records.h"
+#include "rt_wf_stages.h"
 
 namespace {
 
@@ -65,152 +67,6 @@ using ShadeStack = StackMemT<RT_SHADE_LDS_DEPTH>;
 #ifndef RT_EXT_REFILL_MIN
 #define RT_EXT_REFILL_MIN 16 /* refill a wave's idle lanes once this many have finished (a refill stalls the wave on the ray loads) */
 #endif
-
-DEV uint32_t wf_global_pixel(const WfLaunch &L, uint32_t local_pixel) {
-    const uint32_t local_block = local_pixel / L.shard_block;
-    const uint32_t within = local_pixel - local_block * L.shard_block;
-    return (local_block * L.shard_count + L.shard_index) * L.shard_block + within;
-}
-
-// ------------------------------------------------------------------------------------------------ generate
-// The first record of path i, in queue slot i: the ray (o, d) with `rng` as gen_ray left it (behind its two jitter draws), full budget, no
-// pending frames. The one definition of a path's first record: a camera's rays (sensor_ray) and a caller's (wf_generate_rays) both end here.
-// ENVD (every first stage): the scene's mix_dist has the environment as a component (ENV_FLOAT_DIST), which next_shade_class must know.
-template <bool ENVD> DEV void wf_store_first(const DevScene &S, const WfLaunch &L, uint32_t i, V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) {
-    wf_store_path(L.paths_in + i, wf_pack(o, d, i, next_shade_class<ENVD>(rng, S.lights.n_tris != 0), L.ray_depth, 0u, rng.g));
-}
-
-// A camera pass: path i is sample first_sample + ds of local pixel first_pixel + lp; its ray is sensor_ray (rt_dev_sensor.h) of the camera
-// that holds the pixel in the virtual (view-major) image, L.sensors[vpix / view_pixels]. A view of rt_render* is a pinhole record, whose
-// branch of sensor_ray is gen_ray (raytracer.h:527-538) itself. The accumulators' wf_generate_list draws from the same function, so sample
-// s of pixel p is the same ray whichever of them draws it.
-template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate(const DevScene S, const WfLaunch L) {
-    LaneStats<STATS> st;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        L.counters[WF_CNT_IN] = L.n_paths; // the first bounce's queue is the identity: slot i holds path i
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
-        const uint32_t lp = i / L.pass_samples;
-        const uint32_t ds = i - lp * L.pass_samples;
-        const uint32_t vpix = wf_global_pixel(L, L.first_pixel + lp); // pixel of the virtual (view-major) image
-        const uint32_t v = vpix / L.view_pixels;
-        sensor_ray_of(L.sensors, v, L.width, L.height, vpix - v * L.view_pixels, L.first_sample + ds,
-                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
-        st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
-    }
-    st.flush(L.stats);
-}
-
-// An accumulator pass (WfAccum): path i takes the entry whose prefix range holds off[first] + i (binary search; a pixel's paths stay
-// consecutive, so the 64 queue positions of a packet are still the samples of one or a few pixels). Paths [exact count, L.n_paths) of the
-// upper bound get an empty finished sample (no frames), so that wf_fold, which runs over L.n_paths, reads nothing stale.
-template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_list(const DevScene S, const WfLaunch L, const WfAccum A) {
-    LaneStats<STATS> st;
-    const uint32_t *off = A.list_off + A.first_entry;
-    const uint32_t base = off[0], n_exact = off[A.n_entries] - base;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        L.counters[WF_CNT_IN] = n_exact;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
-        if (i >= n_exact) {
-            L.sample_out[i] = RtF4{0.f, 0.f, 0.f, __uint_as_float(0u)};
-            continue;
-        }
-        const uint32_t g = base + i;
-        uint32_t lo = 0, hi = A.n_entries - 1; // the last e with off[e] <= g (entries have k >= 1: off is strictly increasing)
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1u) >> 1;
-            if (off[mid] <= g)
-                lo = mid;
-            else
-                hi = mid - 1u;
-        }
-        const uint32_t e = A.first_entry + lo;
-        sensor_ray_of(L.sensors, 0u, L.width, L.height, A.list_pix[e], A.list_base[e] + (g - off[lo]), // an accumulator has one camera
-                      [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &rng) { wf_store_first<ENVD>(S, L, i, o, d, rng); });
-        st.cast();
-    }
-    st.flush(L.stats);
-}
-
-// A pass of rt_render_rays (WfRays): path i is sample index first_sample + ds of output first_pixel + lp, like wf_generate's, and that is
-// sample `first_sample + ds % K` of ray `output * G + ds / K` of the caller's buffer. The lane reads its 32-byte record as two 16-byte pieces
-// (with K = 1 the lanes of a wave read consecutive records), seeds the stream the record names, makes gen_ray's two jitter draws and discards
-// them (raytracer.h:527-538: the stream then stands where a camera ray's stands), and stores the ray as given: no normalisation.
-template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_rays(const DevScene S, const WfLaunch L, const WfRays R) {
-    LaneStats<STATS> st;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        L.counters[WF_CNT_IN] = L.n_paths;
-    const uint4 *recs = reinterpret_cast<const uint4 *>(R.rays);
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
-        const uint32_t lp = i / L.pass_samples;
-        const uint32_t ds = L.first_sample + (i - lp * L.pass_samples); // < G * K
-        const uint32_t sub = ds / R.samples;                            // < G
-        const size_t ray = (size_t)(L.first_pixel + lp) * R.group + sub;
-        const uint4 p0 = recs[2 * ray], p1 = recs[2 * ray + 1];
-        Rng<RT_RNG_DEVICE> rng;
-        rt_xoshiro_seed(&rng.g, R.seed, p1.z, p1.w + (ds - sub * R.samples)); // the sample index wraps mod 2^32
-        (void)uniform_real(rng, 0.0f, 1.0f);
-        (void)uniform_real(rng, 0.0f, 1.0f);
-        wf_store_first<ENVD>(S, L, i, mk(__uint_as_float(p0.x), __uint_as_float(p0.y), __uint_as_float(p0.z)),
-                       mk(__uint_as_float(p0.w), __uint_as_float(p1.x), __uint_as_float(p1.y)), rng);
-        st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
-    }
-    st.flush(L.stats);
-}
-
-// A pass of rt_bake (WfBake): path i is sample S = bake.first_sample + first_sample + ds of point first_pixel + lp. The lane reads the point's
-// 32-byte record as two 16-byte pieces, seeds the path's stream from (seed, point.stream, S) and makes gen_ray's two jitter draws as
-// wf_generate_rays does, then asks bake_ray (rt_dev_bake.h) for the ray: the rt_ray record rt_bake_rays writes for (point, S) is this ray.
-template <bool STATS, bool ENVD> __global__ __launch_bounds__(256) void wf_generate_bake(const DevScene S, const WfLaunch L, const WfBake B) {
-    LaneStats<STATS> st;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        L.counters[WF_CNT_IN] = L.n_paths;
-    const uint4 *recs = reinterpret_cast<const uint4 *>(B.points);
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < L.n_paths; i += gridDim.x * blockDim.x) {
-        const uint32_t lp = i / L.pass_samples;
-        const uint32_t smp = B.first_sample + (L.first_sample + (i - lp * L.pass_samples)); // the sample index wraps mod 2^32
-        const size_t pt = (size_t)(L.first_pixel + lp);
-        const uint4 p0 = recs[2 * pt], p1 = recs[2 * pt + 1];
-        Rng<RT_RNG_DEVICE> rng;
-        rt_xoshiro_seed(&rng.g, B.seed, p1.z, smp);
-        (void)uniform_real(rng, 0.0f, 1.0f);
-        (void)uniform_real(rng, 0.0f, 1.0f);
-        V3 o, d;
-        bake_ray(B.kind, B.offset, B.seed, p0, p1, smp, o, d);
-        wf_store_first<ENVD>(S, L, i, o, d, rng);
-        st.cast(); // ray_depth >= 1: trace_ray casts (raytracer.h:600)
-    }
-    st.flush(L.stats);
-}
-
-// rt_bake_rays: record i of the output is sample first_sample + i % samples of point i / samples, as an rt_ray {o, d, stream = point.stream,
-// first_sample = S}, stored as two 16-byte pieces per lane like wf_sensor_rays' records.
-__global__ __launch_bounds__(256) void wf_bake_rays(const WfBake B, uint32_t samples, uint32_t n, uint4 *out) {
-    const uint4 *recs = reinterpret_cast<const uint4 *>(B.points);
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t pt = i / samples;
-        const uint32_t smp = B.first_sample + (i - pt * samples);
-        const uint4 p0 = recs[2ull * pt], p1 = recs[2ull * pt + 1];
-        V3 o, d;
-        bake_ray(B.kind, B.offset, B.seed, p0, p1, smp, o, d);
-        out[2ull * i] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
-        out[2ull * i + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), p1.z, smp);
-    }
-}
-
-// rt_sensor_rays: record i of the output is sample first_sample + i % samples of pixel first_pixel + i / samples of the one sensor `sensor[0]`,
-// as an rt_ray {o, d, stream = pix, first_sample = s}, stored as two 16-byte pieces per lane (consecutive lanes, consecutive records). The
-// RNG state is not kept: wf_generate_rays reseeds from (stream, first_sample) and repeats the two draws.
-__global__ __launch_bounds__(256) void wf_sensor_rays(const WfSensor *sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples,
-                                                      uint32_t n, uint4 *out) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t lp = i / samples;
-        const uint32_t pix = first_pixel + lp, s = first_sample + (i - lp * samples);
-        sensor_ray_of(sensor, 0u, width, height, pix, s, [&](V3 o, V3 d, const Rng<RT_RNG_DEVICE> &) {
-            out[2ull * i] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
-            out[2ull * i + 1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), pix, s);
-        });
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ extend
 // Closest hit for every queued ray. Two kinds of work alternate inside a wave instead of being interleaved:
@@ -503,7 +359,7 @@ __global__ __launch_bounds__(256) void wf_extend_prims(const DevScene S, const W
 // ------------------------------------------------------------------------------------------------ first-hit features
 // A pass of a feature accumulator (rt_abi.h RT_ACCUM_FEATURES), after bounce 0's closest hits: the albedo, shading normal and distance of every
 // primary ray's hit, from the shading record wf_shade is about to make of the same (ray, hit) pair (make_surf), one 32-byte record per path.
-// At bounce 0 queue position i holds path i (wf_generate*), and no order is in force. Counts nothing: the event counters are shade()'s.
+// At bounce 0 queue position i holds path i (wf_first_stage), and no order is in force. Counts nothing: the event counters are shade()'s.
 __global__ __launch_bounds__(256) void wf_features(const DevScene S, const WfLaunch L, const WfFeat F) {
     __shared__ float s_lin[256];
     __shared__ float s_gam[256];
@@ -732,187 +588,9 @@ __global__ __launch_bounds__(64) void wf_advance(uint32_t *counters, uint32_t *s
         counters[WF_CNT_XCD + k * WF_CNT_XCD_STRIDE] = 0u;
 }
 
-// ------------------------------------------------------------------------------------------------ fold
-// The return path of the recursion (raytracer.h:588-590): every finished path's pending frames `emission + inner * scl`, innermost
-// first, then sanitize_nans (:607-616). One lane per path of the pass, all lanes busy; frames are stored level by level (WfLaunch::fold), so a
-// wave reads 2 KB of consecutive records per level and nothing it does not need.
-__global__ __launch_bounds__(256) void wf_fold(const WfLaunch L) {
-    for (uint32_t path = blockIdx.x * blockDim.x + threadIdx.x; path < L.n_paths; path += gridDim.x * blockDim.x) {
-        const RtF4 v = L.sample_out[path];
-        V3 res = mk(v.x, v.y, v.z);
-        uint32_t nb = __float_as_uint(v.w);
-        while (nb > 0) {
-            --nb;
-            V3 emission, scl;
-            wf_load_fold(wf_fold_at(L.fold, L.n_paths, nb, path), emission, scl); // frame level nb: adjacent lanes, adjacent records
-            const V3 clr = res * scl;
-            res = emission + clr;
-        }
-        if (isnan_f(res.x))
-            res.x = 0;
-        if (isnan_f(res.y))
-            res.y = 0;
-        if (isnan_f(res.z))
-            res.z = 0;
-        L.sample_out[path] = RtF4{res.x, res.y, res.z, 0.f};
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ resolve
-// render_pixel's `res += sanitize_nans(...)` loop (raytracer.h:621-625) for the samples of this pass, in sample order,
-// continuing the running sum of earlier passes; the final pass divides by the sample count (:626).
-__global__ __launch_bounds__(256) void wf_resolve(const WfLaunch L, int first_pass, int last_pass) {
-    for (uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x; lp < L.pass_pixels; lp += gridDim.x * blockDim.x) {
-        V3 acc = mk(0, 0, 0);
-        if (!first_pass) {
-            const RtF4 a = L.accum[lp];
-            acc = mk(a.x, a.y, a.z);
-        }
-        const RtF4 *src = L.sample_out + (size_t)lp * L.pass_samples;
-        for (uint32_t ds = 0; ds < L.pass_samples; ++ds) {
-            const RtF4 v = src[ds];
-            acc = acc + mk(v.x, v.y, v.z);
-        }
-        if (last_pass) {
-            const V3 out = acc / (float)L.samples;
-            float *dst = L.fb + 3ull * wf_global_pixel(L, L.first_pixel + lp);
-            dst[0] = out.x;
-            dst[1] = out.y;
-            dst[2] = out.z;
-        } else {
-            L.accum[lp] = RtF4{acc.x, acc.y, acc.z, 0.f};
-        }
-    }
-}
-
-// The fold of a pass of rt_bake (WfBake), in wf_resolve's place: one lane per output (point, k) with k < 1 (IRRADIANCE) or k < 9 (SH9) owns its
-// three sums and adds the pass's samples in sample order; the nine lanes of an SH point read the same sample records. The sums of earlier
-// sample passes are in `out` itself; the last pass divides by the sample count and scales. SH9 weighs sample s by Y_k of its own direction,
-// which bake_ray makes again from (seed, stream, S): no direction buffer is kept between the stages.
-__global__ __launch_bounds__(256) void wf_resolve_bake(const WfLaunch L, const WfBake B, int first_pass, int last_pass) {
-    const bool sh = B.kind == RT_BAKE_SH9;
-    const uint32_t nk = sh ? 9u : 1u;
-    const uint64_t n = (uint64_t)L.pass_pixels * nk;
-    const uint4 *recs = reinterpret_cast<const uint4 *>(B.points);
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t lp = (uint32_t)(t / nk), k = (uint32_t)(t - (uint64_t)lp * nk);
-        const size_t pt = (size_t)(L.first_pixel + lp);
-        float *dst = B.out + (pt * nk + k) * 3u;
-        V3 acc = first_pass ? mk(0, 0, 0) : ld3(dst);
-        const RtF4 *src = L.sample_out + (size_t)lp * L.pass_samples;
-        if (sh) {
-            const uint4 p0 = recs[2 * pt], p1 = recs[2 * pt + 1];
-            for (uint32_t ds = 0; ds < L.pass_samples; ++ds) {
-                const RtF4 v = src[ds];
-                V3 o, d;
-                bake_ray(B.kind, B.offset, B.seed, p0, p1, B.first_sample + (L.first_sample + ds), o, d);
-                const float y = bake_sh9(k, d);
-                acc = acc + mk(v.x * y, v.y * y, v.z * y);
-            }
-        } else {
-            for (uint32_t ds = 0; ds < L.pass_samples; ++ds) {
-                const RtF4 v = src[ds];
-                acc = acc + mk(v.x, v.y, v.z);
-            }
-        }
-        if (last_pass)
-            acc = (acc / (float)L.samples) * (sh ? 4.0f * PI_F : PI_F);
-        dst[0] = acc.x;
-        dst[1] = acc.y;
-        dst[2] = acc.z;
-    }
-}
-
-// The same loop for an accumulator pass: one lane per entry adds its k consecutive samples onto S_p, and the even-index ones onto E_p,
-// in sample order, then n_p += k. A pixel has at most one entry per round, so the lane owns the pixel's sums; no division here.
-__global__ __launch_bounds__(256) void wf_resolve_list(const WfLaunch L, const WfAccum A) {
-    const uint32_t *off = A.list_off + A.first_entry;
-    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
-        const uint32_t e = A.first_entry + le, p = A.list_pix[e], s0 = A.list_base[e];
-        const uint32_t k = off[le + 1] - off[le];
-        V3 acc = ld3(A.sum + 3ull * p), ev = ld3(A.even_sum + 3ull * p);
-        const RtF4 *src = L.sample_out + (off[le] - off[0]);
-        for (uint32_t j = 0; j < k; ++j) {
-            const RtF4 v = src[j];
-            acc = acc + mk(v.x, v.y, v.z);
-            if (((s0 + j) & 1u) == 0u)
-                ev = ev + mk(v.x, v.y, v.z);
-        }
-        A.sum[3ull * p] = acc.x, A.sum[3ull * p + 1] = acc.y, A.sum[3ull * p + 2] = acc.z;
-        A.even_sum[3ull * p] = ev.x, A.even_sum[3ull * p + 1] = ev.y, A.even_sum[3ull * p + 2] = ev.z;
-        A.count[p] = s0 + k;
-    }
-}
-
-// The feature sums of the same entries (WfFeat): the lane that owns the pixel adds its k records in sample order. Runs before
-// wf_resolve_list of the pass (it reads the entry's base count from the list, never n_p).
-__global__ __launch_bounds__(256) void wf_resolve_features(const WfAccum A, const WfFeat F) {
-    const uint32_t *off = A.list_off + A.first_entry;
-    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
-        const uint32_t p = A.list_pix[A.first_entry + le];
-        const uint32_t k = off[le + 1] - off[le];
-        V3 al = ld3(F.albedo_sum + 3ull * p), nr = ld3(F.normal_sum + 3ull * p);
-        float z = F.depth_sum[p];
-        uint32_t hits = F.hits[p];
-        const RtF4 *src = F.rec + 2ull * (off[le] - off[0]);
-        for (uint32_t j = 0; j < k; ++j) {
-            const RtF4 r0 = src[2u * j], r1 = src[2u * j + 1u];
-            al = al + mk(r0.x, r0.y, r0.z);
-            nr = nr + mk(r1.x, r1.y, r1.z);
-            z = z + r0.w;
-            hits += __float_as_uint(r1.w);
-        }
-        F.albedo_sum[3ull * p] = al.x, F.albedo_sum[3ull * p + 1] = al.y, F.albedo_sum[3ull * p + 2] = al.z;
-        F.normal_sum[3ull * p] = nr.x, F.normal_sum[3ull * p + 1] = nr.y, F.normal_sum[3ull * p + 2] = nr.z;
-        F.depth_sum[p] = z;
-        F.hits[p] = hits;
-    }
-}
-
-// The id tables of the same entries (WfIds; the rule: rt_abi.h rt_accum_attach_ids): the lane that owns the pixel takes its k ids in sample
-// order. Runs before wf_resolve_list of the pass, like wf_resolve_features, and reads neither n_p nor the base count: the table itself is the
-// state. K is a run-time value, so the slots are walked in memory (slot-major: a wave's lanes stay coalesced), never in a private array. A
-// sample equal to the one before it, the common case, goes to the slot that one went to without a walk.
-__global__ __launch_bounds__(256) void wf_resolve_ids(const WfAccum A, const WfIds I) {
-    const uint32_t *off = A.list_off + A.first_entry;
-    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
-        const uint32_t p = A.list_pix[A.first_entry + le];
-        const uint32_t k = off[le + 1] - off[le];
-        const uint32_t *src = I.rec + (off[le] - off[0]);
-        uint32_t *sid = I.slot_id + p, *cnt = I.slot_count + p;
-        uint32_t other = I.other[p];
-        uint32_t last_id = 0u, last_j = I.k; // last_j == K: no slot known for last_id
-        for (uint32_t s = 0; s < k; ++s) {
-            const uint32_t id = src[s];
-            if (last_j < I.k && id == last_id) {
-                cnt[(size_t)last_j * I.pixels] += 1u;
-                continue;
-            }
-            uint32_t j = 0;
-            for (; j < I.k; ++j) {
-                const size_t w = (size_t)j * I.pixels;
-                const uint32_t c = cnt[w];
-                if (c == 0u) { // the lowest empty slot: every slot below it holds another id
-                    sid[w] = id;
-                    cnt[w] = 1u;
-                    break;
-                }
-                if (sid[w] == id) {
-                    cnt[w] = c + 1u;
-                    break;
-                }
-            }
-            if (j == I.k)
-                other += 1u;
-            last_id = id, last_j = j;
-        }
-        I.other[p] = other;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ probe: rays in, hits out
 // rt_cast_rays_ex: arbitrary rays go through the SAME closest-hit kernels the renderer launches. wf_from_rays writes them as
-// queue records (what wf_generate / wf_shade write for their rays), wf_hits_out turns the hit records into the probe's output.
+// queue records (what wf_first_stage / wf_shade write for their rays), wf_hits_out turns the hit records into the probe's output.
 __global__ __launch_bounds__(256) void wf_from_rays(const WfLaunch L, const float *rays, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0)
@@ -995,11 +673,52 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
     return hipSuccess;
 }
 
-hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int num_cus, bool first_pass, bool last_pass, hipStream_t stream,
-                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync, const WfAccum *acc,
-                                 const WfFeat *feat, const WfRays *rays, const WfBake *bake, const WfIds *ids) {
+// the first stage of the pass's source (rt_wf_stages.h)
+static hipError_t launch_first_stage(const DevScene &S, const WfLaunch &L, const WfPassKind &kind, bool stats, dim3 grid, hipStream_t stream) {
+    return with_bools([&](auto ST, auto ED) {
+        switch (kind.source()) {
+        case WfPassKind::LIST:
+            return RT_LAUNCH_CHECKED((wf_first_stage<ST, ED, WfFromList>), grid, dim3(256), 0, stream, S, L, kind.entries());
+        case WfPassKind::RAYS:
+            return RT_LAUNCH_CHECKED((wf_first_stage<ST, ED, WfFromRays>), grid, dim3(256), 0, stream, S, L, kind.ray_buffer());
+        case WfPassKind::BAKE:
+            return RT_LAUNCH_CHECKED((wf_first_stage<ST, ED, WfFromBake>), grid, dim3(256), 0, stream, S, L, kind.bake_points());
+        default:
+            return RT_LAUNCH_CHECKED((wf_first_stage<ST, ED, WfFromCameras>), grid, dim3(256), 0, stream, S, L, WfFromCameras::Arg{});
+        }
+    }, stats, S.env.texels != nullptr && S.env.marg != nullptr);
+}
+
+// the last stage of the pass's kind: where the folded samples of the pass go
+static hipError_t launch_last_stage(const WfLaunch &L, const WfPassKind &kind, const WfPassStep &step, int num_cus, hipStream_t stream) {
+    const dim3 block(256);
+    const int first = step.first_pass ? 1 : 0, last = step.last_pass ? 1 : 0;
+    if (kind.source() == WfPassKind::LIST) { // the feature sums and the id tables go before the sums: they read the entry's base count from the list
+        const WfAccum &A = kind.entries();
+        const int res_blocks = (int)((A.n_entries + 255u) / 256u);
+        if (kind.features())
+            WF_LAUNCH(wf_resolve_features, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.features());
+        if (kind.ids())
+            WF_LAUNCH(wf_resolve_ids, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.ids());
+        WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, A);
+    } else if (kind.source() == WfPassKind::BAKE) { // the fold the bake's kind asks for, one lane per (point, k)
+        const WfBake &B = kind.bake_points();
+        const uint64_t lanes = (uint64_t)L.pass_pixels * (B.kind == RT_BAKE_SH9 ? 9u : 1u);
+        const uint32_t bake_blocks = (uint32_t)std::min<uint64_t>((lanes + 255u) / 256u, (uint64_t)num_cus * 64u);
+        WF_LAUNCH(wf_resolve_bake, dim3(bake_blocks > 0 ? bake_blocks : 1), block, 0, stream, L, B, first, last);
+    } else { // cameras, a caller's rays: the image, or the outputs as a one-row image
+        const int res_blocks = (int)((L.pass_pixels + 255u) / 256u);
+        WF_LAUNCH(wf_resolve, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, first, last);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind &kind, const WfPassStep &step, bool stats, int num_cus, hipStream_t stream,
+                                 EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
+    if (!step.time_extends)
+        extend_events = nullptr;
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
     if (e != hipSuccess)
         return e;
@@ -1010,16 +729,7 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
         return e;
     if (packet_census_out)
         packet_census_out[0] = packet_census_out[1] = 0ull;
-    e = with_bools([&](auto ST, auto ED) {
-        if (acc) // an accumulator pass: the first stage follows the round's list (wf_generate_list)
-            return RT_LAUNCH_CHECKED((wf_generate_list<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *acc);
-        if (rays) // a pass of rt_render_rays: the caller's rays and streams (wf_generate_rays)
-            return RT_LAUNCH_CHECKED((wf_generate_rays<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *rays);
-        if (bake) // a pass of rt_bake: the samples of the bake points (wf_generate_bake)
-            return RT_LAUNCH_CHECKED((wf_generate_bake<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L, *bake);
-        return RT_LAUNCH_CHECKED((wf_generate<ST, ED>), dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, S, L);
-    }, stats, S.env.texels != nullptr && S.env.marg != nullptr);
-    if (e != hipSuccess)
+    if ((e = launch_first_stage(S, L, kind, stats, dim3(gen_blocks > 0 ? gen_blocks : 1), stream)) != hipSuccess)
         return e;
     const int ext_blocks = (int)(L.stack_stride / 256u); // rt_scene.cpp sizes the overflow workspace for exactly this grid
     const int shade_blocks = num_cus * RT_SHADE_BLOCKS_PER_CU;
@@ -1079,10 +789,10 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             (void)hipEventRecord(e1, stream);
         if (S.n_prims)
             WF_LAUNCH(wf_extend_prims, dim3(shade_blocks), block, 0, stream, S, L);
-        if (b == 0 && acc && feat) // a feature accumulator's pass: the primary rays' first hits are final here
-            WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *feat);
-        if (b == 0 && acc && ids) // ... and so are their ids
-            WF_LAUNCH(wf_ids, dim3(shade_blocks), block, 0, stream, S, L, *ids);
+        if (b == 0 && kind.features()) // a feature accumulator's pass: the primary rays' first hits are final here
+            WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *kind.features());
+        if (b == 0 && kind.ids()) // ... and so are their ids
+            WF_LAUNCH(wf_ids, dim3(shade_blocks), block, 0, stream, S, L, *kind.ids());
         // Will the next bounce be sorted? Its own bound is not known yet (it arrives one bounce late) but cannot exceed this one, so: may it be.
         // Then this wf_shade writes the sort's input itself, key and slot at the physical slot of every ray it makes, and every slot it leaves
         // empty (the ends of the 64 sub-queue regions) must already hold a pad: RT_RAY_KEY_PAD in the compared bits, behind every real key
@@ -1131,24 +841,7 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, bool stats, int 
             return e;
         std::memcpy(packet_census_out, hs->counts + WF_HOST_CENSUS_WORD, 2 * sizeof(unsigned long long));
     }
-    if (acc) { // ... and so does the last
-        const int res_blocks = (int)((acc->n_entries + 255u) / 256u);
-        if (feat)
-            WF_LAUNCH(wf_resolve_features, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, *acc, *feat);
-        if (ids)
-            WF_LAUNCH(wf_resolve_ids, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, *acc, *ids);
-        WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, *acc);
-        return hipSuccess;
-    }
-    if (bake) { // the fold the kind asks for, one lane per (point, k)
-        const uint64_t lanes = (uint64_t)L.pass_pixels * (bake->kind == RT_BAKE_SH9 ? 9u : 1u);
-        const uint32_t bake_blocks = (uint32_t)std::min<uint64_t>((lanes + 255u) / 256u, (uint64_t)num_cus * 64u);
-        WF_LAUNCH(wf_resolve_bake, dim3(bake_blocks > 0 ? bake_blocks : 1), block, 0, stream, L, *bake, first_pass ? 1 : 0, last_pass ? 1 : 0);
-        return hipSuccess;
-    }
-    const int res_blocks = (int)((L.pass_pixels + 255u) / 256u);
-    WF_LAUNCH(wf_resolve, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, first_pass ? 1 : 0, last_pass ? 1 : 0);
-    return hipSuccess;
+    return launch_last_stage(L, kind, step, num_cus, stream);
 }
 
 hipError_t launch_sensor_rays(const WfSensor *d_sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples, uint32_t n,

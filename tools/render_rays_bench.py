@@ -5,7 +5,7 @@ On the sponza-like scene of bench.make_scene at --size x --size x --spp (512 x 5
 device buffer and device outputs, one process:
   * rt_render_rays (samples = 1, rays_per_output = spp) and rt_render of the same shape take turns, --repeat times after one warm-up each;
     Msamples/s of both from the device time of each call (rt_stats.kernel_ms), best and median;
-  * the share of wf_generate_rays in the device time of rt_render_rays' kernels: a child process (this file with --child) that only renders
+  * the share of the rays first stage (wf_first_stage<., ., WfFromRays>) in the device time of rt_render_rays' kernels: a child process (this file with --child) that only renders
     rays, under `rocprofv3 --kernel-trace --stats`, started BEFORE this process touches the GPU, in a process group of its own; if it does
     not end with status 0 this process ends with its status (124 for a time limit) and starts nothing on the GPU.
 Every GPU step of this process runs under --step-timeout too (a watchdog ends the process: a hung step must not be waited for).
@@ -67,7 +67,7 @@ def kernel_share():
             return None, "the profiler wrote no kernel_stats.csv", []
         rows = list(csv.DictReader(open(files[0])))
         total = sum(float(x["TotalDurationNs"]) for x in rows)
-        gen = sum(float(x["TotalDurationNs"]) for x in rows if "wf_generate_rays" in x["Name"])
+        gen = sum(float(x["TotalDurationNs"]) for x in rows if "wf_first_stage" in x["Name"] and "WfFromRays" in x["Name"])
         return gen / total, total / 1e6, sorted(rows, key=lambda x: -float(x["TotalDurationNs"]))[:6]
     finally:
         shutil.rmtree(d, ignore_errors=True)
@@ -159,9 +159,9 @@ if has_rays:
         f"(the same camera model with numpy's jitter instead of gen_ray's: nearly, not exactly, the same paths)")
 if share is not None:
     if share[0] is None:
-        say(f"wf_generate_rays share: not measured ({share[1]})")
+        say(f"rays first stage share: not measured ({share[1]})")
     else:
-        say(f"wf_generate_rays: {100 * share[0]:.2f} % of the {share[1]:.2f} ms of kernel time of a process that only ran rt_render_rays (rocprofv3 --kernel-trace --stats, {1 + CHILD_REPEAT} calls)")
+        say(f"rays first stage (wf_first_stage over WfFromRays): {100 * share[0]:.2f} % of the {share[1]:.2f} ms of kernel time of a process that only ran rt_render_rays (rocprofv3 --kernel-trace --stats, {1 + CHILD_REPEAT} calls)")
         for x in share[2]:
             nm = x["Name"]
             nm = nm[nm.find("wf_"):][:44] if "wf_" in nm else nm[:44]

@@ -6,8 +6,8 @@ cd $R; f=$(ls $O/shardtrace/*/*kernel_trace.csv | head -1)
 python3 - "$f" <<'PY'
 import csv, sys, collections
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
-# the last render of the run = the last wf_generate .. film kernel sequence (shard 1/8)
-gen = [i for i, r in enumerate(rows) if "wf_generate" in r["Kernel_Name"]]
+# the last render of the run = the last first stage .. film kernel sequence (shard 1/8)
+gen = [i for i, r in enumerate(rows) if "wf_first_stage" in r["Kernel_Name"]]
 a = gen[-1]
 seq = rows[a:]
 end = max(i for i, r in enumerate(seq) if "film_kernel" in r["Kernel_Name"] or "wf_resolve" in r["Kernel_Name"])
