@@ -1,7 +1,7 @@
 // rt_accum_host.cpp — the host side of the accumulators (rt_abi.h rt_accum_*; their kernels are rt_accum.hip).
 //
 // An accumulator owns its per-pixel state (S, E, n, err, the round's target and list, about 64 B per pixel) and one camera record; it
-// borrows the scene's stream, its wavefront workspace and its framebuffer staging. Every call ends with the stream synchronised, so an
+// borrows the scene's stream, its wavefront workspace and its staging block (rt_call_io.h). Every call ends with the stream synchronised, so an
 // rt_render on the same scene in between only ever sees an idle workspace, and never touches the accumulator's buffers.
 #include <algorithm>
 #include <cmath>
@@ -231,7 +231,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
         }
         return RT_OK;
     };
-    if (int rc = rt::timed_call(s, counters, [] { return RT_OK; }, rounds_of_call); rc != RT_OK)
+    if (int rc = rt::timed_call(s, counters, nullptr, rounds_of_call); rc != RT_OK)
         return rc;
     if (rounds_out)
         *rounds_out = rounds;
@@ -271,16 +271,31 @@ extern "C" int rt_accum_resolve(rt_accum *acc, uint32_t flags, float *fb_rgb) {
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: null argument or flags other than RT_FLAG_DEVICE_FB");
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)acc->width * acc->height;
-    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
-    if (!device_fb)
-        if (int rc = s->ensure_fb(3 * n); rc != RT_OK)
-            return rc;
-    HIP_TRY(rt::launch_accum_image(acc->R, device_fb ? fb_rgb : s->fb.get(), s->stream));
-    if (!device_fb)
-        HIP_TRY(hipMemcpyAsync(fb_rgb, s->fb.get(), 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_fb;
+    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
+    return io.run([&]() -> int {
+        HIP_TRY(rt::launch_accum_image(acc->R, d_fb, s->stream));
+        return RT_OK;
+    });
+}
+
+// `image` fills an internal float image; the film (image.h:49-82, as rt_render_rgb8) makes the rgb8 destination of it
+template <class Image> static int film_image(rt_accum *acc, uint32_t flags, uint8_t *rgb8, Image image) {
+    rt_scene *s = acc->scene;
+    if (int rc = s->ensure_film(); rc != RT_OK)
+        return rc;
+    const uint32_t n = acc->width * acc->height;
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_fb;
+    uint8_t *d_rgb8;
+    io.scratch(&d_fb, 12ull * n);
+    io.out(&d_rgb8, rgb8, 3ull * n);
+    return io.run([&]() -> int {
+        HIP_TRY(image(d_fb));
+        HIP_TRY(rt::launch_film(d_fb, d_rgb8, n, 0, 1, n, s->film_table.get(), s->stream));
+        return RT_OK;
+    });
 }
 
 extern "C" int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb8) {
@@ -288,20 +303,22 @@ extern "C" int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_rgb8: null argument or flags other than RT_FLAG_DEVICE_FB");
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
-    const uint32_t n = acc->width * acc->height;
-    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
-    int rc = s->ensure_fb(3ull * n);
-    if (rc == RT_OK)
-        rc = s->ensure_film(device_fb ? 0 : 3ull * n);
-    if (rc != RT_OK)
-        return rc;
-    uint8_t *d_rgb8 = device_fb ? rgb8 : s->rgb8.get();
-    HIP_TRY(rt::launch_accum_image(acc->R, s->fb.get(), s->stream));
-    HIP_TRY(rt::launch_film(s->fb.get(), d_rgb8, n, 0, 1, n, s->film_table.get(), s->stream)); // image.h:49-82, as rt_render_rgb8
-    if (!device_fb)
-        HIP_TRY(hipMemcpyAsync(rgb8, d_rgb8, 3ull * n, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    return film_image(acc, flags, rgb8, [&](float *d_fb) { return rt::launch_accum_image(acc->R, d_fb, s->stream); });
+}
+
+// the accumulator's own arrays, each to a host destination that is not null
+struct ReadBack {
+    void *host;
+    const void *dev;
+    size_t bytes;
+};
+static int read_back(rt_scene *s, std::initializer_list<ReadBack> list) {
+    return rt::queue_and_wait(s->stream, [&]() -> int {
+        for (const ReadBack &r : list)
+            if (r.host)
+                HIP_TRY(hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, s->stream));
+        return RT_OK;
+    });
 }
 
 extern "C" int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb, uint32_t *samples, float *error) {
@@ -310,16 +327,7 @@ extern "C" int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb,
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = (size_t)acc->width * acc->height;
-    if (sum_rgb)
-        HIP_TRY(hipMemcpyAsync(sum_rgb, acc->R.sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
-    if (even_sum_rgb)
-        HIP_TRY(hipMemcpyAsync(even_sum_rgb, acc->R.even_sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
-    if (samples)
-        HIP_TRY(hipMemcpyAsync(samples, acc->R.count, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    if (error)
-        HIP_TRY(hipMemcpyAsync(error, acc->R.err, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    return read_back(s, {{sum_rgb, acc->R.sum, 12 * n}, {even_sum_rgb, acc->R.even_sum, 12 * n}, {samples, acc->R.count, 4 * n}, {error, acc->R.err, 4 * n}});
 }
 
 // ---- first-hit features and the denoiser (rt_abi.h RT_ACCUM_FEATURES, rt_accum_denoise)
@@ -337,16 +345,7 @@ extern "C" int rt_accum_read_features(rt_accum *acc, float *albedo_sum, float *n
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = (size_t)acc->width * acc->height;
-    if (albedo_sum)
-        HIP_TRY(hipMemcpyAsync(albedo_sum, acc->F.albedo_sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
-    if (normal_sum)
-        HIP_TRY(hipMemcpyAsync(normal_sum, acc->F.normal_sum, 12 * n, hipMemcpyDeviceToHost, s->stream));
-    if (depth_sum)
-        HIP_TRY(hipMemcpyAsync(depth_sum, acc->F.depth_sum, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    if (hits)
-        HIP_TRY(hipMemcpyAsync(hits, acc->F.hits, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    return read_back(s, {{albedo_sum, acc->F.albedo_sum, 12 * n}, {normal_sum, acc->F.normal_sum, 12 * n}, {depth_sum, acc->F.depth_sum, 4 * n}, {hits, acc->F.hits, 4 * n}});
 }
 
 extern "C" int rt_accum_resolve_features(rt_accum *acc, uint32_t flags, float *albedo, float *normal, float *depth) {
@@ -357,23 +356,15 @@ extern "C" int rt_accum_resolve_features(rt_accum *acc, uint32_t flags, float *a
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = (size_t)acc->width * acc->height;
-    if (flags & RT_FLAG_DEVICE_FB) {
-        HIP_TRY(rt::launch_accum_feature_means(acc->R, acc->F, albedo, normal, depth, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_a, *d_n, *d_z; // on a host call all three are computed; a null destination is not copied
+    io.out(&d_a, albedo, 12 * n);
+    io.out(&d_n, normal, 12 * n);
+    io.out(&d_z, depth, 4 * n);
+    return io.run([&]() -> int {
+        HIP_TRY(rt::launch_accum_feature_means(acc->R, acc->F, d_a, d_n, d_z, s->stream));
         return RT_OK;
-    }
-    if (int rc = s->ensure_fb(7 * n); rc != RT_OK) // staging: albedo, normal, depth
-        return rc;
-    float *d_a = s->fb.get(), *d_n = s->fb.get() + 3 * n, *d_z = s->fb.get() + 6 * n;
-    HIP_TRY(rt::launch_accum_feature_means(acc->R, acc->F, d_a, d_n, d_z, s->stream));
-    if (albedo)
-        HIP_TRY(hipMemcpyAsync(albedo, d_a, 12 * n, hipMemcpyDeviceToHost, s->stream));
-    if (normal)
-        HIP_TRY(hipMemcpyAsync(normal, d_n, 12 * n, hipMemcpyDeviceToHost, s->stream));
-    if (depth)
-        HIP_TRY(hipMemcpyAsync(depth, d_z, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    });
 }
 
 // the defaults of rt_denoise: chosen by the sweep recorded in profiles/denoise_quality.txt
@@ -416,18 +407,15 @@ extern "C" int rt_accum_denoise(rt_accum *acc, const rt_denoise *opt, uint32_t f
         return rc;
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)acc->width * acc->height;
-    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
     if (int rc = denoise_buffers(acc, "rt_accum_denoise"); rc != RT_OK)
         return rc;
-    if (!device_fb)
-        if (int rc = s->ensure_fb(3 * n); rc != RT_OK)
-            return rc;
-    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, device_fb ? fb_rgb : s->fb.get(), s->stream));
-    if (!device_fb)
-        HIP_TRY(hipMemcpyAsync(fb_rgb, s->fb.get(), 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_fb;
+    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
+    return io.run([&]() -> int {
+        HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, d_fb, s->stream));
+        return RT_OK;
+    });
 }
 
 extern "C" int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint32_t flags, uint8_t *rgb8) {
@@ -436,22 +424,9 @@ extern "C" int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint3
         return rc;
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
-    const uint32_t n = acc->width * acc->height;
-    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
-    int rc = denoise_buffers(acc, "rt_accum_denoise_rgb8");
-    if (rc == RT_OK)
-        rc = s->ensure_fb(3ull * n);
-    if (rc == RT_OK)
-        rc = s->ensure_film(device_fb ? 0 : 3ull * n);
-    if (rc != RT_OK)
+    if (int rc = denoise_buffers(acc, "rt_accum_denoise_rgb8"); rc != RT_OK)
         return rc;
-    uint8_t *d_rgb8 = device_fb ? rgb8 : s->rgb8.get();
-    HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, s->fb.get(), s->stream));
-    HIP_TRY(rt::launch_film(s->fb.get(), d_rgb8, n, 0, 1, n, s->film_table.get(), s->stream)); // image.h:49-82, as rt_accum_resolve_rgb8
-    if (!device_fb)
-        HIP_TRY(hipMemcpyAsync(rgb8, d_rgb8, 3ull * n, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    return film_image(acc, flags, rgb8, [&](float *d_fb) { return rt::launch_denoise(acc->R, acc->F, acc->D, O, d_fb, s->stream); });
 }
 
 // ---- id mattes (rt_abi.h rt_accum_attach_ids: the rule; the kernels: rt_wavefront.hip wf_ids / wf_resolve_ids, rt_accum.hip)
@@ -497,7 +472,7 @@ extern "C" int rt_accum_attach_ids(rt_accum *acc, const rt_id_desc *desc) {
             HIP_TRY(hipMemcpyAsync(table, desc->table, 4 * (size_t)n_table, device_table ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
         return RT_OK;
     };
-    if ((rc = rt::queue_and_wait(s, queue)) != RT_OK)
+    if ((rc = rt::queue_and_wait(s->stream, queue)) != RT_OK)
         return rc;
     I.table = table;
     acc->I = I;
@@ -524,16 +499,13 @@ extern "C" int rt_accum_read_ids(rt_accum *acc, uint32_t *ids, uint32_t *counts,
         if (!dst)
             continue;
         slot_major.resize(n * K);
-        HIP_TRY(hipMemcpyAsync(slot_major.data(), src, 4 * n * K, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (int rc = read_back(s, {{slot_major.data(), src, 4 * n * K}}); rc != RT_OK)
+            return rc;
         for (size_t p = 0; p < n; ++p)
             for (size_t j = 0; j < K; ++j)
                 dst[p * K + j] = slot_major[j * n + p];
     }
-    if (other)
-        HIP_TRY(hipMemcpyAsync(other, acc->I.other, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    return read_back(s, {{other, acc->I.other, 4 * n}});
 }
 
 extern "C" int rt_accum_resolve_labels(rt_accum *acc, uint32_t flags, uint32_t *label, float *coverage) {
@@ -543,23 +515,15 @@ extern "C" int rt_accum_resolve_labels(rt_accum *acc, uint32_t flags, uint32_t *
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_labels: flags other than RT_FLAG_DEVICE_FB");
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t n = acc->I.pixels;
-    if (flags & RT_FLAG_DEVICE_FB) {
-        HIP_TRY(rt::launch_accum_labels(acc->R, acc->I, label, coverage, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    uint32_t *d_label;
+    float *d_cov;
+    io.out(&d_label, label, 4 * (size_t)acc->I.pixels);
+    io.out(&d_cov, coverage, 4 * (size_t)acc->I.pixels);
+    return io.run([&]() -> int {
+        HIP_TRY(rt::launch_accum_labels(acc->R, acc->I, d_label, d_cov, s->stream));
         return RT_OK;
-    }
-    if (int rc = s->ensure_fb(2 * n); rc != RT_OK) // staging: label (u32 words), coverage
-        return rc;
-    uint32_t *d_label = reinterpret_cast<uint32_t *>(s->fb.get());
-    float *d_cov = s->fb.get() + n;
-    HIP_TRY(rt::launch_accum_labels(acc->R, acc->I, d_label, d_cov, s->stream));
-    if (label)
-        HIP_TRY(hipMemcpyAsync(label, d_label, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    if (coverage)
-        HIP_TRY(hipMemcpyAsync(coverage, d_cov, 4 * n, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    });
 }
 
 extern "C" int rt_accum_resolve_matte(rt_accum *acc, uint32_t flags, const uint32_t *ids, uint32_t n_ids, float *matte) {
@@ -569,22 +533,16 @@ extern "C" int rt_accum_resolve_matte(rt_accum *acc, uint32_t flags, const uint3
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_matte: null ids or matte, n_ids outside 1..4096, or flags other than RT_FLAG_DEVICE_FB");
     rt_scene *s = acc->scene;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t n = acc->I.pixels;
-    const bool device_fb = (flags & RT_FLAG_DEVICE_FB) != 0;
     std::vector<uint32_t> set(ids, ids + n_ids); // sorted, each id once: the kernel's binary search
     std::sort(set.begin(), set.end());
     set.erase(std::unique(set.begin(), set.end()), set.end());
     HIP_TRY(acc->matte_set.reserve(set.size()));
-    if (!device_fb)
-        if (int rc = s->ensure_fb(n); rc != RT_OK)
-            return rc;
-    float *d_matte = device_fb ? matte : s->fb.get();
-    auto queue = [&]() -> int { // `set` is a local: nothing of this may be in flight when it dies
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_matte;
+    io.out(&d_matte, matte, 4 * (size_t)acc->I.pixels);
+    return io.run([&]() -> int { // `set` is a local: nothing of this may be in flight when it dies
         HIP_TRY(hipMemcpyAsync(acc->matte_set.get(), set.data(), 4 * set.size(), hipMemcpyHostToDevice, s->stream));
         HIP_TRY(rt::launch_accum_matte(acc->R, acc->I, acc->matte_set.get(), (uint32_t)set.size(), d_matte, s->stream));
-        if (!device_fb)
-            HIP_TRY(hipMemcpyAsync(matte, d_matte, 4 * n, hipMemcpyDeviceToHost, s->stream));
         return RT_OK;
-    };
-    return rt::queue_and_wait(s, queue);
+    });
 }

@@ -82,7 +82,7 @@ extern "C" int rt_set_environment(rt_scene *s, const rt_environment *env) {
                  (rc = alloc(temp, 8, &B.total)) != RT_OK))
         return rc;
     double total = 0.0;
-    rc = rt::queue_and_wait(s, [&]() -> int {
+    rc = rt::queue_and_wait(s->stream, [&]() -> int {
         HIP_TRY(hipMemcpyAsync(const_cast<float *>(B.rgb), env->rgb, n * 12, hipMemcpyHostToDevice, s->stream));
         if (dist) {
             HIP_TRY(hipMemcpyAsync(const_cast<double *>(B.omega), omega.data(), (size_t)H * 8, hipMemcpyHostToDevice, s->stream));

@@ -11,35 +11,25 @@ namespace {
 
 // One probe round trip on the scene's own (non-blocking) stream, every copy ordered with the kernel: `in` goes up, `launch(d_in, d_out)`
 // queues the kernel(s) that fill the device buffers d_out[k] (out[k].bytes each), those with a host destination come back in the order
-// of `out`. The stream is synchronised also after a failed call: nothing may stay in flight over the DevBufs.
+// of `out`. The block is the call's own and released on every return path: a large probe leaves nothing on the scene.
 struct ProbeOut {
     void *host; // nullptr: computed, not wanted
     size_t bytes;
-    void *dev = nullptr; // where the kernels leave it, if not in a buffer of the round trip's own
 };
 template <size_t N, class Launch> int probe_round_trip(rt_scene *s, const char *fn, const float *in, size_t in_bytes, const ProbeOut (&out)[N], Launch launch) {
     HIP_TRY(hipSetDevice(s->device));
-    rt::DevBuf<float> b_in; // released on every return path, like b_out
-    rt::DevBuf<char> b_out[N];
+    rt::DevBuf<uint8_t> block;
+    rt::CallIo io(s->stream, block, false);
+    const float *d_in;
     void *d_out[N];
-    HIP_TRY(b_in.reserve(in_bytes ? in_bytes / sizeof(float) : 4));
-    for (size_t k = 0; k < N; ++k) {
-        if (!out[k].dev)
-            HIP_TRY(b_out[k].reserve(out[k].bytes ? out[k].bytes : 16));
-        d_out[k] = out[k].dev ? out[k].dev : b_out[k].get();
-    }
-    hipError_t e = hipMemcpyAsync(b_in.get(), in, in_bytes, hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess)
-        e = launch(b_in.get(), d_out);
+    io.in(&d_in, in, in_bytes);
     for (size_t k = 0; k < N; ++k)
-        if (e == hipSuccess && out[k].host)
-            e = hipMemcpyAsync(out[k].host, d_out[k], out[k].bytes, hipMemcpyDeviceToHost, s->stream);
-    const hipError_t se = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess)
-        e = se;
-    if (e != hipSuccess)
-        return rt::fail(RT_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
-    return RT_OK;
+        io.out(&d_out[k], out[k].host, out[k].bytes);
+    return io.run([&]() -> int {
+        if (hipError_t e = launch(d_in, d_out); e != hipSuccess)
+            return rt::fail(RT_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+        return RT_OK;
+    });
 }
 
 } // namespace
@@ -82,8 +72,7 @@ extern "C" int rt_cast_rays_ex(rt_scene *s, const float *rays, uint32_t n, uint3
     W.global_best = (mode == RT_CAST_EXTEND_GLOBAL || mode == RT_CAST_PACKET_GLOBAL) ? 1u : 0u;
     W.stats = stats ? s->d_stats : nullptr;
     const bool packet = mode == RT_CAST_PACKET || mode == RT_CAST_PACKET_GLOBAL;
-    DevStats h{};
-    const ProbeOut out[] = {{prim_out, (size_t)n * 4}, {bct_out, (size_t)n * 12}, {stats ? &h : nullptr, sizeof(h), s->d_stats}};
+    const ProbeOut out[] = {{prim_out, (size_t)n * 4}, {bct_out, (size_t)n * 12}};
     const int rc = probe_round_trip(s, "rt_cast_rays_ex", rays, (size_t)n * 24, out, [&](const float *d_rays, void *const *d) {
         hipError_t e = stats ? hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream) : hipSuccess;
         if (e == hipSuccess)
@@ -97,11 +86,10 @@ extern "C" int rt_cast_rays_ex(rt_scene *s, const float *rays, uint32_t n, uint3
     if (rc != RT_OK)
         return rc;
     if (stats) {
+        DevStats h{};
+        HIP_TRY(hipMemcpy(&h, s->d_stats, sizeof(h), hipMemcpyDeviceToHost)); // the stream is idle: as fill_stats reads them
+        rt::traversal_stats(h, stats);
         stats->casts = n;
-        stats->nodes_visited = h.nodes;
-        stats->box_tests = h.box_tests;
-        stats->tri_tests = h.tri_tests;
-        stats->light_queries = h.lq, stats->light_nodes = h.lnodes, stats->light_box_tests = h.lbox, stats->light_tri_tests = h.ltri, stats->light_hits = h.lhits;
         float ms = 0;
         if (hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess)
             stats->kernel_ms = ms;

@@ -30,8 +30,8 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
         return RT_OK;
     if (!rays || (!out_rgb && !rgb8_out))
         return rt::fail(RT_ERR_INVALID_ARG, name + ": null argument");
-    const bool device_fb = (p->flags & RT_FLAG_DEVICE_FB) != 0;
-    if (device_fb && (reinterpret_cast<uintptr_t>(rays) & 15u) != 0)
+    rt::CallIo io(s->stream, s->staging, (p->flags & RT_FLAG_DEVICE_FB) != 0);
+    if ((p->flags & RT_FLAG_DEVICE_FB) && (reinterpret_cast<uintptr_t>(rays) & 15u) != 0)
         return rt::fail(RT_ERR_INVALID_ARG, name + ": a device ray buffer must be 16-byte aligned");
     const auto wall0 = std::chrono::steady_clock::now();
     if (s->dev.ray_depth == 0) // raytracer.h:630-631, as rt_render
@@ -40,31 +40,20 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
 
     const uint32_t spo = G * K; // samples per output: the virtual image's SPP
     const size_t fb_floats = (size_t)n_out * 3;
-    float *d_fb = out_rgb;
-    if (!device_fb || rgb8_out) { // the float outputs are internal unless the caller keeps them in HBM
-        if (int rc = s->ensure_fb(fb_floats); rc != RT_OK)
-            return rc;
-        d_fb = s->fb.get();
-    }
+    const rt_ray *d_rays;
+    float *d_fb;
     uint8_t *d_rgb8 = nullptr;
-    if (rgb8_out) {
-        if (int rc = s->ensure_film(device_fb ? 0 : fb_floats); rc != RT_OK)
-            return rc;
-        d_rgb8 = device_fb ? rgb8_out : s->rgb8.get();
+    io.in(&d_rays, rays, (size_t)n_rays * sizeof(rt_ray));
+    if (rgb8_out) { // the float outputs behind an rgb8 destination are internal
+        io.scratch(&d_fb, fb_floats * sizeof(float));
+        io.out(&d_rgb8, rgb8_out, fb_floats);
+    } else {
+        io.out(&d_fb, out_rgb, fb_floats * sizeof(float));
     }
-    const rt_ray *d_rays = rays;
-    if (!device_fb) {
-        if (int rc = s->ensure_rays((size_t)n_rays * sizeof(rt_ray)); rc != RT_OK)
-            return rc;
-        d_rays = reinterpret_cast<const rt_ray *>(s->rays.get());
-    }
+    if (int rc = rgb8_out ? s->ensure_film() : RT_OK; rc != RT_OK)
+        return rc;
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     rt::PacketPolicy pol; // of this call: rt_render's, measured on camera rays of its image shape, is not disturbed
-    auto upload = [&]() -> int {
-        if (!device_fb) // once per call; the caller's buffer outlives the stream sync below
-            HIP_TRY(hipMemcpyAsync(s->rays.get(), rays, (size_t)n_rays * sizeof(rt_ray), hipMemcpyHostToDevice, s->stream));
-        return RT_OK;
-    };
     auto passes = [&]() -> int {
         WfLaunch W = rt::one_row_launch(s, p, n_out, spo, d_fb, counters);
         const WfRays R{reinterpret_cast<const uint4_pod *>(d_rays), G, K, p->seed};
@@ -74,14 +63,8 @@ static int render_rays_impl(rt_scene *s, const rt_params *p, const rt_ray *rays,
             HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_out, 0, 1, n_out, s->film_table.get(), s->stream));
         return RT_OK;
     };
-    if (int rc = rt::timed_call(s, counters, upload, passes); rc != RT_OK)
+    if (int rc = rt::timed_call(s, counters, &io, passes); rc != RT_OK)
         return rc;
-    if (!device_fb) {
-        if (rgb8_out)
-            HIP_TRY(hipMemcpy(rgb8_out, d_rgb8, fb_floats, hipMemcpyDeviceToHost));
-        else
-            HIP_TRY(hipMemcpy(out_rgb, d_fb, fb_floats * sizeof(float), hipMemcpyDeviceToHost));
-    }
     if (stats)
         return rt::fill_stats(s, counters, (uint64_t)n_rays * K, wall0, pol.lanes_x100, stats);
     return RT_OK;

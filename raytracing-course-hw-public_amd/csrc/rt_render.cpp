@@ -283,6 +283,17 @@ int rt::run_passes(rt_scene *s, const rt_params *p, PacketPolicy &pol, WfLaunch 
     return RT_OK;
 }
 
+void rt::traversal_stats(const DevStats &h, rt_stats *stats) {
+    stats->nodes_visited = h.nodes;
+    stats->box_tests = h.box_tests;
+    stats->tri_tests = h.tri_tests;
+    stats->light_queries = h.lq;
+    stats->light_nodes = h.lnodes;
+    stats->light_box_tests = h.lbox;
+    stats->light_tri_tests = h.ltri;
+    stats->light_hits = h.lhits;
+}
+
 // rt_stats of a call that has finished on the scene's stream (timed_call): the device counters (`counters`; else `samples` is what the call
 // knows it drew), the ev0..ev1 time, the extend launches of the event pool, the wall time since `wall0` and the packet census of the call's
 // policy (lanes served per trip x 100; 0 = the packet kernel did not run). passes / packet_passes are the caller's.
@@ -292,17 +303,10 @@ int rt::fill_stats(rt_scene *s, bool counters, uint64_t samples, std::chrono::st
     DevStats h{};
     if (counters)
         HIP_TRY(hipMemcpy(&h, s->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+    rt::traversal_stats(h, stats);
     stats->samples = counters ? h.samples : samples;
     stats->casts = h.casts;
-    stats->nodes_visited = h.nodes;
-    stats->box_tests = h.box_tests;
-    stats->tri_tests = h.tri_tests;
     stats->shaded_hits = h.shaded;
-    stats->light_queries = h.lq;
-    stats->light_nodes = h.lnodes;
-    stats->light_box_tests = h.lbox;
-    stats->light_tri_tests = h.ltri;
-    stats->light_hits = h.lhits;
     stats->texel_fetches = h.texels;
     stats->kernel_ms = kernel_ms;
     stats->packet_lanes_x100 = packet_lanes_x100;
@@ -373,27 +377,27 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
     L.tan_x = table[0].tan_x;
     L.tan_y = table[0].tan_y;
 
-    const bool device_fb = (p->flags & RT_FLAG_DEVICE_FB) != 0;
-    const size_t fb_floats = (size_t)n_pix * 3;
-    float *d_fb = fb_rgb;
-    if (!device_fb || rgb8_out) { // the float framebuffer is internal unless the caller keeps it in HBM
-        int rc = s->ensure_fb(fb_floats);
-        if (rc != RT_OK)
-            return rc;
-        d_fb = s->fb.get();
-    }
+    // Only this shard's blocks come back to a host destination; its other pixels stay untouched. The float framebuffer behind an rgb8
+    // destination is internal.
+    const size_t fb_floats = (size_t)n_pix * 3, elem = rgb8_out ? 1 : sizeof(float);
+    rt::CallIo io(s->stream, s->staging, (p->flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_fb;
     uint8_t *d_rgb8 = nullptr;
-    if (rgb8_out) {
-        int rc = s->ensure_film(device_fb ? 0 : fb_floats);
-        if (rc != RT_OK)
-            return rc;
-        d_rgb8 = device_fb ? rgb8_out : s->rgb8.get();
+    if (rgb8_out)
+        io.scratch(&d_fb, fb_floats * sizeof(float));
+    const size_t image = rgb8_out ? io.out_ranges(&d_rgb8, rgb8_out, fb_floats) : io.out_ranges(&d_fb, fb_rgb, fb_floats * sizeof(float));
+    for (uint64_t b = L.shard_index; b < n_blocks; b += L.shard_count) {
+        const uint64_t first = b * block, last = std::min<uint64_t>(first + block, n_pix);
+        io.range(image, 3 * first * elem, (last - first) * 3 * elem);
     }
+    if (int rc = rgb8_out ? s->ensure_film() : RT_OK; rc != RT_OK)
+        return rc;
+    if (int rc = io.reserve(); rc != RT_OK)
+        return rc;
     L.fb = d_fb;
     L.counter = s->d_counter;
     const bool counters = stats && (p->flags & RT_FLAG_COUNTERS);
     L.stats = counters ? s->d_stats : nullptr;
-    HIP_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(uint32_t), s->stream));
 
     const bool wavefront = p->rng_mode == RT_RNG_DEVICE && !(p->flags & RT_FLAG_MEGAKERNEL);
     if (s->wide_built && !wavefront)
@@ -468,22 +472,9 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
         HIP_TRY(rt::launch_film(d_fb, d_rgb8, n_pix, L.shard_index, L.shard_count, block, s->film_table.get(), s->stream));
     return RT_OK;
     };
-    if (int rc = rt::timed_call(s, counters, [] { return RT_OK; }, queue_render); rc != RT_OK)
+    HIP_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(uint32_t), s->stream)); // nothing returns between it and the bracket: the block is reserved
+    if (int rc = rt::timed_call(s, counters, &io, queue_render); rc != RT_OK)
         return rc;
-
-    if (!device_fb && L.n_items > 0) { // copy back only this shard's blocks; other pixels of the destination stay untouched
-        const size_t elem = rgb8_out ? 1 : sizeof(float);
-        char *dst = rgb8_out ? reinterpret_cast<char *>(rgb8_out) : reinterpret_cast<char *>(fb_rgb);
-        const char *src = rgb8_out ? reinterpret_cast<const char *>(d_rgb8) : reinterpret_cast<const char *>(d_fb);
-        if (L.shard_count == 1) {
-            HIP_TRY(hipMemcpy(dst, src, fb_floats * elem, hipMemcpyDeviceToHost));
-        } else {
-            for (uint64_t b = L.shard_index; b < n_blocks; b += L.shard_count) {
-                uint64_t first = b * block, last = std::min<uint64_t>(first + block, n_pix);
-                HIP_TRY(hipMemcpy(dst + 3 * first * elem, src + 3 * first * elem, (last - first) * 3 * elem, hipMemcpyDeviceToHost));
-            }
-        }
-    }
     if (stats) {
         if (int rc = rt::fill_stats(s, counters, local_pixels * p->samples, wall0, wavefront ? pol.lanes_x100 : 0u, stats); rc != RT_OK)
             return rc;
@@ -543,14 +534,15 @@ extern "C" int rt_film_rgb8(rt_scene *s, const float *rgb, size_t n_pixels, uint
     if (n_pixels == 0)
         return RT_OK;
     HIP_TRY(hipSetDevice(s->device));
-    int rc = s->ensure_fb(n_pixels * 3);
-    if (rc == RT_OK)
-        rc = s->ensure_film(n_pixels * 3);
-    if (rc != RT_OK)
+    if (int rc = s->ensure_film(); rc != RT_OK)
         return rc;
-    HIP_TRY(hipMemcpyAsync(s->fb.get(), rgb, n_pixels * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(rt::launch_film(s->fb.get(), s->rgb8.get(), (uint32_t)n_pixels, 0, 1, (uint32_t)n_pixels, s->film_table.get(), s->stream));
-    HIP_TRY(hipMemcpyAsync(out_rgb8, s->rgb8.get(), n_pixels * 3, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
+    rt::CallIo io(s->stream, s->staging, false);
+    const float *d_rgb;
+    uint8_t *d_rgb8;
+    io.in(&d_rgb, rgb, n_pixels * 3 * sizeof(float));
+    io.out(&d_rgb8, out_rgb8, n_pixels * 3);
+    return io.run([&]() -> int {
+        HIP_TRY(rt::launch_film(d_rgb, d_rgb8, (uint32_t)n_pixels, 0, 1, (uint32_t)n_pixels, s->film_table.get(), s->stream));
+        return RT_OK;
+    });
 }

@@ -1,7 +1,8 @@
 // rt_scene_impl.h — what the host files behind include/rt_abi.h share (internal): the definition of rt_scene and the few helpers
 // with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_rays.cpp (rt_render_rays*), rt_bake.cpp (rt_bake*, rt_lightmap_points),
 // rt_accum_host.cpp (rt_accum_*) and rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through
-// rt_group.h.
+// rt_group.h. The arrays of a call, on the host or in the caller's HBM, are declared on an rt::CallIo (rt_call_io.h) over the scene's one
+// staging block; its run() and timed_call below are the brackets every entry point queues its work in.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -13,6 +14,7 @@
 #include "../../include/rt_abi.h"
 #include "bvh_build.h"
 #include "rt_bvh_device.h"
+#include "rt_call_io.h"
 #include "rt_dev_mem.h"
 #include "rt_device_types.h"
 #include "rt_error.h"
@@ -111,19 +113,13 @@ struct rt_scene {
     uint32_t *d_counter = nullptr; // both of `owned`
     DevStats *d_stats = nullptr;
     // Buffers grown on demand (rt::DevBuf: the content does not survive growth, a failed growth leaves them empty):
-    rt::DevBuf<float> fb;             // framebuffer staging, in floats
-    rt::DevBuf<uint8_t> rgb8;         // device film output (rt_render_rgb8 with a host destination, rt_film_rgb8)
+    rt::DevBuf<uint8_t> staging;      // what a call stages of its arrays: host inputs, host or internal outputs (rt_call_io.h), in bytes
     rt::DevBuf<rt::FilmTable> film_table; // the verified threshold table (host/film.cpp), uploaded by the first ensure_film
     rt::DevBuf<WfSensor> sensors;     // the camera table of a render's wavefront passes (WfLaunch::sensors: one record per view or sensor) / the one
                                       // record of rt_sensor_rays
-    rt::DevBuf<uint8_t> rays;         // the device copy of a host ray buffer (rt_render_rays), in bytes
 
-    int ensure_fb(size_t fb_floats) {
-        HIP_TRY(fb.reserve(fb_floats));
-        return RT_OK;
-    }
-    // device film prerequisites: the threshold table and, optionally, an rgb8 staging buffer
-    int ensure_film(size_t rgb8_bytes) {
+    // device film prerequisite: the threshold table
+    int ensure_film() {
         if (!film_table.get()) {
             rt::FilmTable t{};
             if (!rt::film_table(t.thr, t.special))
@@ -132,15 +128,10 @@ struct rt_scene {
             HIP_TRY(hipMemcpyAsync(film_table.get(), &t, sizeof(t), hipMemcpyHostToDevice, stream));
             HIP_TRY(hipStreamSynchronize(stream)); // `t` is a local
         }
-        HIP_TRY(rgb8.reserve(rgb8_bytes));
         return RT_OK;
     }
     int ensure_sensors(uint32_t n) {
         HIP_TRY(sensors.reserve(n));
-        return RT_OK;
-    }
-    int ensure_rays(size_t bytes) {
-        HIP_TRY(rays.reserve(bytes));
         return RT_OK;
     }
     int num_cus = 0;
@@ -264,7 +255,7 @@ struct rt_scene {
         // point returns with the stream synchronised. In a group's handle all of them are empty.
         for (rt::DevArena *a : {&wf_owned, &owned, &geo_owned, &light_owned, &env_owned})
             a->reset();
-        wf_feat.reset(), wf_ids.reset(), wf_rel.reset(), fb.reset(), rgb8.reset(), rays.reset(), sensors.reset(), film_table.reset();
+        wf_feat.reset(), wf_ids.reset(), wf_rel.reset(), staging.reset(), sensors.reset(), film_table.reset();
         ext_events.destroy();
         if (ev0)
             (void)hipEventDestroy(ev0);
@@ -301,34 +292,27 @@ int render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor> &t
 int check_sensor(const rt_sensor &sn, uint32_t width, uint32_t height, const char *fn);
 WfSensor make_sensor(const rt_sensor &sn, uint32_t width, uint32_t height);
 WfSensor make_sensor(const rt_camera &cam, uint64_t seed, uint32_t width, uint32_t height);
+void traversal_stats(const DevStats &h, rt_stats *stats); // the counters of the walks, scene and light tree, as rt_stats names them
 int fill_stats(rt_scene *s, bool counters, uint64_t samples, std::chrono::steady_clock::time_point wall0, uint32_t packet_lanes_x100, rt_stats *stats);
 
-// Everything `queue` puts on the scene's stream has finished when this returns: a failure in between must not return while kernels are
-// still in flight (a later ensure_wavefront / rt_destroy would free memory under them)
-template <class Queue> int queue_and_wait(rt_scene *s, Queue queue) {
-    if (int rc = queue(); rc != RT_OK) {
-        (void)hipStreamSynchronize(s->stream);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RT_OK;
-}
-
-// The bracket of a call that runs wavefront passes and reports rt_stats: the device counters start from zero (`counters`), `stage` queues what
-// the passes read but the kernel time does not count (an upload of staged input), then ev0, `body` (the passes and what belongs to their
-// time), ev1, and the wait. fill_stats reads the events and the counters afterwards.
-template <class Stage, class Body> int timed_call(rt_scene *s, bool counters, Stage stage, Body body) {
+// The bracket of a call that runs wavefront passes and reports rt_stats (queue_and_wait, rt_call_io.h): the device counters start from zero
+// (`counters`), the staged inputs of `io` (null: the call stages nothing) go up, then ev0, `body` (the passes and what belongs to their
+// time), ev1, the copies back to the host, and the wait: the kernel time counts neither copy. fill_stats reads the events and the counters
+// afterwards.
+template <class Body> int timed_call(rt_scene *s, bool counters, CallIo *io, Body body) {
     s->ext_events.reset();
-    return queue_and_wait(s, [&]() -> int {
+    if (int rc = io ? io->reserve() : RT_OK; rc != RT_OK) // (nothing to do where the caller needed its pointers earlier)
+        return rc;
+    return queue_and_wait(s->stream, [&]() -> int {
         if (counters)
             HIP_TRY(hipMemsetAsync(s->d_stats, 0, sizeof(DevStats), s->stream));
-        if (int rc = stage(); rc != RT_OK)
+        if (int rc = io ? io->upload() : RT_OK; rc != RT_OK)
             return rc;
         HIP_TRY(hipEventRecord(s->ev0, s->stream));
         if (int rc = body(); rc != RT_OK)
             return rc;
         HIP_TRY(hipEventRecord(s->ev1, s->stream));
-        return RT_OK;
+        return io ? io->download() : RT_OK;
     });
 }
 } // namespace rt

@@ -126,18 +126,12 @@ extern "C" int rt_sensor_rays(rt_scene *s, const rt_sensor *sensor, uint32_t wid
     const WfSensor rec = rt::make_sensor(*sensor, width, height);
     if (int rc = s->ensure_sensors(1); rc != RT_OK)
         return rc;
-    void *d_out = rays_out;
-    if (!device_out) {
-        if (int rc = s->ensure_rays((size_t)n * sizeof(rt_ray)); rc != RT_OK)
-            return rc;
-        d_out = s->rays.get();
-    }
-    auto queue = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(s->sensors.get(), &rec, sizeof(rec), hipMemcpyHostToDevice, s->stream)); // `rec` outlives the stream sync below
+    rt::CallIo io(s->stream, s->staging, device_out);
+    rt_ray *d_out;
+    io.out(&d_out, rays_out, (size_t)n * sizeof(rt_ray));
+    return io.run([&]() -> int {
+        HIP_TRY(hipMemcpyAsync(s->sensors.get(), &rec, sizeof(rec), hipMemcpyHostToDevice, s->stream)); // `rec` outlives the bracket's wait
         HIP_TRY(rt::launch_sensor_rays(s->sensors.get(), width, height, first_pixel, first_sample, samples, (uint32_t)n, d_out, s->num_cus, s->stream));
-        if (!device_out)
-            HIP_TRY(hipMemcpyAsync(rays_out, d_out, (size_t)n * sizeof(rt_ray), hipMemcpyDeviceToHost, s->stream));
         return RT_OK;
-    };
-    return rt::queue_and_wait(s, queue);
+    });
 }

@@ -41,3 +41,25 @@ def test_only_the_header_allocates_device_memory():
                 if re.search(r"\bhip(Malloc|Free)\(", text):
                     offenders.append(n)
     assert offenders == []
+
+
+def test_no_entry_point_stages_its_arrays_by_hand():
+    """Host or device arrays are one decision, made by rt::CallIo (rt_call_io.h): no entry point picks a pointer or a copy kind by the
+    RT_FLAG_DEVICE_FB flag itself, and the per-purpose staging buffers it replaced stay gone. rt_group.cpp keeps its own handling of the
+    flag (the RCCL gather)."""
+    allowed = {  # file -> the one line that may stay, and why
+        "rt_accum_host.cpp": "device_table ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice",  # rt_accum_attach_ids: one upload into the accumulator's own arena
+    }
+    gone = re.compile(r"\bensure_fb\b|\bensure_rays\b|s->rgb8\b|s->fb\b")
+    pick = re.compile(r"\?\s*hipMemcpy\w+\s*:\s*hipMemcpy\w+|\bdevice_(fb|out)\s*\?")
+    offenders = []
+    for dirpath, _, names in os.walk(CSRC):
+        for n in names:
+            if not n.endswith((".cpp", ".hip", ".h")):
+                continue
+            for no, line in enumerate(open(os.path.join(dirpath, n), encoding="utf-8", errors="replace"), 1):
+                if gone.search(line):
+                    offenders.append((n, no, "a staging buffer of its own"))
+                if n not in ("rt_call_io.h", "rt_group.cpp") and pick.search(line.replace(allowed.get(n, "\0"), "")):
+                    offenders.append((n, no, "picks by the flag"))
+    assert offenders == []
