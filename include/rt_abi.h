@@ -182,9 +182,13 @@ typedef struct rt_scene_desc {
  *   RT_BUILD_GROUP_COPY (tests; multi-GPU scenes): replace the RCCL exchange by peer copies, which lets a one-GPU box rehearse G > 1
  *       with repeated ordinals (RCCL refuses those). RT_BUILD_GROUP_SELF_EXCHANGE (tests): the first GPU's own blocks also travel
  *       through ncclSend / ncclRecv, which exercises the RCCL path with G = 1.
+ *   RT_BUILD_TEX_TILED (tests, A/B runs): the textures one material samples together are stored as interleaved 16-byte records in
+ *       4 x 2 tiles only. By default such a set stores one 64-byte footprint record per base texel (the four records of a bilinear
+ *       lookup in one line, 4 x the memory) while the scene's footprint records stay below 2 GiB, and falls back to the tiled
+ *       records beyond. Every sampled value is the same in both layouts, bit for bit.
  * rt_create refuses any other bit (8 was a development flag). */
 enum { RT_BUILD_REFERENCE = 0, RT_BUILD_DEVICE_LBVH = 1, RT_BUILD_WIDE = 2, RT_BUILD_WIDE_HOST_COLLAPSE = 4, RT_BUILD_GROUP_COPY = 16,
-       RT_BUILD_GROUP_SELF_EXCHANGE = 32 };
+       RT_BUILD_GROUP_SELF_EXCHANGE = 32, RT_BUILD_TEX_TILED = 128 };
 #define RT_MAX_PRIMITIVES 4096u
 
 /* Progress report of a render: called on the calling thread after every finished pass (pixel tile x sample range) of a single-GPU

@@ -37,6 +37,7 @@ from ._ctypes_abi import (
     RT_BUILD_WIDE_HOST_COLLAPSE,
     RT_BUILD_GROUP_COPY,
     RT_BUILD_GROUP_SELF_EXCHANGE,
+    RT_BUILD_TEX_TILED,
     RT_BUILDER_PLOC,
     RT_BUILDER_LBVH,
     RT_SORT_AUTO,

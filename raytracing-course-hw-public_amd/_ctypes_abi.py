@@ -18,6 +18,7 @@ RT_BUILD_WIDE = 2
 RT_BUILD_WIDE_HOST_COLLAPSE = 4
 RT_BUILD_GROUP_COPY = 16
 RT_BUILD_GROUP_SELF_EXCHANGE = 32
+RT_BUILD_TEX_TILED = 128
 RT_BUILDER_PLOC, RT_BUILDER_LBVH = 0, 1
 RT_SORT_AUTO, RT_SORT_OFF, RT_SORT_OCTANT_CELL_CONE = 0, 1, 6
 RT_PACKET_AUTO, RT_PACKET_OFF, RT_PACKET_ON = range(3)

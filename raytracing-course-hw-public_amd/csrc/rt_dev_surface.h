@@ -112,7 +112,17 @@ DEV TexSet tex_sample_set(const DevScene &S, int32_t view, uint32_t info, float 
     const DevTexture T = load_texture(S, view);
     const uint32_t base = T.offset - ((info >> 4) & 3u); // dword 0 of record (0, 0)
     const TexFoot F(T, u, v);
-    const Tex4<uint4> q = F.fetch([&](int x, int y) { return *reinterpret_cast<const uint4 *>(S.texels + base + tex_tiled(T, x, y) * 4u); });
+    // Where the four 16-byte records are (pool dwords); both layouts then run the same four loads, so the branch holds address arithmetic only.
+    Tex4<uint32_t> a;
+    if (T.stride == RT_TEX_FOOT_STRIDE && F.x0 < F.w && F.y0 < F.h) {
+        // a footprint set (rt_tex_views.h): the record of base texel (x0, y0) IS {q00, q01, q10, q11}: one tiled index, four pieces of one line
+        const uint32_t rec = base + tex_tiled(T, F.x0, F.y0) * RT_TEX_FOOT_STRIDE;
+        a = {rec, rec + 4u, rec + 8u, rec + 12u};
+    } else { // an interleaved set; or a footprint set's out-of-range base (TexFoot::fetch), through q00 of the records it names
+        a = F.fetch([&](int x, int y) { return base + tex_tiled(T, x, y) * T.stride; });
+    }
+    auto piece = [&](uint32_t dw) { return *reinterpret_cast<const uint4 *>(S.texels + dw); };
+    const Tex4<uint4> q = {piece(a.q00), piece(a.q01), piece(a.q10), piece(a.q11)};
     auto blend = [&](uint32_t a00, uint32_t a01, uint32_t a10, uint32_t a11, bool gamma) {
         st.texels(4);
         return tex_blend(F, a00, a01, a10, a11, gamma, s_lin, s_gam);

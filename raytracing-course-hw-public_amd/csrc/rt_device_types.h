@@ -73,7 +73,8 @@ struct alignas(16) DevMaterial {
     float ior;
     int32_t color_tex, emissive_tex, mr_tex, normal_tex; // -1 = WHITE_TEXTURE / NORMAL_UP
     int32_t tex_set;       // >= 0: EVERY texture this material samples is a member of ONE interleaved view set (rt_scene.cpp): the view of
-                           //       one of its members (tex_sample_set: addresses once, a 16-byte load per record). -1: sample slot by slot
+                           //       one of its members (tex_sample_set: addresses once, a 16-byte load per record; ONE address and one line when
+                           //       that view is a footprint set, DevTexture::stride). -1: sample slot by slot
     uint32_t tex_set_info; // bits 0..3: slots present (1 colour, 2 emissive, 4 metallic-roughness, 8 normal); bits 4..5: record dword of view `tex_set`
 };
 static_assert(sizeof(DevMaterial) == 64, "DevMaterial must be 64 bytes");
@@ -81,13 +82,16 @@ static_assert(sizeof(DevMaterial) == 64, "DevMaterial must be 64 bytes");
 // A texture VIEW: what a material slot samples. Texels are stored in tiles of 2^tw_log x 2^th_log records so that a
 // bilinear 2x2 footprint usually lies in one 128-B line, and the textures one material samples at the same (u, v)
 // (colour, normal, metallic-roughness, emissive of equal size) are interleaved record by record (stride 4 dwords: one
-// line serves all of a hit's lookups). rt_create builds the views (rt_scene.cpp build_texture_views); the values
-// Texture::sample returns are unchanged, only the addresses differ.
+// line serves all of a hit's lookups). A FOOTPRINT set (stride RT_TEX_FOOT_STRIDE) stores per base texel (x0, y0) the four set records of
+// its bilinear lookup, {q00, q01, q10, q11} = 64 B in one line: one address and one line per lookup instead of 1.875 lines on average;
+// q00 of record (x, y) is the set record of (x, y) itself. rt_create builds the views (rt_tex_views.h build_texture_views, the one place
+// that decides the layout); the values Texture::sample returns are unchanged, only the addresses differ.
+#define RT_TEX_FOOT_STRIDE 16u
 struct alignas(16) DevTexture {
     uint32_t width, height;
     uint32_t offset; // pool dword of this view's texel (0,0)
     uint32_t count;  // width*height (== 1 -> Texture::sample's 1x1 fast path, geometry.h:548-550)
-    uint32_t stride; // dwords between consecutive records: 1 (stand-alone) or 4 (interleaved set)
+    uint32_t stride; // dwords between consecutive records: 1 (stand-alone), 4 (interleaved set) or RT_TEX_FOOT_STRIDE (footprint set)
     uint32_t tiles_x; // tiles per row of tiles (width padded up to the tile width)
     uint32_t tw_log, th_log;
 };
@@ -217,9 +221,13 @@ struct alignas(16) WfHit { // 16 B: closest hit of the ray in the same queue slo
 struct alignas(16) RtF4 {
     float x, y, z, w;
 };
-struct alignas(16) WfFold { // 32 B: one pending shade() frame, `emission + inner * scale` (raytracer.h:588-590)
-    float e[3], pad0;
-    float s[3], pad1;
+// One pending shade() frame, `emission + inner * scale` (raytracer.h:588-590), is TWO 16-byte records in two arrays (WfLaunch::fold): the scale
+// record {s, flag}, always written, and the emission record {e, -}, written only when one of the three emission words has a non-zero bit
+// pattern (flag = 1: -0.0, denormals, inf and NaN are stored; only an exact +0 triple is implied by flag = 0). Most hits are on materials
+// that emit nothing: their frames cost wf_shade one scattered 16-byte store instead of a 32-byte one, and wf_fold one stream instead of two.
+struct alignas(16) WfFold {
+    float v[3];    // scale, or emission
+    uint32_t flag; // scale record: 1 = this frame has an emission record; emission record: unused
 };
 enum {
     WF_CNT_IN = 0, WF_CNT_TICKET = 2, WF_CNT_SLOTS = 3,
@@ -284,7 +292,8 @@ struct WfLaunch {
                              // waves take contiguous positions, so a line of hits is filled by one wave within one chunk and
                              // leaves L2 as a full line (stored at the ray's own slot, sorted rays scattered 16-B stores over
                              // the whole array: 9x HBM write amplification, profiles/r02_write_amp.txt)
-    WfFold *fold;            // [ray_depth][n_paths]: pending shade() frames, level by level: wf_fold (one lane per path) reads each level coalesced
+    WfFold *fold;            // [2][ray_depth][n_paths]: pending shade() frames, the scale records level by level, then the emission records
+                             // alike: wf_fold (one lane per path) reads each level coalesced, the emission level only where flagged
     RtF4 *sample_out;        // [n_paths]: sanitised radiance of each finished sample
     RtF4 *accum;             // [pass_pixels]: running per-pixel sum across sample passes (reference order)
     float *fb;               // width*height*3

@@ -54,7 +54,7 @@ uint64_t rt::wavefront_max_paths(rt_scene *s, const rt_params *p) {
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t per_path = 2 * sizeof(WfPath) + sizeof(WfHit) + s->dev.ray_depth * sizeof(WfFold) + sizeof(RtF4) + 16 /* sort keys + slots */;
+            const uint64_t per_path = 2 * sizeof(WfPath) + sizeof(WfHit) + s->dev.ray_depth * 2 * sizeof(WfFold) /* scale + emission records */ + sizeof(RtF4) + 16 /* sort keys + slots */;
             const uint64_t have = free_b + s->wf_paths_cap * per_path; // what is already ours can be reused
             const uint64_t fit = (uint64_t)(0.6 * (double)have) / per_path;
             max_paths = std::max<uint64_t>(1u << 16, std::min(max_paths, fit));

@@ -180,7 +180,7 @@ struct rt_scene {
         // + 64: wf_shade's sub-queue regions cover whole wave slots (rt_device_types.h, WF_STRIPES)
         if ((rc = alloc((paths + 64) * sizeof(WfPath), (void **)&wf_paths[0])) != RT_OK || (rc = alloc((paths + 64) * sizeof(WfPath), (void **)&wf_paths[1])) != RT_OK ||
             (rc = alloc(WF_STRIPE_BUF_WORDS * sizeof(uint32_t), (void **)&wf_stripes)) != RT_OK ||
-            (rc = alloc(paths * sizeof(WfHit), (void **)&wf_hits)) != RT_OK || (rc = alloc(paths * depth * sizeof(WfFold), (void **)&wf_fold)) != RT_OK ||
+            (rc = alloc(paths * sizeof(WfHit), (void **)&wf_hits)) != RT_OK || (rc = alloc(paths * depth * 2 * sizeof(WfFold), (void **)&wf_fold)) != RT_OK ||
             (rc = alloc(paths * sizeof(RtF4), (void **)&wf_samples)) != RT_OK || (rc = alloc(pixels * sizeof(RtF4), (void **)&wf_accum)) != RT_OK ||
             (rc = alloc(WF_CNT_ALLOC_WORDS * sizeof(uint32_t), (void **)&wf_counters)) != RT_OK)
             return rc;

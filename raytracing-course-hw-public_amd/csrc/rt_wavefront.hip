@@ -442,9 +442,9 @@ template <bool STATS, bool LIGHTS_LDS, int ENV> __global__ __launch_bounds__(256
         WfPacked next;
         uint32_t next_key = 0u; // the ray-order key of `next`, made only when the next bounce may be sorted (WfLaunch::emit_keys)
         if (active) {
+            const Hit h = wf_load_hit(L.hits + jq); // first: the attributes and texel addresses hang on the hit alone, and loads return in order
             const WfHead in = wf_load_head(L.paths_in + j); // its class bits chose this lane (below); nothing here reads them
             Rng<RT_RNG_DEVICE> rng = wf_load_rng(L.paths_in + j);
-            const Hit h = wf_load_hit(L.hits + jq);
             const uint32_t path = in.id;
             uint32_t depth_left = in.depth_left, nb = in.nb;
             if (h.k != RT_NONE)
@@ -453,7 +453,7 @@ template <bool STATS, bool LIGHTS_LDS, int ENV> __global__ __launch_bounds__(256
             bool terminal = sr.terminal;
             V3 term = sr.term;
             if (sr.push) // emission + trace_ray(...) * scl (raytracer.h:588-590), folded when the path ends
-                wf_store_fold(wf_fold_at(L.fold, L.n_paths, nb++, path), sr.emission, sr.scl);
+                wf_store_fold(L, nb++, path, sr.emission, sr.scl);
             if (!terminal && depth_left == 0) { // trace_ray(..., 0) returns (0,0,0) without casting (:596-598)
                 terminal = true;
                 term = mk(0, 0, 0);

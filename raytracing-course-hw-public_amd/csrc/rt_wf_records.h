@@ -10,7 +10,7 @@ static_assert(offsetof(WfPath, o) == 0 && offsetof(WfPath, dx) == 12 && offsetof
                   offsetof(WfPath, r) == 32 && offsetof(WfPath, fast) == 44 && offsetof(WfPath, s) == 48,
               "WfPath: piece 0 = {o, d.x}, piece 1 = {d.y, d.z, path word, depth word}, piece 2 = {1/d, fast}, piece 3 = RNG state");
 static_assert(sizeof(WfHit) == 16 && offsetof(WfHit, k) == 0 && offsetof(WfHit, b) == 4 && offsetof(WfHit, c) == 8 && offsetof(WfHit, t) == 12, "WfHit: one piece {k, b, c, t}");
-static_assert(sizeof(WfFold) == 32 && offsetof(WfFold, e) == 0 && offsetof(WfFold, s) == 16, "WfFold: piece 0 = emission, piece 1 = scale");
+static_assert(sizeof(WfFold) == 16 && offsetof(WfFold, v) == 0 && offsetof(WfFold, flag) == 12, "WfFold: one piece {scale, flag} or {emission, -}");
 static_assert(sizeof(rt_xoshiro) == 16 && WF_ORDER_CLASS_SHIFT == 30 && WF_ORDER_SLOT_MASK == (1u << WF_ORDER_CLASS_SHIFT) - 1u, "path / order word: slot below, class above");
 
 // ---- WfLaunch::order entries and the path word: queue slot (or path id) in the low 30 bits, sampler class above
@@ -78,15 +78,23 @@ DEV Hit wf_load_hit(const WfHit *p) {
     return Hit{__float_as_uint(q.x), q.y, q.z, q.w};
 }
 
-// ---- WfFold: frame level nb of a path, `emission + inner * scale`; levels are stored one after the other (WfLaunch::fold)
-DEV WfFold *wf_fold_at(WfFold *fold, uint32_t n_paths, uint32_t nb, uint32_t path) { return fold + ((size_t)nb * n_paths + path); }
-DEV void wf_store_fold(WfFold *p, V3 emission, V3 scale) {
-    float4 *q = reinterpret_cast<float4 *>(p);
-    q[0] = make_float4(emission.x, emission.y, emission.z, 0.f);
-    q[1] = make_float4(scale.x, scale.y, scale.z, 0.f);
+// ---- WfFold: frame level nb of a path, `emission + inner * scale`: a scale record, and an emission record only where the emission is not
+// exactly +0 (rt_device_types.h). Both arrays store their levels one after the other; the emission array follows the scale array.
+DEV size_t wf_fold_index(uint32_t n_paths, uint32_t nb, uint32_t path) { return (size_t)nb * n_paths + path; }
+DEV WfFold *wf_fold_scale_at(const WfLaunch &L, uint32_t nb, uint32_t path) { return L.fold + wf_fold_index(L.n_paths, nb, path); }
+DEV WfFold *wf_fold_emission_at(const WfLaunch &L, uint32_t nb, uint32_t path) { return L.fold + wf_fold_index(L.n_paths, L.ray_depth + nb, path); }
+DEV void wf_store_fold(const WfLaunch &L, uint32_t nb, uint32_t path, V3 emission, V3 scale) {
+    const uint32_t lit = ((__float_as_uint(emission.x) | __float_as_uint(emission.y) | __float_as_uint(emission.z)) != 0u) ? 1u : 0u; // bits, not values
+    *reinterpret_cast<float4 *>(wf_fold_scale_at(L, nb, path)) = make_float4(scale.x, scale.y, scale.z, __uint_as_float(lit));
+    if (lit)
+        *reinterpret_cast<float4 *>(wf_fold_emission_at(L, nb, path)) = make_float4(emission.x, emission.y, emission.z, 0.f);
 }
-DEV void wf_load_fold(const WfFold *p, V3 &emission, V3 &scale) {
-    const float4 *q = reinterpret_cast<const float4 *>(p);
-    const float4 fe = q[0], fs = q[1];
-    emission = mk(fe.x, fe.y, fe.z), scale = mk(fs.x, fs.y, fs.z);
+DEV void wf_load_fold(const WfLaunch &L, uint32_t nb, uint32_t path, V3 &emission, V3 &scale) {
+    const float4 fs = *reinterpret_cast<const float4 *>(wf_fold_scale_at(L, nb, path));
+    scale = mk(fs.x, fs.y, fs.z);
+    emission = mk(0.f, 0.f, 0.f); // what an unflagged frame's emission was, bit for bit
+    if (__float_as_uint(fs.w) != 0u) {
+        const float4 fe = *reinterpret_cast<const float4 *>(wf_fold_emission_at(L, nb, path));
+        emission = mk(fe.x, fe.y, fe.z);
+    }
 }

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void wf_sensor_rays(const WfSensor *sensor, ui
 // ------------------------------------------------------------------------------------------------ fold
 // The return path of the recursion (raytracer.h:588-590): every finished path's pending frames `emission + inner * scl`, innermost
 // first, then sanitize_nans (:607-616). One lane per path of the pass, all lanes busy; frames are stored level by level (WfLaunch::fold), so a
-// wave reads 2 KB of consecutive records per level and nothing it does not need.
+// wave reads 1 KB of consecutive scale records per level, the emission records only of the frames that have one, and nothing it does not need.
 __global__ __launch_bounds__(256) void wf_fold(const WfLaunch L) {
     for (uint32_t path = blockIdx.x * blockDim.x + threadIdx.x; path < L.n_paths; path += gridDim.x * blockDim.x) {
         const RtF4 v = L.sample_out[path];
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void wf_fold(const WfLaunch L) {
         while (nb > 0) {
             --nb;
             V3 emission, scl;
-            wf_load_fold(wf_fold_at(L.fold, L.n_paths, nb, path), emission, scl); // frame level nb: adjacent lanes, adjacent records
+            wf_load_fold(L, nb, path, emission, scl); // frame level nb: adjacent lanes, adjacent records; the emission record only where flagged
             const V3 clr = res * scl;
             res = emission + clr;
         }
