@@ -9,9 +9,9 @@ import numpy as np
 import pytest
 
 import hit_contract
-from bvh_dump import LEAF, MASK, flatten_reference
+from bvh_dump import check_invariants, compare_hits_with_oracle, flatten_reference
 from conftest import random_rays
-from hit_contract import explain_pixels, summary, verify_hits
+from hit_contract import explain_pixels
 
 pytestmark = pytest.mark.gpu
 
@@ -37,67 +37,6 @@ def test_device_memory_holds_the_reference_topology(gpu, scenes, name):
         dev.close()
 
 
-def _check_invariants(dump, positions, max_leaf=4):
-    nodes, tris, root = dump["nodes"], dump["tris"], dump["root"]
-    n = tris.shape[0]
-    assert sorted(tris[:, 9].tolist()) == list(range(n)), "leaf order is not a permutation of the triangles"
-    verts = positions[tris[:, 9]].astype(np.float32)  # original vertices, in leaf order
-    tlo, thi = verts.min(axis=1), verts.max(axis=1)
-    covered = np.zeros(n, dtype=np.int32)
-    f32 = lambda w: w.view(np.float32)  # noqa: E731
-    # iterative post-order: box of every subtree from the triangles, compared with the box stored in the parent
-    stack = [(root, 0, None)]  # (ref, depth, where the parent stores this child's box)
-    boxes = {}
-    order = []
-    max_depth = 0
-    while stack:
-        ref, depth, _ = stack.pop()
-        max_depth = max(max_depth, depth)
-        order.append(ref)
-        if ref & LEAF:
-            continue
-        stack.append((int(nodes[ref, 12]), depth + 1, None))
-        stack.append((int(nodes[ref, 13]), depth + 1, None))
-    visited_inner = [r for r in order if not (r & LEAF)]
-    assert len(set(visited_inner)) == len(visited_inner) == nodes.shape[0], "inner nodes are not a tree over all records"
-    for ref in reversed(order):
-        if ref & LEAF:
-            b, cnt = ref & MASK, (ref >> 27) & 15
-            assert 1 <= cnt <= max_leaf
-            covered[b : b + cnt] += 1
-            assert tris[b, 10] & 2 and tris[b + cnt - 1, 10] & 1
-            boxes[ref] = (tlo[b : b + cnt].min(axis=0), thi[b : b + cnt].max(axis=0))
-        else:
-            l, r = int(nodes[ref, 12]), int(nodes[ref, 13])
-            (llo, lhi), (rlo, rhi) = boxes[l], boxes[r]
-            assert np.array_equal(f32(nodes[ref, 0:3]), llo) and np.array_equal(f32(nodes[ref, 3:6]), lhi), ref
-            assert np.array_equal(f32(nodes[ref, 6:9]), rlo) and np.array_equal(f32(nodes[ref, 9:12]), rhi), ref
-            boxes[ref] = (np.minimum(llo, rlo), np.maximum(lhi, rhi))
-            del boxes[l], boxes[r]
-    assert (covered == 1).all(), "a triangle is in no leaf or in two"
-    assert max_depth <= 62
-    return max_depth
-
-
-def _compare_hits_with_oracle(orc, dev, rays, max_tie_share, brute="all"):
-    """Closest hits of a device-built tree against the oracle's: t bit-equal on every ray, same hit / miss; where the index agrees
-    the barycentrics are bit-equal too; where it differs the two triangles tie exactly in t (asserted by the first check), and the returned
-    triangle's own test gives the returned (b, c, t) bit for bit (hit_contract.verify_hits, kind "exact")."""
-    op, ob = orc.cast_rays(rays)
-    gp, gb = dev.cast_rays(rays)
-    assert np.array_equal(op == 0xFFFFFFFF, gp == 0xFFFFFFFF)
-    bad = ob[:, 2].view(np.uint32) != gb[:, 2].view(np.uint32)
-    assert not bad.any(), f"closest-hit distance differs from the oracle on {int(bad.sum())} of {len(rays)} rays"
-    same = op == gp
-    assert np.array_equal(gb[same].view(np.uint32), ob[same].view(np.uint32))
-    share = float(1 - same.mean())
-    assert share <= max_tie_share, f"{int((~same).sum())} index mismatches (exact ties) of {len(rays)} rays: more than {max_tie_share:.1e}"
-    c = verify_hits(orc, rays, op, ob, gp, gb, "exact", brute=brute)
-    print(f"\ndevice-built tree: {summary(c)}")
-    assert c["ties"] == int((~same).sum())
-    return share
-
-
 @pytest.mark.parametrize("case", ["room_5000", "boxes", "tiny_1", "tiny_2", "tiny_5", "tiny_9", "room_1M", "room_5000/lbvh", "boxes/lbvh", "tiny_9/lbvh", "room_1M/lbvh"])
 def test_device_lbvh_invariants_and_closest_hits(gpu, oracle, sg, case, monkeypatch):
     """Both binary builders of rt_bvh_device.hip: PLOC (default; agglomerative clustering along the Morton order) and the Karras
@@ -121,14 +60,14 @@ def test_device_lbvh_invariants_and_closest_hits(gpu, oracle, sg, case, monkeypa
     dev = gpu.DeviceScene(sc, device_bvh=True, **opts)
     try:
         dump = dev.bvh_device_dump(0)
-        depth = _check_invariants(dump, sc.positions)
+        depth = check_invariants(dump, sc.positions, max_leaf=4)
         info = dev.bvh_info(0)  # reference-style description rebuilt from HBM
         leaves = info["nodes"][info["nodes"][:, 6] == 0xFFFFFFFF]
         assert (leaves[:, 9] - leaves[:, 8]).sum() == sc.n_triangles and sorted(info["order"].tolist()) == list(range(sc.n_triangles))
         n_rays = 100_000 if sc.n_triangles >= 5000 else 20_000
         rays = random_rays(sc, n_rays, seed=12)
         # random triangle soups do not tie; the boxes scene does along the shared diagonal of a face's two triangles
-        ties = _compare_hits_with_oracle(orc, dev, rays, max_tie_share=2e-3 if case == "boxes" else 5e-5, brute="all" if sc.n_triangles <= 50_000 else 256)
+        ties = compare_hits_with_oracle(orc, dev, rays, max_tie_share=2e-3 if case == "boxes" else 5e-5, brute="all" if sc.n_triangles <= 50_000 else 256)
         # the render loop runs unchanged on the device-built tree: both schedules agree, and the image is the ORACLE's wherever
         # no path met an exact tie
         W, H, SPP = (96, 64, 4) if sc.n_triangles >= 5000 else (48, 32, 4)
@@ -176,7 +115,7 @@ def test_ploc_terminates_on_collapsed_geometry(gpu, oracle, sg):
             dev = gpu.DeviceScene(sc, **kw)  # raised RT_ERR_HIP before the fix
             try:
                 if not kw.get("wide"):
-                    depth = _check_invariants(dev.bvh_device_dump(0), sc.positions)
+                    depth = check_invariants(dev.bvh_device_dump(0), sc.positions, max_leaf=4)
                     assert depth <= 62
                 gp, gb, _ = dev.cast_rays_ex(rays, gpu.RT_CAST_EXTEND)
                 if kw.get("wide"):  # the superset contract: nothing lost, nothing farther
