@@ -50,8 +50,8 @@ extern "C" {
                                 rt_adaptive were, and after rt_accum_create_ex, the feature reads and rt_accum_denoise / rt_denoise were, and
                                 after rt_update_geometry and rt_ray / rt_render_rays / rt_render_rays_rgb8 were, and after
                                 rt_update_geometry_device and rt_refit_times were, and after rt_set_environment / rt_env_pdf / rt_env_sample were,
-                                and after rt_bake / rt_bake_rays / rt_lightmap_points were, and after rt_accum_attach_ids and the id reads were:
-                                new entry points only, no existing layout changes */
+                                and after rt_bake / rt_bake_rays / rt_lightmap_points were, and after rt_accum_attach_ids and the id reads were,
+                                and after rt_accum_attach_light_groups and the light-group reads were: new entry points only, no existing layout changes */
 #define RT_TEX_NONE (-1)
 #define RT_ALL_DEVICES (-1) /* rt_create: one scene replica on every visible GPU + an RCCL communicator over them */
 
@@ -754,6 +754,65 @@ int rt_accum_attach_ids(rt_accum *acc, const rt_id_desc *desc);
 int rt_accum_read_ids(rt_accum *acc, uint32_t *ids, uint32_t *counts, uint32_t *other);
 int rt_accum_resolve_labels(rt_accum *acc, uint32_t flags, uint32_t *label, float *coverage);
 int rt_accum_resolve_matte(rt_accum *acc, uint32_t flags, const uint32_t *ids, uint32_t n_ids, float *matte);
+
+/* Light groups: a pixel's radiance split by the emitter it came from, so that lights can be dimmed, tinted or switched off after the render
+ * (additive; RT_ABI_VERSION stays 4). rt_accum_attach_light_groups makes an accumulator keep G more sums per pixel, GS_g,p. Groups are attached
+ * by this call, not by a bit of accum_flags; they combine with RT_ACCUM_FEATURES, with ids and with sensor accumulators, on every tree kind and
+ * under RT_FLAG_GLOBAL_BEST. rt_accum_denoise is untouched (denoising a mix is not offered).
+ * The value of a sample, V. The value sample s of pixel p adds to S_p is the fold of its path's frames (raytracer.h:588-590). It starts from the
+ *   path's terminal value T: the background of a miss; the hit's emission at one of shade()'s three early exits (the sampled direction is NaN,
+ *   :569-571; p < EPS, :576-578; the scale is 0, :584-586); or (0,0,0) when the depth budget is used up (:596-598). Then, for every pending frame
+ *   b from the innermost outwards: res = e_b + res * scl_b, with e_b the emission of frame b's hit. Then sanitize_nans (:607-616).
+ * Whose a value is. e_b belongs to the material of frame b's hit: material_ids[prim] of a triangle, primitives[i].material_id of an analytic
+ *   primitive; its group is material_group[that material]. An emission T belongs to its hit's material in the same way; a background T belongs
+ *   to background_group; a depth-exhausted T is (+0,+0,+0) in every group. RT_LIGHT_GROUP_NONE (for a material or for the background) means
+ *   no group: that emitter is in S_p and in no GS_g,p.
+ * The value of a group, V_g. The same sequence of binary32 operations with every e_b and T whose group is not g replaced by (+0,+0,+0), then
+ *   sanitize_nans of V_g itself. No decision of a path reads an emission value, so the paths, the scales and every event counter are those of
+ *   the ungrouped sample.
+ * The group sums. GS_g,p = the sum of V_g over pixel p's samples, in sample order s = 0, 1, ..., in binary32 from +0: the lane that adds a
+ *   list entry's samples to S_p adds their V_g to GS_g,p, in the same rounds; there are no float atomics. After any sequence of
+ *   rt_accum_render / rt_accum_render_adaptive calls GS_g,p is a function of n_p alone, like S_p: for any split over calls, passes and lists,
+ *   any max_paths, sort mode and packet mode.
+ * Exactness. The fold never mixes colour channels, so a channel that only one group's emitters feed is, in that group, bit for bit the
+ *   channel of S_p. In general the groups need NOT add up to S_p bit for bit: float addition is not associative, and V = sum of V_g holds in
+ *   real numbers only (a NaN that sanitize_nans removes from V may also survive in no V_g, or be removed from several).
+ * What stays the same. S_p, E_p, n_p, err, the feature sums, the id tables, every image, every event counter and every adaptive decision of
+ *   an accumulator with groups are, bit for bit, those of one without. An accumulator without groups allocates and launches nothing new.
+ * rt_accum_attach_light_groups: once per accumulator, before any call has added samples to it. material_group is copied; the caller keeps
+ *   theirs.
+ *   RT_ERR_INVALID_ARG: a NULL accumulator or desc; n_groups outside 1..RT_LIGHT_GROUP_MAX; a NULL material_group; n_materials other than the
+ *   scene's material count; a material_group entry or a background_group that is neither < n_groups nor RT_LIGHT_GROUP_NONE; a non-zero
+ *   reserved word; a flag other than RT_FLAG_DEVICE_FB; a device table that is not 4-byte aligned; a second attach; an attach after samples
+ *   were added.
+ *   RT_ERR_OOM (from a later render call): the per-path records (n_groups x 16 B and ray_depth + 1 tag bytes per path of a pass) do not fit
+ *   beside the wavefront workspace.
+ *   After any refusal the accumulator is unchanged.
+ * rt_accum_read_light_groups: GS on the host, [G][pixels][3] floats.
+ * rt_accum_resolve_light_group: fb_p = GS_group,p / (float)n_p per channel, 0 where n_p = 0. fb_rgb: width * height * 3 floats (a device
+ *   buffer with RT_FLAG_DEVICE_FB; `flags` is 0 or that, here and below).
+ * rt_accum_resolve_light_mix: relighting. weights is always a host array of G x 3 floats, w[g][c]. Per pixel and channel c, in binary32 with
+ *   no contraction: acc = +0; for g = 0 .. G-1 ascending: acc = acc + (GS_g,p[c] / (float)n_p) * w[g][c]; fb_p[c] = acc. A quotient is 0
+ *   where n_p = 0. All-ones weights give the image up to the rounding named under "Exactness"; a weight may be negative, inf or NaN and is used
+ *   as given.
+ * rt_accum_resolve_light_mix_rgb8 applies the device film on top: == rt_tonemap_rgb8 of rt_accum_resolve_light_mix's image.
+ * The four reads: RT_ERR_INVALID_ARG for a NULL accumulator, an accumulator without groups, group >= G, a flag other than RT_FLAG_DEVICE_FB, a
+ *   NULL buffer or NULL weights. */
+#define RT_LIGHT_GROUP_MAX  8u
+#define RT_LIGHT_GROUP_NONE 0xFFFFFFFFu
+typedef struct rt_light_group_desc {
+    uint32_t n_groups;              /* G: 1..RT_LIGHT_GROUP_MAX */
+    uint32_t background_group;      /* < G, or RT_LIGHT_GROUP_NONE */
+    const uint32_t *material_group; /* n_materials words: each < G, or RT_LIGHT_GROUP_NONE */
+    uint32_t n_materials;           /* must equal the scene's material count */
+    uint32_t flags;                 /* 0, or RT_FLAG_DEVICE_FB: material_group is a device pointer on the scene's GPU, 4-byte aligned, idle on entry */
+    uint32_t reserved[2];           /* 0 */
+} rt_light_group_desc;              /* 32 bytes */
+int rt_accum_attach_light_groups(rt_accum *acc, const rt_light_group_desc *desc);
+int rt_accum_read_light_groups(rt_accum *acc, float *group_sums /* [G][pixels][3] */);
+int rt_accum_resolve_light_group(rt_accum *acc, uint32_t group, uint32_t flags, float *fb_rgb);
+int rt_accum_resolve_light_mix(rt_accum *acc, const float *weights /* G x 3 */, uint32_t flags, float *fb_rgb);
+int rt_accum_resolve_light_mix_rgb8(rt_accum *acc, const float *weights, uint32_t flags, uint8_t *rgb8);
 
 /* New per-triangle arrays for a built scene (animation frames, deforming meshes, simulation steps) without rt_destroy + rt_create
  * (additive; RT_ABI_VERSION stays 4). Blocking; runs on the scene's own stream. The call replaces the five per-triangle arrays of the

@@ -30,6 +30,8 @@ from ._ctypes_abi import (
     RT_ID_USER,
     RT_ID_MISS,
     RT_ID_MAX_SLOTS,
+    RT_LIGHT_GROUP_MAX,
+    RT_LIGHT_GROUP_NONE,
     RT_FLAG_COUNTERS,
     RT_FLAG_DEVICE_FB,
     RT_BUILD_DEVICE_LBVH,
@@ -73,6 +75,7 @@ from ._ctypes_abi import (
     RtEnvironment,
     RtGeometryUpdate,
     RtIdDesc,
+    RtLightGroupDesc,
     RtParams,
     RtRay,
     RtSceneDesc,
@@ -481,21 +484,25 @@ class DeviceScene:
         _check(lib().rt_update_geometry_device(self._h, C.byref(u)))
 
     def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False, sensor=None, ids=None,
-                    id_slots: int = 4) -> "Accumulator":
+                    id_slots: int = 4, light_groups=None) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
         RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view. `features`: keep the first-hit
         albedo / normal / depth sums as well (rt_accum_create_ex with RT_ACCUM_FEATURES), which features(), read_features() and denoise() need.
         `sensor`: a Sensor in place of `camera` and `seed` (rt_accum_create_sensor): pixel p is then render_sensors(samples = n_p) of it.
-        `ids` (not None): Accumulator.attach_ids(ids, slots=id_slots) on the new accumulator, for read_ids(), labels() and matte()."""
+        `ids` (not None): Accumulator.attach_ids(ids, slots=id_slots) on the new accumulator, for read_ids(), labels() and matte().
+        `light_groups` (not None): Accumulator.attach_light_groups on the new accumulator, for read_light_groups(), light_group() and
+        light_mix(): the group of every material (an array), or a dict of attach_light_groups' arguments."""
         if sensor is not None and camera is not None:
             raise ValueError("accumulator: give a camera or a sensor, not both (the sensor carries its camera and seed)")
         acc = Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0, sensor=sensor)
-        if ids is not None:
-            try:
+        try:
+            if ids is not None:
                 acc.attach_ids(ids, slots=id_slots)
-            except Exception:
-                acc.close()
-                raise
+            if light_groups is not None:
+                acc.attach_light_groups(**(light_groups if isinstance(light_groups, dict) else {"material_group": light_groups}))
+        except Exception:
+            acc.close()
+            raise
         return acc
 
     def render_sensors(self, width: int, height: int, samples: int, sensors, rgb8: bool = False, counters: bool = False, global_best: bool = False,
@@ -1082,6 +1089,65 @@ class Accumulator:
         _check(lib().rt_accum_resolve_matte(self._h, 0, u32ptr(ids), ids.size, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def attach_light_groups(self, material_group, background=None, n_groups: Optional[int] = None, n_materials: Optional[int] = None) -> None:
+        """rt_accum_attach_light_groups: keep, per pixel, one more sum for each of `n_groups` light groups (1..8): the part of the pixel's
+        radiance that the emitters of the group produced. `material_group`: the group of every material of the scene, None or
+        RT_LIGHT_GROUP_NONE for a material in no group: a sequence (copied), or a device pointer to uint32 words (an int, with `n_materials`;
+        RT_FLAG_DEVICE_FB). `background`: the group of the background or environment, None for none. `n_groups`: by default one more than the
+        largest group named. Once, before the first render."""
+        d = RtLightGroupDesc()
+        none = RT_LIGHT_GROUP_NONE
+        d.background_group = none if background is None else int(background)
+        keep = None
+        named = [] if background is None else [int(background)]
+        if isinstance(material_group, (int, np.integer)):
+            if n_materials is None or n_groups is None:
+                raise ValueError("attach_light_groups: a device pointer needs n_materials and n_groups")
+            d.material_group, d.n_materials, d.flags = int(material_group), int(n_materials), RT_FLAG_DEVICE_FB
+        else:
+            keep = np.array([none if g is None else int(g) for g in material_group], dtype=np.uint32)
+            d.material_group, d.n_materials = keep.ctypes.data, keep.size
+            named += [int(g) for g in keep if g != none]
+        d.n_groups = int(n_groups) if n_groups is not None else max(named, default=0) + 1
+        _check(lib().rt_accum_attach_light_groups(self._h, C.byref(d)))
+        self.n_light_groups = int(d.n_groups)
+
+    def read_light_groups(self) -> np.ndarray:
+        """The group sums GS (rt_accum_read_light_groups): (G, H, W, 3) float32, GS[g] the sum over each pixel's samples of the part of their
+        radiance that group g's emitters produced. Needs attach_light_groups."""
+        out = np.zeros((getattr(self, "n_light_groups", 1), self.height, self.width, 3), dtype=np.float32)
+        _check(lib().rt_accum_read_light_groups(self._h, fptr(out)))
+        return out
+
+    def light_group(self, g: int, device_out: Optional[int] = None):
+        """rt_accum_resolve_light_group: the image of group g alone, GS[g] / n: (H, W, 3) float32. `device_out`: a device pointer that
+        receives it in HBM (RT_FLAG_DEVICE_FB); then None is returned."""
+        if device_out:
+            _check(lib().rt_accum_resolve_light_group(self._h, int(g), RT_FLAG_DEVICE_FB, C.c_void_p(device_out)))
+            return None
+        fb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        _check(lib().rt_accum_resolve_light_group(self._h, int(g), 0, fb.ctypes.data_as(C.c_void_p)))
+        return fb
+
+    def light_mix(self, weights, rgb8: bool = False, device_out: Optional[int] = None):
+        """rt_accum_resolve_light_mix: the image relit, sum over g of (GS[g] / n) * weights[g]: `weights` is (G, 3), or (G,) for one factor per
+        group. (H, W, 3) float32, or the device film's uint8 image with `rgb8`. `device_out`: a device pointer that receives it in HBM
+        (RT_FLAG_DEVICE_FB); then None is returned."""
+        G = getattr(self, "n_light_groups", 1)
+        w = np.asarray(weights, dtype=np.float32)
+        if w.shape == (G,):
+            w = np.repeat(w[:, None], 3, axis=1)
+        if w.shape != (G, 3):
+            raise ValueError(f"light_mix: weights must have shape ({G}, 3) or ({G},), not {w.shape}")
+        w = np.ascontiguousarray(w)
+        fn = lib().rt_accum_resolve_light_mix_rgb8 if rgb8 else lib().rt_accum_resolve_light_mix
+        if device_out:
+            _check(fn(self._h, fptr(w), RT_FLAG_DEVICE_FB, C.c_void_p(device_out)))
+            return None
+        img = np.zeros((self.height, self.width, 3), dtype=np.uint8 if rgb8 else np.float32)
+        _check(fn(self._h, fptr(w), 0, img.ctypes.data_as(C.c_void_p)))
+        return img
+
     def close(self) -> None:
         if self._h:
             lib().rt_accum_destroy(self._h)
@@ -1210,6 +1276,8 @@ __all__ = [
     "make_sensors",
     "Sensor",
     "RtSensor",
+    "RT_LIGHT_GROUP_MAX",
+    "RT_LIGHT_GROUP_NONE",
     "pack_rays",
     "rays",
     "RAY_DTYPE",

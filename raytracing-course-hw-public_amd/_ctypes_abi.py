@@ -137,6 +137,21 @@ class RtIdDesc(C.Structure):  # rt_accum_attach_ids: which ids an accumulator ke
     ]
 
 
+RT_LIGHT_GROUP_MAX = 8
+RT_LIGHT_GROUP_NONE = 0xFFFFFFFF
+
+
+class RtLightGroupDesc(C.Structure):  # rt_accum_attach_light_groups: the group of every material and of the background (32 bytes)
+    _fields_ = [
+        ("n_groups", C.c_uint32),
+        ("background_group", C.c_uint32),
+        ("material_group", C.c_void_p),
+        ("n_materials", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 class RtTextureDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgba8", c_u8_p)]
 
@@ -319,6 +334,11 @@ ABI_PROTOTYPES = {
     "rt_accum_read_ids": (C.c_int, [C.c_void_p, c_u32_p, c_u32_p, c_u32_p]),
     "rt_accum_resolve_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_accum_resolve_matte": (C.c_int, [C.c_void_p, C.c_uint32, c_u32_p, C.c_uint32, C.c_void_p]),
+    "rt_accum_attach_light_groups": (C.c_int, [C.c_void_p, C.POINTER(RtLightGroupDesc)]),
+    "rt_accum_read_light_groups": (C.c_int, [C.c_void_p, c_float_p]),
+    "rt_accum_resolve_light_group": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_accum_resolve_light_mix": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, C.c_void_p]),
+    "rt_accum_resolve_light_mix_rgb8": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, C.c_void_p]),
     "rt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),
     "rt_update_geometry_device": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),  # the five pointers are device pointers
     "rt_refit_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -22,6 +22,10 @@
 // progressive call (rt_accum_render). RT_AOV=<prefix> (with or without RT_DENOISE: it renders through a feature accumulator too) also writes
 // the first-hit feature means: <prefix>_albedo.ppm (clamp(a, 0, 1) * 255 + 0.5, truncated), <prefix>_normal.ppm (0.5 * n + 0.5, quantised
 // likewise) and <prefix>_depth.pfm (one channel "Pf", little-endian floats, rows bottom to top as PFM has them).
+// RT_LIGHT_GROUPS=material: render through an accumulator with light groups (rt_accum_attach_light_groups) on one GPU: every emissive material
+// (a non-zero emission factor, the library's own test) is a group of its own, in material order, and the background is the last group; more
+// than RT_LIGHT_GROUP_MAX groups are refused with a message. Besides the image it writes each group alone (rt_accum_resolve_light_group through
+// the film) to <stem>_group_<g><ext> of the output path.
 // RT_CAMERA=pinhole|equirect|fisheye|ortho|thinlens: render the file's camera through a sensor model evaluated on the device (rt_abi.h
 // rt_sensor), on one GPU, with RT_SEED as its seed: rt_render_sensors_rgb8, or rt_accum_create_sensor where RT_ADAPTIVE / RT_DENOISE / RT_AOV ask
 // for an accumulator. RT_CAMERA_FOV_DEG replaces the camera's horizontal field of view (pinhole, fisheye, thinlens); RT_ORTHO_HALF_WIDTH
@@ -90,7 +94,8 @@ int main(int argc, char **argv) {
     const char *adaptive = std::getenv("RT_ADAPTIVE"); // accumulators run on one GPU
     const bool denoise = env_on("RT_DENOISE");
     const char *aov = std::getenv("RT_AOV");
-    const bool accumulate = adaptive || denoise || aov;
+    const char *light_groups = std::getenv("RT_LIGHT_GROUPS");
+    const bool accumulate = adaptive || denoise || aov || light_groups;
     const char *camera_kind = std::getenv("RT_CAMERA"); // sensors are evaluated on one GPU
     rt_scene *scene = nullptr;
     const int device = dev_env ? std::atoi(dev_env) : (rt_device_count() > 1 && !accumulate && !camera_kind && !env_radiance ? RT_ALL_DEVICES : 0);
@@ -106,6 +111,28 @@ int main(int argc, char **argv) {
     if (env_radiance) { // bg_color = intensity, as rt_loaded_set_env_map sets it for the 8-bit map (main.cpp:28)
         const char *k = std::getenv("RT_ENV_MAP_INTENSITY");
         desc.bg_color[0] = desc.bg_color[1] = desc.bg_color[2] = k ? std::strtof(k, nullptr) : 1.0f;
+    }
+    std::vector<uint32_t> material_group; // RT_LIGHT_GROUPS=material: the group of every material, then n_groups with the background last
+    uint32_t n_groups = 0;
+    if (light_groups) {
+        if (std::strcmp(light_groups, "material") != 0) {
+            rt_loaded_free(loaded);
+            std::cerr << "RT_LIGHT_GROUPS: material (one group per emissive material, the background last)" << std::endl;
+            return EXIT_FAILURE;
+        }
+        material_group.assign(desc.n_materials, RT_LIGHT_GROUP_NONE);
+        for (uint32_t i = 0; i < desc.n_materials; ++i) {
+            const float *e = desc.materials[i].emission;
+            if (!((e[0] == 0) & (e[1] == 0) & (e[2] == 0)))
+                material_group[i] = n_groups++;
+        }
+        n_groups += 1; // the background
+        if (n_groups > RT_LIGHT_GROUP_MAX) {
+            rt_loaded_free(loaded);
+            std::cerr << "RT_LIGHT_GROUPS=material: " << n_groups - 1 << " emissive materials and the background make " << n_groups << " groups; at most "
+                      << RT_LIGHT_GROUP_MAX << " are kept" << std::endl;
+            return EXIT_FAILURE;
+        }
     }
     int crc = rt_create(&desc, device, &scene);
     if (crc == RT_ERR_COMM && device == RT_ALL_DEVICES) {
@@ -199,16 +226,25 @@ int main(int argc, char **argv) {
     uint32_t rounds = 0;
     std::vector<uint32_t> spp_map;
     std::vector<float> aov_albedo, aov_normal, aov_depth;
+    std::vector<uint8_t> group_rgb8; // RT_LIGHT_GROUPS: n_groups images
     if (accumulate) {
         if (!views.empty()) {
             rt_destroy(scene);
             rt_loaded_free(loaded);
-            std::cerr << "RT_ADAPTIVE / RT_DENOISE / RT_AOV render the scene's camera only (not with RT_ALL_CAMERAS)" << std::endl;
+            std::cerr << "RT_ADAPTIVE / RT_DENOISE / RT_AOV / RT_LIGHT_GROUPS render the scene's camera only (not with RT_ALL_CAMERAS)" << std::endl;
             return EXIT_FAILURE;
         }
         rt_accum *acc = nullptr;
         const uint32_t accum_flags = (denoise || aov) ? RT_ACCUM_FEATURES : 0u;
         rc = camera_kind ? rt_accum_create_sensor(scene, width, height, &sensor, accum_flags, &acc) : rt_accum_create_ex(scene, width, height, nullptr, p.seed, accum_flags, &acc);
+        if (rc == RT_OK && light_groups) {
+            rt_light_group_desc lg{};
+            lg.n_groups = n_groups;
+            lg.background_group = n_groups - 1;
+            lg.material_group = material_group.data();
+            lg.n_materials = desc.n_materials;
+            rc = rt_accum_attach_light_groups(acc, &lg);
+        }
         if (rc == RT_OK && adaptive) {
             rt_adaptive ad{};
             ad.threshold = std::strtof(adaptive, nullptr);
@@ -229,6 +265,15 @@ int main(int argc, char **argv) {
                 rc = denoise ? rt_accum_denoise(acc, nullptr, 0, fb.data()) : rt_accum_resolve(acc, 0, fb.data());
                 if (rc == RT_OK)
                     rt_tonemap_rgb8(fb.data(), view_pixels, rgb8.data());
+            }
+        }
+        if (rc == RT_OK && light_groups) { // each group alone, through the same film as the image
+            group_rgb8.resize((size_t)n_groups * view_pixels * 3);
+            std::vector<float> fb(view_pixels * 3, 0.0f);
+            for (uint32_t g = 0; g < n_groups && rc == RT_OK; ++g) {
+                rc = rt_accum_resolve_light_group(acc, g, 0, fb.data());
+                if (rc == RT_OK)
+                    rt_tonemap_rgb8(fb.data(), view_pixels, group_rgb8.data() + (size_t)g * view_pixels * 3);
             }
         }
         if (rc == RT_OK && adaptive) {
@@ -270,6 +315,14 @@ int main(int argc, char **argv) {
             std::filesystem::path name = out.parent_path() / (out.stem().string() + "_" + std::to_string(i) + out.extension().string());
             if (rt_write_ppm(name.string().c_str(), width, height, rgb8.data() + i * view_pixels * 3) != RT_OK)
                 return die("write");
+        }
+    }
+    if (light_groups) {
+        const std::filesystem::path out(argv[5]);
+        for (uint32_t g = 0; g < n_groups; ++g) {
+            std::filesystem::path name = out.parent_path() / (out.stem().string() + "_group_" + std::to_string(g) + out.extension().string());
+            if (rt_write_ppm(name.string().c_str(), width, height, group_rgb8.data() + (size_t)g * view_pixels * 3) != RT_OK)
+                return die("RT_LIGHT_GROUPS");
         }
     }
     if (aov) {

@@ -179,6 +179,44 @@ __global__ __launch_bounds__(256) void accum_matte_kernel(const rt::AccumRound R
     }
 }
 
+// GS_g,p / (float)n_p of one group, 0 where n_p = 0: accum_image_kernel's quotient of a group sum (rt_abi.h rt_accum_attach_light_groups)
+DEV V3 accum_group_mean(const WfGroups &G, uint32_t g, uint32_t p, uint32_t n) {
+    if (n == 0u)
+        return mk(0, 0, 0);
+    return ld3(G.sum + 3ull * ((size_t)g * G.pixels + p)) / (float)n;
+}
+
+// rt_accum_resolve_light_group
+__global__ __launch_bounds__(256) void accum_light_group_kernel(const rt::AccumRound R, const WfGroups G, uint32_t group, float *fb) {
+    const uint32_t n_pix = R.width * R.height;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pix; p += gridDim.x * blockDim.x) {
+        const V3 out = accum_group_mean(G, group, p, R.count[p]);
+        fb[3ull * p] = out.x;
+        fb[3ull * p + 1] = out.y;
+        fb[3ull * p + 2] = out.z;
+    }
+}
+
+// rt_accum_resolve_light_mix: per channel acc = +0, then acc = acc + mean_g * w[g][c] for g ascending, one multiplication and one addition each
+// (-ffp-contract=off). The weights are a kernel argument (scalar registers); the loop over g is over a run-time G with one V3 live.
+__global__ __launch_bounds__(256) void accum_light_mix_kernel(const rt::AccumRound R, const WfGroups G, const rt::LightMixWeights W, float *fb) {
+    const uint32_t n_pix = R.width * R.height;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pix; p += gridDim.x * blockDim.x) {
+        const uint32_t n = R.count[p];
+        V3 acc = mk(0, 0, 0);
+#pragma unroll
+        for (uint32_t g = 0; g < RT_LIGHT_GROUP_MAX; ++g) {
+            if (g < G.n_groups) {
+                const V3 m = accum_group_mean(G, g, p, n);
+                acc = acc + mk(m.x * W.w[g][0], m.y * W.w[g][1], m.z * W.w[g][2]);
+            }
+        }
+        fb[3ull * p] = acc.x;
+        fb[3ull * p + 1] = acc.y;
+        fb[3ull * p + 2] = acc.z;
+    }
+}
+
 dim3 accum_grid(const rt::AccumRound &R) {
     const uint64_t n_pix = (uint64_t)R.width * R.height;
     const uint64_t b = (n_pix + 255u) / 256u;
@@ -231,6 +269,14 @@ hipError_t launch_accum_labels(const AccumRound &R, const WfIds &I, uint32_t *la
 
 hipError_t launch_accum_matte(const AccumRound &R, const WfIds &I, const uint32_t *set, uint32_t n_set, float *matte, hipStream_t stream) {
     return RT_LAUNCH_CHECKED(accum_matte_kernel, accum_grid(R), dim3(256), 0, stream, R, I, set, n_set, matte);
+}
+
+hipError_t launch_accum_light_group(const AccumRound &R, const WfGroups &G, uint32_t group, float *fb, hipStream_t stream) {
+    return RT_LAUNCH_CHECKED(accum_light_group_kernel, accum_grid(R), dim3(256), 0, stream, R, G, group, fb);
+}
+
+hipError_t launch_accum_light_mix(const AccumRound &R, const WfGroups &G, const LightMixWeights &w, float *fb, hipStream_t stream) {
+    return RT_LAUNCH_CHECKED(accum_light_mix_kernel, accum_grid(R), dim3(256), 0, stream, R, G, w, fb);
 }
 
 } // namespace rt

@@ -23,7 +23,9 @@ struct rt_accum {
     bool ids = false;      // rt_accum_attach_ids: I holds the per-pixel id tables (I.rec is the scene's, bound per fill)
     WfIds I{};
     rt::DevBuf<uint32_t> matte_set; // rt_accum_resolve_matte's id set on the device
-    bool has_samples = false; // a call has queued a pass of this accumulator: ids can no longer be attached
+    bool groups = false;   // rt_accum_attach_light_groups: G holds the group sums and the material table (G.rec and G.tag are the scene's, bound per fill)
+    WfGroups G{};
+    bool has_samples = false; // a call has queued a pass of this accumulator: ids and light groups can no longer be attached
     ~rt_accum() {
         (void)hipSetDevice(scene->device);
         (void)hipStreamSynchronize(scene->stream); // `owned` frees after this body: on this device, behind this synchronise
@@ -184,6 +186,12 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                     return rc;
                 a->I.rec = s->wf_ids.get();
             }
+            if (a->groups) {
+                if (int rc = s->ensure_groups(a->G.n_groups); rc != RT_OK)
+                    return rc;
+                a->G.rec = s->wf_group_rec.get();
+                a->G.tag = s->wf_group_tag.get();
+            }
             s->wf_bind(W);
             W.fb = nullptr;
             W.accum = nullptr; // wf_resolve does not run on an accumulator pass
@@ -193,7 +201,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
                 a->has_samples = true;
-                const rt::WfPassKind kind = rt::WfPassKind::list(A, a->features ? &a->F : nullptr, a->ids ? &a->I : nullptr, a->sensor);
+                const rt::WfPassKind kind = rt::WfPassKind::list(A, a->features ? &a->F : nullptr, a->ids ? &a->I : nullptr, a->groups ? &a->G : nullptr, a->sensor);
                 HIP_TRY(rt::launch_pass(s, p, a->pkt, W, kind, rt::WfPassStep{true, true, stats != nullptr}));
                 passes += 1;
                 packet_passes += W.use_packet;
@@ -545,4 +553,138 @@ extern "C" int rt_accum_resolve_matte(rt_accum *acc, uint32_t flags, const uint3
         HIP_TRY(rt::launch_accum_matte(acc->R, acc->I, acc->matte_set.get(), (uint32_t)set.size(), d_matte, s->stream));
         return RT_OK;
     });
+}
+
+// ---- light groups (rt_abi.h rt_accum_attach_light_groups: the rule; the kernels: rt_wavefront.hip wf_group_tags, rt_wf_stages.h wf_fold_groups /
+// wf_resolve_groups, rt_accum.hip)
+extern "C" int rt_accum_attach_light_groups(rt_accum *acc, const rt_light_group_desc *desc) {
+    const char *fn = "rt_accum_attach_light_groups";
+    if (!acc || !desc)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null argument");
+    rt_scene *s = acc->scene;
+    const uint32_t G = desc->n_groups, n_mats = (uint32_t)s->prep->mats.size();
+    const bool device_table = (desc->flags & RT_FLAG_DEVICE_FB) != 0;
+    auto in_range = [G](uint32_t g) { return g < G || g == RT_LIGHT_GROUP_NONE; };
+    if (G == 0 || G > RT_LIGHT_GROUP_MAX)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": n_groups must be 1.." + std::to_string(RT_LIGHT_GROUP_MAX));
+    if (desc->reserved[0] != 0 || desc->reserved[1] != 0 || (desc->flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": reserved fields must be 0; flags other than RT_FLAG_DEVICE_FB");
+    if (!desc->material_group || desc->n_materials != n_mats)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": material_group must hold the scene's " + std::to_string(n_mats) + " materials");
+    if (device_table && (reinterpret_cast<uintptr_t>(desc->material_group) & 3u))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the device table must be 4-byte aligned");
+    if (!in_range(desc->background_group))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": background_group must be below n_groups, or RT_LIGHT_GROUP_NONE");
+    if (acc->groups)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator already has light groups");
+    if (acc->has_samples)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator already holds samples; attach light groups before the first render");
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<uint32_t> words(n_mats); // the entries are checked on the host, wherever the table lives
+    if (device_table) {
+        if (int rc = rt::queue_and_wait(s->stream, [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(words.data(), desc->material_group, 4 * (size_t)n_mats, hipMemcpyDeviceToHost, s->stream));
+                return RT_OK;
+            });
+            rc != RT_OK)
+            return rc;
+    } else {
+        std::copy(desc->material_group, desc->material_group + n_mats, words.begin());
+    }
+    std::vector<uint8_t> bytes(n_mats);
+    for (uint32_t m = 0; m < n_mats; ++m) {
+        if (!in_range(words[m]))
+            return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": material_group[" + std::to_string(m) + "] is neither below n_groups nor RT_LIGHT_GROUP_NONE");
+        bytes[m] = words[m] == RT_LIGHT_GROUP_NONE ? (uint8_t)WF_GROUP_NONE : (uint8_t)words[m];
+    }
+    WfGroups W{};
+    W.n_groups = G;
+    W.background = desc->background_group == RT_LIGHT_GROUP_NONE ? WF_GROUP_NONE : desc->background_group;
+    W.pixels = acc->width * acc->height;
+    const size_t sum_bytes = 12 * (size_t)G * W.pixels;
+    uint8_t *table = nullptr;
+    int rc;
+    if ((rc = accum_alloc(acc, sum_bytes, &W.sum, fn)) != RT_OK || (rc = accum_alloc(acc, n_mats, &table, fn)) != RT_OK)
+        return rc; // what was allocated stays with the accumulator's arena, unused, until rt_accum_destroy
+    auto queue = [&]() -> int { // `bytes` is a local: nothing of this may be in flight when it dies
+        HIP_TRY(hipMemsetAsync(W.sum, 0, sum_bytes, s->stream)); // +0.0
+        if (n_mats)
+            HIP_TRY(hipMemcpyAsync(table, bytes.data(), n_mats, hipMemcpyHostToDevice, s->stream));
+        return RT_OK;
+    };
+    if ((rc = rt::queue_and_wait(s->stream, queue)) != RT_OK)
+        return rc;
+    W.material_group = table;
+    acc->G = W;
+    acc->groups = true;
+    return RT_OK;
+}
+
+static int groups_check(const rt_accum *acc, const void *buffer, uint32_t flags, const char *fn) {
+    if (!acc)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null accumulator");
+    if (!acc->groups)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no light groups (rt_accum_attach_light_groups)");
+    if (!buffer || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null buffer or flags other than RT_FLAG_DEVICE_FB");
+    return RT_OK;
+}
+
+extern "C" int rt_accum_read_light_groups(rt_accum *acc, float *group_sums) {
+    if (int rc = groups_check(acc, group_sums, 0u, "rt_accum_read_light_groups"); rc != RT_OK)
+        return rc;
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    return read_back(s, {{group_sums, acc->G.sum, 12 * (size_t)acc->G.n_groups * acc->G.pixels}});
+}
+
+extern "C" int rt_accum_resolve_light_group(rt_accum *acc, uint32_t group, uint32_t flags, float *fb_rgb) {
+    if (int rc = groups_check(acc, fb_rgb, flags, "rt_accum_resolve_light_group"); rc != RT_OK)
+        return rc;
+    if (group >= acc->G.n_groups)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_light_group: group " + std::to_string(group) + " of " + std::to_string(acc->G.n_groups));
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_fb;
+    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
+    return io.run([&]() -> int {
+        HIP_TRY(rt::launch_accum_light_group(acc->R, acc->G, group, d_fb, s->stream));
+        return RT_OK;
+    });
+}
+
+// the G x 3 weights of a mix, as the kernel argument they travel in
+static int mix_weights(const rt_accum *acc, const float *weights, const char *fn, rt::LightMixWeights *w) {
+    if (!weights)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null weights");
+    std::memset(w, 0, sizeof(*w));
+    std::memcpy(w->w, weights, 12 * (size_t)acc->G.n_groups);
+    return RT_OK;
+}
+
+extern "C" int rt_accum_resolve_light_mix(rt_accum *acc, const float *weights, uint32_t flags, float *fb_rgb) {
+    rt::LightMixWeights w;
+    int rc;
+    if ((rc = groups_check(acc, fb_rgb, flags, "rt_accum_resolve_light_mix")) != RT_OK || (rc = mix_weights(acc, weights, "rt_accum_resolve_light_mix", &w)) != RT_OK)
+        return rc;
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
+    float *d_fb;
+    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
+    return io.run([&]() -> int {
+        HIP_TRY(rt::launch_accum_light_mix(acc->R, acc->G, w, d_fb, s->stream));
+        return RT_OK;
+    });
+}
+
+extern "C" int rt_accum_resolve_light_mix_rgb8(rt_accum *acc, const float *weights, uint32_t flags, uint8_t *rgb8) {
+    rt::LightMixWeights w;
+    int rc;
+    if ((rc = groups_check(acc, rgb8, flags, "rt_accum_resolve_light_mix_rgb8")) != RT_OK || (rc = mix_weights(acc, weights, "rt_accum_resolve_light_mix_rgb8", &w)) != RT_OK)
+        return rc;
+    rt_scene *s = acc->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    return film_image(acc, flags, rgb8, [&](float *d_fb) { return rt::launch_accum_light_mix(acc->R, acc->G, w, d_fb, s->stream); });
 }

@@ -364,6 +364,24 @@ struct WfIds {
     uint32_t pixels;       // width * height
 };
 
+// The light groups of an accumulator with groups (rt_abi.h rt_accum_attach_light_groups). wf_group_tags runs once per bounce, between the
+// closest hits and wf_shade, and writes one byte per queued ray: the group of what the ray hit (or of the background), at the frame level
+// the path head carries, tag[nb][path]. A frame that wf_shade pushes at level nb is the frame of that hit; a path that ends with nb frames
+// has the owner of its terminal value at level nb; a pass-through bounce pushes nothing and the next bounce writes level nb again. A path
+// cut by its depth budget straight after a push leaves level nb stale (of an earlier bounce, pass or accumulator), and its terminal value is
+// exactly (+0, +0, +0): the readers compare a tag with g and never index by it. wf_fold_groups then folds every path's frames once for all
+// groups and writes V_g to rec[g][path]; wf_resolve_groups adds them onto GS in sample order, one lane per entry, as wf_resolve_list does.
+#define WF_GROUP_NONE 0xFFu
+struct WfGroups {
+    uint8_t *tag;                  // [ray_depth + 1][n_paths of the pass]: level-major like WfLaunch::fold, in the scene's wavefront workspace
+    RtF4 *rec;                     // [G][n_paths of the pass]: group-major (a wave's stores are contiguous), in the scene's wavefront workspace
+    float *sum;                    // [G][pixels][3]: GS_g,p
+    const uint8_t *material_group; // [n_materials]: the group of each material, WF_GROUP_NONE for none; the accumulator's copy
+    uint32_t n_groups;             // G: 1..RT_LIGHT_GROUP_MAX
+    uint32_t background;           // < G, or WF_GROUP_NONE
+    uint32_t pixels;               // width * height
+};
+
 // A pass of rt_render_rays (rt_rays.cpp): the first stage takes its rays and RNG streams from the caller's buffer instead of a camera
 // (rt_wf_stages.h WfFromRays). The call is a virtual image of n_rays / group "pixels" (outputs) with group * samples samples each, so WfLaunch keeps
 // describing the pass (first_pixel / pass_pixels count outputs, WfLaunch::samples = group * samples) and wf_fold / wf_resolve run unchanged:

@@ -69,7 +69,8 @@ struct WfHostSync {
 // follow bounce 0's closest hits and the last stage, and carries exactly what those read. Made by one of the four named constructors only:
 //   cameras  the camera table WfLaunch::sensors (a view is a pinhole record), whatever the entry point; wf_resolve adds onto the image
 //   list     an accumulator round's entry list; wf_resolve_list adds onto the accumulator's sums, behind the feature sums and the id tables
-//            of an accumulator that keeps them (wf_features / wf_ids after bounce 0, wf_resolve_features / wf_resolve_ids before the sums)
+//            of an accumulator that keeps them (wf_features / wf_ids after bounce 0, wf_resolve_features / wf_resolve_ids before the sums),
+//            and behind the group sums of one with light groups (wf_group_tags at every bounce, wf_fold_groups, wf_resolve_groups)
 //   rays     the caller's rays and streams (rt_render_rays); wf_resolve adds onto the outputs
 //   bake     the samples of bake points (rt_bake); wf_resolve_bake folds them as the bake's kind asks
 // A camera source is made of the call's camera table on the host (run_passes uploads it as WfLaunch::sensors), a list of its accumulator's one
@@ -79,8 +80,8 @@ class WfPassKind {
 public:
     enum Source { CAMERAS, LIST, RAYS, BAKE };
     static WfPassKind cameras(const WfSensor *table, uint32_t n_views) { return WfPassKind(Cameras{table, n_views, single_origin(table, n_views)}); }
-    static WfPassKind list(const WfAccum &entries, const WfFeat *features, const WfIds *ids, const WfSensor &camera) {
-        return WfPassKind(List{entries, features, ids, single_origin(&camera, 1)});
+    static WfPassKind list(const WfAccum &entries, const WfFeat *features, const WfIds *ids, const WfGroups *groups, const WfSensor &camera) {
+        return WfPassKind(List{entries, features, ids, groups, single_origin(&camera, 1)});
     }
     static WfPassKind rays(const WfRays &rays) { return WfPassKind(rays); }
     static WfPassKind bake(const WfBake &bake) { return WfPassKind(bake); }
@@ -93,6 +94,8 @@ public:
     // the launches behind bounce 0's closest hits, whose results are final there: a list's first-hit features and ids; null: none
     const WfFeat *features() const { return source() == LIST ? std::get<List>(v).features : nullptr; }
     const WfIds *ids() const { return source() == LIST ? std::get<List>(v).ids : nullptr; }
+    // the launches of a list with light groups: wf_group_tags at every bounce, wf_fold_groups before wf_fold, wf_resolve_groups; null: none
+    const WfGroups *groups() const { return source() == LIST ? std::get<List>(v).groups : nullptr; }
     // the cameras of the pass: part of the packet policy's key (a caller's rays and bake points count as one)
     uint32_t n_views() const { return source() == CAMERAS ? std::get<Cameras>(v).n_views : 1u; }
     const WfSensor *camera_table() const { return source() == CAMERAS ? std::get<Cameras>(v).table : nullptr; } // [n_views], host; null: no table to upload
@@ -112,6 +115,7 @@ private:
         WfAccum entries;
         const WfFeat *features;
         const WfIds *ids;
+        const WfGroups *groups;
         const float *origin;
     };
     std::variant<Cameras, List, WfRays, WfBake> v; // in the order of Source
@@ -173,6 +177,13 @@ hipError_t launch_accum_feature_means(const AccumRound &R, const WfFeat &F, floa
 // null. `set`: the matte's ids sorted ascending without duplicates, device, n_set >= 1.
 hipError_t launch_accum_labels(const AccumRound &R, const WfIds &I, uint32_t *label, float *coverage, hipStream_t stream);
 hipError_t launch_accum_matte(const AccumRound &R, const WfIds &I, const uint32_t *set, uint32_t n_set, float *matte, hipStream_t stream);
+// the images of the group sums (rt_accum_resolve_light_group, rt_accum_resolve_light_mix): fb[p] = GS_g,p / (float)n_p, or per channel
+// acc = +0; for g ascending: acc = acc + (GS_g,p / (float)n_p) * w[g][c]; a quotient is 0 where n_p = 0. The weights travel as a kernel argument.
+struct LightMixWeights {
+    float w[RT_LIGHT_GROUP_MAX][3];
+};
+hipError_t launch_accum_light_group(const AccumRound &R, const WfGroups &G, uint32_t group, float *fb, hipStream_t stream);
+hipError_t launch_accum_light_mix(const AccumRound &R, const WfGroups &G, const LightMixWeights &w, float *fb, hipStream_t stream);
 // rt_lightmap.hip: rt_lightmap_points. The texel centres of a width x height atlas that the triangles (device arrays: 9 / 9 / 6 floats each) cover,
 // as bake points in increasing texel order: owner per texel (integer atomicMin), exclusive scan, scatter. `owner` and `offs` have room for
 // width * height words, `scan_temp` for lightmap_scan_temp_bytes(width * height); `count` (device, one word) receives the number of owned

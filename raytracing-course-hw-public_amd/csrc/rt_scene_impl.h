@@ -217,6 +217,17 @@ struct rt_scene {
             return rt::hip_fail(e, "id records");
         return RT_OK;
     }
+    // the per-path records of the passes of an accumulator with light groups (WfGroups::rec, n_groups x 16 B per path, and WfGroups::tag, one
+    // byte per path and frame level): as the feature records. Neither needs its content kept or cleared (a stale tag is legal: WfGroups).
+    rt::DevBuf<RtF4> wf_group_rec;
+    rt::DevBuf<uint8_t> wf_group_tag;
+    int ensure_groups(uint32_t n_groups) {
+        if (hipError_t e = wf_group_rec.reserve(wf_paths_cap * n_groups); e != hipSuccess)
+            return rt::hip_fail(e, "light-group records");
+        if (hipError_t e = wf_group_tag.reserve(wf_paths_cap * (wf_depth_cap + 1ull)); e != hipSuccess)
+            return rt::hip_fail(e, "light-group tags");
+        return RT_OK;
+    }
     // the workspace half of a WfLaunch (after ensure_wavefront): queues, hit records, counters, stack workspace, sort buffers
     void wf_bind(WfLaunch &W) {
         W.paths_in = wf_paths[0];
@@ -255,7 +266,7 @@ struct rt_scene {
         // point returns with the stream synchronised. In a group's handle all of them are empty.
         for (rt::DevArena *a : {&wf_owned, &owned, &geo_owned, &light_owned, &env_owned})
             a->reset();
-        wf_feat.reset(), wf_ids.reset(), wf_rel.reset(), staging.reset(), sensors.reset(), film_table.reset();
+        wf_feat.reset(), wf_ids.reset(), wf_group_rec.reset(), wf_group_tag.reset(), wf_rel.reset(), staging.reset(), sensors.reset(), film_table.reset();
         ext_events.destroy();
         if (ev0)
             (void)hipEventDestroy(ev0);

@@ -406,6 +406,23 @@ __global__ __launch_bounds__(256) void wf_ids(const DevScene S, const WfLaunch L
     }
 }
 
+// ------------------------------------------------------------------------------------------------ light-group tags
+// A pass of an accumulator with light groups (rt_abi.h rt_accum_attach_light_groups; WfGroups), at EVERY bounce, between the closest hits and
+// wf_shade: whose emission the frame (or the terminal value) that wf_shade is about to make of this (ray, hit) pair is. It reads what wf_shade
+// reads, the hit at queue position jq and the head of the ray that position stands for, and writes one byte at the head's own frame level:
+// the group of the hit's material, the background's group for a miss, WF_GROUP_NONE for neither. Counts nothing.
+__global__ __launch_bounds__(256) void wf_group_tags(const DevScene S, const WfLaunch L, const WfGroups Gr) {
+    const uint32_t n_in = L.counters[WF_CNT_IN];
+    for (uint32_t jq = blockIdx.x * blockDim.x + threadIdx.x; jq < n_in; jq += gridDim.x * blockDim.x) {
+        const uint32_t k = wf_load_hit(L.hits + jq).k;
+        const WfHead in = wf_load_head(L.paths_in + wf_order_slot(L, jq));
+        uint32_t tag = Gr.background;
+        if (k != RT_NONE)
+            tag = Gr.material_group[(k & RT_PRIM_FLAG) != 0u ? S.prims[k & ~RT_PRIM_FLAG].material_id : S.attrs[k].material];
+        Gr.tag[wf_fold_index(L.n_paths, in.nb, in.id)] = (uint8_t)tag;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ shade
 // LIGHTS_LDS: the light BVH (inner nodes, triangles, aux) is small enough (DevBvh::lds_inner) to be staged in LDS once per
 // block; bvh_mix_dist's sample and pdf then read it there: a dozen dependent L1 round trips per hit become LDS reads.
@@ -693,13 +710,15 @@ static hipError_t launch_first_stage(const DevScene &S, const WfLaunch &L, const
 static hipError_t launch_last_stage(const WfLaunch &L, const WfPassKind &kind, const WfPassStep &step, int num_cus, hipStream_t stream) {
     const dim3 block(256);
     const int first = step.first_pass ? 1 : 0, last = step.last_pass ? 1 : 0;
-    if (kind.source() == WfPassKind::LIST) { // the feature sums and the id tables go before the sums: they read the entry's base count from the list
+    if (kind.source() == WfPassKind::LIST) { // the feature sums, the id tables and the group sums go before the sums: they read the entry's base count from the list
         const WfAccum &A = kind.entries();
         const int res_blocks = (int)((A.n_entries + 255u) / 256u);
         if (kind.features())
             WF_LAUNCH(wf_resolve_features, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.features());
         if (kind.ids())
             WF_LAUNCH(wf_resolve_ids, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.ids());
+        if (kind.groups())
+            WF_LAUNCH(wf_resolve_groups, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.groups(), L.n_paths);
         WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, A);
     } else if (kind.source() == WfPassKind::BAKE) { // the fold the bake's kind asks for, one lane per (point, k)
         const WfBake &B = kind.bake_points();
@@ -793,6 +812,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind
             WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *kind.features());
         if (b == 0 && kind.ids()) // ... and so are their ids
             WF_LAUNCH(wf_ids, dim3(shade_blocks), block, 0, stream, S, L, *kind.ids());
+        if (kind.groups()) // light groups: at every bounce, whose emission the frame or terminal value wf_shade makes of this hit is
+            WF_LAUNCH(wf_group_tags, dim3(shade_blocks), block, 0, stream, S, L, *kind.groups());
         // Will the next bounce be sorted? Its own bound is not known yet (it arrives one bounce late) but cannot exceed this one, so: may it be.
         // Then this wf_shade writes the sort's input itself, key and slot at the physical slot of every ray it makes, and every slot it leaves
         // empty (the ends of the 64 sub-queue regions) must already hold a pad: RT_RAY_KEY_PAD in the compared bits, behind every real key
@@ -835,6 +856,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind
         L.paths_in = L.paths_out;
         L.paths_out = t;
     }
+    if (kind.groups()) // before wf_fold, which overwrites the terminal values in sample_out
+        WF_LAUNCH(wf_fold_groups, dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, L, *kind.groups());
     WF_LAUNCH(wf_fold, dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, L);
     if (census_pending) { // ray_depth <= 2 (no bounce 2 to read it at): wait for bounce 0 only; the rest of the pass is queued behind it
         if ((e = hipEventSynchronize(hs->events[0])) != hipSuccess)

@@ -206,6 +206,49 @@ __global__ __launch_bounds__(256) void wf_fold(const WfLaunch L) {
     }
 }
 
+// The same fold once more for a pass of an accumulator with light groups (WfGroups; the rule: rt_abi.h rt_accum_attach_light_groups), before
+// wf_fold, which overwrites sample_out: V_g of every path, for all groups at once. One lane per path reads the terminal value and then each
+// frame level once, through wf_load_fold like wf_fold, and the byte tag of that level; group g's running value takes the terminal value or a
+// frame's emission where the tag equals g and (+0, +0, +0) elsewhere, in the float operations of wf_fold. A tag is only ever compared: a
+// stale one (WfGroups) stands beside a value that is exactly +0. The eight running values are named by constant indices of unrolled loops
+// (registers, no private array in memory); the loops run to RT_LIGHT_GROUP_MAX whatever G is, and only the G records are stored, group-major.
+__global__ __launch_bounds__(256) void wf_fold_groups(const WfLaunch L, const WfGroups Gr) {
+    for (uint32_t path = blockIdx.x * blockDim.x + threadIdx.x; path < L.n_paths; path += gridDim.x * blockDim.x) {
+        const RtF4 v = L.sample_out[path];
+        const V3 term = mk(v.x, v.y, v.z);
+        uint32_t nb = __float_as_uint(v.w);
+        const uint32_t t_tag = Gr.tag[wf_fold_index(L.n_paths, nb, path)];
+        V3 res[RT_LIGHT_GROUP_MAX];
+#pragma unroll
+        for (uint32_t g = 0; g < RT_LIGHT_GROUP_MAX; ++g)
+            res[g] = t_tag == g ? term : mk(0.f, 0.f, 0.f);
+        while (nb > 0) {
+            --nb;
+            V3 emission, scl;
+            wf_load_fold(L, nb, path, emission, scl);
+            const uint32_t tag = Gr.tag[wf_fold_index(L.n_paths, nb, path)];
+#pragma unroll
+            for (uint32_t g = 0; g < RT_LIGHT_GROUP_MAX; ++g) {
+                const V3 clr = res[g] * scl;
+                res[g] = (tag == g ? emission : mk(0.f, 0.f, 0.f)) + clr;
+            }
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < RT_LIGHT_GROUP_MAX; ++g) {
+            if (g < Gr.n_groups) { // wave-uniform
+                V3 r = res[g];
+                if (isnan_f(r.x))
+                    r.x = 0;
+                if (isnan_f(r.y))
+                    r.y = 0;
+                if (isnan_f(r.z))
+                    r.z = 0;
+                Gr.rec[wf_fold_index(L.n_paths, g, path)] = RtF4{r.x, r.y, r.z, 0.f};
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ resolve
 // render_pixel's `res += sanitize_nans(...)` loop (raytracer.h:621-625) for the samples of this pass, in sample order,
 // continuing the running sum of earlier passes; the final pass divides by the sample count (:626).
@@ -314,6 +357,27 @@ __global__ __launch_bounds__(256) void wf_resolve_features(const WfAccum A, cons
         F.normal_sum[3ull * p] = nr.x, F.normal_sum[3ull * p + 1] = nr.y, F.normal_sum[3ull * p + 2] = nr.z;
         F.depth_sum[p] = z;
         F.hits[p] = hits;
+    }
+}
+
+// The group sums of the same entries (WfGroups): the lane that owns the pixel adds its k records of every group onto GS_g,p in sample order,
+// one group after the other (G is a run-time value: the sums stay in memory, [g][p][3], and one V3 is live at a time). Runs before
+// wf_resolve_list of the pass and reads neither n_p nor the base count. `n_paths` is the pass's WfLaunch::n_paths, the stride of the records.
+__global__ __launch_bounds__(256) void wf_resolve_groups(const WfAccum A, const WfGroups Gr, uint32_t n_paths) {
+    const uint32_t *off = A.list_off + A.first_entry;
+    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
+        const uint32_t p = A.list_pix[A.first_entry + le];
+        const uint32_t k = off[le + 1] - off[le];
+        for (uint32_t g = 0; g < Gr.n_groups; ++g) {
+            float *dst = Gr.sum + 3ull * ((size_t)g * Gr.pixels + p);
+            V3 acc = ld3(dst);
+            const RtF4 *src = Gr.rec + wf_fold_index(n_paths, g, off[le] - off[0]);
+            for (uint32_t j = 0; j < k; ++j) {
+                const RtF4 v = src[j];
+                acc = acc + mk(v.x, v.y, v.z);
+            }
+            dst[0] = acc.x, dst[1] = acc.y, dst[2] = acc.z;
+        }
     }
 }
 
