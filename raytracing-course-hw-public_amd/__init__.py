@@ -923,6 +923,7 @@ class Accumulator:
     def __init__(self, scene: DeviceScene, width: int, height: int, camera=None, seed: int = 0, accum_flags: int = 0, sensor=None):
         self._scene = scene
         self.width, self.height = int(width), int(height)
+        self.id_slots = self.n_light_groups = 1  # K of read_ids(), G of the light-group reads: 1 until attach_ids / attach_light_groups
         self._h = C.c_void_p()
         if sensor is not None:
             _check(lib().rt_accum_create_sensor(scene._h, self.width, self.height, make_sensors([sensor]), int(accum_flags), C.byref(self._h)))
@@ -942,6 +943,24 @@ class Accumulator:
         p = RtParams(self.width, self.height, samples, RT_RNG_DEVICE, 0, 0, 1, 0,
                      (RT_FLAG_GLOBAL_BEST if global_best else 0) | (RT_FLAG_COUNTERS if counters else 0))
         return p, _apply_tuning(p, tuning)
+
+    def _zeros(self, dtype, *tail) -> np.ndarray:
+        return np.zeros((self.height, self.width) + tail, dtype=dtype)
+
+    def _state(self, call, **arrays) -> dict:
+        """name -> a zeroed (H, W, *tail) array per `arrays` (name=(dtype, *tail)), filled by call(*pointers) in that order."""
+        out = {k: self._zeros(*spec) for k, spec in arrays.items()}
+        _check(call(*[(fptr if a.dtype == np.float32 else u32ptr)(a) for a in out.values()]))
+        return out
+
+    def _output(self, call, dtype=np.float32, tail=(3,), device_out=None):
+        """The one output of call(flags, pointer): a new (H, W, *tail) array, or with `device_out` (a device pointer, RT_FLAG_DEVICE_FB) None."""
+        if device_out:
+            _check(call(RT_FLAG_DEVICE_FB, C.c_void_p(device_out)))
+            return None
+        out = self._zeros(dtype, *tail)
+        _check(call(0, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def render(self, samples: int, global_best: bool = False, counters: bool = False, **tuning) -> dict:
         """rt_accum_render: `samples` more samples for every pixel. `tuning`: as DeviceScene.run_raytracer. Returns the stats dict."""
@@ -965,48 +984,23 @@ class Accumulator:
 
     def image(self, rgb8: bool = False) -> np.ndarray:
         """The resolved image S / n: (H, W, 3) float32, or the device film's uint8 image with `rgb8`."""
-        if rgb8:
-            img = np.zeros((self.height, self.width, 3), dtype=np.uint8)
-            _check(lib().rt_accum_resolve_rgb8(self._h, 0, img.ctypes.data_as(C.c_void_p)))
-            return img
-        fb = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(lib().rt_accum_resolve(self._h, 0, fb.ctypes.data_as(C.c_void_p)))
-        return fb
+        fn = lib().rt_accum_resolve_rgb8 if rgb8 else lib().rt_accum_resolve
+        return self._output(lambda flags, p: fn(self._h, flags, p), np.uint8 if rgb8 else np.float32)
 
     def read(self) -> dict:
         """The state: "sum" and "even_sum" (H, W, 3) float32, "samples" (H, W) uint32, "error" (H, W) float32 (the last judge's)."""
-        out = {
-            "sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
-            "even_sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
-            "samples": np.zeros((self.height, self.width), dtype=np.uint32),
-            "error": np.zeros((self.height, self.width), dtype=np.float32),
-        }
-        _check(lib().rt_accum_read(self._h, fptr(out["sum"]), fptr(out["even_sum"]), u32ptr(out["samples"]), fptr(out["error"])))
-        return out
+        return self._state(lambda *p: lib().rt_accum_read(self._h, *p), sum=(np.float32, 3), even_sum=(np.float32, 3), samples=(np.uint32,), error=(np.float32,))
 
     def read_features(self) -> dict:
         """The raw first-hit sums (rt_accum_read_features): "albedo_sum" and "normal_sum" (H, W, 3) float32, "depth_sum" (H, W) float32,
         "hits" (H, W) uint32. Needs accumulator(features=True)."""
-        out = {
-            "albedo_sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
-            "normal_sum": np.zeros((self.height, self.width, 3), dtype=np.float32),
-            "depth_sum": np.zeros((self.height, self.width), dtype=np.float32),
-            "hits": np.zeros((self.height, self.width), dtype=np.uint32),
-        }
-        _check(lib().rt_accum_read_features(self._h, fptr(out["albedo_sum"]), fptr(out["normal_sum"]), fptr(out["depth_sum"]), u32ptr(out["hits"])))
-        return out
+        return self._state(lambda *p: lib().rt_accum_read_features(self._h, *p), albedo_sum=(np.float32, 3), normal_sum=(np.float32, 3), depth_sum=(np.float32,),
+                           hits=(np.uint32,))
 
     def features(self) -> dict:
         """The feature means (rt_accum_resolve_features): "albedo" = AS / n and "normal" = NS / n (not renormalised), (H, W, 3) float32;
         "depth" = ZS / h (0 where no sample hit), (H, W) float32."""
-        out = {
-            "albedo": np.zeros((self.height, self.width, 3), dtype=np.float32),
-            "normal": np.zeros((self.height, self.width, 3), dtype=np.float32),
-            "depth": np.zeros((self.height, self.width), dtype=np.float32),
-        }
-        _check(lib().rt_accum_resolve_features(self._h, 0, out["albedo"].ctypes.data_as(C.c_void_p), out["normal"].ctypes.data_as(C.c_void_p),
-                                               out["depth"].ctypes.data_as(C.c_void_p)))
-        return out
+        return self._state(lambda *p: lib().rt_accum_resolve_features(self._h, 0, *p), albedo=(np.float32, 3), normal=(np.float32, 3), depth=(np.float32,))
 
     def denoise(self, rgb8: bool = False, **opts) -> np.ndarray:
         """rt_accum_denoise: the image filtered by the edge-avoiding a-trous filter that the feature means and the half-buffer noise estimate
@@ -1026,10 +1020,8 @@ class Accumulator:
                 setattr(o, k, int(v) | (o.flags if k == "flags" else 0))
             else:
                 raise TypeError(f"rt_denoise has no field {k!r}")
-        img = np.zeros((self.height, self.width, 3), dtype=np.uint8 if rgb8 else np.float32)
         fn = lib().rt_accum_denoise_rgb8 if rgb8 else lib().rt_accum_denoise
-        _check(fn(self._h, C.byref(o), 0, img.ctypes.data_as(C.c_void_p)))
-        return img
+        return self._output(lambda flags, p: fn(self._h, C.byref(o), flags, p), np.uint8 if rgb8 else np.float32)
 
     def attach_ids(self, kind="primitive", slots: int = 4, n_table: Optional[int] = None) -> None:
         """rt_accum_attach_ids: keep, per pixel, a table of `slots` (id, count) pairs of the ids its samples' primary rays hit, first seen first,
@@ -1056,14 +1048,7 @@ class Accumulator:
     def read_ids(self) -> dict:
         """The id tables (rt_accum_read_ids): "ids" and "counts" (H, W, K) uint32 in first-seen order (an empty slot reads id 0, count 0),
         "other" (H, W) uint32: the samples no slot was left for. Needs attach_ids."""
-        k = getattr(self, "id_slots", 1)
-        out = {
-            "ids": np.zeros((self.height, self.width, k), dtype=np.uint32),
-            "counts": np.zeros((self.height, self.width, k), dtype=np.uint32),
-            "other": np.zeros((self.height, self.width), dtype=np.uint32),
-        }
-        _check(lib().rt_accum_read_ids(self._h, u32ptr(out["ids"]), u32ptr(out["counts"]), u32ptr(out["other"])))
-        return out
+        return self._state(lambda *p: lib().rt_accum_read_ids(self._h, *p), ids=(np.uint32, self.id_slots), counts=(np.uint32, self.id_slots), other=(np.uint32,))
 
     def labels(self, device_out=None):
         """rt_accum_resolve_labels: (label (H, W) uint32: the id of each pixel's fullest slot, RT_ID_MISS where n = 0; coverage (H, W) float32:
@@ -1073,21 +1058,13 @@ class Accumulator:
             lp, cp = device_out
             _check(lib().rt_accum_resolve_labels(self._h, RT_FLAG_DEVICE_FB, C.c_void_p(lp or None), C.c_void_p(cp or None)))
             return None, None
-        label = np.zeros((self.height, self.width), dtype=np.uint32)
-        cov = np.zeros((self.height, self.width), dtype=np.float32)
-        _check(lib().rt_accum_resolve_labels(self._h, 0, label.ctypes.data_as(C.c_void_p), cov.ctypes.data_as(C.c_void_p)))
-        return label, cov
+        return tuple(self._state(lambda *p: lib().rt_accum_resolve_labels(self._h, 0, *p), label=(np.uint32,), coverage=(np.float32,)).values())
 
     def matte(self, ids, device_out: Optional[int] = None):
         """rt_accum_resolve_matte: (H, W) float32, the share of each pixel's samples whose id is one of `ids` (1..4096 of them; duplicates count
         once), as far as the pixel's slots hold it. `device_out`: a device pointer that receives it in HBM; then None is returned."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
-        if device_out:
-            _check(lib().rt_accum_resolve_matte(self._h, RT_FLAG_DEVICE_FB, u32ptr(ids), ids.size, C.c_void_p(device_out)))
-            return None
-        out = np.zeros((self.height, self.width), dtype=np.float32)
-        _check(lib().rt_accum_resolve_matte(self._h, 0, u32ptr(ids), ids.size, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._output(lambda flags, p: lib().rt_accum_resolve_matte(self._h, flags, u32ptr(ids), ids.size, p), tail=(), device_out=device_out)
 
     def attach_light_groups(self, material_group, background=None, n_groups: Optional[int] = None, n_materials: Optional[int] = None) -> None:
         """rt_accum_attach_light_groups: keep, per pixel, one more sum for each of `n_groups` light groups (1..8): the part of the pixel's
@@ -1115,25 +1092,20 @@ class Accumulator:
     def read_light_groups(self) -> np.ndarray:
         """The group sums GS (rt_accum_read_light_groups): (G, H, W, 3) float32, GS[g] the sum over each pixel's samples of the part of their
         radiance that group g's emitters produced. Needs attach_light_groups."""
-        out = np.zeros((getattr(self, "n_light_groups", 1), self.height, self.width, 3), dtype=np.float32)
+        out = np.zeros((self.n_light_groups, self.height, self.width, 3), dtype=np.float32)
         _check(lib().rt_accum_read_light_groups(self._h, fptr(out)))
         return out
 
     def light_group(self, g: int, device_out: Optional[int] = None):
         """rt_accum_resolve_light_group: the image of group g alone, GS[g] / n: (H, W, 3) float32. `device_out`: a device pointer that
         receives it in HBM (RT_FLAG_DEVICE_FB); then None is returned."""
-        if device_out:
-            _check(lib().rt_accum_resolve_light_group(self._h, int(g), RT_FLAG_DEVICE_FB, C.c_void_p(device_out)))
-            return None
-        fb = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        _check(lib().rt_accum_resolve_light_group(self._h, int(g), 0, fb.ctypes.data_as(C.c_void_p)))
-        return fb
+        return self._output(lambda flags, p: lib().rt_accum_resolve_light_group(self._h, int(g), flags, p), device_out=device_out)
 
     def light_mix(self, weights, rgb8: bool = False, device_out: Optional[int] = None):
         """rt_accum_resolve_light_mix: the image relit, sum over g of (GS[g] / n) * weights[g]: `weights` is (G, 3), or (G,) for one factor per
         group. (H, W, 3) float32, or the device film's uint8 image with `rgb8`. `device_out`: a device pointer that receives it in HBM
         (RT_FLAG_DEVICE_FB); then None is returned."""
-        G = getattr(self, "n_light_groups", 1)
+        G = self.n_light_groups
         w = np.asarray(weights, dtype=np.float32)
         if w.shape == (G,):
             w = np.repeat(w[:, None], 3, axis=1)
@@ -1141,12 +1113,7 @@ class Accumulator:
             raise ValueError(f"light_mix: weights must have shape ({G}, 3) or ({G},), not {w.shape}")
         w = np.ascontiguousarray(w)
         fn = lib().rt_accum_resolve_light_mix_rgb8 if rgb8 else lib().rt_accum_resolve_light_mix
-        if device_out:
-            _check(fn(self._h, fptr(w), RT_FLAG_DEVICE_FB, C.c_void_p(device_out)))
-            return None
-        img = np.zeros((self.height, self.width, 3), dtype=np.uint8 if rgb8 else np.float32)
-        _check(fn(self._h, fptr(w), 0, img.ctypes.data_as(C.c_void_p)))
-        return img
+        return self._output(lambda flags, p: fn(self._h, fptr(w), flags, p), np.uint8 if rgb8 else np.float32, device_out=device_out)
 
     def close(self) -> None:
         if self._h:

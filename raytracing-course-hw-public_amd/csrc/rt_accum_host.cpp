@@ -1,4 +1,5 @@
-// rt_accum_host.cpp — the host side of the accumulators (rt_abi.h rt_accum_*; their kernels are rt_accum.hip).
+// rt_accum_host.cpp — the host side of the accumulators (rt_abi.h rt_accum_*; their kernels are rt_accum.hip): create and destroy, the
+// rounds of rt_accum_render*, the image and the state. The optional layers' own entry points are rt_accum_layers.cpp.
 //
 // An accumulator owns its per-pixel state (S, E, n, err, the round's target and list, about 64 B per pixel) and one camera record; it
 // borrows the scene's stream, its wavefront workspace and its staging block (rt_call_io.h). Every call ends with the stream synchronised, so an
@@ -7,39 +8,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "rt_scene_impl.h"
-
-struct rt_accum {
-    rt_scene *scene = nullptr;
-    uint32_t width = 0, height = 0;
-    WfSensor sensor{};            // its camera: rt_accum_create_sensor's, or the pinhole record of {camera, seed} (host copy of d_sensor)
-    WfSensor *d_sensor = nullptr; // WfLaunch::sensors of its passes: the one record
-    rt::AccumRound R{};
-    rt::DevArena owned{16};
-    rt::PacketPolicy pkt; // of its own passes, kept apart from rt_render's
-    bool features = false; // RT_ACCUM_FEATURES: F holds the four first-hit sums (F.rec is the scene's, bound per fill)
-    WfFeat F{};
-    rt::DenoiseBufs D{};   // rt_accum_denoise's workspace (64 B per pixel), allocated by its first call
-    bool ids = false;      // rt_accum_attach_ids: I holds the per-pixel id tables (I.rec is the scene's, bound per fill)
-    WfIds I{};
-    rt::DevBuf<uint32_t> matte_set; // rt_accum_resolve_matte's id set on the device
-    bool groups = false;   // rt_accum_attach_light_groups: G holds the group sums and the material table (G.rec and G.tag are the scene's, bound per fill)
-    WfGroups G{};
-    bool has_samples = false; // a call has queued a pass of this accumulator: ids and light groups can no longer be attached
-    ~rt_accum() {
-        (void)hipSetDevice(scene->device);
-        (void)hipStreamSynchronize(scene->stream); // `owned` frees after this body: on this device, behind this synchronise
-        if (counted)
-            --scene->live_accums;
-    }
-    bool counted = false; // it is one of scene->live_accums
-};
-
-template <class T> static int accum_alloc(rt_accum *a, size_t bytes, T **ptr, const char *fn) {
-    if (hipError_t e = a->owned.alloc_bytes(ptr, bytes); e != hipSuccess)
-        return rt::hip_fail(e, fn);
-    return RT_OK;
-}
+#include "rt_accum_impl.h"
 
 extern "C" int rt_accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_camera *camera, uint64_t seed, rt_accum **out) {
     return rt_accum_create_ex(s, width, height, camera, seed, 0u, out);
@@ -69,7 +38,7 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
         a->sensor = rt::make_sensor(camera ? *camera : s->cam, seed, width, height);
     }
     const size_t n = (size_t)width * height;
-    auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int { return accum_alloc(a.get(), bytes, ptr, "rt_accum_create"); };
+    auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int { return rt::accum_alloc(a.get(), bytes, ptr, "rt_accum_create"); };
     rt::AccumRound &R = a->R;
     R.width = width;
     R.height = height;
@@ -82,7 +51,7 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
         (rc = alloc(sizeof(WfSensor), &a->d_sensor)) != RT_OK)
         return rc;
     if (accum_flags & RT_ACCUM_FEATURES) {
-        WfFeat &F = a->F;
+        WfFeat F{};
         if ((rc = alloc(12 * n, &F.albedo_sum)) != RT_OK || (rc = alloc(12 * n, &F.normal_sum)) != RT_OK || (rc = alloc(4 * n, &F.depth_sum)) != RT_OK ||
             (rc = alloc(4 * n, &F.hits)) != RT_OK)
             return rc;
@@ -90,7 +59,7 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
         HIP_TRY(hipMemsetAsync(F.normal_sum, 0, 12 * n, s->stream));
         HIP_TRY(hipMemsetAsync(F.depth_sum, 0, 4 * n, s->stream));
         HIP_TRY(hipMemsetAsync(F.hits, 0, 4 * n, s->stream));
-        a->features = true;
+        a->features = F;
     }
     HIP_TRY(hipMemsetAsync(R.sum, 0, 12 * n, s->stream)); // +0.0
     HIP_TRY(hipMemsetAsync(R.even_sum, 0, 12 * n, s->stream));
@@ -145,6 +114,9 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
     const uint64_t max_paths = rt::wavefront_max_paths(s, p);
     // the largest k of one list: a pass holds at least one whole entry, and a list's sample prefix stays below 2^32 (rt_accum.hip)
     const uint32_t chunk_cap = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(max_paths, 0xFFFFFFFFull / n_pix));
+    WfFeat *const F = rt::layer_ptr(a->features); // the layers it keeps (null: not this one): their per-path records are bound per fill
+    WfIds *const I = rt::layer_ptr(a->ids);
+    WfGroups *const G = rt::layer_ptr(a->groups);
     WfLaunch W{};
     W.width = a->width;
     W.height = a->height;
@@ -176,22 +148,8 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
             const uint64_t cap = std::min<uint64_t>((uint64_t)std::min(per_pass, tot[0]) * C, tot[1]);
             if (int rc = s->ensure_wavefront(cap, std::max<uint64_t>(s->wf_pixels_cap, 1), s->dev.ray_depth); rc != RT_OK)
                 return rc;
-            if (a->features) {
-                if (int rc = s->ensure_features(); rc != RT_OK)
-                    return rc;
-                a->F.rec = s->wf_feat.get();
-            }
-            if (a->ids) {
-                if (int rc = s->ensure_ids(); rc != RT_OK)
-                    return rc;
-                a->I.rec = s->wf_ids.get();
-            }
-            if (a->groups) {
-                if (int rc = s->ensure_groups(a->G.n_groups); rc != RT_OK)
-                    return rc;
-                a->G.rec = s->wf_group_rec.get();
-                a->G.tag = s->wf_group_tag.get();
-            }
+            if (int rc = s->bind_layer_records(F, I, G); rc != RT_OK)
+                return rc;
             s->wf_bind(W);
             W.fb = nullptr;
             W.accum = nullptr; // wf_resolve does not run on an accumulator pass
@@ -201,7 +159,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
                 a->has_samples = true;
-                const rt::WfPassKind kind = rt::WfPassKind::list(A, a->features ? &a->F : nullptr, a->ids ? &a->I : nullptr, a->groups ? &a->G : nullptr, a->sensor);
+                const rt::WfPassKind kind = rt::WfPassKind::list(A, rt::WfLayers{F, I, G}, a->sensor);
                 HIP_TRY(rt::launch_pass(s, p, a->pkt, W, kind, rt::WfPassStep{true, true, stats != nullptr}));
                 passes += 1;
                 packet_passes += W.use_packet;
@@ -274,417 +232,17 @@ extern "C" int rt_accum_render_adaptive(rt_accum *acc, const rt_params *params, 
     return accum_run(acc, params, ad, rounds, stats);
 }
 
-extern "C" int rt_accum_resolve(rt_accum *acc, uint32_t flags, float *fb_rgb) {
-    if (!acc || !fb_rgb || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve: null argument or flags other than RT_FLAG_DEVICE_FB");
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    float *d_fb;
-    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
-    return io.run([&]() -> int {
-        HIP_TRY(rt::launch_accum_image(acc->R, d_fb, s->stream));
-        return RT_OK;
-    });
+template <class Out> static int resolve(rt_accum *acc, uint32_t flags, Out *out, const char *fn) {
+    if (!acc || !out || rt::other_flags(flags))
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null argument or flags other than RT_FLAG_DEVICE_FB");
+    return rt::accum_image(acc, flags, out, [&](float *d_fb) { return rt::launch_accum_image(acc->R, d_fb, acc->scene->stream); });
 }
-
-// `image` fills an internal float image; the film (image.h:49-82, as rt_render_rgb8) makes the rgb8 destination of it
-template <class Image> static int film_image(rt_accum *acc, uint32_t flags, uint8_t *rgb8, Image image) {
-    rt_scene *s = acc->scene;
-    if (int rc = s->ensure_film(); rc != RT_OK)
-        return rc;
-    const uint32_t n = acc->width * acc->height;
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    float *d_fb;
-    uint8_t *d_rgb8;
-    io.scratch(&d_fb, 12ull * n);
-    io.out(&d_rgb8, rgb8, 3ull * n);
-    return io.run([&]() -> int {
-        HIP_TRY(image(d_fb));
-        HIP_TRY(rt::launch_film(d_fb, d_rgb8, n, 0, 1, n, s->film_table.get(), s->stream));
-        return RT_OK;
-    });
-}
-
-extern "C" int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb8) {
-    if (!acc || !rgb8 || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_rgb8: null argument or flags other than RT_FLAG_DEVICE_FB");
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    return film_image(acc, flags, rgb8, [&](float *d_fb) { return rt::launch_accum_image(acc->R, d_fb, s->stream); });
-}
-
-// the accumulator's own arrays, each to a host destination that is not null
-struct ReadBack {
-    void *host;
-    const void *dev;
-    size_t bytes;
-};
-static int read_back(rt_scene *s, std::initializer_list<ReadBack> list) {
-    return rt::queue_and_wait(s->stream, [&]() -> int {
-        for (const ReadBack &r : list)
-            if (r.host)
-                HIP_TRY(hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, s->stream));
-        return RT_OK;
-    });
-}
+extern "C" int rt_accum_resolve(rt_accum *acc, uint32_t flags, float *fb_rgb) { return resolve(acc, flags, fb_rgb, "rt_accum_resolve"); }
+extern "C" int rt_accum_resolve_rgb8(rt_accum *acc, uint32_t flags, uint8_t *rgb8) { return resolve(acc, flags, rgb8, "rt_accum_resolve_rgb8"); }
 
 extern "C" int rt_accum_read(rt_accum *acc, float *sum_rgb, float *even_sum_rgb, uint32_t *samples, float *error) {
-    if (!acc)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_read: null accumulator");
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = rt::accum_entry(acc, "rt_accum_read", rt::AccumNeed::NONE); rc != RT_OK)
+        return rc;
     const size_t n = (size_t)acc->width * acc->height;
-    return read_back(s, {{sum_rgb, acc->R.sum, 12 * n}, {even_sum_rgb, acc->R.even_sum, 12 * n}, {samples, acc->R.count, 4 * n}, {error, acc->R.err, 4 * n}});
-}
-
-// ---- first-hit features and the denoiser (rt_abi.h RT_ACCUM_FEATURES, rt_accum_denoise)
-static int feature_check(const rt_accum *acc, const char *fn) {
-    if (!acc)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null accumulator");
-    if (!acc->features)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator was created without RT_ACCUM_FEATURES");
-    return RT_OK;
-}
-
-extern "C" int rt_accum_read_features(rt_accum *acc, float *albedo_sum, float *normal_sum, float *depth_sum, uint32_t *hits) {
-    if (int rc = feature_check(acc, "rt_accum_read_features"); rc != RT_OK)
-        return rc;
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)acc->width * acc->height;
-    return read_back(s, {{albedo_sum, acc->F.albedo_sum, 12 * n}, {normal_sum, acc->F.normal_sum, 12 * n}, {depth_sum, acc->F.depth_sum, 4 * n}, {hits, acc->F.hits, 4 * n}});
-}
-
-extern "C" int rt_accum_resolve_features(rt_accum *acc, uint32_t flags, float *albedo, float *normal, float *depth) {
-    if (int rc = feature_check(acc, "rt_accum_resolve_features"); rc != RT_OK)
-        return rc;
-    if (flags & ~(uint32_t)RT_FLAG_DEVICE_FB)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_features: flags other than RT_FLAG_DEVICE_FB");
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)acc->width * acc->height;
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    float *d_a, *d_n, *d_z; // on a host call all three are computed; a null destination is not copied
-    io.out(&d_a, albedo, 12 * n);
-    io.out(&d_n, normal, 12 * n);
-    io.out(&d_z, depth, 4 * n);
-    return io.run([&]() -> int {
-        HIP_TRY(rt::launch_accum_feature_means(acc->R, acc->F, d_a, d_n, d_z, s->stream));
-        return RT_OK;
-    });
-}
-
-// the defaults of rt_denoise: chosen by the sweep recorded in profiles/denoise_quality.txt
-static int denoise_options(const rt_accum *acc, const rt_denoise *opt, uint32_t flags, const void *out, const char *fn, rt::DenoiseOpt *O) {
-    if (int rc = feature_check(acc, fn); rc != RT_OK)
-        return rc;
-    if (!out || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null buffer or flags other than RT_FLAG_DEVICE_FB");
-    const rt_denoise zero{};
-    const rt_denoise &o = opt ? *opt : zero;
-    for (uint32_t r : o.reserved)
-        if (r != 0)
-            return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": reserved fields must be 0");
-    if (o.iterations > 8u || o.normal_sharpness > 8u || (o.flags & ~(uint32_t)RT_DENOISE_NO_DEMODULATE))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": iterations and normal_sharpness are at most 8; unknown rt_denoise.flags bit");
-    if (!(o.sigma_color >= 0.0f) || std::isinf(o.sigma_color) || !(o.sigma_depth >= 0.0f) || std::isinf(o.sigma_depth))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": sigma_color and sigma_depth must be finite and >= 0");
-    O->iterations = o.iterations ? o.iterations : 5u;
-    O->sigma_color = o.sigma_color != 0.0f ? o.sigma_color : 8.0f;
-    O->sigma_depth = o.sigma_depth != 0.0f ? o.sigma_depth : 0.5f;
-    O->sharpness = o.normal_sharpness ? o.normal_sharpness : 3u;
-    O->demodulate = (o.flags & RT_DENOISE_NO_DEMODULATE) ? 0u : 1u;
-    return RT_OK;
-}
-
-static int denoise_buffers(rt_accum *acc, const char *fn) {
-    if (acc->D.guide)
-        return RT_OK;
-    const size_t n = (size_t)acc->width * acc->height;
-    int rc;
-    if ((rc = accum_alloc(acc, 16 * n, &acc->D.sig[0], fn)) != RT_OK || (rc = accum_alloc(acc, 16 * n, &acc->D.sig[1], fn)) != RT_OK ||
-        (rc = accum_alloc(acc, 16 * n, &acc->D.den, fn)) != RT_OK)
-        return rc;
-    return accum_alloc(acc, 32 * n, &acc->D.guide, fn); // last: its pointer says the workspace is complete
-}
-
-extern "C" int rt_accum_denoise(rt_accum *acc, const rt_denoise *opt, uint32_t flags, float *fb_rgb) {
-    rt::DenoiseOpt O{};
-    if (int rc = denoise_options(acc, opt, flags, fb_rgb, "rt_accum_denoise", &O); rc != RT_OK)
-        return rc;
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    if (int rc = denoise_buffers(acc, "rt_accum_denoise"); rc != RT_OK)
-        return rc;
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    float *d_fb;
-    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
-    return io.run([&]() -> int {
-        HIP_TRY(rt::launch_denoise(acc->R, acc->F, acc->D, O, d_fb, s->stream));
-        return RT_OK;
-    });
-}
-
-extern "C" int rt_accum_denoise_rgb8(rt_accum *acc, const rt_denoise *opt, uint32_t flags, uint8_t *rgb8) {
-    rt::DenoiseOpt O{};
-    if (int rc = denoise_options(acc, opt, flags, rgb8, "rt_accum_denoise_rgb8", &O); rc != RT_OK)
-        return rc;
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    if (int rc = denoise_buffers(acc, "rt_accum_denoise_rgb8"); rc != RT_OK)
-        return rc;
-    return film_image(acc, flags, rgb8, [&](float *d_fb) { return rt::launch_denoise(acc->R, acc->F, acc->D, O, d_fb, s->stream); });
-}
-
-// ---- id mattes (rt_abi.h rt_accum_attach_ids: the rule; the kernels: rt_wavefront.hip wf_ids / wf_resolve_ids, rt_accum.hip)
-extern "C" int rt_accum_attach_ids(rt_accum *acc, const rt_id_desc *desc) {
-    if (!acc || !desc)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: null argument");
-    rt_scene *s = acc->scene;
-    const bool user = desc->kind == RT_ID_USER, device_table = (desc->flags & RT_FLAG_DEVICE_FB) != 0;
-    if (desc->kind > (uint32_t)RT_ID_USER)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: unknown kind " + std::to_string(desc->kind));
-    if (desc->slots > RT_ID_MAX_SLOTS)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: slots must be 0 (= 4) or 1..16");
-    if (desc->reserved[0] != 0 || desc->reserved[1] != 0 || (desc->flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: reserved fields must be 0; flags other than RT_FLAG_DEVICE_FB");
-    const uint32_t n_table = s->dev.n_triangles + s->dev.n_prims;
-    if (user && (!desc->table || desc->n_table != n_table))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: RT_ID_USER needs a table of n_triangles + n_primitives = " + std::to_string(n_table) + " ids");
-    if (!user && (desc->table || desc->n_table != 0))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: only RT_ID_USER takes a table");
-    if (user && device_table && (reinterpret_cast<uintptr_t>(desc->table) & 3u))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: the device table must be 4-byte aligned");
-    if (acc->ids)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: the accumulator already has ids");
-    if (acc->has_samples)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_attach_ids: the accumulator already holds samples; attach ids before the first render");
-    HIP_TRY(hipSetDevice(s->device));
-    WfIds I{};
-    I.kind = desc->kind;
-    I.k = desc->slots ? desc->slots : 4u;
-    I.pixels = acc->width * acc->height;
-    const size_t n = I.pixels, words = n * I.k;
-    uint32_t *table = nullptr;
-    int rc;
-    if ((rc = accum_alloc(acc, 4 * words, &I.slot_id, "rt_accum_attach_ids")) != RT_OK || (rc = accum_alloc(acc, 4 * words, &I.slot_count, "rt_accum_attach_ids")) != RT_OK ||
-        (rc = accum_alloc(acc, 4 * n, &I.other, "rt_accum_attach_ids")) != RT_OK ||
-        (user && (rc = accum_alloc(acc, 4 * (size_t)n_table, &table, "rt_accum_attach_ids")) != RT_OK))
-        return rc; // what was allocated stays with the accumulator's arena, unused, until rt_accum_destroy
-    auto queue = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(I.slot_id, 0, 4 * words, s->stream));
-        HIP_TRY(hipMemsetAsync(I.slot_count, 0, 4 * words, s->stream));
-        HIP_TRY(hipMemsetAsync(I.other, 0, 4 * n, s->stream));
-        if (user && n_table)
-            HIP_TRY(hipMemcpyAsync(table, desc->table, 4 * (size_t)n_table, device_table ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-        return RT_OK;
-    };
-    if ((rc = rt::queue_and_wait(s->stream, queue)) != RT_OK)
-        return rc;
-    I.table = table;
-    acc->I = I;
-    acc->ids = true;
-    return RT_OK;
-}
-
-static int ids_check(const rt_accum *acc, const char *fn) {
-    if (!acc)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null accumulator");
-    if (!acc->ids)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no ids (rt_accum_attach_ids)");
-    return RT_OK;
-}
-
-extern "C" int rt_accum_read_ids(rt_accum *acc, uint32_t *ids, uint32_t *counts, uint32_t *other) {
-    if (int rc = ids_check(acc, "rt_accum_read_ids"); rc != RT_OK)
-        return rc;
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = acc->I.pixels, K = acc->I.k;
-    std::vector<uint32_t> slot_major; // the device keeps slot j of pixel p at j * pixels + p
-    for (auto [dst, src] : {std::pair{ids, acc->I.slot_id}, std::pair{counts, acc->I.slot_count}}) {
-        if (!dst)
-            continue;
-        slot_major.resize(n * K);
-        if (int rc = read_back(s, {{slot_major.data(), src, 4 * n * K}}); rc != RT_OK)
-            return rc;
-        for (size_t p = 0; p < n; ++p)
-            for (size_t j = 0; j < K; ++j)
-                dst[p * K + j] = slot_major[j * n + p];
-    }
-    return read_back(s, {{other, acc->I.other, 4 * n}});
-}
-
-extern "C" int rt_accum_resolve_labels(rt_accum *acc, uint32_t flags, uint32_t *label, float *coverage) {
-    if (int rc = ids_check(acc, "rt_accum_resolve_labels"); rc != RT_OK)
-        return rc;
-    if (flags & ~(uint32_t)RT_FLAG_DEVICE_FB)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_labels: flags other than RT_FLAG_DEVICE_FB");
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    uint32_t *d_label;
-    float *d_cov;
-    io.out(&d_label, label, 4 * (size_t)acc->I.pixels);
-    io.out(&d_cov, coverage, 4 * (size_t)acc->I.pixels);
-    return io.run([&]() -> int {
-        HIP_TRY(rt::launch_accum_labels(acc->R, acc->I, d_label, d_cov, s->stream));
-        return RT_OK;
-    });
-}
-
-extern "C" int rt_accum_resolve_matte(rt_accum *acc, uint32_t flags, const uint32_t *ids, uint32_t n_ids, float *matte) {
-    if (int rc = ids_check(acc, "rt_accum_resolve_matte"); rc != RT_OK)
-        return rc;
-    if (!ids || !matte || n_ids == 0 || n_ids > 4096u || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_matte: null ids or matte, n_ids outside 1..4096, or flags other than RT_FLAG_DEVICE_FB");
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    std::vector<uint32_t> set(ids, ids + n_ids); // sorted, each id once: the kernel's binary search
-    std::sort(set.begin(), set.end());
-    set.erase(std::unique(set.begin(), set.end()), set.end());
-    HIP_TRY(acc->matte_set.reserve(set.size()));
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    float *d_matte;
-    io.out(&d_matte, matte, 4 * (size_t)acc->I.pixels);
-    return io.run([&]() -> int { // `set` is a local: nothing of this may be in flight when it dies
-        HIP_TRY(hipMemcpyAsync(acc->matte_set.get(), set.data(), 4 * set.size(), hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(rt::launch_accum_matte(acc->R, acc->I, acc->matte_set.get(), (uint32_t)set.size(), d_matte, s->stream));
-        return RT_OK;
-    });
-}
-
-// ---- light groups (rt_abi.h rt_accum_attach_light_groups: the rule; the kernels: rt_wavefront.hip wf_group_tags, rt_wf_stages.h wf_fold_groups /
-// wf_resolve_groups, rt_accum.hip)
-extern "C" int rt_accum_attach_light_groups(rt_accum *acc, const rt_light_group_desc *desc) {
-    const char *fn = "rt_accum_attach_light_groups";
-    if (!acc || !desc)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null argument");
-    rt_scene *s = acc->scene;
-    const uint32_t G = desc->n_groups, n_mats = (uint32_t)s->prep->mats.size();
-    const bool device_table = (desc->flags & RT_FLAG_DEVICE_FB) != 0;
-    auto in_range = [G](uint32_t g) { return g < G || g == RT_LIGHT_GROUP_NONE; };
-    if (G == 0 || G > RT_LIGHT_GROUP_MAX)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": n_groups must be 1.." + std::to_string(RT_LIGHT_GROUP_MAX));
-    if (desc->reserved[0] != 0 || desc->reserved[1] != 0 || (desc->flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": reserved fields must be 0; flags other than RT_FLAG_DEVICE_FB");
-    if (!desc->material_group || desc->n_materials != n_mats)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": material_group must hold the scene's " + std::to_string(n_mats) + " materials");
-    if (device_table && (reinterpret_cast<uintptr_t>(desc->material_group) & 3u))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the device table must be 4-byte aligned");
-    if (!in_range(desc->background_group))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": background_group must be below n_groups, or RT_LIGHT_GROUP_NONE");
-    if (acc->groups)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator already has light groups");
-    if (acc->has_samples)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator already holds samples; attach light groups before the first render");
-    HIP_TRY(hipSetDevice(s->device));
-    std::vector<uint32_t> words(n_mats); // the entries are checked on the host, wherever the table lives
-    if (device_table) {
-        if (int rc = rt::queue_and_wait(s->stream, [&]() -> int {
-                HIP_TRY(hipMemcpyAsync(words.data(), desc->material_group, 4 * (size_t)n_mats, hipMemcpyDeviceToHost, s->stream));
-                return RT_OK;
-            });
-            rc != RT_OK)
-            return rc;
-    } else {
-        std::copy(desc->material_group, desc->material_group + n_mats, words.begin());
-    }
-    std::vector<uint8_t> bytes(n_mats);
-    for (uint32_t m = 0; m < n_mats; ++m) {
-        if (!in_range(words[m]))
-            return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": material_group[" + std::to_string(m) + "] is neither below n_groups nor RT_LIGHT_GROUP_NONE");
-        bytes[m] = words[m] == RT_LIGHT_GROUP_NONE ? (uint8_t)WF_GROUP_NONE : (uint8_t)words[m];
-    }
-    WfGroups W{};
-    W.n_groups = G;
-    W.background = desc->background_group == RT_LIGHT_GROUP_NONE ? WF_GROUP_NONE : desc->background_group;
-    W.pixels = acc->width * acc->height;
-    const size_t sum_bytes = 12 * (size_t)G * W.pixels;
-    uint8_t *table = nullptr;
-    int rc;
-    if ((rc = accum_alloc(acc, sum_bytes, &W.sum, fn)) != RT_OK || (rc = accum_alloc(acc, n_mats, &table, fn)) != RT_OK)
-        return rc; // what was allocated stays with the accumulator's arena, unused, until rt_accum_destroy
-    auto queue = [&]() -> int { // `bytes` is a local: nothing of this may be in flight when it dies
-        HIP_TRY(hipMemsetAsync(W.sum, 0, sum_bytes, s->stream)); // +0.0
-        if (n_mats)
-            HIP_TRY(hipMemcpyAsync(table, bytes.data(), n_mats, hipMemcpyHostToDevice, s->stream));
-        return RT_OK;
-    };
-    if ((rc = rt::queue_and_wait(s->stream, queue)) != RT_OK)
-        return rc;
-    W.material_group = table;
-    acc->G = W;
-    acc->groups = true;
-    return RT_OK;
-}
-
-static int groups_check(const rt_accum *acc, const void *buffer, uint32_t flags, const char *fn) {
-    if (!acc)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null accumulator");
-    if (!acc->groups)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no light groups (rt_accum_attach_light_groups)");
-    if (!buffer || (flags & ~(uint32_t)RT_FLAG_DEVICE_FB))
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null buffer or flags other than RT_FLAG_DEVICE_FB");
-    return RT_OK;
-}
-
-extern "C" int rt_accum_read_light_groups(rt_accum *acc, float *group_sums) {
-    if (int rc = groups_check(acc, group_sums, 0u, "rt_accum_read_light_groups"); rc != RT_OK)
-        return rc;
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    return read_back(s, {{group_sums, acc->G.sum, 12 * (size_t)acc->G.n_groups * acc->G.pixels}});
-}
-
-extern "C" int rt_accum_resolve_light_group(rt_accum *acc, uint32_t group, uint32_t flags, float *fb_rgb) {
-    if (int rc = groups_check(acc, fb_rgb, flags, "rt_accum_resolve_light_group"); rc != RT_OK)
-        return rc;
-    if (group >= acc->G.n_groups)
-        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_resolve_light_group: group " + std::to_string(group) + " of " + std::to_string(acc->G.n_groups));
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    float *d_fb;
-    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
-    return io.run([&]() -> int {
-        HIP_TRY(rt::launch_accum_light_group(acc->R, acc->G, group, d_fb, s->stream));
-        return RT_OK;
-    });
-}
-
-// the G x 3 weights of a mix, as the kernel argument they travel in
-static int mix_weights(const rt_accum *acc, const float *weights, const char *fn, rt::LightMixWeights *w) {
-    if (!weights)
-        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null weights");
-    std::memset(w, 0, sizeof(*w));
-    std::memcpy(w->w, weights, 12 * (size_t)acc->G.n_groups);
-    return RT_OK;
-}
-
-extern "C" int rt_accum_resolve_light_mix(rt_accum *acc, const float *weights, uint32_t flags, float *fb_rgb) {
-    rt::LightMixWeights w;
-    int rc;
-    if ((rc = groups_check(acc, fb_rgb, flags, "rt_accum_resolve_light_mix")) != RT_OK || (rc = mix_weights(acc, weights, "rt_accum_resolve_light_mix", &w)) != RT_OK)
-        return rc;
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    rt::CallIo io(s->stream, s->staging, (flags & RT_FLAG_DEVICE_FB) != 0);
-    float *d_fb;
-    io.out(&d_fb, fb_rgb, (size_t)acc->width * acc->height * 12);
-    return io.run([&]() -> int {
-        HIP_TRY(rt::launch_accum_light_mix(acc->R, acc->G, w, d_fb, s->stream));
-        return RT_OK;
-    });
-}
-
-extern "C" int rt_accum_resolve_light_mix_rgb8(rt_accum *acc, const float *weights, uint32_t flags, uint8_t *rgb8) {
-    rt::LightMixWeights w;
-    int rc;
-    if ((rc = groups_check(acc, rgb8, flags, "rt_accum_resolve_light_mix_rgb8")) != RT_OK || (rc = mix_weights(acc, weights, "rt_accum_resolve_light_mix_rgb8", &w)) != RT_OK)
-        return rc;
-    rt_scene *s = acc->scene;
-    HIP_TRY(hipSetDevice(s->device));
-    return film_image(acc, flags, rgb8, [&](float *d_fb) { return rt::launch_accum_light_mix(acc->R, acc->G, w, d_fb, s->stream); });
+    return rt::read_back(acc, {{sum_rgb, acc->R.sum, 12 * n}, {even_sum_rgb, acc->R.even_sum, 12 * n}, {samples, acc->R.count, 4 * n}, {error, acc->R.err, 4 * n}});
 }

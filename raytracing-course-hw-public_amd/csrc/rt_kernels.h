@@ -76,13 +76,19 @@ struct WfHostSync {
 // A camera source is made of the call's camera table on the host (run_passes uploads it as WfLaunch::sensors), a list of its accumulator's one
 // camera record; both keep rt::single_origin of it (rt_sensor.cpp): the three floats every ray of the pass starts at, or null.
 const float *single_origin(const WfSensor *table, uint32_t n);
+// What a list pass keeps besides the sums (host only; all null: nothing): an accumulator's optional layers. wf_features and wf_ids run behind
+// bounce 0's closest hits, whose results are final there; wf_group_tags at every bounce, wf_fold_groups before wf_fold; then
+// wf_resolve_features, wf_resolve_ids and wf_resolve_groups, in that order, before wf_resolve_list.
+struct WfLayers {
+    const WfFeat *features;
+    const WfIds *ids;
+    const WfGroups *groups;
+};
 class WfPassKind {
 public:
     enum Source { CAMERAS, LIST, RAYS, BAKE };
     static WfPassKind cameras(const WfSensor *table, uint32_t n_views) { return WfPassKind(Cameras{table, n_views, single_origin(table, n_views)}); }
-    static WfPassKind list(const WfAccum &entries, const WfFeat *features, const WfIds *ids, const WfGroups *groups, const WfSensor &camera) {
-        return WfPassKind(List{entries, features, ids, groups, single_origin(&camera, 1)});
-    }
+    static WfPassKind list(const WfAccum &entries, const WfLayers &layers, const WfSensor &camera) { return WfPassKind(List{entries, layers, single_origin(&camera, 1)}); }
     static WfPassKind rays(const WfRays &rays) { return WfPassKind(rays); }
     static WfPassKind bake(const WfBake &bake) { return WfPassKind(bake); }
 
@@ -91,11 +97,7 @@ public:
     const WfAccum &entries() const { return std::get<List>(v).entries; }
     const WfRays &ray_buffer() const { return std::get<WfRays>(v); }
     const WfBake &bake_points() const { return std::get<WfBake>(v); }
-    // the launches behind bounce 0's closest hits, whose results are final there: a list's first-hit features and ids; null: none
-    const WfFeat *features() const { return source() == LIST ? std::get<List>(v).features : nullptr; }
-    const WfIds *ids() const { return source() == LIST ? std::get<List>(v).ids : nullptr; }
-    // the launches of a list with light groups: wf_group_tags at every bounce, wf_fold_groups before wf_fold, wf_resolve_groups; null: none
-    const WfGroups *groups() const { return source() == LIST ? std::get<List>(v).groups : nullptr; }
+    WfLayers layers() const { return source() == LIST ? std::get<List>(v).layers : WfLayers{}; } // of a list; every other source keeps none
     // the cameras of the pass: part of the packet policy's key (a caller's rays and bake points count as one)
     uint32_t n_views() const { return source() == CAMERAS ? std::get<Cameras>(v).n_views : 1u; }
     const WfSensor *camera_table() const { return source() == CAMERAS ? std::get<Cameras>(v).table : nullptr; } // [n_views], host; null: no table to upload
@@ -113,9 +115,7 @@ private:
     };
     struct List {
         WfAccum entries;
-        const WfFeat *features;
-        const WfIds *ids;
-        const WfGroups *groups;
+        WfLayers layers;
         const float *origin;
     };
     std::variant<Cameras, List, WfRays, WfBake> v; // in the order of Source

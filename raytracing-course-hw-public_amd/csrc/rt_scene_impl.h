@@ -1,6 +1,6 @@
 // rt_scene_impl.h — what the host files behind include/rt_abi.h share (internal): the definition of rt_scene and the few helpers
 // with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_rays.cpp (rt_render_rays*), rt_bake.cpp (rt_bake*, rt_lightmap_points),
-// rt_accum_host.cpp (rt_accum_*) and rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through
+// rt_accum_host.cpp and rt_accum_layers.cpp (rt_accum_*, over rt_accum_impl.h) and rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through
 // rt_group.h. The arrays of a call, on the host or in the caller's HBM, are declared on an rt::CallIo (rt_call_io.h) over the scene's one
 // staging block; its run() and timed_call below are the brackets every entry point queues its work in.
 #pragma once
@@ -202,30 +202,34 @@ struct rt_scene {
         return RT_OK;
     }
 
-    // the per-path feature records of a feature accumulator's passes (WfFeat::rec, 32 B per path): allocated the first time such an
-    // accumulator renders on this scene, and sized like the wavefront workspace (call after ensure_wavefront)
-    rt::DevBuf<RtF4> wf_feat; // two records per path
-    int ensure_features() {
-        if (hipError_t e = wf_feat.reserve(wf_paths_cap * 2); e != hipSuccess)
-            return rt::hip_fail(e, "feature records");
-        return RT_OK;
-    }
-    // the per-path id records of the passes of an accumulator with ids (WfIds::rec, 4 B per path): as the feature records
+    // The per-path records of an accumulator's layers (null: it keeps none), sized like the wavefront workspace and allocated the first time
+    // such an accumulator renders on this scene: two feature records per path (WfFeat::rec, 32 B), one id (WfIds::rec, 4 B), n_groups group
+    // records (WfGroups::rec, 16 B each) and one tag byte per path and frame level (WfGroups::tag). None needs its content kept or cleared
+    // (a stale tag is legal: WfGroups). Call after ensure_wavefront.
+    rt::DevBuf<RtF4> wf_feat;
     rt::DevBuf<uint32_t> wf_ids;
-    int ensure_ids() {
-        if (hipError_t e = wf_ids.reserve(wf_paths_cap); e != hipSuccess)
-            return rt::hip_fail(e, "id records");
-        return RT_OK;
-    }
-    // the per-path records of the passes of an accumulator with light groups (WfGroups::rec, n_groups x 16 B per path, and WfGroups::tag, one
-    // byte per path and frame level): as the feature records. Neither needs its content kept or cleared (a stale tag is legal: WfGroups).
     rt::DevBuf<RtF4> wf_group_rec;
     rt::DevBuf<uint8_t> wf_group_tag;
-    int ensure_groups(uint32_t n_groups) {
-        if (hipError_t e = wf_group_rec.reserve(wf_paths_cap * n_groups); e != hipSuccess)
-            return rt::hip_fail(e, "light-group records");
-        if (hipError_t e = wf_group_tag.reserve(wf_paths_cap * (wf_depth_cap + 1ull)); e != hipSuccess)
-            return rt::hip_fail(e, "light-group tags");
+    int bind_layer_records(WfFeat *features, WfIds *ids, WfGroups *groups) {
+        auto reserve = [](auto &buf, size_t count, const char *what) -> int {
+            if (hipError_t e = buf.reserve(count); e != hipSuccess)
+                return rt::hip_fail(e, what);
+            return RT_OK;
+        };
+        if (int rc = features ? reserve(wf_feat, wf_paths_cap * 2, "feature records") : RT_OK; rc != RT_OK)
+            return rc;
+        if (int rc = ids ? reserve(wf_ids, wf_paths_cap, "id records") : RT_OK; rc != RT_OK)
+            return rc;
+        if (int rc = groups ? reserve(wf_group_rec, wf_paths_cap * groups->n_groups, "light-group records") : RT_OK; rc != RT_OK)
+            return rc;
+        if (int rc = groups ? reserve(wf_group_tag, wf_paths_cap * (wf_depth_cap + 1ull), "light-group tags") : RT_OK; rc != RT_OK)
+            return rc;
+        if (features)
+            features->rec = wf_feat.get();
+        if (ids)
+            ids->rec = wf_ids.get();
+        if (groups)
+            groups->rec = wf_group_rec.get(), groups->tag = wf_group_tag.get();
         return RT_OK;
     }
     // the workspace half of a WfLaunch (after ensure_wavefront): queues, hit records, counters, stack workspace, sort buffers

@@ -712,13 +712,14 @@ static hipError_t launch_last_stage(const WfLaunch &L, const WfPassKind &kind, c
     const int first = step.first_pass ? 1 : 0, last = step.last_pass ? 1 : 0;
     if (kind.source() == WfPassKind::LIST) { // the feature sums, the id tables and the group sums go before the sums: they read the entry's base count from the list
         const WfAccum &A = kind.entries();
+        const WfLayers keep = kind.layers();
         const int res_blocks = (int)((A.n_entries + 255u) / 256u);
-        if (kind.features())
-            WF_LAUNCH(wf_resolve_features, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.features());
-        if (kind.ids())
-            WF_LAUNCH(wf_resolve_ids, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.ids());
-        if (kind.groups())
-            WF_LAUNCH(wf_resolve_groups, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *kind.groups(), L.n_paths);
+        if (keep.features)
+            WF_LAUNCH(wf_resolve_features, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *keep.features);
+        if (keep.ids)
+            WF_LAUNCH(wf_resolve_ids, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *keep.ids);
+        if (keep.groups)
+            WF_LAUNCH(wf_resolve_groups, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, A, *keep.groups, L.n_paths);
         WF_LAUNCH(wf_resolve_list, dim3(res_blocks > 0 ? res_blocks : 1), block, 0, stream, L, A);
     } else if (kind.source() == WfPassKind::BAKE) { // the fold the bake's kind asks for, one lane per (point, k)
         const WfBake &B = kind.bake_points();
@@ -736,6 +737,7 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind
                                  EventPool *extend_events, unsigned long long *packet_census_out, const WfHostSync *host_sync) {
     const int gen_blocks = (int)((L.n_paths + 255u) / 256u < (uint32_t)num_cus * 16u ? (L.n_paths + 255u) / 256u : (uint32_t)num_cus * 16u);
     const dim3 block(256);
+    const WfLayers keep = kind.layers();
     if (!step.time_extends)
         extend_events = nullptr;
     hipError_t e = hipMemsetAsync(L.counters, 0, sizeof(uint32_t) * WF_CNT_WORDS, stream);
@@ -808,12 +810,12 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind
             (void)hipEventRecord(e1, stream);
         if (S.n_prims)
             WF_LAUNCH(wf_extend_prims, dim3(shade_blocks), block, 0, stream, S, L);
-        if (b == 0 && kind.features()) // a feature accumulator's pass: the primary rays' first hits are final here
-            WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *kind.features());
-        if (b == 0 && kind.ids()) // ... and so are their ids
-            WF_LAUNCH(wf_ids, dim3(shade_blocks), block, 0, stream, S, L, *kind.ids());
-        if (kind.groups()) // light groups: at every bounce, whose emission the frame or terminal value wf_shade makes of this hit is
-            WF_LAUNCH(wf_group_tags, dim3(shade_blocks), block, 0, stream, S, L, *kind.groups());
+        if (b == 0 && keep.features) // a feature accumulator's pass: the primary rays' first hits are final here
+            WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *keep.features);
+        if (b == 0 && keep.ids) // ... and so are their ids
+            WF_LAUNCH(wf_ids, dim3(shade_blocks), block, 0, stream, S, L, *keep.ids);
+        if (keep.groups) // light groups: at every bounce, whose emission the frame or terminal value wf_shade makes of this hit is
+            WF_LAUNCH(wf_group_tags, dim3(shade_blocks), block, 0, stream, S, L, *keep.groups);
         // Will the next bounce be sorted? Its own bound is not known yet (it arrives one bounce late) but cannot exceed this one, so: may it be.
         // Then this wf_shade writes the sort's input itself, key and slot at the physical slot of every ray it makes, and every slot it leaves
         // empty (the ends of the 64 sub-queue regions) must already hold a pad: RT_RAY_KEY_PAD in the compared bits, behind every real key
@@ -856,8 +858,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind
         L.paths_in = L.paths_out;
         L.paths_out = t;
     }
-    if (kind.groups()) // before wf_fold, which overwrites the terminal values in sample_out
-        WF_LAUNCH(wf_fold_groups, dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, L, *kind.groups());
+    if (keep.groups) // before wf_fold, which overwrites the terminal values in sample_out
+        WF_LAUNCH(wf_fold_groups, dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, L, *keep.groups);
     WF_LAUNCH(wf_fold, dim3(gen_blocks > 0 ? gen_blocks : 1), block, 0, stream, L);
     if (census_pending) { // ray_depth <= 2 (no bounce 2 to read it at): wait for bounce 0 only; the rest of the pass is queued behind it
         if ((e = hipEventSynchronize(hs->events[0])) != hipSuccess)

@@ -48,7 +48,7 @@ def test_no_entry_point_stages_its_arrays_by_hand():
     RT_FLAG_DEVICE_FB flag itself, and the per-purpose staging buffers it replaced stay gone. rt_group.cpp keeps its own handling of the
     flag (the RCCL gather)."""
     allowed = {  # file -> the one line that may stay, and why
-        "rt_accum_host.cpp": "device_table ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice",  # rt_accum_attach_ids: one upload into the accumulator's own arena
+        "rt_accum_layers.cpp": "device_table ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice",  # attach_arrays: a layer's one table, uploaded into the accumulator's own arena
     }
     gone = re.compile(r"\bensure_fb\b|\bensure_rays\b|s->rgb8\b|s->fb\b")
     pick = re.compile(r"\?\s*hipMemcpy\w+\s*:\s*hipMemcpy\w+|\bdevice_(fb|out)\s*\?")
