@@ -195,7 +195,7 @@ struct DevStats { // device-side counters, see rt_stats in include/rt_abi.h
     unsigned long long samples, casts, nodes, box_tests, tri_tests, shaded, lq, lnodes, lbox, ltri, lhits, texels;
 };
 
-// ---- wavefront pipeline (rt_wavefront.hip): path = one (pixel, sample); queues hold live paths between bounces
+// ---- wavefront pipeline (rt_wavefront.hip, rt_wf_extend.hip, rt_wf_shade.hip): path = one (pixel, sample); queues hold live paths between bounces
 // Queue record, one per live path (64 B = one HBM request): the ray (first 32 B), what wf_extend needs to start its traversal
 // without arithmetic (next 16 B) and the path's RNG state (last 16 B). The state of a path travels WITH its ray through the queues, so wf_shade finds ray
 // and state with one gather and writes both with the coalesced queue traffic instead of a random per-path record.
@@ -311,7 +311,7 @@ struct WfLaunch {
                              // pixel, and what the kernel's own census said on an earlier pass)
     unsigned long long *packet_census; // [2] device: trips, lanes served (summed over the launch's waves)
     const DevNode *rel_nodes; // both non-null: every primary ray of this pass starts at ONE camera position, and these are the binary tree's
-    const DevTri *rel_tris;   // records with that position folded in (rt_wavefront.hip wf_camera_relative); wf_extend_packet walks them.
+    const DevTri *rel_tris;   // records with that position folded in (rt_wf_extend.hip wf_camera_relative); wf_extend_packet walks them.
                               // Null: any origins, the kernel reads the tree's own records (rt_render.cpp launch_pass decides)
     uint32_t global_best;    // 0: the reference's traversal order and pruning (parity mode); 1: prune against the global best
                              // (RT_FLAG_GLOBAL_BEST, production traversal: a subset of the reference's node visits)

@@ -16,6 +16,13 @@
         hipLaunchKernelGGL(__VA_ARGS__);     \
         hipGetLastError();                   \
     })
+// ... inside a launcher that returns hipError_t: a failed launch (bad configuration, lost device) ends it with that error, so it cannot turn
+// into a silently wrong image
+#define WF_LAUNCH(...)                                  \
+    do {                                                \
+        if (hipError_t le_ = RT_LAUNCH_CHECKED(__VA_ARGS__); le_ != hipSuccess) \
+            return le_;                                 \
+    } while (0)
 
 // Run-time bools -> template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}); inside f the
 // arguments are constant expressions (`kernel<A, B>`, `if constexpr (A)`). Every launcher picks its kernel instantiation this way.
@@ -53,7 +60,8 @@ hipError_t launch_cast(const DevScene &S, const float *rays, uint32_t n, uint32_
 hipError_t launch_surface_normals(const DevScene &S, const float *rays, uint32_t n, uint32_t *prim, float *t, float *normal, float *shading, hipStream_t stream);
 hipError_t launch_light_pdf(const DevScene &S, const float *rays, uint32_t n, float *pdf, hipStream_t stream);
 hipError_t launch_bg_at(const DevScene &S, const float *dirs, uint32_t n, float *rgb, hipStream_t stream);
-// rt_wavefront.hip: one pass (pixel tile x sample range) of the wavefront pipeline, stream-ordered
+// rt_wavefront.hip: one pass (pixel tile x sample range) of the wavefront pipeline, stream-ordered. It schedules the stages; the closest-hit
+// kernels are rt_wf_extend.hip's and rt_wide.hip's, wf_shade is rt_wf_shade.hip's (their launchers: below)
 // `extend_events`: with WfPassStep::time_extends, one (start, stop) event pair per wf_extend launch is taken from the pool and recorded on `stream`
 // `packet_census_out` (optional, host, 2 words): trips and lanes served of this pass's wf_extend_packet launch (0, 0 if it did not run)
 // `host_sync` (optional): pinned words + events for the one-bounce-late read-back of the queue sizes (coherence sort and the
@@ -135,6 +143,9 @@ hipError_t launch_bake_rays(const WfBake &B, uint32_t samples, uint32_t n, void 
 // the sensor record `d_sensor` (device) -> `d_rays_out` (device, 32 B per record, 16-byte aligned)
 hipError_t launch_sensor_rays(const WfSensor *d_sensor, uint32_t width, uint32_t height, uint32_t first_pixel, uint32_t first_sample, uint32_t samples, uint32_t n,
                               void *d_rays_out, int num_cus, hipStream_t stream);
+// bytes of temporary storage rocPRIM's radix sort needs for `n` (key, slot) pairs
+size_t wavefront_sort_temp_bytes(size_t n);
+// rt_wf_extend.hip: closest hit over the binary tree
 // closest-hit probe through the renderer's own kernels: `rays` (6 floats each, device) -> queue -> wf_extend (or wf_extend_packet)
 // -> prim / bct (device). `L` carries the workspace (paths_in, hits, counters, stack_overflow, stats) and the traversal mode.
 hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *rays, uint32_t n, bool packet, bool stats, uint32_t *prim, float *bct,
@@ -142,11 +153,16 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 // The camera-relative copy of a binary scene tree's records (WfLaunch::rel_nodes / rel_tris) for the camera position o[3]: one kernel on
 // `stream`; `rel_nodes` has room for n_nodes records, `rel_tris` for bvh.n_tris.
 hipError_t launch_camera_relative(const DevBvh &bvh, uint32_t n_nodes, const float *o, DevNode *rel_nodes, DevTri *rel_tris, int num_cus, hipStream_t stream);
+// the closest-hit kernel of one bounce over the queue of `L`, on the grid the overflow workspace is sized for (L.stack_stride / 256 blocks):
+// wf_extend, or wf_extend_packet for `packet` (coherent primary rays); the 8-wide tree's kernels for a scene that has one (below)
+hipError_t launch_extend(const DevScene &S, const WfLaunch &L, bool packet, bool stats, hipStream_t stream);
+// behind it, for a scene with analytic primitives: the nearer of (tree hit, primitive hit) for every queued ray (wf_extend_prims, grid-stride)
+hipError_t launch_extend_prims(const DevScene &S, const WfLaunch &L, uint32_t blocks, hipStream_t stream);
 // rt_wide.hip: the closest-hit kernel of scenes built with RT_BUILD_WIDE (same queue protocol as wf_extend)
 // `packet`: the wave walks the tree once for its 64 consecutive rays (coherent primary rays), records through the scalar cache
 hipError_t launch_extend_wide(const DevScene &S, const WfLaunch &L, bool packet, bool stats, int blocks, hipStream_t stream);
-// bytes of temporary storage rocPRIM's radix sort needs for `n` (key, slot) pairs
-size_t wavefront_sort_temp_bytes(size_t n);
+// rt_wf_shade.hip: wf_shade over the hits of `L`, in the instantiation the scene's lights and environment ask for
+hipError_t launch_shade(const DevScene &S, const WfLaunch &L, bool stats, uint32_t blocks, hipStream_t stream);
 // rt_accum.hip: the accumulators' per-round kernels (rt_abi.h rt_accum_*). `AccumRound` is the device state of one accumulator.
 struct AccumRound {
     float *sum, *even_sum;     // [3 * pixels]

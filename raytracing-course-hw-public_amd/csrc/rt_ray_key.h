@@ -1,4 +1,4 @@
-// rt_ray_key.h — the ray-order key of the secondary bounces, ONE definition for the kernel that emits it (rt_wavefront.hip: wf_shade, where it
+// rt_ray_key.h — the ray-order key of the secondary bounces, ONE definition for the kernel that emits it (rt_wf_shade.hip: wf_shade, where it
 // makes a ray) and for plain C++ (tests/test_ray_order_key.py compiles a program against it).
 //
 // 24 bits: the direction octant (3 bits), the Morton code of the origin's cell in a 64^3 grid over the scene bounds (18 bits), then which

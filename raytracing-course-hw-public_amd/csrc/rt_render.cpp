@@ -138,7 +138,7 @@ WfLaunch rt::one_row_launch(const rt_scene *s, const rt_params *p, uint32_t n, u
     return W;
 }
 
-// Camera-relative records for the packet kernel (rt_wavefront.hip wf_camera_relative, WfLaunch::rel_nodes / rel_tris) of a pass whose primary
+// Camera-relative records for the packet kernel (rt_wf_extend.hip wf_camera_relative, WfLaunch::rel_nodes / rel_tris) of a pass whose primary
 // rays all start at `cam_pos`. The copy is made on the scene's stream, ahead of the pass, when the camera position (compared as bits) or the
 // tree (rt_scene::geo_generation) differs from what the kept copy was made of; otherwise the kept copy is handed out and nothing is launched.
 // No copy, and the absolute kernel (W.rel_* stay null), when

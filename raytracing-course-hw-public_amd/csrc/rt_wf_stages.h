@@ -1,7 +1,7 @@
 // rt_wf_stages.h — the two ends of a wavefront pass on the device (part of rt_wavefront.hip's translation unit): the first stage, written
 // once over the four sources a pass's paths can come from (rt_kernels.h WfPassKind), wf_fold, the last stages that add a pass's finished
 // samples where its kind keeps them, and the two writers that deliver first rays as rt_ray records (rt_sensor_rays, rt_bake_rays). What runs
-// between the ends (extend, shade, sort, advance) and the launchers are rt_wavefront.hip's.
+// between the ends is rt_wf_extend.hip's (or rt_wide.hip's), rt_wf_shade.hip's and, with the launchers of a pass, rt_wavefront.hip's (sort, advance).
 #pragma once
 #include "rt_dev_bake.h"
 #include "rt_dev_queue.h"

@@ -1,4 +1,4 @@
-"""GPU tests of the camera-relative records of the primary-ray packet kernel (csrc/rt_wavefront.hip: wf_camera_relative, wf_extend_packet<.., REL>).
+"""GPU tests of the camera-relative records of the primary-ray packet kernel (csrc/rt_wf_extend.hip: wf_camera_relative, wf_extend_packet<.., REL>).
 
 A pass of camera rays of ONE view walks a copy of the binary tree's records with the camera position folded in; every other pass (several
 views, caller-supplied rays, packets off) walks the tree's own records. Nothing a caller sees may tell the two apart: framebuffers are compared

@@ -1,4 +1,4 @@
-"""GPU tests of the sorted bounces' queue handling (csrc/rt_wavefront.hip, csrc/rt_ray_key.h): a bounce that may be followed by a sorted one has
+"""GPU tests of the sorted bounces' queue handling (csrc/rt_wavefront.hip, csrc/rt_wf_shade.hip, csrc/rt_wf_policy.h, csrc/rt_ray_key.h): a bounce that may be followed by a sorted one has
 wf_shade write the ray-order sort's input itself, key and slot at the physical slot of every ray it makes (WfLaunch::emit_keys), and the sort
 runs over the queue's physical positions: the filled parts of the 64 sub-queue regions and, between them, the unfilled ends, which hold pad
 keys. A pad that does not lose against a real key, a slot left without its key, or a sort that is too short loses or duplicates a ray, which

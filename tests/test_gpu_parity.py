@@ -135,7 +135,7 @@ def test_queue_shapes_match_oracle(pairs, gpu, shape):
 @pytest.mark.parametrize("name", ["room_textured", "room_manylights"])
 def test_class_sorted_shading_windows_match_oracle(pairs, gpu, name):
     """From 2 M sorted rays up (8 blocks per CU x 1024 positions) a wave of wf_shade takes 256 queue positions at a time and hands them to its
-    lanes sorted by the sampler class the ray-order sort carried along (rt_wavefront.hip, wf_shade). Which lane shades a hit must not
+    lanes sorted by the sampler class the ray-order sort carried along (rt_wf_shade.hip, wf_shade). Which lane shades a hit must not
     change a bit: 3.07 M paths (not a multiple of 256: the last window is ragged) against the oracle, framebuffer bit for bit and every event
     counter, with the counting and the plain kernel variants; sorting off takes the 64-position path over the same queue."""
     dev, orc, _ = pairs[name]

@@ -136,7 +136,7 @@ def test_guarded_rays_through_every_binary_kernel(pairs, gpu, oracle, sg):
     go through EVERY binary closest-hit kernel, shuffled among plain rays: all kernels take the guarded branch of the one inner-node step
     (trav_inner_apply, rt_dev_trav.h). The mix is checked per 64 consecutive rays: exactly a wave of the probe and of a packet, and the
     pool a refilling wave of wf_extend draws from. Parity modes: every field bit-equal to the oracle, and the packet kernel's counters are the per-lane
-    kernel's ("by construction", rt_wavefront.hip). Production modes: the hit contract; these rays are built to tie, so ties are not capped."""
+    kernel's ("by construction", rt_wf_extend.hip). Production modes: the hit contract; these rays are built to tie, so ties are not capped."""
     big = big_leaf_scene(sg)
     big_dev, big_orc = gpu.DeviceScene(big), oracle.OracleScene(big)
     try:

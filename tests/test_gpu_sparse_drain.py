@@ -1,4 +1,4 @@
-"""GPU tests of wf_extend's sparse drain (csrc/rt_wavefront.hip): once a wave's queue is used up and at most RT_EXT_SPARSE_MAX of its lanes
+"""GPU tests of wf_extend's sparse drain (csrc/rt_wf_extend.hip): once a wave's queue is used up and at most RT_EXT_SPARSE_MAX of its lanes
 still walk, it leaves the throughput loop for one that unwinds fully, tests waiting leaves at once and steps inner nodes in the same trip.
 Every lane runs the same state machine in the same order, so hits and counters must not change.
 
