@@ -1,5 +1,6 @@
 // rt_build_dev.h — device code the builders share: rt_bvh_device.hip builds the trees and the records, rt_wide_refit.hip recomputes them
-// for new positions. What both must compute bit for bit alike has its one definition here. Device only (included by .hip files).
+// for new positions, rt_update_dev.hip scans them. What they must compute bit for bit alike has its one definition here, the host's reading
+// of the bounds words included. Included by .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,14 @@ __host__ __device__ __forceinline__ float dec_f(uint32_t e) {
 }
 
 // ---- 1. bounds of all vertices: bounds[0..2] = min (encoded), bounds[3..5] = max
+// What the six words hold before the first atomic (the host uploads them; a caller appends words of its own), and what they say afterwards.
+#define RT_BOUNDS_WORDS_INIT 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u
+inline void bounds_decode(const uint32_t *words, float lo[3], float hi[3]) {
+    for (int c = 0; c < 3; ++c) {
+        lo[c] = dec_f(words[c]);
+        hi[c] = dec_f(words[3 + c]);
+    }
+}
 __global__ __launch_bounds__(256) void k_bounds(const float *__restrict__ pos, uint32_t n, uint32_t *bounds) {
     float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {

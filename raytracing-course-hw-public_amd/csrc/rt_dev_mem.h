@@ -4,7 +4,8 @@
 //   rt::DevArena    a list of allocations with one lifetime: the scratch of a build, the buffers of a scene's geometry, of an environment;
 //   rt::DevBuf<T>   one buffer that is grown on demand: framebuffer staging, ray copies, exchange slabs.
 // Both are move-only and free in their destructors. Neither synchronises: whoever lets one die (or calls reset()) has made sure that no
-// kernel still uses the memory, and that the device it was allocated on is the current one.
+// kernel still uses the memory, and that the device it was allocated on is the current one. The device-side builders' scratch makes sure
+// itself: it is an rt::ScratchArena (rt_build_host.h), a DevArena that knows its stream and drains it before the frees, on every return path.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

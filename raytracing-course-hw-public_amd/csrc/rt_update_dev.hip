@@ -20,9 +20,8 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "rt_build_dev.h"
+#include "rt_build_scan.h"
 #include "rt_kernels.h"
 #include "rt_update_dev.h"
 
@@ -149,47 +148,34 @@ hipError_t scan_update_device(const DeviceArrays &in, const std::vector<uint8_t>
     const uint32_t n = in.n;
     if (n == 0)
         return hipSuccess;
-    // every failure path below leaves no kernel running on the caller's arrays or on the scratch about to be freed
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    };
-    DevArena tmp; // scratch of the scan
-    Drain drain{stream}; // after `tmp`: it runs first
+    ScratchArena tmp{stream}; // scratch of the scan: every return path leaves no kernel running on it or on the caller's arrays
     ScanArgs A{};
     A.pos = in.pos, A.mat = in.mat, A.n = n;
     A.n_mats = (uint32_t)emissive.size();
     A.n_chunks = (uint32_t)(((uint64_t)n + CHUNK - 1) / CHUNK);
     uint8_t *d_em;
     uint32_t *chunk_first;
-    char *scan_tmp;
-    size_t scan_bytes = 0;
+    ExclusiveScan scan;
     HIP_TRY_ERR(tmp.alloc(&d_em, emissive.size()));
     HIP_TRY_ERR(tmp.alloc(&A.words, (size_t)8));
     HIP_TRY_ERR(tmp.alloc(&A.chunk_lights, (size_t)A.n_chunks));
     HIP_TRY_ERR(tmp.alloc(&chunk_first, (size_t)A.n_chunks));
-    HIP_TRY_ERR(rocprim::exclusive_scan(nullptr, scan_bytes, A.chunk_lights, chunk_first, 0u, (size_t)A.n_chunks, rocprim::plus<uint32_t>(), stream));
-    HIP_TRY_ERR(tmp.alloc(&scan_tmp, scan_bytes));
+    HIP_TRY_ERR(scan.prepare(tmp, A.chunk_lights, chunk_first, (size_t)A.n_chunks, stream));
     A.emissive = d_em;
-    static const uint32_t init_words[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, RT_NONE, 0u};
+    static const uint32_t init_words[8] = {RT_BOUNDS_WORDS_INIT, RT_NONE, 0u};
     HIP_TRY_ERR(hipMemcpyAsync(A.words, init_words, sizeof(init_words), hipMemcpyHostToDevice, stream));
     if (!emissive.empty())
         HIP_TRY_ERR(hipMemcpyAsync(d_em, emissive.data(), emissive.size(), hipMemcpyHostToDevice, stream)); // (the caller's vector outlives the call)
     const dim3 grid(std::min<uint32_t>(A.n_chunks, 256u * 16u));
     HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_update_scan, grid, dim3(CHUNK), 0, stream, A));
-    HIP_TRY_ERR(rocprim::exclusive_scan(scan_tmp, scan_bytes, A.chunk_lights, chunk_first, 0u, (size_t)A.n_chunks, rocprim::plus<uint32_t>(), stream));
-    uint32_t h_words[8], h_last[2];
+    HIP_TRY_ERR(scan.run(A.chunk_lights, chunk_first, (size_t)A.n_chunks, stream));
+    uint32_t h_words[8];
+    uint64_t n_lights;
     HIP_TRY_ERR(hipMemcpyAsync(h_words, A.words, sizeof(h_words), hipMemcpyDeviceToHost, stream));
-    HIP_TRY_ERR(hipMemcpyAsync(&h_last[0], chunk_first + (A.n_chunks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY_ERR(hipMemcpyAsync(&h_last[1], A.chunk_lights + (A.n_chunks - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY_ERR(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(scan_total(A.chunk_lights, chunk_first, (size_t)A.n_chunks, stream, &n_lights)); // synchronises: h_words is here too
     out->bad_material = h_words[7] != 0u;
     out->first_non_finite = h_words[6];
-    for (int c = 0; c < 3; ++c) {
-        out->lo[c] = dec_f(h_words[c]);
-        out->hi[c] = dec_f(h_words[3 + c]);
-    }
-    const uint64_t n_lights = (uint64_t)h_last[0] + h_last[1];
+    bounds_decode(h_words, out->lo, out->hi);
     if (out->bad_material || out->first_non_finite != RT_NONE || !want_lights || n_lights == 0)
         return hipSuccess;
     if (n_lights > n) {

@@ -10,12 +10,7 @@
 // costs 4 and never does (profiles/r04_variants.txt: gather rates per record shape; the L1 access rate is what bounds wf_extend_wide).
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <vector>
-
-#include <rocprim/rocprim.hpp>
-
-#include "rt_dev_mem.h"
+#include "rt_build_scan.h"
 #include "rt_kernels.h"
 #include "rt_wide_pack.h"
 #include "wide_grid.h"
@@ -104,7 +99,7 @@ hipError_t pack_wide_device(const WideNode *d_nodes, uint32_t n_wide, const DevT
     *n_units_out = 0;
     if (n_wide == 0)
         return hipSuccess;
-    DevArena scratch{16}; // everything allocated here, the blob included until it is handed out: freed on every return path
+    ScratchArena scratch{stream, 16}; // everything allocated here, the blob included until it is handed out: drained, then freed, on every return path
     void *blob = nullptr;
     PackArgs A{};
     A.nodes = d_nodes, A.n = n_wide, A.tris = d_tris, A.grid = grid;
@@ -113,16 +108,12 @@ hipError_t pack_wide_device(const WideNode *d_nodes, uint32_t n_wide, const DevT
     HIP_TRY_ERR(scratch.alloc_bytes(&A.pos, 4ull * n_wide));
     const dim3 grid_dim((n_wide + 255u) / 256u), block(256);
     HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_pack_sizes, grid_dim, block, 0, stream, A));
-    size_t scan_bytes = 0;
-    HIP_TRY_ERR(rocprim::exclusive_scan(nullptr, scan_bytes, A.units, A.base, 0u, (size_t)n_wide, rocprim::plus<uint32_t>(), stream));
-    void *scan_tmp = nullptr;
-    HIP_TRY_ERR(scratch.alloc_bytes(&scan_tmp, scan_bytes));
-    HIP_TRY_ERR(rocprim::exclusive_scan(scan_tmp, scan_bytes, A.units, A.base, 0u, (size_t)n_wide, rocprim::plus<uint32_t>(), stream));
-    uint32_t last[2] = {0u, 0u};
-    HIP_TRY_ERR(hipMemcpyAsync(&last[0], A.base + (n_wide - 1u), 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY_ERR(hipMemcpyAsync(&last[1], A.units + (n_wide - 1u), 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY_ERR(hipStreamSynchronize(stream));
-    const uint64_t n_units = (uint64_t)RT_WIDE_NODE_UNITS + last[0] + last[1];
+    ExclusiveScan scan;
+    HIP_TRY_ERR(scan.prepare(scratch, A.units, A.base, (size_t)n_wide, stream));
+    HIP_TRY_ERR(scan.run(A.units, A.base, (size_t)n_wide, stream));
+    uint64_t n_units;
+    HIP_TRY_ERR(scan_total(A.units, A.base, (size_t)n_wide, stream, &n_units));
+    n_units += RT_WIDE_NODE_UNITS; // the root's own record
     if (n_units >= 0xFFFFFFF0ull) { // 64 GB of blob: beyond the 32-bit unit index
         if (err)
             *err = "wide blob exceeds 2^32 units";

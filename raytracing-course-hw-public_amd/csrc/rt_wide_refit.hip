@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "rt_build_dev.h"
+#include "rt_build_host.h"
 #include "rt_kernels.h"
 #include "rt_wide_refit.h"
 #include "wide_grid.h"
@@ -215,7 +216,7 @@ hipError_t refit_upload(const rt_geometry_update *upd, hipStream_t stream, Refit
     HIP_TRY_ERR(in->owned.alloc_bytes(&in->uv, 24ull * n));
     HIP_TRY_ERR(in->owned.alloc_bytes(&in->mat, 4ull * n));
     HIP_TRY_ERR(in->owned.alloc_bytes(&in->bounds, 8 * sizeof(uint32_t)));
-    const uint32_t init_bounds[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
+    const uint32_t init_bounds[8] = {RT_BOUNDS_WORDS_INIT, 0u, 0u};
     HIP_TRY_ERR(hipMemcpyAsync(in->pos, upd->positions, 36ull * n, hipMemcpyHostToDevice, stream));
     HIP_TRY_ERR(hipMemcpyAsync(in->nrm, upd->normals, 36ull * n, hipMemcpyHostToDevice, stream));
     HIP_TRY_ERR(hipMemcpyAsync(in->tan, upd->tangents, 36ull * n, hipMemcpyHostToDevice, stream));
@@ -226,12 +227,8 @@ hipError_t refit_upload(const rt_geometry_update *upd, hipStream_t stream, Refit
     const int blocks = (int)std::min<uint64_t>(((uint64_t)n + 255) / 256, 256u * 16u);
     HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_bounds, dim3(blocks), dim3(256), 0, stream, in->pos, n, in->bounds));
     uint32_t h_bounds[8];
-    HIP_TRY_ERR(hipMemcpyAsync(h_bounds, in->bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, stream));
-    HIP_TRY_ERR(hipStreamSynchronize(stream));
-    for (int c = 0; c < 3; ++c) {
-        in->lo[c] = dec_f(h_bounds[c]);
-        in->hi[c] = dec_f(h_bounds[3 + c]);
-    }
+    HIP_TRY_ERR(read_back(h_bounds, in->bounds, 8, stream));
+    bounds_decode(h_bounds, in->lo, in->hi);
     return hipSuccess;
 }
 
@@ -241,7 +238,7 @@ hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs,
         *levels_ms = 0;
     if (n_tris == 0 || n_wide == 0)
         return hipSuccess;
-    DevArena tmp; // scratch of the refit, freed on every return path
+    ScratchArena tmp{stream}; // scratch of the refit: drained, then freed, on every return path
     RefitArgs A{};
     A.pos = in.pos, A.nrm = in.nrm, A.tan = in.tan, A.uv = in.uv, A.mat = in.mat;
     A.tris = tris, A.attrs = attrs, A.n_tris = n_tris;
@@ -264,8 +261,7 @@ hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs,
         A.first = level_first.back(), A.count = level_count.back();
         HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_refit_level, dim3((A.count + 255u) / 256u), dim3(256), 0, stream, A));
         uint32_t h[2];
-        HIP_TRY_ERR(hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, stream));
-        HIP_TRY_ERR(hipStreamSynchronize(stream));
+        HIP_TRY_ERR(read_back(h, A.counters, 2, stream));
         const uint32_t end = A.first + A.count;
         if (h[1] != 0u || h[0] > n_wide || h[0] < end || level_first.size() > 4096u) {
             if (err)
@@ -291,8 +287,7 @@ hipError_t refit_wide_device(const RefitInput &in, DevTri *tris, DevAttr *attrs,
         HIP_TRY_ERR(RT_LAUNCH_CHECKED(k_refit_nodes, dim3((A.count + 63u) / 64u), dim3(64), 0, stream, A));
     }
     uint32_t h[2];
-    HIP_TRY_ERR(hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY_ERR(hipStreamSynchronize(stream));
+    HIP_TRY_ERR(read_back(h, A.counters, 2, stream));
     if (h[1] != 0u) {
         if (err)
             *err = "wide refit: the packed tree is inconsistent";

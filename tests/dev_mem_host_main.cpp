@@ -1,20 +1,26 @@
 // The failure paths of csrc/rt_dev_mem.h on the CPU (tests/test_dev_mem_host.py builds and runs this with the address and undefined-behaviour
 // sanitizers): rt::DevArena, rt::DevBuf and the two try macros against a stub allocator that counts live allocations, logs every call, can
 // fail the k-th hipMalloc with hipErrorOutOfMemory, and aborts on a double free or on a pointer it never handed out. No HIP runtime is linked:
-// the three entry points the header calls are defined here, and so is rt::fail.
+// the entry points the headers call are defined here, and so is rt::fail.
+// Also the builders' shared host steps (csrc/rt_build_host.h): rt::ScratchArena, rt::read_back and rt::scan_total in a builder-shaped function
+// on a stub stream, where every stubbed call fails in turn: the stream is drained before the first free on every path.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <functional>
 #include <set>
 #include <string>
 #include <vector>
 
-#include "rt_dev_mem.h"
+#include "rt_build_host.h"
 
 namespace {
 std::set<void *> live;
 std::vector<size_t> sizes;  // of every successful hipMalloc, in order
-std::string calls;          // 'M' a successful hipMalloc, 'x' a failed one, 'F' a hipFree
+std::string calls;          // 'M' a successful hipMalloc, 'x' a failed one, 'F' a hipFree; on the stream: 'S' hipStreamSynchronize, 'C' hipMemcpyAsync,
+                            // 'L' a kernel launch (stub_launch below), and 's', 'c', 'l' their failures
 long fail_at = -1, n_malloc = 0; // fail the hipMalloc with this index (0-based); -1: none
+long fail_call = -1, n_call = 0; // fail the stubbed call (allocation, copy, launch or synchronise; frees cannot fail) with this index; -1: none
 int last_code = 0;
 std::string last_msg;
 int n_checks = 0;
@@ -28,11 +34,36 @@ void reset_stub(long k = -1) {
     calls.clear();
     fail_at = k;
     n_malloc = 0;
+    fail_call = -1;
+    n_call = 0;
+}
+// a call on the stream: logged, and failed if it is its turn
+hipError_t stream_call(char ok, char failed) {
+    if (n_call++ == fail_call) {
+        calls += failed;
+        return hipErrorLaunchFailure;
+    }
+    calls += ok;
+    return hipSuccess;
+}
+// stands in for RT_LAUNCH_CHECKED: the "kernel" runs at once on the host's stand-in for device memory
+hipError_t stub_launch(const std::function<void()> &kernel) {
+    const hipError_t e = stream_call('L', 'l');
+    if (e == hipSuccess)
+        kernel();
+    return e;
 }
 } // namespace
 
+extern "C" hipError_t hipStreamSynchronize(hipStream_t) { return stream_call('S', 's'); }
+extern "C" hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind, hipStream_t) {
+    const hipError_t e = stream_call('C', 'c');
+    if (e == hipSuccess)
+        std::memcpy(dst, src, bytes);
+    return e;
+}
 extern "C" hipError_t hipMalloc(void **p, size_t bytes) {
-    if (n_malloc++ == fail_at) {
+    if (n_malloc++ == fail_at || n_call++ == fail_call) {
         calls += 'x';
         return hipErrorOutOfMemory; // (*p is left alone, as the runtime leaves it)
     }
@@ -95,6 +126,35 @@ hipError_t builder(rt::DevArena &tmp, rt::DevArena &outs, Slots &s, const char *
     HIP_TRY_ERR(outs.alloc_bytes(&s.f, 12));
     return hipSuccess;
 }
+// ... on a stream: scratch that drains, an upload, a scan kernel and its total, an output allocated half-way, a second kernel, a read-back.
+// On success *total is the scan's total and sum[0..1] the low and high word of it as the second kernel wrote them.
+constexpr int N_STREAM_CALLS = 11; // stubbed calls of the success path, up to the return
+const char *const STREAM_CALL_TEXT[N_STREAM_CALLS] = {"tmp.alloc(&values", "tmp.alloc(&offsets", "hipMemcpyAsync(values", "stub_launch(scan", "rt::scan_total(",
+                                                      "rt::scan_total(", "rt::scan_total(", "outs.alloc(&result", "stub_launch(fill", "rt::read_back(", "rt::read_back("};
+hipError_t stream_builder(rt::DevArena &outs, const std::vector<uint32_t> &h_values, uint64_t *total, uint32_t sum[2], const char **err) {
+    const hipStream_t stream = nullptr;
+    const size_t n = h_values.size();
+    rt::ScratchArena tmp{stream};
+    uint32_t *values, *offsets, *result;
+    HIP_TRY_ERR(tmp.alloc(&values, n));
+    HIP_TRY_ERR(tmp.alloc(&offsets, n));
+    HIP_TRY_ERR(hipMemcpyAsync(values, h_values.data(), 4 * n, hipMemcpyHostToDevice, stream));
+    const auto scan = [&] {
+        uint32_t run = 0;
+        for (size_t i = 0; i < n; ++i) {
+            offsets[i] = run;
+            run += values[i]; // 32 bits, as rocPRIM's scan of 32-bit counts: the last OFFSET fits, the total need not
+        }
+    };
+    HIP_TRY_ERR(stub_launch(scan));
+    HIP_TRY_ERR(rt::scan_total(values, offsets, n, stream, total));
+    HIP_TRY_ERR(outs.alloc(&result, 2)); // after the first launches: a failure here finds kernels possibly in flight
+    const uint64_t t = *total;
+    const auto fill = [&] { result[0] = (uint32_t)t, result[1] = (uint32_t)(t >> 32); };
+    HIP_TRY_ERR(stub_launch(fill));
+    HIP_TRY_ERR(rt::read_back(sum, result, 2, stream));
+    return hipSuccess;
+}
 // ... and of the entry points
 int entry_point(rt::DevBuf<float> &b, size_t n) {
     HIP_TRY(b.reserve(n));
@@ -133,6 +193,38 @@ int main() {
         }
         CHECK(live.empty()); // ... and gone with the arenas
         std::printf("arena sequence, allocation %ld fails: calls %s\n", k, calls.c_str());
+    }
+
+    // ---- the builders' steps on a stream: every stubbed call of the sequence fails in turn (k == N_STREAM_CALLS: none does)
+    CHECK(rt::scan_total(0u, 0u) == 0ull && rt::scan_total(7u, 5u) == 12ull);
+    CHECK(rt::scan_total(0xFFFFFFFFu, 1u) == 0x100000000ull && rt::scan_total(0xFFFFFFFFu, 0xFFFFFFFFu) == 0x1FFFFFFFEull); // carried in 64 bits
+    for (long k = 0; k <= N_STREAM_CALLS; ++k) {
+        reset_stub();
+        fail_call = k < N_STREAM_CALLS ? k : -1;
+        hipError_t e;
+        const char *err = "";
+        uint64_t total = 0;
+        uint32_t sum[2] = {0u, 0u};
+        {
+            rt::DevArena outs(16);
+            e = stream_builder(outs, {5u, 0xFFFFFFFAu, 1u}, &total, sum, &err); // offsets 0, 5, 0xFFFFFFFF: last offset + last value = 2^32
+            if (k == N_STREAM_CALLS) {
+                CHECK(e == hipSuccess && n_call == N_STREAM_CALLS + 1); // (+ 1: the drain)
+                CHECK(total == 0x100000000ull && sum[0] == 0u && sum[1] == 1u);
+                CHECK(outs.size() == 1 && live.size() == 1); // the scratch is gone, the output is the caller's
+            } else {
+                CHECK(e == (calls.find('x') != std::string::npos ? hipErrorOutOfMemory : hipErrorLaunchFailure));
+                CHECK(std::string(err).find(STREAM_CALL_TEXT[k]) == 0); // the failing call's own text
+                CHECK(live.size() == outs.size());
+            }
+        }
+        CHECK(live.empty()); // every allocation freed exactly once (the stub aborts on a second free), the outputs with their arena
+        // the stream is drained after the last launch, copy or failure on it, and before the first free; nothing but frees follows
+        const size_t first_free = calls.find('F'), last_work = calls.find_last_of("CcLl"), drain = calls.rfind('S');
+        CHECK(drain != std::string::npos && (last_work == std::string::npos || drain > last_work));
+        CHECK(first_free == std::string::npos ? drain == calls.size() - 1 : first_free == drain + 1);
+        CHECK(calls.find_first_not_of('F', drain + 1) == std::string::npos);
+        std::printf("stream sequence, call %ld fails: calls %s\n", k, calls.c_str());
     }
 
     // ---- a default arena's alloc_bytes of nothing: no allocation, a null pointer, nothing owned

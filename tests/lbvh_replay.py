@@ -1,4 +1,4 @@
-"""The device BVH builders (csrc/rt_bvh_device.hip) restated from their definitions, in plain numpy; no GPU.
+"""The device BVH builders (csrc/rt_bvh_device.hip; PLOC: csrc/rt_bvh_ploc.hip) restated from their definitions, in plain numpy; no GPU.
 
 What a device build computes before any tree exists is a pure function of the float32 input, so it is held exactly:
   * morton_keys: k_bounds + k_keys statement by statement in float32 (every statement rounds once; nothing in it can contract into an FMA and the

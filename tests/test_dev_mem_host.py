@@ -1,5 +1,6 @@
-"""csrc/rt_dev_mem.h on the CPU: the owners of device memory (rt::DevArena, rt::DevBuf) and the two try macros, run against a stub allocator
-under the address and undefined-behaviour sanitizers. The failure paths they replace (a free on every return path of every builder) are run
+"""csrc/rt_dev_mem.h and csrc/rt_build_host.h on the CPU: the owners of device memory (rt::DevArena, rt::DevBuf, the builders' rt::ScratchArena
+that drains its stream before it frees), the two try macros and the builders' read-back and scan total, run against a stub allocator and a stub
+stream under the address and undefined-behaviour sanitizers. The failure paths they replace (a free on every return path of every builder) are run
 by no GPU test, since nothing there makes an allocation fail; here every allocation of a sequence fails in turn."""
 import os
 import re
@@ -29,6 +30,15 @@ def test_owners_free_everything_on_every_path(tmp_path):
     for k, l in enumerate(seq):
         calls = l.rsplit(" ", 1)[1]
         assert calls == ("M" * k + "x" + "F" * k if k < 6 else "M" * 6 + "F" * 6), l
+    # the builders' steps on a stream (rt_build_host.h), every stubbed call failing in turn: whatever was put on the stream ('C' a copy, 'L' a
+    # launch; lower case: the one that failed), one synchronise ('S') follows the last of it and comes directly before the frees
+    ok = "MMCLCCSMLCS"
+    seq = [l.rsplit(" ", 1)[1] for l in lines if l.startswith("stream sequence")]
+    assert len(seq) == len(ok) + 1
+    for k, calls in enumerate(seq):
+        n_allocs = sum(c == "M" for c in ok[:k])
+        head = ok[:k] + ({"M": "x"}.get(ok[k], ok[k].lower()) if k < len(ok) else "")
+        assert calls == head + "S" + "F" * n_allocs, (k, calls)
 
 
 def test_only_the_header_allocates_device_memory():

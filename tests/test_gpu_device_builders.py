@@ -1,4 +1,5 @@
-"""The device builders of csrc/rt_bvh_device.hip held from the inside. tests/test_gpu_bvh_device.py accepts any proper BVH that finds the oracle's
+"""The device builders of csrc/rt_bvh_device.hip (keys, leaves, radix tree), csrc/rt_bvh_ploc.hip (k_ploc_*) and csrc/rt_bvh_collapse.hip (the
+wide tree) held from the inside. tests/test_gpu_bvh_device.py accepts any proper BVH that finds the oracle's
 hits; here the tree read back from HBM (rt_bvh_device_dump) is compared, exactly, with what the builder is DEFINED to build (tests/lbvh_replay.py):
 
   a. the records are in stable Morton order of the float32 keys (k_bounds, k_keys, the sort, k_leaves), also far from the origin and on a planar
