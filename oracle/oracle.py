@@ -43,6 +43,7 @@ _PROTOS = {
     "rto_light_pdf": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_walk_census": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_u32_p, _abi.c_u32_p]),
     "rto_dump_census": (C.c_int, [_abi.c_u32_p, C.c_uint32, _abi.c_u32_p, C.c_uint32, C.c_uint32, _abi.c_float_p, C.c_uint32, _abi.c_u32_p]),
+    "rto_wide_census": (C.c_int, [_abi.c_u32_p, C.c_uint32, _abi.c_u32_p, C.c_uint32, _abi.c_float_p, C.c_uint32, _abi.c_float_p, C.c_uint32, _abi.c_u32_p]),
     "rto_bg_at": (C.c_int, [C.c_void_p, _abi.c_float_p, C.c_uint32, _abi.c_float_p]),
     "rto_bg_uv": (None, [_abi.c_float_p, C.c_uint32, C.c_int, _abi.c_float_p]),
     "rto_bvh_info": (C.c_int, [C.c_void_p, C.c_int, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p, _abi.c_u32_p]),
@@ -269,6 +270,21 @@ def dump_census(dump, rays):
     out = np.zeros(rays.shape[0], dtype=np.uint32)
     _check(lib().rto_dump_census(_abi.u32ptr(nodes), nodes.shape[0], _abi.u32ptr(tris), tris.shape[0], int(dump["root"]), _abi.fptr(rays), rays.shape[0],
                                  _abi.u32ptr(out)))
+    return out
+
+
+def wide_census(nodes80, order, positions, rays):
+    """The census of the 8-wide walk (rto_wide_census): per ray, the largest number of node groups pending at once when the rule of
+    csrc/rt_wide.hip's wide_node_step walks 80-byte WideNode records, `nodes80` (n, 20) uint32 of bvh_wide_build_host or
+    DeviceScene.bvh_wide_dump. order[k]: the triangle of triangle record k; positions: the scene's (n_triangles, 9) float32. Boxes are tested in
+    float64 on the de-quantised planes, triangles by the oracle's own test; tests/deep_walks.py wide_census states the rule in full."""
+    nodes = np.ascontiguousarray(nodes80, dtype=np.uint32).reshape(-1, 20)
+    order = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 9)
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    out = np.zeros(rays.shape[0], dtype=np.uint32)
+    _check(lib().rto_wide_census(_abi.u32ptr(nodes), nodes.shape[0], _abi.u32ptr(order), order.shape[0], _abi.fptr(pos), pos.shape[0], _abi.fptr(rays),
+                                 rays.shape[0], _abi.u32ptr(out)))
     return out
 
 

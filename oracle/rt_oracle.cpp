@@ -1532,6 +1532,139 @@ int rto_dump_census(const uint32_t *nodes, uint32_t n_inner, const uint32_t *tri
     return RT_OK;
 }
 
+// Test aid: the census of the 8-WIDE walk. pending_out[i] = the largest number of node groups pending at once when the rule of the wide
+// closest-hit kernel (csrc/rt_wide.hip wide_node_step and the unwind of wf_extend_wide) walks 80-byte WideNode records (20 words: origin p in
+// words 0..2, cell exponents in bytes 12..14, inner-slot mask in byte 15, child_base, tri_base, tri_mask in words 4..6, the lower planes
+// [axis][slot] in bytes 32..55 and the upper ones in bytes 56..79), of rt_bvh_wide_build_host or rt_bvh_wide_dump. order[k] = the triangle
+// of triangle record k, positions = 9 floats per triangle. The rule:
+//   * the root is a pseudo-group of one slot; a group is {first inner child, pending priority bits, inner-slot mask};
+//   * a step takes the highest pending priority bit (a slot's priority is slot ^ oct_inv, oct_inv = 7 ^ the direction-sign octant) and pushes
+//     the rest of the group as ONE frame if any inner slot remains pending (one more group pending);
+//   * it tests the child's eight boxes against [EPS, best t]: the hit inner slots are the child's own group, and the triangles of the hit leaf
+//     slots are tested before the next step (intersect_avu, the oracle's own test; a closer t replaces best t);
+//   * a group with nothing pending pops the newest frame, which is NOT tested again against the best t found since.
+// The boxes are the de-quantised ones, p + q * 2^(e - 127), tested in float64 by (plane - o) * (1 / d), a component of |d| < 2^-60 taking
+// 1 / d = +-2^60 as in the kernel; an empty slot (neither inner nor holding a triangle) is never hit. The device tests conservative supersets
+// of these boxes with float32 FMAs, so its walk may enter a box this one does not: the counts are the device's only up to that.
+namespace {
+struct WideWalk {
+    const uint32_t *nodes, *order;
+    const float *pos;
+    uint32_t n_nodes, n_order, n_pos;
+    bool bad = false;
+    uint32_t walk(const float *ray) {
+        const double e = (double)EPS;
+        double o[3], id[3];
+        uint32_t oct = 0;
+        for (int a = 0; a < 3; ++a) {
+            const double d = (double)ray[3 + a];
+            o[a] = (double)ray[a];
+            id[a] = std::fabs(d) < 0x1p-60 ? std::copysign(0x1p60, d) : 1.0 / d;
+            oct |= id[a] < 0.0 ? 1u << a : 0u;
+        }
+        const uint32_t oct_inv = 7u ^ oct;
+        const Ray r{{ray[0], ray[1], ray[2]}, {ray[3], ray[4], ray[5]}};
+        float best = INFINITY;
+        struct Group {
+            uint32_t base, bits, imask;
+        };
+        std::vector<Group> stack;
+        Group g{0u, n_nodes ? 0x80u : 0u, 0u};
+        uint32_t most = 0, steps = 0;
+        for (;;) {
+            if (g.bits == 0u) {
+                if (stack.empty())
+                    return most;
+                g = stack.back();
+                stack.pop_back();
+                continue;
+            }
+            uint32_t bit = 7u;
+            while (!(g.bits >> bit & 1u))
+                --bit;
+            const uint32_t rest = g.bits ^ (1u << bit), slot = bit ^ oct_inv;
+            const uint32_t i = g.base + (uint32_t)__builtin_popcount(g.imask & ((1u << slot) - 1u));
+            if (rest) {
+                stack.push_back({g.base, rest, g.imask});
+                most = std::max(most, (uint32_t)stack.size());
+            }
+            if (i >= n_nodes || ++steps > n_nodes) { // a walk enters a node of a tree once at most
+                bad = true;
+                return most;
+            }
+            const uint32_t *nd = nodes + 20ull * i;
+            const uint8_t *b = reinterpret_cast<const uint8_t *>(nd);
+            float p[3];
+            std::memcpy(p, nd, sizeof(p));
+            const uint32_t imask = b[15], tri_mask = nd[6];
+            uint32_t h = 0;
+            for (uint32_t s = 0; s < 8; ++s) {
+                if (!(imask >> s & 1u) && !((tri_mask >> (3 * s)) & 7u))
+                    continue;
+                double tmin = e, tmax = (double)best;
+                for (int a = 0; a < 3; ++a) {
+                    const double cell = std::ldexp(1.0, (int)b[12 + a] - 127);
+                    const double t0 = (((double)p[a] + (double)b[32 + 8 * a + s] * cell) - o[a]) * id[a];
+                    const double t1 = (((double)p[a] + (double)b[56 + 8 * a + s] * cell) - o[a]) * id[a];
+                    tmin = std::max(tmin, id[a] < 0.0 ? t1 : t0);
+                    tmax = std::min(tmax, id[a] < 0.0 ? t0 : t1);
+                }
+                h |= tmin <= tmax ? 1u << s : 0u;
+            }
+            g = Group{nd[4], 0u, imask};
+            for (uint32_t s = 0; s < 8; ++s) {
+                if (!(h >> s & 1u))
+                    continue;
+                if (imask >> s & 1u) {
+                    g.bits |= 1u << (s ^ oct_inv);
+                    continue;
+                }
+                uint32_t k = nd[5] + (uint32_t)__builtin_popcount(tri_mask & ((1u << (3 * s)) - 1u));
+                for (uint32_t cnt = (uint32_t)__builtin_popcount((tri_mask >> (3 * s)) & 7u); cnt; --cnt, ++k) {
+                    if (k >= n_order || order[k] >= n_pos) {
+                        bad = true;
+                        return most;
+                    }
+                    const float *t = pos + 9ull * order[k];
+                    const V3 a{t[0], t[1], t[2]}, v{t[3], t[4], t[5]}, u{t[6], t[7], t[8]};
+                    V3 xs;
+                    if (intersect_avu(r, a, v - a, u - a, EPS, xs) && best > xs.z)
+                        best = xs.z;
+                }
+            }
+        }
+    }
+};
+} // namespace
+int rto_wide_census(const uint32_t *nodes, uint32_t n_nodes, const uint32_t *order, uint32_t n_order, const float *positions, uint32_t n_triangles,
+                    const float *rays, uint32_t n, uint32_t *pending_out) {
+    if ((n_nodes && !nodes) || (n_order && !order) || (n_triangles && !positions) || (n && (!rays || !pending_out))) {
+        g_err = "rto_wide_census: bad arguments";
+        return RT_ERR_INVALID_ARG;
+    }
+    std::atomic<bool> bad{false};
+    auto range = [&](uint32_t begin, uint32_t end) {
+        for (uint32_t i = begin; i < end; ++i) {
+            WideWalk w{nodes, order, positions, n_nodes, n_order, n_triangles};
+            pending_out[i] = w.walk(rays + 6ull * i);
+            if (w.bad)
+                bad = true;
+        }
+    };
+    const uint32_t n_workers = std::max(1u, std::min({16u, std::thread::hardware_concurrency(), n / 256u})); // rays are independent
+    std::vector<std::thread> workers;
+    for (uint32_t w = 1; w < n_workers; ++w)
+        workers.emplace_back(range, (uint32_t)((uint64_t)n * w / n_workers), (uint32_t)((uint64_t)n * (w + 1) / n_workers));
+    range(0, (uint32_t)((uint64_t)n / n_workers));
+    for (auto &t : workers)
+        t.join();
+    if (bad) {
+        g_err = "rto_wide_census: a child or triangle index points outside the records, or the records are no tree";
+        return RT_ERR_INVALID_ARG;
+    }
+    return RT_OK;
+}
+
 int rto_bg_at(rto_scene *s, const float *dirs, uint32_t n, float *rgb_out) {
     Integrator<RngXoshiro> it(*s, 1, 1, 1);
     for (uint32_t i = 0; i < n; ++i) {

@@ -12,6 +12,7 @@ Pending counts f (deferred far siblings at once) and the tier they enter:
   light walk    f >= 5   wf_shade's scratch half (4 LDS positions)            f >= 13  the probe's / megakernel's scratch half (12 LDS positions)
   closest hit   f >= 8   first eviction of wf_extend's 6-deep ring            f >= 14  the probe's / megakernel's scratch half (the newest frame
                          (newest frame in registers + 6 in LDS)                        is in registers, 12 in LDS)
+  8-wide walk   g >= 10  first eviction of wf_extend_wide's 8-deep ring (g counts pending node GROUPS: `wide_census`, the last part of the file)
 """
 import numpy as np
 
@@ -22,6 +23,12 @@ LIGHT_SHADE_SCRATCH = 5    # lights_pdf through StackMemT<4>: position 4 is the 
 LIGHT_PROBE_SCRATCH = 13   # lights_pdf through StackMemT<12>
 CLOSEST_RING_EVICT = 8     # wf_extend: registers + RingStackT<6>; the 8th pending frame evicts the oldest
 CLOSEST_PROBE_SCRATCH = 14 # cast_kernel / megakernel: registers + StackMemT<12>; the 14th pending frame goes to scratch
+# wf_extend_wide (csrc/rt_wide.hip): the newest pending group in registers (top_x, top_y), older ones in RingStackT<8, 2>, older still in the
+# global workspace. wide_node_step spills the previous top with stk.push(sp - 1, ...) when it stacks a group at sp > 0, and push finds the ring
+# full when pos - base == 8, base = 0: pos = 8 = sp - 1, so sp goes from 9 to 10. The 10th pending group is the first eviction, and every
+# refill from the workspace (pop_masked with pos < base) happens on the way back from there.
+WIDE_RING_EVICT = 10
+WIDE_CLAIM = 12            # what the tests assert: two groups past the first eviction (why: `wide_census`)
 
 # the two generated scenes every deep-walk test and stored answer uses
 BIG_LIGHTS = dict(n_lights=2000, size=6.0, seed=31)
@@ -133,13 +140,14 @@ def tier_shares(counts, thresholds):
     return {int(t): float((counts >= t).mean()) for t in thresholds}, int(counts.max(initial=0))
 
 
-def require_witnesses(what, counts, required):
+def require_witnesses(what, counts, required, tag="deep walks", unit="siblings", report=()):
     """Assert that the rays reach every tier a test claims: `required` maps a pending count to the least share of the rays that must reach
-    it. Prints the measured shares and the maximum (the tests run with -s where a report is wanted); returns them."""
-    shares, most = tier_shares(counts, required.keys())
-    print(f"[deep walks] {what}: most pending {most}; " + ", ".join(f"{100 * s:.1f} % of {len(counts)} rays reach f >= {t}" for t, s in shares.items()))
+    it. Prints the measured shares and the maximum (the tests run with -s where a report is wanted); returns them. `report`: further pending
+    counts whose shares are printed and returned without a claim; `tag`, `unit`: the line's prefix and what is counted."""
+    shares, most = tier_shares(counts, list(required.keys()) + [t for t in report if t not in required])
+    print(f"[{tag}] {what}: most pending {most}; " + ", ".join(f"{100 * s:.1f} % of {len(counts)} rays reach f >= {t}" for t, s in shares.items()))
     for t, need in required.items():
-        assert shares[int(t)] >= need, f"{what}: only {100 * shares[int(t)]:.2f} % of the rays keep {t} siblings pending, the test needs {100 * need:.0f} %"
+        assert shares[int(t)] >= need, f"{what}: only {100 * shares[int(t)]:.2f} % of the rays keep {t} {unit} pending, the test needs {100 * need:.0f} %"
     return shares, most
 
 
@@ -156,6 +164,8 @@ CORNER_CELL = CORNER_EXTENT / 1024.0
 CORNER_MAIN = dict(log2_soup=10, seed=61)    # 1 056 triangles: radix tree 41 deep, up to 40 frames pending
 CORNER_SECOND = dict(log2_soup=15, seed=62)  # 32 800 triangles: 46 deep, up to 45 pending
 CORNER_DEPTH = {10: 41, 15: 46}              # 30 Morton bits, the corner pin against the soup, log2_soup index bits
+CORNER_WIDE = dict(log2_soup=13, seed=62)    # 8 224 triangles: the HOST-collapsed 8-wide tree is 19 levels deep (CORNER_SECOND's: 22)
+CORNER_WIDE_DEPTH = {13: 19, 15: 22}         # levels of bvh_wide_build_host's tree (tests/test_wide_census.py pins them)
 
 
 def corner_ladder_scene(sg, log2_soup, seed, extent=CORNER_EXTENT):
@@ -211,6 +221,17 @@ def corner_rays(cell, n, seed):
     d = rng.uniform(0.3, 1.0, size=(n, 3))
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     return np.concatenate([o, d], axis=1).astype(np.float32)
+
+
+def octant_rays(cell, n, seed):
+    """corner_rays(cell, n, seed) with the direction of ray k turned into octant k % 8: bit a of k % 8 set = component a negative (the
+    octant numbering of csrc/rt_wide.hip wide_init). The 8-wide walk takes a node's slots in the order slot ^ octant, so every octant
+    is another visiting order of the same tree; the origins stay inside the soup."""
+    rays = corner_rays(cell, n, seed)
+    k = np.arange(n) % 8
+    for a in range(3):
+        rays[:, 3 + a] = np.where((k >> a) & 1, -rays[:, 3 + a], rays[:, 3 + a])
+    return rays
 
 
 def _spread10(v):
@@ -414,3 +435,111 @@ def dump_census_numpy(dump, rays, eps=1e-4, max_stack=256):
                 keep = ~finished
                 idx, o, d, cur = idx[keep], o[keep], d[keep], cur[keep]
     return most
+
+
+# ------------------------------------------------------------------------------------------------ the census of the 8-wide walk
+# A radix tree 41 deep does not make the 8-wide walk deep: a wide level absorbs about three binary levels, and the siblings along the radix
+# chain are single triangles, which the collapse keeps as LEAF slots of the chain's nodes, tested on the spot and never stacked (CORNER_MAIN:
+# 144 wide nodes on 10 levels, 5 groups pending at most). What keeps groups pending is a node with several INNER slots whose boxes all hold the
+# ray, level after level: the HOST-collapsed tree of the soup (bvh_wide_build_host over the reference's SAH tree) is 19 levels deep for 2^13
+# soup triangles and 22 for 2^15, and rays from inside the soup keep 12 to 19 groups pending in every direction octant.
+def wide_tree_order(tree):
+    """order[k] = the scene triangle of triangle record k: a host tree's "order", or word 9 of a dump's triangle records."""
+    return np.ascontiguousarray(tree["order"] if "order" in tree else tree["tris"][:, 9], dtype=np.uint32)
+
+
+def wide_census(tree, positions, rays):
+    """Per ray, the largest number of node groups pending at once when the rule of the 8-wide closest-hit kernel (csrc/rt_wide.hip
+    wide_node_step and the unwind of wf_extend_wide) walks the 80-byte WideNode records of `tree`: bvh_wide_build_host's result or
+    DeviceScene.bvh_wide_dump's, with `positions` the scene's triangles. The rule:
+      * the root is a pseudo-group of one slot; a group is {first inner child, pending priority bits, inner-slot mask};
+      * a step takes the highest pending priority bit; a slot's priority is slot ^ oct_inv, oct_inv = 7 ^ the direction-sign octant;
+      * the step pushes the rest of the group as ONE frame if any inner slot remains pending: one more group pending, however many slots;
+      * it then tests the child's eight boxes against [EPS, best.t]; the hit inner slots become the current group;
+      * the triangles of the hit leaf slots are tested before the next step (a closer t replaces best.t);
+      * a group with nothing pending pops the newest frame, which is not tested again against the best.t found since.
+    Boxes are tested in float64 on the de-quantised planes, p + q * 2^(e - 127), by (plane - o) * (1 / d), with 1 / d = +-2^60 for a
+    component below 2^-60 as in the kernel; an empty slot is never hit. Triangles are tested by the oracle's own test.
+    A pending count g means g - 1 groups behind the one in registers: the 10th (WIDE_RING_EVICT) evicts from the 8-deep LDS ring.
+    The DEVICE does not test these boxes: its planes are the same bytes, but the slab test is float32 FMAs with an explicit margin, so it
+    may enter a box this walk does not (never the reverse) and its count may differ by a box at one level or two. The tests therefore never
+    claim the eviction threshold itself: every claim is "share of rays at >= 12" (WIDE_CLAIM), two groups past the first eviction, so that
+    a walk which differs from this one by a group or two still evicts and refills.
+    The walk itself is the oracle's (oracle.wide_census, C++); `wide_census_numpy` states it a second time."""
+    import oracle
+
+    return oracle.wide_census(tree["nodes"], wide_tree_order(tree), positions, rays).astype(np.int64)
+
+
+def wide_tree_arrays(tree):
+    """The fields of (n, 20) uint32 WideNode records the walk reads: de-quantised lower and upper planes [node, axis, slot] in float64,
+    inner-slot mask, child_base, tri_base, tri_mask."""
+    nodes = np.ascontiguousarray(tree["nodes"], dtype=np.uint32).reshape(-1, 20)
+    b = nodes.view(np.uint8).reshape(-1, 80)
+    p = np.ascontiguousarray(nodes[:, 0:3]).view(np.float32).astype(np.float64)
+    cell = np.ldexp(1.0, b[:, 12:15].astype(np.int32) - 127)
+    lo = p[:, :, None] + b[:, 32:56].reshape(-1, 3, 8).astype(np.float64) * cell[:, :, None]
+    hi = p[:, :, None] + b[:, 56:80].reshape(-1, 3, 8).astype(np.float64) * cell[:, :, None]
+    return lo, hi, b[:, 15].astype(np.int64), nodes[:, 4].astype(np.int64), nodes[:, 5].astype(np.int64), nodes[:, 6].astype(np.int64)
+
+
+def wide_census_numpy(tree, positions, rays, eps=1e-4):
+    """wide_census restated in Python, one ray at a time (for a few hundred rays). Same rule, same arithmetic: float64 boxes, float32
+    triangle tests in the reference's operation order (`_det`), so the counts equal the C++ census ray for ray (tests/test_wide_census.py).
+    What does not depend on the walk is computed for the whole tree at once per ray (every slot's entry and exit parameter, every triangle
+    record's t); the walk then only compares them with the best t it has."""
+    lo, hi, imask, child_base, tri_base, tri_mask = wide_tree_arrays(tree)
+    order = wide_tree_order(tree).astype(np.int64)
+    tri = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3, 3)[order]  # in record order
+    ta, tv, tu = tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    eps32 = np.float32(eps)
+    most = np.zeros(len(rays), dtype=np.int64)
+    if len(lo) == 0:
+        return most
+    popcount = lambda v: bin(v).count("1")  # noqa: E731
+    imask, child_base, tri_base, tri_mask = imask.tolist(), child_base.tolist(), tri_base.tolist(), tri_mask.tolist()
+    for r, ray in enumerate(rays):
+        o32, d32 = ray[:3], ray[3:]
+        o, d = o32.astype(np.float64), d32.astype(np.float64)
+        with np.errstate(divide="ignore"):
+            idir = np.where(np.abs(d) < 2.0 ** -60, np.copysign(2.0 ** 60, d), 1.0 / d)
+        neg = idir < 0
+        oct_inv = 7 ^ int(neg[0] + 2 * neg[1] + 4 * neg[2])
+        t0, t1 = (lo - o[None, :, None]) * idir[None, :, None], (hi - o[None, :, None]) * idir[None, :, None]
+        enter = np.maximum(np.where(neg[None, :, None], t1, t0).max(axis=1), float(eps32)).tolist()  # [node][slot]
+        leave = np.where(neg[None, :, None], t0, t1).min(axis=1).tolist()
+        with np.errstate(all="ignore"):  # the reference's intersect_tri on every triangle record, float32
+            at, y = np.broadcast_to(-d32, tv.shape), o32 - ta
+            den = _det(tv, tu, at)
+            xb, xc, xt = _det(y, tu, at) / den, _det(tv, y, at) / den, _det(tv, tu, y) / den
+            tri_t = np.where((xb >= 0) & (xc >= 0) & (xb + xc <= 1) & (xt >= eps32), xt, np.float32(np.inf)).astype(np.float64).tolist()
+        best = float("inf")
+        stack = []
+        base, bits, inner = 0, 0x80, 0  # the root: one pending slot of a group whose children start at record 0
+        while True:
+            if bits == 0:
+                if not stack:
+                    break
+                base, bits, inner = stack.pop()
+                continue
+            bit = bits.bit_length() - 1
+            rest, slot = bits ^ (1 << bit), bit ^ oct_inv
+            i = base + popcount(inner & ((1 << slot) - 1))
+            if rest:
+                stack.append((base, rest, inner))
+                most[r] = max(most[r], len(stack))
+            base, bits, inner, tmask = child_base[i], 0, imask[i], tri_mask[i]
+            limit = best  # all eight boxes are tested before any triangle of the node
+            for s in range(8):
+                is_inner, n_tri = inner >> s & 1, popcount((tmask >> (3 * s)) & 7)
+                if not (is_inner or n_tri) or not enter[i][s] <= min(leave[i][s], limit):
+                    continue
+                if is_inner:
+                    bits |= 1 << (s ^ oct_inv)
+                else:
+                    first = tri_base[i] + popcount(tmask & ((1 << (3 * s)) - 1))
+                    best = min(best, min(tri_t[first : first + n_tri]))
+    return most
+
+

@@ -17,7 +17,9 @@ on an MI355X (the tests print theirs; run with -s):
     main     radix             41      48x32x2 primary rays     100 % at f >= 36           39
     second   radix             46      4 000 corner rays        100 % at f >= 40           45
     main     PLOC (no claim)   31      20 000 corner rays       -                          27
-    main     8-wide tree collapsed from the radix tree: 144 nodes on 10 levels
+    main     8-wide tree collapsed from the radix tree: 144 nodes on 10 levels; its WALK is shallow, 5 node groups pending at most (a wide
+             level absorbs about three binary levels and a chain's siblings are leaf slots): the ring of wf_extend_wide is never full
+             there. Wide walks beyond the ring: tests/test_gpu_deep_wide_walks.py
 
 Every comparison held on the first run: no hit differs from the oracle's in any bit, no tie, no pixel of the render differs.
 """
@@ -156,13 +158,17 @@ def test_renders_from_the_corner(main, gpu):
 def test_wide_tree_collapsed_from_the_deep_radix_tree(main, gpu):
     """The same radix tree as the input of the wide collapse (its dynamic program runs inside k_refit, along the 40-node chain), the device
     pack, and the level-by-level wide refit: wf_extend_wide and the wide packet kernel (one LDS stack level per tree level) under the
-    "superset" contract, and a refit to the arrays the scene was created from changes no hit and no node."""
+    "superset" contract, and a refit to the arrays the scene was created from changes no hit and no node. The depth asserted here is the
+    BINARY tree's: the wide walk on the collapsed tree is shallow (its census is printed, without a claim) and stays inside the LDS ring of
+    wf_extend_wide; tests/test_gpu_deep_wide_walks.py goes beyond it."""
     main.witnesses("corner rays (the binary tree the wide one is collapsed from)")
     op, ob = main.hits
     prod = gpu.DeviceScene(main.sc, wide=True, device_bvh=True, device_builder=gpu.RT_BUILDER_LBVH)
     try:
         before = prod.bvh_wide_dump()
         print(f"[deep trees] {main.name}: 8-wide tree of {len(before['nodes'])} nodes, {before['depth']} levels")
+        dw.require_witnesses(f"{main.name}, node groups pending in the wide walk (no claim)", dw.wide_census(before, main.sc.positions, main.rays), {},
+                             tag="deep trees", unit="groups", report=(dw.WIDE_RING_EVICT,))
         assert sorted(before["tris"][:, 9].tolist()) == list(range(main.sc.n_triangles))
         hits = {}
         for mode in (gpu.RT_CAST_EXTEND, gpu.RT_CAST_PACKET):

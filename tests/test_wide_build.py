@@ -26,6 +26,32 @@ def decode(nodes):
     )
 
 
+def assert_same_wide_tree(got, want):
+    """`got` (a DeviceScene.bvh_wide_dump) is the tree `want` (bvh_wide_build_host's result) record for record, up to the order the records
+    are numbered in: walked in parallel from the roots, every pair of nodes has the origin and exponents bit-equal, the same masks, all 48
+    plane bytes, its inner children in slot order and the same scene triangles in its leaf slots. Returns the levels of the tree walked."""
+    n_tris = len(want["order"])
+    assert len(got["nodes"]) == len(want["nodes"]) and len(got["tris"]) == n_tris
+    A, B = decode(got["nodes"]), decode(want["nodes"])
+    prim_a, prim_b = got["tris"][:, 9], want["order"]
+    assert sorted(got["tris"][:, 11].tolist()) == list(range(n_tris))  # DevTri::pad of a blob record: its DevTri / DevAttr index, each once
+    stack, seen, levels = [(0, 0, 1)], 0, 0
+    while stack:
+        a, b, level = stack.pop()
+        seen += 1
+        levels = max(levels, level)
+        assert np.array_equal(A["p"][a].view(np.uint32), B["p"][b].view(np.uint32)) and np.array_equal(A["e"][a], B["e"][b]), (a, b)
+        assert A["imask"][a] == B["imask"][b] and A["tri_mask"][a] == B["tri_mask"][b]
+        assert np.array_equal(A["qlo"][a], B["qlo"][b]) and np.array_equal(A["qhi"][a], B["qhi"][b])
+        n_inner, n_tri = bin(int(A["imask"][a])).count("1"), bin(int(A["tri_mask"][a])).count("1")
+        for r in range(n_inner):
+            stack.append((int(A["child_base"][a]) + r, int(B["child_base"][b]) + r, level + 1))
+        ta, tb = int(A["tri_base"][a]), int(B["tri_base"][b])
+        assert np.array_equal(prim_a[ta : ta + n_tri], prim_b[tb : tb + n_tri])
+    assert seen == len(want["nodes"])
+    return levels
+
+
 def walk_and_check(nodes, order, positions):
     """Returns (depth, triangles per leaf slot histogram). Raises AssertionError on any structural violation."""
     n_nodes, n_tris = len(nodes), len(order)
