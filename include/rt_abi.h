@@ -879,6 +879,78 @@ int rt_update_geometry_device(rt_scene *scene, const rt_geometry_update *upd);
  * host read per level). A measurement aid, like rt_build_times. RT_ERR_INVALID_ARG: a NULL argument; RT_ERR_UNSUPPORTED: a multi-GPU scene. */
 int rt_refit_times(const rt_scene *scene, double *refit_ms, double *levels_ms);
 
+/* Shutter accumulators: motion blur from two geometry keys and two views (additive; RT_ABI_VERSION stays 4). rt_accum_attach_shutter gives an
+ * accumulator a shutter: the time of a sample is a pure function of its sample index, all samples of one time are rendered against the scene
+ * updated to that time, and the accumulator adds them in sample order as it always does. No closest-hit kernel knows about time. The layer
+ * keeps no sums of its own; it combines with RT_ACCUM_FEATURES, ids, light groups and sensor accumulators, on every single-GPU tree kind.
+ * The rule, operation by operation: IEEE binary32 evaluated as written, no contraction. K = slices, B = block.
+ *   Slice of a sample. For sample index s of any pixel: j = (s / B) mod K (integers); k = the log2(K) low bits of j in reverse order. With
+ *     this order every power-of-two number of consecutive blocks of a progressive render covers the shutter evenly.
+ *   Time of a slice. t_k = open + (close - open) * (((float)k + 0.5f) / (float)K).
+ *   Geometry at t. For every float x of positions, normals and tangents, with x0 and x1 its values in key 0 and key 1:
+ *       b = x0 + t * (x1 - x0)                       (three roundings)
+ *       lo = x0 <= x1 ? x0 : x1;   hi = x0 <= x1 ? x1 : x0
+ *       x(t) = !(b > lo) ? lo : (!(b < hi) ? hi : b)
+ *     the blend held between the keys by comparisons alone. So every slice lies inside the union of the keys' bounds in floats, not only
+ *     in real numbers (at t = 1 the unclamped b can leave [x0, x1]); a b that is NaN (keys of opposite sign whose difference overflows)
+ *     gives lo; equal keys give key 0's bits, the sign of a zero included. Texcoords and material ids are the descriptor's at every t.
+ *   Sensor at t (on the host; sensor1 == NULL: the accumulator's own view, untouched, at every t). P, fov_x, half_width, lens_radius and
+ *     focus_distance are b of the same expression, without the clamp. R, U and F are blended per component in the same way, then each
+ *     vector (x, y, z) is divided, component by component, by sqrtf(x*x + y*y + z*z), for R, U, F in that order. Kind and seed are sensor
+ *     0's. The record is then made like any other (rt_sensor above). Two keys describe small rotations only: the blended axes are unit
+ *     vectors but orthogonal only to first order in the angle between the keys.
+ *   Rendering. rt_accum_render on an accumulator that holds n samples per pixel cuts the call's sample range [n, n + samples) into maximal
+ *     runs of one slice (K = 1: the whole call). For each run it installs slice k: the geometry exactly as
+ *     rt_update_geometry_device(the arrays at t_k, mode) leaves a scene, and the sensor record at t_k; then it adds the run's samples to every
+ *     pixel as rt_accum_render does, with every layer the accumulator keeps. Sample s of pixel p is seeded from (seed, p, s) as ever.
+ *     rt_stats of such a call: the counters and passes sum over its runs; kernel_ms spans the slice changes between them as well.
+ *   On return from rt_accum_attach_shutter and from every render call the scene is what rt_update_geometry_device(key 0, mode) leaves, and
+ *     the view the accumulator's own: every other entry point sees key 0. With n_triangles == 0 the geometry is never touched.
+ * Exactness (in place of the accumulators' sentence): after any sequence of calls, S_p is the in-order binary32 sum over s < n of X(p, s),
+ *   where X(p, s) is sample s of pixel p of rt_render_sensors with sensor(t_k) on a scene updated to geometry(t_k) in that mode, k the slice of
+ *   s; E_p likewise over even s; n_p = n for every pixel; the sums of the other layers likewise. Consequences, bit for bit: K = 1 is a plain
+ *   accumulator on the blended static scene; equal keys and sensor1 == NULL are a plain accumulator on a scene updated with key 0; how
+ *   `samples` is split over calls changes nothing. The accumulator's packet policy is kept across slices (scheduling independence).
+ * Cost. A slice change is one streaming blend plus rt_update_geometry_device's work without its pointer checks. When no emissive triangle (by
+ *   material_ids) has a position float whose keys differ in any bit, an RT_UPDATE_REFIT slice skips the light half of the update (a list
+ *   across the bus, a host build, a tree back): the tree it would build is key 0's bit for bit. Choose B so that a run's render time
+ *   dominates the change (DESIGN.md "Shutter" quotes the measured figures).
+ * rt_accum_attach_shutter: once per accumulator, before any call has added samples to it, on a scene whose only live accumulator it is. The
+ *   keys are copied to device memory the accumulator owns (with RT_FLAG_DEVICE_FB they are device arrays under rt_update_geometry_device's
+ *   buffer rules); the caller keeps theirs.
+ *   RT_ERR_INVALID_ARG: a NULL argument; a second attach; an attach after samples were queued; another live accumulator on the scene;
+ *     n_triangles neither 0 nor the scene's; a NULL array with n_triangles > 0; a misaligned device array or one that is not device memory of
+ *     the scene's GPU; a non-finite position or a material id out of range in either key (found by the update's check kernel, lowest triangle
+ *     named); K not a power of two in 1..1024; B == 0; !(0 <= open <= close <= 1); an unknown mode; a flag other than RT_FLAG_DEVICE_FB;
+ *     sensor1 of another kind than the accumulator's view, or one rt_render_sensors refuses; a non-zero reserved word. Also:
+ *     rt_accum_create* on a scene while an accumulator with a shutter lives. rt_update_geometry* keeps refusing the scene while any lives.
+ *   RT_ERR_UNSUPPORTED: rt_accum_render_adaptive on an accumulator with a shutter (per-pixel counts would put one pass at several times);
+ *     what rt_update_geometry refuses in that mode: RT_UPDATE_REFIT without RT_BUILD_WIDE, either key outside the wide tree's exponent range.
+ *   After any refusal the scene and the accumulator are unchanged. (The exponent range has a lower end too: keys that cross so that a slice's
+ *   extent collapses below 2^-52 where neither key's does make that render call return RT_ERR_UNSUPPORTED, with key 0 installed again.)
+ * rt_accum_shutter_times: of the last rt_accum_render call, *slice_changes the slices it installed and *slice_change_ms their wall time in
+ *   all (blend, update, sensor upload; the return to key 0 is not counted). A measurement aid, like rt_refit_times.
+ * rt_accum_shutter_info: *static_lights 1 when the light half is skipped as described; *light_rebuilds the installs since attach, slices and
+ *   returns to key 0, that built a light tree. Both: RT_ERR_INVALID_ARG for a NULL argument or an accumulator without a shutter. */
+typedef struct rt_shutter_desc {
+    uint32_t n_triangles;         /* the scene's, or 0: the geometry does not move (a camera-only shutter; every scene kind) */
+    uint32_t mode;                /* RT_UPDATE_REFIT (RT_BUILD_WIDE scenes) or RT_UPDATE_REBUILD: how a slice's geometry is installed */
+    const float *positions[2];    /* key 0 (t = 0) and key 1 (t = 1), 9*n floats each */
+    const float *normals[2];      /* 9*n each */
+    const float *tangents[2];     /* 9*n each */
+    const float *texcoords;       /* 6*n: not interpolated */
+    const uint32_t *material_ids; /* n: not interpolated */
+    const rt_sensor *sensor1;     /* the view at t = 1; NULL: the view does not move. The accumulator's own view is t = 0; same kind required */
+    float open, close;            /* 0 <= open <= close <= 1 */
+    uint32_t slices;              /* K: a power of two, 1..1024 */
+    uint32_t block;               /* B >= 1: consecutive samples that share a slice */
+    uint32_t flags;               /* 0: host arrays; RT_FLAG_DEVICE_FB: device arrays on the scene's GPU, 4-byte aligned, idle on entry */
+    uint32_t reserved[7];         /* 0 */
+} rt_shutter_desc;                /* 128 bytes */
+int rt_accum_attach_shutter(rt_accum *acc, const rt_shutter_desc *desc);
+int rt_accum_shutter_times(rt_accum *acc, double *slice_change_ms, uint32_t *slice_changes);
+int rt_accum_shutter_info(rt_accum *acc, uint32_t *static_lights, uint32_t *light_rebuilds);
+
 /* Image-based lighting: a float radiance map as the scene's environment, optionally importance-sampled (additive; RT_ABI_VERSION stays 4).
  * rt_create's bg_texture is the reference's Scene::bg: an 8-bit texture with gamma, which clips an .hdr file to [0, 1]. rt_set_environment
  * replaces that lookup by a float map for a built scene. The texels are copied to device memory (float4 each); the caller keeps `rgb`.

@@ -80,6 +80,7 @@ from ._ctypes_abi import (
     RtRay,
     RtSceneDesc,
     RtSensor,
+    RtShutterDesc,
     RtView,
     RtStats,
     bind,
@@ -484,14 +485,16 @@ class DeviceScene:
         _check(lib().rt_update_geometry_device(self._h, C.byref(u)))
 
     def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False, sensor=None, ids=None,
-                    id_slots: int = 4, light_groups=None) -> "Accumulator":
+                    id_slots: int = 4, light_groups=None, shutter=None) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
         RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view. `features`: keep the first-hit
         albedo / normal / depth sums as well (rt_accum_create_ex with RT_ACCUM_FEATURES), which features(), read_features() and denoise() need.
         `sensor`: a Sensor in place of `camera` and `seed` (rt_accum_create_sensor): pixel p is then render_sensors(samples = n_p) of it.
         `ids` (not None): Accumulator.attach_ids(ids, slots=id_slots) on the new accumulator, for read_ids(), labels() and matte().
         `light_groups` (not None): Accumulator.attach_light_groups on the new accumulator, for read_light_groups(), light_group() and
-        light_mix(): the group of every material (an array), or a dict of attach_light_groups' arguments."""
+        light_mix(): the group of every material (an array), or a dict of attach_light_groups' arguments.
+        `shutter` (not None): a dict of Accumulator.attach_shutter's arguments (key0, key1, sensor1, open, close, slices, block, refit): motion
+        blur between two geometry keys and two views."""
         if sensor is not None and camera is not None:
             raise ValueError("accumulator: give a camera or a sensor, not both (the sensor carries its camera and seed)")
         acc = Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0, sensor=sensor)
@@ -500,6 +503,8 @@ class DeviceScene:
                 acc.attach_ids(ids, slots=id_slots)
             if light_groups is not None:
                 acc.attach_light_groups(**(light_groups if isinstance(light_groups, dict) else {"material_group": light_groups}))
+            if shutter is not None:
+                acc.attach_shutter(**shutter)
         except Exception:
             acc.close()
             raise
@@ -1114,6 +1119,71 @@ class Accumulator:
         w = np.ascontiguousarray(w)
         fn = lib().rt_accum_resolve_light_mix_rgb8 if rgb8 else lib().rt_accum_resolve_light_mix
         return self._output(lambda flags, p: fn(self._h, fptr(w), flags, p), np.uint8 if rgb8 else np.float32, device_out=device_out)
+
+    def attach_shutter(self, key0=None, key1=None, sensor1=None, open: float = 0.0, close: float = 1.0, slices: int = 16, block: int = 4,
+                       refit: bool = True, reserved=None) -> None:
+        """rt_accum_attach_shutter (include/rt_abi.h states the rule): sample s is rendered at time t_k of slice k = bitreverse((s // block) %
+        slices), on the scene blended between `key0` (t = 0) and `key1` (t = 1) and through the view blended between the accumulator's own and
+        `sensor1` (a Sensor of the same kind; None: the view does not move). A key is a scenegen.Scene, a LoadedScene or an arrays dict as
+        update_geometry takes them, or a dict of contiguous torch CUDA tensors (positions, normals, texcoords, tangents, material_ids) as
+        update_geometry_device takes them; both keys of one kind. Texcoords and material ids are key 0's. Both keys None: a camera-only
+        shutter, the geometry is never touched. `refit`: install a slice with RT_UPDATE_REFIT (RT_BUILD_WIDE scenes) instead of
+        RT_UPDATE_REBUILD. Once, before the first render; afterwards and after every render the scene is key 0's."""
+        d = RtShutterDesc()
+        d.mode = RT_UPDATE_REFIT if refit else RT_UPDATE_REBUILD
+        d.open, d.close, d.slices, d.block = float(open), float(close), int(slices), int(block)
+        for i, r in enumerate(reserved or ()):
+            d.reserved[i] = int(r)
+        keep = []
+        if (key0 is None) != (key1 is None):
+            raise ValueError("attach_shutter: give both geometry keys or neither")
+        if key0 is not None:
+            keys, on_device = [], None
+            for key in (key0, key1):
+                dev_key = isinstance(key, dict) and any(hasattr(v, "data_ptr") for v in key.values())
+                if on_device is not None and dev_key != on_device:
+                    raise ValueError("attach_shutter: one key is on the device and the other is not")
+                on_device = dev_key
+                if dev_key:
+                    import torch
+
+                    for name, per, dtype in GEOMETRY_ARRAYS:
+                        a = key[name]
+                        if not a.is_cuda or not a.is_contiguous() or (dtype == np.float32 and a.dtype != torch.float32) or a.element_size() != 4:
+                            raise TypeError(f"attach_shutter: {name} must be a contiguous 4-byte torch CUDA tensor")
+                    torch.cuda.current_stream(key["positions"].device).synchronize()  # the idle precondition
+                    keys.append({name: (key[name].data_ptr() if key[name].numel() else 0, key[name].numel() // per) for name, per, _ in GEOMETRY_ARRAYS})
+                else:
+                    arrays = geometry_arrays(key)
+                    keep.append(arrays)
+                    keys.append({name: (arrays[name].ctypes.data if arrays[name].size else 0, arrays[name].size // per) for name, per, _ in GEOMETRY_ARRAYS})
+            counts = {n for k in keys for _, n in k.values()}
+            if len(counts) != 1:
+                raise ValueError(f"attach_shutter: the arrays of the keys hold different triangle counts {sorted(counts)}")
+            d.n_triangles = counts.pop()
+            d.flags = RT_FLAG_DEVICE_FB if on_device else 0
+            for i in range(2):
+                d.positions[i], d.normals[i], d.tangents[i] = keys[i]["positions"][0], keys[i]["normals"][0], keys[i]["tangents"][0]
+            d.texcoords, d.material_ids = keys[0]["texcoords"][0], keys[0]["material_ids"][0]
+        if sensor1 is not None:
+            rec = make_sensors([sensor1])
+            keep.append(rec)
+            d.sensor1 = C.cast(rec, C.POINTER(RtSensor))
+        _check(lib().rt_accum_attach_shutter(self._h, C.byref(d)))
+
+    def shutter_times(self) -> dict:
+        """rt_accum_shutter_times: of the last render() call, "slice_changes" (the slices it installed) and "slice_change_ms" (their wall time
+        in all)."""
+        ms, n = C.c_double(0), C.c_uint32(0)
+        _check(lib().rt_accum_shutter_times(self._h, C.byref(ms), C.byref(n)))
+        return {"slice_change_ms": float(ms.value), "slice_changes": int(n.value)}
+
+    def shutter_info(self) -> dict:
+        """rt_accum_shutter_info: "static_lights" (no emissive triangle moves: a refit slice skips the light half of the update) and
+        "light_rebuilds" (installs since attach that built a light tree)."""
+        st, n = C.c_uint32(0), C.c_uint32(0)
+        _check(lib().rt_accum_shutter_info(self._h, C.byref(st), C.byref(n)))
+        return {"static_lights": bool(st.value), "light_rebuilds": int(n.value)}
 
     def close(self) -> None:
         if self._h:

@@ -230,6 +230,28 @@ class RtGeometryUpdate(C.Structure):  # rt_update_geometry: the five per-triangl
     ]
 
 
+class RtShutterDesc(C.Structure):  # rt_accum_attach_shutter: two geometry keys, a second view, the shutter interval and its slices (128 bytes)
+    _fields_ = [
+        ("n_triangles", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("positions", C.c_void_p * 2),
+        ("normals", C.c_void_p * 2),
+        ("tangents", C.c_void_p * 2),
+        ("texcoords", C.c_void_p),
+        ("material_ids", C.c_void_p),
+        ("sensor1", C.POINTER(RtSensor)),
+        ("open", C.c_float),
+        ("close", C.c_float),
+        ("slices", C.c_uint32),
+        ("block", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 7),
+    ]
+
+
+assert C.sizeof(RtShutterDesc) == 128
+
+
 class RtEnvironment(C.Structure):  # rt_set_environment: a float radiance map (24 bytes)
     _fields_ = [
         ("width", C.c_uint32),
@@ -342,6 +364,9 @@ ABI_PROTOTYPES = {
     "rt_update_geometry": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),
     "rt_update_geometry_device": (C.c_int, [C.c_void_p, C.POINTER(RtGeometryUpdate)]),  # the five pointers are device pointers
     "rt_refit_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rt_accum_attach_shutter": (C.c_int, [C.c_void_p, C.POINTER(RtShutterDesc)]),
+    "rt_accum_shutter_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    "rt_accum_shutter_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_set_environment": (C.c_int, [C.c_void_p, C.POINTER(RtEnvironment)]),  # NULL: back to the creation background
     "rt_env_pdf": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, c_float_p]),
     "rt_env_sample": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, c_float_p]),

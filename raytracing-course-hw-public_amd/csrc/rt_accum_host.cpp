@@ -25,6 +25,8 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create: image size " + std::to_string(width) + "x" + std::to_string(height));
     if (s->group)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_accum_create: accumulators run on single-GPU scenes only");
+    if (s->shutter_accums)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_create: the scene has an accumulator with a shutter, which moves its geometry: destroy it first");
     HIP_TRY(hipSetDevice(s->device));
     auto a = std::make_unique<rt_accum>();
     a->scene = s;
@@ -33,10 +35,13 @@ static int accum_create(rt_scene *s, uint32_t width, uint32_t height, const rt_c
     if (sensor) {
         if (int rc = rt::check_sensor(*sensor, width, height, "rt_accum_create_sensor"); rc != RT_OK)
             return rc;
-        a->sensor = rt::make_sensor(*sensor, width, height);
-    } else {
-        a->sensor = rt::make_sensor(camera ? *camera : s->cam, seed, width, height);
+        a->sensor_desc = *sensor;
+    } else { // the pinhole record of {camera, seed}, as rt::make_sensor(camera, seed) states it
+        a->sensor_desc.camera = camera ? *camera : s->cam;
+        a->sensor_desc.kind = RT_SENSOR_PINHOLE;
+        a->sensor_desc.seed = seed;
     }
+    a->sensor = rt::make_sensor(a->sensor_desc, width, height);
     const size_t n = (size_t)width * height;
     auto alloc = [&]<class T>(size_t bytes, T **ptr) -> int { return rt::accum_alloc(a.get(), bytes, ptr, "rt_accum_create"); };
     rt::AccumRound &R = a->R;
@@ -172,11 +177,30 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
         }
     };
 
+    // the uniform step: `samples` more for every pixel
+    auto uniform = [&](uint32_t samples) -> int {
+        HIP_TRY(rt::launch_accum_uniform(a->R, samples, s->stream));
+        bool any = false;
+        return fill(samples, &any);
+    };
+    // ... of an accumulator with a shutter (rt_abi.h rt_accum_attach_shutter): the call's sample range in maximal runs of one slice, each
+    // through the uniform step on the scene and the view of its slice; then key 0 again, whatever happened
+    auto shutter_runs = [&]() -> int {
+        rt::Shutter &H = *a->shutter;
+        H.change_ms = 0, H.changes = 0;
+        int rc = RT_OK;
+        for (uint64_t n = H.n_samples, end = n + p->samples; n < end && rc == RT_OK;) {
+            const uint32_t len = (uint32_t)(H.slices == 1 ? end - n : std::min<uint64_t>(end - n, H.block - n % H.block));
+            if ((rc = rt::shutter_install(a, (int)rt::shutter_slice(H, n))) == RT_OK && (rc = uniform(len)) == RT_OK)
+                H.n_samples = n += len;
+        }
+        const int back = rt::shutter_install(a, -1);
+        return rc != RT_OK ? rc : back;
+    };
+
     auto rounds_of_call = [&]() -> int {
         if (!ad) {
-            HIP_TRY(rt::launch_accum_uniform(a->R, p->samples, s->stream));
-            bool any = false;
-            if (int rc = fill(p->samples, &any); rc != RT_OK)
+            if (int rc = a->shutter ? shutter_runs() : uniform(p->samples); rc != RT_OK)
                 return rc;
         } else {
             const uint32_t mn = ad->min_samples ? ad->min_samples : 16u, st = ad->step ? ad->step : 32u, mx = ad->max_samples; // rt_abi.h rt_adaptive
@@ -221,6 +245,8 @@ extern "C" int rt_accum_render_adaptive(rt_accum *acc, const rt_params *params, 
         return rc;
     if (!ad)
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render_adaptive: null argument");
+    if (acc->shutter)
+        return rt::fail(RT_ERR_UNSUPPORTED, "rt_accum_render_adaptive: the accumulator has a shutter; per-pixel sample counts would put one pass at several times");
     if (!(ad->threshold >= 0.0f) || std::isinf(ad->threshold))
         return rt::fail(RT_ERR_INVALID_ARG, "rt_accum_render_adaptive: threshold must be finite and >= 0");
     const uint32_t mn = ad->min_samples ? ad->min_samples : 16u;

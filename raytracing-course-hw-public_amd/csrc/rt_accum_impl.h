@@ -6,12 +6,34 @@
 #include <optional>
 
 #include "rt_scene_impl.h"
+#include "rt_shutter.h"
+
+namespace rt {
+// rt_accum_attach_shutter's layer (rt_accum_shutter.cpp): the two keys and the scratch triple on the device, the second view, the call's
+// bookkeeping. Unlike the other layers it adds no sums: it decides which scene and which view a sample is rendered with.
+struct Shutter {
+    uint32_t n = 0;                  // triangles of the keys; 0: the geometry does not move
+    uint32_t mode = RT_UPDATE_REBUILD, slices = 1, block = 1;
+    float open = 0.0f, close = 1.0f;
+    ShutterArrays key[2], blend;     // positions / normals / tangents of key 0, key 1 and of the slice being rendered
+    float *uv = nullptr;             // not interpolated
+    uint32_t *mat = nullptr;
+    bool static_lights = false;      // no emissive triangle's position keys differ in a bit: every slice's light tree is key 0's
+    bool has_sensor1 = false;
+    rt_sensor sensor1{};
+    uint64_t n_samples = 0;          // n: the samples every pixel holds
+    double change_ms = 0;            // rt_accum_shutter_times: the slice installs of the last render call ...
+    uint32_t changes = 0;            // ... and how many there were
+    uint32_t light_rebuilds = 0;     // installs since attach (slices and key 0) that built a light tree
+};
+} // namespace rt
 
 struct rt_accum {
     rt_scene *scene = nullptr;
     uint32_t width = 0, height = 0;
     WfSensor sensor{};            // its camera: rt_accum_create_sensor's, or the pinhole record of {camera, seed} (host copy of d_sensor)
     WfSensor *d_sensor = nullptr; // WfLaunch::sensors of its passes: the one record
+    rt_sensor sensor_desc{};      // what `sensor` was made of: the view at t = 0 of a shutter
     rt::AccumRound R{};
     rt::DevArena owned{16};
     rt::PacketPolicy pkt; // of its own passes, kept apart from rt_render's
@@ -20,6 +42,7 @@ struct rt_accum {
     std::optional<WfFeat> features; // RT_ACCUM_FEATURES: the four first-hit sums
     std::optional<WfIds> ids;       // rt_accum_attach_ids: the per-pixel id tables
     std::optional<WfGroups> groups; // rt_accum_attach_light_groups: the group sums and the material table
+    std::optional<rt::Shutter> shutter; // rt_accum_attach_shutter: the keys (no sums of its own)
     rt::DenoiseBufs D{};            // rt_accum_denoise's workspace (64 B per pixel), allocated by its first call
     rt::DevBuf<uint32_t> matte_set; // rt_accum_resolve_matte's id set on the device
     bool has_samples = false; // a call has queued a pass of this accumulator: ids and light groups can no longer be attached
@@ -28,6 +51,8 @@ struct rt_accum {
         (void)hipStreamSynchronize(scene->stream); // `owned` frees after this body: on this device, behind this synchronise
         if (counted)
             --scene->live_accums;
+        if (shutter)
+            --scene->shutter_accums;
     }
     bool counted = false; // it is one of scene->live_accums
 };
@@ -54,6 +79,10 @@ inline int accum_entry(const rt_accum *acc, const char *fn, AccumNeed need) {
         return fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no light groups (rt_accum_attach_light_groups)");
     return RT_OK;
 }
+// rt_accum_shutter.cpp: the scene and the accumulator's view at slice k of its shutter (k < 0: key 0 and the accumulator's own view, what every
+// call leaves behind), and the slice of sample index s
+int shutter_install(rt_accum *a, int k, bool keep_static_lights = true);
+uint32_t shutter_slice(const Shutter &H, uint64_t s);
 // "flags other than RT_FLAG_DEVICE_FB": the one flag an accumulator's reads and tables take
 inline bool other_flags(uint32_t flags) { return (flags & ~(uint32_t)RT_FLAG_DEVICE_FB) != 0; }
 

@@ -100,6 +100,7 @@ struct rt_scene {
     std::shared_ptr<const rt::PreparedScene> prep; // the host half of rt_create, shared by the replicas of a multi-GPU scene
     std::shared_ptr<const rt::PreparedGeometry> geo; // its geometry half: prep->geo until rt_update_geometry replaces it
     uint32_t live_accums = 0;  // accumulators of this scene (rt_accum_create* / rt_accum_destroy): their sums pin the geometry
+    uint32_t shutter_accums = 0; // ... of which have a shutter (rt_accum_attach_shutter): it moves the geometry, so it must be the only one
     bool refitted = false;     // the wide tree was refitted: the binary tree it was collapsed from no longer describes the scene
     rt::HostBvh rebuilt_bvh;   // device-built scene BVH: the reference-style node list, reconstructed from HBM on demand
     bool device_built = false; // scene BVH built by rt_bvh_device.hip
@@ -292,6 +293,13 @@ int upload_geometry(rt_scene *s, const rt_scene_desc *d, const PreparedScene &PS
                     const DeviceArrays *arrays = nullptr);
 void install_geometry(rt_scene *s, GeometryOnDevice &g);
 uint32_t light_lds_inner(const FlatBvh &f); // DevBvh::lds_inner of a light tree
+// rt_update.cpp: the update from device arrays behind rt_update_geometry_device's argument checks, and those of its checks a shutter
+// accumulator (rt_accum_shutter.cpp) makes of its keys at attach
+struct UpdateScan;
+std::vector<uint8_t> emissive_materials(const PreparedScene &P); // one byte per material: does it emit?
+int check_device_pointers(const rt_scene *s, const rt_geometry_update *u);
+int refuse_device_arrays(rt_scene *s, const rt_geometry_update *u, const std::string &fn, UpdateScan *scan);
+int update_from_device_arrays(rt_scene *s, const rt_geometry_update *u, bool keep_lights);
 // rt_render.cpp: the checks of rt_params, the wavefront pass policy, the pass loop and the statistics of a finished call
 void set_camera(DevScene &D, const float *pos, const float *right, const float *up, const float *fwd);
 int check_pass_params(const rt_params *p, const char *fn);

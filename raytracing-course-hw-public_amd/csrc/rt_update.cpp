@@ -17,6 +17,15 @@
 #include "rt_wide_refit.h"
 #include "wide_grid.h"
 
+std::vector<uint8_t> rt::emissive_materials(const rt::PreparedScene &P) {
+    std::vector<uint8_t> em(P.mats.size());
+    for (size_t i = 0; i < em.size(); ++i) {
+        const float *e = P.mats[i].emission;
+        em[i] = !((e[0] == 0) & (e[1] == 0) & (e[2] == 0));
+    }
+    return em;
+}
+
 namespace {
 
 // The checks of the two entry points, in the order both make them. `fn` names the entry point in the message.
@@ -92,14 +101,7 @@ rt_scene_desc geometry_desc(const rt_scene *s, const rt_geometry_update *u) {
     return d;
 }
 
-std::vector<uint8_t> emissive_materials(const rt::PreparedScene &P) {
-    std::vector<uint8_t> em(P.mats.size());
-    for (size_t i = 0; i < em.size(); ++i) {
-        const float *e = P.mats[i].emission;
-        em[i] = !((e[0] == 0) & (e[1] == 0) & (e[2] == 0));
-    }
-    return em;
-}
+using rt::emissive_materials;
 
 // The new buffers from a prepared geometry half, beside the live ones; then swap and free. `arrays`: see rt::upload_geometry.
 int rebuild_from(rt_scene *s, const rt_scene_desc &d, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::DeviceArrays *arrays, const std::string &fn) {
@@ -126,7 +128,8 @@ int rebuild(rt_scene *s, const rt_scene_desc &d, const std::string &fn) {
 }
 
 // The refit proper, from arrays on the device and the light half prepared on the host: `in` has the five arrays and the bounds of their
-// vertices, `G` the light tree and its records.
+// vertices, `G` the light tree and its records (null: the light tree, its records and s->geo stay as they are; the caller knows that the
+// tree `G` would hold is the live one bit for bit).
 int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::RefitInput &in, const std::string &fn);
 
 int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
@@ -171,7 +174,7 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
         HIP_TRY(hipStreamSynchronize(s->stream));
         return RT_OK;
     };
-    if (int rc = upload_lights(); rc != RT_OK) {
+    if (int rc = G ? upload_lights() : RT_OK; rc != RT_OK) {
         (void)hipStreamSynchronize(s->stream); // before `lg` frees what the copies write
         return rc;
     }
@@ -185,26 +188,29 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
         return rt::hip_fail(e, fn + ": " + what);
     }
     // ---- host: what the launches read of the tree besides the blob
-    const rt::FlatBvh &f = G->flat[1];
-    DevBvh &L = D.lights;
-    const DevNode *ln = lg.lights.nodes;
-    const DevTri *lt = lg.lights.tris;
-    L = DevBvh{};
-    L.nodes = ln;
-    L.tris = lt;
-    L.root = f.root;
-    L.n_tris = (uint32_t)f.tris.size();
-    L.fast_ok = f.fast_ok ? 1u : 0u;
-    L.lds_inner = rt::light_lds_inner(f);
-    D.light_aux = lg.light_aux;
-    s->dev_n_inner[1] = (uint32_t)f.nodes.size();
-    s->light_owned = std::move(lg.light_owned); // frees the old light buffers
+    if (G) {
+        const rt::FlatBvh &f = G->flat[1];
+        DevBvh &L = D.lights;
+        const DevNode *ln = lg.lights.nodes;
+        const DevTri *lt = lg.lights.tris;
+        L = DevBvh{};
+        L.nodes = ln;
+        L.tris = lt;
+        L.root = f.root;
+        L.n_tris = (uint32_t)f.tris.size();
+        L.fast_ok = f.fast_ok ? 1u : 0u;
+        L.lds_inner = rt::light_lds_inner(f);
+        D.light_aux = lg.light_aux;
+        s->dev_n_inner[1] = (uint32_t)f.nodes.size();
+        s->light_owned = std::move(lg.light_owned); // frees the old light buffers
+    }
     D.scene.grid = grid;
     for (int k = 0; k < 3; ++k)
         rt::sort_bounds_axis(in.lo[k], in.hi[k], D.bounds_lo[k], D.bounds_inv[k]);
     s->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_refit).count();
     s->refit_levels_ms = levels_ms;
-    s->geo = G; // (its host_bvh[0] / wide are empty: the tree the wide one was collapsed from no longer describes the scene)
+    if (G)
+        s->geo = G; // (its host_bvh[0] / wide are empty: the tree the wide one was collapsed from no longer describes the scene)
     s->refitted = true;
     ++s->geo_generation; // records rewritten in place: nothing derived from the old ones may be used again
     return RT_OK;
@@ -213,7 +219,8 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
 // ------------------------------------------------------------------------------------------------ arrays that are on the device already
 // "device memory of the scene's GPU": first and last byte of each array, by hipPointerGetAttributes (an unregistered host pointer is an error
 // or hipMemoryTypeUnregistered, depending on the runtime; pinned host memory is hipMemoryTypeHost; both are refused before any launch)
-int check_device_pointers(const rt_scene *s, const rt_geometry_update *u) {
+} // namespace
+int rt::check_device_pointers(const rt_scene *s, const rt_geometry_update *u) {
     const size_t n = u->n_triangles;
     const struct {
         const void *p;
@@ -230,6 +237,8 @@ int check_device_pointers(const rt_scene *s, const rt_geometry_update *u) {
         }
     return RT_OK;
 }
+namespace {
+using rt::check_device_pointers;
 
 // the light half of a PreparedGeometry from the scan's compacted lights (rt::prepare_lights states why the tree is the host path's)
 int lights_from_scan(const rt::UpdateScan &scan, uint32_t n, rt::PreparedGeometry &G) {
@@ -297,9 +306,37 @@ extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *
     if ((rc = check_struct(u, FN_DEVICE, true)) != RT_OK || (rc = check_scene(s, u, FN_DEVICE)) != RT_OK)
         return rc;
     HIP_TRY(hipSetDevice(s->device));
-    const uint32_t n = u->n_triangles;
-    if (n && (rc = check_device_pointers(s, u)) != RT_OK) // before any launch
+    if (u->n_triangles && (rc = check_device_pointers(s, u)) != RT_OK) // before any launch
         return rc;
+    return rt::update_from_device_arrays(s, u, false);
+}
+
+// Everything rt_update_geometry_device can refuse of device arrays it may read, found without writing anything: the two data-dependent
+// refusals, the mode against the scene, the wide tree's exponent range. A shutter accumulator asks this of both keys at attach. `scan`: the
+// bounds of the vertices, for the caller.
+int rt::refuse_device_arrays(rt_scene *s, const rt_geometry_update *u, const std::string &fn, rt::UpdateScan *scan) {
+    const char *what = "";
+    const rt::DeviceArrays arrays{u->positions, u->normals, u->texcoords, u->tangents, u->material_ids, u->n_triangles};
+    if (hipError_t e = rt::scan_update_device(arrays, emissive_materials(*s->prep), false, s->stream, scan, &what); e != hipSuccess)
+        return rt::hip_fail(e, fn + ": " + what);
+    if (scan->bad_material)
+        return refuse_material(fn);
+    if (scan->first_non_finite != RT_NONE)
+        return refuse_non_finite(fn, scan->first_non_finite);
+    if (int rc = check_mode(s, u, fn); rc != RT_OK)
+        return rc;
+    if (u->n_triangles && s->dev.scene.n_wide != 0u && !rt::wide_grid_in_range(rt::make_wide_grid(scan->lo, scan->hi)))
+        return rt::fail(RT_ERR_UNSUPPORTED, fn + ": the new extent is outside the 8-wide tree's exponent range (2^-52 .. 2^52)");
+    return RT_OK;
+}
+
+// rt_update_geometry_device behind its argument checks: `u` names device arrays of the scene's GPU and of the scene's triangle count, in a
+// known mode. Also the path by which a shutter accumulator installs a slice (rt_accum_shutter.cpp), which is why the live-accumulator
+// refusal is the entry point's and not this function's. `keep_lights` (REFIT only): the emissive triangles have the positions the live
+// light tree was built from, bit for bit, so the light half (a list across the bus, a host build, a tree back) is skipped.
+int rt::update_from_device_arrays(rt_scene *s, const rt_geometry_update *u, bool keep_lights) {
+    int rc;
+    const uint32_t n = u->n_triangles;
     HIP_TRY(hipStreamSynchronize(s->stream));
     const rt::PreparedScene &P = *s->prep;
     const bool dev_build = n > 0 && (P.build_flags & RT_BUILD_DEVICE_LBVH), wide_build = n > 0 && (P.build_flags & RT_BUILD_WIDE); // as prepare_geometry
@@ -311,7 +348,8 @@ extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *
     // ---- one pass over positions and ids: the two data-dependent refusals, the bounds, the lights (writes only its own scratch)
     rt::UpdateScan scan;
     const char *what = "";
-    const bool want_lights = !staged && check_mode_ok(s, u); // (a call check_mode is about to refuse needs no light list)
+    keep_lights = keep_lights && refit && !staged;
+    const bool want_lights = !staged && !keep_lights && check_mode_ok(s, u); // (a call check_mode is about to refuse needs no light list)
     if (hipError_t e = rt::scan_update_device(arrays, emissive_materials(P), want_lights, s->stream, &scan, &what); e != hipSuccess)
         return rt::hip_fail(e, FN_DEVICE + ": " + what);
     if (scan.bad_material)
@@ -325,10 +363,13 @@ extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *
     else if (refit && n == 0)
         rc = RT_OK;
     else {
-        auto G = std::make_shared<rt::PreparedGeometry>();
-        G->dev_build = dev_build, G->wide_build = wide_build; // as prepare_geometry sets them
-        if ((rc = lights_from_scan(scan, n, *G)) != RT_OK)
-            return rc;
+        std::shared_ptr<rt::PreparedGeometry> G;
+        if (!keep_lights) {
+            G = std::make_shared<rt::PreparedGeometry>();
+            G->dev_build = dev_build, G->wide_build = wide_build; // as prepare_geometry sets them
+            if ((rc = lights_from_scan(scan, n, *G)) != RT_OK)
+                return rc;
+        }
         if (refit) { // the caller's arrays are the refit's input: nothing is allocated or copied for them, and `in` owns nothing
             rt::RefitInput in;
             in.pos = const_cast<float *>(u->positions), in.nrm = const_cast<float *>(u->normals), in.uv = const_cast<float *>(u->texcoords);
