@@ -951,6 +951,65 @@ int rt_accum_attach_shutter(rt_accum *acc, const rt_shutter_desc *desc);
 int rt_accum_shutter_times(rt_accum *acc, double *slice_change_ms, uint32_t *slice_changes);
 int rt_accum_shutter_info(rt_accum *acc, uint32_t *static_lights, uint32_t *light_rebuilds);
 
+/* Motion vectors: a first-hit optical-flow layer for accumulators (additive; RT_ABI_VERSION stays 4). rt_accum_attach_flow gives an accumulator
+ * two geometry keys and an optional second view; every sample then also records the screen-space displacement, between the keys, of the
+ * surface point its primary ray sees. The layer has the shape of the ids and the light groups: per-path records behind bounce 0's closest
+ * hits, a fold in sample order, read and resolve entry points. It changes no other sum. include/rt_flowspec.h is this rule as code, for host
+ * and device. The rule, operation by operation: IEEE binary32, evaluated as written, no contraction; vector expressions per component, left
+ * to right.
+ *   The point of a sample. Sample s of pixel p has the primary ray (o, d) that the sensor rule above makes of (sensor, p, s); its closest hit
+ *     (k, b, c, t) is the one the scene's own traversal returns: the hit the feature sums and the ids use. The alpha coin is not consulted.
+ *       a miss                                   the sample has no flow
+ *       an analytic primitive, or n_triangles == 0   X0 = X1 = o + t * d
+ *       a triangle of original index i           Xk = (V0k * ((1 - b) - c) + V1k * b) + V2k * c for k = 0, 1, from positions[k][9*i ..]
+ *     (triangle::interop of the reference). Both points come from the same expression: a triangle whose keys are equal gives X0 == X1 bit
+ *     for bit.
+ *   Projection proj(sensor, W, H, X) -> (fx, fy, ok), the inverse of the sensor rule. v = X - P; r = dot(v, R), u = dot(v, U), f = dot(v, F),
+ *     each (x*x' + y*y') + z*z'. tan_x, tan_y, half_fov and half_h are the host values of the sensor record.
+ *       PINHOLE, THIN_LENS (through the lens centre)   ok = f > 0;  nx = (r / f) / tan_x;  ny = (-(u / f)) / tan_y
+ *       ORTHOGRAPHIC  ok = f > 0;  nx = r / half_width;  ny = (-u) / half_h
+ *       EQUIRECT      len = sqrtf((r*r + u*u) + f*f);  ok = len > 0;  nx = rt_atan2f_libm(r, f) / PI_F;
+ *                     q = u / len held to [-1, 1] by comparisons (q < -1 ? -1 : q > 1 ? 1 : q);  ny = (-rt_asinf_libm(q)) / (PI_F * 0.5f)
+ *       FISHEYE       rho = sqrtf(r*r + u*u);  th = rt_atan2f_libm(rho, f);  rr = th / half_fov
+ *                     rho == 0: ok = f > 0, nx = ny = 0;  else ok = true, nx = rr * (r / rho), ny = (rr * ((-u) / rho)) / ((float)H / (float)W)
+ *     then fx = (nx + 1) * (0.5f * (float)W), fy = (ny + 1) * (0.5f * (float)H). Pixel x covers [x, x + 1): the inverse of
+ *     nx = 2 * (x + ox) / W - 1. The inverse is that of an orthonormal frame; R, U and F are used as given.
+ *   Flow of a sample. (fx0, fy0, ok0) = proj(the accumulator's view, X0); (fx1, fy1, ok1) = proj(sensor1, or the same view, X1);
+ *     dx = fx1 - fx0; dy = fy1 - fy0. EQUIRECT only, the seam: dx > 0.5f*W subtracts (float)W once, dx < -0.5f*W adds it once. The sample is
+ *     VALID iff it hit, ok0 && ok1, and dx and dy are finite. The flow is not clipped to the image: a point that leaves the frame still has one.
+ *   Per pixel, over its samples in sample order (one lane owns the pixel, no atomics):
+ *       FS_p (2 floats) += (dx, dy) of every valid sample;  m_p (u32) counts them
+ *       NT_p (float), NF_p (2 floats): a valid sample replaces them iff no valid sample came before, or its t < NT_p strictly: the nearest
+ *         surface wins, a tie goes to the lowest s
+ *     All four are functions of n_p alone, for any split over calls, passes and lists, any max_paths, sort mode and packet mode.
+ *   Resolve. RT_FLOW_MEAN: flow = FS / (float)m; RT_FLOW_NEAREST: flow = NF; (0, 0) where m == 0. mask = (float)m / (float)n, 0 where n == 0.
+ *   With flow attached S, E, n, features, ids, light groups, the image and every event counter are those of an accumulator without it, bit for
+ *     bit; an accumulator without flow allocates and launches nothing new.
+ * rt_accum_attach_flow: once per accumulator, before any call has added samples to it. The keys are copied to device memory the accumulator
+ *   owns; the caller keeps theirs. Key 0 is the geometry the scene holds now: the caller's word, not checked.
+ *   RT_ERR_INVALID_ARG: a NULL argument; a second attach; an attach after samples were added; n_triangles neither 0 nor the scene's; a NULL key
+ *     with n_triangles > 0; a misaligned device array or one that is not device memory of the scene's GPU; a non-finite position in either key
+ *     (found by the update's check kernel, lowest triangle named); an unknown flag; a non-zero reserved word; sensor1 of another kind than the
+ *     accumulator's view, or one rt_render_sensors refuses.
+ *   RT_ERR_UNSUPPORTED: flow together with a shutter, in either attach order: a slice's geometry is not key 0.
+ *   RT_ERR_OOM (from a later render call): the per-path records (16 B per path of a pass) do not fit beside the wavefront workspace.
+ *   After any refusal nothing is changed.
+ * rt_accum_read_flow: the raw state (any pointer may be NULL): FS [p][2], m [p], NF [p][2], NT [p].
+ * rt_accum_resolve_flow: flow [p][2] and mask [p] (either may be NULL), host buffers, or device buffers on the scene's GPU with
+ *   RT_FLAG_DEVICE_FB (4-byte aligned, idle on entry), as rt_accum_resolve_labels. RT_ERR_INVALID_ARG: an unknown mode or flag.
+ * Both reads: RT_ERR_INVALID_ARG for a NULL accumulator or one without flow. */
+enum { RT_FLOW_MEAN = 0, RT_FLOW_NEAREST = 1 };
+typedef struct rt_flow_desc {
+    uint32_t n_triangles;      /* the scene's, or 0: no triangle moves (camera-only flow; every scene kind) */
+    uint32_t flags;            /* 0: host arrays; RT_FLAG_DEVICE_FB: device arrays on the scene's GPU, 4-byte aligned, idle on entry */
+    const float *positions[2]; /* key 0 (the geometry the scene holds now: the caller's word, not checked) and key 1; 9*n floats each, as rt_scene_desc */
+    const rt_sensor *sensor1;  /* the view at key 1; NULL: the accumulator's own view. Same kind as the accumulator's view */
+    uint32_t reserved[8];      /* 0 */
+} rt_flow_desc;                /* 64 bytes */
+int rt_accum_attach_flow(rt_accum *acc, const rt_flow_desc *desc);
+int rt_accum_read_flow(rt_accum *acc, float *flow_sum /*[p][2]*/, uint32_t *valid /*[p]*/, float *near_flow /*[p][2]*/, float *near_t /*[p]*/);
+int rt_accum_resolve_flow(rt_accum *acc, uint32_t mode, uint32_t flags, float *flow /*[p][2]*/, float *mask /*[p]*/);
+
 /* Image-based lighting: a float radiance map as the scene's environment, optionally importance-sampled (additive; RT_ABI_VERSION stays 4).
  * rt_create's bg_texture is the reference's Scene::bg: an 8-bit texture with gamma, which clips an .hdr file to [0, 1]. rt_set_environment
  * replaces that lookup by a float map for a built scene. The texels are copied to device memory (float4 each); the caller keeps `rgb`.

@@ -60,6 +60,8 @@ from ._ctypes_abi import (
     RT_UPDATE_REBUILD,
     RT_UPDATE_REFIT,
     RT_ENV_IMPORTANCE,
+    RT_FLOW_MEAN,
+    RT_FLOW_NEAREST,
     RT_RNG_DEVICE,
     RT_RNG_REFERENCE,
     RAY_DTYPE,
@@ -73,6 +75,7 @@ from ._ctypes_abi import (
     RtCamera,
     RtDenoise,
     RtEnvironment,
+    RtFlowDesc,
     RtGeometryUpdate,
     RtIdDesc,
     RtLightGroupDesc,
@@ -123,6 +126,18 @@ def _check(code: int) -> None:
 
 def device_count() -> int:
     return int(lib().rt_device_count())
+
+
+def write_flo(path, flow) -> None:
+    """An (H, W, 2) flow field (Accumulator.flow) as a Middlebury .flo file: the float32 tag 202021.25 ("PIEH"), width and height as
+    little-endian int32, then the (dx, dy) float32 pairs row by row."""
+    f = np.asarray(flow, dtype="<f4")
+    if f.ndim != 3 or f.shape[2] != 2:
+        raise ValueError(f"write_flo: the flow must have shape (H, W, 2), not {f.shape}")
+    with open(path, "wb") as out:
+        out.write(np.array([202021.25], dtype="<f4").tobytes())
+        out.write(np.array([f.shape[1], f.shape[0]], dtype="<i4").tobytes())
+        out.write(np.ascontiguousarray(f).tobytes())
 
 
 class LoadedScene:
@@ -485,7 +500,7 @@ class DeviceScene:
         _check(lib().rt_update_geometry_device(self._h, C.byref(u)))
 
     def accumulator(self, width: int, height: int, camera=None, seed: int = 0, features: bool = False, sensor=None, ids=None,
-                    id_slots: int = 4, light_groups=None, shutter=None) -> "Accumulator":
+                    id_slots: int = 4, light_groups=None, shutter=None, flow=None) -> "Accumulator":
         """A resumable sample accumulator of this scene (rt_accum_create): `camera` a scenegen.Camera (None: the scene's own), `seed` the
         RT_RNG_DEVICE seed. Pixel p of its image is bit for bit run_raytracer(samples = n_p) of that view. `features`: keep the first-hit
         albedo / normal / depth sums as well (rt_accum_create_ex with RT_ACCUM_FEATURES), which features(), read_features() and denoise() need.
@@ -494,7 +509,9 @@ class DeviceScene:
         `light_groups` (not None): Accumulator.attach_light_groups on the new accumulator, for read_light_groups(), light_group() and
         light_mix(): the group of every material (an array), or a dict of attach_light_groups' arguments.
         `shutter` (not None): a dict of Accumulator.attach_shutter's arguments (key0, key1, sensor1, open, close, slices, block, refit): motion
-        blur between two geometry keys and two views."""
+        blur between two geometry keys and two views.
+        `flow` (not None): a dict of Accumulator.attach_flow's arguments (key0, key1, sensor1): motion vectors between two geometry keys and
+        two views, for flow() and read_flow()."""
         if sensor is not None and camera is not None:
             raise ValueError("accumulator: give a camera or a sensor, not both (the sensor carries its camera and seed)")
         acc = Accumulator(self, width, height, camera, seed, RT_ACCUM_FEATURES if features else 0, sensor=sensor)
@@ -505,6 +522,8 @@ class DeviceScene:
                 acc.attach_light_groups(**(light_groups if isinstance(light_groups, dict) else {"material_group": light_groups}))
             if shutter is not None:
                 acc.attach_shutter(**shutter)
+            if flow is not None:
+                acc.attach_flow(**flow)
         except Exception:
             acc.close()
             raise
@@ -1184,6 +1203,74 @@ class Accumulator:
         st, n = C.c_uint32(0), C.c_uint32(0)
         _check(lib().rt_accum_shutter_info(self._h, C.byref(st), C.byref(n)))
         return {"static_lights": bool(st.value), "light_rebuilds": int(n.value)}
+
+    def attach_flow(self, key0=None, key1=None, sensor1=None, reserved=None) -> None:
+        """rt_accum_attach_flow (include/rt_abi.h states the rule): keep, per pixel, the motion vectors of its samples: the displacement in
+        pixels, from key 0 to key 1, of the surface point each primary ray sees, as the mean over the samples and as the nearest sample's.
+        `key0` is the geometry the scene holds now, `key1` the same triangles at the other time: each a scenegen.Scene, a LoadedScene or an
+        arrays dict as update_geometry takes them (only the positions are read), a (n, 3, 3) float32 array, or a contiguous float32 torch
+        CUDA tensor of the positions (or a dict holding one under "positions"); both keys of one kind. Both None: no triangle moves, the flow
+        is the camera's alone. `sensor1`: the view at key 1, a Sensor of the accumulator's kind (None: the view does not move). Once, before
+        the first render; not together with a shutter."""
+        d = RtFlowDesc()
+        for i, r in enumerate(reserved or ()):
+            d.reserved[i] = int(r)
+        keep = []
+        if (key0 is None) != (key1 is None):
+            raise ValueError("attach_flow: give both geometry keys or neither")
+        if key0 is not None:
+            ptrs, counts, on_device = [], set(), None
+            for key in (key0, key1):
+                if isinstance(key, dict) and hasattr(key.get("positions"), "data_ptr"):
+                    key = key["positions"]
+                dev_key = hasattr(key, "data_ptr")
+                if on_device is not None and dev_key != on_device:
+                    raise ValueError("attach_flow: one key is on the device and the other is not")
+                on_device = dev_key
+                if dev_key:
+                    import torch
+
+                    if not key.is_cuda or not key.is_contiguous() or key.dtype != torch.float32:
+                        raise TypeError("attach_flow: a device key must be a contiguous float32 torch CUDA tensor")
+                    torch.cuda.current_stream(key.device).synchronize()  # the idle precondition
+                    ptrs.append(key.data_ptr() if key.numel() else 0)
+                    counts.add(key.numel() // 9)
+                else:
+                    pos = np.ascontiguousarray(key, dtype=np.float32).reshape(-1) if isinstance(key, np.ndarray) else geometry_arrays(key)["positions"]
+                    keep.append(pos)
+                    ptrs.append(pos.ctypes.data if pos.size else 0)
+                    counts.add(pos.size // 9)
+            if len(counts) != 1:
+                raise ValueError(f"attach_flow: the keys hold different triangle counts {sorted(counts)}")
+            d.n_triangles = counts.pop()
+            d.flags = RT_FLAG_DEVICE_FB if on_device else 0
+            d.positions[0], d.positions[1] = ptrs
+        if sensor1 is not None:
+            rec = make_sensors([sensor1])
+            keep.append(rec)
+            d.sensor1 = C.cast(rec, C.POINTER(RtSensor))
+        _check(lib().rt_accum_attach_flow(self._h, C.byref(d)))
+
+    def read_flow(self) -> dict:
+        """The raw flow state (rt_accum_read_flow): "flow_sum" (H, W, 2) float32, the sum of (dx, dy) over each pixel's valid samples; "valid"
+        (H, W) uint32, their number; "near_flow" (H, W, 2) and "near_t" (H, W) float32, the flow and the distance of the nearest valid
+        sample. Needs attach_flow."""
+        return self._state(lambda *p: lib().rt_accum_read_flow(self._h, *p), flow_sum=(np.float32, 2), valid=(np.uint32,), near_flow=(np.float32, 2), near_t=(np.float32,))
+
+    def flow(self, mode: str = "mean", device_out=None):
+        """rt_accum_resolve_flow: (flow (H, W, 2) float32, in pixels, x to the right and y down; mask (H, W) float32, the share of the pixel's
+        samples that have a flow). `mode`: "mean" over the valid samples, or "nearest": the flow of the sample nearest to the camera, which
+        does not mix two surfaces at an edge. (0, 0) where no sample is valid. `device_out`: a pair of device pointers (flow, mask; either may
+        be None or 0) that receive them in HBM (RT_FLAG_DEVICE_FB); then (None, None) is returned."""
+        modes = {"mean": RT_FLOW_MEAN, "nearest": RT_FLOW_NEAREST}
+        m = modes[mode] if isinstance(mode, str) else int(mode)
+        if device_out is not None:
+            fp, mp = device_out
+            _check(lib().rt_accum_resolve_flow(self._h, m, RT_FLAG_DEVICE_FB, C.c_void_p(fp or None), C.c_void_p(mp or None)))
+            return None, None
+        flow, mask = self._zeros(np.float32, 2), self._zeros(np.float32)
+        _check(lib().rt_accum_resolve_flow(self._h, m, 0, flow.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p)))
+        return flow, mask
 
     def close(self) -> None:
         if self._h:

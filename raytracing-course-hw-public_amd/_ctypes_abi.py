@@ -33,6 +33,7 @@ RT_ACCUM_FEATURES = 1
 RT_DENOISE_NO_DEMODULATE = 1
 RT_UPDATE_REBUILD, RT_UPDATE_REFIT = 0, 1
 RT_ENV_IMPORTANCE = 1  # rt_environment.flags
+RT_FLOW_MEAN, RT_FLOW_NEAREST = 0, 1  # rt_accum_resolve_flow's mode
 RT_CAST_PROBE, RT_CAST_EXTEND, RT_CAST_EXTEND_GLOBAL, RT_CAST_PACKET, RT_CAST_PACKET_GLOBAL = range(5)
 
 RT_OK = 0
@@ -252,6 +253,19 @@ class RtShutterDesc(C.Structure):  # rt_accum_attach_shutter: two geometry keys,
 assert C.sizeof(RtShutterDesc) == 128
 
 
+class RtFlowDesc(C.Structure):  # rt_accum_attach_flow: the positions of two geometry keys and the view at key 1 (64 bytes)
+    _fields_ = [
+        ("n_triangles", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("positions", C.c_void_p * 2),
+        ("sensor1", C.POINTER(RtSensor)),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
+assert C.sizeof(RtFlowDesc) == 64
+
+
 class RtEnvironment(C.Structure):  # rt_set_environment: a float radiance map (24 bytes)
     _fields_ = [
         ("width", C.c_uint32),
@@ -367,6 +381,9 @@ ABI_PROTOTYPES = {
     "rt_accum_attach_shutter": (C.c_int, [C.c_void_p, C.POINTER(RtShutterDesc)]),
     "rt_accum_shutter_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "rt_accum_shutter_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rt_accum_attach_flow": (C.c_int, [C.c_void_p, C.POINTER(RtFlowDesc)]),
+    "rt_accum_read_flow": (C.c_int, [C.c_void_p, c_float_p, c_u32_p, c_float_p, c_float_p]),
+    "rt_accum_resolve_flow": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_set_environment": (C.c_int, [C.c_void_p, C.POINTER(RtEnvironment)]),  # NULL: back to the creation background
     "rt_env_pdf": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, c_float_p]),
     "rt_env_sample": (C.c_int, [C.c_void_p, c_float_p, C.c_uint32, c_float_p]),

@@ -217,6 +217,25 @@ __global__ __launch_bounds__(256) void accum_light_mix_kernel(const rt::AccumRou
     }
 }
 
+// rt_accum_resolve_flow: the mean or the nearest sample's flow, and the share of the pixel's samples that have one
+__global__ __launch_bounds__(256) void accum_flow_kernel(const rt::AccumRound R, const WfFlow F, uint32_t mode, float *flow, float *mask) {
+    const uint32_t n_pix = R.width * R.height;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_pix; p += gridDim.x * blockDim.x) {
+        const uint32_t n = R.count[p], m = F.valid[p];
+        if (flow) {
+            float x = 0.0f, y = 0.0f;
+            if (m != 0u && mode == RT_FLOW_NEAREST)
+                x = F.near_flow[2ull * p], y = F.near_flow[2ull * p + 1];
+            else if (m != 0u)
+                x = F.flow_sum[2ull * p] / (float)m, y = F.flow_sum[2ull * p + 1] / (float)m;
+            flow[2ull * p] = x;
+            flow[2ull * p + 1] = y;
+        }
+        if (mask)
+            mask[p] = n != 0u ? (float)m / (float)n : 0.0f;
+    }
+}
+
 dim3 accum_grid(const rt::AccumRound &R) {
     const uint64_t n_pix = (uint64_t)R.width * R.height;
     const uint64_t b = (n_pix + 255u) / 256u;
@@ -277,6 +296,10 @@ hipError_t launch_accum_light_group(const AccumRound &R, const WfGroups &G, uint
 
 hipError_t launch_accum_light_mix(const AccumRound &R, const WfGroups &G, const LightMixWeights &w, float *fb, hipStream_t stream) {
     return RT_LAUNCH_CHECKED(accum_light_mix_kernel, accum_grid(R), dim3(256), 0, stream, R, G, w, fb);
+}
+
+hipError_t launch_accum_flow(const AccumRound &R, const WfFlow &F, uint32_t mode, float *flow, float *mask, hipStream_t stream) {
+    return RT_LAUNCH_CHECKED(accum_flow_kernel, accum_grid(R), dim3(256), 0, stream, R, F, mode, flow, mask);
 }
 
 } // namespace rt

@@ -122,6 +122,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
     WfFeat *const F = rt::layer_ptr(a->features); // the layers it keeps (null: not this one): their per-path records are bound per fill
     WfIds *const I = rt::layer_ptr(a->ids);
     WfGroups *const G = rt::layer_ptr(a->groups);
+    WfFlow *const Fl = rt::layer_ptr(a->flow);
     WfLaunch W{};
     W.width = a->width;
     W.height = a->height;
@@ -153,7 +154,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
             const uint64_t cap = std::min<uint64_t>((uint64_t)std::min(per_pass, tot[0]) * C, tot[1]);
             if (int rc = s->ensure_wavefront(cap, std::max<uint64_t>(s->wf_pixels_cap, 1), s->dev.ray_depth); rc != RT_OK)
                 return rc;
-            if (int rc = s->bind_layer_records(F, I, G); rc != RT_OK)
+            if (int rc = s->bind_layer_records(F, I, G, Fl); rc != RT_OK)
                 return rc;
             s->wf_bind(W);
             W.fb = nullptr;
@@ -164,7 +165,7 @@ static int accum_run(rt_accum *a, const rt_params *p, const rt_adaptive *ad, uin
                 W.first_pixel = 0, W.pass_pixels = A.n_entries;
                 W.first_sample = 0, W.pass_samples = C, W.samples = C;
                 a->has_samples = true;
-                const rt::WfPassKind kind = rt::WfPassKind::list(A, rt::WfLayers{F, I, G}, a->sensor);
+                const rt::WfPassKind kind = rt::WfPassKind::list(A, rt::WfLayers{F, I, G, Fl}, a->sensor);
                 HIP_TRY(rt::launch_pass(s, p, a->pkt, W, kind, rt::WfPassStep{true, true, stats != nullptr}));
                 passes += 1;
                 packet_passes += W.use_packet;

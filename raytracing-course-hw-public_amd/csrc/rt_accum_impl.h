@@ -1,7 +1,7 @@
 // rt_accum_impl.h — what the two host files of the accumulators share (internal): the definition of rt_accum and the helpers with more
 // than one user. rt_accum_host.cpp creates, renders, resolves and reads an accumulator; rt_accum_layers.cpp holds its optional layers (first-hit
-// features with the denoiser, ids, light groups), each with its attach / read / resolve entry points. DESIGN.md "accumulator layers" lists
-// what a layer consists of.
+// features with the denoiser, ids, light groups) and rt_accum_flow.cpp the fourth (motion vectors), each with its attach / read / resolve
+// entry points. DESIGN.md "accumulator layers" lists what a layer consists of.
 #pragma once
 #include <optional>
 
@@ -42,6 +42,7 @@ struct rt_accum {
     std::optional<WfFeat> features; // RT_ACCUM_FEATURES: the four first-hit sums
     std::optional<WfIds> ids;       // rt_accum_attach_ids: the per-pixel id tables
     std::optional<WfGroups> groups; // rt_accum_attach_light_groups: the group sums and the material table
+    std::optional<WfFlow> flow;     // rt_accum_attach_flow: the four flow values per pixel, the two keys and the second view
     std::optional<rt::Shutter> shutter; // rt_accum_attach_shutter: the keys (no sums of its own)
     rt::DenoiseBufs D{};            // rt_accum_denoise's workspace (64 B per pixel), allocated by its first call
     rt::DevBuf<uint32_t> matte_set; // rt_accum_resolve_matte's id set on the device
@@ -67,7 +68,7 @@ template <class T> int accum_alloc(rt_accum *a, size_t bytes, T **ptr, const cha
 }
 
 // The entry check of a call on a live accumulator: it is there, and it keeps the layer the call reads.
-enum class AccumNeed { NONE, FEATURES, IDS, GROUPS };
+enum class AccumNeed { NONE, FEATURES, IDS, GROUPS, FLOW };
 inline int accum_entry(const rt_accum *acc, const char *fn, AccumNeed need) {
     if (!acc)
         return fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null accumulator");
@@ -77,6 +78,8 @@ inline int accum_entry(const rt_accum *acc, const char *fn, AccumNeed need) {
         return fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no ids (rt_accum_attach_ids)");
     if (need == AccumNeed::GROUPS && !acc->groups)
         return fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no light groups (rt_accum_attach_light_groups)");
+    if (need == AccumNeed::FLOW && !acc->flow)
+        return fail(RT_ERR_INVALID_ARG, std::string(fn) + ": the accumulator has no flow (rt_accum_attach_flow)");
     return RT_OK;
 }
 // rt_accum_shutter.cpp: the scene and the accumulator's view at slice k of its shutter (k < 0: key 0 and the accumulator's own view, what every

@@ -116,6 +116,8 @@ extern "C" int rt_accum_attach_shutter(rt_accum *acc, const rt_shutter_desc *des
         return rc;
     if (acc->shutter)
         return rt::fail(RT_ERR_INVALID_ARG, FN + ": the accumulator already has a shutter");
+    if (acc->flow)
+        return rt::fail(RT_ERR_UNSUPPORTED, FN + ": the accumulator has flow (rt_accum_attach_flow), whose key 0 is the scene's one geometry; a slice's is not");
     if (acc->has_samples)
         return rt::fail(RT_ERR_INVALID_ARG, FN + ": the accumulator already holds samples; attach a shutter before the first render");
     if (s->live_accums != 1)

@@ -382,6 +382,22 @@ struct WfGroups {
     uint32_t pixels;               // width * height
 };
 
+// The motion vectors of an accumulator with flow (rt_abi.h rt_accum_attach_flow; the rule as code: include/rt_flowspec.h). wf_flow writes one
+// record per path after bounce 0's closest hits, from the hit records wf_features and wf_ids read: {dx, dy, t, valid (u32 bits: 1, or 0 with
+// the rest zero)}. wf_resolve_flow folds them into the pixel's four values in sample order, one lane per entry, as wf_resolve_ids does. The
+// keys are two arrays as the caller gave them, 36 bytes per triangle each, indexed by DevTri::prim (DESIGN.md "Motion vectors": the layout).
+struct WfFlow {
+    RtF4 *rec;                // [paths of the pass]: 16 B per path, in the scene's wavefront workspace
+    float *flow_sum;          // [2 * pixels]: FS_p
+    uint32_t *valid;          // [pixels]: m_p
+    float *near_flow;         // [2 * pixels]: NF_p
+    float *near_t;            // [pixels]: NT_p
+    const float *key[2];      // [9 * n_triangles] each, the accumulator's copies; null with n_triangles == 0
+    const WfSensor *sensor1;  // the view at key 1, device: the accumulator's own record where the descriptor named none
+    uint32_t n_triangles;     // the scene's, or 0: every hit's points are o + t * d
+    uint32_t pixels;          // width * height
+};
+
 // A pass of rt_render_rays (rt_rays.cpp): the first stage takes its rays and RNG streams from the caller's buffer instead of a camera
 // (rt_wf_stages.h WfFromRays). The call is a virtual image of n_rays / group "pixels" (outputs) with group * samples samples each, so WfLaunch keeps
 // describing the pass (first_pixel / pass_pixels count outputs, WfLaunch::samples = group * samples) and wf_fold / wf_resolve run unchanged:

@@ -78,19 +78,21 @@ struct WfHostSync {
 //   cameras  the camera table WfLaunch::sensors (a view is a pinhole record), whatever the entry point; wf_resolve adds onto the image
 //   list     an accumulator round's entry list; wf_resolve_list adds onto the accumulator's sums, behind the feature sums and the id tables
 //            of an accumulator that keeps them (wf_features / wf_ids after bounce 0, wf_resolve_features / wf_resolve_ids before the sums),
-//            and behind the group sums of one with light groups (wf_group_tags at every bounce, wf_fold_groups, wf_resolve_groups)
+//            and behind the group sums of one with light groups (wf_group_tags at every bounce, wf_fold_groups, wf_resolve_groups) and the
+//            motion vectors of one with flow (wf_flow after bounce 0, wf_resolve_flow)
 //   rays     the caller's rays and streams (rt_render_rays); wf_resolve adds onto the outputs
 //   bake     the samples of bake points (rt_bake); wf_resolve_bake folds them as the bake's kind asks
 // A camera source is made of the call's camera table on the host (run_passes uploads it as WfLaunch::sensors), a list of its accumulator's one
 // camera record; both keep rt::single_origin of it (rt_sensor.cpp): the three floats every ray of the pass starts at, or null.
 const float *single_origin(const WfSensor *table, uint32_t n);
 // What a list pass keeps besides the sums (host only; all null: nothing): an accumulator's optional layers. wf_features and wf_ids run behind
-// bounce 0's closest hits, whose results are final there; wf_group_tags at every bounce, wf_fold_groups before wf_fold; then
-// wf_resolve_features, wf_resolve_ids and wf_resolve_groups, in that order, before wf_resolve_list.
+// bounce 0's closest hits, whose results are final there, and so does wf_flow; wf_group_tags at every bounce, wf_fold_groups before wf_fold;
+// then wf_resolve_features, wf_resolve_ids, wf_resolve_groups and wf_resolve_flow, in that order, before wf_resolve_list.
 struct WfLayers {
     const WfFeat *features;
     const WfIds *ids;
     const WfGroups *groups;
+    const WfFlow *flow;
 };
 class WfPassKind {
 public:
@@ -200,6 +202,9 @@ struct LightMixWeights {
 };
 hipError_t launch_accum_light_group(const AccumRound &R, const WfGroups &G, uint32_t group, float *fb, hipStream_t stream);
 hipError_t launch_accum_light_mix(const AccumRound &R, const WfGroups &G, const LightMixWeights &w, float *fb, hipStream_t stream);
+// the motion vectors (rt_accum_resolve_flow): flow[p] = FS_p / (float)m_p (RT_FLOW_MEAN) or NF_p (RT_FLOW_NEAREST), (0, 0) where m_p = 0;
+// mask[p] = (float)m_p / (float)n_p, 0 where n_p = 0. Device outputs; either may be null.
+hipError_t launch_accum_flow(const AccumRound &R, const WfFlow &F, uint32_t mode, float *flow, float *mask, hipStream_t stream);
 // rt_lightmap.hip: rt_lightmap_points. The texel centres of a width x height atlas that the triangles (device arrays: 9 / 9 / 6 floats each) cover,
 // as bake points in increasing texel order: owner per texel (integer atomicMin), exclusive scan, scatter. `owner` and `offs` have room for
 // width * height words, `scan_temp` for lightmap_scan_temp_bytes(width * height); `count` (device, one word) receives the number of owned

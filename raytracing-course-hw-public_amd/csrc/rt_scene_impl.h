@@ -205,13 +205,14 @@ struct rt_scene {
 
     // The per-path records of an accumulator's layers (null: it keeps none), sized like the wavefront workspace and allocated the first time
     // such an accumulator renders on this scene: two feature records per path (WfFeat::rec, 32 B), one id (WfIds::rec, 4 B), n_groups group
-    // records (WfGroups::rec, 16 B each) and one tag byte per path and frame level (WfGroups::tag). None needs its content kept or cleared
-    // (a stale tag is legal: WfGroups). Call after ensure_wavefront.
+    // records (WfGroups::rec, 16 B each), one tag byte per path and frame level (WfGroups::tag) and one flow record (WfFlow::rec, 16 B). None
+    // needs its content kept or cleared (a stale tag is legal: WfGroups). Call after ensure_wavefront.
     rt::DevBuf<RtF4> wf_feat;
     rt::DevBuf<uint32_t> wf_ids;
     rt::DevBuf<RtF4> wf_group_rec;
     rt::DevBuf<uint8_t> wf_group_tag;
-    int bind_layer_records(WfFeat *features, WfIds *ids, WfGroups *groups) {
+    rt::DevBuf<RtF4> wf_flow;
+    int bind_layer_records(WfFeat *features, WfIds *ids, WfGroups *groups, WfFlow *flow) {
         auto reserve = [](auto &buf, size_t count, const char *what) -> int {
             if (hipError_t e = buf.reserve(count); e != hipSuccess)
                 return rt::hip_fail(e, what);
@@ -225,6 +226,10 @@ struct rt_scene {
             return rc;
         if (int rc = groups ? reserve(wf_group_tag, wf_paths_cap * (wf_depth_cap + 1ull), "light-group tags") : RT_OK; rc != RT_OK)
             return rc;
+        if (int rc = flow ? reserve(wf_flow, wf_paths_cap, "flow records") : RT_OK; rc != RT_OK)
+            return rc;
+        if (flow)
+            flow->rec = wf_flow.get();
         if (features)
             features->rec = wf_feat.get();
         if (ids)
@@ -271,7 +276,7 @@ struct rt_scene {
         // point returns with the stream synchronised. In a group's handle all of them are empty.
         for (rt::DevArena *a : {&wf_owned, &owned, &geo_owned, &light_owned, &env_owned})
             a->reset();
-        wf_feat.reset(), wf_ids.reset(), wf_group_rec.reset(), wf_group_tag.reset(), wf_rel.reset(), staging.reset(), sensors.reset(), film_table.reset();
+        wf_feat.reset(), wf_ids.reset(), wf_group_rec.reset(), wf_group_tag.reset(), wf_flow.reset(), wf_rel.reset(), staging.reset(), sensors.reset(), film_table.reset();
         ext_events.destroy();
         if (ev0)
             (void)hipEventDestroy(ev0);
@@ -298,7 +303,9 @@ uint32_t light_lds_inner(const FlatBvh &f); // DevBvh::lds_inner of a light tree
 struct UpdateScan;
 std::vector<uint8_t> emissive_materials(const PreparedScene &P); // one byte per material: does it emit?
 int check_device_pointers(const rt_scene *s, const rt_geometry_update *u);
+int check_device_array(const rt_scene *s, const void *p, size_t bytes, const std::string &fn); // one array of them, named by the caller's `fn`
 int refuse_device_arrays(rt_scene *s, const rt_geometry_update *u, const std::string &fn, UpdateScan *scan);
+int refuse_non_finite_positions(rt_scene *s, const float *d_positions, uint32_t n, const std::string &fn);
 int update_from_device_arrays(rt_scene *s, const rt_geometry_update *u, bool keep_lights);
 // rt_render.cpp: the checks of rt_params, the wavefront pass policy, the pass loop and the statistics of a finished call
 void set_camera(DevScene &D, const float *pos, const float *right, const float *up, const float *fwd);

@@ -220,6 +220,17 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
 // "device memory of the scene's GPU": first and last byte of each array, by hipPointerGetAttributes (an unregistered host pointer is an error
 // or hipMemoryTypeUnregistered, depending on the runtime; pinned host memory is hipMemoryTypeHost; both are refused before any launch)
 } // namespace
+int rt::check_device_array(const rt_scene *s, const void *p, size_t bytes, const std::string &fn) {
+    for (const char *q : {(const char *)p, (const char *)p + bytes - 1}) {
+        hipPointerAttribute_t at{};
+        const hipError_t e = hipPointerGetAttributes(&at, q);
+        if (e != hipSuccess)
+            (void)hipGetLastError(); // "not a pointer HIP knows" is an answer, not a failure of the library
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != s->device)
+            return rt::fail(RT_ERR_INVALID_ARG, fn + ": a geometry array is not device memory of the scene's GPU (device " + std::to_string(s->device) + ")");
+    }
+    return RT_OK;
+}
 int rt::check_device_pointers(const rt_scene *s, const rt_geometry_update *u) {
     const size_t n = u->n_triangles;
     const struct {
@@ -227,14 +238,8 @@ int rt::check_device_pointers(const rt_scene *s, const rt_geometry_update *u) {
         size_t bytes;
     } arrays[5] = {{u->positions, 36 * n}, {u->normals, 36 * n}, {u->texcoords, 24 * n}, {u->tangents, 36 * n}, {u->material_ids, 4 * n}};
     for (const auto &a : arrays)
-        for (const char *q : {(const char *)a.p, (const char *)a.p + a.bytes - 1}) {
-            hipPointerAttribute_t at{};
-            const hipError_t e = hipPointerGetAttributes(&at, q);
-            if (e != hipSuccess)
-                (void)hipGetLastError(); // "not a pointer HIP knows" is an answer, not a failure of the library
-            if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != s->device)
-                return rt::fail(RT_ERR_INVALID_ARG, FN_DEVICE + ": a geometry array is not device memory of the scene's GPU (device " + std::to_string(s->device) + ")");
-        }
+        if (int rc = rt::check_device_array(s, a.p, a.bytes, FN_DEVICE); rc != RT_OK)
+            return rc;
     return RT_OK;
 }
 namespace {
@@ -327,6 +332,20 @@ int rt::refuse_device_arrays(rt_scene *s, const rt_geometry_update *u, const std
         return rc;
     if (u->n_triangles && s->dev.scene.n_wide != 0u && !rt::wide_grid_in_range(rt::make_wide_grid(scan->lo, scan->hi)))
         return rt::fail(RT_ERR_UNSUPPORTED, fn + ": the new extent is outside the 8-wide tree's exponent range (2^-52 .. 2^52)");
+    return RT_OK;
+}
+
+// The same scan over positions alone (no material ids: nothing is emissive, no id is checked): the finite-position refusal for arrays that
+// are not an update, the keys of rt_accum_attach_flow. Writes nothing but the scan's own scratch.
+int rt::refuse_non_finite_positions(rt_scene *s, const float *d_positions, uint32_t n, const std::string &fn) {
+    const char *what = "";
+    rt::DeviceArrays arrays;
+    arrays.pos = d_positions, arrays.n = n;
+    rt::UpdateScan scan;
+    if (hipError_t e = rt::scan_update_device(arrays, {}, false, s->stream, &scan, &what); e != hipSuccess)
+        return rt::hip_fail(e, fn + ": " + what);
+    if (scan.first_non_finite != RT_NONE)
+        return refuse_non_finite(fn, scan.first_non_finite);
     return RT_OK;
 }
 

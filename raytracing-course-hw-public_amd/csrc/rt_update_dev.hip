@@ -47,7 +47,7 @@ struct ScanArgs {
 __device__ __forceinline__ bool chunk_emissive(const ScanArgs &A, uint32_t chunk, uint32_t &tri, bool &bad) {
     const uint64_t i = (uint64_t)CHUNK * chunk + threadIdx.x;
     tri = (uint32_t)i;
-    if (i >= A.n)
+    if (i >= A.n || !A.mat) // no ids (a scan of positions alone): nothing is emissive
         return false;
     const uint32_t id = A.mat[i];
     if (id >= A.n_mats) {

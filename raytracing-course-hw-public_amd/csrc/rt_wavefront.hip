@@ -20,7 +20,7 @@
 //                 what the pass's kind keeps its samples in).
 // The two ends of a pass, which depend on its kind (rt_kernels.h WfPassKind), are rt_wf_stages.h. What runs between them for every kind alike
 // is split by job: wf_extend and its kin with the closest-hit probe are rt_wf_extend.hip (the 8-wide tree: rt_wide.hip), wf_shade is
-// rt_wf_shade.hip; this file has the small kernels between the stages (first-hit features, ids, group tags, the identity order, advance),
+// rt_wf_shade.hip; this file has the small kernels between the stages (first-hit features, ids, motion vectors, group tags, the identity order, advance),
 // the ray-order sort (the only user of rocPRIM) and the scheduler, launch_wavefront_pass, whose decisions are rt_wf_policy.h's.
 //
 // Every path owns an xoshiro128++ stream seeded from (seed, pixel, sample) and consumes it in the reference's draw
@@ -31,6 +31,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "../../include/rt_flowspec.h"
 #include "rt_kernels.h"
 #include "rt_wf_policy.h"
 #include "rt_wf_stages.h"
@@ -84,6 +85,51 @@ __global__ __launch_bounds__(256) void wf_ids(const DevScene S, const WfLaunch L
             }
         }
         I.rec[in.id] = id;
+    }
+}
+
+// The motion vectors of the same hits (rt_abi.h rt_accum_attach_flow), for a pass of an accumulator with flow: one 16-byte record per path.
+// Queue position i holds path i here, as for wf_features. The arithmetic is include/rt_flowspec.h's, which the CPU tests read too. Both views
+// are wave-uniform: scalar loads, and the kind a scalar branch, as in sensor_ray. The two gathers of 36 bytes per triangle hit, one per key
+// at DevTri::prim, are the kernel's whole cost; an analytic primitive and an accumulator whose triangles do not move gather nothing.
+DEV rt_flow_view wf_flow_view(const WfSensor &sn) {
+    rt_flow_view v;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        v.P[c] = sn.pos[c], v.R[c] = sn.right[c], v.U[c] = sn.up[c], v.F[c] = sn.fwd[c];
+    v.tan_x = sn.tan_x, v.tan_y = sn.tan_y;
+    v.half_fov = sn.half_fov;
+    v.half_width = sn.half_width, v.half_h = sn.half_h;
+    v.kind = sn.kind;
+    return v;
+}
+__global__ __launch_bounds__(256) void wf_flow(const DevScene S, const WfLaunch L, const WfFlow Fl) {
+    const rt_flow_view v0 = wf_flow_view(L.sensors[0]), v1 = wf_flow_view(*Fl.sensor1); // an accumulator has one camera
+    const uint32_t n_in = L.counters[WF_CNT_IN];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_in; i += gridDim.x * blockDim.x) {
+        const WfHead in = wf_load_head(L.paths_in + i);
+        const Hit h = wf_load_hit(L.hits + i);
+        RtF4 r{0.f, 0.f, 0.f, __uint_as_float(0u)};
+        if (h.k != RT_NONE) {
+            float X0[3], X1[3];
+            if ((h.k & RT_PRIM_FLAG) != 0u || Fl.n_triangles == 0u) {
+                const float o[3] = {in.o.x, in.o.y, in.o.z}, d[3] = {in.d.x, in.d.y, in.d.z};
+                rt_flow_ray_point(o, d, h.t, X0);
+                X1[0] = X0[0], X1[1] = X0[1], X1[2] = X0[2];
+            } else {
+                const size_t at = 9ull * S.scene.tris[h.k].prim;
+                float k0[9], k1[9];
+#pragma unroll
+                for (int j = 0; j < 9; ++j)
+                    k0[j] = Fl.key[0][at + j], k1[j] = Fl.key[1][at + j];
+                rt_flow_tri_point(k0, h.b, h.c, X0);
+                rt_flow_tri_point(k1, h.b, h.c, X1);
+            }
+            float dx, dy;
+            if (rt_flow_sample(&v0, &v1, L.width, L.height, X0, X1, &dx, &dy))
+                r = RtF4{dx, dy, h.t, __uint_as_float(1u)};
+        }
+        Fl.rec[in.id] = r;
     }
 }
 
@@ -177,7 +223,7 @@ static hipError_t launch_first_stage(const DevScene &S, const WfLaunch &L, const
 static hipError_t launch_last_stage(const WfLaunch &L, const WfPassKind &kind, const WfPassStep &step, int num_cus, hipStream_t stream) {
     const dim3 block(256);
     const int first = step.first_pass ? 1 : 0, last = step.last_pass ? 1 : 0;
-    if (kind.source() == WfPassKind::LIST) { // the feature sums, the id tables and the group sums go before the sums: they read the entry's base count from the list
+    if (kind.source() == WfPassKind::LIST) { // the feature sums, the id tables, the group sums and the flow go before the sums: they read the entry's base count from the list
         const WfAccum &A = kind.entries();
         const WfLayers keep = kind.layers();
         const dim3 grid(wf_grid_items(A.n_entries));
@@ -187,6 +233,8 @@ static hipError_t launch_last_stage(const WfLaunch &L, const WfPassKind &kind, c
             WF_LAUNCH(wf_resolve_ids, grid, block, 0, stream, A, *keep.ids);
         if (keep.groups)
             WF_LAUNCH(wf_resolve_groups, grid, block, 0, stream, A, *keep.groups, L.n_paths);
+        if (keep.flow)
+            WF_LAUNCH(wf_resolve_flow, grid, block, 0, stream, A, *keep.flow);
         WF_LAUNCH(wf_resolve_list, grid, block, 0, stream, L, A);
     } else if (kind.source() == WfPassKind::BAKE) { // the fold the bake's kind asks for, one lane per (point, k)
         const WfBake &B = kind.bake_points();
@@ -298,6 +346,8 @@ hipError_t launch_wavefront_pass(const DevScene &S, WfLaunch L, const WfPassKind
             WF_LAUNCH(wf_features, dim3(shade_blocks), block, 0, stream, S, L, *keep.features);
         if (b == 0 && keep.ids) // ... and so are their ids
             WF_LAUNCH(wf_ids, dim3(shade_blocks), block, 0, stream, S, L, *keep.ids);
+        if (b == 0 && keep.flow) // ... and their motion vectors
+            WF_LAUNCH(wf_flow, dim3(shade_blocks), block, 0, stream, S, L, *keep.flow);
         if (keep.groups) // light groups: at every bounce, whose emission the frame or terminal value wf_shade makes of this hit is
             WF_LAUNCH(wf_group_tags, dim3(shade_blocks), block, 0, stream, S, L, *keep.groups);
         // May the next bounce be sorted (WfPassPolicy::emits_keys)? Then this wf_shade writes the sort's input itself, key and slot at the

@@ -421,4 +421,34 @@ __global__ __launch_bounds__(256) void wf_resolve_ids(const WfAccum A, const WfI
         I.other[p] = other;
     }
 }
+
+// The motion vectors of the same entries (WfFlow; the rule: rt_abi.h rt_accum_attach_flow): the lane that owns the pixel takes its k records
+// in sample order: a valid one is added onto FS_p and counted in m_p, and replaces (NT_p, NF_p) where it is the pixel's first valid sample or
+// strictly nearer. Runs before wf_resolve_list of the pass and reads neither n_p nor the base count: the four values are the state.
+__global__ __launch_bounds__(256) void wf_resolve_flow(const WfAccum A, const WfFlow Fl) {
+    const uint32_t *off = A.list_off + A.first_entry;
+    for (uint32_t le = blockIdx.x * blockDim.x + threadIdx.x; le < A.n_entries; le += gridDim.x * blockDim.x) {
+        const uint32_t p = A.list_pix[A.first_entry + le];
+        const uint32_t k = off[le + 1] - off[le];
+        float sx = Fl.flow_sum[2ull * p], sy = Fl.flow_sum[2ull * p + 1];
+        float nx = Fl.near_flow[2ull * p], ny = Fl.near_flow[2ull * p + 1], nt = Fl.near_t[p];
+        uint32_t m = Fl.valid[p];
+        const RtF4 *src = Fl.rec + (off[le] - off[0]);
+        for (uint32_t j = 0; j < k; ++j) { // selects, no branch: the loads of later records need not wait for this one's test
+            const RtF4 r = src[j];
+            const bool valid = __float_as_uint(r.w) != 0u;
+            const bool nearer = valid && (m == 0u || r.z < nt);
+            sx = valid ? sx + r.x : sx; // (an invalid sample adds nothing, not +0: the sign of a zero sum stays)
+            sy = valid ? sy + r.y : sy;
+            nx = nearer ? r.x : nx;
+            ny = nearer ? r.y : ny;
+            nt = nearer ? r.z : nt;
+            m += valid ? 1u : 0u;
+        }
+        Fl.flow_sum[2ull * p] = sx, Fl.flow_sum[2ull * p + 1] = sy;
+        Fl.near_flow[2ull * p] = nx, Fl.near_flow[2ull * p + 1] = ny;
+        Fl.near_t[p] = nt;
+        Fl.valid[p] = m;
+    }
+}
 } // namespace
