@@ -23,6 +23,8 @@ RT_BUILDER_PLOC, RT_BUILDER_LBVH = 0, 1
 RT_SORT_AUTO, RT_SORT_OFF, RT_SORT_OCTANT_CELL_CONE = 0, 1, 6
 RT_PACKET_AUTO, RT_PACKET_OFF, RT_PACKET_ON = range(3)
 RT_TEX_NONE = -1
+RT_ALL_DEVICES = -1  # rt_create's device: one replica per visible GPU
+RT_SENSOR_PINHOLE, RT_SENSOR_EQUIRECT, RT_SENSOR_FISHEYE, RT_SENSOR_ORTHOGRAPHIC, RT_SENSOR_THIN_LENS = range(5)  # rt_sensor.kind
 RT_RNG_DEVICE = 0
 RT_RNG_REFERENCE = 1
 RT_FLAG_DEVICE_FB = 1

@@ -36,29 +36,59 @@ def test_ctypes_prototypes_cover_the_headers(rt):
     assert declared == bound, declared ^ bound
 
 
-def test_struct_layouts_match_the_c_headers(rt, tmp_path):
-    """sizeof/offsetof of the POD structs as the C compiler sees them == the ctypes mirrors."""
+def _abi():
+    return __import__("importlib").import_module("raytracing-course-hw-public_amd._ctypes_abi")
+
+
+def _compile_and_run(tmp_path, name, body):
+    """The whitespace-separated integers a C program prints whose main() is `body`, compiled against include/rt_abi.h."""
     import subprocess
 
-    abi = __import__("importlib").import_module("raytracing-course-hw-public_amd._ctypes_abi")
-    src = tmp_path / "sz.c"
-    src.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "rt_abi.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
-        "sizeof(rt_camera),sizeof(rt_texture_desc),sizeof(rt_material_desc),sizeof(rt_scene_desc),sizeof(rt_params),sizeof(rt_stats),"
-        "offsetof(rt_scene_desc,camera),offsetof(rt_params,seed),sizeof(rt_primitive_desc),offsetof(rt_scene_desc,primitives),offsetof(rt_primitive_desc,rotation));"
-        'printf("%zu %zu %zu %zu %zu %zu %zu\\n",sizeof(rt_build_options),offsetof(rt_scene_desc,build),offsetof(rt_build_options,reserved1),offsetof(rt_params,sort_mode),'
-        "offsetof(rt_params,max_paths),offsetof(rt_params,progress_user),offsetof(rt_stats,packet_passes));return 0;}\n"
-    )
-    exe = tmp_path / "sz"
+    src = tmp_path / (name + ".c")
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "rt_abi.h"\nint main(void){\n' + body + "return 0;}\n")
+    exe = tmp_path / name
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(abi.RtCamera), ctypes.sizeof(abi.RtTextureDesc), ctypes.sizeof(abi.RtMaterialDesc), ctypes.sizeof(abi.RtSceneDesc),
-            ctypes.sizeof(abi.RtParams), ctypes.sizeof(abi.RtStats), abi.RtSceneDesc.camera.offset, abi.RtParams.seed.offset,
-            ctypes.sizeof(abi.RtPrimitiveDesc), abi.RtSceneDesc.primitives.offset, abi.RtPrimitiveDesc.rotation.offset,
-            # ABI 4: build options, tuning fields, progress callback, packet census
-            ctypes.sizeof(abi.RtBuildOptions), abi.RtSceneDesc.build.offset, abi.RtBuildOptions.reserved1.offset, abi.RtParams.sort_mode.offset,
-            abi.RtParams.max_paths.offset, abi.RtParams.progress_user.offset, abi.RtStats.packet_passes.offset]
-    assert got == want
+    return [int(x) for x in subprocess.check_output([str(exe)]).split()]
+
+
+def test_struct_layouts_match_the_c_headers(rt, tmp_path):
+    """sizeof of every struct and offsetof of every field as the C compiler sees them == the ctypes mirrors: every ctypes.Structure of
+    _ctypes_abi has exactly one typedef of rt_abi.h (its name in snake_case, or that + _desc), and no struct of the header lacks a mirror."""
+    abi = _abi()
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rt_abi.h")).read(), flags=re.S)
+    typedefs = set(re.findall(r"typedef\s+struct\s+(rt_\w+)\s*\{", header))
+    mirrors = {}
+    for cls in vars(abi).values():
+        if isinstance(cls, type) and issubclass(cls, ctypes.Structure) and cls is not ctypes.Structure:
+            snake = re.sub(r"(?<!^)(?=[A-Z])", "_", cls.__name__).lower()
+            match = {snake, snake + "_desc"} & typedefs
+            assert len(match) == 1, f"{cls.__name__}: {sorted(match)} of rt_abi.h match"
+            mirrors[match.pop()] = cls
+    assert set(mirrors) == typedefs, f"no ctypes mirror: {sorted(typedefs - set(mirrors))}"
+    exprs, want = [], []
+    for cname, cls in sorted(mirrors.items()):
+        exprs.append(f"sizeof({cname})")
+        want.append(ctypes.sizeof(cls))
+        for field, _ in cls._fields_:
+            exprs.append(f"offsetof({cname}, {field})")
+            want.append(getattr(cls, field).offset)
+    got = _compile_and_run(tmp_path, "layouts", "".join(f'printf("%zu\\n", {e});\n' for e in exprs))
+    assert len(mirrors) >= 21 and len(want) >= 182
+    wrong = [(e, g, w) for e, g, w in zip(exprs, got, want) if g != w]
+    assert len(got) == len(want) and not wrong, wrong
+
+
+def test_constants_match_the_c_headers(rt, tmp_path):
+    """Every RT_* integer of _ctypes_abi and every name of ERROR_NAMES has the value rt_abi.h gives it (a name the header lacks does not
+    compile)."""
+    abi = _abi()
+    want = {n: v for n, v in vars(abi).items() if re.fullmatch(r"RT_[A-Z0-9_]+", n) and isinstance(v, int) and not isinstance(v, bool)}
+    assert want["RT_ALL_DEVICES"] == -1 and want["RT_SENSOR_THIN_LENS"] == 4 and len(want) >= 50
+    want.update({name: code for code, name in abi.ERROR_NAMES.items()})
+    names = sorted(want)
+    got = _compile_and_run(tmp_path, "constants", "".join(f'printf("%lld\\n", (long long)({n}));\n' for n in names))
+    wrong = [(n, g, want[n]) for n, g in zip(names, got) if g != want[n]]
+    assert len(got) == len(names) and not wrong, wrong
 
 
 def test_library_reads_no_environment_variable():
