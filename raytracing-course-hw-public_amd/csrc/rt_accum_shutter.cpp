@@ -149,7 +149,7 @@ extern "C" int rt_accum_attach_shutter(rt_accum *acc, const rt_shutter_desc *des
                 if (int rc = rt::check_device_pointers(s, &u); rc != RT_OK)
                     return rc;
             }
-        const std::vector<uint8_t> emissive = rt::emissive_materials(*s->prep);
+        const std::vector<uint8_t> emissive = rt::emissive_materials(s->prep->mats);
         uint8_t *d_emissive = nullptr;
         uint32_t *d_moving = nullptr;
         auto alloc = [&]<class T>(T **p, size_t bytes) -> int {

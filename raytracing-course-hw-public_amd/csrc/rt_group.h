@@ -14,9 +14,9 @@
 namespace rt {
 
 struct Group;
-struct PreparedScene; // rt_scene.cpp: the host half of rt_create (BVH builds, texture pool, ...), shared by all replicas
+struct PreparedScene; // rt_scene_prepare.cpp: the host half of rt_create (BVH builds, texture pool, ...), shared by all replicas
 
-// rt_scene.cpp: build the host half once / put one replica of it on a device
+// rt_scene_prepare.cpp / rt_scene.cpp: build the host half once / put one replica of it on a device
 int prepare(const rt_scene_desc *desc, std::shared_ptr<const PreparedScene> *out);
 int create_replica(const rt_scene_desc *desc, const std::shared_ptr<const PreparedScene> &prep, int device, rt_scene **out);
 

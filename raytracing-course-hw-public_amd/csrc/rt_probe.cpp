@@ -41,7 +41,7 @@ extern "C" int rt_cast_rays(rt_scene *s, const float *rays, uint32_t n, uint32_t
         return rt::fail(RT_ERR_INVALID_ARG, "rt_cast_rays: null argument");
     if (n == 0)
         return RT_OK;
-    if (s->wide_built) // no binary tree in HBM: the probe goes through the renderer's own wide kernel
+    if (s->facts.wide_built) // no binary tree in HBM: the probe goes through the renderer's own wide kernel
         return rt_cast_rays_ex(s, rays, n, RT_CAST_EXTEND, prim_out, bct_out, nullptr);
     const ProbeOut out[] = {{prim_out, (size_t)n * 4}, {bct_out, (size_t)n * 12}};
     return probe_round_trip(s, "rt_cast_rays", rays, (size_t)n * 24, out, [&](const float *d_rays, void *const *d) {
@@ -52,7 +52,7 @@ extern "C" int rt_cast_rays(rt_scene *s, const float *rays, uint32_t n, uint32_t
 extern "C" int rt_cast_rays_ex(rt_scene *s, const float *rays, uint32_t n, uint32_t mode, uint32_t *prim_out, float *bct_out, rt_stats *stats) {
     if (s && s->group)
         return rt_cast_rays_ex(rt::group_primary(s->group), rays, n, mode, prim_out, bct_out, stats);
-    if (mode == RT_CAST_PROBE && !(s && s->wide_built)) {
+    if (mode == RT_CAST_PROBE && !(s && s->facts.wide_built)) {
         if (stats)
             std::memset(stats, 0, sizeof(*stats));
         return rt_cast_rays(s, rays, n, prim_out, bct_out);
@@ -102,7 +102,7 @@ extern "C" int rt_surface_normals(rt_scene *s, const float *rays, uint32_t n, ui
         return rt_surface_normals(rt::group_primary(s->group), rays, n, prim_out, t_out, normal_out, shading_out);
     if (!s || (n && (!rays || !prim_out || !t_out)))
         return rt::fail(RT_ERR_INVALID_ARG, "rt_surface_normals: null argument");
-    if (s->wide_built)
+    if (s->facts.wide_built)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_surface_normals: a probe of the binary tree; create the scene without RT_BUILD_WIDE");
     if (n == 0)
         return RT_OK;
@@ -174,18 +174,18 @@ extern "C" int rt_bvh_device_dump(rt_scene *s, int which, uint32_t *n_inner, uin
         return rt::fail(RT_ERR_INVALID_ARG, "rt_bvh_device_dump: bad argument");
     if (s->group)
         return rt_bvh_device_dump(rt::group_primary(s->group), which, n_inner, n_tris, root, nodes64, tris48);
-    if (which == 0 && s->wide_built)
+    if (which == 0 && s->facts.wide_built)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_bvh_device_dump: the scene BVH is the 8-wide tree (RT_BUILD_WIDE): use rt_bvh_wide_dump");
     const DevBvh &b = which == 0 ? s->dev.scene : s->dev.lights;
     if (n_inner)
-        *n_inner = s->dev_n_inner[which];
+        *n_inner = s->facts.dev_n_inner[which];
     if (n_tris)
         *n_tris = b.n_tris;
     if (root)
         *root = b.root;
     HIP_TRY(hipSetDevice(s->device));
-    if (nodes64 && s->dev_n_inner[which])
-        HIP_TRY(hipMemcpy(nodes64, b.nodes, sizeof(DevNode) * (size_t)s->dev_n_inner[which], hipMemcpyDeviceToHost));
+    if (nodes64 && s->facts.dev_n_inner[which])
+        HIP_TRY(hipMemcpy(nodes64, b.nodes, sizeof(DevNode) * (size_t)s->facts.dev_n_inner[which], hipMemcpyDeviceToHost));
     if (tris48 && b.n_tris)
         HIP_TRY(hipMemcpy(tris48, b.tris, sizeof(DevTri) * (size_t)b.n_tris, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -196,7 +196,7 @@ extern "C" int rt_bvh_wide_dump(rt_scene *s, uint32_t *n_nodes, uint32_t *n_tris
         return rt::fail(RT_ERR_INVALID_ARG, "rt_bvh_wide_dump: null argument");
     if (s->group)
         return rt_bvh_wide_dump(rt::group_primary(s->group), n_nodes, n_tris, depth, nodes80, tris48);
-    if (!s->wide_built)
+    if (!s->facts.wide_built)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_bvh_wide_dump: the scene was not built with RT_BUILD_WIDE");
     const DevBvh &b = s->dev.scene;
     if (n_nodes)
@@ -204,7 +204,7 @@ extern "C" int rt_bvh_wide_dump(rt_scene *s, uint32_t *n_nodes, uint32_t *n_tris
     if (n_tris)
         *n_tris = b.n_tris;
     if (depth)
-        *depth = s->wide_depth;
+        *depth = s->facts.wide_depth;
     HIP_TRY(hipSetDevice(s->device));
     if ((!nodes80 && !tris48) || b.n_wide == 0)
         return RT_OK;
@@ -263,7 +263,7 @@ extern "C" int rt_bvh_wide_dump(rt_scene *s, uint32_t *n_nodes, uint32_t *n_tris
 // A device-built scene BVH has no host copy: rebuild the reference-style description (pre-order nodes with their OWN box,
 // bvh.h:157-163) from what is in HBM, once, when a caller asks for it.
 static int reconstruct_host_bvh(rt_scene *s) {
-    const uint32_t n_inner = s->dev_n_inner[0], n_tris = s->dev.scene.n_tris;
+    const uint32_t n_inner = s->facts.dev_n_inner[0], n_tris = s->dev.scene.n_tris;
     std::vector<DevNode> nodes(n_inner);
     std::vector<DevTri> tris(n_tris);
     HIP_TRY(hipSetDevice(s->device));
@@ -356,14 +356,14 @@ extern "C" int rt_bvh_info(rt_scene *s, int which, uint32_t *n_nodes, uint32_t *
         return rt::fail(RT_ERR_INVALID_ARG, "rt_bvh_info: bad argument");
     if (s->group)
         return rt_bvh_info(rt::group_primary(s->group), which, n_nodes, n_objects, root, nodes_out, order_out);
-    if (which == 0 && s->device_built && s->wide_built)
+    if (which == 0 && s->facts.device_built && s->facts.wide_built)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_bvh_info: the binary tree of a device-built wide scene is not kept");
-    if (which == 0 && s->wide_built && s->refitted)
+    if (which == 0 && s->facts.wide_built && s->refitted)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_bvh_info: the wide tree was refitted (RT_UPDATE_REFIT): the binary tree it was collapsed from is not kept");
-    if (which == 0 && s->device_built && s->rebuilt_bvh.nodes.empty() && s->dev.scene.n_tris)
+    if (which == 0 && s->facts.device_built && s->rebuilt_bvh.nodes.empty() && s->dev.scene.n_tris)
         if (int rc = reconstruct_host_bvh(s); rc != RT_OK)
             return rc;
-    const rt::HostBvh &b = (which == 0 && s->device_built) ? s->rebuilt_bvh : rt::prepared_host_bvh(s, which);
+    const rt::HostBvh &b = (which == 0 && s->facts.device_built) ? s->rebuilt_bvh : rt::prepared_host_bvh(s, which);
     if (n_nodes)
         *n_nodes = (uint32_t)b.nodes.size();
     if (n_objects)

@@ -84,13 +84,13 @@ static rt::WfHostSync wavefront_host_sync(rt_scene *s) {
 // nodes + triangles: 436 vs 409 Msamples/s without / with; S-10M, 0.7 GB: 196 vs 220; profiles/r03_wide.txt).
 static uint32_t wavefront_sort_mode(const rt_scene *s, const rt_params *p) {
     const size_t bvh_bytes = (size_t)s->dev.scene.n_units * 16u; // the packed wide tree: nodes and triangle records in one blob
-    const bool sort_default = !(s->wide_built && bvh_bytes < ((size_t)128 << 20));
+    const bool sort_default = !(s->facts.wide_built && bvh_bytes < ((size_t)128 << 20));
     return (p->sort_mode == RT_SORT_AUTO ? sort_default : p->sort_mode == RT_SORT_OCTANT_CELL_CONE) ? 1u : 0u;
 }
 
 // lanes served per packet trip below which the per-lane kernel is faster (the wide packet kernel's break-even is lower, profiles/r03_wide.txt)
 static double packet_min_lanes(const rt_scene *s, const rt_params *p) {
-    return p->packet_min_lanes > 0.0f ? (double)p->packet_min_lanes : (s->wide_built ? RT_WIDE_PACKET_MIN_LANES : 33.0);
+    return p->packet_min_lanes > 0.0f ? (double)p->packet_min_lanes : (s->facts.wide_built ? RT_WIDE_PACKET_MIN_LANES : 33.0);
 }
 
 // the pass options of rt_params, checked alike by every entry point that runs wavefront passes (`fn`: its name)
@@ -156,8 +156,8 @@ WfLaunch rt::one_row_launch(const rt_scene *s, const rt_params *p, uint32_t n, u
 #endif
 static hipError_t camera_relative_records(rt_scene *s, WfLaunch &W, const float *cam_pos) {
     const DevBvh &B = s->dev.scene;
-    const uint32_t n_nodes = s->dev_n_inner[0];
-    if (s->wide_built || B.wide || !B.nodes || !B.tris || B.root == RT_NONE || n_nodes == 0 || B.n_tris == 0)
+    const uint32_t n_nodes = s->facts.dev_n_inner[0];
+    if (s->facts.wide_built || B.wide || !B.nodes || !B.tris || B.root == RT_NONE || n_nodes == 0 || B.n_tris == 0)
         return hipSuccess;
     const size_t node_bytes = (size_t)n_nodes * sizeof(DevNode), bytes = node_bytes + (size_t)B.n_tris * sizeof(DevTri);
     if (bytes > RT_REL_MAX_BYTES || bytes > RT_REL_BYTES_PER_PATH * W.n_paths)
@@ -207,7 +207,7 @@ hipError_t rt::launch_pass(rt_scene *s, const rt_params *p, PacketPolicy &pol, W
         pol.key = key;
         pol.off = false;
     }
-    const uint32_t pkt_min_spp = s->wide_built ? 4u : 16u; // measured break-even of the two packet kernels
+    const uint32_t pkt_min_spp = s->facts.wide_built ? 4u : 16u; // measured break-even of the two packet kernels
     W.use_packet = p->packet_mode == RT_PACKET_OFF ? 0u : p->packet_mode == RT_PACKET_ON ? 1u : (W.pass_samples >= pkt_min_spp && !pol.off && kind.auto_packets()) ? 1u : 0u;
     W.rel_nodes = nullptr, W.rel_tris = nullptr;
     if (const float *origin = kind.relative_origin(); W.use_packet && origin)
@@ -400,7 +400,7 @@ int rt::render_image(rt_scene *s, const rt_params *p, const std::vector<WfSensor
     L.stats = counters ? s->d_stats : nullptr;
 
     const bool wavefront = p->rng_mode == RT_RNG_DEVICE && !(p->flags & RT_FLAG_MEGAKERNEL);
-    if (s->wide_built && !wavefront)
+    if (s->facts.wide_built && !wavefront)
         return rt::fail(RT_ERR_UNSUPPORTED, "rt_render: a scene built with RT_BUILD_WIDE renders through the wavefront pipeline only (the megakernel and "
                                             "the reference-RNG parity mode walk the reference's binary tree: create the scene without RT_BUILD_WIDE)");
     if (s->dev.env.texels && !wavefront)

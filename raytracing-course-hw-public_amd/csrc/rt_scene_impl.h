@@ -1,5 +1,5 @@
 // rt_scene_impl.h — what the host files behind include/rt_abi.h share (internal): the definition of rt_scene and the few helpers
-// with more than one user. rt_scene.cpp creates and destroys scenes; rt_render.cpp (rt_render*), rt_rays.cpp (rt_render_rays*), rt_bake.cpp (rt_bake*, rt_lightmap_points),
+// with more than one user. rt_scene_prepare.cpp is the host half of rt_create, rt_scene.cpp its device half with the entry points that create and destroy scenes; rt_render.cpp (rt_render*), rt_rays.cpp (rt_render_rays*), rt_bake.cpp (rt_bake*, rt_lightmap_points),
 // rt_accum_host.cpp and rt_accum_layers.cpp (rt_accum_*, over rt_accum_impl.h) and rt_probe.cpp (probes, BVH dumps) run on them. rt_group.cpp sees rt_scene as an opaque type through
 // rt_group.h. The arrays of a call, on the host or in the caller's HBM, are declared on an rt::CallIo (rt_call_io.h) over the scene's one
 // staging block; its run() and timed_call below are the brackets every entry point queues its work in.
@@ -33,13 +33,32 @@ struct PacketPolicy {
     uint32_t lanes_x100 = 0; // last packet census: lanes served per trip x 100 (rt_stats.packet_lanes_x100)
 };
 
+// How a scene of n triangles created with build_flags gets its scene tree: the one derivation for rt_create and both update entry points.
+struct BuildKind {
+    bool dev_build, wide_build; // rt_bvh_device.hip builds the binary tree / the tree in HBM is the 8-wide one
+    bool device_collapse;       // ... emitted on the device too (scenes of a handful of triangles and RT_BUILD_WIDE_HOST_COLLAPSE collapse on the host)
+    bool host_reads;            // some step reads the five arrays on the host: the reference-topology builds, the host collapse
+};
+inline BuildKind build_kind(uint32_t build_flags, uint32_t n) {
+    const bool dev = n > 0 && (build_flags & RT_BUILD_DEVICE_LBVH), wide = n > 0 && (build_flags & RT_BUILD_WIDE);
+    const bool emitted = dev && wide && !(build_flags & RT_BUILD_WIDE_HOST_COLLAPSE) && n > 8u;
+    return {dev, wide, emitted, !dev || (wide && !emitted)};
+}
+// What the queries report of a build (rt_build_times*, rt_wide_info, the BVH dumps) and the launch policy reads.
+struct BuildFacts {
+    bool device_built = false; // scene BVH built by rt_bvh_device.hip
+    bool wide_built = false;   // RT_BUILD_WIDE: the 8-wide quantised tree (wide_build.cpp); host_bvh[0] is the binary tree it was collapsed from when built on the host
+    uint32_t wide_depth = 0;
+    double wide_ms = 0, wide_cost = 0, build_ms = 0, build_upload_ms = 0;
+    uint32_t dev_n_inner[2] = {0, 0}; // inner nodes of the binary trees in HBM: scene (0 for a wide one), lights
+};
+
 // The host half of rt_create comes in two halves. The GEOMETRY half is everything that follows from the five per-triangle arrays: both
 // trees, the triangle, shading and light records. rt_update_geometry makes a new one; the other half (below) is never copied for that.
 struct PreparedGeometry {
-    bool dev_build = false, wide_build = false;
     HostBvh host_bvh[2];
     FlatBvh flat[2];            // [0] empty when the scene BVH is built on the device or is wide
-    WideBvh wide;               // wide_build && !dev_build
+    WideBvh wide;               // BuildKind: wide_build && !dev_build
     std::vector<DevTri> wide_tris;
     std::vector<DevAttr> attrs; // scene-BVH order (empty when built on the device)
     std::vector<DevLightAux> laux;
@@ -61,7 +80,7 @@ struct PreparedScene {
 };
 
 // What the geometry half leaves on one device (rt_scene.cpp upload_geometry): the buffers it allocated, the two trees as the kernels
-// address them, and the build facts the queries report. The buffers die with the struct unless install_geometry hands them to the scene.
+// address them, and the build facts. The buffers die with the struct unless install_geometry hands them to the scene.
 struct GeometryOnDevice {
     DevArena owned;       // scene tree, triangle records, shading records
     DevArena light_owned; // light tree, its triangle records, DevLightAux
@@ -69,14 +88,11 @@ struct GeometryOnDevice {
     const DevAttr *attrs = nullptr;
     const DevLightAux *light_aux = nullptr;
     float bounds_lo[3] = {0, 0, 0}, bounds_inv[3] = {0, 0, 0};
-    bool device_built = false, wide_built = false;
-    uint32_t wide_depth = 0;
-    double wide_ms = 0, wide_cost = 0, build_ms = 0, build_upload_ms = 0;
-    uint32_t dev_n_inner[2] = {0, 0};
+    BuildFacts facts;
 };
 
 // The wide kernels' exponent arithmetic stays among normal floats while the scene's largest cell exponent (e_base + 15) lies in [-60, 44]
-// (rt_scene.cpp upload_geometry states why): the one test rt_create and rt_update_geometry make on a grid.
+// (rt_scene.cpp pack_wide_tree states why): the one test rt_create and rt_update_geometry make on a grid.
 inline bool wide_grid_in_range(const WideGrid &grid) { return !(grid.e_base + 15 < -60 || grid.e_base + 15 > 44); }
 // one axis of the ray-ordering key's scene box: lower bound and 1 / extent (0 for a flat axis)
 inline void sort_bounds_axis(float lo, float hi, float &bounds_lo, float &bounds_inv) {
@@ -103,13 +119,7 @@ struct rt_scene {
     uint32_t shutter_accums = 0; // ... of which have a shutter (rt_accum_attach_shutter): it moves the geometry, so it must be the only one
     bool refitted = false;     // the wide tree was refitted: the binary tree it was collapsed from no longer describes the scene
     rt::HostBvh rebuilt_bvh;   // device-built scene BVH: the reference-style node list, reconstructed from HBM on demand
-    bool device_built = false; // scene BVH built by rt_bvh_device.hip
-    bool wide_built = false;   // RT_BUILD_WIDE: the scene BVH in HBM is the 8-wide quantised tree (wide_build.cpp); host_bvh[0] is the
-                               // binary tree it was collapsed from when that one was built on the host
-    uint32_t wide_depth = 0;
-    double wide_ms = 0, wide_cost = 0;
-    uint32_t dev_n_inner[2] = {0, 0};
-    double build_ms = 0, build_upload_ms = 0;
+    rt::BuildFacts facts;      // of the trees in HBM (install_geometry; a refit renews dev_n_inner[1])
     double refit_ms = 0, refit_levels_ms = 0; // the last RT_UPDATE_REFIT: refit_wide_device in all, and its top-down level pass (rt_refit_times)
     uint32_t *d_counter = nullptr; // both of `owned`
     DevStats *d_stats = nullptr;
@@ -288,20 +298,29 @@ struct rt_scene {
 };
 
 namespace rt {
-// rt_scene.cpp
-const HostBvh &prepared_host_bvh(const rt_scene *s, int which); // the host-built trees kept by the scene's PreparedGeometry
-// the two halves of the geometry build, host and device, that rt_create and rt_update_geometry (rt_update.cpp) both run
+// the two refusals for the contents of geometry arrays, whoever found the fault: a host loop (check_geometry_contents) or the device scan
+inline int refuse_material(const std::string &fn) { return fail(RT_ERR_INVALID_ARG, fn + ": material id out of range"); }
+inline int refuse_non_finite(const std::string &fn, size_t triangle) {
+    return fail(RT_ERR_INVALID_ARG, fn + ": non-finite vertex position (triangle " + std::to_string(triangle) + ")");
+}
+// rt_scene_prepare.cpp: the host half of the geometry build, which rt_create and rt_update_geometry (rt_update.cpp) both run, and its steps
+// with a second user: the refusals for the arrays' contents (`fn` names the entry point) and the records of a wide tree collapsed on the host
+int check_geometry_contents(const uint32_t *material_ids, const float *positions, uint32_t n, size_t n_materials, const std::string &fn);
 void prepare_geometry(const rt_scene_desc *d, const std::vector<uint8_t> &emissive, float wide_cost_node, float wide_cost_tri, PreparedGeometry &P,
                       bool lights_only = false);
+std::vector<uint8_t> emissive_materials(const std::vector<DevMaterial> &mats); // one byte per material: does it emit?
 void prepare_lights(const float *positions, uint32_t n_total, const std::vector<uint32_t> &lights, const uint32_t *original, PreparedGeometry &P);
+void make_attrs(const rt_scene_desc *d, const std::vector<DevTri> &tris, std::vector<DevAttr> &attrs);
+void make_wide_tris(const rt_scene_desc *d, const WideBvh &wide, std::vector<DevTri> &tris);
+// rt_scene.cpp: the device half
+const HostBvh &prepared_host_bvh(const rt_scene *s, int which); // the host-built trees kept by the scene's PreparedGeometry
 int upload_geometry(rt_scene *s, const rt_scene_desc *d, const PreparedScene &PS, const PreparedGeometry &P, GeometryOnDevice &out,
                     const DeviceArrays *arrays = nullptr);
+int upload_light_tree(const FlatBvh &f, const std::vector<DevLightAux> &laux, DevArena &owned, hipStream_t stream, DevBvh &tree, const DevLightAux *&aux, uint32_t &n_inner);
 void install_geometry(rt_scene *s, GeometryOnDevice &g);
-uint32_t light_lds_inner(const FlatBvh &f); // DevBvh::lds_inner of a light tree
 // rt_update.cpp: the update from device arrays behind rt_update_geometry_device's argument checks, and those of its checks a shutter
 // accumulator (rt_accum_shutter.cpp) makes of its keys at attach
 struct UpdateScan;
-std::vector<uint8_t> emissive_materials(const PreparedScene &P); // one byte per material: does it emit?
 int check_device_pointers(const rt_scene *s, const rt_geometry_update *u);
 int check_device_array(const rt_scene *s, const void *p, size_t bytes, const std::string &fn); // one array of them, named by the caller's `fn`
 int refuse_device_arrays(rt_scene *s, const rt_geometry_update *u, const std::string &fn, UpdateScan *scan);

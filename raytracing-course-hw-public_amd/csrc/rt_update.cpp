@@ -2,29 +2,19 @@
 //
 // Everything that does not follow from the five arrays stays where it is: materials, texture views, the 268 MB texel pool, the tables, the
 // analytic primitives, the camera, the stream, the wavefront workspace. What does follow from them is the geometry half of rt_create
-// (rt_scene.cpp: prepare_geometry on the host, upload_geometry on the device), and the two modes differ in how much of it runs again:
+// (prepare_geometry on the host: rt_scene_prepare.cpp; upload_geometry on the device: rt_scene.cpp), and the two modes differ in how much of it runs again:
 //   RT_UPDATE_REBUILD  all of it, into new buffers beside the live ones; then swap and free. The scene is the one rt_create would build.
 //   RT_UPDATE_REFIT    (RT_BUILD_WIDE) the light half on the host as in REBUILD; the scene tree keeps its topology and is refitted in
 //                      place on the device (rt_wide_refit.hip), the triangle and shading records are rewritten in place.
 // rt_update_geometry_device is the same call for arrays that are in the scene GPU's memory already. What rt_update_geometry does with two host
 // loops (the data-dependent refusals, the pick of the lights) one pass on the device does (rt_update_dev.hip); the device build and the refit
 // read the caller's arrays where they are; only the builds that read the arrays on the host stage a copy and run the host path.
-#include <cmath>
 #include <cstring>
 
 #include "rt_scene_impl.h"
 #include "rt_update_dev.h"
 #include "rt_wide_refit.h"
 #include "wide_grid.h"
-
-std::vector<uint8_t> rt::emissive_materials(const rt::PreparedScene &P) {
-    std::vector<uint8_t> em(P.mats.size());
-    for (size_t i = 0; i < em.size(); ++i) {
-        const float *e = P.mats[i].emission;
-        em[i] = !((e[0] == 0) & (e[1] == 0) & (e[2] == 0));
-    }
-    return em;
-}
 
 namespace {
 
@@ -59,19 +49,13 @@ int check_scene(const rt_scene *s, const rt_geometry_update *u, const std::strin
                                                 " live accumulator(s), whose sums are of the old geometry: destroy them first");
     return RT_OK;
 }
-// ... of the arrays' contents: the host loops here, k_update_scan's findings for device arrays (the same two refusals in the same order)
-int refuse_material(const std::string &fn) { return rt::fail(RT_ERR_INVALID_ARG, fn + ": material id out of range"); }
-int refuse_non_finite(const std::string &fn, size_t triangle) {
-    return rt::fail(RT_ERR_INVALID_ARG, fn + ": non-finite vertex position (triangle " + std::to_string(triangle) + ")");
-}
-int check_data(const rt_scene *s, const rt_geometry_update *u, const std::string &fn) {
-    const size_t n_mats = s->prep->mats.size();
-    for (uint32_t i = 0; i < u->n_triangles; ++i)
-        if (u->material_ids[i] >= n_mats)
-            return refuse_material(fn);
-    for (size_t i = 0; i < (size_t)u->n_triangles * 9; ++i) // as rt_create: no builder has an answer for NaN or infinity
-        if (!std::isfinite(u->positions[i]))
-            return refuse_non_finite(fn, i / 9);
+// ... of the arrays' contents: rt_create's host loops (rt::check_geometry_contents) for host arrays, k_update_scan's findings for device arrays:
+// the same two refusals in the same order
+int refuse_scan_findings(const rt::UpdateScan &scan, const std::string &fn) {
+    if (scan.bad_material)
+        return rt::refuse_material(fn);
+    if (scan.first_non_finite != RT_NONE)
+        return rt::refuse_non_finite(fn, scan.first_non_finite);
     return RT_OK;
 }
 // ... and of the mode against the scene
@@ -101,8 +85,6 @@ rt_scene_desc geometry_desc(const rt_scene *s, const rt_geometry_update *u) {
     return d;
 }
 
-using rt::emissive_materials;
-
 // The new buffers from a prepared geometry half, beside the live ones; then swap and free. `arrays`: see rt::upload_geometry.
 int rebuild_from(rt_scene *s, const rt_scene_desc &d, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::DeviceArrays *arrays, const std::string &fn) {
     const rt::PreparedScene &P = *s->prep;
@@ -123,61 +105,22 @@ int rebuild_from(rt_scene *s, const rt_scene_desc &d, const std::shared_ptr<rt::
 int rebuild(rt_scene *s, const rt_scene_desc &d, const std::string &fn) {
     const rt::PreparedScene &P = *s->prep;
     auto G = std::make_shared<rt::PreparedGeometry>();
-    rt::prepare_geometry(&d, emissive_materials(P), P.wide_cost_node, P.wide_cost_tri, *G);
+    rt::prepare_geometry(&d, rt::emissive_materials(P.mats), P.wide_cost_node, P.wide_cost_tri, *G);
     return rebuild_from(s, d, G, nullptr, fn);
 }
 
 // The refit proper, from arrays on the device and the light half prepared on the host: `in` has the five arrays and the bounds of their
 // vertices, `G` the light tree and its records (null: the light tree, its records and s->geo stay as they are; the caller knows that the
 // tree `G` would hold is the live one bit for bit).
-int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::RefitInput &in, const std::string &fn);
-
-int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
-    const rt::PreparedScene &P = *s->prep;
-    if (u->n_triangles == 0)
-        return RT_OK;
-    // ---- host: the light tree and its records, as in REBUILD (the light set follows the new material ids)
-    auto G = std::make_shared<rt::PreparedGeometry>();
-    rt::prepare_geometry(&d, emissive_materials(P), P.wide_cost_node, P.wide_cost_tri, *G, /*lights_only=*/true);
-    // ---- device, part 1: nothing a render kernel reads is written before the update can no longer be refused
-    rt::RefitInput in;
-    const char *what = "";
-    if (hipError_t e = rt::refit_upload(u, s->stream, &in, &what); e != hipSuccess)
-        return rt::hip_fail(e, std::string("rt_update_geometry: ") + what);
-    return refit_from(s, G, in, FN_HOST);
-}
-
 int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, const rt::RefitInput &in, const std::string &fn) {
     DevScene &D = s->dev;
     const char *what = "";
     const WideGrid grid = rt::make_wide_grid(in.lo, in.hi);
     if (D.scene.n_wide != 0u && !rt::wide_grid_in_range(grid))
         return rt::fail(RT_ERR_UNSUPPORTED, fn + ": the new extent is outside the 8-wide tree's exponent range (2^-52 .. 2^52)");
-    rt::GeometryOnDevice lg; // only its light half is filled
-    auto upload_lights = [&]() -> int {
-        auto up = [&](const void *src, size_t bytes, const void **dst) -> int {
-            *dst = nullptr;
-            if (!bytes)
-                return RT_OK;
-            void *p = nullptr;
-            HIP_TRY(lg.light_owned.alloc_bytes(&p, bytes));
-            HIP_TRY(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s->stream));
-            *dst = p;
-            return RT_OK;
-        };
-        const rt::FlatBvh &f = G->flat[1];
-        int rc;
-        if ((rc = up(f.nodes.data(), f.nodes.size() * sizeof(DevNode), (const void **)&lg.lights.nodes)) != RT_OK ||
-            (rc = up(f.tris.data(), f.tris.size() * sizeof(DevTri), (const void **)&lg.lights.tris)) != RT_OK ||
-            (rc = up(G->laux.data(), G->laux.size() * sizeof(DevLightAux), (const void **)&lg.light_aux)) != RT_OK)
-            return rc;
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        return RT_OK;
-    };
-    if (int rc = G ? upload_lights() : RT_OK; rc != RT_OK) {
-        (void)hipStreamSynchronize(s->stream); // before `lg` frees what the copies write
+    rt::GeometryOnDevice lg; // only its light half is filled: the new tree beside the live one (a failure leaves the stream idle before `lg` frees it)
+    if (int rc = G ? rt::upload_light_tree(G->flat[1], G->laux, lg.light_owned, s->stream, lg.lights, lg.light_aux, lg.facts.dev_n_inner[1]) : RT_OK; rc != RT_OK)
         return rc;
-    }
     // ---- device, part 2: records and nodes in place (its scratch is allocated first: RT_ERR_OOM still leaves the scene as it was)
     double levels_ms = 0;
     const auto t_refit = std::chrono::steady_clock::now();
@@ -189,19 +132,9 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
     }
     // ---- host: what the launches read of the tree besides the blob
     if (G) {
-        const rt::FlatBvh &f = G->flat[1];
-        DevBvh &L = D.lights;
-        const DevNode *ln = lg.lights.nodes;
-        const DevTri *lt = lg.lights.tris;
-        L = DevBvh{};
-        L.nodes = ln;
-        L.tris = lt;
-        L.root = f.root;
-        L.n_tris = (uint32_t)f.tris.size();
-        L.fast_ok = f.fast_ok ? 1u : 0u;
-        L.lds_inner = rt::light_lds_inner(f);
+        D.lights = lg.lights;
         D.light_aux = lg.light_aux;
-        s->dev_n_inner[1] = (uint32_t)f.nodes.size();
+        s->facts.dev_n_inner[1] = lg.facts.dev_n_inner[1];
         s->light_owned = std::move(lg.light_owned); // frees the old light buffers
     }
     D.scene.grid = grid;
@@ -214,6 +147,21 @@ int refit_from(rt_scene *s, const std::shared_ptr<rt::PreparedGeometry> &G, cons
     s->refitted = true;
     ++s->geo_generation; // records rewritten in place: nothing derived from the old ones may be used again
     return RT_OK;
+}
+
+int refit(rt_scene *s, const rt_geometry_update *u, const rt_scene_desc &d) {
+    const rt::PreparedScene &P = *s->prep;
+    if (u->n_triangles == 0)
+        return RT_OK;
+    // ---- host: the light tree and its records, as in REBUILD (the light set follows the new material ids)
+    auto G = std::make_shared<rt::PreparedGeometry>();
+    rt::prepare_geometry(&d, rt::emissive_materials(P.mats), P.wide_cost_node, P.wide_cost_tri, *G, /*lights_only=*/true);
+    // ---- device, part 1: nothing a render kernel reads is written before the update can no longer be refused
+    rt::RefitInput in;
+    const char *what = "";
+    if (hipError_t e = rt::refit_upload(u, s->stream, &in, &what); e != hipSuccess)
+        return rt::hip_fail(e, std::string("rt_update_geometry: ") + what);
+    return refit_from(s, G, in, FN_HOST);
 }
 
 // ------------------------------------------------------------------------------------------------ arrays that are on the device already
@@ -243,7 +191,6 @@ int rt::check_device_pointers(const rt_scene *s, const rt_geometry_update *u) {
     return RT_OK;
 }
 namespace {
-using rt::check_device_pointers;
 
 // the light half of a PreparedGeometry from the scan's compacted lights (rt::prepare_lights states why the tree is the host path's)
 int lights_from_scan(const rt::UpdateScan &scan, uint32_t n, rt::PreparedGeometry &G) {
@@ -282,8 +229,8 @@ int rebuild_staged(rt_scene *s, const rt_geometry_update *u) {
 
 extern "C" int rt_update_geometry(rt_scene *s, const rt_geometry_update *u) {
     int rc; // before any HIP call
-    if ((rc = check_struct(u, FN_HOST, false)) != RT_OK || (rc = check_scene(s, u, FN_HOST)) != RT_OK || (rc = check_data(s, u, FN_HOST)) != RT_OK ||
-        (rc = check_mode(s, u, FN_HOST)) != RT_OK)
+    if ((rc = check_struct(u, FN_HOST, false)) != RT_OK || (rc = check_scene(s, u, FN_HOST)) != RT_OK ||
+        (rc = rt::check_geometry_contents(u->material_ids, u->positions, u->n_triangles, s->prep->mats.size(), FN_HOST)) != RT_OK || (rc = check_mode(s, u, FN_HOST)) != RT_OK)
         return rc;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream)); // (every entry point leaves it idle: this costs nothing and says so)
@@ -311,7 +258,7 @@ extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *
     if ((rc = check_struct(u, FN_DEVICE, true)) != RT_OK || (rc = check_scene(s, u, FN_DEVICE)) != RT_OK)
         return rc;
     HIP_TRY(hipSetDevice(s->device));
-    if (u->n_triangles && (rc = check_device_pointers(s, u)) != RT_OK) // before any launch
+    if (u->n_triangles && (rc = rt::check_device_pointers(s, u)) != RT_OK) // before any launch
         return rc;
     return rt::update_from_device_arrays(s, u, false);
 }
@@ -322,12 +269,10 @@ extern "C" int rt_update_geometry_device(rt_scene *s, const rt_geometry_update *
 int rt::refuse_device_arrays(rt_scene *s, const rt_geometry_update *u, const std::string &fn, rt::UpdateScan *scan) {
     const char *what = "";
     const rt::DeviceArrays arrays{u->positions, u->normals, u->texcoords, u->tangents, u->material_ids, u->n_triangles};
-    if (hipError_t e = rt::scan_update_device(arrays, emissive_materials(*s->prep), false, s->stream, scan, &what); e != hipSuccess)
+    if (hipError_t e = rt::scan_update_device(arrays, rt::emissive_materials(s->prep->mats), false, s->stream, scan, &what); e != hipSuccess)
         return rt::hip_fail(e, fn + ": " + what);
-    if (scan->bad_material)
-        return refuse_material(fn);
-    if (scan->first_non_finite != RT_NONE)
-        return refuse_non_finite(fn, scan->first_non_finite);
+    if (int rc = refuse_scan_findings(*scan, fn); rc != RT_OK)
+        return rc;
     if (int rc = check_mode(s, u, fn); rc != RT_OK)
         return rc;
     if (u->n_triangles && s->dev.scene.n_wide != 0u && !rt::wide_grid_in_range(rt::make_wide_grid(scan->lo, scan->hi)))
@@ -344,9 +289,7 @@ int rt::refuse_non_finite_positions(rt_scene *s, const float *d_positions, uint3
     rt::UpdateScan scan;
     if (hipError_t e = rt::scan_update_device(arrays, {}, false, s->stream, &scan, &what); e != hipSuccess)
         return rt::hip_fail(e, fn + ": " + what);
-    if (scan.first_non_finite != RT_NONE)
-        return refuse_non_finite(fn, scan.first_non_finite);
-    return RT_OK;
+    return refuse_scan_findings(scan, fn); // (no ids were scanned: bad_material is unset)
 }
 
 // rt_update_geometry_device behind its argument checks: `u` names device arrays of the scene's GPU and of the scene's triangle count, in a
@@ -358,10 +301,9 @@ int rt::update_from_device_arrays(rt_scene *s, const rt_geometry_update *u, bool
     const uint32_t n = u->n_triangles;
     HIP_TRY(hipStreamSynchronize(s->stream));
     const rt::PreparedScene &P = *s->prep;
-    const bool dev_build = n > 0 && (P.build_flags & RT_BUILD_DEVICE_LBVH), wide_build = n > 0 && (P.build_flags & RT_BUILD_WIDE); // as prepare_geometry
+    const rt::BuildKind kind = rt::build_kind(P.build_flags, n);
     const bool refit = u->mode == RT_UPDATE_REFIT;
-    // a rebuild that reads the arrays on the host: the reference-topology builds, and the host collapse of a device-built binary tree
-    const bool staged = !refit && (!dev_build || (wide_build && ((P.build_flags & RT_BUILD_WIDE_HOST_COLLAPSE) || n <= 8u)));
+    const bool staged = !refit && kind.host_reads; // a rebuild that reads the arrays on the host
     rt::DeviceArrays arrays;
     arrays.pos = u->positions, arrays.nrm = u->normals, arrays.uv = u->texcoords, arrays.tan = u->tangents, arrays.mat = u->material_ids, arrays.n = n;
     // ---- one pass over positions and ids: the two data-dependent refusals, the bounds, the lights (writes only its own scratch)
@@ -369,13 +311,9 @@ int rt::update_from_device_arrays(rt_scene *s, const rt_geometry_update *u, bool
     const char *what = "";
     keep_lights = keep_lights && refit && !staged;
     const bool want_lights = !staged && !keep_lights && check_mode_ok(s, u); // (a call check_mode is about to refuse needs no light list)
-    if (hipError_t e = rt::scan_update_device(arrays, emissive_materials(P), want_lights, s->stream, &scan, &what); e != hipSuccess)
+    if (hipError_t e = rt::scan_update_device(arrays, rt::emissive_materials(P.mats), want_lights, s->stream, &scan, &what); e != hipSuccess)
         return rt::hip_fail(e, FN_DEVICE + ": " + what);
-    if (scan.bad_material)
-        return refuse_material(FN_DEVICE);
-    if (scan.first_non_finite != RT_NONE)
-        return refuse_non_finite(FN_DEVICE, scan.first_non_finite);
-    if ((rc = check_mode(s, u, FN_DEVICE)) != RT_OK)
+    if ((rc = refuse_scan_findings(scan, FN_DEVICE)) != RT_OK || (rc = check_mode(s, u, FN_DEVICE)) != RT_OK)
         return rc;
     if (staged)
         rc = rebuild_staged(s, u);
@@ -385,7 +323,6 @@ int rt::update_from_device_arrays(rt_scene *s, const rt_geometry_update *u, bool
         std::shared_ptr<rt::PreparedGeometry> G;
         if (!keep_lights) {
             G = std::make_shared<rt::PreparedGeometry>();
-            G->dev_build = dev_build, G->wide_build = wide_build; // as prepare_geometry sets them
             if ((rc = lights_from_scan(scan, n, *G)) != RT_OK)
                 return rc;
         }
