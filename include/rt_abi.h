@@ -349,9 +349,28 @@ int rt_bvh_info(rt_scene *scene, int which, uint32_t *n_nodes, uint32_t *n_objec
 
 /* The BVH exactly as the traversal kernels see it, copied back from HBM (tests: validates what rt_create uploaded or built
  * on the device, not a host copy). nodes64: n_inner records of 16 words {lmin.xyz, lmax.xyz, rmin.xyz, rmax.xyz, left,
- * right, pad, pad}; a child ref is an inner index, or 0x80000000 | count << 27 | first triangle for a leaf. tris48: n_tris
+ * right, sel, pad}; a child ref is an inner index, or 0x80000000 | count << 27 | first triangle for a leaf. tris48: n_tris
  * records of 12 words {a.xyz, (b-a).xyz, (c-a).xyz, original triangle index, flags, pad}. Pass NULL buffers for the counts. */
 int rt_bvh_device_dump(rt_scene *scene, int which, uint32_t *n_inner, uint32_t *n_tris, uint32_t *root, uint32_t *nodes64, uint32_t *tris48);
+/* The compact node records of the binary scene tree (additive, RT_ABI_VERSION stays 4), copied back from HBM: n_inner records of 8 words
+ * {six planes, left, right}, one per record of rt_bvh_device_dump(scene, 0) and in its order. Word 14 (`sel`) of THAT dump's records says how a
+ * node's two children expand: per child (left: bits 0..6, right: bits 8..14) six selector bits and a valid bit. With C a child that has
+ * `valid`, box(C) = its box in the parent's record (faces f = 0..5: min x, y, z, max x, y, z) and p = C's compact planes, C's own record is
+ *   selector bit f clear: left child's face f = box(C)'s, right child's = p[f];      set: left child's = p[f], right child's = box(C)'s
+ * and its child references are the compact record's, bit for bit. valid = 0: a leaf child, or a child some face of which does not follow
+ * the rule; its compact record is zero. A NULL buffer: the count. RT_ERR_UNSUPPORTED for RT_BUILD_WIDE and multi-GPU scenes. */
+int rt_bvh_compact_dump(rt_scene *scene, uint32_t *n_inner, uint32_t *compact32);
+/* The same derivation on host arrays, by the code the device runs (no GPU needed): nodes64 = n_inner records of 16 words as
+ * rt_bvh_device_dump returns them, whose `sel` words (word 14) are overwritten; compact32 = n_inner records of 8 words, written. */
+int rt_compact_derive_host(uint32_t *nodes64, uint32_t n_inner, uint32_t *compact32);
+/* PROBE, for tests only, like the dumps above (nothing a renderer calls; it may change without an ABI bump): overwrite plane `word` (0..11)
+ * of record `node` of the binary scene tree in HBM, then derive the compact records and selector words again, as every build does. A plane
+ * moved outwards leaves a correct, looser tree whose affected child loses `valid`: the one way to show the kernels a record that does not
+ * follow the inheritance rule, which no builder makes. Blocking. */
+int rt_bvh_patch_plane(rt_scene *scene, uint32_t node, uint32_t word, float value);
+/* Of rt_stats::nodes_visited of the last call with counters on this scene: the inner-node visits the per-lane closest-hit kernel made from a
+ * compact record (the second visit of a trip). 0 for multi-GPU scenes. */
+int rt_second_visits(const rt_scene *scene, uint64_t *count);
 /* The 8-wide scene BVH of a scene built with RT_BUILD_WIDE, copied back from HBM: nodes80 = n_nodes records of 20 words
  * (layout: WideNode, csrc/rt_device_types.h — origin xyz, exponents + inner mask, first inner child, first triangle, triangle
  * mask, pad, then qlo[3][8] and qhi[3][8] bytes); tris48 as in rt_bvh_device_dump, in the wide tree's order. NULL buffers: counts. */

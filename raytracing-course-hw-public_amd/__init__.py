@@ -32,7 +32,7 @@ from ._records import GEOMETRY_ARRAYS, _as_desc, geometry_arrays, pack_bake_poin
 from ._marshal import _apply_tuning
 from ._accumulator import Accumulator
 from ._device_scene import DeviceScene
-from ._host import bvh_build_host, bvh_wide_build_host, bvh_wide_refit_host, film_table, image_decode, load_hdr, png_decode, tonemap, write_flo, write_ppm
+from ._host import bvh_build_host, bvh_wide_build_host, compact_derive_host, bvh_wide_refit_host, film_table, image_decode, load_hdr, png_decode, tonemap, write_flo, write_ppm
 
 
 def __getattr__(name):

@@ -396,6 +396,10 @@ ABI_PROTOTYPES = {
     "rt_create_on": (C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "rt_scene_device_count": (C.c_int, [C.c_void_p]),
     "rt_bvh_device_dump": (C.c_int, [C.c_void_p, C.c_int, c_u32_p, c_u32_p, c_u32_p, c_u32_p, c_u32_p]),
+    "rt_bvh_compact_dump": (C.c_int, [C.c_void_p, c_u32_p, c_u32_p]),
+    "rt_compact_derive_host": (C.c_int, [c_u32_p, C.c_uint32, c_u32_p]),
+    "rt_bvh_patch_plane": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float]),
+    "rt_second_visits": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_build_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_build_times_ex": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }

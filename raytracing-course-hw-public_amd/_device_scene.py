@@ -421,6 +421,24 @@ class DeviceScene:
         root, nodes, tris = _dump(lambda *a: lib().rt_bvh_device_dump(self._h, which, *a), (16,), (12,))
         return {"root": root, "nodes": nodes, "tris": tris}
 
+    def bvh_compact_dump(self) -> np.ndarray:
+        """The compact node records of the binary scene tree read back from HBM: (n_inner, 8) u32, in bvh_device_dump(0)'s node order."""
+        n = C.c_uint32()
+        _check(lib().rt_bvh_compact_dump(self._h, C.byref(n), None))
+        out = np.zeros((n.value, 8), dtype=np.uint32)
+        _check(lib().rt_bvh_compact_dump(self._h, C.byref(n), u32ptr(out)))
+        return out
+
+    def bvh_patch_plane(self, node: int, word: int, value: float) -> None:
+        """rt_bvh_patch_plane (test aid): one plane of one node record in HBM, then the compact records derived again."""
+        _check(lib().rt_bvh_patch_plane(self._h, node, word, float(value)))
+
+    def second_visits(self) -> int:
+        """rt_second_visits: inner-node visits of the last counted call that ran from a compact record."""
+        n = C.c_uint64()
+        _check(lib().rt_second_visits(self._h, C.byref(n)))
+        return n.value
+
     def bvh_wide_dump(self):
         """The 8-wide scene BVH read back from HBM: {depth, nodes (n,20) u32 (WideNode records), tris (n_tris,12) u32}."""
         depth, nodes, tris = _dump(lambda *a: lib().rt_bvh_wide_dump(self._h, *a), (20,), (12,))

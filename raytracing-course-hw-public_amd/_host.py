@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -39,6 +39,15 @@ def bvh_build_host(positions: np.ndarray, subset: Optional[np.ndarray] = None) -
     rc = lib().rt_bvh_build_host(fptr(pos), n, u32ptr(sub), len(sub), C.byref(nn), C.byref(root), u32ptr(nodes), u32ptr(order))
     _ok(rc, "rt_bvh_build_host")
     return {"root": root.value, "nodes": nodes[: nn.value].copy(), "order": order}
+
+
+def compact_derive_host(nodes: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_compact_derive_host, no GPU needed: the compact records and selector words of DevNode records (n, 16) u32 (DeviceScene.bvh_device_dump,
+    or a tree flattened on the host), by the code the device runs. Returns (a copy of the records with word 14 set, compact records (n, 8) u32)."""
+    nodes = np.array(nodes, dtype=np.uint32).reshape(-1, 16)
+    compact = np.zeros((nodes.shape[0], 8), dtype=np.uint32)
+    _ok(lib().rt_compact_derive_host(u32ptr(nodes), nodes.shape[0], u32ptr(compact)), "rt_compact_derive_host")
+    return nodes, compact
 
 
 def bvh_wide_build_host(positions: np.ndarray, cost_node: float = 1.0, cost_tri: float = 0.3) -> dict:

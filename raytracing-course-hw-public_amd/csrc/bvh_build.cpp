@@ -299,7 +299,7 @@ FlatBvh flatten_bvh(const HostBvh &bvh, const float *positions) {
         std::memcpy(d.rmax, r.hi, 12);
         d.left = ref_of(nd.left);
         d.right = ref_of(nd.right);
-        d.pad[0] = d.pad[1] = 0;
+        d.sel = d.pad = 0;
         for (const float *bx : {d.lmin, d.lmax, d.rmin, d.rmax})
             for (int c = 0; c < 3; ++c) {
                 const float m = std::fabs(bx[c]);

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_radix_tree(const BuildArrays A) {
             nd.right = (uint32_t)(gamma + 1);
             A.node_parent[gamma + 1] = (uint32_t)i;
         }
-        nd.pad[0] = nd.pad[1] = 0;
+        nd.sel = nd.pad = 0;
         if (i == 0)
             A.node_parent[0] = RT_NONE;
     }

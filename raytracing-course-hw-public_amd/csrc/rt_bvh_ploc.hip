@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void k_ploc_merge(const Ploc P, const BuildArr
     }
     nd.left = lref;
     nd.right = rref;
-    nd.pad[0] = nd.pad[1] = 0;
+    nd.sel = nd.pad = 0;
     const uint32_t dl = (lref & RT_LEAF_FLAG) ? 0u : P.depth[lref], dr = (rref & RT_LEAF_FLAG) ? 0u : P.depth[rref];
     const uint32_t d = 1u + (dl > dr ? dl : dr);
     P.depth[node] = d;

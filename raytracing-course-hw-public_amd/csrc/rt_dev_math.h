@@ -106,11 +106,12 @@ template <> struct LaneStats<false> {
     DEV void lhit() {}
     DEV void texels(uint32_t) {}
     DEV void sample() {}
+    DEV void second() {}
     DEV void flush(DevStats *) {}
 };
 template <> struct LaneStats<true> {
     unsigned long long c_cast = 0, c_node = 0, c_box = 0, c_tri = 0, c_shaded = 0, c_lq = 0, c_lnode = 0, c_lbox = 0, c_ltri = 0, c_lhit = 0,
-                       c_tex = 0, c_sample = 0;
+                       c_tex = 0, c_sample = 0, c_second = 0;
     DEV void cast() { ++c_cast; }
     DEV void node() { ++c_node; }
     DEV void box(uint32_t n) { c_box += n; }
@@ -123,6 +124,7 @@ template <> struct LaneStats<true> {
     DEV void lhit() { ++c_lhit; }
     DEV void texels(uint32_t n) { c_tex += n; }
     DEV void sample() { ++c_sample; }
+    DEV void second() { ++c_second; }
     DEV void flush(DevStats *s) {
         if (!s)
             return;
@@ -138,6 +140,8 @@ template <> struct LaneStats<true> {
         atomicAdd(&s->lhits, c_lhit);
         atomicAdd(&s->texels, c_tex);
         atomicAdd(&s->samples, c_sample);
+        if (c_second)
+            atomicAdd(&s->second_visits, c_second);
     }
 };
 

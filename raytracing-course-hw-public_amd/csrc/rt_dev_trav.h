@@ -73,7 +73,7 @@ DEV bool box_hit_fast_rel(V3 a1, V3 a2, V3 d, V3 r, float min_dst, float &dist) 
 
 // The two BVH records as the kernels hold them: built ONCE from the record's 16-byte pieces, whichever way those were loaded (float4: a vector
 // load per lane; F4v: one scalar load for the wave, rt_dev_math.h as_const_f4).
-//   DevNode = lmin.xyz lmax.xyz rmin.xyz rmax.xyz left right - -        DevTri = a.xyz v.xyz u.xyz prim flags index
+//   DevNode = lmin.xyz lmax.xyz rmin.xyz rmax.xyz left right sel -      DevTri = a.xyz v.xyz u.xyz prim flags index
 struct NodeRec {
     V3 lmin, lmax, rmn, rmx;
     uint32_t left, right;
@@ -326,12 +326,42 @@ template <bool STATS, class STK> DEV void trav_step(Trav &T, const DevBvh &bvh, 
     trav_step_core<STATS, false>(T, bvh, stk, min_dst, st);
     trav_pop(T, stk);
 }
+// A compact record (DevNodeCompact, rt_device_types.h) expanded with the node's own box {bmin, bmax} and its six selector bits: the record
+// node_rec makes of the node's DevNode, bit for bit, when the parent says `valid` (wf_derive_compact compared all twelve planes).
+DEV NodeRec node_rec_compact(const float4 &c0, const float4 &c1, V3 bmin, V3 bmax, uint32_t sel) {
+    const bool s0 = sel & 1u, s1 = sel & 2u, s2 = sel & 4u, s3 = sel & 8u, s4 = sel & 16u, s5 = sel & 32u;
+    return NodeRec{mk(s0 ? c0.x : bmin.x, s1 ? c0.y : bmin.y, s2 ? c0.z : bmin.z), mk(s3 ? c0.w : bmax.x, s4 ? c1.x : bmax.y, s5 ? c1.y : bmax.z),
+                   mk(s0 ? bmin.x : c0.x, s1 ? bmin.y : c0.y, s2 ? bmin.z : c0.z), mk(s3 ? bmax.x : c0.w, s4 ? bmax.y : c1.x, s5 ? bmax.z : c1.y),
+                   __float_as_uint(c1.z), __float_as_uint(c1.w)};
+}
 // The node step for lanes the caller knows to be on an inner node with T.fast (wf_extend's hot loop): load, then apply without the guard.
+// Two visits per trip where the tree has compact records (DevBvh::compact): a lane that steps straight into an inner child (the near child
+// of a double hit or the only child hit; not a pop) holds that child's box in the record it has just read, and visits the child at once
+// from its 32-byte compact record: 2 vector-L1 accesses instead of 4. Nothing of the box outlives the call: the next trip starts on T.cur
+// with a DevNode. The lanes visit the same nodes in the same order, two to a trip: hits, frames and counters are unchanged.
 template <bool STATS, bool GB = false, class STK> DEV void trav_step_inner_fast(Trav &T, const DevBvh &bvh, STK &stk, float min_dst, LaneStats<STATS> &st) {
+    typedef float f3v __attribute__((ext_vector_type(3)));
     const float4 *p = reinterpret_cast<const float4 *>(bvh.nodes + T.cur);
     const float4 r0 = p[0], r1 = p[1], r2 = p[2];
-    const float2 r3 = *reinterpret_cast<const float2 *>(p + 3);
-    trav_inner_apply<STATS, GB, true>(T, stk, node_rec(r0, r1, r2, r3), min_dst, st);
+    const f3v r3 = *reinterpret_cast<const f3v *>(p + 3); // left right sel
+    const NodeRec n = node_rec(r0, r1, r2, r3);
+    trav_inner_apply<STATS, GB, true>(T, stk, n, min_dst, st);
+    if (bvh.compact == nullptr) // wave-uniform
+        return;
+    const bool went_left = T.cur == n.left; // else n.right or T_POP
+    const uint32_t sel = __float_as_uint(r3.z) >> (went_left ? 0u : RT_SEL_RIGHT_SHIFT);
+    const bool second = ((T.cur & RT_LEAF_FLAG) == 0u) & ((sel & RT_SEL_VALID) != 0u); // (T_POP has the leaf bit)
+    if (__ballot(second) == 0ull)
+        return;
+    if (second) {
+        V3 bmin = went_left ? n.lmin : n.rmn, bmax = went_left ? n.lmax : n.rmx;
+        // the parent's other ten planes die here, before the compact record arrives (the scheduler would hoist its loads above the selects)
+        asm volatile("" : "+v"(bmin.x), "+v"(bmin.y), "+v"(bmin.z), "+v"(bmax.x), "+v"(bmax.y), "+v"(bmax.z)::"memory");
+        const float4 *c = reinterpret_cast<const float4 *>(bvh.compact + T.cur);
+        const float4 c0 = c[0], c1 = c[1];
+        st.second();
+        trav_inner_apply<STATS, GB, true>(T, stk, node_rec_compact(c0, c1, bmin, bmax, sel), min_dst, st);
+    }
 }
 // one unwind step for every lane in T_POP, as straight-line wave code (lanes in other states pass through unchanged)
 template <bool GB = false, class STK> DEV void trav_pop_once(Trav &T, STK &stk) {

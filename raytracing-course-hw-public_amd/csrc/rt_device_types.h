@@ -32,9 +32,69 @@ struct alignas(16) DevNode {
     float lmin[3], lmax[3]; // bounding box of the left child (bvh.h:208)
     float rmin[3], rmax[3]; // bounding box of the right child (bvh.h:212)
     uint32_t left, right;   // inner: index into DevNode[]; leaf: RT_LEAF_FLAG | first DevTri index
-    uint32_t pad[2];
+    uint32_t sel;           // how each child's own two child boxes follow from its compact record (below); 0 from the builders, set by wf_derive_compact
+    uint32_t pad;
 };
 static_assert(sizeof(DevNode) == 64, "DevNode must be 64 bytes");
+
+// The compact record of an inner node C (one per DevNode, same index): what is left of C's DevNode once the box of C itself is known. A builder
+// makes a node's box the exact min / max of its children's boxes, so on each of the six faces (min x, y, z, max x, y, z) one of C's two child
+// boxes has the plane of C's box, bit for bit. The record holds the OTHER child's plane of each face and C's child references; six selector
+// bits in the PARENT's DevNode::sel say which child owns the stored plane: bit f clear: the left child has the box's plane and p[f] is the
+// right child's; set: the other way round. A lane that has just read C's box out of the parent's DevNode visits C from these 32 bytes
+// (2 vector-L1 accesses instead of 4; rt_dev_trav.h trav_step_inner_fast). DevNode::sel: bits 0..5 selectors and bit 6 `valid` of the left
+// child, bits 8..13 and bit 14 of the right child. valid = 0: the child is a leaf, or some face of its record does not follow the rule
+// (wf_derive_compact compares every face, it assumes nothing about the builder): that child is visited from its DevNode as before.
+struct alignas(16) DevNodeCompact {
+    float p[6];
+    uint32_t left, right;
+};
+static_assert(sizeof(DevNodeCompact) == 32, "DevNodeCompact must be 32 bytes");
+#define RT_SEL_VALID 0x40u
+#define RT_SEL_RIGHT_SHIFT 8u
+// The derivation, for node i of `nodes` (records of 16 words, DevNode) with `compact` (records of 8 words) beside it: the one statement of
+// the rule, run by one lane per node on the device (rt_wf_extend.hip wf_derive_compact) and by a loop on the host (rt_compact_derive_host).
+// It compares, face by face and bit by bit, the box of each INNER child C that node i holds with the two child boxes in C's own record. A
+// face on which neither of C's children has the box's plane (a box looser than the union of its children, whoever made it) leaves C without
+// `valid`. Node i's turn writes its own `sel` word and the compact records of its children (each node has one parent); it reads words
+// 0..13 of its children, which no turn writes. The root has no parent and no use for a compact record: its slot, like those of children
+// without `valid`, is not written (the callers zero the array first).
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline void compact_derive_node(uint32_t *nodes, uint32_t n_nodes, uint32_t i, uint32_t *compact) {
+    const uint32_t *box = nodes + 16ull * i; // lmin lmax rmin rmax left right
+    uint32_t sel = 0u;
+    for (int side = 0; side < 2; ++side) {
+        const uint32_t c = box[12 + side];
+        if ((c & RT_LEAF_FLAG) != 0u || c >= n_nodes)
+            continue;
+        const uint32_t *cl = nodes + 16ull * c, *cr = cl + 6;
+        uint32_t bits = 0u, out[6];
+        bool ok = true;
+        for (int f = 0; f < 6; ++f) {
+            const uint32_t b = box[6 * side + f];
+            if (cl[f] == b) { // C's left child has the plane of C's box: keep the right child's
+                out[f] = cr[f];
+            } else if (cr[f] == b) {
+                out[f] = cl[f];
+                bits |= 1u << f;
+            } else {
+                out[f] = 0u;
+                ok = false;
+            }
+        }
+        if (!ok)
+            continue;
+        uint32_t *w = compact + 8ull * c;
+        for (int f = 0; f < 6; ++f)
+            w[f] = out[f];
+        w[6] = cl[12];
+        w[7] = cl[13];
+        sel |= (bits | RT_SEL_VALID) << (side ? RT_SEL_RIGHT_SHIFT : 0u);
+    }
+    nodes[16ull * i + 14] = sel;
+}
 
 struct alignas(16) DevTri {
     float a[3];
@@ -146,6 +206,7 @@ struct WideGrid {
 
 struct DevBvh {
     const DevNode *nodes;
+    const DevNodeCompact *compact; // scene BVH, binary tree only: one record per DevNode (above); null: every visit reads the DevNode
     const DevTri *tris;
     uint32_t root;   // RT_NONE (no objects at all), inner index, or RT_LEAF_FLAG|0
     uint32_t n_tris; // BVH::objects.size()
@@ -193,6 +254,7 @@ struct DevScene {
 
 struct DevStats { // device-side counters, see rt_stats in include/rt_abi.h
     unsigned long long samples, casts, nodes, box_tests, tri_tests, shaded, lq, lnodes, lbox, ltri, lhits, texels;
+    unsigned long long second_visits; // of `nodes`: inner-node visits wf_extend made from a compact record (rt_second_visits)
 };
 
 // ---- wavefront pipeline (rt_wavefront.hip, rt_wf_extend.hip, rt_wf_shade.hip): path = one (pixel, sample); queues hold live paths between bounces

@@ -155,6 +155,9 @@ hipError_t launch_wavefront_cast(const DevScene &S, WfLaunch L, const float *ray
 // The camera-relative copy of a binary scene tree's records (WfLaunch::rel_nodes / rel_tris) for the camera position o[3]: one kernel on
 // `stream`; `rel_nodes` has room for n_nodes records, `rel_tris` for bvh.n_tris.
 hipError_t launch_camera_relative(const DevBvh &bvh, uint32_t n_nodes, const float *o, DevNode *rel_nodes, DevTri *rel_tris, int num_cus, hipStream_t stream);
+// The compact records of a binary scene tree (DevBvh::compact) and the selector / valid bits in its DevNode::sel words, from the `n_nodes`
+// final DevNode records: a memset and one kernel on `stream`; `compact` has room for n_nodes records.
+hipError_t launch_derive_compact(DevNode *nodes, uint32_t n_nodes, DevNodeCompact *compact, int num_cus, hipStream_t stream);
 // the closest-hit kernel of one bounce over the queue of `L`, on the grid the overflow workspace is sized for (L.stack_stride / 256 blocks):
 // wf_extend, or wf_extend_packet for `packet` (coherent primary rays); the 8-wide tree's kernels for a scene that has one (below)
 hipError_t launch_extend(const DevScene &S, const WfLaunch &L, bool packet, bool stats, hipStream_t stream);

@@ -89,6 +89,7 @@ extern "C" int rt_cast_rays_ex(rt_scene *s, const float *rays, uint32_t n, uint3
         DevStats h{};
         HIP_TRY(hipMemcpy(&h, s->d_stats, sizeof(h), hipMemcpyDeviceToHost)); // the stream is idle: as fill_stats reads them
         rt::traversal_stats(h, stats);
+        s->second_visits = h.second_visits;
         stats->casts = n;
         float ms = 0;
         if (hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess)
@@ -188,6 +189,64 @@ extern "C" int rt_bvh_device_dump(rt_scene *s, int which, uint32_t *n_inner, uin
         HIP_TRY(hipMemcpy(nodes64, b.nodes, sizeof(DevNode) * (size_t)s->facts.dev_n_inner[which], hipMemcpyDeviceToHost));
     if (tris48 && b.n_tris)
         HIP_TRY(hipMemcpy(tris48, b.tris, sizeof(DevTri) * (size_t)b.n_tris, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+static int check_compact_scene(const rt_scene *s, const char *fn) {
+    if (!s)
+        return rt::fail(RT_ERR_INVALID_ARG, std::string(fn) + ": null argument");
+    if (s->group)
+        return rt::fail(RT_ERR_UNSUPPORTED, std::string(fn) + ": a probe of one GPU's tree");
+    if (s->facts.wide_built)
+        return rt::fail(RT_ERR_UNSUPPORTED, std::string(fn) + ": the scene BVH is the 8-wide tree (RT_BUILD_WIDE), which has no compact records");
+    return RT_OK;
+}
+
+extern "C" int rt_bvh_compact_dump(rt_scene *s, uint32_t *n_inner, uint32_t *compact32) {
+    if (int rc = check_compact_scene(s, "rt_bvh_compact_dump"); rc != RT_OK)
+        return rc;
+    const uint32_t n = s->dev.scene.compact ? s->facts.dev_n_inner[0] : 0u;
+    if (n_inner)
+        *n_inner = n;
+    HIP_TRY(hipSetDevice(s->device));
+    if (compact32 && n)
+        HIP_TRY(hipMemcpy(compact32, s->dev.scene.compact, sizeof(DevNodeCompact) * (size_t)n, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_bvh_patch_plane(rt_scene *s, uint32_t node, uint32_t word, float value) {
+    if (int rc = check_compact_scene(s, "rt_bvh_patch_plane"); rc != RT_OK)
+        return rc;
+    const uint32_t n = s->facts.dev_n_inner[0];
+    if (node >= n || word >= 12u || !s->dev.scene.compact)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_bvh_patch_plane: no such plane");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    DevNode *nodes = const_cast<DevNode *>(s->dev.scene.nodes);
+    HIP_TRY(hipMemcpy(reinterpret_cast<float *>(nodes + node) + word, &value, sizeof(float), hipMemcpyHostToDevice));
+    if (hipError_t e = rt::launch_derive_compact(nodes, n, const_cast<DevNodeCompact *>(s->dev.scene.compact), s->num_cus, s->stream); e != hipSuccess)
+        return rt::hip_fail(e, "rt_bvh_patch_plane: compact node records");
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    ++s->geo_generation; // a camera-relative copy of the old records is stale
+    s->rebuilt_bvh = rt::HostBvh{};
+    return RT_OK;
+}
+
+extern "C" int rt_compact_derive_host(uint32_t *nodes64, uint32_t n_inner, uint32_t *compact32) {
+    if (n_inner == 0u)
+        return RT_OK;
+    if (!nodes64 || !compact32)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_compact_derive_host: null argument");
+    std::memset(compact32, 0, sizeof(DevNodeCompact) * (size_t)n_inner);
+    for (uint32_t i = 0; i < n_inner; ++i)
+        compact_derive_node(nodes64, n_inner, i, compact32);
+    return RT_OK;
+}
+
+extern "C" int rt_second_visits(const rt_scene *s, uint64_t *count) {
+    if (!s || !count)
+        return rt::fail(RT_ERR_INVALID_ARG, "rt_second_visits: null argument");
+    *count = s->group ? 0u : s->second_visits;
     return RT_OK;
 }
 

@@ -304,6 +304,7 @@ int rt::fill_stats(rt_scene *s, bool counters, uint64_t samples, std::chrono::st
     if (counters)
         HIP_TRY(hipMemcpy(&h, s->d_stats, sizeof(h), hipMemcpyDeviceToHost));
     rt::traversal_stats(h, stats);
+    s->second_visits = h.second_visits;
     stats->samples = counters ? h.samples : samples;
     stats->casts = h.casts;
     stats->shaded_hits = h.shaded;

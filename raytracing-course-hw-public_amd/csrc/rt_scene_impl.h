@@ -123,6 +123,7 @@ struct rt_scene {
     double refit_ms = 0, refit_levels_ms = 0; // the last RT_UPDATE_REFIT: refit_wide_device in all, and its top-down level pass (rt_refit_times)
     uint32_t *d_counter = nullptr; // both of `owned`
     DevStats *d_stats = nullptr;
+    uint64_t second_visits = 0;    // DevStats::second_visits of the last call that counted (rt_second_visits)
     // Buffers grown on demand (rt::DevBuf: the content does not survive growth, a failed growth leaves them empty):
     rt::DevBuf<uint8_t> staging;      // what a call stages of its arrays: host inputs, host or internal outputs (rt_call_io.h), in bytes
     rt::DevBuf<rt::FilmTable> film_table; // the verified threshold table (host/film.cpp), uploaded by the first ensure_film

@@ -299,6 +299,13 @@ __global__ __launch_bounds__(256) void wf_camera_relative(const DevNode *nodes, 
     }
 }
 
+// The compact records of a binary tree (DevNodeCompact) and the selector / valid bits in DevNode::sel, derived from the DevNode array once it
+// is final: one lane per inner node runs compact_derive_node (rt_device_types.h: the rule, and why the lanes do not race).
+__global__ __launch_bounds__(256) void wf_derive_compact(DevNode *nodes, uint32_t n_nodes, DevNodeCompact *compact) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes; i += gridDim.x * blockDim.x)
+        compact_derive_node(reinterpret_cast<uint32_t *>(nodes), n_nodes, i, reinterpret_cast<uint32_t *>(compact));
+}
+
 // ------------------------------------------------------------------------------------------------ extend: analytic primitives
 // Scenes of the scene-txt front end may hold analytic primitives (ELLIPSOID / PLANE, include/rt_primspec.h) next to their
 // triangles. They have no BVH (a plane is unbounded; BASELINE config 2 is "intersect kernel only, no BVH"): every queued
@@ -370,6 +377,14 @@ hipError_t launch_extend_prims(const DevScene &S, const WfLaunch &L, uint32_t bl
 hipError_t launch_camera_relative(const DevBvh &bvh, uint32_t n_nodes, const float *o, DevNode *rel_nodes, DevTri *rel_tris, int num_cus, hipStream_t stream) {
     const uint32_t n = n_nodes + bvh.n_tris;
     return RT_LAUNCH_CHECKED(wf_camera_relative, dim3(wf_grid_stride(n, num_cus, 16u)), dim3(256), 0, stream, bvh.nodes, n_nodes, bvh.tris, bvh.n_tris, V3{o[0], o[1], o[2]}, rel_nodes, rel_tris);
+}
+
+hipError_t launch_derive_compact(DevNode *nodes, uint32_t n_nodes, DevNodeCompact *compact, int num_cus, hipStream_t stream) {
+    if (n_nodes == 0u)
+        return hipSuccess;
+    if (hipError_t e = hipMemsetAsync(compact, 0, sizeof(DevNodeCompact) * (size_t)n_nodes, stream); e != hipSuccess)
+        return e;
+    return RT_LAUNCH_CHECKED(wf_derive_compact, dim3(wf_grid_stride(n_nodes, num_cus, 16u)), dim3(256), 0, stream, nodes, n_nodes, compact);
 }
 
 // ---- closest-hit probe through the production kernels (rt_cast_rays_ex): rays -> queue -> wf_extend / wf_extend_packet -> hits
